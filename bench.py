@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's headline: images/sec for 1920x1080 -> 224x224 bicubic resize.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode cubic|area|chain|lanczos]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode cubic|area|chain|lanczos] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -667,6 +667,26 @@ def jpeg_stage_profile(imp, files, batch, out_quality, reps=6):
     return out
 
 
+DUMP_BYTES = 64 * 10 ** 6   # --dump-outputs: what one run may write in all
+
+
+def dump_outputs(out_dir, frames):
+    """--dump-outputs: the (N, H, W, C) uint8 frames one step left on the device -> out_dir/output.npy (float32) and
+    out_dir/output_frame_index.npy (float64: which of the N frames those are).  When all N would pass DUMP_BYTES, a fixed,
+    seeded sample of whole frames, so that two builds run with the same arguments can be compared output for output."""
+    import numpy as np
+    import torch
+
+    n = frames.shape[0]
+    k = min(n, (DUMP_BYTES - 8 * n) // (frames[0].numel() * 4))
+    assert k >= 1, "one output frame is larger than the --dump-outputs budget"
+    idx = np.arange(n) if k == n else np.sort(np.random.Generator(np.random.PCG64(0x1A4D0D0D)).choice(n, k, replace=False))
+    sample = frames[torch.from_numpy(idx).to(frames.device)].float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "output.npy"), sample)
+    np.save(os.path.join(out_dir, "output_frame_index.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -702,7 +722,14 @@ def main():
     ap.add_argument("--channels", type=int, default=4, choices=(3, 4), help="--mixed / --stream: BGRA (4) or BGR (3, what a JPEG decodes to)")
     ap.add_argument("--e2e", type=int, default=0, metavar="N",
                     help="instead of the headline, time N PCIe-inclusive requests (upload + resize + download) and exit")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the frames the last step computed to DIR/*.npy (float32, a seeded sample "
+                         "when larger than 64 MB); rank 0's frames under torch.distributed")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.workers or args.stream or args.mixed or args.e2e):
+        ap.error("--dump-outputs covers the batch workloads of --mode, not --workers / --stream / --mixed / --e2e")
     global NUMA_BIND
     NUMA_BIND = not args.no_numa
 
@@ -931,6 +958,17 @@ def main():
     # two gloo ranks in tests/test_multirank.py)
     elapsed, (frames_all,) = job_totals(elapsed, [batch * args.steps], dist if use_dist else None, "cuda")
     dev_ms = elapsed_max(dev_ms, dist if use_dist else None, "cuda")
+
+    if args.dump_outputs and rank == 0:
+        if interp in (-2, -3):
+            # the filter modes work in place, so the timed steps filtered the frames as many times as the clock-bound
+            # pre-warm ran: dump what one step makes of the seeded frames instead
+            g.manual_seed(0x1A4D0001 + rank)
+            src = torch.randint(0, 256, (batch, sh, sw, 4), dtype=torch.uint8, device="cuda", generator=g)
+            stream.wait_stream(torch.cuda.current_stream())
+            step()
+            torch.cuda.synchronize()
+        dump_outputs(args.dump_outputs, src if interp in (-2, -3) else dst)
 
     if rank == 0:
         launch_ms = dev_ms / args.steps                  # one kernel launch per step (chain: its launches together)
