@@ -345,6 +345,18 @@ int impgpu_hsv2rgb(impgpu_image* image);
  * Crop is folded into the next operator's source view, consecutive pointwise filters
  * run as one kernel. */
 int impgpu_run_ops(impgpu_image** pointer, const impgpu_job* job, const impgpu_config* config, int* step);
+/* The operator segment of RunJob (impgpu_run_ops) for `count` independent requests at once -- a request queue's worth, each
+ * with its own job and config.  On return images[i], codes[i] and steps[i] are exactly what
+ * impgpu_run_ops(&images[i], &jobs[i], configs[i], &steps[i]) would have left, in request order; the fault points
+ * (impgpu_fault_arm) are entered in the same order as by that loop.  A single BGR / BGRA frame whose chain is
+ * [crop ->] resize (general INTER_AREA) [-> one filter-rotate] [-> a BGRA overlay] [-> flatten] rides ONE launch per channel
+ * count with every other such request, the tail on the resize's stores (bare resizes share the launch of
+ * impgpu_batch_resize_mixed); every other request goes through impgpu_run_ops inside the call.  launches (may be NULL)
+ * receives the number of kernels enqueued.  IMP_ERROR_INVALID_ARGS with nothing enqueued when the arguments are malformed
+ * (NULL arrays, count < 0 or > 4096, the same handle twice); IMP_ERROR_DEVICE without an env (every codes[i] says so too);
+ * otherwise IMP_OK, and the verdicts are in codes[].  Asynchronous on the env stream, like impgpu_run_ops. */
+int impgpu_batch_run_ops(impgpu_image** images, const impgpu_job* jobs, const impgpu_config* const* configs,
+                         int count, int* codes, int* steps, int* launches);
 
 /* ---- argument grammar only (host, no device): what Crop / Resize decide before they
  *      touch pixels.  Used by the module to answer 400/405/413 without a GPU round trip. ---- */

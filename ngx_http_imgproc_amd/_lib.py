@@ -173,6 +173,7 @@ SIGNATURES = {
     "impgpu_rgb2hsv": (C.c_int, [P]),
     "impgpu_hsv2rgb": (C.c_int, [P]),
     "impgpu_run_ops": (C.c_int, [PP, C.POINTER(CJob), C.POINTER(CConfig), IP]),
+    "impgpu_batch_run_ops": (C.c_int, [PP, C.POINTER(CJob), C.POINTER(C.POINTER(CConfig)), C.c_int, IP, IP, IP]),
     "impgpu_crop_geometry": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_char_p, IP, IP, IP, IP]),
     "impgpu_resize_geometry": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.POINTER(CConfig), C.c_int, IP, IP, IP]),
     "impgpu_filter_check": (C.c_int, [C.c_char_p, C.c_int]),

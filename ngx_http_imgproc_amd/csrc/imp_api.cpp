@@ -3,6 +3,7 @@
 // (imp_args.cpp), then enqueues kernels on the env stream.  impgpu_run_ops is the operator
 // segment of RunJob (bridge.c:574-656) with Crop folded into the next operator's source view
 // and runs of pointwise filters fused into one launch.
+#include <algorithm>
 #include <cstddef>
 #include <cstring>
 #include "imp_internal.h"
@@ -121,6 +122,63 @@ int do_watermark(Work& wk, const impgpu_config* cfg) {
     const float alpha = 1 - opacity;                                  // filters.c:620
     return launch_blend_over(wk.px(), wk.stride(), wk.v.w, wk.v.h, wk.v.c, wk.v.step, wk.count(), ov,
                              rx, ry, maxcol, maxrow, alpha, env_stream());
+}
+
+// What impgpu_batch_run_ops needs to know to put a request on the mixed launch instead of impgpu_run_ops: a single colour
+// frame, [crop ->] resize (general INTER_AREA that launch_area_rotate takes) [-> one quarter or half turn] [-> a BGRA overlay
+// watermark_rect places] [-> flatten].  Host-only, no fault point entered: a request this refuses goes to impgpu_run_ops whole.
+struct FusedPlan {
+    View v;                 // the source window (after the crop)
+    int w, h;               // the resized geometry
+    int rot;                // 0 when the request has no filter
+    bool turn;              // its one filter is the turn
+    bool has_wm;
+    OverlayArgs wm;
+    bool flat;
+    int fw, fh;             // the final frame
+};
+
+bool fused_plan(const impgpu_image* im, const impgpu_job* job, const impgpu_config* cfg, FusedPlan* p) {
+    if (!im || !job || !cfg || im->frames != 1 || (im->c != 3 && im->c != 4) || !job->resize) return false;
+    if (cfg->max_filters_count > 0 && job->filter_count > cfg->max_filters_count) return false;
+    if (job->filter_count < 0 || job->filter_count > 1 || (job->filter_count == 1 && (!job->filters || !job->filters[0]))) return false;
+    View v = view_of(im);
+    if (job->crop) {
+        int x, y, w, h;
+        if (crop_geometry(v.w, v.h, job->crop, job->gravity, &x, &y, &w, &h) != IMP_OK) return false;
+        v = view_sub(v, x, y, w, h);
+    }
+    int w, h, interp;
+    if (resize_geometry(v.w, v.h, job->resize, cfg->max_target_w, cfg->max_target_h, job->simple, &w, &h, &interp) != IMP_OK ||
+        interp != IMP_INTER_AREA)
+        return false;
+    p->rot = 0;
+    p->turn = job->filter_count == 1;
+    if (p->turn) {                                                     // impgpu_run_ops' first-filter rule
+        FilterPlan first;
+        PixelProgram none;
+        if (filter_plan(job->filters[0], cfg->allow_experiments, v.c, w, h, &first, &none) != IMP_OK || first.cls != FC_ROTATE) return false;
+        p->rot = first.rotate;
+    }
+    const bool swap = p->rot == 90 || p->rot == 270;
+    p->fw = swap ? h : w;
+    p->fh = swap ? w : h;
+    Frames f{};
+    f.src = v.d; f.v = v; f.dw = w; f.dh = h; f.dstep = aligned_step(p->fw, v.c); f.count = 1;
+    int ww, bh;
+    if (!area_tail_plan(f, &ww, &bh)) return false;
+    p->has_wm = false;
+    p->wm = OverlayArgs{};
+    if (const impgpu_image* ov = cfg->watermark) {                     // the fused lone path's condition (impgpu_run_ops)
+        if (ov->c != 4 || (((uintptr_t)ov->d | (uintptr_t)ov->step) & 3)) return false;
+        if (watermark_rect(p->fw, p->fh, ov->w, ov->h, cfg, &p->wm.rx, &p->wm.ry, &p->wm.maxcol, &p->wm.maxrow) != IMP_OK) return false;
+        p->wm.ov = ov->d; p->wm.ostep = ov->step;
+        p->wm.alpha = 1 - (float)(cfg->watermark_opacity / 100.0);     // bridge.c:275, filters.c:620
+        p->has_wm = true;
+    }
+    p->flat = job->need_flatten && v.c == 4;
+    p->v = v; p->w = w; p->h = h;
+    return true;
 }
 
 }  // namespace
@@ -444,6 +502,89 @@ int impgpu_run_ops(impgpu_image** pointer, const impgpu_job* job, const impgpu_c
 done:
     *pointer = wk.owner;
     return rc;
+}
+
+int impgpu_batch_run_ops(impgpu_image** images, const impgpu_job* jobs, const impgpu_config* const* configs, int count,
+                         int* codes, int* steps, int* launches) {
+    if (launches) *launches = 0;
+    if (count < 0 || count > 4096 || (count > 0 && (!images || !jobs || !configs || !codes || !steps))) return IMP_ERROR_INVALID_ARGS;
+    {
+        std::vector<const impgpu_image*> seen;                          // the same handle twice: one request would free the other's frame
+        seen.reserve((size_t)count);
+        for (int i = 0; i < count; i++) if (images[i]) seen.push_back(images[i]);
+        std::sort(seen.begin(), seen.end());
+        if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return IMP_ERROR_INVALID_ARGS;
+    }
+    if (int rc = need_env()) {
+        for (int i = 0; i < count; i++) { codes[i] = rc; steps[i] = IMP_STEP_START; }
+        return rc;
+    }
+    const unsigned long long launched = t_launches;
+    hipStream_t s = env_stream();
+    // per channel count (index c - 3): requests with a tail -> k_resize_area_mix_tail, bare resizes -> launch_resize_mixed
+    std::vector<TailItem> tails[2];
+    std::vector<MixFrame> bares[2];
+    std::vector<int> tail_who[2], bare_who[2];
+    std::vector<impgpu_image*> outs((size_t)count, nullptr);
+    std::vector<int> final_code((size_t)count, IMP_OK), final_step((size_t)count, IMP_STEP_INFO);
+    for (int i = 0; i < count; i++) {
+        const impgpu_job* job = &jobs[i];
+        const impgpu_config* cfg = configs[i];
+        FusedPlan p;
+        if (!fused_plan(images[i], job, cfg, &p)) {
+            codes[i] = impgpu_run_ops(&images[i], job, cfg, &steps[i]);
+            continue;
+        }
+        // the fault points impgpu_run_ops enters for this chain, in its order (bridge.c:574-640)
+        codes[i] = IMP_ERROR_DEVICE;
+        steps[i] = IMP_STEP_CROP;
+        if (job->crop && fault_hit(IMP_STEP_CROP)) continue;
+        steps[i] = IMP_STEP_RESIZE;
+        if (fault_hit(IMP_STEP_RESIZE)) continue;
+        bool has_wm = p.has_wm, flat = p.flat;
+        int failed = -1;
+        if (job->filter_count > 0 && fault_hit(IMP_STEP_FILTERING)) failed = IMP_STEP_FILTERING;
+        else if (cfg->watermark && fault_hit(IMP_STEP_WATERMARK)) failed = IMP_STEP_WATERMARK;
+        if (failed >= 0) {
+            // impgpu_run_ops fails behind its resize: the frame it leaves is resized -- and turned, with the overlay its turning
+            // launch carried -- and never flattened
+            final_code[(size_t)i] = IMP_ERROR_DEVICE;
+            final_step[(size_t)i] = failed;
+            has_wm = has_wm && p.turn;
+            flat = false;
+        }
+        impgpu_image* out = nullptr;
+        if (int rc = image_new_album(p.fw, p.fh, p.v.c, 1, &out)) { codes[i] = rc; continue; }      // (as Work::fresh)
+        outs[(size_t)i] = out;
+        const int k = p.v.c - 3;
+        if (p.rot == 0 && !has_wm && !flat) {
+            bares[k].push_back(MixFrame{p.v.d, p.v.w, p.v.h, p.v.step, out->d, p.w, p.h, out->step});
+            bare_who[k].push_back(i);
+        } else {
+            tails[k].push_back(TailItem{p.v, out->d, p.w, p.h, out->step, p.rot, has_wm, p.wm, flat});
+            tail_who[k].push_back(i);
+        }
+    }
+    auto settle = [&](const std::vector<int>& who, int rc) {
+        for (int i : who) {
+            if (rc != IMP_OK) {                                         // the launch failed: the request keeps its frame
+                image_delete(outs[(size_t)i]);
+                codes[i] = rc;
+                steps[i] = IMP_STEP_RESIZE;
+                continue;
+            }
+            image_delete(images[i]);                                    // (pool memory: recycled in stream order, behind the launch)
+            images[i] = outs[(size_t)i];
+            codes[i] = final_code[(size_t)i];
+            steps[i] = final_step[(size_t)i];
+        }
+    };
+    for (int k = 0; k < 2; k++) {
+        if (!bares[k].empty()) settle(bare_who[k], launch_resize_mixed(bares[k].data(), (int)bares[k].size(), k + 3, 0, s));
+        if (!tails[k].empty()) settle(tail_who[k], launch_area_tail_mixed(tails[k].data(), (int)tails[k].size(), k + 3, s));
+    }
+    if (launches) *launches = (int)(t_launches - launched);
+    return IMP_OK;
 }
 
 // ------------------------------------------------------------------ batch entry points

@@ -6,8 +6,9 @@
 // are queued when it looks (up to --batch), so the number of files per launch follows the load by itself: one idle worker
 // gets a batch of one (the latency of the in-process path plus two futex hops), 32 busy workers ride 16-32 to a launch --
 //     files          impgpu_batch_decode_jpeg            cvDecodeImage, bridge.c:545-552
-//     resize-only    impgpu_batch_resize_mixed           Resize(), bridge.c:588-604     (anything else: impgpu_run_ops per frame,
-//                                                                                        bridge.c:574-656 in the reference's order)
+//     operators      impgpu_batch_run_ops                bridge.c:574-656: crop -> resize -> rotate -> watermark -> flatten
+//                                                        chains share one launch per channel count; anything else runs
+//                                                        request by request (impgpu_run_ops) inside the same call
 //     JPEG answers   impgpu_batch_encode_jpeg            cvEncodeImage(".jpg"), bridge.c:704
 //     pixel answers  impgpu_batch_download               for the host encoders (PNG, WebP, FreeImage formats)
 // Nothing a worker writes into its slot is trusted further than a request is: the request record is copied out of shared
@@ -166,7 +167,6 @@ struct Req {
     impb_slot_fields q;                 // private copy of the record (the strings included)
     const uint8_t* in = nullptr;        // the slot's data area (shared: read once by the decoder)
     impgpu_image* img = nullptr;
-    impgpu_image* out = nullptr;        // resize-only path: the thumbnail
     int code = IMP_OK, step = IMP_STEP_START;
     bool done = false;                  // the answer is final (an error, NOT_TAKEN, a registration)
     std::string err;
@@ -235,15 +235,6 @@ bool is_png(const uint8_t* p, uint64_t n) {
     return n >= 8 && !std::memcmp(p, sig, 8);
 }
 
-// Does the request's operator segment come down to one Resize() of a colour frame?  (Then it rides the mixed launch.)
-bool resize_only(const Req& r) {
-    if (!r.job.resize || r.job.crop || r.job.filter_count || r.cfg.watermark) return false;
-    const int c = impgpu_image_channels(r.img);
-    if (c == 1) return false;                                   // gray -> BGR first (bridge.c:613-618): run_ops knows
-    if (c == 4 && r.job.need_flatten) return false;
-    return impgpu_album_count(r.img) == 1;
-}
-
 // A batch on its way through a lane.  Its three steps -- begin (copy the records, enqueue the JPEG decode), middle (read the
 // verdicts, operators, enqueue the answers' encode), end (fetch the files, wake the workers) -- are separate because the lane
 // runs them INTERLEAVED with the next batch's: while the device writes batch k's answers the thread unpacks batch k + 1 and
@@ -267,7 +258,10 @@ struct Worker {
     Batch slots_[2];
     // scratch reused from batch to batch
     std::vector<impgpu_image*> imgs;
-    std::vector<int> codes;
+    std::vector<int> codes, steps;
+    std::vector<size_t> live;
+    std::vector<impgpu_job> jobs;
+    std::vector<const impgpu_config*> cfgs;
 
     Worker(const Segment& s, const Options& o, int i) : S(s), O(o), id(i) {}
 
@@ -302,7 +296,6 @@ struct Worker {
         std::snprintf(s->error, sizeof s->error, "%s", r.err.c_str());
         s->broker_us = (uint32_t)(now_us() - r.t_taken);
         impgpu_image_release(&r.img);
-        impgpu_image_release(&r.out);
         __atomic_add_fetch(&S.h->served, (uint64_t)1, __ATOMIC_RELAXED);
         if (aload(&s->owner_pid) == 0) { astore(&s->state, (uint32_t)IMPB_FREE); return; }     // abandoned by a worker that timed out
         astore(&s->state, (uint32_t)IMPB_DONE);
@@ -407,44 +400,27 @@ struct Worker {
 
         const double t2 = now_us();
         g_us_decode += (uint64_t)(t2 - t1);
-        // ---- operators (bridge.c:574-656)
-        std::map<int, std::vector<size_t>> mixed;                // channels * 2 + simple -> requests of one mixed launch
-        for (size_t k = 0; k < n; k++) {
-            Req& r = reqs[k];
-            if (r.done) continue;
-            if (r.cfg.max_filters_count > 0 && r.job.filter_count > r.cfg.max_filters_count) { fail(r, IMP_ERROR_TOO_MUCH_FILTERS, IMP_STEP_START, ""); continue; }
-            if (n > 1 && resize_only(r)) {
-                int ow = 0, oh = 0, ip = 0;
-                const int sw = impgpu_image_width(r.img), sh = impgpu_image_height(r.img), c = impgpu_image_channels(r.img);
-                const int rc = impgpu_resize_geometry(sw, sh, r.job.resize, &r.cfg, r.job.simple, &ow, &oh, &ip);
-                if (rc != IMP_OK) { fail(r, rc, IMP_STEP_RESIZE, ""); continue; }
-                if (ow != sw || oh != sh) {
-                    const int rc2 = impgpu_image_create(ow, oh, c, &r.out);
-                    if (rc2 != IMP_OK) { fail(r, rc2, IMP_STEP_RESIZE, impgpu_last_error()); continue; }
-                    mixed[c * 2 + (r.job.simple ? 1 : 0)].push_back(k);
-                    continue;
-                }
+        // ---- operators (bridge.c:574-656): every live request in ONE call -- the chains the mixed launch takes share a launch
+        // per channel count, the rest run request by request inside it
+        live.clear();
+        for (size_t k = 0; k < n; k++) if (!reqs[k].done) live.push_back(k);
+        if (!live.empty()) {
+            const size_t m = live.size();
+            imgs.resize(m);
+            jobs.resize(m);
+            cfgs.resize(m);
+            codes.assign(m, IMP_OK);
+            steps.assign(m, IMP_STEP_START);
+            for (size_t j = 0; j < m; j++) {
+                Req& r = reqs[live[j]];
+                imgs[j] = r.img; jobs[j] = r.job; cfgs[j] = &r.cfg;
             }
-            int step = IMP_STEP_START;
-            const int rc = impgpu_run_ops(&r.img, &r.job, &r.cfg, &step);
-            if (rc != IMP_OK) fail(r, rc, step, rc == IMP_ERROR_DEVICE ? impgpu_last_error() : "");
-        }
-        for (auto& kv : mixed) {
-            std::vector<impgpu_resize_item> items(kv.second.size());
-            for (size_t j = 0; j < kv.second.size(); j++) {
-                Req& r = reqs[kv.second[j]];
-                items[j].src = impgpu_image_device_ptr(r.img); items[j].src_width = impgpu_image_width(r.img);
-                items[j].src_height = impgpu_image_height(r.img); items[j].src_step = impgpu_image_step(r.img);
-                items[j].dst = impgpu_image_device_ptr(r.out); items[j].dst_width = impgpu_image_width(r.out);
-                items[j].dst_height = impgpu_image_height(r.out); items[j].dst_step = impgpu_image_step(r.out);
-            }
-            const int rc = impgpu_batch_resize_mixed(items.data(), (int)items.size(), kv.first / 2, kv.first & 1, nullptr);
-            for (size_t j = 0; j < kv.second.size(); j++) {
-                Req& r = reqs[kv.second[j]];
-                if (rc != IMP_OK) { fail(r, rc, IMP_STEP_RESIZE, impgpu_last_error()); continue; }
-                impgpu_image_release(&r.img);                    // (pool memory: recycled in stream order, behind the launch)
-                r.img = r.out;
-                r.out = nullptr;
+            const int rc = impgpu_batch_run_ops(imgs.data(), jobs.data(), cfgs.data(), (int)m, codes.data(), steps.data(), nullptr);
+            for (size_t j = 0; j < m; j++) {
+                Req& r = reqs[live[j]];
+                if (rc != IMP_OK) { fail(r, rc, IMP_STEP_START, impgpu_last_error()); continue; }
+                r.img = imgs[j];
+                if (codes[j] != IMP_OK) fail(r, codes[j], steps[j], codes[j] == IMP_ERROR_DEVICE ? impgpu_last_error() : "");
             }
         }
 

@@ -120,6 +120,17 @@ bool fault_hit(int step);
     do {                                                          \
         if (imp::fault_hit(step)) return IMP_ERROR_DEVICE;        \
     } while (0)
+// Kernels the calling thread has enqueued since it started (impgpu_batch_run_ops reports the difference): every launch
+// site of the library goes through hipLaunchKernelGGL, which counts here before it launches.
+extern thread_local unsigned long long t_launches;
+#ifdef hipLaunchKernelGGL
+#undef hipLaunchKernelGGL
+#define hipLaunchKernelGGL(kernelName, ...)                              \
+    do {                                                                  \
+        ++imp::t_launches;                                                \
+        hipLaunchKernelGGLInternal((kernelName), __VA_ARGS__);            \
+    } while (0)
+#endif
 #define IMP_HIP(call)                                             \
     do {                                                          \
         hipError_t _e = (call);                                   \
@@ -164,6 +175,17 @@ __device__ __forceinline__ uint32_t blend_over_bgr(uint32_t d, uint32_t s, float
         tR = (int)__fdiv_rn(__fadd_rn(__fmul_rn((float)sR, sA), __fmul_rn(__fmul_rn((float)dR, dA), inv)), tA);
     }
     return (uint32_t)(tB & 0xff) | ((uint32_t)(tG & 0xff) << 8) | ((uint32_t)(tR & 0xff) << 16);
+}
+// BlendWithPaper on one BGRA pixel (filters.c:666-687): the colour over white by its alpha, alpha 255.  Shared by
+// k_blend_paper (imp_pixel.hip) and the tail of the mixed resize launch (imp_resize.hip), so the two stay bit-identical.
+__device__ __forceinline__ uint32_t blend_paper_bgra(uint32_t u) {
+    const int a = u >> 24;
+    const int diff = 255 - a;
+    const float prod = (float)((double)a / 255.0);
+    const int tb = (int)__fadd_rn((float)diff, __fmul_rn((float)(u & 0xff), prod));
+    const int tg = (int)__fadd_rn((float)diff, __fmul_rn((float)((u >> 8) & 0xff), prod));
+    const int tr = (int)__fadd_rn((float)diff, __fmul_rn((float)((u >> 16) & 0xff), prod));
+    return (uint32_t)(tb & 0xff) | ((uint32_t)(tg & 0xff) << 8) | ((uint32_t)(tr & 0xff) << 16) | 0xff000000u;
 }
 #endif
 
@@ -248,6 +270,14 @@ int launch_area2x2_rotate(const Frames& f, int amount, const OverlayArgs* overla
 // general INTER_AREA of BGRA frames + rotate 0/90/180/270 + watermark in one pass (f.dw x f.dh = the resized geometry,
 // f.dst = the final frames); IMP_ERROR_UNSUPPORTED when the geometry takes another resize kernel.
 int launch_area_rotate(const Frames& f, int amount, const OverlayArgs* overlay, hipStream_t s);
+// Does launch_area_rotate take this resize (f.v -> f.dw x f.dh, f.count frames into f.dst)?  *w / *bh: its window and band
+// height.  The one acceptance test of the fused resize tail, for the lone launch and the mixed one alike.
+bool area_tail_plan(const Frames& f, int* w, int* bh);
+// The mixed launch with a tail per frame: resize (general INTER_AREA) -> rotate 0/90/180/270 -> watermark -> flatten, frames
+// of different geometry and one channel count in ONE launch.  Every item must pass area_tail_plan (IMP_ERROR_INVALID_ARGS
+// otherwise, nothing launched).  `dw` x `dh` of an item is the resized geometry, `dst` the final (turned) frame.
+struct TailItem { View v; uint8_t* dst; int dw, dh, dstep; int rot; bool has_wm; OverlayArgs wm; bool flatten; };
+int launch_area_tail_mixed(const TailItem* items, int count, int channels, hipStream_t s);
 // imp_geom.hip
 int launch_copy(const Frames& f, hipStream_t s);                       // crop copy / clone (dw,dh = v.w,v.h)
 int launch_flip(const Frames& f, int mode, hipStream_t s);             // cvFlip

@@ -414,14 +414,7 @@ __global__ __launch_bounds__(256) void k_blend_paper(uint8_t* base, long long st
     if (idx >= (long long)w * h) return;
     const int y = (int)(idx / w), x = (int)(idx - (long long)y * w);
     uint32_t* p = (uint32_t*)(base + (long long)blockIdx.y * stride + (size_t)y * step + (size_t)x * 4);
-    const uint32_t u = *p;
-    const int a = u >> 24;
-    const int diff = 255 - a;
-    const float prod = (float)((double)a / 255.0);
-    const int tb = (int)__fadd_rn((float)diff, __fmul_rn((float)(u & 0xff), prod));
-    const int tg = (int)__fadd_rn((float)diff, __fmul_rn((float)((u >> 8) & 0xff), prod));
-    const int tr = (int)__fadd_rn((float)diff, __fmul_rn((float)((u >> 16) & 0xff), prod));
-    *p = (uint32_t)(tb & 0xff) | ((uint32_t)(tg & 0xff) << 8) | ((uint32_t)(tr & 0xff) << 16) | 0xff000000u;
+    *p = blend_paper_bgra(*p);
 }
 
 int launch_blend_paper(uint8_t* d, long long stride, int w, int h, int step, int count, hipStream_t s) {

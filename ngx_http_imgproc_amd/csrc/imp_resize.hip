@@ -2137,9 +2137,12 @@ __device__ __forceinline__ uint32_t overlay_px(const OverlayArgs& wm, uint32_t p
 }
 __device__ __forceinline__ void store_bgr(uint8_t* q, uint32_t px) { q[0] = (uint8_t)px; q[1] = (uint8_t)(px >> 8); q[2] = (uint8_t)(px >> 16); }
 
-template <int CN, int W>
+// PAPER: the tail may end in BlendWithPaper (`flat`, BGRA only), after the overlay -- compiled in for the mixed tail kernel
+// alone, so the other kernels that share this body keep their code.
+template <int CN, int W, bool PAPER = false>
 __device__ __forceinline__ void area_rows_body(const RArgs& a, const AreaGeom& gm, int frame, int item, int nstrips, int bh,
-                                               uint32_t* __restrict__ line, const AreaTail& tail, uint32_t* __restrict__ tile) {
+                                               uint32_t* __restrict__ line, const AreaTail& tail, uint32_t* __restrict__ tile,
+                                               bool flat = false) {
     static_assert(CN == 3 || CN == 4, "interleaved BGR / BGRA");
     constexpr int NV = (W + 3) / 4;                              // 16-byte granules a lane fetches per source row
     const int lane = threadIdx.x & 63;
@@ -2269,7 +2272,8 @@ __device__ __forceinline__ void area_rows_body(const RArgs& a, const AreaGeom& g
         else if (live) {
             // R[i][j] = H[rh-1-i][rw-1-j] (180); H = the resized frame, dw x dh
             const int orow = tail.rot == 180 ? a.dh - 1 - dy : dy, ocol = tail.rot == 180 ? a.dw - 1 - dx : dx;
-            const uint32_t o = overlay_px<CN>(tail.wm, px, orow, ocol);
+            uint32_t o = overlay_px<CN>(tail.wm, px, orow, ocol);
+            if constexpr (PAPER && CN == 4) o = flat ? blend_paper_bgra(o) : o;
             if constexpr (CN == 4) *(uint32_t*)(D + (size_t)orow * a.dstep + (size_t)ocol * 4) = o;
             else store_bgr(D + (size_t)orow * a.dstep + (size_t)ocol * 3, o);
         }
@@ -2292,6 +2296,7 @@ __device__ __forceinline__ void area_rows_body(const RArgs& a, const AreaGeom& g
                 const int k = 4 * qi + jj;                       // k-th pixel of the run
                 const int r = tail.rot == 90 ? nb - 1 - k : k;   // band row it comes from
                 v[jj] = overlay_px<CN>(tail.wm, tile[min(max(r, 0), nb - 1) * 65 + col], orow, j0 + k);
+                if constexpr (PAPER && CN == 4) v[jj] = flat ? blend_paper_bgra(v[jj]) : v[jj];
             }
             uint8_t* q = D + (size_t)orow * a.dstep + (size_t)(j0 + 4 * qi) * CN;
             if constexpr (CN == 3) {                              // (a run of BGR pixels starts at any byte: byte stores)
@@ -2538,6 +2543,42 @@ __global__ __launch_bounds__(256) void k_resize_area_mix(const MixDesc* __restri
     }
 }
 
+// The same launch for requests whose Resize() is followed by more of RunJob's chain (bridge.c:606-656): a quarter or half
+// turn (Filter "rotate"), the watermark and BlendWithPaper ride on the stores of the row-streaming body, exactly as in the
+// lone launch_area_rotate, with the tail read from the frame's descriptor instead of the launch arguments.  A kernel of its
+// own: the turned band's LDS tile (4 x 16 x 65 words, 16.6 KB a block) is not paid by k_resize_area_mix's bare batches.
+// Every descriptor is a row-streaming one (nitems > 0, nv = the window, 1..20: area_tail_plan's, the lone launch's).
+struct MixTailDesc { MixDesc m; AreaTail tail; int flat; };
+
+template <int CN>
+__global__ __launch_bounds__(256) void k_resize_area_mix_tail(const MixTailDesc* __restrict__ d, MixIndex ix) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_line[4][64 * MIX_NV * 4 + 4];
+    __shared__ uint32_t s_tile[4][16 * 65];                      // quarter turns: a band (<= 16 rows) waits here to leave turned
+    const int g = blockIdx.x & 7, q = blockIdx.x >> 3;
+    int lo = ix.off[g], hi = ix.off[g + 1];
+    if (lo == hi || q >= d[hi - 1].m.first + d[hi - 1].m.nblk) return;
+    while (hi - lo > 1) {                              // last descriptor whose first block is <= q
+        const int mid = (lo + hi) >> 1;
+        if (d[mid].m.first <= q) lo = mid; else hi = mid;
+    }
+    const MixTailDesc& t = d[lo];
+    const MixDesc& m = t.m;
+    const int blk = q - m.first;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int item = blk * 4 + wv;
+    if (item >= m.nitems) return;
+    const bool flat = t.flat != 0;
+    switch (m.nv) {                                    // (block-uniform: a scalar branch)
+#define IMP_TAIL_W(W_) \
+        case W_: area_rows_body<CN, W_, true>(m.a, m.gm, 0, item, m.nstrips, m.rows, s_line[wv], t.tail, s_tile[wv], flat); break;
+        IMP_TAIL_W(1) IMP_TAIL_W(2) IMP_TAIL_W(3) IMP_TAIL_W(4) IMP_TAIL_W(5) IMP_TAIL_W(6) IMP_TAIL_W(7) IMP_TAIL_W(8)
+        IMP_TAIL_W(9) IMP_TAIL_W(10) IMP_TAIL_W(11) IMP_TAIL_W(12) IMP_TAIL_W(13) IMP_TAIL_W(14) IMP_TAIL_W(15) IMP_TAIL_W(16)
+        IMP_TAIL_W(17) IMP_TAIL_W(18) IMP_TAIL_W(19)
+#undef IMP_TAIL_W
+        default: area_rows_body<CN, 20, true>(m.a, m.gm, 0, item, m.nstrips, m.rows, s_line[wv], t.tail, s_tile[wv], flat); break;
+    }
+}
+
 // ------------------------------------------------------------------ per-geometry table cache
 struct TableSet {
     void* blob = nullptr;     // one device allocation
@@ -2744,18 +2785,25 @@ static void launch_area_rows(int w, dim3 grid, hipStream_t s, const RArgs& a, co
 
 // Resize (general INTER_AREA, BGRA or BGR) + rotate + watermark (a BGRA overlay) in one pass; f.dw x f.dh is the RESIZED geometry, f.dst the final
 // (rotated) frames.  IMP_ERROR_UNSUPPORTED when the geometry takes another resize kernel.
-int launch_area_rotate(const Frames& f, int amount, const OverlayArgs* overlay, hipStream_t s) {
+bool area_tail_plan(const Frames& f, int* w, int* bh) {
     const View& v = f.v;
-    if ((v.c != 4 && v.c != 3) || f.count <= 0 || f.count > 65535 || f.dw > v.w || f.dh > v.h) return IMP_ERROR_UNSUPPORTED;
-    if (v.c == 3 && v.w < 6) return IMP_ERROR_UNSUPPORTED;   // (the BGR windows' aligned-dword reads need a few pixels of row)
+    if ((v.c != 4 && v.c != 3) || f.count <= 0 || f.count > 65535 || f.dw <= 0 || f.dh <= 0 || f.dw > v.w || f.dh > v.h) return false;
+    if (v.c == 3 && v.w < 6) return false;                 // (the BGR windows' aligned-dword reads need a few pixels of row)
     if (((uintptr_t)f.src | (uintptr_t)f.dst | (uintptr_t)v.step | (uintptr_t)f.dstep | (uintptr_t)f.src_stride | (uintptr_t)f.dst_stride) & 3)
-        return IMP_ERROR_UNSUPPORTED;
+        return false;
     const double scale_x = 1. / ((double)f.dw / v.w), scale_y = 1. / ((double)f.dh / v.h);
     if (std::fabs(scale_x - std::lrint(scale_x)) < 2.220446049250313e-16 && std::fabs(scale_y - std::lrint(scale_y)) < 2.220446049250313e-16)
-        return IMP_ERROR_UNSUPPORTED;                      // resizeAreaFast_: the box kernels' arithmetic
+        return false;                                      // resizeAreaFast_: the box kernels' arithmetic
+    if (!area_rows_plan(v.w, v.h, f.dw, f.dh, scale_x, f.count, false, w, bh)) return false;
+    *bh = std::min(*bh, 16);                               // (the turned band's LDS tile)
+    return true;
+}
+
+int launch_area_rotate(const Frames& f, int amount, const OverlayArgs* overlay, hipStream_t s) {
+    const View& v = f.v;
     int w = 0, bh = 0;
-    if (!area_rows_plan(v.w, v.h, f.dw, f.dh, scale_x, f.count, false, &w, &bh)) return IMP_ERROR_UNSUPPORTED;
-    bh = std::min(bh, 16);                                 // (the turned band's LDS tile)
+    if (!area_tail_plan(f, &w, &bh)) return IMP_ERROR_UNSUPPORTED;
+    const double scale_x = 1. / ((double)f.dw / v.w), scale_y = 1. / ((double)f.dh / v.h);
     const RArgs a{f.src, f.src_stride, v.step, v.w, v.h, f.dst, f.dst_stride, f.dstep, f.dw, f.dh};
     const AreaGeom gm{scale_x, scale_y};
     AreaTail tail{};
@@ -3336,14 +3384,15 @@ int launch_cv_resize(const Frames& f, int interp, hipStream_t s) {
 // general AREA path (every non-integer shrink whose cells span at most 16 source columns) are gathered into descriptor
 // launches, one per window width class, with their weights computed in the kernel; the rest (integer factors,
 // enlargements, NN, extreme ratios) go one launch each on the same stream.
-static int launch_mix(std::vector<MixDesc>& v, int cn, hipStream_t s) {
-    if (v.empty()) return IMP_OK;
-    // blocks differ a hundredfold in work (a 4K source against a 256-pixel one, same 224-wide output): the frames go
-    // longest first to the XCD list with the least source bytes so far, so each list starts with its heavy frames and
-    // the launch's tail is made of light ones
+// Blocks differ a hundredfold in work (a 4K source against a 256-pixel one, same 224-wide output): the frames go
+// longest first to the XCD list with the least source bytes so far, so each list starts with its heavy frames and
+// the launch's tail is made of light ones.  `v` is consumed; *sorted holds the descriptors list by list, *most = the
+// blocks of the longest list (the grid is 8 * most).
+template <class D, class M>
+static void mix_deal(std::vector<D>& v, M desc, std::vector<D>* sorted_out, MixIndex* ix_out, int* most_out) {
     std::vector<int> order(v.size());
     for (size_t i = 0; i < v.size(); i++) order[i] = (int)i;
-    auto cost = [&](int i) { return (long long)v[i].a.sw * v[i].a.sh; };
+    auto cost = [&](int i) { return (long long)desc(v[i]).a.sw * desc(v[i]).a.sh; };
     static const bool no_sort = ab_env("IMPGPU_MIX_NOSORT") != nullptr;
     if (!no_sort) std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return cost(x) > cost(y); });
     std::vector<int> list[8];
@@ -3355,23 +3404,34 @@ static int launch_mix(std::vector<MixDesc>& v, int cn, hipStream_t s) {
         list[g].push_back(i);
         load[g] += cost(i) + 4096;
     }
-    std::vector<MixDesc> sorted;
+    std::vector<D>& sorted = *sorted_out;
+    sorted.clear();
     sorted.reserve(v.size());
-    MixIndex ix{};
+    MixIndex& ix = *ix_out;
+    ix = MixIndex{};
     int most = 0;
     for (int g = 0; g < 8; g++) {
         ix.off[g] = (int)sorted.size();
         int first = 0;
         for (int i : list[g]) {
-            MixDesc d = v[i];
-            d.first = first;
-            first += d.nblk;
+            D d = v[i];
+            desc(d).first = first;
+            first += desc(d).nblk;
             sorted.push_back(d);
         }
         most = std::max(most, first);
     }
     ix.off[8] = (int)sorted.size();
     v.clear();
+    *most_out = most;
+}
+
+static int launch_mix(std::vector<MixDesc>& v, int cn, hipStream_t s) {
+    if (v.empty()) return IMP_OK;
+    std::vector<MixDesc> sorted;
+    MixIndex ix{};
+    int most = 0;
+    mix_deal(v, [](MixDesc& d) -> MixDesc& { return d; }, &sorted, &ix, &most);
     void* dev = nullptr;
     if (int rc = upload_small(sorted.data(), sorted.size() * sizeof(MixDesc), &dev, s)) return rc;
     const dim3 grid((unsigned)most * 8), block(256);
@@ -3444,6 +3504,50 @@ int launch_resize_mixed(const MixFrame* fr, int count, int cn, int simple, hipSt
         }
     }
     return launch_mix(gathered_frames, cn, s);
+}
+
+int launch_area_tail_mixed(const TailItem* items, int count, int cn, hipStream_t s) {
+    if (count <= 0) return IMP_OK;
+    if (!items || (cn != 3 && cn != 4)) return IMP_ERROR_INVALID_ARGS;
+    std::vector<MixTailDesc> v((size_t)count);
+    for (int i = 0; i < count; i++) {                      // nothing is launched unless every item is one the lone launch takes
+        const TailItem& it = items[i];
+        if (it.v.c != cn || !it.v.d || !it.dst || !view_fits(it.v.w, it.v.h, cn, it.v.step)) return IMP_ERROR_INVALID_ARGS;
+        if (it.rot != 0 && it.rot != 90 && it.rot != 180 && it.rot != 270) return IMP_ERROR_INVALID_ARGS;
+        const bool swap = it.rot == 90 || it.rot == 270;
+        if (!view_fits(swap ? it.dh : it.dw, swap ? it.dw : it.dh, cn, it.dstep)) return IMP_ERROR_INVALID_ARGS;
+        if (it.has_wm && (!it.wm.ov || ((uintptr_t)it.wm.ov | (uintptr_t)it.wm.ostep) & 3)) return IMP_ERROR_INVALID_ARGS;
+        Frames f{};
+        f.src = it.v.d; f.v = it.v; f.dst = it.dst; f.dw = it.dw; f.dh = it.dh; f.dstep = it.dstep;
+        f.count = count;                                   // (the band height follows the whole launch, as in launch_resize_mixed)
+        int w = 0, bh = 0;
+        if (!area_tail_plan(f, &w, &bh)) return IMP_ERROR_INVALID_ARGS;
+        MixTailDesc& d = v[(size_t)i];
+        d = MixTailDesc{};
+        d.m.a = RArgs{it.v.d, 0, it.v.step, it.v.w, it.v.h, it.dst, 0, it.dstep, it.dw, it.dh};
+        d.m.gm = AreaGeom{1. / ((double)it.dw / it.v.w), 1. / ((double)it.dh / it.v.h)};
+        d.m.nv = w;
+        d.m.rows = bh;
+        d.m.nstrips = (it.dw + 63) / 64;
+        d.m.nitems = d.m.nstrips * ((it.dh + bh - 1) / bh);
+        d.m.nblk = (d.m.nitems + 3) / 4;
+        d.tail.rot = it.rot;
+        if (it.has_wm) d.tail.wm = it.wm;
+        d.flat = it.flatten && cn == 4;
+    }
+    std::vector<MixTailDesc> sorted;
+    MixIndex ix{};
+    int most = 0;
+    mix_deal(v, [](MixTailDesc& d) -> MixDesc& { return d.m; }, &sorted, &ix, &most);
+    void* dev = nullptr;
+    if (int rc = upload_small(sorted.data(), sorted.size() * sizeof(MixTailDesc), &dev, s)) return rc;
+    const dim3 grid((unsigned)most * 8), block(256);
+    if (cn == 4) hipLaunchKernelGGL((k_resize_area_mix_tail<4>), grid, block, 0, s, (const MixTailDesc*)dev, ix);
+    else hipLaunchKernelGGL((k_resize_area_mix_tail<3>), grid, block, 0, s, (const MixTailDesc*)dev, ix);
+    const hipError_t e = hipGetLastError();
+    dev_free_on(dev, s);
+    IMP_HIP(e);
+    return IMP_OK;
 }
 
 }  // namespace imp

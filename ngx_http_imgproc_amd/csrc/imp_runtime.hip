@@ -108,6 +108,7 @@ struct LaneReturn {
 };
 static thread_local LaneReturn t_lane_return;
 static thread_local std::string t_error;
+thread_local unsigned long long t_launches = 0;
 
 // ---- rocTX (optional) and fault injection
 static void (*g_roctx_push)(const char*) = nullptr;

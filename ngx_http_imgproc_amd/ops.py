@@ -257,9 +257,8 @@ class Image:
         return lib.impgpu_hsv2rgb(self.h)
 
 
-def run_ops(image, config, crop=None, gravity=None, resize=None, simple=0, filters=(), need_flatten=0):
-    """RunJob's operator segment, bridge.c:574-656. Returns (code, step)."""
-    job = CJob()
+def _job(job, crop=None, gravity=None, resize=None, simple=0, filters=(), need_flatten=0):
+    """Fill a CJob; returns the filter array, which must outlive the call."""
     job.crop = _b(crop)
     job.gravity = _b(gravity)
     job.resize = _b(resize)
@@ -268,9 +267,37 @@ def run_ops(image, config, crop=None, gravity=None, resize=None, simple=0, filte
     job.filters = arr
     job.filter_count = len(filters)
     job.need_flatten = need_flatten
+    return arr
+
+
+def run_ops(image, config, crop=None, gravity=None, resize=None, simple=0, filters=(), need_flatten=0):
+    """RunJob's operator segment, bridge.c:574-656. Returns (code, step)."""
+    job = CJob()
+    keep = _job(job, crop, gravity, resize, simple, filters, need_flatten)  # noqa: F841
     step = C.c_int()
     rc = lib.impgpu_run_ops(C.byref(image.h), C.byref(job), C.byref(config.c), C.byref(step))
     return rc, step.value
+
+
+def batch_run_ops(images, configs, jobs):
+    """impgpu_batch_run_ops: run_ops for request i = (images[i], configs[i], **jobs[i]) at once.  The Image objects take
+    their new handles like run_ops' do.  Returns ([(code, step)], launches)."""
+    n = len(images)
+    if len(configs) != n or len(jobs) != n:
+        raise ValueError("images, configs and jobs differ in length")
+    handles = (C.c_void_p * max(1, n))(*[im.h.value for im in images])
+    cjobs = (CJob * max(1, n))()
+    keep = [_job(cjobs[i], **jobs[i]) for i in range(n)]  # noqa: F841
+    cfgs = (C.POINTER(CConfig) * max(1, n))(*[C.pointer(c.c) for c in configs])
+    codes = (C.c_int * max(1, n))()
+    steps = (C.c_int * max(1, n))()
+    launches = C.c_int()
+    rc = lib.impgpu_batch_run_ops(handles, cjobs, cfgs, n, codes, steps, C.byref(launches))
+    if rc:
+        raise ImpError(rc, "impgpu_batch_run_ops")
+    for i, im in enumerate(images):
+        im.h = C.c_void_p(handles[i])
+    return [(codes[i], steps[i]) for i in range(n)], launches.value
 
 
 def batch_decode_jpeg(blobs):

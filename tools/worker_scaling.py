@@ -19,6 +19,11 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 HARNESS = os.path.join(ROOT, "tests", "c", "_build", "worker_harness")
+# Other requests than resize=224,0 (broker only): --query takes a query string (impgpu_parse_request), --watermark the location's
+# placement gx,gy,ox,oy,opacity of a fixed 96 x 32 BGRA overlay; the workers are then tools/request_worker.c.  --check writes the
+# oracle's answers for the pool and that request first, and every answer is compared with them.
+#     python tools/worker_scaling.py broker 1 8 16 32 --query "crop=16,9&resize=224,0" --watermark r,b,6,4,70 --check
+REQUEST_WORKER = os.path.join(ROOT, "tools", "_build", "request_worker")
 BROKER = os.path.join(ROOT, "ngx_http_imgproc_amd", "impgpu_broker")
 
 
@@ -62,10 +67,80 @@ def stop_broker(p):
     return err
 
 
-def run_point(pool, mode, nproc, seconds, answers=None, broker_name=None, timeout=300):
+def build_request_worker():
+    src = [os.path.join(ROOT, "tools", "request_worker.c"), os.path.join(ROOT, "glue", "imp_gpu_client.c")]
+    deps = src + [os.path.join(ROOT, "include", "impgpu.h"), os.path.join(ROOT, "include", "impgpu_broker.h")]
+    if os.path.exists(REQUEST_WORKER) and all(os.path.getmtime(f) <= os.path.getmtime(REQUEST_WORKER) for f in deps):
+        return
+    os.makedirs(os.path.dirname(REQUEST_WORKER), exist_ok=True)
+    lib = os.path.join(ROOT, "ngx_http_imgproc_amd")
+    subprocess.check_call(["gcc", "-std=gnu99", "-O2", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include")] + src +
+                          ["-o", REQUEST_WORKER, "-L", lib, "-limpgpu", "-lm", "-lrt", "-Wl,-rpath," + lib, "-Wl,-rpath-link,/opt/rocm/lib"])
+
+
+def overlay_frame():
+    """The --watermark overlay: 32 x 96 BGRA, fixed noise."""
+    import numpy as np
+
+    return np.random.Generator(np.random.PCG64(0x1A4D0096)).integers(0, 256, size=(32, 96, 4), dtype=np.uint8)
+
+
+def write_overlay(path):
+    ov = overlay_frame()
+    with open(path, "wb") as f:
+        f.write(struct.pack("<III", ov.shape[1], ov.shape[0], ov.shape[2]))
+        f.write(ov.tobytes())
+
+
+def oracle_answers(pool, query, placement, path):
+    """The file the reference writes for every pool file under `query` (and the --watermark placement), quality 86 unless
+    the query names one: the CPU oracle's decode -> RunJob's operators -> encode."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_lib as orc
+    import ngx_http_imgproc_amd as imp
+
+    req = imp.Request("/pool.jpg?" + query, "jpg", imp.Config())
+    assert req.code == 0, (query, req.code)
+    quality = int(req.quality) if req.quality else 86
+    with open(pool, "rb") as f:
+        data = f.read()
+    n, at, blobs = struct.unpack_from("<I", data, 0)[0], 4, []
+    for _ in range(n):
+        sz = struct.unpack_from("<I", data, at)[0]
+        blobs.append(data[at + 4:at + 4 + sz])
+        at += 4 + sz
+    answers = []
+    for b in blobs:
+        rc, cur = orc.jpeg_decode(b)
+        assert rc == 0
+        if req.crop is not None:
+            rc, cur = orc.crop(cur, req.crop, req.gravity)
+        if rc == 0 and req.resize is not None:
+            rc, cur = orc.resize(cur, req.resize, 2000, 2000, req.simple)
+        if rc == 0 and cur.shape[2] == 1:
+            cur = orc.gray2bgr(cur)
+        for flt in req.filters:
+            if rc == 0:
+                rc, cur = orc.filter(cur, flt, 0)
+        if rc == 0 and placement:
+            gx, gy, ox, oy, op = placement.split(",")
+            rc, cur = orc.watermark(cur, overlay_frame(), gx, gy, int(ox), int(oy), int(op))
+        if rc == 0 and req.need_flatten and cur.shape[2] == 4:
+            cur = orc.blend_with_paper(cur)
+        assert rc == 0, (query, rc)
+        rc, ans = orc.jpeg_encode(cur, quality)
+        assert rc == 0
+        answers.append(ans)
+    write_pool(path, answers)
+
+
+def run_point(pool, mode, nproc, seconds, answers=None, broker_name=None, timeout=300, query=None, overlay=None, placement=None):
     d = tempfile.mkdtemp(prefix="impw_")
     how = "direct" if mode == "direct" else "broker:%s" % broker_name
-    cmd = lambda i: [HARNESS, pool, str(seconds), str(i), d, how] + ([answers] if answers else [])
+    if query is not None:           # any request: tools/request_worker.c (broker only)
+        cmd = lambda i: [REQUEST_WORKER, pool, str(seconds), str(i), d, how, query, overlay or "-", placement or "-"] + ([answers] if answers else [])
+    else:
+        cmd = lambda i: [HARNESS, pool, str(seconds), str(i), d, how] + ([answers] if answers else [])
     procs = [subprocess.Popen(cmd(i), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for i in range(nproc)]
     t_end = time.time() + timeout
     try:
@@ -113,9 +188,25 @@ def main():
     ap.add_argument("--split-kb", type=int, default=0, help="a launch takes files up to so many KB, or above (A/B)")
     ap.add_argument("--pipeline", type=int, default=0, help="0: the broker's lanes take one batch at a time (A/B)")
     ap.add_argument("--cu-split", type=int, default=0, help="IMPGPU_LANE_CU_SPLIT for the broker: every lane on its own n-th of the CUs")
+    ap.add_argument("--query", default=None, help="the request's query string (default resize=224,0 through worker_harness)")
+    ap.add_argument("--watermark", default=None, metavar="GX,GY,OX,OY,OPACITY", help="a location watermark with this placement")
+    ap.add_argument("--check", action="store_true", help="with --query: compare every answer with the oracle's file")
     args = ap.parse_args()
     os.makedirs(os.path.dirname(args.pool), exist_ok=True)
     make_pool(args.pool)
+    overlay = None
+    if args.query is not None or args.watermark:
+        if args.mode != "broker":
+            ap.error("--query / --watermark: broker mode only")
+        args.query = args.query if args.query is not None else "resize=224,0"
+        build_request_worker()
+        tmp = tempfile.mkdtemp(prefix="impq_")
+        if args.watermark:
+            overlay = os.path.join(tmp, "overlay.bin")
+            write_overlay(overlay)
+        if args.check:
+            args.answers = os.path.join(tmp, "answers.bin")
+            oracle_answers(args.pool, args.query, args.watermark, args.answers)
     for n in args.procs:
         if args.mode == "direct" and n > 6:
             print(json.dumps({"mode": "direct", "processes": n, "skipped": "more than 6 processes on the card"}), flush=True)
@@ -130,7 +221,11 @@ def main():
                 env["IMPGPU_LANE_CU_SPLIT"] = str(args.cu_split)
             broker = start_broker(name, args.threads, args.gather_us, env=env or None, extra=["--pipeline", str(args.pipeline), "--split-kb", str(args.split_kb)])
         try:
-            r = run_point(args.pool, args.mode, n, args.seconds, args.answers, name)
+            r = run_point(args.pool, args.mode, n, args.seconds, args.answers, name, query=args.query, overlay=overlay,
+                          placement=args.watermark)
+            if args.query is not None:
+                r["query"] = args.query
+                r["watermark"] = args.watermark
             if broker:
                 r["broker_threads"] = args.threads
                 r["gather_us"] = args.gather_us
