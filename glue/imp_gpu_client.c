@@ -312,7 +312,7 @@ int impgpu_client_run(impgpu_client* c, const impgpu_client_request* r, impgpu_c
     memset(a, 0, sizeof *a);
     a->error = "";
     if (r->in_kind != IMPB_IN_FILE && r->in_kind != IMPB_IN_FRAME) return IMP_ERROR_INVALID_ARGS;
-    if (r->out_kind < IMPB_OUT_JPEG || r->out_kind > IMPB_OUT_ASCII) return IMP_ERROR_INVALID_ARGS;
+    if (r->out_kind < IMPB_OUT_JPEG || r->out_kind > IMPB_OUT_PNG) return IMP_ERROR_INVALID_ARGS;
     if (r->watermark_id < 0 || r->watermark_id > c->nmarks) return IMP_ERROR_INVALID_ARGS;
     int rc = ready(c);
     if (rc != IMP_OK) return rc;

@@ -254,6 +254,28 @@ int   impgpu_batch_encode_jpeg_begin(const impgpu_image* const* images, int coun
 int   impgpu_batch_encode_jpeg_finish(impgpu_jpeg_encode** encode, unsigned char* const* outs, const size_t* capacities,
                                       size_t* lengths, int* codes);
 size_t impgpu_jpeg_encode_bound(int width, int height, int channels);
+/* The PNG answer: CvMat* encoded = cvEncodeImage(".png", image, basicCoderopt)                         bridge.c:704
+ * with basicCoderopt = {CV_IMWRITE_PNG_COMPRESSION, level} (bridge.c:487-497; quality= in 0..9, 9 when absent), for the
+ * frame the operators left in HBM: the row filters, the deflate symbols, the Huffman trees and the bit stream are made on
+ * the device and the compressed file crosses the link instead of the pixels.  OpenCV 2.4.9's PngEncoder asks libpng for
+ * strategy Z_RLE, libpng's own filter choice, png_set_bgr, 8-bit gray / RGB / RGBA (1 / 3 / 4 channels), no interlace,
+ * no chunks besides IHDR, IDAT, IEND -- and the file is the same, byte for byte, as libpng 1.6.37 over zlib 1.2.11's.
+ * Under Z_RLE levels 1..9 give the same file.  A 4-channel frame keeps its alpha (RunJob flattens only for JPEG); an album
+ * handle encodes frame 0, like bridge.c:703; a view with step > width * channels is fine.  IMP_ERROR_UNSUPPORTED = level 0
+ * (stored blocks whose sizes depend on how libpng feeds zlib), a 2-channel frame, a width or height above 1 000 000 (libpng's
+ * write limits: cvEncodeImage fails there too) or more than 2^28 bytes of filtered rows: encode it with cvEncodeImage as before.  IMP_ERROR_INVALID_ARGS = any other level outside 1..9.  *length receives the
+ * file's size; IMP_ERROR_MALLOC_FAILED = capacity is smaller than that (nothing is written; impgpu_png_encode_bound(w, h, c)
+ * is always enough, stored blocks included).  Waits for the device. */
+int   impgpu_image_encode_png(const impgpu_image* image, int level, unsigned char* out, size_t capacity, size_t* length);
+/* `count` frames (count <= 256; any sizes and channel counts mixed) in one set of launches and two waits; codes[i] /
+ * lengths[i] are what impgpu_image_encode_png would give for frame i. */
+int   impgpu_batch_encode_png(const impgpu_image* const* images, int count, int level, unsigned char* const* outs,
+                              const size_t* capacities, size_t* lengths, int* codes);
+size_t impgpu_png_encode_bound(int width, int height, int channels);
+/* Diagnostic (host, no device): the zlib stream libpng would write for `size` bytes of filtered scanlines, made by the
+ * device's own symbol / tree / bit code (csrc/imp_png_deflate.h) run on one host thread.  *length = the stream's size;
+ * IMP_ERROR_MALLOC_FAILED when capacity is smaller. */
+int   impgpu_png_deflate(const unsigned char* data, size_t size, unsigned char* out, size_t capacity, size_t* length);
 /* the SOF header alone (host, no device): the size checks the module makes before decoding */
 int   impgpu_jpeg_info(const unsigned char* blob, size_t size, int* width, int* height, int* channels);
 /* Diagnostics (host, no device): the quantised coefficients of the file's components, MCU-padded planes one after the

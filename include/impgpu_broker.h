@@ -52,7 +52,8 @@ enum { IMPB_IN_FILE = 0 /* a JPEG or PNG file */, IMPB_IN_FRAME = 1 /* decoded p
        IMPB_IN_WATERMARK = 2 /* pixels of a location's overlay: registered, answer = its id */ };
 enum { IMPB_OUT_JPEG = 0 /* cvEncodeImage(".jpg"), bridge.c:704 */, IMPB_OUT_FRAME = 1 /* pixels for a host encoder */,
        IMPB_OUT_INFO = 2 /* width, height, brightness (bridge.c:283-300) */,
-       IMPB_OUT_ASCII = 3 /* the text exit, ASCII() of filters.c:486-522 (bridge.c:669-670) */ };
+       IMPB_OUT_ASCII = 3 /* the text exit, ASCII() of filters.c:486-522 (bridge.c:669-670) */,
+       IMPB_OUT_PNG = 4 /* cvEncodeImage(".png"), bridge.c:704; `quality` = the compression level */ };
 /* answer codes besides IMP_*: the broker did not take the file (not a JPEG/PNG the device decodes, or damaged) -- the
  * worker decodes on the host as before and comes back with IMPB_IN_FRAME */
 #define IMPB_NOT_TAKEN    (-1)
@@ -88,7 +89,7 @@ typedef struct {
      * out of their byte stuffing and IMPGPU_JPEG_SCAN_TAIL bytes of 0xFF; in_bytes covers all of it */
     uint64_t in_head_bytes, in_scan_at, in_scan_bytes;
     int32_t  in_w, in_h, in_c, in_step; /* IMPB_IN_FRAME / IMPB_IN_WATERMARK */
-    int32_t  quality;                   /* IMPB_OUT_JPEG */
+    int32_t  quality;                   /* IMPB_OUT_JPEG; IMPB_OUT_PNG: the compression level */
     int32_t  simple, need_flatten, filter_count;
     int32_t  crop_at, gravity_at, resize_at;        /* offsets into text[], -1 = absent */
     int32_t  ascii_at;                  /* IMPB_OUT_ASCII: the argument string of ASCII(), -1 = "" */

@@ -151,6 +151,10 @@ SIGNATURES = {
     "impgpu_image_encode_jpeg": (C.c_int, [P, C.c_int, P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "impgpu_batch_encode_jpeg": (C.c_int, [PP, C.c_int, C.c_int, PP, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), IP]),
     "impgpu_jpeg_encode_bound": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "impgpu_image_encode_png": (C.c_int, [P, C.c_int, P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "impgpu_batch_encode_png": (C.c_int, [PP, C.c_int, C.c_int, PP, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), IP]),
+    "impgpu_png_encode_bound": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "impgpu_png_deflate": (C.c_int, [C.c_char_p, C.c_size_t, P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "impgpu_album_upload": (C.c_int, [PP, C.c_int, C.c_int, C.c_int, C.c_int, IP, PP]),
     "impgpu_album_download": (C.c_int, [P, PP, IP]),
     "impgpu_album_count": (C.c_int, [P]),

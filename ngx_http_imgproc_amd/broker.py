@@ -10,7 +10,7 @@ CLIENT_LIB_PATH = os.path.join(HERE, "libimpgpu_client.so")
 BROKER_PATH = os.path.join(HERE, "impgpu_broker")
 
 IN_FILE, IN_FRAME = 0, 1
-OUT_JPEG, OUT_FRAME, OUT_INFO, OUT_ASCII = 0, 1, 2, 3
+OUT_JPEG, OUT_FRAME, OUT_INFO, OUT_ASCII, OUT_PNG = 0, 1, 2, 3, 4
 NOT_TAKEN = -1
 
 
@@ -69,7 +69,8 @@ class Client:
 
     def run(self, blob=None, frame=None, crop=None, gravity=None, resize=None, filters=(), simple=0, need_flatten=0,
             config=None, watermark_id=0, out=OUT_JPEG, quality=86, ascii_args=None):
-        """-> (transport rc, code, step, payload, answer).  payload: bytes (JPEG), ndarray (FRAME), or None."""
+        """-> (transport rc, code, step, payload, answer).  payload: bytes (JPEG, PNG, ASCII), ndarray (FRAME), or None.
+        For out=OUT_PNG, `quality` is the compression level."""
         import numpy as np
 
         r = CRequest()
@@ -94,7 +95,7 @@ class Client:
         del buf
         if rc != 0 or a.code != 0:
             return rc, a.code, a.step, None, a
-        if out in (OUT_JPEG, OUT_ASCII):
+        if out in (OUT_JPEG, OUT_ASCII, OUT_PNG):
             return rc, 0, a.step, C.string_at(a.data, a.bytes), a
         if out == OUT_FRAME:
             rows = np.ctypeslib.as_array(C.cast(a.data, C.POINTER(C.c_ubyte)), shape=(a.height, a.row_step))

@@ -23,6 +23,7 @@ SOURCES = [
     "imp_jpeg.hip",
     "imp_jpeg_enc.hip",
     "imp_png.hip",
+    "imp_png_enc.hip",
     "imp_api.cpp",
     "imp_args.cpp",
     "imp_request.cpp",
@@ -32,7 +33,7 @@ SOURCES = [
     "imp_png.cpp",
     "imp_inflate.cpp",
 ]
-HEADERS = ["imp_internal.h", "imp_jpeg.h", "imp_jpeg_core.h", "imp_jpeg_std.h", "imp_png.h", "imp_inflate.h", os.path.join("..", "..", "include", "impgpu.h")]
+HEADERS = ["imp_internal.h", "imp_jpeg.h", "imp_jpeg_core.h", "imp_jpeg_std.h", "imp_png.h", "imp_png_deflate.h", "imp_inflate.h", os.path.join("..", "..", "include", "impgpu.h")]
 FLAGS = [
     "--offload-arch=gfx950",
     "-O3",

@@ -10,6 +10,7 @@
 //                                                        chains share one launch per channel count; anything else runs
 //                                                        request by request (impgpu_run_ops) inside the same call
 //     JPEG answers   impgpu_batch_encode_jpeg            cvEncodeImage(".jpg"), bridge.c:704
+//     PNG answers    impgpu_batch_encode_png             cvEncodeImage(".png"), bridge.c:704
 //     pixel answers  impgpu_batch_download               for the host encoders (PNG, WebP, FreeImage formats)
 // Nothing a worker writes into its slot is trusted further than a request is: the request record is copied out of shared
 // memory once and validated (sizes against the slot, offsets against the text area, frame geometry against the bytes).
@@ -174,6 +175,7 @@ struct Req {
     impgpu_job job{};
     impgpu_config cfg{};
     double t_taken = 0;
+    uint64_t out_at = 0;                // where the answer goes in the slot's data area (kept here: the slot is shared memory)
 };
 
 struct Watermarks {
@@ -193,7 +195,7 @@ void prepare(Req& r, const Segment& S) {
     impb_slot_fields& q = r.q;
     q.text[IMPB_TEXT_BYTES - 1] = 0;
     if (q.in_bytes > S.slot_bytes) return fail(r, IMP_ERROR_INVALID_ARGS, IMP_STEP_VALIDATE, "in_bytes past the slot");
-    if (q.in_kind > IMPB_IN_WATERMARK || q.out_kind > IMPB_OUT_ASCII) return fail(r, IMP_ERROR_INVALID_ARGS, IMP_STEP_VALIDATE, "unknown kind");
+    if (q.in_kind > IMPB_IN_WATERMARK || q.out_kind > IMPB_OUT_PNG) return fail(r, IMP_ERROR_INVALID_ARGS, IMP_STEP_VALIDATE, "unknown kind");
     if (q.filter_count < 0 || q.filter_count > IMPB_MAX_FILTERS || !text_ok(q, q.crop_at) || !text_ok(q, q.gravity_at) || !text_ok(q, q.resize_at) || !text_ok(q, q.ascii_at))
         return fail(r, IMP_ERROR_INVALID_ARGS, IMP_STEP_VALIDATE, "bad text offsets");
     for (int i = 0; i < q.filter_count; i++) {
@@ -428,7 +430,7 @@ struct Worker {
         g_us_ops += (uint64_t)(t3 - t2);
         // ---- answers (bridge.c:659-710)
         std::map<int, std::vector<size_t>> by_quality;
-        std::vector<size_t> raw;
+        std::vector<size_t> raw, png;
         for (size_t k = 0; k < n; k++) {
             Req& r = reqs[k];
             if (r.done) continue;
@@ -436,6 +438,7 @@ struct Worker {
             const uint64_t at = (r.q.in_bytes + 63) & ~uint64_t(63);
             s->out_w = impgpu_image_width(r.img); s->out_h = impgpu_image_height(r.img); s->out_c = impgpu_image_channels(r.img);
             s->out_offset = at;
+            r.out_at = at;
             if (r.q.out_kind == IMPB_OUT_INFO) {
                 r.step = IMP_STEP_INFO;
                 float b = 0;
@@ -456,6 +459,16 @@ struct Worker {
                 r.step = IMP_STEP_ENCODE;
                 if (at >= S.slot_bytes || S.slot_bytes - at < impgpu_jpeg_encode_bound(s->out_w, s->out_h, s->out_c)) { fail(r, IMP_ERROR_MALLOC_FAILED, IMP_STEP_ENCODE, "answer does not fit the slot"); continue; }
                 by_quality[r.q.quality].push_back(k);
+            } else if (r.q.out_kind == IMPB_OUT_PNG) {
+                r.step = IMP_STEP_ENCODE;
+                // levels 1..9 give one file (Z_RLE): every PNG answer of the batch goes into one call; the others are refused
+                // here exactly as impgpu_image_encode_png refuses them
+                if (r.q.quality == 0) { fail(r, IMP_ERROR_UNSUPPORTED, IMP_STEP_ENCODE, "PNG level 0 is encoded on the host"); continue; }
+                if (r.q.quality < 1 || r.q.quality > 9) { fail(r, IMP_ERROR_INVALID_ARGS, IMP_STEP_ENCODE, "PNG level outside 0..9"); continue; }
+                const size_t bound = impgpu_png_encode_bound(s->out_w, s->out_h, s->out_c);
+                if (!bound) { fail(r, IMP_ERROR_UNSUPPORTED, IMP_STEP_ENCODE, "frame the device does not encode as PNG"); continue; }
+                if (at >= S.slot_bytes || S.slot_bytes - at < bound) { fail(r, IMP_ERROR_MALLOC_FAILED, IMP_STEP_ENCODE, "answer does not fit the slot"); continue; }
+                png.push_back(k);
             } else {
                 r.step = IMP_STEP_ENCODE;
                 const uint64_t need = (uint64_t)impgpu_image_step(r.img) * (uint64_t)s->out_h;
@@ -487,6 +500,27 @@ struct Worker {
             const int rc = impgpu_batch_encode_jpeg(im.data(), (int)m, kv.first, outs.data(), caps.data(), lens.data(), cs.data());
             for (size_t j = 0; j < m; j++) {
                 Req& r = reqs[kv.second[j]];
+                const int c = rc != IMP_OK ? rc : cs[j];
+                if (c != IMP_OK) { fail(r, c, IMP_STEP_ENCODE, impgpu_last_error()); continue; }
+                S.slots[r.slot].f.out_bytes = lens[j];
+                r.code = IMP_OK; r.step = IMP_STEP_ENCODE; r.done = true;
+            }
+        }
+        if (!png.empty()) {
+            const size_t m = png.size();
+            std::vector<const impgpu_image*> im(m);
+            std::vector<unsigned char*> outs(m);
+            std::vector<size_t> caps(m), lens(m, 0);
+            std::vector<int> cs(m, IMP_OK);
+            for (size_t j = 0; j < m; j++) {
+                const Req& r = reqs[png[j]];
+                im[j] = r.img;
+                outs[j] = S.slot_data(r.slot) + r.out_at;
+                caps[j] = (size_t)(S.slot_bytes - r.out_at);
+            }
+            const int rc = impgpu_batch_encode_png(im.data(), (int)m, 9, outs.data(), caps.data(), lens.data(), cs.data());
+            for (size_t j = 0; j < m; j++) {
+                Req& r = reqs[png[j]];
                 const int c = rc != IMP_OK ? rc : cs[j];
                 if (c != IMP_OK) { fail(r, c, IMP_STEP_ENCODE, impgpu_last_error()); continue; }
                 S.slots[r.slot].f.out_bytes = lens[j];

@@ -164,6 +164,15 @@ class Image:
         rc = lib.impgpu_image_encode_jpeg(self.h, int(quality), buf.ctypes.data, cap, C.byref(n))
         return rc, (buf[: n.value].tobytes() if rc == 0 else None)
 
+    def encode_png(self, level=9):
+        """cvEncodeImage(".png", frame, {CV_IMWRITE_PNG_COMPRESSION, level}) (bridge.c:704) on the device -> (code, file bytes or None)."""
+        hh, ww, cc = self.shape
+        cap = lib.impgpu_png_encode_bound(ww, hh, cc)
+        buf = np.empty(max(1, cap), dtype=np.uint8)
+        n = C.c_size_t()
+        rc = lib.impgpu_image_encode_png(self.h, int(level), buf.ctypes.data, cap, C.byref(n))
+        return rc, (buf[: n.value].tobytes() if rc == 0 else None)
+
     def release(self):
         if self.h:
             lib.impgpu_image_release(C.byref(self.h))
@@ -436,6 +445,34 @@ def batch_encode_jpeg(images, quality=95):
     if rc:
         raise ImpError(rc, "impgpu_batch_encode_jpeg")
     return [(codes[i], bufs[i][: lens[i]].tobytes() if codes[i] == 0 else None) for i in range(n)]
+
+
+def batch_encode_png(images, level=9):
+    """impgpu_batch_encode_png -> [(code, file bytes or None)] in the order of `images`."""
+    n = len(images)
+    hs = (C.c_void_p * n)(*[im.h.value for im in images])
+    caps = [lib.impgpu_png_encode_bound(im.shape[1], im.shape[0], im.shape[2]) for im in images]
+    bufs = [np.empty(max(1, c), dtype=np.uint8) for c in caps]
+    outs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+    ccaps = (C.c_size_t * n)(*caps)
+    lens = (C.c_size_t * n)()
+    codes = (C.c_int * n)()
+    rc = lib.impgpu_batch_encode_png(hs, n, int(level), outs, ccaps, lens, codes)
+    if rc:
+        raise ImpError(rc, "impgpu_batch_encode_png")
+    return [(codes[i], bufs[i][: lens[i]].tobytes() if codes[i] == 0 else None) for i in range(n)]
+
+
+def png_deflate(data):
+    """impgpu_png_deflate (host, no device): the zlib stream libpng writes for these filtered scanlines -> (code, bytes)."""
+    data = bytes(data)
+    n = C.c_size_t()
+    rc = lib.impgpu_png_deflate(data, len(data), None, 0, C.byref(n))
+    if rc not in (0, IMP_ERROR_MALLOC_FAILED):
+        return rc, None
+    buf = np.empty(max(1, n.value), dtype=np.uint8)
+    rc = lib.impgpu_png_deflate(data, len(data), buf.ctypes.data, n.value, C.byref(n))
+    return rc, (buf[: n.value].tobytes() if rc == 0 else None)
 
 
 def jpeg_info(blob):
