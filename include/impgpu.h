@@ -299,6 +299,17 @@ void  impgpu_jpeg_sync_stats(int stats[8]);
  * impgpu_png_stage_times: the calling thread's last decode, host clock, microseconds: [0] header, [1] chunk walk + CRC +
  * inflate, [2] filter-type check + enqueue (upload, kernel); [3] = bytes of filtered scanlines. */
 int   impgpu_image_decode_png(const unsigned char* blob, size_t size, impgpu_image** out);
+/* Many PNG files in one call (count <= 256): codes[i] / images[i] are what impgpu_image_decode_png(blobs[i], sizes[i]) returns
+ * alone -- the same pixels, refusals and damage verdicts; a refused or damaged file changes no other file's result.  The headers
+ * are read on the calling thread, the accepted files are inflated side by side (the helper threads the JPEG batch uses) into
+ * one pinned buffer, uploaded once, and ONE k_png_unfilter_batch launch per channel count present (1 / 3 / 4) unfilters them,
+ * a workgroup per file.  Files whose scanlines together exceed IMPGPU_STAGE_CAP_MB go in groups, in file order, each of
+ * its own upload and launches.  *launches (may be NULL) = the kernels the call launched: no copy or fill kernels, so at most
+ * one per channel count and group.  The blobs are not read after the call returns; it does not wait for the device.
+ * IMP_ERROR_INVALID_ARGS = a NULL array or count outside 0..256 (before any device is looked for); IMP_ERROR_DEVICE =
+ * impgpu_env_start has not been called.  impgpu_png_stage_times keeps describing the thread's last single-file decode. */
+int   impgpu_batch_decode_png(const unsigned char* const* blobs, const size_t* sizes, int count,
+                              impgpu_image** images, int* codes, int* launches);
 int   impgpu_png_info(const unsigned char* blob, size_t size, int* width, int* height, int* channels);
 int   impgpu_png_stage_times(double* microseconds, int n);
 /* Diagnostics (host, no device): the filtered scanlines of the file -- height rows of (1 filter byte + width * channels bytes),

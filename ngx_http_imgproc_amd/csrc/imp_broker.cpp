@@ -261,7 +261,9 @@ struct Worker {
     // scratch reused from batch to batch
     std::vector<impgpu_image*> imgs;
     std::vector<int> codes, steps;
-    std::vector<size_t> live;
+    std::vector<size_t> live, pngs;
+    std::vector<const unsigned char*> png_blobs;
+    std::vector<size_t> png_sizes;
     std::vector<impgpu_job> jobs;
     std::vector<const impgpu_config*> cfgs;
 
@@ -376,18 +378,38 @@ struct Worker {
                 else fail(r, c, IMP_STEP_DECODE, impgpu_last_error());
             }
         }
+        // every PNG file of the batch in one call (after the JPEG verdicts: both are on the lane's stream, and the PNG call's
+        // inflates could overlap the JPEG kernels if issued before _finish -- not done, DESIGN.md section 8 says why)
+        pngs.clear();
+        for (size_t k = 0; k < n; k++) {
+            const Req& r = reqs[k];
+            if (!r.done && !r.img && r.q.in_kind == IMPB_IN_FILE && is_png(r.in, r.q.in_bytes)) pngs.push_back(k);
+        }
+        if (!pngs.empty()) {
+            const size_t m = pngs.size();
+            png_blobs.resize(m);
+            png_sizes.resize(m);
+            imgs.assign(m, nullptr);
+            codes.assign(m, IMP_OK);
+            for (size_t j = 0; j < m; j++) {
+                png_blobs[j] = reqs[pngs[j]].in;
+                png_sizes[j] = (size_t)reqs[pngs[j]].q.in_bytes;
+            }
+            const int rc = impgpu_batch_decode_png(png_blobs.data(), png_sizes.data(), (int)m, imgs.data(), codes.data(), nullptr);
+            for (size_t j = 0; j < m; j++) {
+                Req& r = reqs[pngs[j]];
+                const int c = rc != IMP_OK ? rc : codes[j];
+                if (c == IMP_OK) { r.img = imgs[j]; continue; }
+                if (c == IMP_ERROR_UNSUPPORTED || c == IMP_ERROR_DECODE_FAILED) fail(r, IMPB_NOT_TAKEN, IMP_STEP_DECODE, "not a file the device decodes");
+                else fail(r, c, IMP_STEP_DECODE, impgpu_last_error());
+            }
+        }
         for (size_t k = 0; k < n; k++) {
             Req& r = reqs[k];
             if (r.done || r.img) continue;
             int rc = IMP_OK;
-            if (r.q.in_kind == IMPB_IN_FILE) {
-                if (is_png(r.in, r.q.in_bytes)) {
-                    rc = impgpu_image_decode_png(r.in, (size_t)r.q.in_bytes, &r.img);
-                    if (rc == IMP_ERROR_UNSUPPORTED || rc == IMP_ERROR_DECODE_FAILED) { fail(r, IMPB_NOT_TAKEN, IMP_STEP_DECODE, "not a file the device decodes"); continue; }
-                } else { fail(r, IMPB_NOT_TAKEN, IMP_STEP_DECODE, "neither JPEG nor PNG"); continue; }
-            } else {
-                rc = impgpu_image_upload(r.in, r.q.in_w, r.q.in_h, r.q.in_c, r.q.in_step, &r.img);
-            }
+            if (r.q.in_kind == IMPB_IN_FILE) { fail(r, IMPB_NOT_TAKEN, IMP_STEP_DECODE, "neither JPEG nor PNG"); continue; }
+            rc = impgpu_image_upload(r.in, r.q.in_w, r.q.in_h, r.q.in_c, r.q.in_step, &r.img);
             if (rc != IMP_OK) { fail(r, rc, IMP_STEP_DECODE, impgpu_last_error()); continue; }
             if (r.q.in_kind == IMPB_IN_WATERMARK) {             // PrepareWatermark (bridge.c:199-237): kept, answered with its id
                 std::lock_guard<std::mutex> lk(g_marks.mu);

@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include "imp_host_pool.h"
 #include "imp_jpeg_core.h"
 
 using namespace imp;
@@ -135,85 +136,6 @@ void group_release(Group& G) {
     G.d_words = G.d_coef = G.d_side = G.d_ctl = G.d_work = nullptr;
     if (G.slot >= 0) { t_slots_busy &= ~(1u << G.slot); g_groups_in_flight.fetch_sub(1, std::memory_order_relaxed); }
     G.slot = -1;
-}
-
-// ---- a few helper threads for the host's per-file work of a BATCH (never started by single-file calls)
-class HostPool {
-public:
-    // (never destroyed: its threads sleep on the condition variable for life, and destroying a condition variable that has
-    // waiters blocks -- a static instance made every process that had run a batch hang in its exit handlers)
-    static HostPool& get() { static HostPool* p = new HostPool(); return *p; }
-    int helpers() const { return (int)threads_.size(); }
-    // runs fn(items[k]) for every k, the caller taking part; returns when all are done
-    template <class Fn>
-    void run(const std::vector<int>& items, Fn& fn) {
-        std::atomic<size_t> next{0}, done{0};
-        const size_t n = items.size();
-        auto work = [&]() {
-            for (;;) {
-                const size_t k = next.fetch_add(1, std::memory_order_relaxed);
-                if (k >= n) break;
-                fn(items[k]);
-                done.fetch_add(1, std::memory_order_release);
-            }
-        };
-        std::function<void()> job = work;
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            const int want = (int)std::min<size_t>(threads_.size(), n > 1 ? n - 1 : 0);
-            for (int i = 0; i < want; i++) queue_.push_back(&job);
-        }
-        cv_.notify_all();
-        work();
-        // helpers that took the job but found nothing left have touched nothing of ours; those in the middle of an item are waited for
-        while (done.load(std::memory_order_acquire) < n) std::this_thread::yield();
-        std::unique_lock<std::mutex> lk(mu_);
-        for (auto it = queue_.begin(); it != queue_.end();) it = (*it == &job) ? queue_.erase(it) : it + 1;
-        idle_.wait(lk, [&] { return running_ == 0 || !uses(&job); });
-    }
-private:
-    HostPool() {
-        const char* s = std::getenv("IMPGPU_HOST_THREADS");
-        unsigned hw = std::thread::hardware_concurrency();
-        int n = s ? std::atoi(s) : (int)std::min(3u, hw / 8);              // helpers beside the caller
-        if (n < 0) n = 0;
-        if (n > 15) n = 15;
-        for (int i = 0; i < n; i++) threads_.emplace_back([this] { loop(); });
-        for (auto& t : threads_) t.detach();
-    }
-    bool uses(std::function<void()>* j) const { for (auto* c : current_) if (c == j) return true; return false; }
-    void loop() {
-        for (;;) {
-            std::function<void()>* job = nullptr;
-            {
-                std::unique_lock<std::mutex> lk(mu_);
-                cv_.wait(lk, [&] { return !queue_.empty(); });
-                job = queue_.front();
-                queue_.pop_front();
-                current_.push_back(job);
-                running_++;
-            }
-            (*job)();
-            {
-                std::lock_guard<std::mutex> lk(mu_);
-                running_--;
-                for (auto it = current_.begin(); it != current_.end(); ++it) if (*it == job) { current_.erase(it); break; }
-            }
-            idle_.notify_all();
-        }
-    }
-    std::mutex mu_;
-    std::condition_variable cv_, idle_;
-    std::deque<std::function<void()>*> queue_;
-    std::vector<std::function<void()>*> current_;
-    std::vector<std::thread> threads_;
-    int running_ = 0;
-};
-
-template <class Fn>
-void host_parallel(const std::vector<int>& items, size_t bytes, Fn& fn) {
-    if (items.size() >= 4 && bytes >= (size_t(256) << 10) && HostPool::get().helpers() > 0) HostPool::get().run(items, fn);
-    else for (int i : items) fn(i);
 }
 
 // Everything up to the last enqueue: headers, the unstuffing copy (or the host's entropy decoding), job tables, uploads,

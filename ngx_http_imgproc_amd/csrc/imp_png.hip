@@ -17,6 +17,7 @@
 // IMP_ERROR_UNSUPPORTED (decode with cvDecodeImage as before); a damaged file is IMP_ERROR_DECODE_FAILED.
 #include <chrono>
 #include <cstring>
+#include "imp_host_pool.h"
 #include "imp_internal.h"
 #include "imp_png.h"
 
@@ -106,8 +107,11 @@ __device__ __forceinline__ uint4 png_prev_group(const uint8_t* prev, int g) {
     }
 }
 
-template <int BPP>
-__global__ __launch_bounds__(PNG_WAVES * 64) void k_png_unfilter(const PngJob J) {
+// One workgroup of PNG_WAVES waves walks rows [0, J.h) of one job; s_png: png_lds_bytes(J.w, J.h) of dynamic LDS.  SLICED: the
+// job may be a slice whose first row reads the row above from J.prev (a single-file decode that streams its rows); a job of
+// the batch kernel is always a whole file, and the code that would read J.prev is not compiled there.
+template <int BPP, bool SLICED>
+__device__ __forceinline__ void png_unfilter_body(const PngJob J) {
     extern __shared__ uint4 s_png[];
     const int G = (J.w + 3) >> 2;                                    // groups of 4 pixels per row
     const int nbands = (J.h + 63) >> 6;
@@ -144,7 +148,7 @@ __global__ __launch_bounds__(PNG_WAVES * 64) void k_png_unfilter(const PngJob J)
             for (int i = 0; i <= NW; i++) nxt[i] = wp[g0 * NW + i];
         }
         uint4 pe = make_uint4(0, 0, 0, 0);                           // band 0 of a slice: lane 0's next group of the row above
-        if (band == 0 && J.prev != nullptr && lane == 0) pe = png_prev_group<BPP>(J.prev, 0);
+        if (SLICED && band == 0 && J.prev != nullptr && lane == 0) pe = png_prev_group<BPP>(J.prev, 0);
         const int steps = G + 63;
         for (int S = 0; S < steps; S++) {
             const int g = S - lane;
@@ -180,7 +184,7 @@ __global__ __launch_bounds__(PNG_WAVES * 64) void k_png_unfilter(const PngJob J)
             // the row above: the previous band's last row for lane 0 (LDS; for the first band of a slice the row the slice before
             // left in the image, fetched one step ahead), the lane above for everyone else
             uint4 e = make_uint4(0, 0, 0, 0);
-            if (band == 0 && J.prev != nullptr) {
+            if (SLICED && band == 0 && J.prev != nullptr) {
                 e = pe;
                 if (lane == 0) pe = png_prev_group<BPP>(J.prev, S + 1 < G ? S + 1 : G - 1);
             }
@@ -244,6 +248,20 @@ __global__ __launch_bounds__(PNG_WAVES * 64) void k_png_unfilter(const PngJob J)
     }
 }
 
+template <int BPP>
+__global__ __launch_bounds__(PNG_WAVES * 64) void k_png_unfilter(const PngJob J) {
+    png_unfilter_body<BPP, true>(J);
+}
+
+// impgpu_batch_decode_png: workgroup b walks the whole of file jobs[b] (prev is null: a batch never slices a file).  The
+// dynamic LDS is sized for the widest / tallest file of the launch (png_lds_bytes, at most 129 KB of the CU's 160 KB), so a
+// CU may hold only one of these workgroups; a launch has at most 256 of them (one per file of a call) and the MI355X has 256 CUs (8
+// XCDs x 32), so every file still gets a CU of its own -- the LDS of the largest file costs the launch no concurrency.
+template <int BPP>
+__global__ __launch_bounds__(PNG_WAVES * 64) void k_png_unfilter_batch(const PngJob* __restrict__ jobs) {
+    png_unfilter_body<BPP, false>(jobs[blockIdx.x]);
+}
+
 static size_t png_lds_bytes(int w, int h) { return (size_t)PNG_WAVES * ((w + 3) / 4) * 16 + (size_t)((h + 63) / 64) * 4; }
 
 static int launch_png_unfilter(const PngJob& job, int bpp, hipStream_t s) {
@@ -265,6 +283,101 @@ static int launch_png_unfilter(const PngJob& job, int bpp, hipStream_t s) {
     return IMP_OK;
 }
 
+// `count` whole files of `bpp` channels, their descriptors already in device memory: ONE launch of count workgroups
+static int launch_png_unfilter_batch(const PngJob* djobs, int count, size_t lds, int bpp, hipStream_t s) {
+    hipError_t e = hipSuccess;
+#define PNG_LAUNCH(BPP_)                                                                                                      \
+    do {                                                                                                                      \
+        e = lds_limit_once<k_png_unfilter_batch<BPP_>>();                                                                     \
+        if (e == hipSuccess) {                                                                                                \
+            hipLaunchKernelGGL(k_png_unfilter_batch<BPP_>, dim3(count), dim3(PNG_WAVES * 64), lds, s, djobs);                 \
+            e = hipGetLastError();                                                                                            \
+        }                                                                                                                     \
+    } while (0)
+    if (bpp == 4) PNG_LAUNCH(4);
+    else if (bpp == 3) PNG_LAUNCH(3);
+    else PNG_LAUNCH(1);
+#undef PNG_LAUNCH
+    if (e != hipSuccess) { set_error("k_png_unfilter_batch", e); return IMP_ERROR_DEVICE; }
+    return IMP_OK;
+}
+
+// ---- impgpu_batch_decode_png: many files, one set of launches
+constexpr int PNG_MAX_BATCH = 256;
+constexpr size_t PNG_REGION_ALIGN = 256;    // a file's scanlines start on this boundary of the staging buffer (and its device copy)
+
+namespace {
+struct PngBatchFile {
+    PngHeader H;
+    size_t raw = 0, off = 0;                 // scanline bytes; their region in the group's buffer
+};
+}  // namespace
+
+// What the summed scanlines of one group may take: the staging cap (IMPGPU_STAGE_CAP_MB, imp_runtime.hip) that the lane's
+// pinned buffers are trimmed to.  A file larger than that alone is a group of its own.
+static size_t png_group_cap() {
+    static const size_t cap = [] {
+        const char* s = std::getenv("IMPGPU_STAGE_CAP_MB");
+        const size_t mb = (size_t)(s ? std::atoll(s) : 512);
+        return (mb ? mb : 512) << 20;
+    }();
+    return cap;
+}
+
+// Files idx[0..n) (all accepted by their headers), one staging buffer: the inflates side by side on the host helper pool, one
+// upload, the frames, one k_png_unfilter_batch launch per channel count present.  Sets codes[] / images[] of its files; a
+// non-zero return is a device error that ends the call.
+static int png_group(const unsigned char* const* blobs, const size_t* sizes, std::vector<PngBatchFile>& F, const std::vector<int>& idx,
+                     impgpu_image** images, int* codes) {
+    size_t total = 0;
+    for (int i : idx) {
+        F[(size_t)i].off = total;
+        total += (F[(size_t)i].raw + PNG_RAW_SLACK + PNG_REGION_ALIGN - 1) / PNG_REGION_ALIGN * PNG_REGION_ALIGN;
+    }
+    void *host = nullptr, *token = nullptr;
+    int rc = stage_begin(total, &host, &token);
+    if (rc) return rc;
+    uint8_t* hb = (uint8_t*)host;
+    auto inflate = [&](int i) {
+        PngBatchFile& f = F[(size_t)i];
+        std::memset(hb + f.off + f.raw, 0, PNG_RAW_SLACK);
+        codes[i] = png_scanlines(blobs[i], sizes[i], f.H, hb + f.off);
+    };
+    host_parallel(idx, total, inflate);
+    void* dev = nullptr;
+    rc = dev_alloc(total, &dev);
+    if (rc) { (void)stage_upload(token, nullptr, 0); return rc; }
+    rc = stage_upload(token, dev, total);
+    if (rc) { dev_free(dev); return rc; }
+    std::vector<PngJob> jobs[5];
+    size_t lds[5] = {0, 0, 0, 0, 0};
+    for (int i : idx) {
+        if (codes[i] != IMP_OK) continue;
+        const PngBatchFile& f = F[(size_t)i];
+        impgpu_image* im = nullptr;
+        codes[i] = image_new(f.H.w, f.H.h, f.H.bpp, &im);
+        if (codes[i] != IMP_OK) continue;
+        images[i] = im;
+        jobs[f.H.bpp].push_back(PngJob{(const uint8_t*)dev + f.off, im->d, nullptr, f.H.w, f.H.h, im->step});
+        lds[f.H.bpp] = std::max(lds[f.H.bpp], png_lds_bytes(f.H.w, f.H.h));
+    }
+    hipStream_t s = env_stream();
+    for (int bpp : {1, 3, 4}) {
+        if (jobs[bpp].empty() || rc) continue;
+        void* djobs = nullptr;
+        rc = upload_small(jobs[bpp].data(), jobs[bpp].size() * sizeof(PngJob), &djobs, s);
+        if (!rc) {
+            rc = launch_png_unfilter_batch((const PngJob*)djobs, (int)jobs[bpp].size(), lds[bpp], bpp, s);
+            dev_free(djobs);                                         // (handed out again in lane-stream order)
+        }
+    }
+    dev_free(dev);
+    if (rc)
+        for (int i : idx)
+            if (images[i]) { image_delete(images[i]); images[i] = nullptr; }
+    return rc;
+}
+
 static thread_local double t_png_us[4] = {0, 0, 0, 0};
 
 static double png_now_us() {
@@ -281,6 +394,50 @@ int impgpu_png_stage_times(double* microseconds, int n) {
     if (!microseconds || n < 0) return IMP_ERROR_INVALID_ARGS;
     for (int i = 0; i < n; i++) microseconds[i] = i < 4 ? t_png_us[i] : 0.0;
     return IMP_OK;
+}
+
+int impgpu_batch_decode_png(const unsigned char* const* blobs, const size_t* sizes, int count, impgpu_image** images, int* codes,
+                            int* launches) {
+    if (!blobs || !sizes || !images || !codes || count < 0 || count > PNG_MAX_BATCH) return IMP_ERROR_INVALID_ARGS;
+    if (launches) *launches = 0;
+    if (!env_ready()) { set_error_text("impgpu_env_start has not been called"); return IMP_ERROR_DEVICE; }
+    if (count == 0) return IMP_OK;
+    const unsigned long long launched = t_launches;
+    TraceRange tr("IMP_STEP_DECODE");
+    IMP_FAULT_POINT(IMP_STEP_DECODE);
+    // headers on the calling thread: what impgpu_image_decode_png refuses before it stages anything is refused here alike
+    std::vector<PngBatchFile> F((size_t)count);
+    std::vector<int> taken;
+    for (int i = 0; i < count; i++) {
+        images[i] = nullptr;
+        PngBatchFile& f = F[(size_t)i];
+        codes[i] = png_header(blobs[i], sizes[i], &f.H);
+        if (codes[i]) continue;
+        if (!f.H.taken) { codes[i] = IMP_ERROR_UNSUPPORTED; continue; }
+        f.raw = ((size_t)f.H.w * f.H.bpp + 1) * f.H.h;
+        if (f.raw / 1032 > sizes[i]) { codes[i] = IMP_ERROR_DECODE_FAILED; continue; }
+        taken.push_back(i);
+    }
+    // groups in file order, each within the staging cap
+    const size_t cap = png_group_cap();
+    int rc = IMP_OK;
+    for (size_t a = 0; a < taken.size() && !rc;) {
+        std::vector<int> idx;
+        size_t bytes = 0;
+        for (; a < taken.size(); a++) {
+            const size_t need = F[(size_t)taken[a]].raw + PNG_RAW_SLACK + PNG_REGION_ALIGN;
+            if (!idx.empty() && bytes + need > cap) break;
+            idx.push_back(taken[a]);
+            bytes += need;
+        }
+        rc = png_group(blobs, sizes, F, idx, images, codes);
+        if (rc) {                                                    // (a device error: no frame of this group or a later one)
+            for (int i : idx) if (codes[i] == IMP_OK) codes[i] = rc;
+            for (size_t b = a; b < taken.size(); b++) codes[taken[b]] = rc;
+        }
+    }
+    if (launches) *launches = (int)(t_launches - launched);
+    return rc;
 }
 
 int impgpu_image_decode_png(const unsigned char* blob, size_t size, impgpu_image** out) {

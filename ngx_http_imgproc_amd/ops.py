@@ -323,6 +323,21 @@ def batch_decode_jpeg(blobs):
     return [(codes[i], Image(handle=imgs[i]) if codes[i] == 0 else None) for i in range(n)]
 
 
+def batch_decode_png(blobs):
+    """impgpu_batch_decode_png -> ([(code, Image or None)] in the order of `blobs`, kernel launches of the call)."""
+    n = len(blobs)
+    keep = [bytes(b) for b in blobs]
+    arr = (C.c_char_p * max(1, n))(*keep)
+    sizes = (C.c_size_t * max(1, n))(*[len(b) for b in keep])
+    imgs = (C.c_void_p * max(1, n))()
+    codes = (C.c_int * max(1, n))()
+    launches = C.c_int()
+    rc = lib.impgpu_batch_decode_png(arr, sizes, n, imgs, codes, C.byref(launches))
+    if rc:
+        raise ImpError(rc, "impgpu_batch_decode_png")
+    return [(codes[i], Image(handle=imgs[i]) if codes[i] == 0 else None) for i in range(n)], launches.value
+
+
 def jpeg_unstuff(blob):
     """impgpu_jpeg_unstuff of libimpgpu_client.so (what a worker does on the way into its slot) -> (head, scan) or None when
     the file is to go as it is."""

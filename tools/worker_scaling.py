@@ -21,8 +21,10 @@ sys.path.insert(0, ROOT)
 HARNESS = os.path.join(ROOT, "tests", "c", "_build", "worker_harness")
 # Other requests than resize=224,0 (broker only): --query takes a query string (impgpu_parse_request), --watermark the location's
 # placement gx,gy,ox,oy,opacity of a fixed 96 x 32 BGRA overlay; the workers are then tools/request_worker.c.  --check writes the
-# oracle's answers for the pool and that request first, and every answer is compared with them.
+# oracle's answers for the pool and that request first, and every answer is compared with them.  --pool png sends the same
+# files as PNG uploads (the broker decodes a batch's PNG files in one impgpu_batch_decode_png call).
 #     python tools/worker_scaling.py broker 1 8 16 32 --query "crop=16,9&resize=224,0" --watermark r,b,6,4,70 --check
+#     python tools/worker_scaling.py broker 16 32 --pool png --check
 REQUEST_WORKER = os.path.join(ROOT, "tools", "_build", "request_worker")
 BROKER = os.path.join(ROOT, "ngx_http_imgproc_amd", "impgpu_broker")
 
@@ -41,6 +43,23 @@ def make_pool(path, n_files=64):
     import bench
 
     write_pool(path, [b for _, _, b in bench.jpeg_pool(n_files)])
+
+
+def make_png_pool(path, n_files=64):
+    """The same files as make_pool's, as PNG (RGB, Pillow's default level): PNG uploads through the broker."""
+    if os.path.exists(path):
+        return
+    import io
+
+    import bench
+    from PIL import Image
+
+    blobs = []
+    for _, _, jpeg in bench.jpeg_pool(n_files):
+        b = io.BytesIO()
+        Image.open(io.BytesIO(jpeg)).convert("RGB").save(b, "PNG")
+        blobs.append(b.getvalue())
+    write_pool(path, blobs)
 
 
 def start_broker(name, threads, gather_us, slots=64, extra=(), env=None):
@@ -111,7 +130,7 @@ def oracle_answers(pool, query, placement, path):
         at += 4 + sz
     answers = []
     for b in blobs:
-        rc, cur = orc.jpeg_decode(b)
+        rc, cur = orc.png_decode(b) if b[:8] == b"\x89PNG\r\n\x1a\n" else orc.jpeg_decode(b)
         assert rc == 0
         if req.crop is not None:
             rc, cur = orc.crop(cur, req.crop, req.gravity)
@@ -192,8 +211,16 @@ def main():
     ap.add_argument("--watermark", default=None, metavar="GX,GY,OX,OY,OPACITY", help="a location watermark with this placement")
     ap.add_argument("--check", action="store_true", help="with --query: compare every answer with the oracle's file")
     args = ap.parse_args()
-    os.makedirs(os.path.dirname(args.pool), exist_ok=True)
-    make_pool(args.pool)
+    if args.pool == "png":               # the same 64 files as PNG uploads (broker only, through --query's worker)
+        if args.mode != "broker":
+            ap.error("--pool png: broker mode only (the direct worker decodes JPEG)")
+        args.pool = os.path.join(os.path.dirname(ap.get_default("pool")), "png_pool.bin")   # (beside the JPEG pool)
+        args.query = args.query if args.query is not None else "resize=224,0"
+        os.makedirs(os.path.dirname(args.pool), exist_ok=True)
+        make_png_pool(args.pool)
+    else:
+        os.makedirs(os.path.dirname(args.pool), exist_ok=True)
+        make_pool(args.pool)
     overlay = None
     if args.query is not None or args.watermark:
         if args.mode != "broker":
