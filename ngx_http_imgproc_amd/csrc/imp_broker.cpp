@@ -4,8 +4,10 @@
 //
 // Every broker thread is a lane of libimpgpu.so (its own stream, pools, pinned staging).  A thread takes ALL requests that
 // are queued when it looks (up to --batch), so the number of files per launch follows the load by itself: one idle worker
-// gets a batch of one (the latency of the in-process path plus two futex hops), 32 busy workers ride 16-32 to a launch --
-//     files          impgpu_batch_decode_jpeg            cvDecodeImage, bridge.c:545-552
+// gets a batch of one (the latency of the in-process path plus two futex hops), 32 busy workers ride 16-32 to a launch.
+// A batch is one straight pass: take, prepare, decode, operators, answers, finish --
+//     files          impgpu_batch_decode_jpeg_prepared   cvDecodeImage, bridge.c:545-552
+//                    impgpu_batch_decode_png
 //     operators      impgpu_batch_run_ops                bridge.c:574-656: crop -> resize -> rotate -> watermark -> flatten
 //                                                        chains share one launch per channel count; anything else runs
 //                                                        request by request (impgpu_run_ops) inside the same call
@@ -13,9 +15,10 @@
 //     PNG answers    impgpu_batch_encode_png             cvEncodeImage(".png"), bridge.c:704
 //     pixel answers  impgpu_batch_download               for the host encoders (PNG, WebP, FreeImage formats)
 // Nothing a worker writes into its slot is trusted further than a request is: the request record is copied out of shared
-// memory once and validated (sizes against the slot, offsets against the text area, frame geometry against the bytes).
+// memory once and validated (sizes against the slot, offsets against the text area, frame geometry against the bytes), and
+// the answer's placement is the broker's own: it is written to the slot for the worker and never read back from there.
 //
-//   impgpu_broker [--name /impgpu-broker-0] [--device 0] [--slots 64] [--slot-mb 32] [--register-mb 8] [--pipeline 1] [--threads 2] [--batch 64]
+//   impgpu_broker [--name /impgpu-broker-0] [--device 0] [--slots 64] [--slot-mb 32] [--register-mb 8] [--threads 2] [--batch 64]
 //                 [--gather-us 0] [--supervise] [--ready-file PATH]
 // --supervise: this process only forks and watches; the child is the broker.  A child that dies (a lost device, a bug) is
 // replaced by a FRESH child -- fork() from a parent that never touched the GPU, no exec of a process that did.
@@ -50,13 +53,11 @@ struct Options {
     int slots = 64;
     long slot_mb = 32;
     long register_mb = 8;               // page-locked at the front of every slot (0: none)
-    // --pipeline 1: a lane unpacks the next batch while the device writes the answers of the one before (Batch, below).  Measured
-    // (one box, four lanes, requests/s at 8 / 16 / 32 workers): 11.5 / 15.6 / 21.1 k against 11.7 / 16.7 / 23.0 k one batch at a time.
+    // (Measured and removed: a lane that unpacks the next batch while the device writes the answers of the one before -- one
+    // box, four lanes, requests/s at 8 / 16 / 32 workers: 11.5 / 15.6 / 21.1 k against 11.7 / 16.7 / 23.0 k one batch at a time.
     // The device idles less, and it does not matter: with N synchronous workers the rate is N / latency, and a request whose
-    // lane also unpacks its successor and hands out its predecessor waits longer for its own answer.  It pays with a backlog
-    // (a caller that keeps many requests in flight per connection); IMP's workers do not have one.
-    bool pipeline = false;
-    long split_kb = 0;
+    // lane also unpacks its successor and hands out its predecessor waits longer for its own answer.  Launches of one size
+    // class only: DESIGN.md section 6.)
     // (Also measured and not kept: the frames taken ahead of their verdicts -- impgpu_batch_decode_jpeg_pending -- so that a batch's
     // operators and answers are enqueued behind its decode and the lane waits once.  From C, in process, a lone request gains 8-11 us
     // (tests/c/latency_harness.c); through the broker a lone worker's request is level (p50 0.36 ms both ways) and under load the
@@ -175,7 +176,12 @@ struct Req {
     impgpu_job job{};
     impgpu_config cfg{};
     double t_taken = 0;
-    uint64_t out_at = 0;                // where the answer goes in the slot's data area (kept here: the slot is shared memory)
+    // the answer, copied into the slot by finish() (the slot is shared memory: nothing here is read back from it)
+    uint64_t out_offset = 0, out_bytes = 0;
+    uint64_t cap = 0;                   // bytes from out_offset to the end of the slot's data area (0: none)
+    int32_t out_w = 0, out_h = 0, out_c = 0, out_step = 0;
+    float brightness = 0;
+    bool fits(uint64_t need) const { return cap > 0 && cap >= need; }
 };
 
 struct Watermarks {
@@ -237,31 +243,16 @@ bool is_png(const uint8_t* p, uint64_t n) {
     return n >= 8 && !std::memcmp(p, sig, 8);
 }
 
-// A batch on its way through a lane.  Its three steps -- begin (copy the records, enqueue the JPEG decode), middle (read the
-// verdicts, operators, enqueue the answers' encode), end (fetch the files, wake the workers) -- are separate because the lane
-// runs them INTERLEAVED with the next batch's: while the device writes batch k's answers the thread unpacks batch k + 1 and
-// puts its decode behind them on the same stream, and while that decode runs it hands batch k's files out.  One lane, one
-// stream, no second hardware queue (more than four queues in use slow every kernel on them: tools/contention_probe.sh).
-struct Batch {
-    std::vector<Req> reqs;
-    std::vector<size_t> who;                    // requests whose JPEG rides the batch's decode
-    std::vector<impgpu_jpeg_prepared> pre;
-    impgpu_jpeg_batch* dec = nullptr;           // begun, not finished
-    impgpu_jpeg_encode* enc = nullptr;          // the answers of ONE quality, begun and not fetched
-    std::vector<size_t> enc_who;
-    std::vector<const impgpu_image*> enc_im;
-    bool live = false;
-};
-
 struct Worker {
     const Segment& S;
     const Options& O;
     int id;
-    Batch slots_[2];
     // scratch reused from batch to batch
+    std::vector<Req> reqs;
     std::vector<impgpu_image*> imgs;
     std::vector<int> codes, steps;
-    std::vector<size_t> live, pngs;
+    std::vector<size_t> jpegs, pngs, live;
+    std::vector<impgpu_jpeg_prepared> pre;
     std::vector<const unsigned char*> png_blobs;
     std::vector<size_t> png_sizes;
     std::vector<impgpu_job> jobs;
@@ -269,22 +260,13 @@ struct Worker {
 
     Worker(const Segment& s, const Options& o, int i) : S(s), O(o), id(i) {}
 
-    // --split-kb K (A/B): a launch takes files of ONE size class -- up to K KB, or above -- so that a small file does not wait
-    // for the decode of a large one it happens to share a launch with (a launch's kernels take what its longest file takes)
-    int klass_ = -1;
     int take(std::vector<int>& mine, int start) {
         const int n = (int)S.h->nslots;
         int got = 0;
-        if (mine.empty()) klass_ = -1;
         for (int k = 0; k < n && (int)mine.size() < O.batch; k++) {
             const int i = (start + k) % n;
             impb_slot_fields* s = &S.slots[i].f;
             if (aload(&s->state) != IMPB_SUBMITTED) continue;
-            if (O.split_kb > 0) {
-                const int kl = s->in_bytes > ((uint64_t)O.split_kb << 10) ? 1 : 0;
-                if (klass_ >= 0 && kl != klass_) continue;
-                klass_ = kl;
-            }
             uint32_t expect = IMPB_SUBMITTED;
             if (__atomic_compare_exchange_n(&s->state, &expect, (uint32_t)IMPB_TAKEN, false, __ATOMIC_ACQ_REL, __ATOMIC_RELAXED)) {
                 mine.push_back(i);
@@ -294,9 +276,13 @@ struct Worker {
         return got;
     }
 
-    void finish(Req& r) {
+    void finish(Req& r, int batch_size) {
         impb_slot_fields* s = &S.slots[r.slot].f;
         s->code = r.code; s->step = r.step;
+        s->out_offset = r.out_offset; s->out_bytes = r.out_bytes;
+        s->out_w = r.out_w; s->out_h = r.out_h; s->out_c = r.out_c; s->out_step = r.out_step;
+        s->brightness = r.brightness;
+        s->batch_size = (int32_t)batch_size;
         std::snprintf(s->error, sizeof s->error, "%s", r.err.c_str());
         s->broker_us = (uint32_t)(now_us() - r.t_taken);
         impgpu_image_release(&r.img);
@@ -306,11 +292,48 @@ struct Worker {
         futex(&s->state, FUTEX_WAKE, 1, nullptr);
     }
 
-    void begin(Batch& B, const std::vector<int>& mine) {
-        std::vector<Req>& reqs = B.reqs;
+    // A decode call's verdicts: a file the device does not take goes back to the worker as NOT_TAKEN.
+    void decoded(const std::vector<size_t>& who, int rc) {
+        for (size_t j = 0; j < who.size(); j++) {
+            Req& r = reqs[who[j]];
+            const int c = rc != IMP_OK ? rc : codes[j];
+            if (c == IMP_OK) { r.img = imgs[j]; continue; }
+            if (c == IMP_ERROR_UNSUPPORTED || c == IMP_ERROR_DECODE_FAILED) fail(r, IMPB_NOT_TAKEN, IMP_STEP_DECODE, "not a file the device decodes");
+            else fail(r, c, IMP_STEP_DECODE, impgpu_last_error());
+        }
+    }
+
+    // One batched answer call for the requests `who`, from their placement in Req: call(images, count, outs, capacities,
+    // steps, lengths, codes) -> IMP_*.  An answer that came back goes out with its length, a failure with the library's error.
+    template <class Call>
+    void answer(const std::vector<size_t>& who, Call call) {
+        const size_t m = who.size();
+        if (!m) return;
+        std::vector<const impgpu_image*> im(m);
+        std::vector<unsigned char*> outs(m);
+        std::vector<size_t> caps(m), lens(m);
+        std::vector<int> row_steps(m), cs(m, IMP_OK);
+        for (size_t j = 0; j < m; j++) {
+            const Req& r = reqs[who[j]];
+            im[j] = r.img;
+            outs[j] = S.slot_data(r.slot) + r.out_offset;
+            caps[j] = (size_t)r.cap;
+            row_steps[j] = r.out_step;
+            lens[j] = (size_t)r.out_bytes;
+        }
+        const int rc = call(im.data(), (int)m, outs.data(), caps.data(), row_steps.data(), lens.data(), cs.data());
+        for (size_t j = 0; j < m; j++) {
+            Req& r = reqs[who[j]];
+            const int c = rc != IMP_OK ? rc : cs[j];
+            if (c != IMP_OK) { fail(r, c, IMP_STEP_ENCODE, impgpu_last_error()); continue; }
+            r.out_bytes = lens[j];
+            r.code = IMP_OK; r.step = IMP_STEP_ENCODE; r.done = true;
+        }
+    }
+
+    void run(const std::vector<int>& mine) {
         const size_t n = mine.size();
         const double t0 = now_us();
-        B.live = true;
         reqs.clear();
         reqs.resize(n);
         for (size_t k = 0; k < n; k++) {
@@ -320,24 +343,19 @@ struct Worker {
             r.in = S.slot_data(r.slot);
             r.t_taken = t0;
             prepare(r, S);
-            impb_slot_fields* s = &S.slots[r.slot].f;
-            s->out_offset = 0; s->out_bytes = 0; s->out_w = s->out_h = s->out_c = s->out_step = 0; s->brightness = 0;
-            s->batch_size = (int32_t)n;
         }
         __atomic_add_fetch(&S.h->batches, (uint64_t)1, __ATOMIC_RELAXED);
         const double t1 = now_us();
         g_us_prepare += (uint64_t)(t1 - t0);
 
-        // ---- decode (bridge.c:541-572): all JPEG files of the batch in one call, enqueued here, waited for in middle()
-        std::vector<size_t>& who = B.who;
-        std::vector<impgpu_jpeg_prepared>& pre = B.pre;
-        who.clear(); pre.clear();
+        // ---- decode (bridge.c:541-572): all JPEG files of the batch in one call, then all PNG files in one call
+        jpegs.clear(); pre.clear();
         for (size_t k = 0; k < n; k++) {
             Req& r = reqs[k];
             if (r.done) continue;
             r.step = IMP_STEP_DECODE;
             if (r.q.in_kind != IMPB_IN_FILE || !is_jpeg(r.in, r.q.in_bytes)) continue;
-            who.push_back(k);
+            jpegs.push_back(k);
             impgpu_jpeg_prepared f{r.in, (size_t)r.q.in_bytes, nullptr, 0, 0};
             if (r.q.in_scan_bytes) {
                 // (its bytes go to the device from the slot when they lie in its page-locked part; the worker sleeps until DONE)
@@ -348,38 +366,13 @@ struct Worker {
             }
             pre.push_back(f);
         }
-        B.dec = nullptr;
-        if (!who.empty()) {
-            const int rc = impgpu_batch_decode_jpeg_prepared_begin(pre.data(), (int)who.size(), &B.dec);
-            if (rc != IMP_OK) {
-                B.dec = nullptr;
-                for (size_t j = 0; j < who.size(); j++) fail(reqs[who[j]], rc, IMP_STEP_DECODE, impgpu_last_error());
-                who.clear();
-            }
+        if (!jpegs.empty()) {
+            imgs.assign(jpegs.size(), nullptr);
+            codes.assign(jpegs.size(), IMP_OK);
+            decoded(jpegs, impgpu_batch_decode_jpeg_prepared(pre.data(), (int)jpegs.size(), imgs.data(), codes.data()));
         }
-        g_us_decode += (uint64_t)(now_us() - t1);
-    }
-
-    void middle(Batch& B) {
-        std::vector<Req>& reqs = B.reqs;
-        const std::vector<size_t>& who = B.who;
-        const size_t n = reqs.size();
-        const double t1 = now_us();
-        if (B.dec) {
-            imgs.assign(who.size(), nullptr);
-            codes.assign(who.size(), IMP_OK);
-            const int rc = impgpu_batch_decode_jpeg_finish(&B.dec, imgs.data(), codes.data());
-            B.dec = nullptr;
-            for (size_t j = 0; j < who.size(); j++) {
-                Req& r = reqs[who[j]];
-                const int c = rc != IMP_OK ? rc : codes[j];
-                if (c == IMP_OK) { r.img = imgs[j]; continue; }
-                if (c == IMP_ERROR_UNSUPPORTED || c == IMP_ERROR_DECODE_FAILED) fail(r, IMPB_NOT_TAKEN, IMP_STEP_DECODE, "not a file the device decodes");
-                else fail(r, c, IMP_STEP_DECODE, impgpu_last_error());
-            }
-        }
-        // every PNG file of the batch in one call (after the JPEG verdicts: both are on the lane's stream, and the PNG call's
-        // inflates could overlap the JPEG kernels if issued before _finish -- not done, DESIGN.md section 8 says why)
+        // (after the JPEG call: both are on the lane's stream, and the PNG call's inflates could overlap the JPEG kernels if
+        // issued before it -- not done, DESIGN.md section 8 says why)
         pngs.clear();
         for (size_t k = 0; k < n; k++) {
             const Req& r = reqs[k];
@@ -395,14 +388,7 @@ struct Worker {
                 png_blobs[j] = reqs[pngs[j]].in;
                 png_sizes[j] = (size_t)reqs[pngs[j]].q.in_bytes;
             }
-            const int rc = impgpu_batch_decode_png(png_blobs.data(), png_sizes.data(), (int)m, imgs.data(), codes.data(), nullptr);
-            for (size_t j = 0; j < m; j++) {
-                Req& r = reqs[pngs[j]];
-                const int c = rc != IMP_OK ? rc : codes[j];
-                if (c == IMP_OK) { r.img = imgs[j]; continue; }
-                if (c == IMP_ERROR_UNSUPPORTED || c == IMP_ERROR_DECODE_FAILED) fail(r, IMPB_NOT_TAKEN, IMP_STEP_DECODE, "not a file the device decodes");
-                else fail(r, c, IMP_STEP_DECODE, impgpu_last_error());
-            }
+            decoded(pngs, impgpu_batch_decode_png(png_blobs.data(), png_sizes.data(), (int)m, imgs.data(), codes.data(), nullptr));
         }
         for (size_t k = 0; k < n; k++) {
             Req& r = reqs[k];
@@ -415,7 +401,7 @@ struct Worker {
                 std::lock_guard<std::mutex> lk(g_marks.mu);
                 g_marks.imgs.push_back(r.img);
                 r.img = nullptr;
-                S.slots[r.slot].f.out_w = (int32_t)g_marks.imgs.size();
+                r.out_w = (int32_t)g_marks.imgs.size();
                 r.code = IMP_OK; r.step = IMP_STEP_INFO; r.done = true;
             }
         }
@@ -450,36 +436,34 @@ struct Worker {
 
         const double t3 = now_us();
         g_us_ops += (uint64_t)(t3 - t2);
-        // ---- answers (bridge.c:659-710)
+        // ---- answers (bridge.c:659-710): placed right behind the request's input in its slot
         std::map<int, std::vector<size_t>> by_quality;
         std::vector<size_t> raw, png;
         for (size_t k = 0; k < n; k++) {
             Req& r = reqs[k];
             if (r.done) continue;
-            impb_slot_fields* s = &S.slots[r.slot].f;
-            const uint64_t at = (r.q.in_bytes + 63) & ~uint64_t(63);
-            s->out_w = impgpu_image_width(r.img); s->out_h = impgpu_image_height(r.img); s->out_c = impgpu_image_channels(r.img);
-            s->out_offset = at;
-            r.out_at = at;
+            r.out_w = impgpu_image_width(r.img); r.out_h = impgpu_image_height(r.img); r.out_c = impgpu_image_channels(r.img);
+            r.out_offset = (r.q.in_bytes + 63) & ~uint64_t(63);
+            r.cap = r.out_offset < S.slot_bytes ? S.slot_bytes - r.out_offset : 0;
             if (r.q.out_kind == IMPB_OUT_INFO) {
                 r.step = IMP_STEP_INFO;
                 float b = 0;
                 const int rc = impgpu_calc_perceived_brightness(r.img, &b);
                 if (rc != IMP_OK) { fail(r, rc, IMP_STEP_INFO, impgpu_last_error()); continue; }
-                s->brightness = b;
+                r.brightness = b;
                 r.code = IMP_OK; r.done = true;
             } else if (r.q.out_kind == IMPB_OUT_ASCII) {            // the text exit (bridge.c:669-670): (width + 1) * height - 1 characters
                 r.step = IMP_STEP_INFO;
-                const long need = (long)(s->out_w + 1) * s->out_h - 1;
-                if (at >= S.slot_bytes || (uint64_t)(need > 0 ? need : 1) > S.slot_bytes - at) { fail(r, IMP_ERROR_MALLOC_FAILED, IMP_STEP_INFO, "answer does not fit the slot"); continue; }
+                const long need = (long)(r.out_w + 1) * r.out_h - 1;
+                if (!r.fits((uint64_t)(need > 0 ? need : 1))) { fail(r, IMP_ERROR_MALLOC_FAILED, IMP_STEP_INFO, "answer does not fit the slot"); continue; }
                 long len = 0;
-                const int rc = impgpu_ascii(r.img, r.q.ascii_at >= 0 ? r.q.text + r.q.ascii_at : "", S.slot_data(r.slot) + at, need, &len);
+                const int rc = impgpu_ascii(r.img, r.q.ascii_at >= 0 ? r.q.text + r.q.ascii_at : "", S.slot_data(r.slot) + r.out_offset, need, &len);
                 if (rc != IMP_OK) { fail(r, rc, IMP_STEP_INFO, rc == IMP_ERROR_DEVICE ? impgpu_last_error() : ""); continue; }
-                s->out_bytes = (uint64_t)len;
+                r.out_bytes = (uint64_t)len;
                 r.code = IMP_OK; r.done = true;
             } else if (r.q.out_kind == IMPB_OUT_JPEG) {
                 r.step = IMP_STEP_ENCODE;
-                if (at >= S.slot_bytes || S.slot_bytes - at < impgpu_jpeg_encode_bound(s->out_w, s->out_h, s->out_c)) { fail(r, IMP_ERROR_MALLOC_FAILED, IMP_STEP_ENCODE, "answer does not fit the slot"); continue; }
+                if (!r.fits(impgpu_jpeg_encode_bound(r.out_w, r.out_h, r.out_c))) { fail(r, IMP_ERROR_MALLOC_FAILED, IMP_STEP_ENCODE, "answer does not fit the slot"); continue; }
                 by_quality[r.q.quality].push_back(k);
             } else if (r.q.out_kind == IMPB_OUT_PNG) {
                 r.step = IMP_STEP_ENCODE;
@@ -487,171 +471,70 @@ struct Worker {
                 // here exactly as impgpu_image_encode_png refuses them
                 if (r.q.quality == 0) { fail(r, IMP_ERROR_UNSUPPORTED, IMP_STEP_ENCODE, "PNG level 0 is encoded on the host"); continue; }
                 if (r.q.quality < 1 || r.q.quality > 9) { fail(r, IMP_ERROR_INVALID_ARGS, IMP_STEP_ENCODE, "PNG level outside 0..9"); continue; }
-                const size_t bound = impgpu_png_encode_bound(s->out_w, s->out_h, s->out_c);
+                const size_t bound = impgpu_png_encode_bound(r.out_w, r.out_h, r.out_c);
                 if (!bound) { fail(r, IMP_ERROR_UNSUPPORTED, IMP_STEP_ENCODE, "frame the device does not encode as PNG"); continue; }
-                if (at >= S.slot_bytes || S.slot_bytes - at < bound) { fail(r, IMP_ERROR_MALLOC_FAILED, IMP_STEP_ENCODE, "answer does not fit the slot"); continue; }
+                if (!r.fits(bound)) { fail(r, IMP_ERROR_MALLOC_FAILED, IMP_STEP_ENCODE, "answer does not fit the slot"); continue; }
                 png.push_back(k);
             } else {
                 r.step = IMP_STEP_ENCODE;
-                const uint64_t need = (uint64_t)impgpu_image_step(r.img) * (uint64_t)s->out_h;
-                if (at >= S.slot_bytes || S.slot_bytes - at < need) { fail(r, IMP_ERROR_MALLOC_FAILED, IMP_STEP_ENCODE, "answer does not fit the slot"); continue; }
-                s->out_step = impgpu_image_step(r.img);
-                s->out_bytes = need;
+                const uint64_t need = (uint64_t)impgpu_image_step(r.img) * (uint64_t)r.out_h;
+                if (!r.fits(need)) { fail(r, IMP_ERROR_MALLOC_FAILED, IMP_STEP_ENCODE, "answer does not fit the slot"); continue; }
+                r.out_step = impgpu_image_step(r.img);
+                r.out_bytes = need;
                 raw.push_back(k);
             }
         }
-        // the JPEG answers of the batch's most common quality are only ENQUEUED here (end() fetches them); what else the batch
-        // wants -- other qualities, pixels for host encoders -- is answered on the spot, before that encode goes on the stream
-        int async_quality = -1;
+        // one call per JPEG quality, the batch's most common one last; then the PNG answers, then pixels for host encoders
+        int common = -1;
         size_t most = 0;
-        for (auto& kv : by_quality) if (kv.second.size() > most) { most = kv.second.size(); async_quality = kv.first; }
-        for (auto& kv : by_quality) {
-            if (kv.first == async_quality) continue;
-            const size_t m = kv.second.size();
-            std::vector<const impgpu_image*> im(m);
-            std::vector<unsigned char*> outs(m);
-            std::vector<size_t> caps(m), lens(m, 0);
-            std::vector<int> cs(m, IMP_OK);
-            for (size_t j = 0; j < m; j++) {
-                Req& r = reqs[kv.second[j]];
-                const impb_slot_fields* s = &S.slots[r.slot].f;
-                im[j] = r.img;
-                outs[j] = S.slot_data(r.slot) + s->out_offset;
-                caps[j] = (size_t)(S.slot_bytes - s->out_offset);
-            }
-            const int rc = impgpu_batch_encode_jpeg(im.data(), (int)m, kv.first, outs.data(), caps.data(), lens.data(), cs.data());
-            for (size_t j = 0; j < m; j++) {
-                Req& r = reqs[kv.second[j]];
-                const int c = rc != IMP_OK ? rc : cs[j];
-                if (c != IMP_OK) { fail(r, c, IMP_STEP_ENCODE, impgpu_last_error()); continue; }
-                S.slots[r.slot].f.out_bytes = lens[j];
-                r.code = IMP_OK; r.step = IMP_STEP_ENCODE; r.done = true;
-            }
-        }
-        if (!png.empty()) {
-            const size_t m = png.size();
-            std::vector<const impgpu_image*> im(m);
-            std::vector<unsigned char*> outs(m);
-            std::vector<size_t> caps(m), lens(m, 0);
-            std::vector<int> cs(m, IMP_OK);
-            for (size_t j = 0; j < m; j++) {
-                const Req& r = reqs[png[j]];
-                im[j] = r.img;
-                outs[j] = S.slot_data(r.slot) + r.out_at;
-                caps[j] = (size_t)(S.slot_bytes - r.out_at);
-            }
-            const int rc = impgpu_batch_encode_png(im.data(), (int)m, 9, outs.data(), caps.data(), lens.data(), cs.data());
-            for (size_t j = 0; j < m; j++) {
-                Req& r = reqs[png[j]];
-                const int c = rc != IMP_OK ? rc : cs[j];
-                if (c != IMP_OK) { fail(r, c, IMP_STEP_ENCODE, impgpu_last_error()); continue; }
-                S.slots[r.slot].f.out_bytes = lens[j];
-                r.code = IMP_OK; r.step = IMP_STEP_ENCODE; r.done = true;
-            }
-        }
-        if (!raw.empty()) {
-            const size_t m = raw.size();
-            std::vector<const impgpu_image*> im(m);
-            std::vector<unsigned char*> outs(m);
-            std::vector<int> steps(m);
-            for (size_t j = 0; j < m; j++) {
-                Req& r = reqs[raw[j]];
-                const impb_slot_fields* s = &S.slots[r.slot].f;
-                im[j] = r.img; outs[j] = S.slot_data(r.slot) + s->out_offset; steps[j] = s->out_step;
-            }
-            const int rc = impgpu_batch_download(im.data(), (int)m, outs.data(), steps.data());
-            for (size_t j = 0; j < m; j++) {
-                Req& r = reqs[raw[j]];
-                if (rc != IMP_OK) { fail(r, rc, IMP_STEP_ENCODE, impgpu_last_error()); continue; }
-                r.code = IMP_OK; r.step = IMP_STEP_ENCODE; r.done = true;
-            }
-        }
-        B.enc = nullptr;
-        B.enc_who.clear();
-        if (most) {
-            B.enc_who = by_quality[async_quality];
-            B.enc_im.resize(B.enc_who.size());
-            for (size_t j = 0; j < B.enc_who.size(); j++) B.enc_im[j] = reqs[B.enc_who[j]].img;
-            const int rc = impgpu_batch_encode_jpeg_begin(B.enc_im.data(), (int)B.enc_im.size(), async_quality, &B.enc);
-            if (rc != IMP_OK) {
-                B.enc = nullptr;
-                for (size_t j = 0; j < B.enc_who.size(); j++) fail(reqs[B.enc_who[j]], rc, IMP_STEP_ENCODE, impgpu_last_error());
-                B.enc_who.clear();
-            }
-        }
+        for (auto& kv : by_quality) if (kv.second.size() > most) { most = kv.second.size(); common = kv.first; }
+        auto jpeg = [](int quality) {
+            return [quality](const impgpu_image* const* im, int m, unsigned char* const* outs, const size_t* caps, const int*, size_t* lens, int* cs) {
+                return impgpu_batch_encode_jpeg(im, m, quality, outs, caps, lens, cs);
+            };
+        };
+        for (auto& kv : by_quality)
+            if (kv.first != common) answer(kv.second, jpeg(kv.first));
+        answer(png, [](const impgpu_image* const* im, int m, unsigned char* const* outs, const size_t* caps, const int*, size_t* lens, int* cs) {
+            return impgpu_batch_encode_png(im, m, 9, outs, caps, lens, cs);
+        });
+        answer(raw, [](const impgpu_image* const* im, int m, unsigned char* const* outs, const size_t*, const int* row_steps, size_t*, int*) {
+            return impgpu_batch_download(im, m, outs, row_steps);
+        });
+        if (most) answer(by_quality[common], jpeg(common));
+        for (size_t k = 0; k < n; k++) finish(reqs[k], (int)n);
         g_us_answer += (uint64_t)(now_us() - t3);
-    }
-
-    void end(Batch& B) {
-        std::vector<Req>& reqs = B.reqs;
-        const double t0 = now_us();
-        if (B.enc) {
-            const size_t m = B.enc_who.size();
-            std::vector<unsigned char*> outs(m);
-            std::vector<size_t> caps(m), lens(m, 0);
-            std::vector<int> cs(m, IMP_OK);
-            for (size_t j = 0; j < m; j++) {
-                Req& r = reqs[B.enc_who[j]];
-                const impb_slot_fields* s = &S.slots[r.slot].f;
-                outs[j] = S.slot_data(r.slot) + s->out_offset;
-                caps[j] = (size_t)(S.slot_bytes - s->out_offset);
-            }
-            const int rc = impgpu_batch_encode_jpeg_finish(&B.enc, outs.data(), caps.data(), lens.data(), cs.data());
-            B.enc = nullptr;
-            for (size_t j = 0; j < m; j++) {
-                Req& r = reqs[B.enc_who[j]];
-                const int c = rc != IMP_OK ? rc : cs[j];
-                if (c != IMP_OK) { fail(r, c, IMP_STEP_ENCODE, impgpu_last_error()); continue; }
-                S.slots[r.slot].f.out_bytes = lens[j];
-                r.code = IMP_OK; r.step = IMP_STEP_ENCODE; r.done = true;
-            }
-        }
-        for (size_t k = 0; k < reqs.size(); k++) finish(reqs[k]);
-        B.live = false;
-        g_us_answer += (uint64_t)(now_us() - t0);
     }
 
     void loop() {
         impb_header_fields* h = S.h;
         std::vector<int> mine;
         int start = id * 7;
-        Batch* P = nullptr;                                 // the batch whose decode is on the stream
-        while (!g_stop || P) {
-            if (P) middle(*P);                              // its verdicts, its operators, its answers enqueued
+        while (!g_stop) {
             mine.clear();
-            if (!g_stop) {
-                const uint32_t bell = __atomic_load_n(&h->doorbell, __ATOMIC_SEQ_CST);
-                take(mine, start);
-                if (mine.empty() && !P) {
-                    const double idle0 = now_us();
-                    __atomic_add_fetch(&h->sleepers, 1u, __ATOMIC_SEQ_CST);
-                    take(mine, start);                      // (a submit between the scan and the count)
-                    if (mine.empty()) {
-                        timespec tick{0, 100 * 1000 * 1000};
-                        futex(&h->doorbell, FUTEX_WAIT, bell, &tick);
-                    }
-                    __atomic_sub_fetch(&h->sleepers, 1u, __ATOMIC_SEQ_CST);
-                    g_us_idle += (uint64_t)(now_us() - idle0);
-                    if (mine.empty()) continue;
+            const uint32_t bell = __atomic_load_n(&h->doorbell, __ATOMIC_SEQ_CST);
+            take(mine, start);
+            if (mine.empty()) {
+                const double idle0 = now_us();
+                __atomic_add_fetch(&h->sleepers, 1u, __ATOMIC_SEQ_CST);
+                take(mine, start);                          // (a submit between the scan and the count)
+                if (mine.empty()) {
+                    timespec tick{0, 100 * 1000 * 1000};
+                    futex(&h->doorbell, FUTEX_WAIT, bell, &tick);
                 }
-                if (!P && O.gather_us > 0 && (int)mine.size() < O.batch) {
-                    // a few workers answered together come back together: give the stragglers of that wave a moment
-                    const double until = now_us() + O.gather_us;
-                    while (now_us() < until && (int)mine.size() < O.batch) {
-                        if (!take(mine, start)) { timespec nap{0, 5000}; nanosleep(&nap, nullptr); }
-                    }
+                __atomic_sub_fetch(&h->sleepers, 1u, __ATOMIC_SEQ_CST);
+                g_us_idle += (uint64_t)(now_us() - idle0);
+                if (mine.empty()) continue;
+            }
+            if (O.gather_us > 0 && (int)mine.size() < O.batch) {
+                // a few workers answered together come back together: give the stragglers of that wave a moment
+                const double until = now_us() + O.gather_us;
+                while (now_us() < until && (int)mine.size() < O.batch) {
+                    if (!take(mine, start)) { timespec nap{0, 5000}; nanosleep(&nap, nullptr); }
                 }
             }
-            Batch* B = nullptr;
-            if (!mine.empty()) {
-                // what is queued NOW is unpacked and its decode goes on the stream behind P's answers, while those are written
-                B = P == &slots_[0] ? &slots_[1] : &slots_[0];
-                start = (start + 1) % (int)h->nslots;
-                begin(*B, mine);
-            }
-            if (P) end(*P);                                 // fetch P's files, wake its workers (B's decode runs meanwhile)
-            P = B;
-            if (P && !O.pipeline) { middle(*P); end(*P); P = nullptr; }      // (A/B: one batch at a time, as round 5 began)
+            start = (start + 1) % (int)h->nslots;
+            run(mine);
         }
     }
 };
@@ -773,15 +656,13 @@ int main(int argc, char** argv) {
         else if (a == "--device") o.device = std::atoi(val("--device"));
         else if (a == "--slots") o.slots = std::atoi(val("--slots"));
         else if (a == "--slot-mb") o.slot_mb = std::atol(val("--slot-mb"));
-        else if (a == "--split-kb") o.split_kb = std::atol(val("--split-kb"));
-        else if (a == "--pipeline") o.pipeline = std::atoi(val("--pipeline")) != 0;
         else if (a == "--register-mb") o.register_mb = std::max(0l, std::atol(val("--register-mb")));
         else if (a == "--threads") o.threads = std::atoi(val("--threads"));
         else if (a == "--batch") o.batch = std::atoi(val("--batch"));
         else if (a == "--gather-us") o.gather_us = std::atoi(val("--gather-us"));
         else if (a == "--ready-file") o.ready_file = val("--ready-file");
         else if (a == "--supervise") o.supervise = true;
-        else { std::fprintf(stderr, "usage: impgpu_broker [--name /impgpu-broker-0] [--device 0] [--slots 64] [--slot-mb 32] [--register-mb 8] [--pipeline 1] [--threads 2] [--batch 64] [--gather-us 0] [--supervise] [--ready-file PATH]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: impgpu_broker [--name /impgpu-broker-0] [--device 0] [--slots 64] [--slot-mb 32] [--register-mb 8] [--threads 2] [--batch 64] [--gather-us 0] [--supervise] [--ready-file PATH]\n"); return 2; }
     }
     if (o.slots < 1 || o.slots > IMPB_MAX_SLOTS || o.slot_mb < 1 || o.slot_mb > 4096 || o.threads < 1 || o.threads > 32 || o.batch < 1 || o.batch > 256 ||
         o.name.empty() || o.name[0] != '/') {

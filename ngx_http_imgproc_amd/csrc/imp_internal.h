@@ -49,20 +49,9 @@ inline bool view_fits(long long w, long long h, int c, long long step) {
            w * h <= (1LL << 30) && step * h <= 0xffffffffLL;
 }
 
-// ---------------------------------------------------------------- A/B switches
-// The environment switches of the measurement sessions (tools/switch_matrix.sh; DESIGN.md lists them with what each one
-// measured) select kernel variants that LOST their comparison or tuning values other than the chosen ones.  They are compiled
-// in only with -DIMPGPU_AB_SWITCHES (IMPGPU_EXTRA_FLAGS=-DIMPGPU_AB_SWITCHES python ngx_http_imgproc_amd/build.py): the
-// shipped library reads none of them, and the variants only they reach are not in its binary.
-#ifdef IMPGPU_AB_SWITCHES
-inline const char* ab_env(const char* name) { return std::getenv(name); }
-#else
-constexpr const char* ab_env(const char*) { return nullptr; }
-#endif
-inline int ab_env_int(const char* name, int otherwise) {
-    const char* s = ab_env(name);
-    return s ? std::atoi(s) : otherwise;
-}
+// The measurement sessions' environment switches, and the kernel variants and tuning values that only they selected, were
+// removed once those variants lost their comparisons: each dispatch keeps the branch that won.  The numbers stay in
+// profiles/ and in DESIGN.md section 5.
 
 // ---------------------------------------------------------------- runtime (imp_runtime.hip)
 void set_error(const char* what, hipError_t e);

@@ -247,10 +247,6 @@ size_t jpeg_scan_capacity(size_t scan_bytes, size_t nsegs) {
 // rest of its chunk is filled with 1-bits, exactly what the encoder pads the last byte with) and the next one starts on a
 // chunk boundary.  Stops at EOI, at any other marker, or at the end of the file.
 size_t jpeg_chunk_bytes_for(size_t file_bytes, size_t launch_bytes, bool busy) {
-    if (const char* s = ab_env("IMPGPU_JPEG_CHUNK_WORDS")) {
-        const int w = std::atoi(s);
-        if (w == 8 || w == 16 || w == 32 || w == 64 || w == 128) return (size_t)w * 4;
-    }
     // measured, one request at a time (profiles/r03_request_latency.txt; 256 / 512 / 1024 bits): 640x480 0.77 / 0.76 / 0.89 ms,
     // 720p 0.83 / 0.84 / 0.94, 1080p 0.90 / 0.84 / 0.95, 4K 1.45 / 1.24 / 1.24; a queue's worth of files (28 MB) is a little
     // faster on 1024
@@ -272,12 +268,9 @@ size_t jpeg_chunk_bytes_for(size_t file_bytes, size_t launch_bytes, bool busy) {
 }
 
 unsigned jpeg_overlap_bits_for(unsigned chunk_bits, size_t scan_bytes, size_t total_blocks) {
-    if (const char* s = ab_env("IMPGPU_JPEG_OVERLAP")) {
-        const int v = std::atoi(s);
-        if (v >= 0 && v <= 1 << 20) return (unsigned)v;
-    }
-    // tools/jpeg_sync_probe.py: with five blocks' worth of bits in front of the chunk 97.5-99.5 % of a photograph's chunks find
-    // their true entry state among their walks' (quality 50-90, 1-2.5 bits per pixel); with two or three, four in five
+    // measured on the host model (impgpu_jpeg_sync_stats over content, quality, sampling and overlap): with five blocks' worth
+    // of bits in front of the chunk 97.5-99.5 % of a photograph's chunks find their true entry state among their walks'
+    // (quality 50-90, 1-2.5 bits per pixel); with two or three, four in five
     (void)chunk_bits;
     const size_t bits_per_block = total_blocks ? scan_bytes * 8 / total_blocks : 64;
     const size_t want = (5 * bits_per_block + 63) / 64 * 64;

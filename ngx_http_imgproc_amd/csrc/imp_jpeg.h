@@ -91,11 +91,10 @@ struct JpegScan {
 // is a chain of per-chunk walks that nothing else overlaps with, so its counting and writing walks -- which touch every
 // chunk once -- finish sooner on shorter chunks, while the resynchronising rounds take the same time either way (a round's
 // length and the number of rounds trade against each other).  launch_bytes = entropy-coded bytes of the whole launch.
-// IMPGPU_JPEG_CHUNK_WORDS = 8 | 16 | 32 overrides (A/B).
 size_t jpeg_chunk_bytes_for(size_t file_bytes, size_t launch_bytes, bool busy = false);
 // How far in front of its chunk a synchronising walk starts: long enough to hold a block end or two of THIS file (its
 // entropy-coded bytes over its blocks), so that one of the walks has fallen into step with the true decoder by the chunk's
-// first bit.  IMPGPU_JPEG_OVERLAP (bits) overrides (A/B).
+// first bit.
 unsigned jpeg_overlap_bits_for(unsigned chunk_bits, size_t scan_bytes, size_t total_blocks);
 // worst-case bytes jpeg_prepare_scan writes for `scan_bytes` of entropy-coded data and `nsegs` intervals
 size_t jpeg_scan_capacity(size_t scan_bytes, size_t nsegs);

@@ -82,7 +82,7 @@ struct Prep {                                       // one file on its way to th
 
 // A file whose blocks average more bits than this keeps its Huffman stage on the calling thread even inside a launch that is
 // the device's: blocks that long seldom end inside a walk's overlap, so their chunks are reached one after the other by an
-// explicit state (tools/jpeg_sync_probe.py: 4.5 % of the chunks at 210 bits per block, a quality-98 photograph; 25-70 % for
+// explicit state (the host model, impgpu_jpeg_sync_stats: 4.5 % of the chunks at 210 bits per block, a quality-98 photograph; 25-70 % for
 // white noise), and a 4 MB file of noise would hold a workgroup chain for most of a second where the host needs 25 ms.
 constexpr size_t DENSE_BITS_PER_BLOCK = 200;
 constexpr int CODE_DEFERRED = -0x7fff;              // internal: "decode this one in the host-entropy group"
@@ -254,8 +254,8 @@ int group_begin(Group& G, const unsigned char* const* blobs, const size_t* sizes
                 // launch is a latency chain, that is (a lone 640 x 480: k_jpeg_write 65 -> 56 us, 4K 99 -> 89); a launch that fills
                 // the device gains nothing from shorter chains and loses to the second round of workgroups its LDS forces
                 // (64 files, 28 MB: 349 -> 415 us), so from 4 MB on -- where the chunks grow to 256 bytes -- a chunk keeps its
-                // one lane.  IMPGPU_JPEG_SPLIT=0 | 1 forces either (A/B, read per call).
-                { const char* sp = std::getenv("IMPGPU_JPEG_SPLIT"); p.F.wsplit = sp ? (sp[0] == '0' ? 1u : 2u) : launch_bytes > (size_t(4) << 20) ? 1u : 2u; }
+                // one lane.
+                p.F.wsplit = launch_bytes > (size_t(4) << 20) ? 1u : 2u;
             }
         } else {
             int16_t* planes = (int16_t*)((uint8_t*)host + p.coef_off);
@@ -440,10 +440,7 @@ int group_begin(Group& G, const unsigned char* const* blobs, const size_t* sizes
             // (k_jpeg_entropy_small; measured, one file at a time, fused / five kernels: 640 x 480 0.221 / 0.235 ms, 720p equal,
             // 1080p 0.323 / 0.313, 4K 0.546 / 0.510 -- from a few hundred KB on every phase is bound by what it computes, not by
             // its launch, and a workgroup that waits inside a kernel holds slots a kernel boundary would have given to others).
-            // IMPGPU_JPEG_FUSED=0 keeps the five kernels, =1 fuses up to 4 MB (A/B, read per call).
-            const char* fz = std::getenv("IMPGPU_JPEG_FUSED");
-            const size_t fuse_up_to = fz && fz[0] == '1' ? (size_t(4) << 20) : (size_t(192) << 10);
-            const bool small = launch_bytes <= fuse_up_to && !(fz && fz[0] == '0');
+            const bool small = launch_bytes <= (size_t(192) << 10);
             rc = launch_jpeg_entropy((const JpegJob*)((uint8_t*)d_side + side_jobs), (const JpegMapEntry*)((uint8_t*)d_side + side_sync), (unsigned)sync_blocks,
                                      (const JpegMapEntry*)((uint8_t*)d_side + side_blocks), (unsigned)total_blocks, (uint32_t*)d_ctl, s, profile ? ev + 2 : nullptr, small);
             if (rc) goto fail;
@@ -682,9 +679,8 @@ int impgpu_batch_decode_jpeg_begin(const unsigned char* const* blobs, const size
     TraceRange tr("IMP_STEP_DECODE");
     IMP_FAULT_POINT(IMP_STEP_DECODE);
     impgpu_jpeg_batch* b = new impgpu_jpeg_batch();
-    // on the lane's side stream: what the thread enqueues before _finish overlaps it (IMPGPU_JPEG_AHEAD_STREAM=lane: behind it on the lane's own)
-    const char* where = std::getenv("IMPGPU_JPEG_AHEAD_STREAM");
-    const int rc = group_begin(b->G, blobs, sizes, count, 0, !(where && !std::strcmp(where, "lane")));
+    // on the lane's side stream: what the thread enqueues before _finish overlaps it
+    const int rc = group_begin(b->G, blobs, sizes, count, 0, true);
     if (rc) { delete b; return rc; }
     *batch = b;
     return IMP_OK;

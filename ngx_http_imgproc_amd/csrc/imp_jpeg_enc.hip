@@ -843,7 +843,6 @@ int encode_begin(const impgpu_image* const* images, int count, int quality, EncS
     hipStream_t s = env_stream();
     EncTables T;
     enc_static_tables(&T, quality);
-    static const bool one_wg = ab_env("IMPGPU_JPEG_ENC_ONE_WG") != nullptr;       // A/B: every frame through k_jpeg_enc_huff
     std::vector<EncJob>& jobs = E.jobs;                         // small frames first, then the large ones
     std::vector<int>& owner = E.owner;
     std::vector<std::vector<uint8_t>>& heads = E.heads;
@@ -853,9 +852,9 @@ int encode_begin(const impgpu_image* const* images, int count, int quality, EncS
     // batch's -- up to sixteen frames -- and ONE workgroup of 1024 threads each when it is a queue's worth: measured, same box,
     // the lone call 72 -> 69 us at 224 x 168 and 86 -> 71 at 224 x 224 (1176 blocks: two passes of the one workgroup), the
     // broker's four lanes 16.95 -> 17.4 k requests/s at 16 workers and 23.7 -> 24.6 k at 32; but 64 frames per call 447 -> 504 us
-    // and the eight-thread stream 46.8 -> 44.6 k.  IMPGPU_JPEG_ENC_SEG=0 | 1 forces either (A/B, read per call).
+    // and the eight-thread stream 46.8 -> 44.6 k.  IMPGPU_JPEG_ENC_SEG=0 | 1 forces either (the tests take both paths; read per call).
     const char* segenv = std::getenv("IMPGPU_JPEG_ENC_SEG");
-    const bool seg_on = !one_wg && (segenv ? segenv[0] != '0' : count <= 16);
+    const bool seg_on = segenv ? segenv[0] != '0' : count <= 16;
     for (int pass = 0; pass < 3; pass++)                        // 0: frames of up to 256 block slots (or all small ones), 1: up to 2048 in segments, 2: the large ones
         for (int i = 0; i < count; i++) {
             const impgpu_image* im = images[i];
@@ -866,7 +865,7 @@ int encode_begin(const impgpu_image* const* images, int count, int quality, EncS
             }
             if (E.early[(size_t)i] != IMP_OK) continue;
             (void)enc_geom(im->w, im->h, im->c, &g);
-            const bool big = !one_wg && g.nblocks > ENC_BIG_BLOCKS && (uint64_t)g.nblocks * 1658u < (1ull << 32);
+            const bool big = g.nblocks > ENC_BIG_BLOCKS && (uint64_t)g.nblocks * 1658u < (1ull << 32);
             const bool mid = !big && seg_on && g.nblocks > 256;
             if ((big ? 2 : mid ? 1 : 0) != pass) continue;
             EncJob J{};

@@ -2679,8 +2679,7 @@ static int get_tables(int interp, int sw, int sh, int dw, int dh, double scale_x
             }
             yr[dh] = yr[dh - 1];
             yr[dh].adv = 0;
-            static const bool no_period = ab_env("IMPGPU_UP_NO_PERIOD") != nullptr;
-            for (int per = 2; per <= 4 && !ts.up_period && !no_period; per++) {   // rows p, p + per, p + 2 per ... advance by one, the others not at all
+            for (int per = 2; per <= 4 && !ts.up_period; per++) {   // rows p, p + per, p + 2 per ... advance by one, the others not at all
                 int p0 = 1;
                 while (p0 < dh && yr[p0].adv == 0) p0++;
                 bool ok = p0 < dh;
@@ -2763,12 +2762,10 @@ static bool area_rows_plan(int sw, int sh, int dw, int dh, double scale_x, long 
     if (even) ww += ww & 1;                                // the mixed-geometry kernel carries the even windows only
     while (ww <= 4 * MIX_NV && 63 * scale_x + ww + 8 > 256 * ((ww + 3) / 4)) ww += even ? 2 : 1;
     if (ww < 1 || ww > 4 * MIX_NV || sw < ww || sw < 4) return false;
-    static const int bh_env = ab_env_int("IMPGPU_AREA_BH", 0);
     int b = 16;
     const long long nstrips = (dw + 63) / 64;
     while (b > 4 && frames * nstrips * ((dh + b - 1) / b) < 4096) b /= 2;
     while (b > 1 && frames * nstrips * ((dh + b - 1) / b) < 1024) b /= 2;
-    if (bh_env > 0) b = std::min(64, bh_env);
     *w = ww;
     *bh = b;
     return true;
@@ -2832,26 +2829,22 @@ static int launch_cn(const RArgs& a, int count, int interp, double scale_x, doub
                 const dim3 qgrid((unsigned)(((long long)qpr * a.dh + 255) / 256), (unsigned)count);
                 const int gpr2 = a.sw / 4;
                 const dim3 cgrid2((unsigned)(((long long)gpr2 * a.dh + 511) / 512), (unsigned)count);
-                static const bool no_c4 = ab_env("IMPGPU_NO_C4") != nullptr;
-                if (CN == 4 && !(a.dw & 1) && !no_c4) hipLaunchKernelGGL(k_area2x2_c4, cgrid2, block, 0, s, a, gpr2);
+                if (CN == 4 && !(a.dw & 1)) hipLaunchKernelGGL(k_area2x2_c4, cgrid2, block, 0, s, a, gpr2);
                 else if (CN == 4) hipLaunchKernelGGL(k_area2x2_v4, qgrid, block, 0, s, a, qpr);
                 else hipLaunchKernelGGL(k_area2x2_v3, qgrid, block, 0, s, a, qpr);
             } else if (CN == 4 && rows4 && isx >= 3 && isx <= 8 && isy >= 1 && isx * isy <= 257 && a.sw == isx * a.dw && a.sh >= isy * a.dh) {
                 const float scale = 1.f / (float)(isx * isy);
                 const int cpr = a.sw / 4;                         // 16-byte granules per source row (k_area_boxc)
                 const dim3 cgrid((unsigned)(((long long)cpr * a.dh + 1023) / 1024), (unsigned)count);
-                static const bool all_lds = ab_env("IMPGPU_BOXL") != nullptr;        // A/B: 4 and 8 through their other form
                 const int P = (4096 / (4 * isx)) & ~3, lcpr = (a.dw + P - 1) / P;
                 const dim3 lgrid((unsigned)(((long long)lcpr * a.dh + 3) / 4), (unsigned)count);
-                switch (isx + (all_lds ? 100 : 0)) {
-                    case 104: hipLaunchKernelGGL((k_area_boxc<4>), cgrid, block, 0, s, a, isy, cpr, scale); break;
+                switch (isx) {
                     case 8: hipLaunchKernelGGL((k_area_boxc<8>), cgrid, block, 0, s, a, isy, cpr, scale); break;
-                    case 3: case 103: hipLaunchKernelGGL((k_area_boxl<4, 3>), lgrid, block, 0, s, a, isy, P, lcpr, scale); break;
-                    case 5: case 105: hipLaunchKernelGGL((k_area_boxl<4, 5>), lgrid, block, 0, s, a, isy, P, lcpr, scale); break;
-                    case 6: case 106: hipLaunchKernelGGL((k_area_boxl<4, 6>), lgrid, block, 0, s, a, isy, P, lcpr, scale); break;
-                    case 7: case 107: hipLaunchKernelGGL((k_area_boxl<4, 7>), lgrid, block, 0, s, a, isy, P, lcpr, scale); break;
-                    case 4: hipLaunchKernelGGL((k_area_boxl<4, 4>), lgrid, block, 0, s, a, isy, P, lcpr, scale); break;
-                    default: hipLaunchKernelGGL((k_area_boxl<4, 8>), lgrid, block, 0, s, a, isy, P, lcpr, scale); break;
+                    case 3: hipLaunchKernelGGL((k_area_boxl<4, 3>), lgrid, block, 0, s, a, isy, P, lcpr, scale); break;
+                    case 5: hipLaunchKernelGGL((k_area_boxl<4, 5>), lgrid, block, 0, s, a, isy, P, lcpr, scale); break;
+                    case 6: hipLaunchKernelGGL((k_area_boxl<4, 6>), lgrid, block, 0, s, a, isy, P, lcpr, scale); break;
+                    case 7: hipLaunchKernelGGL((k_area_boxl<4, 7>), lgrid, block, 0, s, a, isy, P, lcpr, scale); break;
+                    default: hipLaunchKernelGGL((k_area_boxl<4, 4>), lgrid, block, 0, s, a, isy, P, lcpr, scale); break;
                 }
             } else if (CN == 3 && rows4 && isx >= 2 && isx <= 8 && isy >= 1 && isx * isy <= 257 && !(isx == 2 && isy == 2) &&
                        a.sw == isx * a.dw && a.sh >= isy * a.dh) {
@@ -2877,10 +2870,9 @@ static int launch_cn(const RArgs& a, int count, int interp, double scale_x, doub
             if (CN == 4 || (CN == 3 && rows4b && a.sw >= 6)) {
                 int w = 0, bh = 0;
                 if (area_rows_plan(a.sw, a.sh, a.dw, a.dh, scale_x, count, false, &w, &bh)) {
-                    static const bool no_rows4 = ab_env("IMPGPU_NO_ROWS4") != nullptr;
                     // four columns per lane while the windows are small and there are enough columns and waves for it
                     const long long waves4 = (long long)count * ((a.dw + 255) / 256) * ((a.dh + bh - 1) / bh);
-                    if (!no_rows4 && w >= 2 && w <= 5 && a.dw >= 160 && waves4 >= 2048 && 255 * scale_x + w + 8 <= (CN == 4 ? 1024 : 1340)) {
+                    if (w >= 2 && w <= 5 && a.dw >= 160 && waves4 >= 2048 && 255 * scale_x + w + 8 <= (CN == 4 ? 1024 : 1340)) {
                         constexpr int C34 = CN == 3 ? 3 : 4;
                         const int nstrips = (a.dw + 255) / 256, nitems = nstrips * ((a.dh + bh - 1) / bh), rbpf = (nitems + 3) / 4;
                         const dim3 rgrid((unsigned)rbpf, (unsigned)((count + 7) / 8 * 8));
@@ -2935,13 +2927,11 @@ static int launch_cn(const RArgs& a, int count, int interp, double scale_x, doub
         TableSet ts;
         if (int rc = get_tables(interp, a.sw, a.sh, a.dw, a.dh, scale_x, scale_y, s, &ts)) return rc;
         // both scales <= 2: neighbouring outputs share taps -> LDS-tiled separable kernel (BGRA)
-        static const bool no_roll = ab_env("IMPGPU_NO_ROLL") != nullptr;
-        if (CN == 3 && ts.step2 && a.sw >= 8 && !no_roll && interp != IMP_INTER_LINEAR) {
+        if (CN == 3 && ts.step2 && a.sw >= 8 && interp != IMP_INTER_LINEAR) {
             // exact 2x decimation of a 3-channel frame: register-rolling strips
             const int nstrips = (a.dh + ROLL_STRIP - 1) / ROLL_STRIP;
             const dim3 rgrid((a.dw + 255) / 256, nstrips, (unsigned)count);
-            static const bool no_dma3 = ab_env("IMPGPU_NO_DMA3") != nullptr;
-            const bool dma3 = !no_dma3 && (a.sw & 15) == 0 && (long long)a.sh * a.sstep < (1LL << 32) && (long long)a.dh * a.dstep < (1LL << 32) &&
+            const bool dma3 = (a.sw & 15) == 0 && (long long)a.sh * a.sstep < (1LL << 32) && (long long)a.dh * a.dstep < (1LL << 32) &&
                               !(((uintptr_t)a.src | (uintptr_t)a.sstep | (uintptr_t)a.src_stride) & 15);
             const int nbx = (a.dw + 255) / 256, bpf = nbx * nstrips;
             const dim3 dgrid((unsigned)(bpf * 8), (unsigned)((count + 7) / 8));
@@ -2957,42 +2947,28 @@ static int launch_cn(const RArgs& a, int count, int interp, double scale_x, doub
                 hipLaunchKernelGGL((k_resize_2x_roll3<8, M_LANCZOS, true>), rgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0);
             else
                 hipLaunchKernelGGL((k_resize_2x_roll3<8, M_LANCZOS, false>), rgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0);
-        } else if (CN == 4 && ts.step2 && a.sw >= 8 && !no_roll) {
+        } else if (CN == 4 && ts.step2 && a.sw >= 8) {
             // exact 2x decimation: register-rolling kernel, one wave per 64-column x ROLL_STRIP-row strip
             const int nstrips = (a.dh + ROLL_STRIP - 1) / ROLL_STRIP;
-            // LDS-DMA row ring when the 16-byte DMA granules line up with the rows; IMPGPU_DMA_DEPTH = iterations
-            // prefetched (0 = off: the register-rolling kernel, which has no alignment demands)
-            static const int dma_depth = ab_env_int("IMPGPU_DMA_DEPTH", 3);
-            const bool dma_ok = dma_depth > 0 && interp != IMP_INTER_LINEAR && (a.sw & 3) == 0 &&
+            // LDS-DMA row ring, three iterations prefetched, when the 16-byte DMA granules line up with the rows (otherwise
+            // the register-rolling kernel, which has no alignment demands)
+            const bool dma_ok = interp != IMP_INTER_LINEAR && (a.sw & 3) == 0 &&
                                 (long long)a.sh * a.sstep < (1LL << 32) && (long long)a.dh * a.dstep < (1LL << 32) &&
                                 !(((uintptr_t)a.src | (uintptr_t)a.sstep | (uintptr_t)a.src_stride) & 15);
             const dim3 rgrid((a.dw + 255) / 256, nstrips, (unsigned)count);
-            // waves of a block are independent (no barriers, private LDS rings): small blocks only shorten the tail
-            static const int wpb = ab_env_int("IMPGPU_DMA_WPB", 4);
-            const int nbx = (a.dw + 64 * wpb - 1) / (64 * wpb), bpf = nbx * nstrips;
+            // four waves per block; they are independent (no barriers, private LDS rings)
+            const int nbx = (a.dw + 255) / 256, bpf = nbx * nstrips;
             const dim3 dgrid((unsigned)(bpf * 8), (unsigned)((count + 7) / 8));
-#define IMP_DMA_W(KS_, MODE_, VEC_, VS_, D_)                                                                             \
-    do {                                                                                                                 \
-        if (wpb == 1) hipLaunchKernelGGL((k_resize_2x_dma<KS_, MODE_, D_, VS_, 1>), dgrid, dim3(64), 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, VEC_, nbx, bpf, count); \
-        else if (wpb == 2) hipLaunchKernelGGL((k_resize_2x_dma<KS_, MODE_, D_, VS_, 2>), dgrid, dim3(128), 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, VEC_, nbx, bpf, count); \
-        else hipLaunchKernelGGL((k_resize_2x_dma<KS_, MODE_, D_, VS_, 4>), dgrid, dim3(256), 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, VEC_, nbx, bpf, count); \
-    } while (0)
-#define IMP_DMA(KS_, MODE_, VEC_, VS_)                                                                                   \
-    do {                                                                                                                 \
-        if (dma_depth == 2) IMP_DMA_W(KS_, MODE_, VEC_, VS_, 2);                                                         \
-        else if (dma_depth == 4) IMP_DMA_W(KS_, MODE_, VEC_, VS_, 4);                                                    \
-        else IMP_DMA_W(KS_, MODE_, VEC_, VS_, 3);                                                                        \
-    } while (0)
-            // the horizontal pass on the matrix unit (k_resize_2x_dma's MF form) where every column has the same taps, the strips'
-            // first tap is dword 1 of its 16-byte granule (xofs[0] = 0: sx00 = 2 dx0 - 3), and the block is four waves deep
-            static const bool no_mf = ab_env("IMPGPU_NO_HMFMA") != nullptr;
-            const bool mf = dma_ok && ts.xuni && ts.ysym && !no_mf && wpb == 4 && dma_depth == 3 && interp == IMP_INTER_LANCZOS4 && ts.x0 == 0;
-            if (mf) hipLaunchKernelGGL((k_resize_2x_dma<8, M_LANCZOS, 3, true, 4, true>), dgrid, dim3(256), 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0, nbx, bpf, count);
-            else if (dma_ok && interp == IMP_INTER_CUBIC) IMP_DMA(4, M_CUBIC, (a.dw * 4) & ~7, false);
-            else if (dma_ok && ts.ysym) IMP_DMA(8, M_LANCZOS, 0, true);
-            else if (dma_ok) IMP_DMA(8, M_LANCZOS, 0, false);
-#undef IMP_DMA_W
-#undef IMP_DMA
+            // the horizontal pass on the matrix unit (k_resize_2x_dma's MF form) where every column has the same taps and the
+            // strips' first tap is dword 1 of its 16-byte granule (xofs[0] = 0: sx00 = 2 dx0 - 3)
+            const bool mf = dma_ok && ts.xuni && ts.ysym && interp == IMP_INTER_LANCZOS4 && ts.x0 == 0;
+            if (mf) hipLaunchKernelGGL((k_resize_2x_dma<8, M_LANCZOS, 3, true, 4, true>), dgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0, nbx, bpf, count);
+            else if (dma_ok && interp == IMP_INTER_CUBIC)
+                hipLaunchKernelGGL((k_resize_2x_dma<4, M_CUBIC, 3, false, 4>), dgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, (a.dw * 4) & ~7, nbx, bpf, count);
+            else if (dma_ok && ts.ysym)
+                hipLaunchKernelGGL((k_resize_2x_dma<8, M_LANCZOS, 3, true, 4>), dgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0, nbx, bpf, count);
+            else if (dma_ok)
+                hipLaunchKernelGGL((k_resize_2x_dma<8, M_LANCZOS, 3, false, 4>), dgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0, nbx, bpf, count);
             else if (interp == IMP_INTER_LINEAR)
                 hipLaunchKernelGGL((k_resize_2x_roll<2, M_LINEAR>), rgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0);
             else if (interp == IMP_INTER_CUBIC)
@@ -3000,7 +2976,7 @@ static int launch_cn(const RArgs& a, int count, int interp, double scale_x, doub
             else
                 hipLaunchKernelGGL((k_resize_2x_roll<8, M_LANCZOS>), rgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0);
         } else if (CN == 3 && interp == IMP_INTER_CUBIC && scale_y <= 1.0 && scale_x <= 2.0 && a.sw >= 4 &&
-                   (long long)a.dh * a.dstep < (1LL << 32) && !ab_env("IMPGPU_NO_UP")) {
+                   (long long)a.dh * a.dstep < (1LL << 32)) {
             // enlargement of a 3-channel frame (every JPEG): the BGRA kernel's structure on bytes
             const int nbx = (a.dw + 255) / 256;
             const int wbmax = ((((int)std::floor(63 * scale_x) + 6) * 3 + 3) & ~3) + 4;
@@ -3018,16 +2994,14 @@ static int launch_cn(const RArgs& a, int count, int interp, double scale_x, doub
               else hipLaunchKernelGGL(k_resize_up_cubic3<0>, dim3((unsigned)(nbx * ncy), (unsigned)count), block, 0, s, a,
                                ts.xofs, ts.xco, ts.yco, (const UpRow*)ts.yrows, (a.dw * 3) & ~7, nbx, rpw); }
         } else if (CN == 4 && interp == IMP_INTER_CUBIC && scale_y <= 1.0 && scale_x <= 2.0 && a.sw >= 4 &&
-                   (long long)a.dh * a.dstep < (1LL << 32) && !ab_env("IMPGPU_NO_UP")) {
+                   (long long)a.dh * a.dstep < (1LL << 32)) {
             // enlargement (bridge.c:190's CUBIC case): wave-private strips, float H sums in a register ring
             const int nbx = (a.dw + 255) / 256;                 // four 64-column strips per block, one per wave
-            // few frames: shorter row chunks so that every CU still gets waves
-            static const int up_rows = ab_env_int("IMPGPU_UP_ROWS", UP_ROWS);
             // rows per wave chunk: as many as keep the chunk's source footprint (strip columns x footprint rows, from the
             // bound floor(n * scale) + 1 on how far n + 1 sample positions spread, + 3 taps + 1) inside the wave's LDS
             // patch, at most UP_ROWS; fewer when there are too few frames to fill the chip otherwise
             const int wmax = (int)std::floor(63 * scale_x) + 6;
-            int rpw = std::max(4, std::min(up_rows, 512)) & ~3;
+            int rpw = UP_ROWS;
             while (rpw > 4 && ((int)std::floor((rpw - 1) * scale_y) + 6) * wmax > UP_CAP_PX) rpw -= 4;
             while (rpw > 16 && (long long)nbx * 4 * ((a.dh + rpw - 1) / rpw) * count < 8192) rpw -= rpw > 64 ? 64 : 16;
             const int ncy = (a.dh + rpw - 1) / rpw;
@@ -3048,11 +3022,10 @@ static int launch_cn(const RArgs& a, int count, int interp, double scale_x, doub
             const dim3 sgrid((unsigned)nsx, (unsigned)((a.dh + rps - 1) / rps), (unsigned)count);
             const int ks = interp == IMP_INTER_LINEAR ? 2 : interp == IMP_INTER_CUBIC ? 4 : 8;
             const int pat = ts.strip_a0 * 4 + ts.strip_a1;          // (1,0) 4, (0,1) 1, (1,2) 6, (2,1) 9; rps is a multiple of the 2 * ks row block
-            static const bool no_static = ab_env("IMPGPU_STRIP_DYNAMIC") != nullptr;
-            const bool periodic = !no_static && ts.strip_a0 >= 0 && rps % (2 * ks) == 0;
+            const bool periodic = ts.strip_a0 >= 0 && rps % (2 * ks) == 0;
             const int ve = interp == IMP_INTER_CUBIC ? (a.dw * CN) & ~7 : 0;
             // the patch stores are 16 bytes (BGR: 4) at row start + a multiple of 256 (192): rows and frames aligned to that
-            const int wide = !(((uintptr_t)a.dst | (uintptr_t)a.dstep | (uintptr_t)a.dst_stride) & (CN == 4 ? 15 : 3)) && !ab_env("IMPGPU_STRIP_NARROW");
+            const int wide = !(((uintptr_t)a.dst | (uintptr_t)a.dstep | (uintptr_t)a.dst_stride) & (CN == 4 ? 15 : 3));
 #define IMP_STRIP2(KS_, MODE_, A0_, A1_) hipLaunchKernelGGL((k_resize_strip2<KS_, MODE_, C34, A0_, A1_>), sgrid, block, 0, s, a, ts.xofs, ts.xco, ts.srows, ve, rps, wide)
             if (periodic && interp == IMP_INTER_LINEAR && pat == 4) IMP_STRIP2(2, M_LINEAR, 1, 0);
             else if (periodic && interp == IMP_INTER_LINEAR && pat == 1) IMP_STRIP2(2, M_LINEAR, 0, 1);
@@ -3102,8 +3075,7 @@ __device__ __forceinline__ uint32_t box2x2(uint32_t a, uint32_t b, uint32_t c, u
 }
 
 template <int TX, int TY>      // tile of the halved image: TX columns x TY rows, 4096 pixels or a multiple
-__global__ __launch_bounds__(256) void k_area2x2_rotate_bgra(RArgs a, int amount, int rw, int rh, int ntx, int nty, int count, int order,
-                                                             OverlayArgs wm) {
+__global__ __launch_bounds__(256) void k_area2x2_rotate_bgra(RArgs a, int amount, int rw, int rh, int ntx, int nty, int count, OverlayArgs wm) {
     __shared__ uint32_t tile[TY][TX + 1];                     // odd pitch: the transposed read is bank-conflict free
     // Block order: a group of 8 frames is dealt one frame per XCD (linear id mod 8), and inside a frame the tiles of
     // one tile column are walked top to bottom back to back.  Vertically adjacent tiles store neighbouring column
@@ -3114,8 +3086,7 @@ __global__ __launch_bounds__(256) void k_area2x2_rotate_bgra(RArgs a, int amount
     const int frame = (int)(q / tpf) * 8 + (int)(lin & 7);
     if (frame >= count) return;
     const int t = (int)(q % tpf);
-    int bx, by;
-    if (order) { by = t / ntx; bx = t - by * ntx; } else { bx = t / nty; by = t - bx * nty; }
+    const int bx = t / nty, by = t - bx * nty;
     const uint8_t* S = a.src + (long long)frame * a.src_stride;
     uint8_t* D = a.dst + (long long)frame * a.dst_stride;
     const int rx0 = bx * TX, ry0 = by * TY;                   // tile origin in the halved (pre-rotation) image
@@ -3208,8 +3179,7 @@ __global__ __launch_bounds__(256) void k_area2x2_rotate_bgra(RArgs a, int amount
     }
 }
 
-// Streaming form of the same chain (the default for even halved widths; IMPGPU_CHAIN_STREAM=0 selects the block-tile kernel
-// above): no block-wide phases.  A WAVE owns SW = 128 columns of the halved image and a band of BH = 32 rows; it reads its
+// Streaming form of the same chain (for even halved widths; odd ones take the block-tile kernel above): no block-wide phases.  A WAVE owns SW = 128 columns of the halved image and a band of BH = 32 rows; it reads its
 // two source rows per halved row as one contiguous KB each, four halved rows per batch with the next batch already in
 // flight, boxes them into a wave-private LDS band tile and, once the band is full, writes it out turned: BH pixels per
 // destination row, 16 bytes per lane.  The four waves of a block take four consecutive bands of one strip, so a block
@@ -3293,7 +3263,6 @@ __global__ __launch_bounds__(256) void k_area2x2_turn(RArgs a, int amount, int r
 // geometry is not the exact-2x BGRA case so the caller can fall back to resize + rotate.
 int launch_area2x2_rotate(const Frames& f, int amount, const OverlayArgs* overlay, hipStream_t s) {
     const View& v = f.v;
-    static const int shape = ab_env_int("IMPGPU_CHAIN_TILE", 64);   // measured (profiles/r01_chain_tiles.txt): 64x64 with the column walk
     if (v.c != 4 || (amount != 90 && amount != 270) || (v.w & 1) || (v.h & 1)) return IMP_ERROR_UNSUPPORTED;
     const int rw = v.w / 2, rh = v.h / 2;
     if (rw < 2 || rh < 1) return IMP_ERROR_UNSUPPORTED;
@@ -3302,54 +3271,25 @@ int launch_area2x2_rotate(const Frames& f, int amount, const OverlayArgs* overla
     if (((uintptr_t)f.dst | (uintptr_t)f.dstep | (uintptr_t)f.dst_stride) & 3) return IMP_ERROR_UNSUPPORTED;
     RArgs a{f.src, f.src_stride, v.step, v.w, v.h, f.dst, f.dst_stride, f.dstep, f.dw, f.dh};
     const dim3 block(256);
-    static const int stream_cfg = ab_env_int("IMPGPU_CHAIN_STREAM", 128032);   // SW * 1000 + BH; 0 = the block-tile kernel
-    if (stream_cfg && !(rw & 1)) {
-        OverlayArgs wm0{};
-        if (overlay) wm0 = *overlay;
-        const int sw = stream_cfg / 1000 == 64 ? 64 : 128, bh = stream_cfg % 1000 == 64 ? 64 : (stream_cfg % 1000 == 16 ? 16 : 32);
+    OverlayArgs wm{};
+    if (overlay) wm = *overlay;
+    if (!(rw & 1)) {
+        constexpr int sw = 128, bh = 32;
         const int nstrips = (rw + sw - 1) / sw, nbands = (rh + bh - 1) / bh, bpf = (nstrips * nbands + 3) / 4;
         const dim3 sgrid((unsigned)bpf, (unsigned)((f.count + 7) / 8 * 8));
         const size_t lds = (size_t)4 * bh * (sw + 1) * 4;
-        hipError_t e = hipSuccess;
-#define IMP_TURN(SW_, BH_)                                                                                                        \
-    do {                                                                                                                          \
-        e = lds_limit_once<k_area2x2_turn<SW_, BH_>>();                                                                           \
-        if (e == hipSuccess)                                                                                                      \
-            hipLaunchKernelGGL((k_area2x2_turn<SW_, BH_>), sgrid, block, lds, s, a, amount, rw, rh, nstrips, nbands, bpf, f.count, wm0); \
-    } while (0)
-#ifdef IMPGPU_AB_SWITCHES      // the other strip shapes (IMPGPU_CHAIN_STREAM)
-        if (sw == 64 && bh == 64) IMP_TURN(64, 64);
-        else if (sw == 64 && bh == 32) IMP_TURN(64, 32);
-        else if (sw == 128 && bh == 64) IMP_TURN(128, 64);
-        else if (sw == 128 && bh == 16) IMP_TURN(128, 16);
-        else
-#endif
-        IMP_TURN(128, 32);
-#undef IMP_TURN
-        if (e == hipSuccess) e = hipGetLastError();
+        hipError_t e = lds_limit_once<k_area2x2_turn<sw, bh>>();
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL((k_area2x2_turn<sw, bh>), sgrid, block, lds, s, a, amount, rw, rh, nstrips, nbands, bpf, f.count, wm);
+            e = hipGetLastError();
+        }
         if (e != hipSuccess) { set_error("k_area2x2_turn", e); return IMP_ERROR_DEVICE; }
         return IMP_OK;
     }
-    static const int shape_y = ab_env_int("IMPGPU_CHAIN_TILE_Y", 0);
-    const int tx = shape, ty = shape_y ? shape_y : 4096 / shape;
-    const int ntx = (rw + tx - 1) / tx, nty = (rh + ty - 1) / ty;
-    static const int order = ab_env_int("IMPGPU_CHAIN_ORDER", 0);
+    // odd halved widths: 64x64 block tiles, walked one tile column at a time (profiles/r01_chain_tiles.txt)
+    const int ntx = (rw + 63) / 64, nty = (rh + 63) / 64;
     const dim3 grid((unsigned)(ntx * nty), (unsigned)((f.count + 7) / 8 * 8));
-    OverlayArgs wm{};
-    if (overlay) wm = *overlay;
-#ifdef IMPGPU_AB_SWITCHES      // the other tile shapes of profiles/r01_chain_tiles.txt (IMPGPU_CHAIN_TILE / _TILE_Y)
-    if (tx == 64 && ty == 128) hipLaunchKernelGGL((k_area2x2_rotate_bgra<64, 128>), grid, block, 0, s, a, amount, rw, rh, ntx, nty, f.count, order, wm);
-    else if (tx == 128 && ty == 64) hipLaunchKernelGGL((k_area2x2_rotate_bgra<128, 64>), grid, block, 0, s, a, amount, rw, rh, ntx, nty, f.count, order, wm);
-    else if (tx == 64 && ty == 256) hipLaunchKernelGGL((k_area2x2_rotate_bgra<64, 256>), grid, block, 0, s, a, amount, rw, rh, ntx, nty, f.count, order, wm);
-    else if (tx == 32 && ty == 256) hipLaunchKernelGGL((k_area2x2_rotate_bgra<32, 256>), grid, block, 0, s, a, amount, rw, rh, ntx, nty, f.count, order, wm);
-    else if (tx == 128 && ty == 128) hipLaunchKernelGGL((k_area2x2_rotate_bgra<128, 128>), grid, block, 0, s, a, amount, rw, rh, ntx, nty, f.count, order, wm);
-    else if (tx == 16) hipLaunchKernelGGL((k_area2x2_rotate_bgra<16, 256>), grid, block, 0, s, a, amount, rw, rh, ntx, nty, f.count, order, wm);
-    else if (tx == 32) hipLaunchKernelGGL((k_area2x2_rotate_bgra<32, 128>), grid, block, 0, s, a, amount, rw, rh, ntx, nty, f.count, order, wm);
-    else if (tx == 128) hipLaunchKernelGGL((k_area2x2_rotate_bgra<128, 32>), grid, block, 0, s, a, amount, rw, rh, ntx, nty, f.count, order, wm);
-    else if (tx == 256) hipLaunchKernelGGL((k_area2x2_rotate_bgra<256, 16>), grid, block, 0, s, a, amount, rw, rh, ntx, nty, f.count, order, wm);
-    else
-#endif
-    hipLaunchKernelGGL((k_area2x2_rotate_bgra<64, 64>), grid, block, 0, s, a, amount, rw, rh, ntx, nty, f.count, order, wm);
+    hipLaunchKernelGGL((k_area2x2_rotate_bgra<64, 64>), grid, block, 0, s, a, amount, rw, rh, ntx, nty, f.count, wm);
     IMP_HIP(hipGetLastError());
     return IMP_OK;
 }
@@ -3393,8 +3333,7 @@ static void mix_deal(std::vector<D>& v, M desc, std::vector<D>* sorted_out, MixI
     std::vector<int> order(v.size());
     for (size_t i = 0; i < v.size(); i++) order[i] = (int)i;
     auto cost = [&](int i) { return (long long)desc(v[i]).a.sw * desc(v[i]).a.sh; };
-    static const bool no_sort = ab_env("IMPGPU_MIX_NOSORT") != nullptr;
-    if (!no_sort) std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return cost(x) > cost(y); });
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return cost(x) > cost(y); });
     std::vector<int> list[8];
     long long load[8] = {0};
     for (int i : order) {
@@ -3466,8 +3405,7 @@ int launch_resize_mixed(const MixFrame* fr, int count, int cn, int simple, hipSt
             d.gm = AreaGeom{scale_x, scale_y};
             const bool aligned = !(((uintptr_t)f.src | (uintptr_t)f.sstep) & 3);
             int w4 = 0, bh4 = 0;
-            static const bool no_rows4 = ab_env("IMPGPU_NO_ROWS4") != nullptr;
-            if (!no_rows4 && (cn == 4 || (aligned && f.sw >= 6)) && f.dw >= 160 && area_rows_plan(f.sw, f.sh, f.dw, f.dh, scale_x, count, false, &w4, &bh4) &&
+            if ((cn == 4 || (aligned && f.sw >= 6)) && f.dw >= 160 && area_rows_plan(f.sw, f.sh, f.dw, f.dh, scale_x, count, false, &w4, &bh4) &&
                 w4 >= 2 && w4 <= 5 && 255 * scale_x + w4 + 8 <= (cn == 4 ? 1024 : 1340)) {
                 // windows of at most five pixels (factors below ~3.9): four destination columns per lane, like the uniform batches
                 d.nv = -w4;

@@ -204,9 +204,6 @@ def main():
     ap.add_argument("--pool", default=os.path.join(ROOT, "gpurun_out", "jpeg_pool.bin"))
     ap.add_argument("--answers", default=None)
     ap.add_argument("--hw-queues", type=int, default=0, help="GPU_MAX_HW_QUEUES for the broker (0: the runtime's default, 4)")
-    ap.add_argument("--split-kb", type=int, default=0, help="a launch takes files up to so many KB, or above (A/B)")
-    ap.add_argument("--pipeline", type=int, default=0, help="0: the broker's lanes take one batch at a time (A/B)")
-    ap.add_argument("--cu-split", type=int, default=0, help="IMPGPU_LANE_CU_SPLIT for the broker: every lane on its own n-th of the CUs")
     ap.add_argument("--query", default=None, help="the request's query string (default resize=224,0 through worker_harness)")
     ap.add_argument("--watermark", default=None, metavar="GX,GY,OX,OY,OPACITY", help="a location watermark with this placement")
     ap.add_argument("--check", action="store_true", help="with --query: compare every answer with the oracle's file")
@@ -244,9 +241,7 @@ def main():
             env = {}
             if args.hw_queues:
                 env["GPU_MAX_HW_QUEUES"] = str(args.hw_queues)
-            if args.cu_split:
-                env["IMPGPU_LANE_CU_SPLIT"] = str(args.cu_split)
-            broker = start_broker(name, args.threads, args.gather_us, env=env or None, extra=["--pipeline", str(args.pipeline), "--split-kb", str(args.split_kb)])
+            broker = start_broker(name, args.threads, args.gather_us, env=env or None)
         try:
             r = run_point(args.pool, args.mode, n, args.seconds, args.answers, name, query=args.query, overlay=overlay,
                           placement=args.watermark)
@@ -257,8 +252,6 @@ def main():
                 r["broker_threads"] = args.threads
                 r["gather_us"] = args.gather_us
                 r["hw_queues"] = args.hw_queues or 8
-                r["cu_split"] = args.cu_split
-                r["pipeline"] = args.pipeline
             print(json.dumps(r), flush=True)
         finally:
             if broker:
