@@ -381,12 +381,19 @@ int impgpu_run_ops(impgpu_image** pointer, const impgpu_job* job, const impgpu_c
 /* The operator segment of RunJob (impgpu_run_ops) for `count` independent requests at once -- a request queue's worth, each
  * with its own job and config.  On return images[i], codes[i] and steps[i] are exactly what
  * impgpu_run_ops(&images[i], &jobs[i], configs[i], &steps[i]) would have left, in request order; the fault points
- * (impgpu_fault_arm) are entered in the same order as by that loop.  A single BGR / BGRA frame whose chain is
- * [crop ->] resize (general INTER_AREA) [-> one filter-rotate] [-> a BGRA overlay] [-> flatten] rides ONE launch per channel
- * count with every other such request, the tail on the resize's stores (bare resizes share the launch of
- * impgpu_batch_resize_mixed); every other request goes through impgpu_run_ops inside the call.  launches (may be NULL)
- * receives the number of kernels enqueued.  IMP_ERROR_INVALID_ARGS with nothing enqueued when the arguments are malformed
- * (NULL arrays, count < 0 or > 4096, the same handle twice); IMP_ERROR_DEVICE without an env (every codes[i] says so too);
+ * (impgpu_fault_arm) are entered in the same order as by that loop, before anything is launched.  A single BGR / BGRA
+ * frame whose chain is [crop ->] resize (general INTER_AREA) [-> one filter-rotate] [-> a BGRA overlay] [-> flatten] rides
+ * ONE launch per channel count with every other such request, the tail on the resize's stores (bare resizes share the
+ * launch of impgpu_batch_resize_mixed).  Any other single BGR / BGRA frame whose chain is [crop ->] resize -> any filters
+ * -> [watermark] -> [flatten] shares launches in rounds: the resizes first, then round k launches the k-th segment of every
+ * chain that has one -- a run of pointwise filters (with the watermark and the flatten when it is the last), a blur, or a
+ * flip / turn -- one launch per kind and channel count, so the number of launches follows the chains' length, not the
+ * number of requests.  Resizes launch_resize_mixed does not gather (integer factors, enlargements) and blurs outside the
+ * one-pass forms (large radii) still take a launch per request inside their round.  Albums, gray frames, requests
+ * without a resize and requests whose arguments fail (a bad filter, too many filters, a watermark that does not fit) go
+ * through impgpu_run_ops inside the call.  A shared launch that fails gives each of its requests IMP_ERROR_DEVICE with the
+ * step of the segment it ran.  launches (may be NULL) receives the number of kernels enqueued.  IMP_ERROR_INVALID_ARGS
+ * with nothing enqueued when the arguments are malformed (NULL arrays, count < 0 or > 4096, the same handle twice); IMP_ERROR_DEVICE without an env (every codes[i] says so too);
  * otherwise IMP_OK, and the verdicts are in codes[].  Asynchronous on the env stream, like impgpu_run_ops. */
 int impgpu_batch_run_ops(impgpu_image** images, const impgpu_job* jobs, const impgpu_config* const* configs,
                          int count, int* codes, int* steps, int* launches);

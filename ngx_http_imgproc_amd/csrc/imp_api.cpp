@@ -124,24 +124,44 @@ int do_watermark(Work& wk, const impgpu_config* cfg) {
                              rx, ry, maxcol, maxrow, alpha, env_stream());
 }
 
-// What impgpu_batch_run_ops needs to know to put a request on the mixed launch instead of impgpu_run_ops: a single colour
-// frame, [crop ->] resize (general INTER_AREA that launch_area_rotate takes) [-> one quarter or half turn] [-> a BGRA overlay
-// watermark_rect places] [-> flatten].  Host-only, no fault point entered: a request this refuses goes to impgpu_run_ops whole.
-struct FusedPlan {
-    View v;                 // the source window (after the crop)
-    int w, h;               // the resized geometry
-    int rot;                // 0 when the request has no filter
-    bool turn;              // its one filter is the turn
-    bool has_wm;
-    OverlayArgs wm;
-    bool flat;
-    int fw, fh;             // the final frame
+// What impgpu_batch_run_ops needs to know to run a request in shared launches instead of through impgpu_run_ops: a single
+// colour frame whose chain is [crop ->] resize -> any filters -> [watermark] -> [flatten], every decision made here on the
+// host.  Host-only, no fault point entered: a request this refuses goes to impgpu_run_ops whole.
+// The resize is launch_resize_mixed, or the row-streaming AREA kernel with a tail on its stores (k_resize_area_mix_tail,
+// the one acceptance test area_tail_plan) when something rides there: the first filter when it is a turn, as impgpu_run_ops
+// fuses it (with the overlay when the turn is the only filter and the overlay is BGRA, as that launch carries it too), and
+// -- when nothing but the watermark and the flatten follows the resize -- the tail.  The rest of the chain is a list of
+// segments, each one launch of its own kind: a pointwise run (do_filter's PixelProgram, cut where launch_pixel_program cuts
+// it), a barrier (one blur, flip or turn), and the tail -- the last run, the watermark and the flatten as one per-pixel pass.
+enum SegKind { SEG_PIXEL = 0, SEG_BLUR, SEG_GEOM };
+struct Segment {
+    int kind;
+    int step;                   // what a failure of its launch reports
+    PixelProgram prog;          // SEG_PIXEL
+    bool has_wm, flat;          // SEG_PIXEL: the tail's watermark / flatten
+    FilterPlan plan;            // SEG_BLUR / SEG_GEOM
+    int w, h;                   // the frame entering the segment
+};
+struct ChainPlan {
+    View v;                     // the source window (after the crop)
+    int w, h, interp;           // the resize
+    int fw, fh;                 // the frame the resize launch leaves (turned when rot is 90 / 270)
+    int rot;                    // first filter turned on the AREA stores (0: none)
+    bool wm_turn;               // the overlay rides the turn's launch, as in impgpu_run_ops: part of the resize step
+    bool fold_wm, fold_flat;    // the tail (watermark, flatten) folded onto the resize's stores
+    std::vector<Segment> segs;
+    OverlayArgs wm;             // the overlay's placement on the final frame
 };
 
-bool fused_plan(const impgpu_image* im, const impgpu_job* job, const impgpu_config* cfg, FusedPlan* p) {
-    if (!im || !job || !cfg || im->frames != 1 || (im->c != 3 && im->c != 4) || !job->resize) return false;
+static bool bgra_overlay(const impgpu_image* ov) {                    // what the resize tail's overlay path takes
+    return ov && ov->c == 4 && !(((uintptr_t)ov->d | (uintptr_t)ov->step) & 3);
+}
+
+bool chain_plan(const impgpu_image* im, const impgpu_job* job, const impgpu_config* cfg, ChainPlan* p) {
+    if (!im || !job || !cfg || im->frames != 1 || (im->c != 3 && im->c != 4) || !job->resize || job->filter_count < 0) return false;
     if (cfg->max_filters_count > 0 && job->filter_count > cfg->max_filters_count) return false;
-    if (job->filter_count < 0 || job->filter_count > 1 || (job->filter_count == 1 && (!job->filters || !job->filters[0]))) return false;
+    if (job->filter_count > 0 && !job->filters) return false;
+    for (int i = 0; i < job->filter_count; i++) if (!job->filters[i]) return false;
     View v = view_of(im);
     if (job->crop) {
         int x, y, w, h;
@@ -149,35 +169,80 @@ bool fused_plan(const impgpu_image* im, const impgpu_job* job, const impgpu_conf
         v = view_sub(v, x, y, w, h);
     }
     int w, h, interp;
-    if (resize_geometry(v.w, v.h, job->resize, cfg->max_target_w, cfg->max_target_h, job->simple, &w, &h, &interp) != IMP_OK ||
-        interp != IMP_INTER_AREA)
-        return false;
-    p->rot = 0;
-    p->turn = job->filter_count == 1;
-    if (p->turn) {                                                     // impgpu_run_ops' first-filter rule
+    if (resize_geometry(v.w, v.h, job->resize, cfg->max_target_w, cfg->max_target_h, job->simple, &w, &h, &interp) != IMP_OK) return false;
+    const int c = v.c;
+    const impgpu_image* ov = cfg->watermark;
+    p->v = v; p->w = w; p->h = h; p->interp = interp; p->rot = 0;
+    p->wm_turn = p->fold_wm = p->fold_flat = false;
+    p->wm = OverlayArgs{};
+    p->segs.clear();
+    // does the AREA kernel with a tail take this resize, turned by `rot`?
+    auto tail_takes = [&](int rot) {
+        if (interp != IMP_INTER_AREA) return false;
+        const bool swap = rot == 90 || rot == 270;
+        Frames f{};
+        f.src = v.d; f.v = v; f.dw = w; f.dh = h; f.dstep = aligned_step(swap ? h : w, c); f.count = 1;
+        int ww, bh;
+        return area_tail_plan(f, &ww, &bh);
+    };
+    int cw = w, ch = h, i0 = 0;
+    if (job->filter_count >= 1 && interp == IMP_INTER_AREA) {          // impgpu_run_ops' first-filter rule
         FilterPlan first;
         PixelProgram none;
-        if (filter_plan(job->filters[0], cfg->allow_experiments, v.c, w, h, &first, &none) != IMP_OK || first.cls != FC_ROTATE) return false;
-        p->rot = first.rotate;
+        if (filter_plan(job->filters[0], cfg->allow_experiments, c, w, h, &first, &none) == IMP_OK && first.cls == FC_ROTATE &&
+            tail_takes(first.rotate)) {
+            const bool swap = first.rotate != 180;
+            p->rot = first.rotate;
+            cw = swap ? h : w; ch = swap ? w : h;
+            i0 = 1;
+        }
     }
-    const bool swap = p->rot == 90 || p->rot == 270;
-    p->fw = swap ? h : w;
-    p->fh = swap ? w : h;
-    Frames f{};
-    f.src = v.d; f.v = v; f.dw = w; f.dh = h; f.dstep = aligned_step(p->fw, v.c); f.count = 1;
-    int ww, bh;
-    if (!area_tail_plan(f, &ww, &bh)) return false;
-    p->has_wm = false;
-    p->wm = OverlayArgs{};
-    if (const impgpu_image* ov = cfg->watermark) {                     // the fused lone path's condition (impgpu_run_ops)
-        if (ov->c != 4 || (((uintptr_t)ov->d | (uintptr_t)ov->step) & 3)) return false;
-        if (watermark_rect(p->fw, p->fh, ov->w, ov->h, cfg, &p->wm.rx, &p->wm.ry, &p->wm.maxcol, &p->wm.maxrow) != IMP_OK) return false;
+    p->fw = cw; p->fh = ch;
+    auto push_runs = [&](const PixelProgram& prog, PixelProgram* tail) {
+        std::vector<PixelProgram> parts;
+        if (!prog.empty()) split_program(prog, &parts);
+        for (size_t k = 0; k < parts.size(); k++) {
+            if (tail && k + 1 == parts.size()) { *tail = parts[k]; break; }
+            Segment sg{};
+            sg.kind = SEG_PIXEL; sg.step = IMP_STEP_FILTERING; sg.prog = parts[k]; sg.w = cw; sg.h = ch;
+            p->segs.push_back(sg);
+        }
+    };
+    PixelProgram prog;
+    for (int i = i0; i < job->filter_count; i++) {                     // do_filter, planned
+        FilterPlan plan;
+        if (filter_plan(job->filters[i], cfg->allow_experiments, c, cw, ch, &plan, &prog) != IMP_OK) return false;
+        if (plan.cls == FC_POINTWISE || plan.cls == FC_NOOP) continue;
+        push_runs(prog, nullptr);
+        prog.clear();
+        Segment sg{};
+        sg.kind = plan.cls == FC_BLUR ? SEG_BLUR : SEG_GEOM;
+        sg.step = IMP_STEP_FILTERING; sg.plan = plan; sg.w = cw; sg.h = ch;
+        p->segs.push_back(sg);
+        if (plan.cls == FC_ROTATE && plan.rotate != 180) std::swap(cw, ch);
+    }
+    Segment tail{};
+    tail.kind = SEG_PIXEL; tail.w = cw; tail.h = ch;
+    push_runs(prog, &tail.prog);
+    if (ov) {                                                          // do_watermark, planned
+        if (c < 3 || ov->c < 3) return false;
+        if (watermark_rect(cw, ch, ov->w, ov->h, cfg, &p->wm.rx, &p->wm.ry, &p->wm.maxcol, &p->wm.maxrow) != IMP_OK) return false;
         p->wm.ov = ov->d; p->wm.ostep = ov->step;
-        p->wm.alpha = 1 - (float)(cfg->watermark_opacity / 100.0);     // bridge.c:275, filters.c:620
-        p->has_wm = true;
+        p->wm.alpha = 1 - (float)(cfg->watermark_opacity / 100.0);    // bridge.c:275, filters.c:620
+        // impgpu_run_ops' turn launch carries the overlay when the turn is the only filter (its watermark step is then done)
+        p->wm_turn = p->rot != 0 && job->filter_count == 1 && bgra_overlay(ov);
+        tail.has_wm = !p->wm_turn;
     }
-    p->flat = job->need_flatten && v.c == 4;
-    p->v = v; p->w = w; p->h = h;
+    tail.flat = job->need_flatten && c == 4;
+    // nothing but the watermark and the flatten after the resize: they ride the resize's stores
+    if (p->segs.empty() && tail.prog.empty() && (tail.has_wm || tail.flat) && (!tail.has_wm || bgra_overlay(ov)) &&
+        (p->rot != 0 || tail_takes(0))) {
+        p->fold_wm = tail.has_wm;
+        p->fold_flat = tail.flat;
+        return true;
+    }
+    tail.step = tail.prog.empty() ? IMP_STEP_WATERMARK : IMP_STEP_FILTERING;
+    if (!tail.prog.empty() || tail.has_wm || tail.flat) p->segs.push_back(tail);
     return true;
 }
 
@@ -522,16 +587,20 @@ int impgpu_batch_run_ops(impgpu_image** images, const impgpu_job* jobs, const im
     const unsigned long long launched = t_launches;
     hipStream_t s = env_stream();
     // per channel count (index c - 3): requests with a tail -> k_resize_area_mix_tail, bare resizes -> launch_resize_mixed
+    // (NN resizes of `simple` requests: a launch_resize_mixed of their own)
     std::vector<TailItem> tails[2];
-    std::vector<MixFrame> bares[2];
-    std::vector<int> tail_who[2], bare_who[2];
+    std::vector<MixFrame> bares[2], nns[2];
+    std::vector<int> tail_who[2], bare_who[2], nn_who[2];
     std::vector<impgpu_image*> outs((size_t)count, nullptr);
     std::vector<int> final_code((size_t)count, IMP_OK), final_step((size_t)count, IMP_STEP_INFO);
+    std::vector<ChainPlan> chains((size_t)count);
+    std::vector<int> nsegs((size_t)count, 0);                          // segments a chain request runs (fewer when a fault cuts it)
+    size_t rounds = 0;
     for (int i = 0; i < count; i++) {
         const impgpu_job* job = &jobs[i];
         const impgpu_config* cfg = configs[i];
-        FusedPlan p;
-        if (!fused_plan(images[i], job, cfg, &p)) {
+        ChainPlan& cp = chains[(size_t)i];
+        if (!chain_plan(images[i], job, cfg, &cp)) {
             codes[i] = impgpu_run_ops(&images[i], job, cfg, &steps[i]);
             continue;
         }
@@ -541,47 +610,139 @@ int impgpu_batch_run_ops(impgpu_image** images, const impgpu_job* jobs, const im
         if (job->crop && fault_hit(IMP_STEP_CROP)) continue;
         steps[i] = IMP_STEP_RESIZE;
         if (fault_hit(IMP_STEP_RESIZE)) continue;
-        bool has_wm = p.has_wm, flat = p.flat;
         int failed = -1;
         if (job->filter_count > 0 && fault_hit(IMP_STEP_FILTERING)) failed = IMP_STEP_FILTERING;
         else if (cfg->watermark && fault_hit(IMP_STEP_WATERMARK)) failed = IMP_STEP_WATERMARK;
+        int n = (int)cp.segs.size();
         if (failed >= 0) {
-            // impgpu_run_ops fails behind its resize: the frame it leaves is resized -- and turned, with the overlay its turning
-            // launch carried -- and never flattened
+            // impgpu_run_ops fails behind its resize step (which carries the turn, and the overlay the turn's launch carries):
+            // at FILTERING the frame is the resized one; at WATERMARK the filtered one -- never overlaid after the filters, never
+            // flattened
             final_code[(size_t)i] = IMP_ERROR_DEVICE;
             final_step[(size_t)i] = failed;
-            has_wm = has_wm && p.turn;
-            flat = false;
+            cp.fold_wm = cp.fold_flat = false;
+            if (failed == IMP_STEP_FILTERING) n = 0;
+            else if (n > 0 && cp.segs.back().kind == SEG_PIXEL && (cp.segs.back().has_wm || cp.segs.back().flat)) {
+                Segment& t = cp.segs.back();
+                t.has_wm = t.flat = false;
+                if (t.prog.empty()) n--;
+            }
         }
+        nsegs[(size_t)i] = n;
+        rounds = std::max(rounds, (size_t)n);
         impgpu_image* out = nullptr;
-        if (int rc = image_new_album(p.fw, p.fh, p.v.c, 1, &out)) { codes[i] = rc; continue; }      // (as Work::fresh)
+        if (int rc = image_new_album(cp.fw, cp.fh, cp.v.c, 1, &out)) { codes[i] = rc; nsegs[(size_t)i] = 0; continue; }   // (as Work::fresh)
         outs[(size_t)i] = out;
-        const int k = p.v.c - 3;
-        if (p.rot == 0 && !has_wm && !flat) {
-            bares[k].push_back(MixFrame{p.v.d, p.v.w, p.v.h, p.v.step, out->d, p.w, p.h, out->step});
-            bare_who[k].push_back(i);
-        } else {
-            tails[k].push_back(TailItem{p.v, out->d, p.w, p.h, out->step, p.rot, has_wm, p.wm, flat});
+        const int k = images[i]->c - 3;
+        const bool on_stores = cp.wm_turn || cp.fold_wm;
+        if (cp.rot || on_stores || cp.fold_flat) {
+            tails[k].push_back(TailItem{cp.v, out->d, cp.w, cp.h, out->step, cp.rot, on_stores, on_stores ? cp.wm : OverlayArgs{}, cp.fold_flat});
             tail_who[k].push_back(i);
+        } else if (job->simple) {
+            nns[k].push_back(MixFrame{cp.v.d, cp.v.w, cp.v.h, cp.v.step, out->d, cp.w, cp.h, out->step});
+            nn_who[k].push_back(i);
+        } else {
+            bares[k].push_back(MixFrame{cp.v.d, cp.v.w, cp.v.h, cp.v.step, out->d, cp.w, cp.h, out->step});
+            bare_who[k].push_back(i);
         }
     }
+    // round 0: every resize.  A request whose launch fails keeps its frame and stops there.
     auto settle = [&](const std::vector<int>& who, int rc) {
         for (int i : who) {
             if (rc != IMP_OK) {                                         // the launch failed: the request keeps its frame
                 image_delete(outs[(size_t)i]);
-                codes[i] = rc;
+                outs[(size_t)i] = nullptr;
+                codes[i] = IMP_ERROR_DEVICE;
                 steps[i] = IMP_STEP_RESIZE;
+                nsegs[(size_t)i] = 0;
                 continue;
             }
             image_delete(images[i]);                                    // (pool memory: recycled in stream order, behind the launch)
             images[i] = outs[(size_t)i];
+            outs[(size_t)i] = nullptr;
             codes[i] = final_code[(size_t)i];
             steps[i] = final_step[(size_t)i];
         }
     };
     for (int k = 0; k < 2; k++) {
         if (!bares[k].empty()) settle(bare_who[k], launch_resize_mixed(bares[k].data(), (int)bares[k].size(), k + 3, 0, s));
+        if (!nns[k].empty()) settle(nn_who[k], launch_resize_mixed(nns[k].data(), (int)nns[k].size(), k + 3, 1, s));
         if (!tails[k].empty()) settle(tail_who[k], launch_area_tail_mixed(tails[k].data(), (int)tails[k].size(), k + 3, s));
+    }
+    // rounds 1 ..: segment r of every chain that has one, one launch per (kind, channel count) -- and the blur forms no mixed
+    // kernel takes one request at a time.  Barriers write fresh frames (pool memory, released in stream order behind the
+    // launch); pointwise segments work in place.
+    auto fail = [&](int i, int rc, int step) {
+        codes[i] = rc;
+        steps[i] = step;
+        nsegs[(size_t)i] = 0;
+    };
+    for (size_t r = 0; r < rounds; r++) {
+        std::vector<PixelTailItem> pix[2];
+        std::vector<GeomItem> geo[2];
+        std::vector<BlurItem> blu[2];
+        std::vector<int> pix_who[2], geo_who[2], blu_who[2];
+        for (int i = 0; i < count; i++) {
+            if ((size_t)nsegs[(size_t)i] <= r) continue;
+            const ChainPlan& cp = chains[(size_t)i];
+            const Segment& sg = cp.segs[r];
+            impgpu_image* cur = images[i];
+            const int k = cur->c - 3;
+            if (sg.kind == SEG_PIXEL) {
+                PixelTailItem it{};
+                it.d = cur->d; it.w = cur->w; it.h = cur->h; it.step = cur->step; it.prog = &sg.prog;
+                if (sg.has_wm) {
+                    it.has_wm = true; it.ov = configs[i]->watermark;
+                    it.rx = cp.wm.rx; it.ry = cp.wm.ry; it.maxcol = cp.wm.maxcol; it.maxrow = cp.wm.maxrow; it.alpha = cp.wm.alpha;
+                }
+                it.flatten = sg.flat;
+                pix[k].push_back(it);
+                pix_who[k].push_back(i);
+                continue;
+            }
+            const bool mixable = sg.kind == SEG_GEOM ||
+                                 blur_form(cur->w, cur->h, cur->c, !(((uintptr_t)cur->d | (uintptr_t)cur->step) & 3), sg.plan.sigma) == BLUR_MIXABLE;
+            if (!mixable) {                                             // a blur form of its own: launched alone, as apply_plan does
+                Work wk{cur, view_of(cur)};
+                const int rc = apply_plan(wk, sg.plan);
+                images[i] = wk.owner;
+                if (rc) fail(i, rc, sg.step);
+                continue;
+            }
+            const bool swap = sg.kind == SEG_GEOM && sg.plan.cls == FC_ROTATE && sg.plan.rotate != 180;
+            impgpu_image* out = nullptr;
+            if (int rc = image_new_album(swap ? cur->h : cur->w, swap ? cur->w : cur->h, cur->c, 1, &out)) { fail(i, rc, sg.step); continue; }
+            outs[(size_t)i] = out;
+            if (sg.kind == SEG_GEOM) {
+                const bool turn = sg.plan.cls == FC_ROTATE;
+                geo[k].push_back(GeomItem{cur->d, cur->w, cur->h, cur->step, out->d, out->w, out->h, out->step, turn ? 1 : 0,
+                                          turn ? sg.plan.rotate : sg.plan.flip_mode});
+                geo_who[k].push_back(i);
+            } else {
+                blu[k].push_back(BlurItem{cur->d, out->d, cur->w, cur->h, cur->step, out->step, (double)sg.plan.sigma});
+                blu_who[k].push_back(i);
+            }
+        }
+        auto adopt = [&](const std::vector<int>& who, int rc) {        // a barrier's launch is done: its fresh frames replace the old
+            for (int i : who) {
+                if (rc != IMP_OK) {
+                    image_delete(outs[(size_t)i]);
+                    fail(i, IMP_ERROR_DEVICE, chains[(size_t)i].segs[r].step);
+                } else {
+                    image_delete(images[i]);
+                    images[i] = outs[(size_t)i];
+                }
+                outs[(size_t)i] = nullptr;
+            }
+        };
+        for (int k = 0; k < 2; k++) {
+            if (!pix[k].empty()) {
+                const int rc = launch_pixel_tail_mixed(pix[k].data(), (int)pix[k].size(), k + 3, s);
+                if (rc) for (int i : pix_who[k]) fail(i, IMP_ERROR_DEVICE, chains[(size_t)i].segs[r].step);
+            }
+            if (!geo[k].empty()) adopt(geo_who[k], launch_geom_mixed(geo[k].data(), (int)geo[k].size(), k + 3, s));
+            if (!blu[k].empty()) adopt(blu_who[k], launch_blur_mixed(blu[k].data(), (int)blu[k].size(), k + 3, s));
+        }
     }
     if (launches) *launches = (int)(t_launches - launched);
     return IMP_OK;

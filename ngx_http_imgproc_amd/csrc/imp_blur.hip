@@ -117,12 +117,12 @@ __global__ __launch_bounds__(256) void k_blur_col_any(const int* __restrict__ tm
 // (3 w) % 4 elements of a row take SymmColumnVec's scalar tail, (sum + 2^15) >> 16 on integers, like the CPU.
 typedef short bl_short2 __attribute__((ext_vector_type(2)));
 
+// The tile body: output tile (tx0, ty0) of frame S -> D.  k_blur_fused4 (a grid over equal frames) and k_blur_mix (a
+// descriptor per frame) both run it.
 template <int TH, int CN>
-__global__ __launch_bounds__(256) void k_blur_fused4(const uint8_t* __restrict__ src, long long sstride, int sstep, int w, int h,
-                                                     uint8_t* __restrict__ dst, long long dstride, int dstep,
-                                                     const int* __restrict__ kxp, const float* __restrict__ kyf,
-                                                     const int* __restrict__ kyi, int rx, int ry) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+__device__ __forceinline__ void blur_fused4_tile(const uint8_t* __restrict__ S, int sstep, int w, int h, uint8_t* __restrict__ D, int dstep,
+                                                 const int* __restrict__ kxp, const float* __restrict__ kyf,
+                                                 const int* __restrict__ kyi, int rx, int ry, int tx0, int ty0, uint8_t* smem) {
     const int SW = 64 + 2 * rx + 2, SH = TH + 2 * ry;         // +2: the padded last tap pair reads one dword further
     const int npair = rx + 1;                                 // 2*rx+1 taps -> rx+1 pairs, last one (tap, 0)
     uint32_t* s_kx = (uint32_t*)smem;                         // packed (k[2j], k[2j+1]) as 2 x i16
@@ -131,8 +131,6 @@ __global__ __launch_bounds__(256) void k_blur_fused4(const uint8_t* __restrict__
     uint32_t* s_src = (uint32_t*)(s_kyi + ((ry + 1 + 3) & ~3));
     uint2* s_pl = (uint2*)(s_src + ((SW * SH + 3) & ~3));     // [SH][64] x 4 x u16
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int tx0 = blockIdx.x * 64, ty0 = blockIdx.y * TH;
-    const uint8_t* S = src + (long long)blockIdx.z * sstride;
     for (int i = tid; i < npair; i += 256) s_kx[i] = (uint32_t)kxp[i];
     for (int i = tid; i <= ry; i += 256) { s_ky[i] = kyf[i]; s_kyi[i] = kyi[i]; }
 
@@ -214,7 +212,7 @@ __global__ __launch_bounds__(256) void k_blur_fused4(const uint8_t* __restrict__
             if (CN == 4) {
                 const uint32_t o = (uint32_t)sat8(__float2int_rn(s0)) | ((uint32_t)sat8(__float2int_rn(s1)) << 8) |
                                    ((uint32_t)sat8(__float2int_rn(s2)) << 16) | ((uint32_t)sat8(__float2int_rn(s3)) << 24);
-                *(uint32_t*)(dst + (long long)blockIdx.z * dstride + (size_t)y * dstep + (size_t)x * 4) = o;
+                *(uint32_t*)(D + (size_t)y * dstep + (size_t)x * 4) = o;
             } else {
                 int o[3] = {sat8(__float2int_rn(s0)), sat8(__float2int_rn(s1)), sat8(__float2int_rn(s2))};
                 const int vec_end = (w * 3) & ~3;                   // SymmColumnVec_32s8u covers whole groups of 4 elements
@@ -234,11 +232,21 @@ __global__ __launch_bounds__(256) void k_blur_fused4(const uint8_t* __restrict__
                         if (x * 3 + ch >= vec_end) o[ch] = sat8(ti[ch]);
                     }
                 }
-                uint8_t* q = dst + (long long)blockIdx.z * dstride + (size_t)y * dstep + (size_t)x * 3;
+                uint8_t* q = D + (size_t)y * dstep + (size_t)x * 3;
                 q[0] = (uint8_t)o[0]; q[1] = (uint8_t)o[1]; q[2] = (uint8_t)o[2];
             }
         }
     }
+}
+
+template <int TH, int CN>
+__global__ __launch_bounds__(256) void k_blur_fused4(const uint8_t* __restrict__ src, long long sstride, int sstep, int w, int h,
+                                                     uint8_t* __restrict__ dst, long long dstride, int dstep,
+                                                     const int* __restrict__ kxp, const float* __restrict__ kyf,
+                                                     const int* __restrict__ kyi, int rx, int ry) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    blur_fused4_tile<TH, CN>(src + (long long)blockIdx.z * sstride, sstep, w, h, dst + (long long)blockIdx.z * dstride, dstep,
+                             kxp, kyf, kyi, rx, ry, blockIdx.x * 64, blockIdx.y * TH, smem);
 }
 
 // ------------------------------------------------------------------ large radii: column strips with an LDS ring
@@ -639,20 +647,17 @@ __global__ __launch_bounds__(256) void k_blur_mfma_cols(const uint8_t* __restric
 // Both passes in ONE launch for the radii whose tile fits LDS twice per compute unit: the rows of the tile AND its 2r halo rows
 // are reduced into the transposed planes in LDS (never in memory), then the columns.  The halo rows are reduced once per tile
 // row they border (x (64 + 2r) / 64 of the row pass: the matrix unit has the time), the row sums never leave the chip.
+// The tile body: tile (tbx, tby) of frame `frame` -> `out`.  k_blur_mfma_fused (a grid over equal frames) and k_blur_mix
+// (a descriptor per frame) both run it.
 template <int CN, bool WIDE>
-__global__ __launch_bounds__(256) void k_blur_mfma_fused(const uint8_t* __restrict__ src, long long sstride, int sstep, int w, int h,
-                                                         uint8_t* __restrict__ dst, long long dstride, int dstep,
-                                                         const bm_v4i* __restrict__ bands_r, const bm_v4i* __restrict__ bands_c, int r, int nrc, int ncc,
-                                                         int pitch_s, int pitch_p, int bias_r, int bias_c) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t bm_smem[];
+__device__ __forceinline__ void blur_mfma_fused_tile(const uint8_t* __restrict__ frame, int sstep, int w, int h, uint8_t* __restrict__ out, int dstep,
+                                                     const bm_v4i* __restrict__ bands_r, const bm_v4i* __restrict__ bands_c, int r, int nrc, int ncc,
+                                                     int pitch_s, int pitch_p, int bias_r, int bias_c, int tbx, int tby, uint8_t* bm_smem) {
     const int nr16 = (BM_H + 2 * r + 15) & ~15;                     // staged rows: image rows y0 - r .. (replicated past the borders)
     uint8_t* s_src = bm_smem;                                       // [nr16][pitch_s]
     uint8_t* s_pl = bm_smem + (size_t)nr16 * pitch_s;               // [2 or 3][BM_W][pitch_p], row 0 = image row y0 - r
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    int tbx, tby, tbz;
-    bm_xcd_tile<false>(&tbx, &tby, &tbz);
     const int x0b = tbx * BM_W, y0 = tby * BM_H, roww = w * CN;
-    const uint8_t* frame = src + (long long)tbz * sstride;
     const int wbytes = BM_W + 2 * CN * r, wq = (wbytes + 15) >> 4;
     for (int idx = t; idx < nr16 * wq; idx += 256) {
         const int ry = idx / wq, bc = (idx - ry * wq) * 16;
@@ -703,7 +708,6 @@ __global__ __launch_bounds__(256) void k_blur_mfma_fused(const uint8_t* __restri
 #pragma unroll
     for (int c = 0; c < 3; c++) bandc[c] = c < ncc ? bands_c[c * 64 + lane] : bm_v4i{0, 0, 0, 0};
     __syncthreads();
-    uint8_t* out = dst + (long long)tbz * dstride;
     const int vec_end = roww & ~3;
     for (int tile = wv; tile < (BM_W / 16) * (BM_H / 16); tile += 4) {
         const int xg = tile & 3, og = tile >> 2;
@@ -734,27 +738,60 @@ __global__ __launch_bounds__(256) void k_blur_mfma_fused(const uint8_t* __restri
     }
 }
 
+template <int CN, bool WIDE>
+__global__ __launch_bounds__(256) void k_blur_mfma_fused(const uint8_t* __restrict__ src, long long sstride, int sstep, int w, int h,
+                                                         uint8_t* __restrict__ dst, long long dstride, int dstep,
+                                                         const bm_v4i* __restrict__ bands_r, const bm_v4i* __restrict__ bands_c, int r, int nrc, int ncc,
+                                                         int pitch_s, int pitch_p, int bias_r, int bias_c) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t bm_smem[];
+    int tbx, tby, tbz;
+    bm_xcd_tile<false>(&tbx, &tby, &tbz);
+    blur_mfma_fused_tile<CN, WIDE>(src + (long long)tbz * sstride, sstep, w, h, dst + (long long)tbz * dstride, dstep, bands_r, bands_c,
+                                   r, nrc, ncc, pitch_s, pitch_p, bias_r, bias_c, tbx, tby, bm_smem);
+}
+
 // The two launches above.  IMP_ERROR_UNSUPPORTED when the exactness conditions (taps <= 127, sum <= 257) or the size limits
 // do not hold: the caller goes on to the VALU kernels.
-static int launch_gaussian_mfma(const Frames& f, const std::vector<int>& ik, int r, hipStream_t s) {
-    const View& v = f.v;
+// The matrix-unit form's geometry for taps `ik` (radius r) on frames of cn channels: false when its exactness conditions
+// (taps <= 127, sum <= 257 or the wide form's 260) or its chunk limits do not hold.  Shared by the lone launch and blur_form.
+struct MfmaGeom { long long sum; bool wide; int npl, nrc, ncc, pitch_s, pitch_p; size_t lds_f; bool fused; };
+static bool mfma_geom(const std::vector<int>& ik, int r, int cn, MfmaGeom* g) {
     long long sum = 0;
     int top = 0;
     for (int k : ik) { sum += k; top = std::max(top, k); }
     // (taps are operands of the i8 MFMA; 2 * 255 * sum * top < 2^24 keeps every product of OpenCV's float column pass exact)
-    if (top > 127 || sum > 511 || 2LL * 255 * sum * top >= (1LL << 24) || r < 1 || 2 * r + 1 > 250) return IMP_ERROR_UNSUPPORTED;
+    if (top > 127 || sum > 511 || 2LL * 255 * sum * top >= (1LL << 24) || r < 1 || 2 * r + 1 > 250) return false;
     // Tap sums of 258 .. 260 (eleven of the sigmas 0.5 .. 25.0 in steps of 0.1, sigma = 4 among them) make row sums of 17
     // bits: a third byte plane holds bit 16 and the column pass takes a third MFMA per chunk (round 5; those sigmas ran on
     // the VALU kernels before).  The column sum is exact all the same: a partial sum can only round in float once it is past
     // 256.0, and then the pixel saturates to 255 whatever the rounding did.
-    const bool wide = sum > 257;
-    const int npl = wide ? 3 : 2;
+    g->sum = sum;
+    g->wide = sum > 257;
+    g->npl = g->wide ? 3 : 2;
+    g->nrc = (16 + 2 * cn * r + 63) / 64;
+    g->ncc = (16 + 2 * r + 63) / 64;
+    if (g->nrc > BM_MAXC || g->ncc > 3) return false;
+    g->pitch_s = 64 * g->nrc + 64 + 16;                      // (+16: sixteen rows / byte columns start in sixteen different 16-byte slots of the banks)
+    g->pitch_p = 64 * g->ncc + 64 + 16;
+    // one launch for the small radii (the halo rows are cheap there and four tiles fit a compute unit)
+    const int nr16 = (BM_H + 2 * r + 15) & ~15;
+    g->lds_f = (size_t)nr16 * g->pitch_s + (size_t)g->npl * BM_W * g->pitch_p;
+    g->fused = g->lds_f <= (size_t)(g->wide ? 50 : 40) * 1024;   // (measured at 1080p BGRA: sigma 2 19 us against 24 in two launches, sigma 8 32 against 30, sigma 12 48 against 35)
+    return true;
+}
+
+static int launch_gaussian_mfma(const Frames& f, const std::vector<int>& ik, int r, hipStream_t s) {
+    const View& v = f.v;
+    MfmaGeom g;
+    if (!mfma_geom(ik, r, v.c, &g)) return IMP_ERROR_UNSUPPORTED;
+    const long long sum = g.sum;
+    const bool wide = g.wide;
+    const int npl = g.npl;
     const int cn = v.c, roww = v.w * cn;
-    const int nrc = (16 + 2 * cn * r + 63) / 64, ncc = (16 + 2 * r + 63) / 64;
-    if (nrc > BM_MAXC || ncc > 3) return IMP_ERROR_UNSUPPORTED;
+    const int nrc = g.nrc, ncc = g.ncc;
     if ((f.dstep & 3) || ((uintptr_t)f.dst & 3) || (f.dst_stride & 3)) return IMP_ERROR_UNSUPPORTED;
     const int roww_pad = (roww + BM_W - 1) / BM_W * BM_W, hp = (v.h + BM_H - 1) / BM_H * BM_H;
-    const int pitch_s = 64 * nrc + 64 + 16, pitch_p = 64 * ncc + 64 + 16;   // (+16: sixteen rows / byte columns start in sixteen different 16-byte slots of the banks)
+    const int pitch_s = g.pitch_s, pitch_p = g.pitch_p;
     const size_t lds_r = (size_t)BM_H * pitch_s + (size_t)npl * BM_W * (BM_H + 16), lds_c = (size_t)npl * BM_W * pitch_p;
     const long long pstride = (long long)npl * roww_pad * hp;
     void *dev_k = nullptr, *planes = nullptr;
@@ -763,10 +800,8 @@ static int launch_gaussian_mfma(const Frames& f, const std::vector<int>& ik, int
     const size_t off_c = blob.size();
     bm_band_host(ik, r, 1, ncc, &blob);
     if (int rc = upload_small(blob.data(), blob.size() * 4, &dev_k, s)) return rc;
-    // one launch for the small radii (the halo rows are cheap there and four tiles fit a compute unit)
-    const int nr16 = (BM_H + 2 * r + 15) & ~15;
-    const size_t lds_f = (size_t)nr16 * pitch_s + (size_t)npl * BM_W * pitch_p;
-    if (lds_f <= (size_t)(wide ? 50 : 40) * 1024 && f.count <= 65535) {        // (measured at 1080p BGRA: sigma 2 19 us against 24 in two launches, sigma 8 32 against 30, sigma 12 48 against 35)
+    const size_t lds_f = g.lds_f;
+    if (g.fused && f.count <= 65535) {
         hipError_t e = hipSuccess;
         const dim3 grid((unsigned)(roww_pad / BM_W), (unsigned)(hp / BM_H), (unsigned)f.count);
         const bm_v4i* br = (const bm_v4i*)dev_k;
@@ -817,23 +852,17 @@ static int launch_gaussian_mfma(const Frames& f, const std::vector<int>& ik, int
     return IMP_OK;
 }
 
-// src view -> dst (same size, BGRA, separate buffers).  IMP_ERROR_UNSUPPORTED when the fused form does not apply
-// (other channel counts, radius > 16, fixed-point taps summing above 257, 1-pixel axes): callers fall back to
-// launch_gaussian.  sigma must give ksize > 1.
-int launch_gaussian_fused(const Frames& f, double sigma, hipStream_t s) {
-    const View& v = f.v;
-    if ((v.c != 4 && v.c != 3) || f.count <= 0 || f.count > 65535 || f.dw != v.w || f.dh != v.h || v.w < 2 || v.h < 2) return IMP_ERROR_UNSUPPORTED;
-    if (f.src == f.dst) return IMP_ERROR_UNSUPPORTED;
-    if (v.c == 4 && (((uintptr_t)f.src | (uintptr_t)f.dst | (uintptr_t)v.step | (uintptr_t)f.dstep | (uintptr_t)f.src_stride | (uintptr_t)f.dst_stride) & 3))
-        return IMP_ERROR_UNSUPPORTED;
+// The fixed-point taps of launch_gaussian_fused, trimmed to their non-zero core (radius *r); false when no fused form
+// takes them.  *fits16: row sums fit 16 bits (the fused kernel's plane, the u16 ring).
+static bool blur_taps(double sigma, std::vector<int>* ikp, int* rp, bool* fits16) {
+    std::vector<int>& ik = *ikp;
     const int ks0 = gaussian_ksize(sigma);
-    if (ks0 <= 1 || ks0 > 4096) return IMP_ERROR_UNSUPPORTED;
-    std::vector<int> ik;
+    if (ks0 <= 1 || ks0 > 4096) return false;
     gaussian_kernel_fixed(ks0, sigma, &ik);
     long long sum = 0;
     for (int k : ik) sum += k;
-    const bool fits16 = sum <= 257;                           // row sums fit 16 bits (the fused kernel's plane, the u16 ring)
-    if (sum > 65536) return IMP_ERROR_UNSUPPORTED;            // (float ring: 255 * sum < 2^24 stays exact)
+    *fits16 = sum <= 257;
+    if (sum > 65536) return false;                            // (float ring: 255 * sum < 2^24 stays exact)
     // The 8-bit fixed-point taps of a wide Gaussian are ZERO towards both ends (sigma = 8: 49 taps, the outer 4 + 4 round
     // to 0/256).  A zero tap adds 0 to the integer row sum and +0.0f to the non-negative float column sum -- both exact
     // no-ops -- and a replicated border pixel under a zero tap is irrelevant, so the kernels run on the non-zero core only.
@@ -843,27 +872,56 @@ int launch_gaussian_fused(const Frames& f, double sigma, hipStream_t s) {
         while (r > 1 && ik[r0 + r] == 0 && ik[r0 - r] == 0) r--;
         ik = std::vector<int>(ik.begin() + (r0 - r), ik.begin() + (r0 + r + 1));
     }
+    *rp = r;
+    return true;
+}
+
+// k_blur_fused4's tap blob: pairs (k[2j], k[2j+1]) as 2 x i16 | ky halves as floats (/ 65536) | ky halves as ints
+static void fused4_taps(const std::vector<int>& ik, int r, std::vector<int>* blobp, size_t* off_f, size_t* off_i) {
+    std::vector<int>& blob = *blobp;
     const int ks = 2 * r + 1;
-    if (r >= 3) {                                           // the matrix-unit form (exact when its conditions hold; else the VALU kernels below)
-        const int rc = launch_gaussian_mfma(f, ik, r, s);
-        if (rc != IMP_ERROR_UNSUPPORTED) return rc;
-    }
-    if (r > 60) return IMP_ERROR_UNSUPPORTED;
-    std::vector<int> blob;
     for (int j = 0; j <= r; j++) {                           // pairs (k[2j], k[2j+1]); the pair past the end is (k[2r], 0)
         const int lo = ik[2 * j], hi = (2 * j + 1 < ks) ? ik[2 * j + 1] : 0;
         blob.push_back((lo & 0xffff) | (hi << 16));
     }
     while (blob.size() % 4) blob.push_back(0);
-    const size_t off_f = blob.size();
+    *off_f = blob.size();
     for (int k = 0; k <= r; k++) {
         float fk = (float)(ik[r + k] * (1. / 65536));
         int bits;
         std::memcpy(&bits, &fk, 4);
         blob.push_back(bits);
     }
-    const size_t off_i = blob.size();
+    *off_i = blob.size();
     for (int k = 0; k <= r; k++) blob.push_back(ik[r + k]);
+}
+static size_t fused4_lds(int r) {
+    const int TH = 32;
+    const int SW = 64 + 2 * r + 2, SH = TH + 2 * r;
+    return (size_t)(((r + 1 + 3) & ~3) * 3 + ((SW * SH + 3) & ~3)) * 4 + (size_t)SH * 64 * 8;
+}
+
+// src view -> dst (same size, BGRA, separate buffers).  IMP_ERROR_UNSUPPORTED when the fused form does not apply
+// (other channel counts, radius > 16, fixed-point taps summing above 257, 1-pixel axes): callers fall back to
+// launch_gaussian.  sigma must give ksize > 1.
+int launch_gaussian_fused(const Frames& f, double sigma, hipStream_t s) {
+    const View& v = f.v;
+    if ((v.c != 4 && v.c != 3) || f.count <= 0 || f.count > 65535 || f.dw != v.w || f.dh != v.h || v.w < 2 || v.h < 2) return IMP_ERROR_UNSUPPORTED;
+    if (f.src == f.dst) return IMP_ERROR_UNSUPPORTED;
+    if (v.c == 4 && (((uintptr_t)f.src | (uintptr_t)f.dst | (uintptr_t)v.step | (uintptr_t)f.dstep | (uintptr_t)f.src_stride | (uintptr_t)f.dst_stride) & 3))
+        return IMP_ERROR_UNSUPPORTED;
+    std::vector<int> ik;
+    int r;
+    bool fits16;
+    if (!blur_taps(sigma, &ik, &r, &fits16)) return IMP_ERROR_UNSUPPORTED;
+    if (r >= 3) {                                           // the matrix-unit form (exact when its conditions hold; else the VALU kernels below)
+        const int rc = launch_gaussian_mfma(f, ik, r, s);
+        if (rc != IMP_ERROR_UNSUPPORTED) return rc;
+    }
+    if (r > 60) return IMP_ERROR_UNSUPPORTED;
+    std::vector<int> blob;
+    size_t off_f, off_i;
+    fused4_taps(ik, r, &blob, &off_f, &off_i);
     void* dev_k = nullptr;
     if (int rc = upload_small(blob.data(), blob.size() * 4, &dev_k, s)) return rc;
     if (r > 16 || !fits16) {   // column strips with an LDS ring (k_blur_strip4); also any radius whose rounded taps sum above 257
@@ -909,8 +967,7 @@ int launch_gaussian_fused(const Frames& f, double sigma, hipStream_t s) {
         return IMP_OK;
     }
     const int TH = 32;
-    const int SW = 64 + 2 * r + 2, SH = TH + 2 * r;
-    const size_t lds = (size_t)(((r + 1 + 3) & ~3) * 3 + ((SW * SH + 3) & ~3)) * 4 + (size_t)SH * 64 * 8;
+    const size_t lds = fused4_lds(r);
     const dim3 grid((v.w + 63) / 64, (v.h + TH - 1) / TH, f.count), block(256);
     if (grid.y > 65535) { dev_free_on(dev_k, s); return IMP_ERROR_UNSUPPORTED; }
     if (v.c == 4)
@@ -922,6 +979,141 @@ int launch_gaussian_fused(const Frames& f, double sigma, hipStream_t s) {
     hipError_t e = hipGetLastError();
     dev_free_on(dev_k, s);
     if (e != hipSuccess) { set_error("k_blur_fused4", e); return IMP_ERROR_DEVICE; }
+    return IMP_OK;
+}
+
+// ------------------------------------------------------------------ the one-pass forms over frames of different geometry
+// impgpu_batch_run_ops' blur segments: every frame whose lone launch_gaussian_fused would take k_blur_fused4 or
+// k_blur_mfma_fused, in one launch per (channel count, form, plane count).  A descriptor per frame carries its own taps
+// (offsets into one uploaded blob), radius and tile grid; workgroups are dealt like k_resize_area_mix's, one tile each, and
+// run the lone kernel's tile body.  The dynamic LDS is the largest of the launch's frames (each frame lays its own out).
+enum { BF_FUSED4 = 0, BF_MFMA = 1 };
+struct BlurDesc {
+    const uint8_t* src; uint8_t* dst; int w, h, sstep, dstep;
+    int r, ntx;                  // radius, tiles across
+    int k0, k1, k2;              // FUSED4: pair / float / int taps; MFMA: row bands, column bands (int offsets into the blob)
+    int nrc, ncc, pitch_s, pitch_p, bias_r, bias_c;
+    int first, nblk;
+};
+
+template <int CN, int FORM, bool WIDE>
+__global__ __launch_bounds__(256) void k_blur_mix(const BlurDesc* __restrict__ descs, MixIndex ix, const int* __restrict__ taps) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t bm_smem[];
+    int blk;
+    const int di = mix_pick(descs, ix, &blk);
+    if (di < 0) return;
+    const BlurDesc* m = descs + di;
+    const int ty = blk / m->ntx, tx = blk - ty * m->ntx;
+    if constexpr (FORM == BF_FUSED4) {
+        blur_fused4_tile<32, CN>(m->src, m->sstep, m->w, m->h, m->dst, m->dstep, taps + m->k0, (const float*)(taps + m->k1), taps + m->k2,
+                                 m->r, m->r, tx * 64, ty * 32, bm_smem);
+    } else {
+        blur_mfma_fused_tile<CN, WIDE>(m->src, m->sstep, m->w, m->h, m->dst, m->dstep, (const bm_v4i*)(taps + m->k0),
+                                       (const bm_v4i*)(taps + m->k1), m->r, m->nrc, m->ncc, m->pitch_s, m->pitch_p, m->bias_r,
+                                       m->bias_c, tx, ty, bm_smem);
+    }
+}
+
+// launch_gaussian_fused's choice of form for a frame (its order of tests), without launching anything
+static int blur_form_of(int w, int h, int c, bool aligned, double sigma, std::vector<int>* ik, int* r, int* form, MfmaGeom* g) {
+    if ((c != 4 && c != 3) || w < 2 || h < 2 || (c == 4 && !aligned)) return BLUR_LONE;
+    bool fits16;
+    if (!blur_taps(sigma, ik, r, &fits16)) return BLUR_LONE;
+    if (*r >= 3 && mfma_geom(*ik, *r, c, g)) {             // (a fresh frame's pointer and step are dword aligned: launch_gaussian_mfma's last test holds)
+        *form = BF_MFMA;
+        return g->fused ? BLUR_MIXABLE : BLUR_LONE;
+    }
+    if (*r > 16 || !fits16) return BLUR_LONE;              // (k_blur_strip4, or nothing)
+    if ((h + 31) / 32 > 65535) return BLUR_LONE;
+    *form = BF_FUSED4;
+    return BLUR_MIXABLE;
+}
+
+int blur_form(int w, int h, int c, bool aligned, double sigma) {
+    std::vector<int> ik;
+    int r = 0, form = 0;
+    MfmaGeom g{};
+    return blur_form_of(w, h, c, aligned, sigma, &ik, &r, &form, &g);
+}
+
+int launch_blur_mixed(const BlurItem* items, int count, int cn, hipStream_t s) {
+    if (count <= 0) return IMP_OK;
+    if (!items || (cn != 3 && cn != 4)) return IMP_ERROR_INVALID_ARGS;
+    std::vector<BlurDesc> v[3];                             // FUSED4, MFMA, MFMA wide
+    size_t lds[3] = {0, 0, 0};
+    std::vector<int> blob;
+    for (int i = 0; i < count; i++) {                      // nothing is launched unless every item is well-formed and mixable
+        const BlurItem& it = items[i];
+        if (!it.src || !it.dst || it.src == it.dst || !view_fits(it.w, it.h, cn, it.sstep) || !view_fits(it.w, it.h, cn, it.dstep))
+            return IMP_ERROR_INVALID_ARGS;
+        if (((uintptr_t)it.dst | (uintptr_t)it.dstep) & 3) return IMP_ERROR_INVALID_ARGS;
+        const bool aligned = !(((uintptr_t)it.src | (uintptr_t)it.sstep) & 3);
+        std::vector<int> ik;
+        int r = 0, form = 0;
+        MfmaGeom g{};
+        if (blur_form_of(it.w, it.h, cn, aligned, it.sigma, &ik, &r, &form, &g) != BLUR_MIXABLE) return IMP_ERROR_INVALID_ARGS;
+        BlurDesc d{};
+        d.src = it.src; d.dst = it.dst; d.w = it.w; d.h = it.h; d.sstep = it.sstep; d.dstep = it.dstep; d.r = r;
+        while (blob.size() % 4) blob.push_back(0);          // (16-byte aligned operands)
+        int k = 0;
+        if (form == BF_FUSED4) {
+            std::vector<int> t;
+            size_t off_f, off_i;
+            fused4_taps(ik, r, &t, &off_f, &off_i);
+            d.k0 = (int)blob.size(); d.k1 = d.k0 + (int)off_f; d.k2 = d.k0 + (int)off_i;
+            blob.insert(blob.end(), t.begin(), t.end());
+            d.ntx = (it.w + 63) / 64;
+            d.nblk = d.ntx * ((it.h + 31) / 32);
+            lds[0] = std::max(lds[0], fused4_lds(r));
+        } else {
+            d.k0 = (int)blob.size();
+            bm_band_host(ik, r, cn, g.nrc, &blob);
+            d.k1 = (int)blob.size();
+            bm_band_host(ik, r, 1, g.ncc, &blob);
+            d.nrc = g.nrc; d.ncc = g.ncc; d.pitch_s = g.pitch_s; d.pitch_p = g.pitch_p;
+            d.bias_r = (int)(128 * g.sum); d.bias_c = (int)(128 * g.sum * 257);
+            const int roww_pad = (it.w * cn + BM_W - 1) / BM_W * BM_W, hp = (it.h + BM_H - 1) / BM_H * BM_H;
+            d.ntx = roww_pad / BM_W;
+            d.nblk = d.ntx * (hp / BM_H);
+            k = g.wide ? 2 : 1;
+            lds[k] = std::max(lds[k], g.lds_f);
+        }
+        v[k].push_back(d);
+    }
+    if (blob.empty()) blob.resize(4, 0);
+    void* dev_k = nullptr;
+    if (int rc = upload_small(blob.data(), blob.size() * 4, &dev_k, s)) return rc;
+    const int* taps = (const int*)dev_k;
+    hipError_t e = hipSuccess;
+    int rc = IMP_OK;
+    for (int k = 0; k < 3 && rc == IMP_OK && e == hipSuccess; k++) {
+        if (v[k].empty()) continue;
+        std::vector<BlurDesc> sorted;
+        MixIndex ix{};
+        int most = 0;
+        mix_deal(v[k], [](BlurDesc& d) -> BlurDesc& { return d; }, [](BlurDesc& d) { return (long long)d.w * d.h * (2 * d.r + 1); },
+                 &sorted, &ix, &most);
+        void* dev_d = nullptr;
+        if ((rc = upload_small(sorted.data(), sorted.size() * sizeof(BlurDesc), &dev_d, s))) break;
+        const dim3 grid((unsigned)most * 8), block(256);
+        const BlurDesc* dd = (const BlurDesc*)dev_d;
+#define IMP_BLUR_MIX(CN_, F_, W_)                                                                                  \
+    do {                                                                                                           \
+        e = lds_limit_once<k_blur_mix<CN_, F_, W_>>();                                                             \
+        if (e == hipSuccess) hipLaunchKernelGGL((k_blur_mix<CN_, F_, W_>), grid, block, lds[k], s, dd, ix, taps);  \
+    } while (0)
+        if (cn == 4) {
+            if (k == 0) IMP_BLUR_MIX(4, BF_FUSED4, false); else if (k == 1) IMP_BLUR_MIX(4, BF_MFMA, false); else IMP_BLUR_MIX(4, BF_MFMA, true);
+        } else {
+            if (k == 0) IMP_BLUR_MIX(3, BF_FUSED4, false); else if (k == 1) IMP_BLUR_MIX(3, BF_MFMA, false); else IMP_BLUR_MIX(3, BF_MFMA, true);
+        }
+#undef IMP_BLUR_MIX
+        if (e == hipSuccess) e = hipGetLastError();
+        dev_free_on(dev_d, s);
+    }
+    dev_free_on(dev_k, s);
+    if (rc) return rc;
+    if (e != hipSuccess) { set_error("k_blur_mix", e); return IMP_ERROR_DEVICE; }
     return IMP_OK;
 }
 

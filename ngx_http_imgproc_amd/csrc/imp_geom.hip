@@ -28,13 +28,24 @@ __global__ __launch_bounds__(256) void k_copy(GArgs a, int row_units) {
 }
 
 // ---- cvFlip: mode 0 = vertical (around x axis), > 0 = horizontal, < 0 = both ----
+// the source pixel of destination (x, y); shared by k_flip and k_geom_mix
+__device__ __forceinline__ void flip_src(int mode, int sw, int sh, int x, int y, int* sx, int* sy) {
+    *sy = mode <= 0 ? sh - 1 - y : y;
+    *sx = mode != 0 ? sw - 1 - x : x;
+}
+// rotate 90 (clockwise): R[i][j] = S[H-1-j][i];  270: R[i][j] = S[j][W-1-i]  (filters.c:116-119); shared by k_rotate_* and k_geom_mix
+__device__ __forceinline__ void turn_src(int amount, int sw, int sh, int i, int j, int* srow, int* scol) {
+    *srow = amount == 90 ? sh - 1 - j : j;
+    *scol = amount == 90 ? i : sw - 1 - i;
+}
+
 template <int CN>
 __global__ __launch_bounds__(256) void k_flip(GArgs a, int mode) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long long)a.dw * a.dh) return;
     const int y = (int)(idx / a.dw), x = (int)(idx - (long long)y * a.dw);
-    const int sy = mode <= 0 ? a.sh - 1 - y : y;
-    const int sx = mode != 0 ? a.sw - 1 - x : x;
+    int sx, sy;
+    flip_src(mode, a.sw, a.sh, x, y, &sx, &sy);
     const uint8_t* s = a.src + (long long)blockIdx.y * a.src_stride + (size_t)sy * a.sstep + (size_t)sx * CN;
     uint8_t* d = a.dst + (long long)blockIdx.y * a.dst_stride + (size_t)y * a.dstep + (size_t)x * CN;
     if (CN == 4) *(uint32_t*)d = *(const uint32_t*)s;
@@ -44,7 +55,7 @@ __global__ __launch_bounds__(256) void k_flip(GArgs a, int mode) {
     }
 }
 
-// ---- rotate 90 (clockwise): R[i][j] = S[H-1-j][i];  270: R[i][j] = S[j][W-1-i]  (filters.c:116-119) ----
+// ---- rotate 90 / 270 (turn_src) ----
 __global__ __launch_bounds__(256) void k_rotate_bgra(GArgs a, int amount) {
     __shared__ uint32_t tile[32][33];
     const int tx0 = blockIdx.x * 32, ty0 = blockIdx.y * 32;   // destination tile origin (x along dw = sh)
@@ -56,8 +67,8 @@ __global__ __launch_bounds__(256) void k_rotate_bgra(GArgs a, int amount) {
         const int lj = threadIdx.y + 8 * r;
         const int j = tx0 + lj, i = ty0 + li;                  // destination (x = j, y = i)
         if (j < a.dw && i < a.dh) {
-            const int srow = amount == 90 ? a.sh - 1 - j : j;
-            const int scol = amount == 90 ? i : a.sw - 1 - i;
+            int srow, scol;
+            turn_src(amount, a.sw, a.sh, i, j, &srow, &scol);
             tile[lj][li] = *(const uint32_t*)(S + (size_t)srow * a.sstep + (size_t)scol * 4);
         }
     }
@@ -135,8 +146,8 @@ __global__ __launch_bounds__(256) void k_rotate_any(GArgs a, int amount) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long long)a.dw * a.dh) return;
     const int i = (int)(idx / a.dw), j = (int)(idx - (long long)i * a.dw);
-    const int srow = amount == 90 ? a.sh - 1 - j : j;
-    const int scol = amount == 90 ? i : a.sw - 1 - i;
+    int srow, scol;
+    turn_src(amount, a.sw, a.sh, i, j, &srow, &scol);
     const uint8_t* s = a.src + (long long)blockIdx.y * a.src_stride + (size_t)srow * a.sstep + (size_t)scol * CN;
     uint8_t* d = a.dst + (long long)blockIdx.y * a.dst_stride + (size_t)i * a.dstep + (size_t)j * CN;
 #pragma unroll
@@ -282,6 +293,85 @@ int launch_rotate(const Frames& f, int amount, hipStream_t s) {
         else hipLaunchKernelGGL((k_rotate_any<1>), grid, block, 0, s, a, amount);
     }
     IMP_HIP(hipGetLastError());
+    return IMP_OK;
+}
+
+// ---- flips and turns of frames of different geometry (impgpu_batch_run_ops' geometry segments) ----
+// A descriptor per frame, dealt like k_resize_area_mix's; a workgroup covers GEOM_PIX destination pixels of one frame,
+// each a gather through flip_src / turn_src (a half turn is cvFlip mode -1, as in launch_rotate).
+#define GEOM_PIX (256 * 8)
+struct GeomDesc {
+    const uint8_t* src; int sw, sh, sstep;
+    uint8_t* dst; int dw, dh, dstep;
+    int kind, mode;              // 0: flip (mode), 1: turn 90 / 270
+    int first, nblk;
+};
+
+template <int CN>
+__global__ __launch_bounds__(256) void k_geom_mix(const GeomDesc* __restrict__ descs, MixIndex ix) {
+    int blk;
+    const int di = mix_pick(descs, ix, &blk);
+    if (di < 0) return;
+    const GeomDesc* m = descs + di;
+    const int dw = m->dw, kind = m->kind, mode = m->mode;
+    const long long npix = (long long)dw * m->dh;
+    const long long first = (long long)blk * GEOM_PIX + threadIdx.x;
+#pragma unroll 1
+    for (int it = 0; it < GEOM_PIX / 256; it++) {
+        const long long idx = first + (long long)it * 256;
+        if (idx >= npix) break;
+        const int y = (int)(idx / dw), x = (int)(idx - (long long)y * dw);
+        int sx, sy;
+        if (kind == 0) flip_src(mode, m->sw, m->sh, x, y, &sx, &sy);
+        else turn_src(mode, m->sw, m->sh, y, x, &sy, &sx);
+        const uint8_t* s = m->src + (size_t)sy * m->sstep + (size_t)sx * CN;
+        uint8_t* d = m->dst + (size_t)y * m->dstep + (size_t)x * CN;
+        if (CN == 4) *(uint32_t*)d = *(const uint32_t*)s;
+        else {
+#pragma unroll
+            for (int c = 0; c < CN; c++) d[c] = s[c];
+        }
+    }
+}
+
+int launch_geom_mixed(const GeomItem* items, int count, int cn, hipStream_t s) {
+    if (count <= 0) return IMP_OK;
+    if (!items || (cn != 3 && cn != 4)) return IMP_ERROR_INVALID_ARGS;
+    std::vector<GeomDesc> v;
+    v.reserve((size_t)count);
+    for (int i = 0; i < count; i++) {                      // nothing is launched unless every item is well-formed
+        const GeomItem& it = items[i];
+        if (!it.src || !it.dst || !view_fits(it.sw, it.sh, cn, it.sstep) || !view_fits(it.dw, it.dh, cn, it.dstep)) return IMP_ERROR_INVALID_ARGS;
+        if (cn == 4 && (((uintptr_t)it.src | (uintptr_t)it.dst | (uintptr_t)it.sstep | (uintptr_t)it.dstep) & 3)) return IMP_ERROR_INVALID_ARGS;
+        GeomDesc d{};
+        d.src = it.src; d.sw = it.sw; d.sh = it.sh; d.sstep = it.sstep;
+        d.dst = it.dst; d.dw = it.dw; d.dh = it.dh; d.dstep = it.dstep;
+        if (it.kind == 0 || (it.kind == 1 && it.mode == 180)) {
+            if (it.dw != it.sw || it.dh != it.sh) return IMP_ERROR_INVALID_ARGS;
+            d.kind = 0;
+            d.mode = it.kind == 0 ? it.mode : -1;
+        } else if (it.kind == 1 && (it.mode == 90 || it.mode == 270)) {
+            if (it.dw != it.sh || it.dh != it.sw) return IMP_ERROR_INVALID_ARGS;
+            d.kind = 1;
+            d.mode = it.mode;
+        } else {
+            return IMP_ERROR_INVALID_ARGS;
+        }
+        d.nblk = (int)(((long long)it.dw * it.dh + GEOM_PIX - 1) / GEOM_PIX);
+        v.push_back(d);
+    }
+    std::vector<GeomDesc> sorted;
+    MixIndex ix{};
+    int most = 0;
+    mix_deal(v, [](GeomDesc& d) -> GeomDesc& { return d; }, [](GeomDesc& d) { return (long long)d.dw * d.dh; }, &sorted, &ix, &most);
+    void* dev = nullptr;
+    if (int rc = upload_small(sorted.data(), sorted.size() * sizeof(GeomDesc), &dev, s)) return rc;
+    const dim3 grid((unsigned)most * 8), block(256);
+    if (cn == 4) hipLaunchKernelGGL((k_geom_mix<4>), grid, block, 0, s, (const GeomDesc*)dev, ix);
+    else hipLaunchKernelGGL((k_geom_mix<3>), grid, block, 0, s, (const GeomDesc*)dev, ix);
+    const hipError_t e = hipGetLastError();
+    dev_free_on(dev, s);
+    IMP_HIP(e);
     return IMP_OK;
 }
 

@@ -1,6 +1,7 @@
 // imp_internal.h -- shared declarations of libimpgpu.so (not installed; the public ABI is include/impgpu.h).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <cstdlib>
@@ -292,6 +293,95 @@ int launch_gaussian(uint8_t* d, long long stride, int w, int h, int c, int step,
 
 // fused single-pass BGRA Gaussian, out of place; IMP_ERROR_UNSUPPORTED when it does not apply
 int launch_gaussian_fused(const Frames& f, double sigma, hipStream_t s);
+
+// ---------------------------------------------------------------- launches over frames of different geometry
+// The descriptor tables of the mixed launches (k_resize_area_mix and the chain kernels of impgpu_batch_run_ops): every
+// descriptor owns `nblk` consecutive workgroups of ONE frame (a workgroup never spans two), and the descriptors are dealt
+// to the eight XCD lists (workgroup id mod 8 = XCD), heaviest first to the lightest list.  List g is [off[g], off[g + 1]).
+struct MixIndex { int off[9]; };
+// `desc(d)` names the part of a descriptor holding `first` and `nblk`, `cost(d)` its weight; `v` is consumed, *sorted_out
+// holds the lists back to back, *most_out the workgroups of the longest list (the grid is 8 * most).
+template <class D, class M, class C>
+void mix_deal(std::vector<D>& v, M desc, C cost, std::vector<D>* sorted_out, MixIndex* ix_out, int* most_out) {
+    std::vector<int> order(v.size());
+    for (size_t i = 0; i < v.size(); i++) order[i] = (int)i;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return cost(v[x]) > cost(v[y]); });
+    std::vector<int> list[8];
+    long long load[8] = {0};
+    for (int i : order) {
+        int g = 0;
+        for (int k = 1; k < 8; k++)
+            if (load[k] < load[g]) g = k;
+        list[g].push_back(i);
+        load[g] += cost(v[i]) + 4096;
+    }
+    std::vector<D>& sorted = *sorted_out;
+    sorted.clear();
+    sorted.reserve(v.size());
+    MixIndex& ix = *ix_out;
+    ix = MixIndex{};
+    int most = 0;
+    for (int g = 0; g < 8; g++) {
+        ix.off[g] = (int)sorted.size();
+        int first = 0;
+        for (int i : list[g]) {
+            D d = v[i];
+            desc(d).first = first;
+            first += desc(d).nblk;
+            sorted.push_back(d);
+        }
+        most = first > most ? first : most;
+    }
+    ix.off[8] = (int)sorted.size();
+    v.clear();
+    *most_out = most;
+}
+#ifdef __HIPCC__
+// The descriptor of this workgroup (its index; -1: none, the workgroup returns) and the workgroup's index inside it;
+// `desc(d)` names the part of a descriptor holding `first` and `nblk`, as in mix_deal.  An index rather than a pointer: the
+// callers read the descriptor as d[i], which keeps its fields in scalar registers.
+template <class D, class M>
+__device__ __forceinline__ int mix_pick(const D* __restrict__ d, const MixIndex& ix, int* blk, M desc) {
+    const int g = blockIdx.x & 7, q = blockIdx.x >> 3;
+    int lo = ix.off[g], hi = ix.off[g + 1];
+    if (lo == hi || q >= desc(d[hi - 1]).first + desc(d[hi - 1]).nblk) return -1;
+    while (hi - lo > 1) {                              // last descriptor whose first block is <= q
+        const int mid = (lo + hi) >> 1;
+        if (desc(d[mid]).first <= q) lo = mid; else hi = mid;
+    }
+    *blk = q - desc(d[lo]).first;
+    return lo;
+}
+template <class D>
+__device__ __forceinline__ int mix_pick(const D* __restrict__ d, const MixIndex& ix, int* blk) {
+    return mix_pick(d, ix, blk, [](const D& x) -> const D& { return x; });
+}
+#endif
+
+// The chain kernels of impgpu_batch_run_ops: one launch per channel count over frames of different geometry.
+// imp_pixel.hip: a run of pointwise stages [-> watermark] [-> flatten] on a frame in place.  `prog` must fit one
+// k_pixel_program launch (split_program); an overlay of 3 or 4 channels.
+struct PixelTailItem {
+    uint8_t* d; int w, h, step;
+    const PixelProgram* prog;            // may be empty
+    bool has_wm; const impgpu_image* ov; int rx, ry, maxcol, maxrow; float alpha;
+    bool flatten;
+};
+int launch_pixel_tail_mixed(const PixelTailItem* items, int count, int channels, hipStream_t s);
+// A program past one launch's stage / table limits, cut where launch_pixel_program cuts it (exact anywhere: every stage
+// already rounds to 8 bits per channel).  One part when it fits.
+void split_program(const PixelProgram& prog, std::vector<PixelProgram>* parts);
+// imp_geom.hip: cvFlip (kind 0, mode = flip mode) or a quarter / half turn (kind 1, mode = 90 / 180 / 270) into a fresh frame
+struct GeomItem { const uint8_t* src; int sw, sh, sstep; uint8_t* dst; int dw, dh, dstep; int kind, mode; };
+int launch_geom_mixed(const GeomItem* items, int count, int channels, hipStream_t s);
+// imp_blur.hip: which form launch_gaussian_fused gives a frame of this geometry and sigma -- BLUR_MIXABLE when it is one of
+// the one-pass forms k_blur_mix takes (k_blur_fused4, k_blur_mfma_fused), BLUR_LONE for the others.  `aligned`: the
+// dword alignment launch_gaussian_fused asks of BGRA pointers and steps holds.
+enum { BLUR_LONE = 0, BLUR_MIXABLE = 1 };
+int blur_form(int w, int h, int c, bool aligned, double sigma);
+struct BlurItem { const uint8_t* src; uint8_t* dst; int w, h, sstep, dstep; double sigma; };   // out of place, same geometry
+// every item must be BLUR_MIXABLE (IMP_ERROR_INVALID_ARGS otherwise, nothing launched)
+int launch_blur_mixed(const BlurItem* items, int count, int channels, hipStream_t s);
 
 // Watermark placement (bridge.c:254-274 + cvSetImageROI clipping). Returns IMP_* code.
 int watermark_rect(int basew, int baseh, int overw, int overh, const impgpu_config* cfg,

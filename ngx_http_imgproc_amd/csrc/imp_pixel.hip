@@ -290,29 +290,43 @@ __global__ __launch_bounds__(256) void k_pixel_program_v4(uint8_t* base, long lo
     }
 }
 
+static bool program_fits(const PixelProgram& prog) {
+    return prog.stages.size() <= IMP_MAX_STAGES && prog.tables.size() <= IMP_MAX_TABLE_BYTES;
+}
+
+void split_program(const PixelProgram& prog, std::vector<PixelProgram>* parts) {
+    parts->clear();
+    if (program_fits(prog)) { parts->push_back(prog); return; }
+    PixelProgram part;
+    for (const Stage& st : prog.stages) {
+        const size_t tb = st.kind == ST_LUT4 ? 1024 : (st.kind == ST_GRADMAP ? 768 : 0);
+        if (part.stages.size() + 1 > IMP_MAX_STAGES || part.tables.size() + tb > IMP_MAX_TABLE_BYTES) {
+            parts->push_back(part);
+            part.clear();
+        }
+        Stage cp = st;
+        if (tb) {
+            cp.lut_off = (int)part.tables.size();
+            part.tables.insert(part.tables.end(), prog.tables.begin() + st.lut_off, prog.tables.begin() + st.lut_off + tb);
+        }
+        part.stages.push_back(cp);
+    }
+    parts->push_back(part);
+}
+
 int launch_pixel_program(uint8_t* d, long long stride, int w, int h, int c, int step, int count,
                          const PixelProgram& prog, hipStream_t s) {
     if (prog.empty() || count <= 0) return IMP_OK;
     if (count > 65535) return IMP_ERROR_INVALID_ARGS;
-    if (prog.stages.size() > IMP_MAX_STAGES || prog.tables.size() > IMP_MAX_TABLE_BYTES) {
+    if (!program_fits(prog)) {
         // a long run of pointwise filters (a raised imgproc_max_filters): the reference just runs them one after another,
         // so cut the program into launches that fit.  Exact anywhere: every stage already rounds to 8 bits per channel,
         // which is all a frame in HBM holds between two launches.
-        PixelProgram part;
-        for (const Stage& st : prog.stages) {
-            const size_t tb = st.kind == ST_LUT4 ? 1024 : (st.kind == ST_GRADMAP ? 768 : 0);
-            if (part.stages.size() + 1 > IMP_MAX_STAGES || part.tables.size() + tb > IMP_MAX_TABLE_BYTES) {
-                if (int rc = launch_pixel_program(d, stride, w, h, c, step, count, part, s)) return rc;
-                part.clear();
-            }
-            Stage cp = st;
-            if (tb) {
-                cp.lut_off = (int)part.tables.size();
-                part.tables.insert(part.tables.end(), prog.tables.begin() + st.lut_off, prog.tables.begin() + st.lut_off + tb);
-            }
-            part.stages.push_back(cp);
-        }
-        return launch_pixel_program(d, stride, w, h, c, step, count, part, s);
+        std::vector<PixelProgram> parts;
+        split_program(prog, &parts);
+        for (const PixelProgram& part : parts)
+            if (int rc = launch_pixel_program(d, stride, w, h, c, step, count, part, s)) return rc;
+        return IMP_OK;
     }
     if (c == 4 && (((uintptr_t)d | (uintptr_t)step | (uintptr_t)stride) & 3)) return IMP_ERROR_INVALID_ARGS;
     ProgDev pd{};
@@ -423,6 +437,134 @@ int launch_blend_paper(uint8_t* d, long long stride, int w, int h, int step, int
     hipLaunchKernelGGL(k_blend_paper, dim3((unsigned)(((long long)w * h + 255) / 256), (unsigned)count), dim3(256), 0, s,
                        d, stride, w, h, step);
     IMP_HIP(hipGetLastError());
+    return IMP_OK;
+}
+
+// ------------------------------------------------------------------ pointwise run + Watermark + BlendWithPaper, frames of different geometry
+// impgpu_batch_run_ops' pointwise segments (bridge.c:606-656): per pixel the program of k_pixel_program (run_stages), then,
+// inside the overlay's rectangle, AlphaBlendOver (blend_over_bgra / blend_over_bgr, k_blend_over's expression -- a 3-channel
+// overlay pixel enters with alpha byte 255, which is the 1.0f k_blend_over<DC, 3> uses), then BlendWithPaper
+// (blend_paper_bgra) -- the reference's order, each step rounding to 8 bits as the lone launches do between them.  A
+// descriptor per frame, dealt like k_resize_area_mix's; a workgroup covers TAIL_PIX pixels of one frame and stages that
+// frame's tables into LDS once.  VIG as k_pixel_program's (the host groups the frames by it).
+#define TAIL_PIX (256 * PIX_PER_THREAD)
+struct PixTailDesc {
+    uint8_t* d; int w, h, step;
+    int first, nblk;
+    int tab_off;                 // the frame's tables in the launch's table blob
+    int has_wm, flat;
+    const uint8_t* ov; int ostep, oc, rx, ry, maxcol, maxrow; float alpha;
+    ProgDev prog;
+};
+
+template <int CN, bool VIG>
+__global__ __launch_bounds__(256) void k_pixel_tail_mix(const PixTailDesc* __restrict__ descs, MixIndex ix, const uint8_t* __restrict__ tables) {
+    __shared__ __attribute__((aligned(16))) uint8_t lut[IMP_MAX_TABLE_BYTES];
+    int blk;
+    const int di = mix_pick(descs, ix, &blk);
+    if (di < 0) return;
+    const PixTailDesc* m = descs + di;
+    const ProgDev& prog = m->prog;
+    const uint8_t* tb = tables + m->tab_off;
+    for (int i = threadIdx.x * 4; i < prog.table_bytes; i += 256 * 4)
+        *(uint32_t*)(lut + i) = *(const uint32_t*)(tb + i);
+    __syncthreads();
+    const int w = m->w, step = m->step;
+    const long long npix = (long long)w * m->h;
+    const long long first = (long long)blk * TAIL_PIX + threadIdx.x;
+    const bool wm = m->has_wm != 0, flat = CN == 4 && m->flat != 0;
+#pragma unroll 1
+    for (int it = 0; it < PIX_PER_THREAD; it++) {
+        const long long idx = first + (long long)it * 256;
+        if (idx >= npix) break;
+        const int y = (int)(idx / w), x = (int)(idx - (long long)y * w);
+        uint8_t* p = m->d + (size_t)y * step + (size_t)x * CN;
+        int c0, c1, c2, c3 = 255;
+        if (CN == 4) {
+            const uint32_t u = *(const uint32_t*)p;
+            c0 = u & 0xff; c1 = (u >> 8) & 0xff; c2 = (u >> 16) & 0xff; c3 = u >> 24;
+        } else {
+            c0 = p[0]; c1 = p[1]; c2 = p[2];
+        }
+        run_stages<CN, VIG>(c0, c1, c2, c3, x, y, prog, lut);
+        uint32_t u = (uint32_t)(c0 & 0xff) | ((uint32_t)(c1 & 0xff) << 8) | ((uint32_t)(c2 & 0xff) << 16) | ((uint32_t)(c3 & 0xff) << 24);
+        const int ox = x - m->rx, oy = y - m->ry;
+        if (wm && ox >= 0 && ox < m->maxcol && oy >= 0 && oy < m->maxrow) {
+            const uint8_t* sp = m->ov + (size_t)oy * m->ostep + (size_t)ox * m->oc;
+            const uint32_t sv = (uint32_t)sp[0] | ((uint32_t)sp[1] << 8) | ((uint32_t)sp[2] << 16) | ((uint32_t)(m->oc == 4 ? sp[3] : 255) << 24);
+            u = CN == 4 ? blend_over_bgra(u, sv, m->alpha) : (blend_over_bgr(u, sv, m->alpha) | (u & 0xff000000u));
+        }
+        if (flat) u = blend_paper_bgra(u);
+        if (CN == 4) *(uint32_t*)p = u;
+        else { p[0] = (uint8_t)u; p[1] = (uint8_t)(u >> 8); p[2] = (uint8_t)(u >> 16); }
+    }
+}
+
+int launch_pixel_tail_mixed(const PixelTailItem* items, int count, int cn, hipStream_t s) {
+    if (count <= 0) return IMP_OK;
+    if (!items || (cn != 3 && cn != 4)) return IMP_ERROR_INVALID_ARGS;
+    std::vector<PixTailDesc> v[2];                         // without / with a vignette stage
+    std::vector<uint8_t> tables;
+    for (int i = 0; i < count; i++) {                      // nothing is launched unless every item is well-formed
+        const PixelTailItem& it = items[i];
+        if (!it.d || !view_fits(it.w, it.h, cn, it.step)) return IMP_ERROR_INVALID_ARGS;
+        if (cn == 4 && (((uintptr_t)it.d | (uintptr_t)it.step) & 3)) return IMP_ERROR_INVALID_ARGS;
+        const bool has_prog = it.prog && !it.prog->empty();
+        if (has_prog && !program_fits(*it.prog)) return IMP_ERROR_INVALID_ARGS;
+        const bool wm = it.has_wm && it.maxcol > 0 && it.maxrow > 0;
+        if (wm && (!it.ov || it.ov->c < 3 || it.rx < 0 || it.ry < 0 || it.rx + it.maxcol > it.w || it.ry + it.maxrow > it.h ||
+                   it.maxcol > it.ov->w || it.maxrow > it.ov->h))
+            return IMP_ERROR_INVALID_ARGS;
+        const bool flat = it.flatten && cn == 4;
+        if (!has_prog && !wm && !flat) continue;
+        PixTailDesc d{};
+        d.d = it.d; d.w = it.w; d.h = it.h; d.step = it.step;
+        d.nblk = (int)(((long long)it.w * it.h + TAIL_PIX - 1) / TAIL_PIX);
+        d.tab_off = (int)tables.size();
+        bool vig = false;
+        if (has_prog) {
+            d.prog.n = (int)it.prog->stages.size();
+            for (int k = 0; k < d.prog.n; k++) {
+                d.prog.st[k] = it.prog->stages[(size_t)k];
+                vig = vig || d.prog.st[k].kind == ST_VIGNETTE;
+            }
+            d.prog.table_bytes = ((int)it.prog->tables.size() + 3) & ~3;
+            tables.insert(tables.end(), it.prog->tables.begin(), it.prog->tables.end());
+            tables.resize((tables.size() + 15) & ~size_t(15), 0);
+        }
+        if (wm) {
+            d.has_wm = 1;
+            d.ov = it.ov->d; d.ostep = it.ov->step; d.oc = it.ov->c;
+            d.rx = it.rx; d.ry = it.ry; d.maxcol = it.maxcol; d.maxrow = it.maxrow; d.alpha = it.alpha;
+        }
+        d.flat = flat ? 1 : 0;
+        v[vig ? 1 : 0].push_back(d);
+    }
+    if (tables.empty()) tables.resize(16, 0);
+    for (int vig = 0; vig < 2; vig++) {
+        if (v[vig].empty()) continue;
+        std::vector<PixTailDesc> sorted;
+        MixIndex ix{};
+        int most = 0;
+        mix_deal(v[vig], [](PixTailDesc& d) -> PixTailDesc& { return d; }, [](PixTailDesc& d) { return (long long)d.w * d.h; },
+                 &sorted, &ix, &most);
+        const size_t dbytes = (sorted.size() * sizeof(PixTailDesc) + 15) & ~size_t(15);
+        std::vector<uint8_t> blob(dbytes + tables.size(), 0);
+        std::memcpy(blob.data(), sorted.data(), sorted.size() * sizeof(PixTailDesc));
+        std::memcpy(blob.data() + dbytes, tables.data(), tables.size());
+        void* dev = nullptr;
+        if (int rc = upload_small(blob.data(), blob.size(), &dev, s)) return rc;
+        const PixTailDesc* dd = (const PixTailDesc*)dev;
+        const uint8_t* dt = (const uint8_t*)dev + dbytes;
+        const dim3 grid((unsigned)most * 8), block(256);
+        if (cn == 4 && vig) hipLaunchKernelGGL((k_pixel_tail_mix<4, true>), grid, block, 0, s, dd, ix, dt);
+        else if (cn == 4) hipLaunchKernelGGL((k_pixel_tail_mix<4, false>), grid, block, 0, s, dd, ix, dt);
+        else if (vig) hipLaunchKernelGGL((k_pixel_tail_mix<3, true>), grid, block, 0, s, dd, ix, dt);
+        else hipLaunchKernelGGL((k_pixel_tail_mix<3, false>), grid, block, 0, s, dd, ix, dt);
+        const hipError_t e = hipGetLastError();
+        dev_free_on(dev, s);
+        if (e != hipSuccess) { set_error("k_pixel_tail_mix", e); return IMP_ERROR_DEVICE; }
+    }
     return IMP_OK;
 }
 

@@ -2487,20 +2487,14 @@ __global__ __launch_bounds__(256) void k_resize_area_rows4(RArgs a, AreaGeom gm,
 // XCDs like frame_block deals them (block id mod 8 = XCD): descriptor list g holds the frames of XCD g back to back, each
 // with the number of the first block it owns inside that list, and a block finds its frame by bisection over those.
 struct MixDesc { RArgs a; AreaGeom gm; int first, nblk, nv, rows, nstrips, nitems; };   // nitems > 0: row-streaming body, nv = window W (negative: four columns per lane, window -nv), rows = band height
-struct MixIndex { int off[9]; };                       // descriptors of XCD g: [off[g], off[g + 1])
 
 template <int CN>
 __global__ __launch_bounds__(256) void k_resize_area_mix(const MixDesc* __restrict__ d, MixIndex ix) {
     __shared__ __attribute__((aligned(16))) uint32_t s_line[4][64 * MIX_NV * 4 + 4];
-    const int g = blockIdx.x & 7, q = blockIdx.x >> 3;
-    int lo = ix.off[g], hi = ix.off[g + 1];
-    if (lo == hi || q >= d[hi - 1].first + d[hi - 1].nblk) return;
-    while (hi - lo > 1) {                              // last descriptor whose first block is <= q
-        const int mid = (lo + hi) >> 1;
-        if (d[mid].first <= q) lo = mid; else hi = mid;
-    }
-    const MixDesc& m = d[lo];
-    const int blk = q - m.first;
+    int blk;
+    const int di = mix_pick(d, ix, &blk);              // (bisection over the first-block numbers of the XCD's list)
+    if (di < 0) return;
+    const MixDesc& m = d[di];
     if (m.nitems > 0 && m.nv < 0) {                    // small factors: four destination columns per lane (k_resize_area_rows4's body)
         const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
         const int item = blk * 4 + wv;
@@ -2554,16 +2548,11 @@ template <int CN>
 __global__ __launch_bounds__(256) void k_resize_area_mix_tail(const MixTailDesc* __restrict__ d, MixIndex ix) {
     __shared__ __attribute__((aligned(16))) uint32_t s_line[4][64 * MIX_NV * 4 + 4];
     __shared__ uint32_t s_tile[4][16 * 65];                      // quarter turns: a band (<= 16 rows) waits here to leave turned
-    const int g = blockIdx.x & 7, q = blockIdx.x >> 3;
-    int lo = ix.off[g], hi = ix.off[g + 1];
-    if (lo == hi || q >= d[hi - 1].m.first + d[hi - 1].m.nblk) return;
-    while (hi - lo > 1) {                              // last descriptor whose first block is <= q
-        const int mid = (lo + hi) >> 1;
-        if (d[mid].m.first <= q) lo = mid; else hi = mid;
-    }
-    const MixTailDesc& t = d[lo];
+    int blk;
+    const int di = mix_pick(d, ix, &blk, [](const MixTailDesc& x) -> const MixDesc& { return x.m; });
+    if (di < 0) return;
+    const MixTailDesc& t = d[di];
     const MixDesc& m = t.m;
-    const int blk = q - m.first;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int item = blk * 4 + wv;
     if (item >= m.nitems) return;
@@ -3329,40 +3318,8 @@ int launch_cv_resize(const Frames& f, int interp, hipStream_t s) {
 // the launch's tail is made of light ones.  `v` is consumed; *sorted holds the descriptors list by list, *most = the
 // blocks of the longest list (the grid is 8 * most).
 template <class D, class M>
-static void mix_deal(std::vector<D>& v, M desc, std::vector<D>* sorted_out, MixIndex* ix_out, int* most_out) {
-    std::vector<int> order(v.size());
-    for (size_t i = 0; i < v.size(); i++) order[i] = (int)i;
-    auto cost = [&](int i) { return (long long)desc(v[i]).a.sw * desc(v[i]).a.sh; };
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return cost(x) > cost(y); });
-    std::vector<int> list[8];
-    long long load[8] = {0};
-    for (int i : order) {
-        int g = 0;
-        for (int k = 1; k < 8; k++)
-            if (load[k] < load[g]) g = k;
-        list[g].push_back(i);
-        load[g] += cost(i) + 4096;
-    }
-    std::vector<D>& sorted = *sorted_out;
-    sorted.clear();
-    sorted.reserve(v.size());
-    MixIndex& ix = *ix_out;
-    ix = MixIndex{};
-    int most = 0;
-    for (int g = 0; g < 8; g++) {
-        ix.off[g] = (int)sorted.size();
-        int first = 0;
-        for (int i : list[g]) {
-            D d = v[i];
-            desc(d).first = first;
-            first += desc(d).nblk;
-            sorted.push_back(d);
-        }
-        most = std::max(most, first);
-    }
-    ix.off[8] = (int)sorted.size();
-    v.clear();
-    *most_out = most;
+static void mix_deal_area(std::vector<D>& v, M desc, std::vector<D>* sorted_out, MixIndex* ix_out, int* most_out) {
+    imp::mix_deal(v, desc, [&](D& d) { return (long long)desc(d).a.sw * desc(d).a.sh; }, sorted_out, ix_out, most_out);
 }
 
 static int launch_mix(std::vector<MixDesc>& v, int cn, hipStream_t s) {
@@ -3370,7 +3327,7 @@ static int launch_mix(std::vector<MixDesc>& v, int cn, hipStream_t s) {
     std::vector<MixDesc> sorted;
     MixIndex ix{};
     int most = 0;
-    mix_deal(v, [](MixDesc& d) -> MixDesc& { return d; }, &sorted, &ix, &most);
+    mix_deal_area(v, [](MixDesc& d) -> MixDesc& { return d; }, &sorted, &ix, &most);
     void* dev = nullptr;
     if (int rc = upload_small(sorted.data(), sorted.size() * sizeof(MixDesc), &dev, s)) return rc;
     const dim3 grid((unsigned)most * 8), block(256);
@@ -3476,7 +3433,7 @@ int launch_area_tail_mixed(const TailItem* items, int count, int cn, hipStream_t
     std::vector<MixTailDesc> sorted;
     MixIndex ix{};
     int most = 0;
-    mix_deal(v, [](MixTailDesc& d) -> MixDesc& { return d.m; }, &sorted, &ix, &most);
+    mix_deal_area(v, [](MixTailDesc& d) -> MixDesc& { return d.m; }, &sorted, &ix, &most);
     void* dev = nullptr;
     if (int rc = upload_small(sorted.data(), sorted.size() * sizeof(MixTailDesc), &dev, s)) return rc;
     const dim3 grid((unsigned)most * 8), block(256);
