@@ -316,6 +316,31 @@ int   impgpu_png_stage_times(double* microseconds, int n);
  * as the device receives them -- after the chunk walk, the CRC checks and the inflate.  *length = the bytes the image needs
  * (set whenever the header was readable); IMP_ERROR_MALLOC_FAILED when capacity is smaller. */
 int   impgpu_png_scanlines(const unsigned char* blob, size_t size, unsigned char* out, size_t capacity, size_t* length);
+/* ---- PNG in, more kinds (opt-in: DESIGN.md "PNG decode", items and passes) ----
+ * The calls above with an `accept` mask of further kinds, each decoded as cvDecodeImage(blob, -1) over libpng 1.6 gives it:
+ *   IMPGPU_PNG_PALETTE   colour type 3, depth 1 / 2 / 4 / 8, no tRNS -> 3 channels, B,G,R from PLTE; an index past the
+ *                        PLTE's entries gives (0, 0, 0)
+ *   IMPGPU_PNG_LOW_GRAY  colour type 0, depth 1 / 2 / 4 -> 1 channel, samples scaled by 255 / 85 / 17 (tRNS not expanded)
+ *   IMPGPU_PNG_ADAM7     interlaced files of every kind otherwise taken (today's 8-bit gray / RGB / RGBA included): the
+ *                        pixels of the same image not interlaced
+ * A kind outside the mask is refused exactly as the call without _ex refuses it, and accept == 0 gives that call's answers.
+ * Still IMP_ERROR_UNSUPPORTED: palette with tRNS, gray + alpha, 16-bit, a PLTE of more than 2^depth entries, width > 4096
+ * or height > 16384.  IMP_ERROR_DECODE_FAILED besides the usual damage: a palette file without one PLTE before its IDAT, or
+ * with an empty PLTE, one longer than 768 bytes or not a multiple of 3; an Adam7 stream too short for its passes.
+ * Files of today's kinds that are not interlaced go the way they go without _ex (a lone file streams its rows); the others
+ * are inflated on the host, each non-empty pass (or the whole file) is unfiltered by k_png_unfilter_batch as an item of its
+ * own, and k_png_place writes the answer's pixels: one launch per channel count for the whole call. */
+#define IMPGPU_PNG_PALETTE  1
+#define IMPGPU_PNG_LOW_GRAY 2
+#define IMPGPU_PNG_ADAM7    4
+#define IMPGPU_PNG_ALL      (IMPGPU_PNG_PALETTE | IMPGPU_PNG_LOW_GRAY | IMPGPU_PNG_ADAM7)
+int   impgpu_image_decode_png_ex(const unsigned char* blob, size_t size, int accept, impgpu_image** out);
+int   impgpu_batch_decode_png_ex(const unsigned char* const* blobs, const size_t* sizes, int count, int accept,
+                                 impgpu_image** images, int* codes, int* launches);
+int   impgpu_png_info_ex(const unsigned char* blob, size_t size, int accept, int* width, int* height, int* channels);
+/* Diagnostic (host, no device): the filtered bytes of every non-empty pass in pass order (one item when not interlaced), each
+ * pass's rows of (1 filter byte + ceil(pass width * bits per pixel / 8) bytes).  *length as impgpu_png_scanlines. */
+int   impgpu_png_scanlines_ex(const unsigned char* blob, size_t size, int accept, unsigned char* out, size_t capacity, size_t* length);
 int   impgpu_image_wrap(void* device_ptr, int width, int height, int channels, int step,
                         impgpu_image** out);               /* borrow memory already in HBM */
 int   impgpu_image_clone(const impgpu_image* src, impgpu_image** out);

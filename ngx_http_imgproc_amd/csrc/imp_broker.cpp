@@ -7,7 +7,7 @@
 // gets a batch of one (the latency of the in-process path plus two futex hops), 32 busy workers ride 16-32 to a launch.
 // A batch is one straight pass: take, prepare, decode, operators, answers, finish --
 //     files          impgpu_batch_decode_jpeg_prepared   cvDecodeImage, bridge.c:545-552
-//                    impgpu_batch_decode_png
+//                    impgpu_batch_decode_png (_ex with --png-accept all)
 //     operators      impgpu_batch_run_ops                bridge.c:574-656: crop -> resize -> rotate -> watermark -> flatten
 //                                                        chains share one launch per channel count; anything else runs
 //                                                        request by request (impgpu_run_ops) inside the same call
@@ -19,7 +19,7 @@
 // the answer's placement is the broker's own: it is written to the slot for the worker and never read back from there.
 //
 //   impgpu_broker [--name /impgpu-broker-0] [--device 0] [--slots 64] [--slot-mb 32] [--register-mb 8] [--threads 2] [--batch 64]
-//                 [--gather-us 0] [--supervise] [--ready-file PATH]
+//                 [--gather-us 0] [--png-accept none|all] [--supervise] [--ready-file PATH]
 // --supervise: this process only forks and watches; the child is the broker.  A child that dies (a lost device, a bug) is
 // replaced by a FRESH child -- fork() from a parent that never touched the GPU, no exec of a process that did.
 #include <impgpu_broker.h>
@@ -65,6 +65,9 @@ struct Options {
     int threads = 2;
     int batch = 64;
     int gather_us = 0;
+    // --png-accept all: the batch's PNG uploads go through impgpu_batch_decode_png_ex with IMPGPU_PNG_ALL (palette, 1/2/4-bit
+    // gray, Adam7); none (the default) keeps the kinds impgpu_batch_decode_png takes.  Refusals are NOT_TAKEN either way.
+    int png_accept = 0;
     bool supervise = false;
     std::string ready_file;
 };
@@ -388,7 +391,7 @@ struct Worker {
                 png_blobs[j] = reqs[pngs[j]].in;
                 png_sizes[j] = (size_t)reqs[pngs[j]].q.in_bytes;
             }
-            decoded(pngs, impgpu_batch_decode_png(png_blobs.data(), png_sizes.data(), (int)m, imgs.data(), codes.data(), nullptr));
+            decoded(pngs, impgpu_batch_decode_png_ex(png_blobs.data(), png_sizes.data(), (int)m, O.png_accept, imgs.data(), codes.data(), nullptr));
         }
         for (size_t k = 0; k < n; k++) {
             Req& r = reqs[k];
@@ -661,8 +664,14 @@ int main(int argc, char** argv) {
         else if (a == "--batch") o.batch = std::atoi(val("--batch"));
         else if (a == "--gather-us") o.gather_us = std::atoi(val("--gather-us"));
         else if (a == "--ready-file") o.ready_file = val("--ready-file");
+        else if (a == "--png-accept") {
+            const std::string v = val("--png-accept");
+            if (v == "all") o.png_accept = IMPGPU_PNG_ALL;
+            else if (v == "none") o.png_accept = 0;
+            else { std::fprintf(stderr, "impgpu_broker: --png-accept takes all or none\n"); return 2; }
+        }
         else if (a == "--supervise") o.supervise = true;
-        else { std::fprintf(stderr, "usage: impgpu_broker [--name /impgpu-broker-0] [--device 0] [--slots 64] [--slot-mb 32] [--register-mb 8] [--threads 2] [--batch 64] [--gather-us 0] [--supervise] [--ready-file PATH]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: impgpu_broker [--name /impgpu-broker-0] [--device 0] [--slots 64] [--slot-mb 32] [--register-mb 8] [--threads 2] [--batch 64] [--gather-us 0] [--png-accept none|all] [--supervise] [--ready-file PATH]\n"); return 2; }
     }
     if (o.slots < 1 || o.slots > IMPB_MAX_SLOTS || o.slot_mb < 1 || o.slot_mb > 4096 || o.threads < 1 || o.threads > 32 || o.batch < 1 || o.batch > 256 ||
         o.name.empty() || o.name[0] != '/') {

@@ -302,6 +302,112 @@ static int launch_png_unfilter_batch(const PngJob* djobs, int count, size_t lds,
     return IMP_OK;
 }
 
+// ---- k_png_place: the answer's pixels of a file whose items (Adam7 passes, or the whole file of a palette / low-bit gray
+// kind) k_png_unfilter_batch has unfiltered into planes of their own.  A gather: every output pixel is written once, four per
+// thread (one word of gray, three words of B,G,R, four of B,G,R,A); its pass and pass coordinates follow from (x & 7, y & 7)
+// (PNG specification 8.2).  Samples of 1 / 2 / 4 bits are unpacked from the plane's bytes (the leftmost pixel in the high
+// bits, 7.2), low-bit gray is scaled to 8 bits (x 255 / 85 / 17, as png_set_expand_gray_1_2_4_to_8), a palette index is looked
+// up in the file's 256-entry palette, copied to LDS.  RGB / RGBA planes are B,G,R(,A) already: k_png_unfilter_batch swaps.
+// Descriptors are dealt like k_geom_mix's; a workgroup covers PLACE_QUADS quads of one file.
+constexpr int PLACE_QUADS = 256 * 4;
+struct PngPlaceDesc {
+    uint8_t* dst; int w, h, step;
+    const uint8_t* plane[7];             // by Adam7 pass (plane[0] alone when not interlaced)
+    int pstep[7];
+    const uint32_t* pal;                 // palette files: 256 words B | G << 8 | R << 16; null otherwise
+    int depth, spp, adam7, scale;        // scale: the gray multiplier (1 at depth 8)
+    int first, nblk;
+};
+
+template <int C>
+__device__ __forceinline__ uint32_t png_place_pixel(const PngPlaceDesc& d, const uint32_t* s_pal, int x, int y) {
+    int p = 0, px = x, py = y;
+    if (d.adam7) {
+        // the pass of (x, y): odd rows are pass 7, odd columns pass 6, then 5, 4, 3, 2 by the next bits, else pass 1
+        p = (y & 1) ? 6 : (x & 1) ? 5 : (y & 2) ? 4 : (x & 2) ? 3 : (y & 4) ? 2 : (x & 4) ? 1 : 0;
+        const int xs = p == 6 ? 0 : p >= 4 ? 1 : p >= 2 ? 2 : 3;                 // log2 of the pass's column step
+        const int ys = p >= 5 ? 1 : p >= 3 ? 2 : 3;
+        px = x >> xs;
+        py = y >> ys;
+    }
+    const uint8_t* row = d.plane[p] + (size_t)py * d.pstep[p];
+    if (C == 1 || d.pal) {
+        uint32_t v;
+        if (d.depth == 8) v = row[px];
+        else {
+            const int bit = px * d.depth;
+            v = ((uint32_t)row[bit >> 3] >> (8 - d.depth - (bit & 7))) & ((1u << d.depth) - 1u);
+        }
+        if (C == 1) return v * (uint32_t)d.scale;
+        return s_pal[v];
+    }
+    const uint8_t* q = row + (size_t)px * C;
+    uint32_t v = (uint32_t)q[0] | (uint32_t)q[1] << 8 | (uint32_t)q[2] << 16;
+    if (C == 4) v |= (uint32_t)q[3] << 24;
+    return v;
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void k_png_place(const PngPlaceDesc* __restrict__ descs, MixIndex ix) {
+    __shared__ uint32_t s_pal[256];
+    int blk;
+    const int di = mix_pick(descs, ix, &blk);
+    if (di < 0) return;
+    const PngPlaceDesc& d = descs[di];
+    if (C == 3 && d.pal) {                                           // (the branch is the workgroup's: one file)
+        s_pal[threadIdx.x] = d.pal[threadIdx.x];
+        __syncthreads();
+    }
+    const int Q = (d.w + 3) >> 2;
+    const long long nq = (long long)Q * d.h;
+#pragma unroll 1
+    for (int it = 0; it < PLACE_QUADS / 256; it++) {
+        const long long q = (long long)blk * PLACE_QUADS + it * 256 + threadIdx.x;
+        if (q >= nq) break;
+        const int y = (int)(q / Q), x0 = (int)(q - (long long)y * Q) * 4;
+        const int n = d.w - x0 >= 4 ? 4 : d.w - x0;
+        uint32_t v[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            if (i < n) v[i] = png_place_pixel<C>(d, s_pal, x0 + i, y);
+        uint8_t* o = d.dst + (size_t)y * d.step + (size_t)x0 * C;
+        if (n == 4) {                                                // (rows are 4-byte aligned)
+            uint32_t* w = (uint32_t*)o;
+            if (C == 1) w[0] = v[0] | v[1] << 8 | v[2] << 16 | v[3] << 24;
+            else if (C == 3) {
+                w[0] = v[0] | v[1] << 24;
+                w[1] = v[1] >> 8 | v[2] << 16;
+                w[2] = v[2] >> 16 | v[3] << 8;
+            } else {
+                w[0] = v[0]; w[1] = v[1]; w[2] = v[2]; w[3] = v[3];
+            }
+        } else {
+            for (int i = 0; i < n; i++)
+                for (int ch = 0; ch < C; ch++) o[i * C + ch] = (uint8_t)(v[i] >> (8 * ch));
+        }
+    }
+}
+
+// the descriptors of one channel count: ONE launch
+static int launch_png_place(std::vector<PngPlaceDesc>& v, int c, hipStream_t s) {
+    if (v.empty()) return IMP_OK;
+    for (PngPlaceDesc& d : v) d.nblk = (int)(((long long)((d.w + 3) >> 2) * d.h + PLACE_QUADS - 1) / PLACE_QUADS);
+    std::vector<PngPlaceDesc> sorted;
+    MixIndex ix{};
+    int most = 0;
+    mix_deal(v, [](PngPlaceDesc& d) -> PngPlaceDesc& { return d; }, [](PngPlaceDesc& d) { return (long long)d.w * d.h; }, &sorted, &ix, &most);
+    void* dev = nullptr;
+    if (int rc = upload_small(sorted.data(), sorted.size() * sizeof(PngPlaceDesc), &dev, s)) return rc;
+    const dim3 grid((unsigned)most * 8), block(256);
+    if (c == 4) hipLaunchKernelGGL(k_png_place<4>, grid, block, 0, s, (const PngPlaceDesc*)dev, ix);
+    else if (c == 3) hipLaunchKernelGGL(k_png_place<3>, grid, block, 0, s, (const PngPlaceDesc*)dev, ix);
+    else hipLaunchKernelGGL(k_png_place<1>, grid, block, 0, s, (const PngPlaceDesc*)dev, ix);
+    const hipError_t e = hipGetLastError();
+    dev_free(dev);                                                   // (handed out again in lane-stream order)
+    if (e != hipSuccess) { set_error("k_png_place", e); return IMP_ERROR_DEVICE; }
+    return IMP_OK;
+}
+
 // ---- impgpu_batch_decode_png: many files, one set of launches
 constexpr int PNG_MAX_BATCH = 256;
 constexpr size_t PNG_REGION_ALIGN = 256;    // a file's scanlines start on this boundary of the staging buffer (and its device copy)
@@ -309,8 +415,18 @@ constexpr size_t PNG_REGION_ALIGN = 256;    // a file's scanlines start on this 
 namespace {
 struct PngBatchFile {
     PngHeader H;
+    PngLayout L;
     size_t raw = 0, off = 0;                 // scanline bytes; their region in the group's buffer
+    size_t region = 0;                       // bytes of that region: scanlines, slack, the palette of a palette file
+    size_t poff = 0;                         // an item file's planes: their place in the group's plane buffer
 };
+// the plane of an item: its unfiltered rows, 4-byte aligned
+size_t png_plane_step(const PngItem& it) { return (it.rowbytes + 3) & ~(size_t)3; }
+size_t png_planes_bytes(const PngLayout& L) {
+    size_t b = 0;
+    for (int k = 0; k < L.n; k++) b += png_plane_step(L.item[k]) * L.item[k].h;
+    return b;
+}
 }  // namespace
 
 // What the summed scanlines of one group may take: the staging cap (IMPGPU_STAGE_CAP_MB, imp_runtime.hip) that the lane's
@@ -326,13 +442,22 @@ static size_t png_group_cap() {
 
 // Files idx[0..n) (all accepted by their headers), one staging buffer: the inflates side by side on the host helper pool, one
 // upload, the frames, one k_png_unfilter_batch launch per channel count present.  Sets codes[] / images[] of its files; a
-// non-zero return is a device error that ends the call.
+// non-zero return is a device error that ends the call.  A file of today's kinds, not interlaced (L.plain), is one job that
+// k_png_unfilter_batch unfilters into its frame; every other file's items are jobs of the same launches that unfilter into
+// planes of a second device buffer (rows of bytes: the filter unit is the launch's bpp, the R/B swap of 3 / 4 makes the
+// planes B,G,R(,A)), and k_png_place then writes those files' frames, one launch per channel count.  A group of plain files
+// alone makes exactly the launches it made before the item files existed.
 static int png_group(const unsigned char* const* blobs, const size_t* sizes, std::vector<PngBatchFile>& F, const std::vector<int>& idx,
                      impgpu_image** images, int* codes) {
-    size_t total = 0;
+    size_t total = 0, ptotal = 0;
     for (int i : idx) {
-        F[(size_t)i].off = total;
-        total += (F[(size_t)i].raw + PNG_RAW_SLACK + PNG_REGION_ALIGN - 1) / PNG_REGION_ALIGN * PNG_REGION_ALIGN;
+        PngBatchFile& f = F[(size_t)i];
+        f.off = total;
+        total += f.region;
+        if (!f.L.plain) {
+            f.poff = ptotal;
+            ptotal += (png_planes_bytes(f.L) + PNG_REGION_ALIGN - 1) / PNG_REGION_ALIGN * PNG_REGION_ALIGN;
+        }
     }
     void *host = nullptr, *token = nullptr;
     int rc = stage_begin(total, &host, &token);
@@ -341,7 +466,8 @@ static int png_group(const unsigned char* const* blobs, const size_t* sizes, std
     auto inflate = [&](int i) {
         PngBatchFile& f = F[(size_t)i];
         std::memset(hb + f.off + f.raw, 0, PNG_RAW_SLACK);
-        codes[i] = png_scanlines(blobs[i], sizes[i], f.H, hb + f.off);
+        if (f.L.palette) std::memcpy(hb + f.off + f.region - sizeof f.L.pal, f.L.pal, sizeof f.L.pal);
+        codes[i] = f.L.plain ? png_scanlines(blobs[i], sizes[i], f.H, hb + f.off) : png_scanlines_items(blobs[i], sizes[i], f.L, hb + f.off);
     };
     host_parallel(idx, total, inflate);
     void* dev = nullptr;
@@ -349,17 +475,40 @@ static int png_group(const unsigned char* const* blobs, const size_t* sizes, std
     if (rc) { (void)stage_upload(token, nullptr, 0); return rc; }
     rc = stage_upload(token, dev, total);
     if (rc) { dev_free(dev); return rc; }
+    void* planes = nullptr;
+    if (ptotal && (rc = dev_alloc(ptotal, &planes))) { dev_free(dev); return rc; }
     std::vector<PngJob> jobs[5];
+    std::vector<PngPlaceDesc> place[5];
     size_t lds[5] = {0, 0, 0, 0, 0};
     for (int i : idx) {
         if (codes[i] != IMP_OK) continue;
         const PngBatchFile& f = F[(size_t)i];
         impgpu_image* im = nullptr;
-        codes[i] = image_new(f.H.w, f.H.h, f.H.bpp, &im);
+        codes[i] = image_new(f.H.w, f.H.h, f.L.channels, &im);
         if (codes[i] != IMP_OK) continue;
         images[i] = im;
-        jobs[f.H.bpp].push_back(PngJob{(const uint8_t*)dev + f.off, im->d, nullptr, f.H.w, f.H.h, im->step});
-        lds[f.H.bpp] = std::max(lds[f.H.bpp], png_lds_bytes(f.H.w, f.H.h));
+        const uint8_t* raw = (const uint8_t*)dev + f.off;
+        if (f.L.plain) {
+            jobs[f.H.bpp].push_back(PngJob{raw, im->d, nullptr, f.H.w, f.H.h, im->step});
+            lds[f.H.bpp] = std::max(lds[f.H.bpp], png_lds_bytes(f.H.w, f.H.h));
+            continue;
+        }
+        PngPlaceDesc d{};
+        d.dst = im->d; d.w = f.H.w; d.h = f.H.h; d.step = im->step;
+        d.pal = f.L.palette ? (const uint32_t*)(raw + f.region - sizeof f.L.pal) : nullptr;
+        d.depth = f.L.depth; d.spp = f.L.spp; d.adam7 = f.H.interlace;
+        d.scale = f.L.depth == 8 || f.L.palette ? 1 : 255 / ((1 << f.L.depth) - 1);
+        uint8_t* pl = (uint8_t*)planes + f.poff;
+        for (int k = 0; k < f.L.n; k++) {
+            const PngItem& it = f.L.item[k];
+            const int jw = (int)(it.rowbytes / (size_t)f.L.fu);         // the item as a frame of jw pixels of fu bytes
+            jobs[f.L.fu].push_back(PngJob{raw + it.off, pl, nullptr, jw, it.h, (int)png_plane_step(it)});
+            lds[f.L.fu] = std::max(lds[f.L.fu], png_lds_bytes(jw, it.h));
+            d.plane[it.pass] = pl;
+            d.pstep[it.pass] = (int)png_plane_step(it);
+            pl += png_plane_step(it) * it.h;
+        }
+        place[f.L.channels].push_back(d);
     }
     hipStream_t s = env_stream();
     for (int bpp : {1, 3, 4}) {
@@ -371,6 +520,9 @@ static int png_group(const unsigned char* const* blobs, const size_t* sizes, std
             dev_free(djobs);                                         // (handed out again in lane-stream order)
         }
     }
+    for (int c : {1, 3, 4})
+        if (!rc) rc = launch_png_place(place[c], c, s);
+    if (planes) dev_free(planes);
     dev_free(dev);
     if (rc)
         for (int i : idx)
@@ -398,6 +550,11 @@ int impgpu_png_stage_times(double* microseconds, int n) {
 
 int impgpu_batch_decode_png(const unsigned char* const* blobs, const size_t* sizes, int count, impgpu_image** images, int* codes,
                             int* launches) {
+    return impgpu_batch_decode_png_ex(blobs, sizes, count, 0, images, codes, launches);
+}
+
+int impgpu_batch_decode_png_ex(const unsigned char* const* blobs, const size_t* sizes, int count, int accept, impgpu_image** images,
+                               int* codes, int* launches) {
     if (!blobs || !sizes || !images || !codes || count < 0 || count > PNG_MAX_BATCH) return IMP_ERROR_INVALID_ARGS;
     if (launches) *launches = 0;
     if (!env_ready()) { set_error_text("impgpu_env_start has not been called"); return IMP_ERROR_DEVICE; }
@@ -413,9 +570,10 @@ int impgpu_batch_decode_png(const unsigned char* const* blobs, const size_t* siz
         PngBatchFile& f = F[(size_t)i];
         codes[i] = png_header(blobs[i], sizes[i], &f.H);
         if (codes[i]) continue;
-        if (!f.H.taken) { codes[i] = IMP_ERROR_UNSUPPORTED; continue; }
-        f.raw = ((size_t)f.H.w * f.H.bpp + 1) * f.H.h;
+        if ((codes[i] = png_layout(blobs[i], sizes[i], f.H, accept, &f.L))) continue;
+        f.raw = f.L.raw;
         if (f.raw / 1032 > sizes[i]) { codes[i] = IMP_ERROR_DECODE_FAILED; continue; }
+        f.region = (f.raw + PNG_RAW_SLACK + PNG_REGION_ALIGN - 1) / PNG_REGION_ALIGN * PNG_REGION_ALIGN + (f.L.palette ? sizeof f.L.pal : 0);
         taken.push_back(i);
     }
     // groups in file order, each within the staging cap
@@ -425,7 +583,8 @@ int impgpu_batch_decode_png(const unsigned char* const* blobs, const size_t* siz
         std::vector<int> idx;
         size_t bytes = 0;
         for (; a < taken.size(); a++) {
-            const size_t need = F[(size_t)taken[a]].raw + PNG_RAW_SLACK + PNG_REGION_ALIGN;
+            const PngBatchFile& f = F[(size_t)taken[a]];
+            const size_t need = f.raw + PNG_RAW_SLACK + PNG_REGION_ALIGN + (f.L.plain ? 0 : sizeof f.L.pal + png_planes_bytes(f.L) + PNG_REGION_ALIGN);
             if (!idx.empty() && bytes + need > cap) break;
             idx.push_back(taken[a]);
             bytes += need;
@@ -438,6 +597,20 @@ int impgpu_batch_decode_png(const unsigned char* const* blobs, const size_t* siz
     }
     if (launches) *launches = (int)(t_launches - launched);
     return rc;
+}
+
+int impgpu_image_decode_png_ex(const unsigned char* blob, size_t size, int accept, impgpu_image** out) {
+    if (!out) return IMP_ERROR_INVALID_ARGS;
+    *out = nullptr;
+    if (!env_ready()) { set_error_text("impgpu_env_start has not been called"); return IMP_ERROR_DEVICE; }
+    PngHeader H;
+    int rc = png_header(blob, size, &H);
+    if (rc) return rc;
+    if (H.taken || !accept) return impgpu_image_decode_png(blob, size, out);       // (today's kinds stream their rows)
+    // every other kind: a batch of one (its items are the launch's workgroups)
+    int code = IMP_OK;
+    rc = impgpu_batch_decode_png_ex(&blob, &size, 1, accept, out, &code, nullptr);
+    return rc ? rc : code;
 }
 
 int impgpu_image_decode_png(const unsigned char* blob, size_t size, impgpu_image** out) {

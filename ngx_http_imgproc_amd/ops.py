@@ -24,6 +24,12 @@ IMP_ERROR_TOO_MUCH_FILTERS = 55
 IMP_ERROR_DEVICE = 90
 INTER_NN, INTER_LINEAR, INTER_CUBIC, INTER_AREA, INTER_LANCZOS4 = 0, 1, 2, 3, 4
 
+# impgpu_*_png_ex accept masks (include/impgpu.h)
+PNG_PALETTE = 1
+PNG_LOW_GRAY = 2
+PNG_ADAM7 = 4
+PNG_ALL = PNG_PALETTE | PNG_LOW_GRAY | PNG_ADAM7
+
 
 def _b(s):
     return None if s is None else (s if isinstance(s, bytes) else str(s).encode())
@@ -123,6 +129,14 @@ class Image:
         -> (code, Image or None)."""
         h = C.c_void_p()
         rc = lib.impgpu_image_decode_png(bytes(blob), len(blob), C.byref(h))
+        return rc, (cls(handle=h.value) if rc == 0 else None)
+
+    @classmethod
+    def decode_png_ex(cls, blob, accept):
+        """impgpu_image_decode_png_ex: decode_png that also takes the kinds of `accept` (PNG_PALETTE | PNG_LOW_GRAY | PNG_ADAM7)
+        -> (code, Image or None)."""
+        h = C.c_void_p()
+        rc = lib.impgpu_image_decode_png_ex(bytes(blob), len(blob), int(accept), C.byref(h))
         return rc, (cls(handle=h.value) if rc == 0 else None)
 
     @classmethod
@@ -338,6 +352,21 @@ def batch_decode_png(blobs):
     return [(codes[i], Image(handle=imgs[i]) if codes[i] == 0 else None) for i in range(n)], launches.value
 
 
+def batch_decode_png_ex(blobs, accept):
+    """impgpu_batch_decode_png_ex -> ([(code, Image or None)] in the order of `blobs`, kernel launches of the call)."""
+    n = len(blobs)
+    keep = [bytes(b) for b in blobs]
+    arr = (C.c_char_p * max(1, n))(*keep)
+    sizes = (C.c_size_t * max(1, n))(*[len(b) for b in keep])
+    imgs = (C.c_void_p * max(1, n))()
+    codes = (C.c_int * max(1, n))()
+    launches = C.c_int()
+    rc = lib.impgpu_batch_decode_png_ex(arr, sizes, n, int(accept), imgs, codes, C.byref(launches))
+    if rc:
+        raise ImpError(rc, "impgpu_batch_decode_png_ex")
+    return [(codes[i], Image(handle=imgs[i]) if codes[i] == 0 else None) for i in range(n)], launches.value
+
+
 def jpeg_unstuff(blob):
     """impgpu_jpeg_unstuff of libimpgpu_client.so (what a worker does on the way into its slot) -> (head, scan) or None when
     the file is to go as it is."""
@@ -500,6 +529,23 @@ def png_info(blob):
     w, h, c = C.c_int(), C.c_int(), C.c_int()
     rc = lib.impgpu_png_info(bytes(blob), len(blob), w, h, c)
     return rc, (w.value, h.value, c.value)
+
+
+def png_info_ex(blob, accept):
+    w, h, c = C.c_int(), C.c_int(), C.c_int()
+    rc = lib.impgpu_png_info_ex(bytes(blob), len(blob), int(accept), w, h, c)
+    return rc, (w.value, h.value, c.value)
+
+
+def png_scanlines_ex(blob, accept):
+    """impgpu_png_scanlines_ex (host, no device): the filtered bytes of every non-empty pass -> (code, bytes or None)"""
+    n = C.c_size_t(0)
+    rc = lib.impgpu_png_scanlines_ex(bytes(blob), len(blob), int(accept), None, 0, C.byref(n))
+    if rc != IMP_ERROR_MALLOC_FAILED:
+        return rc, None
+    buf = np.zeros(max(1, n.value), np.uint8)
+    rc = lib.impgpu_png_scanlines_ex(bytes(blob), len(blob), int(accept), buf.ctypes.data, buf.size, C.byref(n))
+    return rc, (buf[: n.value].tobytes() if rc == 0 else None)
 
 
 def png_stage_times():
