@@ -288,6 +288,49 @@ int   impgpu_jpeg_info(const unsigned char* blob, size_t size, int* width, int* 
  * [5] = overlap bits, [6] = walks per chunk. */
 int   impgpu_jpeg_coefficients(const unsigned char* blob, size_t size, int how, short* out, size_t capacity, int* info);
 void  impgpu_jpeg_sync_stats(int stats[8]);
+/* ---- progressive JPEG in (opt-in: nothing changes for a caller who does not ask) ----
+ * The calls above with an `accept` mask.  accept == 0: the old call's answers, codes and launch counts.  With
+ * IMPGPU_JPEG_PROGRESSIVE a call also takes SOF2 files: 8-bit, 1 or 3 components, the sampling factors the sequential path
+ * takes, up to 32 scans in any legal order (libjpeg's default script has 10, mozjpeg's 9 to 12) -- DC scans interleaved or
+ * not, AC scans, spectral selection, successive approximation, DHT and DRI segments between scans, restart intervals.  A
+ * complete progressive file holds the coefficients of its sequential twin and libjpeg makes the same pixels of them, so
+ * the frame is bit-identical to libjpeg-turbo's here too.
+ * IMP_ERROR_UNSUPPORTED, at the header (decode with cvDecodeImage as before): a scan script after which some coefficient
+ * has not been sent down to Al = 0 (libjpeg would smooth, or show a coarse image); a progression T.81 G.1.1.1.1 forbids (AC
+ * before DC, a refinement whose Ah is not the previous Al, a band sent twice, an AC scan of several components, Ss / Se out
+ * of range: libjpeg only warns); more than 32 scans; a DQT segment behind the first scan.  IMP_ERROR_DECODE_FAILED: damaged
+ * entropy data (a code that is not in the table, an interval that runs out of bits or has a byte or more left over, a wrong
+ * RSTn, no EOI), found on the device per file -- a bad file changes no other file's result.
+ * How it runs: the host walks the markers and unstuffs every scan into the call's one upload; the device zeroes the
+ * planes, then decodes (file, scan, restart interval) items, one launch per LEVEL for the whole call -- a scan's level is
+ * 1 + the highest level of an earlier scan that touches the same component and an overlapping band; libjpeg's ten-scan
+ * script has three -- so the launches follow the deepest script of the batch, not the number of files; then the same
+ * pixel kernels as for sequential files.  (impgpu_batch_decode_jpeg_ex cuts a batch of 32 files or more into two groups
+ * like impgpu_batch_decode_jpeg does: each group has its own launches.)  There is no parallelism INSIDE an interval: a
+ * lone large file without restart intervals has a handful of items per level and is decoded by as many lanes.
+ * MEASURED (profiles/jpeg_prog_probe.json): that loses to the host.  A lone 640 x 480 / 1080p / 4K progressive
+ * photograph takes 0.30 / 2.1 / 8.3 s here against 3.2 / 21 / 103 ms for libjpeg-turbo on one core plus
+ * impgpu_image_upload, and a batch of 64 still 10 / 67 ms per file against those 3.2 / 21: a lane decodes about 0.3 MB/s.
+ * Until a scan is decoded by many lanes (not built) keep progressive files on the host unless moving the work off the
+ * host's cores is worth that latency; the call does not switch by size on its own.
+ * _finish and _pending serve batches begun either way; _pending returns the frame of a progressive file like any other's
+ * (it is NULL only where the old call's is).  In _prepared_begin_ex a progressive file comes whole: head = the file,
+ * scan == NULL (impgpu_jpeg_unstuff passes such a file on whole).  impgpu_jpeg_classify keeps answering 1 for SOF2: it
+ * names a kind, not a refusal.  impgpu_jpeg_counters [13] = progressive files decoded on the device, [14] = level
+ * launches made for them ([5] keeps counting the progressive files REFUSED).  impgpu_jpeg_stage_times [13] = the zero fill
+ * and the level launches of the call's last group in microseconds (events), [14] = how many level launches, [15] = its
+ * progressive files.
+ * impgpu_jpeg_coefficients_ex (host, no device): how = 0 a plain bit-by-bit decoder of the file as it is; how = 1 the
+ * device's items run one after the other on the host by the lanes' own code; info[2] = the script's levels. */
+#define IMPGPU_JPEG_PROGRESSIVE 1
+int   impgpu_image_decode_jpeg_ex(const unsigned char* blob, size_t size, int accept, impgpu_image** out);
+int   impgpu_batch_decode_jpeg_ex(const unsigned char* const* blobs, const size_t* sizes, int count, int accept,
+                                  impgpu_image** images, int* codes);
+int   impgpu_batch_decode_jpeg_begin_ex(const unsigned char* const* blobs, const size_t* sizes, int count, int accept,
+                                        impgpu_jpeg_batch** batch);
+int   impgpu_batch_decode_jpeg_prepared_begin_ex(const impgpu_jpeg_prepared* files, int count, int accept, impgpu_jpeg_batch** batch);
+int   impgpu_jpeg_info_ex(const unsigned char* blob, size_t size, int accept, int* width, int* height, int* channels);
+int   impgpu_jpeg_coefficients_ex(const unsigned char* blob, size_t size, int how, int accept, short* out, size_t capacity, int* info);
 /* ---- PNG in (round 4, a bounded experiment: DESIGN.md "PNG decode") ----
  * cvDecodeImage(&rawencoded, -1) (bridge.c:545-552) for a PNG blob (SIG_PNG, bridge.c:376-378), i.e. OpenCV 2.4's PngDecoder
  * over libpng with the "unchanged" flag: 8-bit gray -> 1 channel, RGB -> BGR, RGBA -> BGRA, tRNS not expanded.  The zlib

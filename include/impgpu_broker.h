@@ -55,7 +55,10 @@ enum { IMPB_OUT_JPEG = 0 /* cvEncodeImage(".jpg"), bridge.c:704 */, IMPB_OUT_FRA
        IMPB_OUT_ASCII = 3 /* the text exit, ASCII() of filters.c:486-522 (bridge.c:669-670) */,
        IMPB_OUT_PNG = 4 /* cvEncodeImage(".png"), bridge.c:704; `quality` = the compression level */ };
 /* answer codes besides IMP_*: the broker did not take the file (not a JPEG/PNG the device decodes, or damaged) -- the
- * worker decodes on the host as before and comes back with IMPB_IN_FRAME */
+ * worker decodes on the host as before and comes back with IMPB_IN_FRAME.  Which files the device decodes is the
+ * broker's to say: `impgpu_broker --jpeg-accept progressive` takes progressive (SOF2) JPEG uploads too -- they reach it
+ * whole, impgpu_jpeg_unstuff passes them on -- and `--png-accept all` palette, 1/2/4-bit gray and Adam7 PNG uploads;
+ * by default both stay IMPB_NOT_TAKEN.  The client side is the same either way. */
 #define IMPB_NOT_TAKEN    (-1)
 
 typedef struct {

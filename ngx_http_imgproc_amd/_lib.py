@@ -137,6 +137,12 @@ SIGNATURES = {
     "impgpu_png_info_ex": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, IP, IP, IP]),
     "impgpu_png_scanlines_ex": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "impgpu_jpeg_coefficients": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, P, C.c_size_t, IP]),
+    "impgpu_image_decode_jpeg_ex": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, PP]),
+    "impgpu_batch_decode_jpeg_ex": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, PP, IP]),
+    "impgpu_batch_decode_jpeg_begin_ex": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, PP]),
+    "impgpu_batch_decode_jpeg_prepared_begin_ex": (C.c_int, [C.POINTER(CJpegPrepared), C.c_int, C.c_int, PP]),
+    "impgpu_jpeg_info_ex": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, IP, IP, IP]),
+    "impgpu_jpeg_coefficients_ex": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.c_int, P, C.c_size_t, IP]),
     "impgpu_jpeg_sync_stats": (None, [IP]),
     "impgpu_jpeg_profile": (C.c_int, [C.c_int]),
     "impgpu_jpeg_counters": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),

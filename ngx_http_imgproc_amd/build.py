@@ -22,6 +22,7 @@ SOURCES = [
     "imp_blur.hip",
     "imp_jpeg.hip",
     "imp_jpeg_enc.hip",
+    "imp_jpeg_prog.hip",
     "imp_png.hip",
     "imp_png_enc.hip",
     "imp_api.cpp",
@@ -30,10 +31,11 @@ SOURCES = [
     "imp_tables.cpp",
     "imp_jpeg.cpp",
     "imp_jpeg_api.cpp",
+    "imp_jpeg_prog.cpp",
     "imp_png.cpp",
     "imp_inflate.cpp",
 ]
-HEADERS = ["imp_internal.h", "imp_host_pool.h", "imp_jpeg.h", "imp_jpeg_core.h", "imp_jpeg_std.h", "imp_png.h", "imp_png_deflate.h", "imp_inflate.h", os.path.join("..", "..", "include", "impgpu.h")]
+HEADERS = ["imp_internal.h", "imp_host_pool.h", "imp_jpeg.h", "imp_jpeg_core.h", "imp_jpeg_prog.h", "imp_jpeg_std.h", "imp_png.h", "imp_png_deflate.h", "imp_inflate.h", os.path.join("..", "..", "include", "impgpu.h")]
 FLAGS = [
     "--offload-arch=gfx950",
     "-O3",

@@ -19,7 +19,7 @@
 // the answer's placement is the broker's own: it is written to the slot for the worker and never read back from there.
 //
 //   impgpu_broker [--name /impgpu-broker-0] [--device 0] [--slots 64] [--slot-mb 32] [--register-mb 8] [--threads 2] [--batch 64]
-//                 [--gather-us 0] [--png-accept none|all] [--supervise] [--ready-file PATH]
+//                 [--gather-us 0] [--png-accept none|all] [--jpeg-accept none|progressive] [--supervise] [--ready-file PATH]
 // --supervise: this process only forks and watches; the child is the broker.  A child that dies (a lost device, a bug) is
 // replaced by a FRESH child -- fork() from a parent that never touched the GPU, no exec of a process that did.
 #include <impgpu_broker.h>
@@ -68,6 +68,10 @@ struct Options {
     // --png-accept all: the batch's PNG uploads go through impgpu_batch_decode_png_ex with IMPGPU_PNG_ALL (palette, 1/2/4-bit
     // gray, Adam7); none (the default) keeps the kinds impgpu_batch_decode_png takes.  Refusals are NOT_TAKEN either way.
     int png_accept = 0;
+    // --jpeg-accept progressive: the batch's JPEG uploads go through impgpu_batch_decode_jpeg_prepared_begin_ex with
+    // IMPGPU_JPEG_PROGRESSIVE, so a progressive upload (which the workers pass on whole) is answered instead of NOT_TAKEN;
+    // none (the default) keeps impgpu_batch_decode_jpeg_prepared.
+    int jpeg_accept = 0;
     bool supervise = false;
     std::string ready_file;
 };
@@ -372,7 +376,14 @@ struct Worker {
         if (!jpegs.empty()) {
             imgs.assign(jpegs.size(), nullptr);
             codes.assign(jpegs.size(), IMP_OK);
-            decoded(jpegs, impgpu_batch_decode_jpeg_prepared(pre.data(), (int)jpegs.size(), imgs.data(), codes.data()));
+            if (!O.jpeg_accept) decoded(jpegs, impgpu_batch_decode_jpeg_prepared(pre.data(), (int)jpegs.size(), imgs.data(), codes.data()));
+            else {
+                // (a lane's batch is at most --batch requests; the two-halves call takes 256 files)
+                impgpu_jpeg_batch* jb = nullptr;
+                int rc = jpegs.size() <= 256 ? impgpu_batch_decode_jpeg_prepared_begin_ex(pre.data(), (int)jpegs.size(), O.jpeg_accept, &jb) : IMP_ERROR_INVALID_ARGS;
+                if (rc == IMP_OK) rc = impgpu_batch_decode_jpeg_finish(&jb, imgs.data(), codes.data());
+                decoded(jpegs, rc);
+            }
         }
         // (after the JPEG call: both are on the lane's stream, and the PNG call's inflates could overlap the JPEG kernels if
         // issued before it -- not done, DESIGN.md section 8 says why)
@@ -670,8 +681,14 @@ int main(int argc, char** argv) {
             else if (v == "none") o.png_accept = 0;
             else { std::fprintf(stderr, "impgpu_broker: --png-accept takes all or none\n"); return 2; }
         }
+        else if (a == "--jpeg-accept") {
+            const std::string v = val("--jpeg-accept");
+            if (v == "progressive") o.jpeg_accept = IMPGPU_JPEG_PROGRESSIVE;
+            else if (v == "none") o.jpeg_accept = 0;
+            else { std::fprintf(stderr, "impgpu_broker: --jpeg-accept takes progressive or none\n"); return 2; }
+        }
         else if (a == "--supervise") o.supervise = true;
-        else { std::fprintf(stderr, "usage: impgpu_broker [--name /impgpu-broker-0] [--device 0] [--slots 64] [--slot-mb 32] [--register-mb 8] [--threads 2] [--batch 64] [--gather-us 0] [--png-accept none|all] [--supervise] [--ready-file PATH]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: impgpu_broker [--name /impgpu-broker-0] [--device 0] [--slots 64] [--slot-mb 32] [--register-mb 8] [--threads 2] [--batch 64] [--gather-us 0] [--png-accept none|all] [--jpeg-accept none|progressive] [--supervise] [--ready-file PATH]\n"); return 2; }
     }
     if (o.slots < 1 || o.slots > IMPB_MAX_SLOTS || o.slot_mb < 1 || o.slot_mb > 4096 || o.threads < 1 || o.threads > 32 || o.batch < 1 || o.batch > 256 ||
         o.name.empty() || o.name[0] != '/') {

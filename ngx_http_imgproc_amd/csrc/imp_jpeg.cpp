@@ -10,7 +10,7 @@
 #include <cstdio>
 #include <cstring>
 #include <algorithm>
-#include "imp_jpeg_core.h"
+#include "imp_jpeg_prog.h"
 
 namespace imp {
 
@@ -88,18 +88,127 @@ int take_dqt(const Segment& s, JpegHeader* H) {
 
 }  // namespace
 
-int jpeg_parse(const uint8_t* blob, size_t size, JpegHeader* H) {
+int jpeg_parse(const uint8_t* blob, size_t size, JpegHeader* H) { return jpeg_parse_ex(blob, size, H, nullptr); }
+
+namespace {
+// A progressive file's scan header: its place in the progression (T.81 G.1.1.1.1) and its level.  `al` / `lvl`: per
+// component and coefficient, the point transform it has been sent down to (-1: not sent) and the level of the last scan
+// that touched it.
+int take_prog_scan(const Segment& s, const JpegHeader& H, JpegProg* prog, int8_t al[3][64], int8_t lvl[3][64]) {
+    auto refuse = []() { return IMP_ERROR_UNSUPPORTED; };
+    if ((int)prog->scans.size() >= JPEG_PROG_MAX_SCANS) return refuse();
+    const int ns = s.u8(0);
+    if (s.n != size_t(4 + 2 * ns)) return IMP_ERROR_DECODE_FAILED;
+    if (ns < 1 || ns > H.ncomp) return refuse();
+    JpegProgScan sc;
+    sc.ncomp = ns;
+    int prev = -1;
+    for (int i = 0; i < ns; i++) {
+        int ci = -1;
+        for (int k = 0; k < H.ncomp; k++) if (H.comp[k].id == s.u8(1 + 2 * i)) ci = k;
+        if (ci <= prev) return refuse();                             // not a component of the frame, or out of the frame's order
+        prev = ci;
+        sc.comp[i] = ci;
+        sc.td[i] = s.u8(2 + 2 * i) >> 4;
+        sc.ta[i] = s.u8(2 + 2 * i) & 15;
+        if (sc.td[i] > 3 || sc.ta[i] > 3) return IMP_ERROR_DECODE_FAILED;
+    }
+    sc.ss = s.u8(1 + 2 * ns); sc.se = s.u8(2 + 2 * ns); sc.ah = s.u8(3 + 2 * ns) >> 4; sc.al = s.u8(3 + 2 * ns) & 15;
+    if (sc.ss > sc.se || sc.se > 63 || sc.ah > 13 || sc.al > 13) return refuse();
+    if (sc.ss == 0 ? sc.se != 0 : ns != 1) return refuse();          // a DC scan holds DC terms only; an AC scan one component
+    if (sc.ah && sc.al != sc.ah - 1) return refuse();
+    int level = 0;
+    for (int i = 0; i < ns; i++) {
+        const int ci = sc.comp[i];
+        if (sc.ss > 0 && al[ci][0] < 0) return refuse();             // AC before the component's DC
+        for (int k = sc.ss; k <= sc.se; k++) {
+            if (sc.ah == 0 ? al[ci][k] >= 0 : al[ci][k] != sc.ah) return refuse();   // sent twice / a refinement that does not follow its predecessor
+            if (lvl[ci][k] + 1 > level) level = lvl[ci][k] + 1;
+        }
+    }
+    for (int i = 0; i < ns; i++)
+        for (int k = sc.ss; k <= sc.se; k++) { al[sc.comp[i]][k] = (int8_t)sc.al; lvl[sc.comp[i]][k] = (int8_t)level; }
+    sc.level = level;
+    sc.kind = sc.ss == 0 ? (sc.ah ? JPEG_PROG_DC_REFINE : JPEG_PROG_DC_FIRST) : (sc.ah ? JPEG_PROG_AC_REFINE : JPEG_PROG_AC_FIRST);
+    // the tables in force now (a DC refinement reads none)
+    for (int i = 0; i < ns && sc.kind != JPEG_PROG_DC_REFINE; i++) {
+        const bool is_dc = sc.ss == 0;
+        const JpegHuffSpec& t = is_dc ? H.dc[sc.td[i]] : H.ac[sc.ta[i]];
+        if (!t.present) return IMP_ERROR_DECODE_FAILED;
+        size_t k = 0;
+        for (; k < prog->tables.size(); k++)
+            if ((prog->table_is_dc[k] != 0) == is_dc && prog->tables[k].nvals == t.nvals && !std::memcmp(prog->tables[k].bits, t.bits, sizeof t.bits) &&
+                !std::memcmp(prog->tables[k].vals, t.vals, (size_t)t.nvals)) break;
+        if (k == prog->tables.size()) { prog->tables.push_back(t); prog->table_is_dc.push_back(is_dc ? 1 : 0); }
+        sc.tab[i] = (int)k;
+    }
+    sc.restart_interval = H.restart_interval;
+    if (ns > 1) sc.nunits = (uint32_t)H.mcux * (uint32_t)H.mcuy;
+    else {
+        const JpegComp& c = H.comp[sc.comp[0]];
+        sc.nunits = (uint32_t)((c.dsw + 7) / 8) * (uint32_t)((c.dsh + 7) / 8);
+    }
+    sc.nsegs = sc.restart_interval ? (sc.nunits + (uint32_t)sc.restart_interval - 1) / (uint32_t)sc.restart_interval : 1u;
+    if (level + 1 > prog->nlevels) prog->nlevels = level + 1;
+    prog->scans.push_back(sc);
+    return IMP_OK;
+}
+}  // namespace
+
+int jpeg_parse_ex(const uint8_t* blob, size_t size, JpegHeader* H, JpegProg* prog) {
     H->why = JPEG_WHY_NONE;
+    if (prog) *prog = JpegProg();
     if (!blob || size < 4 || blob[0] != 0xFF || blob[1] != 0xD8) { H->why = JPEG_WHY_OTHER; return IMP_ERROR_UNSUPPORTED; }
     size_t at = 2;
-    bool have_frame = false, jfif = false, adobe = false;
+    bool have_frame = false, jfif = false, adobe = false, progressive = false;
     int adobe_transform = 1;
+    int8_t prog_al[3][64], prog_lvl[3][64];
+    std::memset(prog_al, -1, sizeof prog_al);
+    std::memset(prog_lvl, -1, sizeof prog_lvl);
+    // what the first SOS settles: which colour space three components mean (libjpeg's default_decompress_parms), the geometry
+    auto frame_ready = [&](bool sequential) -> int {
+        H->ycc = true;
+        if (H->ncomp == 3 && !jfif) {
+            if (adobe) H->ycc = adobe_transform != 0;
+            else if (H->comp[0].id == 'R' && H->comp[1].id == 'G' && H->comp[2].id == 'B') H->ycc = false;
+        }
+        if (H->ncomp == 1) {
+            H->comp[0].h = H->comp[0].v = 1;                          // a one-component scan is never interleaved
+        } else {
+            if (H->comp[1].h != 1 || H->comp[1].v != 1 || H->comp[2].h != 1 || H->comp[2].v != 1) { H->why = JPEG_WHY_SAMPLING; return IMP_ERROR_UNSUPPORTED; }
+            if (H->comp[0].h > 2 || H->comp[0].v > 2) { H->why = JPEG_WHY_SAMPLING; return IMP_ERROR_UNSUPPORTED; }
+        }
+        H->hs = H->comp[0].h;
+        H->vs = H->comp[0].v;
+        H->mcux = (H->width + 8 * H->hs - 1) / (8 * H->hs);
+        H->mcuy = (H->height + 8 * H->vs - 1) / (8 * H->vs);
+        H->bpm = 0;
+        for (int i = 0; i < H->ncomp; i++) {
+            JpegComp& c = H->comp[i];
+            c.bw = H->mcux * c.h;
+            c.bh = H->mcuy * c.v;
+            c.dsw = (H->width * c.h + H->hs - 1) / H->hs;
+            c.dsh = (H->height * c.v + H->vs - 1) / H->vs;
+            H->bpm += c.h * c.v;
+            if (!H->qt_present[c.tq]) return IMP_ERROR_DECODE_FAILED;
+            if (sequential && (!H->dc[c.td].present || !H->ac[c.ta].present)) return IMP_ERROR_DECODE_FAILED;
+        }
+        return IMP_OK;
+    };
     for (;;) {
         if (at + 2 > size || blob[at] != 0xFF) return IMP_ERROR_DECODE_FAILED;
         while (at < size && blob[at] == 0xFF) at++;                   // any number of fill bytes may precede a marker
         if (at >= size) return IMP_ERROR_DECODE_FAILED;
         const int marker = blob[at++];
         if (marker == 0xD8 || marker == 0x01 || (marker >= 0xD0 && marker <= 0xD7)) continue;   // no payload
+        if (marker == 0xD9 && progressive && !prog->scans.empty()) {
+            // complete only when every coefficient of every component has been sent down to Al = 0: libjpeg would smooth, or
+            // show a coarse image, where one has not
+            for (int c = 0; c < H->ncomp; c++)
+                for (int k = 0; k < 64; k++)
+                    if (prog_al[c][k] != 0) { H->why = JPEG_WHY_PROGRESSIVE; return IMP_ERROR_UNSUPPORTED; }
+            return IMP_OK;
+        }
         if (marker == 0xD9) return IMP_ERROR_DECODE_FAILED;           // the file ends before a scan
         if (at + 2 > size) return IMP_ERROR_DECODE_FAILED;
         const size_t len = (size_t(blob[at]) << 8) | blob[at + 1];
@@ -112,11 +221,23 @@ int jpeg_parse(const uint8_t* blob, size_t size, JpegHeader* H) {
             rc = take_sof(s, H);
             have_frame = true;
             break;
-        case 0xC2: case 0xC3: case 0xC5: case 0xC6: case 0xC7: case 0xC9: case 0xCA: case 0xCB: case 0xCD: case 0xCE: case 0xCF:
+        case 0xC2:
+            if (prog) {                                               // progressive, Huffman: taken when the caller asks
+                if (have_frame) return IMP_ERROR_DECODE_FAILED;
+                rc = take_sof(s, H);
+                have_frame = progressive = true;
+                break;
+            }
+            [[fallthrough]];
+        case 0xC3: case 0xC5: case 0xC6: case 0xC7: case 0xC9: case 0xCA: case 0xCB: case 0xCD: case 0xCE: case 0xCF:
             H->why = marker == 0xC2 ? JPEG_WHY_PROGRESSIVE : JPEG_WHY_PROCESS;
             return IMP_ERROR_UNSUPPORTED;                             // progressive, lossless, hierarchical, arithmetic
         case 0xC4: rc = take_dht(s, H); break;
-        case 0xDB: rc = take_dqt(s, H); break;
+        case 0xDB:
+            // (libjpeg keeps the table a component had at its first scan: a table sent later is left to it)
+            if (progressive && !prog->scans.empty()) { H->why = JPEG_WHY_PROGRESSIVE; return IMP_ERROR_UNSUPPORTED; }
+            rc = take_dqt(s, H);
+            break;
         case 0xDD:
             if (s.n != 2) return IMP_ERROR_DECODE_FAILED;
             H->restart_interval = s.u16(0);
@@ -127,6 +248,32 @@ int jpeg_parse(const uint8_t* blob, size_t size, JpegHeader* H) {
             break;
         case 0xDA: {
             if (!have_frame || s.n < 1) return IMP_ERROR_DECODE_FAILED;
+            if (progressive) {
+                if (prog->scans.empty()) if (int rg = frame_ready(false)) return rg;
+                rc = take_prog_scan(s, *H, prog, prog_al, prog_lvl);
+                if (rc == IMP_ERROR_UNSUPPORTED) H->why = JPEG_WHY_PROGRESSIVE;
+                if (rc) return rc;
+                // over the entropy-coded bytes to the marker that ends them
+                JpegProgScan& sc = prog->scans.back();
+                size_t q = at + len;
+                sc.data_begin = q;
+                size_t rst = 0;
+                for (;;) {
+                    const uint8_t* ff = q < size ? (const uint8_t*)std::memchr(blob + q, 0xFF, size - q) : nullptr;
+                    if (!ff || (size_t)(ff - blob) + 1 >= size) return IMP_ERROR_DECODE_FAILED;      // no EOI
+                    q = (size_t)(ff - blob);
+                    const int code = blob[q + 1];
+                    if (code == 0x00) { q += 2; continue; }
+                    if (code == 0xFF) { q += 1; continue; }           // a fill byte
+                    if (code >= 0xD0 && code <= 0xD7) { rst++; q += 2; continue; }
+                    break;
+                }
+                sc.data_end = q;
+                prog->data_bytes += sc.data_end - sc.data_begin;
+                prog->max_items += rst + 1;
+                at = q;
+                continue;
+            }
             const int ns = s.u8(0);
             if (s.n != size_t(4 + 2 * ns)) return IMP_ERROR_DECODE_FAILED;
             if (ns != H->ncomp) { H->why = JPEG_WHY_SCANS; return IMP_ERROR_UNSUPPORTED; }         // one scan per component
@@ -138,34 +285,7 @@ int jpeg_parse(const uint8_t* blob, size_t size, JpegHeader* H) {
             }
             if (s.u8(1 + 2 * ns) != 0 || s.u8(2 + 2 * ns) != 63 || s.u8(3 + 2 * ns) != 0) { H->why = JPEG_WHY_SCANS; return IMP_ERROR_UNSUPPORTED; }
             H->scan_begin = at + len;
-            // which colour space three components mean (libjpeg's default_decompress_parms)
-            H->ycc = true;
-            if (H->ncomp == 3 && !jfif) {
-                if (adobe) H->ycc = adobe_transform != 0;
-                else if (H->comp[0].id == 'R' && H->comp[1].id == 'G' && H->comp[2].id == 'B') H->ycc = false;
-            }
-            // geometry
-            if (H->ncomp == 1) {
-                H->comp[0].h = H->comp[0].v = 1;                      // a one-component scan is never interleaved
-            } else {
-                if (H->comp[1].h != 1 || H->comp[1].v != 1 || H->comp[2].h != 1 || H->comp[2].v != 1) { H->why = JPEG_WHY_SAMPLING; return IMP_ERROR_UNSUPPORTED; }
-                if (H->comp[0].h > 2 || H->comp[0].v > 2) { H->why = JPEG_WHY_SAMPLING; return IMP_ERROR_UNSUPPORTED; }
-            }
-            H->hs = H->comp[0].h;
-            H->vs = H->comp[0].v;
-            H->mcux = (H->width + 8 * H->hs - 1) / (8 * H->hs);
-            H->mcuy = (H->height + 8 * H->vs - 1) / (8 * H->vs);
-            H->bpm = 0;
-            for (int i = 0; i < H->ncomp; i++) {
-                JpegComp& c = H->comp[i];
-                c.bw = H->mcux * c.h;
-                c.bh = H->mcuy * c.v;
-                c.dsw = (H->width * c.h + H->hs - 1) / H->hs;
-                c.dsh = (H->height * c.v + H->vs - 1) / H->vs;
-                H->bpm += c.h * c.v;
-                if (!H->qt_present[c.tq] || !H->dc[c.td].present || !H->ac[c.ta].present) return IMP_ERROR_DECODE_FAILED;
-            }
-            return IMP_OK;
+            return frame_ready(true);
         }
         default: break;                                               // comments, other application segments
         }

@@ -12,7 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include "imp_host_pool.h"
-#include "imp_jpeg_core.h"
+#include "imp_jpeg_prog.h"
 
 using namespace imp;
 
@@ -26,11 +26,13 @@ namespace {
 // rounds: near 100 KB), so a launch smaller than that keeps its Huffman decoding on the thread that is about to sleep in the
 // wait anyway (dequantisation, IDCT, upsampling and colour stay on the device either way), and everything larger -- every
 // batch -- is the device's.  IMPGPU_JPEG_HUFF = device | host forces one (read per call: a getenv is nothing next to a decode).
-bool entropy_on_device(size_t launch_bytes) {
+// (`progressive`: the launch holds progressive files, taken because the caller asked for them on the device -- their scans
+// are the device's whatever the launch weighs, so that a call's launches do not depend on how many files it holds)
+bool entropy_on_device(size_t launch_bytes, bool progressive = false) {
     const char* s = std::getenv("IMPGPU_JPEG_HUFF");
     if (s && !std::strcmp(s, "host")) return false;
     if (s && !std::strcmp(s, "device")) return true;
-    return launch_bytes >= (size_t(40) << 10);
+    return progressive || launch_bytes >= (size_t(40) << 10);
 }
 
 // impgpu_jpeg_profile(1): every decode call leaves its stages' durations with the calling thread (impgpu_jpeg_stage_times) --
@@ -39,7 +41,8 @@ std::atomic<int> g_profile{0};
 // process-wide: files whose entropy stage ran on the device, of those refused by its verdict, of those with a chain wait
 // that ran out (JPEG_ST_CHAIN_TIMEOUT: the file is then decoded by the caller's fallback -- a box that does this silently
 // looks healthy and is not), files kept on the calling thread because their blocks are too long
-std::atomic<unsigned long long> g_count[4 + JPEG_WHY_COUNT + 1];    // [4 + why]: files refused at their header, by reason; [4 + JPEG_WHY_COUNT]: damaged headers
+constexpr int COUNT_PROG = 4 + JPEG_WHY_COUNT + 1, COUNT_PROG_LAUNCHES = COUNT_PROG + 1, COUNT_SLOTS = COUNT_PROG + 2;   // (impgpu_jpeg_counters [13], [14])
+std::atomic<unsigned long long> g_count[COUNT_SLOTS];    // [4 + why]: files refused at their header, by reason; [4 + JPEG_WHY_COUNT]: damaged headers
 thread_local double t_stage[16];
 
 // IMPGPU_JPEG_TRACE=1: one line per call on stderr with the host's share of it, in microseconds
@@ -78,6 +81,13 @@ struct Prep {                                       // one file on its way to th
     bool given = false;                             // the frame has been handed to the caller ahead of its verdict (impgpu_batch_decode_jpeg_pending)
     bool direct = false;                            // ... into registered memory: its words go to the device from there
     size_t direct_off = 0;                          // bytes behind the staged part of the words' block
+    // a progressive file (imp_jpeg_prog.h): its scans, its items as jpeg_prog_prepare cut them, its tables and scan records in the side blob
+    JpegProg prog;
+    bool is_prog = false;
+    std::vector<JpegProgItem> items;
+    std::vector<uint32_t> level_first;
+    std::vector<JpegHuffDev> ptabs;
+    size_t side_ptabs = 0, side_pscans = 0;
 };
 
 // A file whose blocks average more bits than this keeps its Huffman stage on the calling thread even inside a launch that is
@@ -104,7 +114,8 @@ struct Group {
     uint32_t* mailbox = nullptr;
     int slot = -1;
     size_t live = 0, ctl_total = 0;
-    hipEvent_t ev[8] = {};
+    hipEvent_t ev[10] = {};                         // [8], [9]: around the progressive files' launches
+    unsigned prog_files = 0, prog_launches = 0;
     Stopwatch sw;
     const void* owner = nullptr;                    // the thread that began the group (its slot, its lane): only it may finish it
     const impgpu_jpeg_prepared* prep = nullptr;     // per file, or nullptr: every blob is a whole file
@@ -129,7 +140,7 @@ std::vector<uint8_t> restuffed(const impgpu_jpeg_prepared& f) {
 }
 
 void group_release(Group& G) {
-    for (int i = 0; i < 8; i++) if (G.ev[i]) { (void)hipEventDestroy(G.ev[i]); G.ev[i] = nullptr; }
+    for (int i = 0; i < 10; i++) if (G.ev[i]) { (void)hipEventDestroy(G.ev[i]); G.ev[i] = nullptr; }
     void* blocks[5] = {G.d_words, G.d_coef, G.one_block ? nullptr : G.d_side, G.one_block ? nullptr : G.d_ctl, G.d_work};
     for (void* b : blocks)
         if (b) { if (G.stream && !on_lane_stream(G.stream)) dev_free_on(b, G.stream); else dev_free(b); }
@@ -142,7 +153,7 @@ void group_release(Group& G) {
 // the entropy and pixel kernels, the verdicts' copy.  Does NOT wait.  A non-zero return means nothing is in flight and
 // nothing is held (codes[] of the caller are then filled by the caller from G.P where they are set, else with the return).
 int group_begin(Group& G, const unsigned char* const* blobs, const size_t* sizes, int count, int force_host, bool side = false,
-                const impgpu_jpeg_prepared* prep = nullptr) {
+                const impgpu_jpeg_prepared* prep = nullptr, int accept = 0) {
     Stopwatch& sw = G.sw;
     hipStream_t s = side ? lane_side_stream() : nullptr;
     if (!s) s = env_stream();
@@ -163,14 +174,17 @@ int group_begin(Group& G, const unsigned char* const* blobs, const size_t* sizes
         Prep& p = P[(size_t)i];
         if (!blobs[i]) { p.code = IMP_ERROR_INVALID_ARGS; continue; }
         if (prep && prep[i].scan) p.pre = &prep[i];
-        p.code = jpeg_parse(blobs[i], sizes[i], &p.H);
+        // (a progressive file comes whole: a scan the caller unstuffed is a sequential file's)
+        p.code = jpeg_parse_ex(blobs[i], sizes[i], &p.H, (accept & IMPGPU_JPEG_PROGRESSIVE) && !p.pre ? &p.prog : nullptr);
+        p.is_prog = !p.code && !p.prog.scans.empty();
+        if (p.is_prog) for (int c = 0; c < p.H.ncomp; c++) p.H.comp[c].td = p.H.comp[c].ta = 0;      // (its tables belong to its scans)
         // (a prepared file: its head ends where its scan began, and nothing cuts the scan into intervals)
         if (!p.code && p.pre && (p.H.scan_begin != sizes[i] || p.H.restart_interval || !p.pre->scan_size)) {
             set_error_text("prepared JPEG: the head does not end at its scan, or the file has a restart interval");
             p.code = IMP_ERROR_INVALID_ARGS;
             continue;
         }
-        if (!p.code) p.scan_len = p.pre ? p.pre->scan_size : sizes[i] - p.H.scan_begin;
+        if (!p.code) p.scan_len = p.is_prog ? p.prog.data_bytes : p.pre ? p.pre->scan_size : sizes[i] - p.H.scan_begin;
         if (!p.code && !frame_fits(p.H.width, p.H.height, p.H.ncomp)) { p.code = IMP_ERROR_UNSUPPORTED; p.H.why = JPEG_WHY_OTHER; }
         if (p.code == IMP_ERROR_UNSUPPORTED) g_count[4 + (p.H.why > 0 && p.H.why < JPEG_WHY_COUNT ? p.H.why : JPEG_WHY_OTHER)].fetch_add(1, std::memory_order_relaxed);
         else if (p.code == IMP_ERROR_DECODE_FAILED) g_count[4 + JPEG_WHY_COUNT].fetch_add(1, std::memory_order_relaxed);
@@ -182,6 +196,15 @@ int group_begin(Group& G, const unsigned char* const* blobs, const size_t* sizes
         // code and an end-of-block code -- a few hundred bytes that announce 30000 x 30000 pixels, or a restart interval of one
         // MCU on a frame of 2^30, would otherwise have pinned and device memory allocated by the gigabyte before the decode fails.
         const size_t scan_bytes = p.scan_len;
+        if (p.is_prog) {
+            // (a first DC scan spends a bit or more on every block of every component: nothing smaller holds the frame it announces)
+            if ((size_t)p.F.total_slots / 64 > 8 * scan_bytes + 64) { p.code = IMP_ERROR_DECODE_FAILED; continue; }
+            p.words_cap = align_up(jpeg_prog_capacity(p.prog), JPEG_CHUNK_BYTES_MAX);
+            p.words_off = words_total; words_total += p.words_cap;
+            p.coef_off = coef_total;
+            coef_total += align_up((size_t)p.F.total_slots * sizeof(int16_t), 256);
+            continue;
+        }
         if (p.nsegs > scan_bytes / 3 + 1 || (size_t)p.F.total_slots / 64 > 4 * scan_bytes + 64) { p.code = IMP_ERROR_DECODE_FAILED; continue; }
         p.words_cap = align_up(jpeg_scan_capacity(scan_bytes, p.nsegs), JPEG_CHUNK_BYTES_MAX);
         p.direct = p.pre && p.pre->registered && !force_host;
@@ -190,10 +213,14 @@ int group_begin(Group& G, const unsigned char* const* blobs, const size_t* sizes
         p.coef_off = coef_total;
         coef_total += align_up((size_t)p.F.total_slots * sizeof(int16_t), 256);
     }
-    size_t launch_bytes = 0;
+    size_t launch_bytes = 0, prog_bytes = 0;                        // (launch_bytes: the sequential files' -- what their chunking goes by)
+    unsigned nprog = 0;
     for (int i = 0; i < count; i++)
-        if (!P[(size_t)i].code) launch_bytes += P[(size_t)i].scan_len;
-    const bool on_device = G.on_device = !force_host && entropy_on_device(launch_bytes);
+        if (!P[(size_t)i].code) {
+            if (P[(size_t)i].is_prog) { prog_bytes += P[(size_t)i].scan_len; nprog++; }
+            else launch_bytes += P[(size_t)i].scan_len;
+        }
+    const bool on_device = G.on_device = !force_host && entropy_on_device(launch_bytes, nprog != 0);
     if (!on_device && direct_total) {                               // (a launch of under 40 KB: its files are staged after all)
         for (Prep& p : P) if (!p.code && p.direct) { p.direct = false; p.words_off = words_total; words_total += p.words_cap; }
         direct_total = 0;
@@ -201,7 +228,7 @@ int group_begin(Group& G, const unsigned char* const* blobs, const size_t* sizes
     if (on_device && !std::getenv("IMPGPU_JPEG_HUFF"))
         for (int i = 0; i < count; i++) {
             Prep& p = P[(size_t)i];
-            if (!p.code && p.scan_len * 8 > DENSE_BITS_PER_BLOCK * ((size_t)p.F.total_slots / 64)) {
+            if (!p.code && !p.is_prog && p.scan_len * 8 > DENSE_BITS_PER_BLOCK * ((size_t)p.F.total_slots / 64)) {
                 p.code = CODE_DEFERRED;
                 g_count[3].fetch_add(1, std::memory_order_relaxed);
             }
@@ -224,6 +251,12 @@ int group_begin(Group& G, const unsigned char* const* blobs, const size_t* sizes
         const bool busy = g_groups_in_flight.load(std::memory_order_relaxed) > 1;    // (this group is counted already)
         auto prepare = [&](int i) {
             Prep& p = P[(size_t)i];
+            if (p.is_prog) {
+                p.ptabs.resize(p.prog.tables.size());
+                for (size_t k = 0; k < p.ptabs.size() && !p.code; k++) p.code = jpeg_build_table(p.prog.tables[k], p.prog.table_is_dc[k] != 0, &p.ptabs[k]);
+                if (!p.code) p.code = jpeg_prog_prepare(blobs[i], sizes[i], p.H, p.prog, (uint8_t*)host + p.words_off, p.words_cap, &p.items, &p.level_first);
+                return;
+            }
             p.scan.chunk_bytes = jpeg_chunk_bytes_for(p.scan_len, launch_bytes, busy);
             if (!p.pre) { p.code = jpeg_prepare_scan(blobs[i], sizes[i], p.H, (uint8_t*)host + p.words_off, p.words_cap, &p.scan); return; }
             // the caller's unstuffed bytes are one interval: what jpeg_prepare_scan would have left -- the bytes, 1-bits up to
@@ -238,13 +271,13 @@ int group_begin(Group& G, const unsigned char* const* blobs, const size_t* sizes
             std::memcpy(out, p.pre->scan, n);
             std::memset(out + n, 0xFF, padded - n + JPEG_CHUNK_BYTES);
         };
-        host_parallel(todo, launch_bytes, prepare);
+        host_parallel(todo, launch_bytes + prog_bytes, prepare);
     }
     for (int i = 0; i < count; i++) {
         Prep& p = P[(size_t)i];
         if (p.code) continue;
         if (on_device) {
-            if (!p.code) {
+            if (!p.code && !p.is_prog) {
                 p.F.nchunks = (unsigned)p.scan.nchunks;
                 p.F.nsegs = (unsigned)p.scan.seg_first_chunk.size();
                 p.F.chunk_bits = (unsigned)p.scan.chunk_bytes * 8;
@@ -260,7 +293,8 @@ int group_begin(Group& G, const unsigned char* const* blobs, const size_t* sizes
         } else {
             int16_t* planes = (int16_t*)((uint8_t*)host + p.coef_off);
             std::memset(planes, 0, (size_t)p.F.total_slots * sizeof(int16_t));
-            if (p.pre) {
+            if (p.is_prog) p.code = jpeg_prog_reference(blobs[i], sizes[i], p.H, p.prog, p.F, planes);     // (IMPGPU_JPEG_HUFF=host: the A/B path)
+            else if (p.pre) {
                 const std::vector<uint8_t> file = restuffed(*p.pre);
                 p.code = jpeg_host_entropy(file.data(), file.size(), p.H, planes, p.F);
             } else p.code = jpeg_host_entropy(blobs[i], sizes[i], p.H, planes, p.F);
@@ -283,6 +317,8 @@ int group_begin(Group& G, const unsigned char* const* blobs, const size_t* sizes
         size_t side = 0, ctl_words = 4;                             // control: [0] ticket, then the jobs' headers, then their records
         size_t total_blocks = 0, sync_blocks = 0, work = 0;
         size_t tiles[5] = {0, 0, 0, 0, 0};                          // per sampling class
+        size_t prog_items = 0, prog_on_device = 0;
+        int prog_levels = 0;
         auto klass = [](const JpegFrame& F) { return F.ncomp == 1 ? 0 : F.hs == 1 ? (F.vs == 1 ? 1 : 3) : (F.vs == 1 ? 2 : 4); };
         for (Prep& p : P) {
             if (p.code) continue;
@@ -292,7 +328,15 @@ int group_begin(Group& G, const unsigned char* const* blobs, const size_t* sizes
         for (Prep& p : P) {
             if (p.code) continue;
             njobs++;
-            if (on_device) {
+            if (on_device && p.is_prog) {
+                p.side_ptabs = side;
+                side += align_up((p.prog.tables.size() + 1) * sizeof(JpegHuffDev), 64);
+                p.side_pscans = side;
+                side += align_up(p.prog.scans.size() * sizeof(JpegProgScanDev), 64);
+                prog_items += p.items.size();
+                prog_levels = std::max(prog_levels, p.prog.nlevels);
+                prog_on_device++;
+            } else if (on_device) {
                 p.side_tables = side;
                 side += align_up(4 * sizeof(JpegHuffDev), 64);
                 p.side_meta = side;
@@ -320,6 +364,10 @@ int group_begin(Group& G, const unsigned char* const* blobs, const size_t* sizes
         side += align_up(total_blocks * sizeof(JpegMapEntry), 64);
         const size_t side_sync = side;
         side += align_up(sync_blocks * sizeof(JpegMapEntry), 64);
+        const size_t side_pfiles = side;
+        side += align_up(prog_on_device * sizeof(JpegProgFileDev), 64);
+        const size_t side_pitems = side;
+        side += align_up(prog_items * sizeof(JpegProgItem), 64);
         size_t side_tiles[5];
         for (int k = 0; k < 5; k++) { side_tiles[k] = side; side += align_up(tiles[k] * sizeof(JpegMapEntry), 64); }
         // The scan words, the side blob and the (zeroed) control area cross the link as ONE copy when the pinned buffer the
@@ -354,12 +402,32 @@ int group_begin(Group& G, const unsigned char* const* blobs, const size_t* sizes
         for (int k = 0; k < 5; k++) tmap[k] = (JpegMapEntry*)(blob.data() + side_tiles[k]);
         size_t j = 0, nb = 0, ns = 0, nt[5] = {0, 0, 0, 0, 0};
         std::vector<uint32_t> meta;
+        JpegProgFileDev* pfiles = (JpegProgFileDev*)(blob.data() + side_pfiles);
+        std::vector<JpegProgItem> pitems;                           // every file's, by (level, kind): a launch per level, a decoder per wave
+        pitems.reserve(prog_items);
+        std::vector<const JpegProg*> prog_of;                       // per progressive file of the launch
+        size_t npf = 0;
         for (Prep& p : P) {
             if (p.code) continue;
             JpegJob& J = jobs[j];
             std::memset(&J, 0, sizeof J);
             J.F = p.F;
-            if (on_device) {
+            if (on_device && p.is_prog) {
+                if (!p.ptabs.empty()) std::memcpy(blob.data() + p.side_ptabs, p.ptabs.data(), p.ptabs.size() * sizeof(JpegHuffDev));
+                jpeg_prog_scans_dev(p.prog, (JpegProgScanDev*)(blob.data() + p.side_pscans));
+                J.header = (uint32_t*)d_ctl + p.ctl_header;
+                JpegProgFileDev& D = pfiles[npf];
+                jpeg_prog_file_dev(p.H, p.F, &D);
+                D.coef = (int16_t*)((uint8_t*)d_coef + p.coef_off);
+                D.words = (const uint32_t*)((uint8_t*)d_words + p.words_off);
+                D.tables = (const JpegHuffDev*)((uint8_t*)d_side + p.side_ptabs);
+                D.scans = (const JpegProgScanDev*)((uint8_t*)d_side + p.side_pscans);
+                D.header = J.header;
+                D.verdict = verdict_dev ? verdict_dev + 4 * j : nullptr;
+                for (JpegProgItem it : p.items) { it.file = (uint32_t)npf; pitems.push_back(it); }
+                prog_of.push_back(&p.prog);
+                npf++;
+            } else if (on_device) {
                 rc = jpeg_build_tables(p.H, p.dc_ids, p.ac_ids, (JpegHuffDev*)(blob.data() + p.side_tables));
                 if (rc) { p.code = rc; rc = IMP_OK; }               // (cannot happen after jpeg_parse; keeps the job inert)
                 jpeg_scan_meta(p.scan, &meta);
@@ -412,9 +480,19 @@ int group_begin(Group& G, const unsigned char* const* blobs, const size_t* sizes
             for (uint32_t tl = 0; tl < ntiles; tl++) tmap[k][nt[k]++] = JpegMapEntry{(uint32_t)j, tl};
             j++;
         }
+        std::vector<uint32_t> plevel_first((size_t)prog_levels + 1, 0u);
+        if (npf) {
+            // (each file's list is sorted already; the key is recomputed from the file's scans)
+            auto key = [&](const JpegProgItem& it) { const JpegProgScan& sc = prog_of[it.file]->scans[it.scan]; return sc.level * 4 + sc.kind; };
+            std::stable_sort(pitems.begin(), pitems.end(), [&](const JpegProgItem& a, const JpegProgItem& b) { return key(a) < key(b); });
+            for (const JpegProgItem& it : pitems) plevel_first[(size_t)prog_of[it.file]->scans[it.scan].level + 1]++;
+            for (int l = 0; l < prog_levels; l++) plevel_first[(size_t)l + 1] += plevel_first[(size_t)l];
+            if (!pitems.empty()) std::memcpy(blob.data() + side_pitems, pitems.data(), pitems.size() * sizeof(JpegProgItem));
+        }
+        G.prog_files = (unsigned)npf;
         sw.mark();                                                  // [2] tables + job table
         if (profile && on_device) {
-            for (int i = 0; i < 8; i++) if (hipEventCreate(&ev[i]) != hipSuccess) { ev[i] = nullptr; profile = false; }
+            for (int i = 0; i < 10; i++) if (hipEventCreate(&ev[i]) != hipSuccess) { ev[i] = nullptr; profile = false; }
             if (profile) (void)hipEventRecord(ev[0], s);
         }
         rc = stage_upload(token, on_device ? d_words : d_coef, one ? in_total : on_device ? words_total : coef_total);
@@ -444,6 +522,13 @@ int group_begin(Group& G, const unsigned char* const* blobs, const size_t* sizes
             rc = launch_jpeg_entropy((const JpegJob*)((uint8_t*)d_side + side_jobs), (const JpegMapEntry*)((uint8_t*)d_side + side_sync), (unsigned)sync_blocks,
                                      (const JpegMapEntry*)((uint8_t*)d_side + side_blocks), (unsigned)total_blocks, (uint32_t*)d_ctl, s, profile ? ev + 2 : nullptr, small);
             if (rc) goto fail;
+            // the progressive files: the planes zeroed, a launch per level of the deepest scan script, their verdict words
+            if (profile && npf) (void)hipEventRecord(ev[8], s);
+            rc = launch_jpeg_prog((const JpegProgFileDev*)((uint8_t*)d_side + side_pfiles), (unsigned)npf, (const JpegProgItem*)((uint8_t*)d_side + side_pitems),
+                                  plevel_first.data(), prog_levels, s, nullptr, &G.prog_launches);
+            if (rc) goto fail;
+            if (profile && npf) (void)hipEventRecord(ev[9], s);
+            g_count[COUNT_PROG_LAUNCHES].fetch_add(G.prog_launches, std::memory_order_relaxed);
             // the kernel's verdicts (did every interval decode to exactly its MCUs?) are read before a frame is handed on:
             // k_jpeg_dcfix has written them into the pinned words; copied only where the device cannot address those
             if (!verdict_dev) {
@@ -546,6 +631,7 @@ int group_finish(Group& G, impgpu_image** images, int* codes) {
             g_count[0].fetch_add(1, std::memory_order_relaxed);
             if (status) g_count[1].fetch_add(1, std::memory_order_relaxed);
             if (status & JPEG_ST_CHAIN_TIMEOUT) g_count[2].fetch_add(1, std::memory_order_relaxed);
+            if (p.is_prog && !status) g_count[COUNT_PROG].fetch_add(1, std::memory_order_relaxed);
             if (status) {
                 char text[96];
                 std::snprintf(text, sizeof text, "jpeg entropy stage refused the scan (status 0x%x)", status);
@@ -563,8 +649,15 @@ int group_finish(Group& G, impgpu_image** images, int* codes) {
             for (int i = 0; i < 7; i++) {
                 float ms = 0;
                 if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) t_stage[5 + i] = 1e3 * ms;
+                else (void)hipGetLastError();                       // (a group of progressive files alone records no event between the sequential kernels)
             }
         t_stage[12] = (double)live;
+        if (profile && on_device && G.prog_files) {
+            float ms = 0;
+            if (hipEventElapsedTime(&ms, ev[8], ev[9]) == hipSuccess) t_stage[13] = 1e3 * ms;
+        }
+        t_stage[14] = (double)G.prog_launches;
+        t_stage[15] = (double)G.prog_files;
     }
     if (sw.on && std::getenv("IMPGPU_JPEG_TRACE"))
         std::fprintf(stderr, "jpeg x%d (%zu live): headers %.0f %s %.0f jobs %.0f enqueue %.0f wait %.0f us\n", count, live, sw.marks[0],
@@ -615,14 +708,14 @@ int group_deferred(const unsigned char* const* blobs, const size_t* sizes, int c
 // unstuffing copy, job table: 2.3 of a 64-file call's 5.8 ms) while the device already works on the first: one calling thread
 // went 11 -> 15 k requests/s with that.  When other threads keep the device busy anyway (four or more groups in flight) the
 // group stays whole: two launches of half the size are the less efficient way to fill a device that is already full.
-int decode_group(const unsigned char* const* blobs, const size_t* sizes, int count, impgpu_image** images, int* codes) {
+int decode_group(const unsigned char* const* blobs, const size_t* sizes, int count, impgpu_image** images, int* codes, int accept = 0) {
     const bool whole = std::getenv("IMPGPU_JPEG_WHOLE") != nullptr;      // measurements of ONE launch per batch (tools/jpeg_prof_r04.sh, bench.py's stage profile); read per call
     // (the two halves take a mailbox slot each: with batches begun and not finished on this thread -- impgpu_batch_decode_jpeg_begin --
     // holding three of the four, the group stays whole instead of failing for want of a second slot)
     const int free_slots = GROUP_SLOTS - __builtin_popcount(t_slots_busy & ((1u << GROUP_SLOTS) - 1));
     const int first = !whole && count >= 32 && free_slots >= 2 && g_groups_in_flight.load(std::memory_order_relaxed) < 4 ? count / 2 : count;
     Group A, B;
-    int rc = group_begin(A, blobs, sizes, first, 0);
+    int rc = group_begin(A, blobs, sizes, first, 0, false, nullptr, accept);
     if (rc) {
         for (int i = 0; i < count; i++) { images[i] = nullptr; codes[i] = i < first && A.P.size() > (size_t)i && A.P[(size_t)i].code ? A.P[(size_t)i].code : rc; }
         return rc;
@@ -630,7 +723,7 @@ int decode_group(const unsigned char* const* blobs, const size_t* sizes, int cou
     int rcb = IMP_OK;
     // Both halves on the lane's stream (the second half on the lane's side stream was measured on one box, two repetitions: the
     // same at 1, 2 and 8 threads, 7 % slower at 4 -- so it is not used here; impgpu_batch_decode_jpeg_begin does use it).
-    if (first < count) rcb = group_begin(B, blobs + first, sizes + first, count - first, 0);
+    if (first < count) rcb = group_begin(B, blobs + first, sizes + first, count - first, 0, false, nullptr, accept);
     rc = group_finish(A, images, codes);
     if (first < count) {
         if (!rcb) rcb = group_finish(B, images + first, codes + first);
@@ -656,13 +749,17 @@ struct impgpu_jpeg_batch {
 extern "C" {
 
 int impgpu_batch_decode_jpeg(const unsigned char* const* blobs, const size_t* sizes, int count, impgpu_image** images, int* codes) {
+    return impgpu_batch_decode_jpeg_ex(blobs, sizes, count, 0, images, codes);
+}
+
+int impgpu_batch_decode_jpeg_ex(const unsigned char* const* blobs, const size_t* sizes, int count, int accept, impgpu_image** images, int* codes) {
     if (count < 0 || (count && (!blobs || !sizes || !images || !codes))) return IMP_ERROR_INVALID_ARGS;
     if (!env_ready()) { set_error_text("impgpu_env_start has not been called"); return IMP_ERROR_DEVICE; }
     TraceRange tr("IMP_STEP_DECODE");
     IMP_FAULT_POINT(IMP_STEP_DECODE);
     for (int at = 0; at < count; at += MAX_BATCH) {
         const int n = count - at < MAX_BATCH ? count - at : MAX_BATCH;
-        if (int rc = decode_group(blobs + at, sizes + at, n, images + at, codes + at)) {
+        if (int rc = decode_group(blobs + at, sizes + at, n, images + at, codes + at, accept)) {
             for (int i = 0; i < at; i++) impgpu_image_release(&images[i]);
             for (int i = at + n; i < count; i++) { images[i] = nullptr; codes[i] = rc; }
             return rc;
@@ -672,6 +769,10 @@ int impgpu_batch_decode_jpeg(const unsigned char* const* blobs, const size_t* si
 }
 
 int impgpu_batch_decode_jpeg_begin(const unsigned char* const* blobs, const size_t* sizes, int count, impgpu_jpeg_batch** batch) {
+    return impgpu_batch_decode_jpeg_begin_ex(blobs, sizes, count, 0, batch);
+}
+
+int impgpu_batch_decode_jpeg_begin_ex(const unsigned char* const* blobs, const size_t* sizes, int count, int accept, impgpu_jpeg_batch** batch) {
     if (!batch) return IMP_ERROR_INVALID_ARGS;
     *batch = nullptr;
     if (count <= 0 || count > MAX_BATCH || !blobs || !sizes) return IMP_ERROR_INVALID_ARGS;
@@ -680,7 +781,7 @@ int impgpu_batch_decode_jpeg_begin(const unsigned char* const* blobs, const size
     IMP_FAULT_POINT(IMP_STEP_DECODE);
     impgpu_jpeg_batch* b = new impgpu_jpeg_batch();
     // on the lane's side stream: what the thread enqueues before _finish overlaps it
-    const int rc = group_begin(b->G, blobs, sizes, count, 0, true);
+    const int rc = group_begin(b->G, blobs, sizes, count, 0, true, nullptr, accept);
     if (rc) { delete b; return rc; }
     *batch = b;
     return IMP_OK;
@@ -719,6 +820,10 @@ int impgpu_batch_decode_jpeg_pending(impgpu_jpeg_batch* batch, impgpu_image** im
 }
 
 int impgpu_batch_decode_jpeg_prepared_begin(const impgpu_jpeg_prepared* files, int count, impgpu_jpeg_batch** batch) {
+    return impgpu_batch_decode_jpeg_prepared_begin_ex(files, count, 0, batch);
+}
+
+int impgpu_batch_decode_jpeg_prepared_begin_ex(const impgpu_jpeg_prepared* files, int count, int accept, impgpu_jpeg_batch** batch) {
     if (!batch) return IMP_ERROR_INVALID_ARGS;
     *batch = nullptr;
     if (count <= 0 || count > MAX_BATCH || !files) return IMP_ERROR_INVALID_ARGS;
@@ -730,7 +835,7 @@ int impgpu_batch_decode_jpeg_prepared_begin(const impgpu_jpeg_prepared* files, i
     b->blobs.resize((size_t)count);
     b->sizes.resize((size_t)count);
     for (int i = 0; i < count; i++) { b->blobs[(size_t)i] = files[i].head; b->sizes[(size_t)i] = files[i].head_size; }
-    const int rc = group_begin(b->G, b->blobs.data(), b->sizes.data(), count, 0, false, b->files.data());
+    const int rc = group_begin(b->G, b->blobs.data(), b->sizes.data(), count, 0, false, b->files.data(), accept);
     if (rc) { delete b; return rc; }
     *batch = b;
     return IMP_OK;
@@ -777,7 +882,7 @@ int impgpu_host_unregister(void* p) {
 
 int impgpu_jpeg_counters(unsigned long long* counters, int n) {
     if (!counters || n < 0) return IMP_ERROR_INVALID_ARGS;
-    for (int i = 0; i < n; i++) counters[i] = i < 4 + JPEG_WHY_COUNT + 1 ? g_count[i].load(std::memory_order_relaxed) : 0ull;
+    for (int i = 0; i < n; i++) counters[i] = i < COUNT_SLOTS ? g_count[i].load(std::memory_order_relaxed) : 0ull;
     return IMP_OK;
 }
 
@@ -792,10 +897,14 @@ int impgpu_jpeg_stage_times(double* microseconds, int n) {
 }
 
 int impgpu_image_decode_jpeg(const unsigned char* blob, size_t size, impgpu_image** out) {
+    return impgpu_image_decode_jpeg_ex(blob, size, 0, out);
+}
+
+int impgpu_image_decode_jpeg_ex(const unsigned char* blob, size_t size, int accept, impgpu_image** out) {
     if (!blob || !out) return IMP_ERROR_INVALID_ARGS;
     *out = nullptr;
     int code = IMP_OK;
-    const int rc = impgpu_batch_decode_jpeg(&blob, &size, 1, out, &code);
+    const int rc = impgpu_batch_decode_jpeg_ex(&blob, &size, 1, accept, out, &code);
     return rc ? rc : code;
 }
 

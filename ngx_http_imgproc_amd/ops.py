@@ -24,6 +24,8 @@ IMP_ERROR_TOO_MUCH_FILTERS = 55
 IMP_ERROR_DEVICE = 90
 INTER_NN, INTER_LINEAR, INTER_CUBIC, INTER_AREA, INTER_LANCZOS4 = 0, 1, 2, 3, 4
 
+# impgpu_*_jpeg_ex accept mask (include/impgpu.h)
+JPEG_PROGRESSIVE = 1
 # impgpu_*_png_ex accept masks (include/impgpu.h)
 PNG_PALETTE = 1
 PNG_LOW_GRAY = 2
@@ -121,6 +123,13 @@ class Image:
         """cvDecodeImage(&rawencoded, -1) for a JPEG blob (bridge.c:545-552), on the device -> (code, Image or None)."""
         h = C.c_void_p()
         rc = lib.impgpu_image_decode_jpeg(bytes(blob), len(blob), C.byref(h))
+        return rc, (cls(handle=h.value) if rc == 0 else None)
+
+    @classmethod
+    def decode_jpeg_ex(cls, blob, accept):
+        """impgpu_image_decode_jpeg_ex: decode_jpeg that also takes the kinds of `accept` (JPEG_PROGRESSIVE) -> (code, Image or None)."""
+        h = C.c_void_p()
+        rc = lib.impgpu_image_decode_jpeg_ex(bytes(blob), len(blob), int(accept), C.byref(h))
         return rc, (cls(handle=h.value) if rc == 0 else None)
 
     @classmethod
@@ -335,6 +344,79 @@ def batch_decode_jpeg(blobs):
     if rc:
         raise ImpError(rc, "impgpu_batch_decode_jpeg")
     return [(codes[i], Image(handle=imgs[i]) if codes[i] == 0 else None) for i in range(n)]
+
+
+def batch_decode_jpeg_ex(blobs, accept):
+    """impgpu_batch_decode_jpeg_ex -> [(code, Image or None)] in the order of `blobs`."""
+    n = len(blobs)
+    keep = [bytes(b) for b in blobs]
+    arr = (C.c_char_p * max(1, n))(*keep)
+    sizes = (C.c_size_t * max(1, n))(*[len(b) for b in keep])
+    imgs = (C.c_void_p * max(1, n))()
+    codes = (C.c_int * max(1, n))()
+    rc = lib.impgpu_batch_decode_jpeg_ex(arr, sizes, n, int(accept), imgs, codes)
+    if rc:
+        raise ImpError(rc, "impgpu_batch_decode_jpeg_ex")
+    return [(codes[i], Image(handle=imgs[i]) if codes[i] == 0 else None) for i in range(n)]
+
+
+def batch_decode_jpeg_begin_finish_ex(blobs, accept, prepared=False, pending=False):
+    """impgpu_batch_decode_jpeg_begin_ex (or, prepared=True, _prepared_begin_ex with every file whole) and _finish, one
+    group -> ([(code, Image or None)], level launches of the group).  pending=True (prepared only): the frames are taken
+    through impgpu_batch_decode_jpeg_pending ahead of the verdicts."""
+    from ._lib import CJpegPrepared
+
+    n = len(blobs)
+    keep = [np.frombuffer(bytes(b), np.uint8) for b in blobs]
+    h = C.c_void_p()
+    if prepared:
+        arr = (CJpegPrepared * n)()
+        for i, b in enumerate(keep):
+            arr[i].head, arr[i].head_size, arr[i].scan, arr[i].scan_size, arr[i].registered = b.ctypes.data, b.size, None, 0, 0
+        rc = lib.impgpu_batch_decode_jpeg_prepared_begin_ex(arr, n, int(accept), C.byref(h))
+    else:
+        raw = [bytes(b) for b in blobs]
+        arr = (C.c_char_p * n)(*raw)
+        sizes = (C.c_size_t * n)(*[len(b) for b in raw])
+        rc = lib.impgpu_batch_decode_jpeg_begin_ex(arr, sizes, n, int(accept), C.byref(h))
+    if rc:
+        raise ImpError(rc, "impgpu_batch_decode_jpeg_begin_ex")
+    early = (C.c_void_p * n)()
+    if pending:
+        rc = lib.impgpu_batch_decode_jpeg_pending(h, early)
+        if rc:
+            raise ImpError(rc, "impgpu_batch_decode_jpeg_pending")
+    was = lib.impgpu_jpeg_profile(1)
+    imgs = (C.c_void_p * n)()
+    codes = (C.c_int * n)()
+    rc = lib.impgpu_batch_decode_jpeg_finish(C.byref(h), imgs, codes)
+    t = (C.c_double * 16)()
+    lib.impgpu_jpeg_stage_times(t, 16)
+    lib.impgpu_jpeg_profile(was)
+    if rc:
+        raise ImpError(rc, "impgpu_batch_decode_jpeg_finish")
+    out = []
+    for i in range(n):
+        handle = imgs[i] or early[i]
+        im = Image(handle=handle) if handle else None
+        if codes[i] != 0 and im is not None:
+            im.release()
+            im = None
+        out.append((codes[i], im))
+    return out, int(t[14])
+
+
+def jpeg_info_ex(blob, accept):
+    w, h, c = C.c_int(), C.c_int(), C.c_int()
+    rc = lib.impgpu_jpeg_info_ex(bytes(blob), len(blob), int(accept), w, h, c)
+    return rc, ((w.value, h.value, c.value) if rc == 0 else None)
+
+
+def jpeg_counters():
+    """impgpu_jpeg_counters -> a list of 16 counts"""
+    c = (C.c_ulonglong * 16)()
+    lib.impgpu_jpeg_counters(c, 16)
+    return list(c)
 
 
 def batch_decode_png(blobs):
