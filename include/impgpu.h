@@ -434,6 +434,25 @@ int impgpu_calc_perceived_brightness(const impgpu_image* image, float* brightnes
 /* Memory ASCII(IplImage* input, char* args, ngx_pool_t* pool)         filters.h:18, filters.c:486-522.
  * out must hold (width+1)*height-1 bytes; like the reference it leaves the image in HSV. */
 int impgpu_ascii(impgpu_image* image, const char* args, unsigned char* out, long capacity, long* length);
+/* The two exits above for `count` frames (0..256) at once -- a request queue's json and text answers: launches shared by
+ * every frame of a channel count, ONE wait for the device per call.  brightness[i] / codes[i] are what
+ * impgpu_calc_perceived_brightness(images[i], &brightness[i]) would give, bit for bit; outs[i] / lengths[i] / codes[i] and
+ * the frame's pixels afterwards (HSV) what impgpu_ascii(images[i], args[i], outs[i], capacities[i], &lengths[i]) would.
+ * An entry that call would refuse (a NULL handle; for the text a NULL outs[i], fewer than 3 channels, capacities[i] below
+ * (width+1)*height-1) gets IMP_ERROR_INVALID_ARGS alone: its frame and buffer are untouched, no other entry changes.
+ * args[i] may be NULL (""), and so may args (all "").  An album gives frame 0, as the lone calls do.  The fault point of
+ * the brightness call (IMP_STEP_INFO) is entered per non-NULL entry, in entry order, before anything is launched; an
+ * entry whose point fires gets IMP_ERROR_DEVICE and is left out, the rest is served.  A shared launch that fails gives
+ * every entry in it IMP_ERROR_DEVICE.  launches (may be NULL) receives the number of kernels enqueued: at most two per
+ * channel count present for the brightness (one when no frame of it has 4113 pixels), one per channel count for the
+ * text, whatever `count` is.  IMP_ERROR_INVALID_ARGS with nothing enqueued for NULL arrays (count > 0), a count outside
+ * 0..256 and -- impgpu_batch_ascii writes its frames in place -- the same handle twice (the brightness only reads:
+ * repeats are allowed there); IMP_ERROR_DEVICE without an env (every codes[i] says so too); otherwise IMP_OK, and the
+ * verdicts are in codes[].  Both return with their answers: the wait is inside. */
+int impgpu_batch_calc_perceived_brightness(const impgpu_image* const* images, int count, float* brightness, int* codes,
+                                           int* launches);
+int impgpu_batch_ascii(impgpu_image* const* images, const char* const* args, int count, unsigned char* const* outs,
+                       const long* capacities, long* lengths, int* codes, int* launches);
 /* cvCvtColor(image, colored, CV_GRAY2BGR)                             bridge.c:613-618 */
 int impgpu_gray2bgr(impgpu_image** pointer);
 /* void RGB2HSV(IplImage*) / void HSV2RGB(IplImage*)                   helpers.h:17-18, helpers.c:70-176 */

@@ -184,6 +184,8 @@ SIGNATURES = {
     "impgpu_blend_with_paper": (C.c_int, [P]),
     "impgpu_calc_perceived_brightness": (C.c_int, [P, C.POINTER(C.c_float)]),
     "impgpu_ascii": (C.c_int, [P, C.c_char_p, P, C.c_long, C.POINTER(C.c_long)]),
+    "impgpu_batch_calc_perceived_brightness": (C.c_int, [PP, C.c_int, C.POINTER(C.c_float), IP, IP]),
+    "impgpu_batch_ascii": (C.c_int, [PP, C.POINTER(C.c_char_p), C.c_int, PP, C.POINTER(C.c_long), C.POINTER(C.c_long), IP, IP]),
     "impgpu_gray2bgr": (C.c_int, [PP]),
     "impgpu_rgb2hsv": (C.c_int, [P]),
     "impgpu_hsv2rgb": (C.c_int, [P]),

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstring>
+#include <vector>
 #include "imp_internal.h"
 
 using namespace imp;
@@ -447,6 +448,82 @@ int impgpu_ascii(impgpu_image* image, const char* args, unsigned char* out, long
     dev_free(dev_out);
     if (!rc) *length = buflen;
     return rc;
+}
+
+// The json exit of many requests at once: impgpu_calc_perceived_brightness per entry, at most two launches per channel count
+// and ONE wait for the call.
+int impgpu_batch_calc_perceived_brightness(const impgpu_image* const* images, int count, float* brightness, int* codes, int* launches) {
+    if (launches) *launches = 0;
+    if (count < 0 || count > 256 || (count > 0 && (!images || !brightness || !codes))) return IMP_ERROR_INVALID_ARGS;
+    if (int rc = need_env()) {
+        for (int i = 0; i < count; i++) codes[i] = rc;
+        return rc;
+    }
+    TraceRange tr("IMP_STEP_INFO");
+    const unsigned long long launched = t_launches;
+    // the fault point impgpu_calc_perceived_brightness enters, per entry that call would take, in entry order, before anything
+    // is launched (the rule of impgpu_batch_run_ops); an entry whose point fires is left out of the launch
+    std::vector<View> views;
+    std::vector<int> who;
+    views.reserve((size_t)count);
+    who.reserve((size_t)count);
+    for (int i = 0; i < count; i++) {
+        if (!images[i]) { codes[i] = IMP_ERROR_INVALID_ARGS; continue; }
+        if (fault_hit(IMP_STEP_INFO)) { codes[i] = IMP_ERROR_DEVICE; continue; }
+        views.push_back(view_of(images[i]));
+        who.push_back(i);
+    }
+    const int m = (int)who.size();
+    std::vector<float> vals((size_t)m, 0.f);
+    std::vector<int> cs((size_t)m, IMP_OK);
+    const int rc = launch_brightness_mixed(views.data(), m, vals.data(), cs.data(), env_stream());
+    for (int j = 0; j < m; j++) {
+        codes[who[(size_t)j]] = rc ? rc : cs[(size_t)j];
+        if (!rc && cs[(size_t)j] == IMP_OK) brightness[who[(size_t)j]] = vals[(size_t)j];
+    }
+    if (launches) *launches = (int)(t_launches - launched);
+    return IMP_OK;
+}
+
+// The text exit of many requests at once: impgpu_ascii per entry, one launch per channel count, one copy of all texts and ONE wait.
+int impgpu_batch_ascii(impgpu_image* const* images, const char* const* args, int count, unsigned char* const* outs,
+                       const long* capacities, long* lengths, int* codes, int* launches) {
+    if (launches) *launches = 0;
+    if (count < 0 || count > 256 || (count > 0 && (!images || !outs || !capacities || !lengths || !codes))) return IMP_ERROR_INVALID_ARGS;
+    {
+        std::vector<const impgpu_image*> seen;                          // the same handle twice: its frame would be converted twice
+        seen.reserve((size_t)count);
+        for (int i = 0; i < count; i++) if (images[i]) seen.push_back(images[i]);
+        std::sort(seen.begin(), seen.end());
+        if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return IMP_ERROR_INVALID_ARGS;
+    }
+    if (int rc = need_env()) {
+        for (int i = 0; i < count; i++) codes[i] = rc;
+        return rc;
+    }
+    const unsigned long long launched = t_launches;
+    std::vector<AsciiItem> items;
+    std::vector<int> who;
+    items.reserve((size_t)count);
+    who.reserve((size_t)count);
+    for (int i = 0; i < count; i++) {
+        const impgpu_image* im = images[i];
+        // impgpu_ascii's refusals, in its order: nothing of a refused entry is touched
+        if (!im || !outs[i] || im->c < 3 || capacities[i] < (long)(im->w + 1) * im->h - 1) { codes[i] = IMP_ERROR_INVALID_ARGS; continue; }
+        const char* a = args ? args[i] : nullptr;
+        items.push_back(AsciiItem{im->d, im->w, im->h, im->c, im->step, a && !std::strcmp(a, "wide"), outs[i]});
+        who.push_back(i);
+    }
+    const int m = (int)who.size();
+    std::vector<int> cs((size_t)m, IMP_OK);
+    const int rc = launch_ascii_mixed(items.data(), m, cs.data(), env_stream());
+    for (int j = 0; j < m; j++) {
+        const int i = who[(size_t)j];
+        codes[i] = rc ? rc : cs[(size_t)j];
+        if (codes[i] == IMP_OK) lengths[i] = (long)(images[i]->w + 1) * images[i]->h - 1;
+    }
+    if (launches) *launches = (int)(t_launches - launched);
+    return IMP_OK;
 }
 
 int impgpu_gray2bgr(impgpu_image** pointer) {

@@ -14,6 +14,8 @@
 //     JPEG answers   impgpu_batch_encode_jpeg            cvEncodeImage(".jpg"), bridge.c:704
 //     PNG answers    impgpu_batch_encode_png             cvEncodeImage(".png"), bridge.c:704
 //     pixel answers  impgpu_batch_download               for the host encoders (PNG, WebP, FreeImage formats)
+//     json answers   impgpu_batch_calc_perceived_brightness   Info(), bridge.c:283-300 (two or more; one: the lone call)
+//     text answers   impgpu_batch_ascii                  ASCII(), bridge.c:668-676 (likewise)
 // Nothing a worker writes into its slot is trusted further than a request is: the request record is copied out of shared
 // memory once and validated (sizes against the slot, offsets against the text area, frame geometry against the bytes), and
 // the answer's placement is the broker's own: it is written to the slot for the worker and never read back from there.
@@ -310,6 +312,81 @@ struct Worker {
         }
     }
 
+    // The json exit (Info(), bridge.c:283-300) of the requests `who`: one impgpu_batch_calc_perceived_brightness -- one wait
+    // for all of them instead of one each.  (A lane's batch is at most --batch <= 256 requests, which is what the call takes.)
+    // A list of one keeps the lone call.  For the json exit that is also what the measurement says: at count 1 the batch
+    // call loses the descriptor table's upload and the staging buffer (94 against 90 us), at count 2 it wins (95 against
+    // 168; profiles/r09_info_batch_probe.jsonl).  For the text exit it is the rule alone -- a lone request keeps the path it
+    // always had: the recorded count = 1 row has the batch call ahead (20 against 29 us; impgpu_ascii allocates twice and
+    // waits on the stream itself).
+    static constexpr size_t INFO_BATCH_MIN = 2, TEXT_BATCH_MIN = 2;
+    void answer_info(const std::vector<size_t>& who) {
+        if (who.size() < INFO_BATCH_MIN) {
+            for (size_t k : who) {
+                Req& r = reqs[k];
+                float b = 0;
+                const int rc = impgpu_calc_perceived_brightness(r.img, &b);
+                if (rc != IMP_OK) { fail(r, rc, IMP_STEP_INFO, impgpu_last_error()); continue; }
+                r.brightness = b;
+                r.code = IMP_OK; r.done = true;
+            }
+            return;
+        }
+        const size_t m = who.size();
+        std::vector<const impgpu_image*> im(m);
+        std::vector<float> vals(m, 0.f);
+        std::vector<int> cs(m, IMP_OK);
+        for (size_t j = 0; j < m; j++) im[j] = reqs[who[j]].img;
+        const int rc = impgpu_batch_calc_perceived_brightness(im.data(), (int)m, vals.data(), cs.data(), nullptr);
+        for (size_t j = 0; j < m; j++) {
+            Req& r = reqs[who[j]];
+            const int c = rc != IMP_OK ? rc : cs[j];
+            if (c != IMP_OK) { fail(r, c, IMP_STEP_INFO, impgpu_last_error()); continue; }
+            r.brightness = vals[j];
+            r.code = IMP_OK; r.done = true;
+        }
+    }
+
+    // The text exit (ASCII(), bridge.c:668-676) of the requests `who` (each fits its slot: checked where they were collected):
+    // one impgpu_batch_ascii, the texts straight into the slots at slot_data + out_offset.  The argument string comes from the
+    // private copy in Req, never from the slot.
+    void answer_text(const std::vector<size_t>& who) {
+        auto arg_of = [](const Req& r) { return r.q.ascii_at >= 0 ? r.q.text + r.q.ascii_at : ""; };
+        if (who.size() < TEXT_BATCH_MIN) {
+            for (size_t k : who) {
+                Req& r = reqs[k];
+                const long need = (long)(r.out_w + 1) * r.out_h - 1;
+                long len = 0;
+                const int rc = impgpu_ascii(r.img, arg_of(r), S.slot_data(r.slot) + r.out_offset, need, &len);
+                if (rc != IMP_OK) { fail(r, rc, IMP_STEP_INFO, rc == IMP_ERROR_DEVICE ? impgpu_last_error() : ""); continue; }
+                r.out_bytes = (uint64_t)len;
+                r.code = IMP_OK; r.done = true;
+            }
+            return;
+        }
+        const size_t m = who.size();
+        std::vector<impgpu_image*> im(m);
+        std::vector<const char*> args(m);
+        std::vector<unsigned char*> outs(m);
+        std::vector<long> caps(m), lens(m, 0);
+        std::vector<int> cs(m, IMP_OK);
+        for (size_t j = 0; j < m; j++) {
+            const Req& r = reqs[who[j]];
+            im[j] = r.img;
+            args[j] = arg_of(r);
+            outs[j] = S.slot_data(r.slot) + r.out_offset;
+            caps[j] = (long)(r.out_w + 1) * r.out_h - 1;
+        }
+        const int rc = impgpu_batch_ascii(im.data(), args.data(), (int)m, outs.data(), caps.data(), lens.data(), cs.data(), nullptr);
+        for (size_t j = 0; j < m; j++) {
+            Req& r = reqs[who[j]];
+            const int c = rc != IMP_OK ? rc : cs[j];
+            if (c != IMP_OK) { fail(r, c, IMP_STEP_INFO, c == IMP_ERROR_DEVICE ? impgpu_last_error() : ""); continue; }
+            r.out_bytes = (uint64_t)lens[j];
+            r.code = IMP_OK; r.done = true;
+        }
+    }
+
     // One batched answer call for the requests `who`, from their placement in Req: call(images, count, outs, capacities,
     // steps, lengths, codes) -> IMP_*.  An answer that came back goes out with its length, a failure with the library's error.
     template <class Call>
@@ -452,7 +529,7 @@ struct Worker {
         g_us_ops += (uint64_t)(t3 - t2);
         // ---- answers (bridge.c:659-710): placed right behind the request's input in its slot
         std::map<int, std::vector<size_t>> by_quality;
-        std::vector<size_t> raw, png;
+        std::vector<size_t> raw, png, info, text;
         for (size_t k = 0; k < n; k++) {
             Req& r = reqs[k];
             if (r.done) continue;
@@ -461,20 +538,12 @@ struct Worker {
             r.cap = r.out_offset < S.slot_bytes ? S.slot_bytes - r.out_offset : 0;
             if (r.q.out_kind == IMPB_OUT_INFO) {
                 r.step = IMP_STEP_INFO;
-                float b = 0;
-                const int rc = impgpu_calc_perceived_brightness(r.img, &b);
-                if (rc != IMP_OK) { fail(r, rc, IMP_STEP_INFO, impgpu_last_error()); continue; }
-                r.brightness = b;
-                r.code = IMP_OK; r.done = true;
+                info.push_back(k);
             } else if (r.q.out_kind == IMPB_OUT_ASCII) {            // the text exit (bridge.c:669-670): (width + 1) * height - 1 characters
                 r.step = IMP_STEP_INFO;
                 const long need = (long)(r.out_w + 1) * r.out_h - 1;
                 if (!r.fits((uint64_t)(need > 0 ? need : 1))) { fail(r, IMP_ERROR_MALLOC_FAILED, IMP_STEP_INFO, "answer does not fit the slot"); continue; }
-                long len = 0;
-                const int rc = impgpu_ascii(r.img, r.q.ascii_at >= 0 ? r.q.text + r.q.ascii_at : "", S.slot_data(r.slot) + r.out_offset, need, &len);
-                if (rc != IMP_OK) { fail(r, rc, IMP_STEP_INFO, rc == IMP_ERROR_DEVICE ? impgpu_last_error() : ""); continue; }
-                r.out_bytes = (uint64_t)len;
-                r.code = IMP_OK; r.done = true;
+                text.push_back(k);
             } else if (r.q.out_kind == IMPB_OUT_JPEG) {
                 r.step = IMP_STEP_ENCODE;
                 if (!r.fits(impgpu_jpeg_encode_bound(r.out_w, r.out_h, r.out_c))) { fail(r, IMP_ERROR_MALLOC_FAILED, IMP_STEP_ENCODE, "answer does not fit the slot"); continue; }
@@ -516,6 +585,13 @@ struct Worker {
             return impgpu_batch_download(im, m, outs, row_steps);
         });
         if (most) answer(by_quality[common], jpeg(common));
+        // The json and text exits go LAST.  Each of the calls above and below ends in a wait of its own, and the lane's stream
+        // is in order, so the order changes nobody's device time -- only how long the host sits in each wait.  The encoders'
+        // calls carry most of a batch's device work; behind them the one-workgroup brightness walks and the texts are a short
+        // tail, where in front they would hold back the enqueueing of everybody's encode (what the per-request calls in the
+        // collecting loop used to do).  Nothing leaves before finish() below either way.
+        answer_info(info);
+        answer_text(text);
         for (size_t k = 0; k < n; k++) finish(reqs[k], (int)n);
         g_us_answer += (uint64_t)(now_us() - t3);
     }

@@ -287,6 +287,11 @@ int launch_blend_paper(uint8_t* d, long long stride, int w, int h, int step, int
 int launch_brightness(const View& v, float* host_result, hipStream_t s);
 int launch_ascii(uint8_t* d, int w, int h, int c, int step, const uint8_t* table, int tablelen,
                  float factor, uint8_t* dev_out, hipStream_t s);
+// the two of many frames at once (impgpu_batch_calc_perceived_brightness, impgpu_batch_ascii): launches per channel count,
+// one wait, a verdict per frame in codes[]; the return value is IMP_OK unless the arguments are unusable
+int launch_brightness_mixed(const View* views, int count, float* results, int* codes, hipStream_t s);
+struct AsciiItem { uint8_t* d; int w, h, c, step; bool wide; unsigned char* out; };     // out: (w + 1) * h - 1 bytes of host memory
+int launch_ascii_mixed(const AsciiItem* items, int count, int* codes, hipStream_t s);
 // imp_blur.hip
 int launch_gaussian(uint8_t* d, long long stride, int w, int h, int c, int step, int count,
                     double sigma, hipStream_t s);

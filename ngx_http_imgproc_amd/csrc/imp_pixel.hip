@@ -667,13 +667,14 @@ __device__ __forceinline__ uint32_t br_load_px(const uint8_t* p) {
     return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
 }
 
+// The fold of block `blk` of one frame: shared by the lone kernel and by k_brightness_fold_mix (a frame per descriptor).
 template <int CN>
-__global__ __launch_bounds__(64 * BR_FOLD_WAVES) void k_brightness_fold(const uint8_t* __restrict__ src, int w, int h, int step, long long n,
-                                                                         int ne, long long nchunks, ParityFn* __restrict__ summ) {
+__device__ __forceinline__ void br_fold_body(const uint8_t* __restrict__ src, int w, int h, int step, long long n, int ne, long long nchunks,
+                                             ParityFn* __restrict__ summ, int blk) {
     constexpr int BT = BR_WCHUNK * BR_FOLD_WAVES;                 // terms per block
     __shared__ uint32_t s_px[BT + BT / 16];                       // term j of the block at j + j / 16: a lane's 16 terms are contiguous, lanes 17 words apart
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const long long i0 = (long long)blockIdx.x * BT;
+    const long long i0 = (long long)blk * BT;
     // the block's terms are the pixels of a few whole columns (visiting order: x outer, y inner): read them along the rows
     const int x0 = (int)(i0 / h);
     const long long ilast = min(n, i0 + BT) - 1;
@@ -692,7 +693,7 @@ __global__ __launch_bounds__(64 * BR_FOLD_WAVES) void k_brightness_fold(const ui
     const long long mine = i0 + (long long)t * BR_EPT;
 #pragma unroll
     for (int j = 0; j < BR_EPT; j++) td[j] = br_term_of<CN>(s_px[t * 17 + j]);
-    const long long chunk = (long long)blockIdx.x * BR_FOLD_WAVES + wv;
+    const long long chunk = (long long)blk * BR_FOLD_WAVES + wv;
     for (int e = 0; e < ne; e++) {
         const BrRegime g = br_regime(BR_E0 + e);
         ParityFn f = pf_identity();
@@ -702,6 +703,12 @@ __global__ __launch_bounds__(64 * BR_FOLD_WAVES) void k_brightness_fold(const ui
         f = pf_wave_scan(f);
         if (lane == 63 && chunk < nchunks) summ[(long long)e * nchunks + chunk] = f;
     }
+}
+
+template <int CN>
+__global__ __launch_bounds__(64 * BR_FOLD_WAVES) void k_brightness_fold(const uint8_t* __restrict__ src, int w, int h, int step, long long n,
+                                                                         int ne, long long nchunks, ParityFn* __restrict__ summ) {
+    br_fold_body<CN>(src, w, h, step, n, ne, nchunks, summ, (int)blockIdx.x);
 }
 
 // inclusive scan of one ParityFn per thread over a block of BR_WALK_WAVES waves; s_part: that many entries of shared scratch
@@ -722,9 +729,10 @@ __device__ __forceinline__ ParityFn pf_block_scan(ParityFn f, ParityFn* s_part) 
 // One block of four waves carries the accumulator through the frame (every thread holds the same sum and position).  A step
 // handles 1024 entries, four consecutive ones per thread: the thread folds its four, the block scans 256 functions -- the scan
 // is all shuffles, and four waves of them cost a quarter of what sixteen did.
+// (the body: the lone kernel runs it on its arguments, k_brightness_walk_mix on a descriptor per workgroup)
 template <int CN>
-__global__ __launch_bounds__(64 * BR_WALK_WAVES) void k_brightness_walk(const uint8_t* __restrict__ src, int w, int h, int step, long long n, int ne,
-                                                                         long long nchunks, const ParityFn* __restrict__ summ, float* __restrict__ out) {
+__device__ __forceinline__ void br_walk_body(const uint8_t* __restrict__ src, int w, int h, int step, long long n, int ne, long long nchunks,
+                                             const ParityFn* __restrict__ summ, float* __restrict__ out) {
     constexpr int NT = 64 * BR_WALK_WAVES, EPT = BR_WALK_EPT;
     __shared__ ParityFn s_part[BR_WALK_WAVES];
     __shared__ uint32_t s_tot[NT];
@@ -865,6 +873,12 @@ __global__ __launch_bounds__(64 * BR_WALK_WAVES) void k_brightness_walk(const ui
     if (tid == 0) *out = sum;
 }
 
+template <int CN>
+__global__ __launch_bounds__(64 * BR_WALK_WAVES) void k_brightness_walk(const uint8_t* __restrict__ src, int w, int h, int step, long long n, int ne,
+                                                                         long long nchunks, const ParityFn* __restrict__ summ, float* __restrict__ out) {
+    br_walk_body<CN>(src, w, h, step, n, ne, nchunks, summ, out);
+}
+
 int launch_brightness(const View& v, float* host_result, hipStream_t s) {
     const long long n = (long long)v.w * v.h;
     if (!view_fits(v.w, v.h, v.c, v.step)) return IMP_ERROR_INVALID_ARGS;       // (n <= 2^30: the kernels divide in 32 bits)
@@ -902,11 +916,154 @@ int launch_brightness(const View& v, float* host_result, hipStream_t s) {
     return IMP_OK;
 }
 
-// ------------------------------------------------------------------ ASCII, filters.c:486-522
+// ------------------------------------------------------------------ CalcPerceivedBrightness of many frames (impgpu_batch_calc_perceived_brightness)
+// The two launches above, once per channel count for ALL frames: k_brightness_fold_mix runs br_fold_body on every block of
+// every frame that has summaries, k_brightness_walk_mix one br_walk_body workgroup per frame -- N one-workgroup walks side by
+// side on N compute units instead of one behind the other, each with a wait of its own.  The arithmetic is the bodies': nothing
+// here touches a float.
+// The descriptors of one channel count stand longest frame first: workgroups are dispatched in index order, so the walks that
+// last longest start first and the launch's tail is short ones; and since ne grows with the pixel count, the frames with
+// summaries are a prefix of that order -- the fold's table is the first `nf` descriptors of the walk's.
+// A fold workgroup finds its frame by bisection over a plain prefix table of first-block numbers (at most eight uniform
+// steps), NOT through MixIndex / mix_deal: those deal whole frames to XCD lists, which keeps a frame's blocks on one L2 --
+// worth it for the resize and chain kernels, whose neighbouring blocks share source rows.  A fold block reads its 8 192
+// pixels once and shares nothing with its neighbours, while a pool of thumbnails with one 4K frame in it would fold that
+// frame's 1 013 blocks on an eighth of the device.  Consecutive block numbers spread every frame over all XCDs, as the lone
+// launch does.
+struct BrDesc {
+    const uint8_t* src;
+    int w, h, step, ne;
+    long long n, nchunks;
+    long long summ_off;          // the frame's summaries in the call's ONE block, in ParityFn
+    int first;                   // its first workgroup in the fold launch
+    int pad;
+};
+
 template <int CN>
-__global__ __launch_bounds__(256) void k_ascii(uint8_t* img, int w, int h, int step, const uint8_t* __restrict__ table,
-                                               float factor, uint8_t* __restrict__ out) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+__global__ __launch_bounds__(64 * BR_FOLD_WAVES) void k_brightness_fold_mix(const BrDesc* __restrict__ descs, int nf, ParityFn* __restrict__ summ) {
+    const int b = (int)blockIdx.x;
+    int lo = 0, hi = nf;
+    while (hi - lo > 1) {                                  // last frame whose first block is <= b
+        const int mid = (lo + hi) >> 1;
+        if (descs[mid].first <= b) lo = mid; else hi = mid;
+    }
+    const BrDesc& d = descs[lo];
+    br_fold_body<CN>(d.src, d.w, d.h, d.step, d.n, d.ne, d.nchunks, summ + d.summ_off, b - d.first);
+}
+
+template <int CN>
+__global__ __launch_bounds__(64 * BR_WALK_WAVES) void k_brightness_walk_mix(const BrDesc* __restrict__ descs, const ParityFn* __restrict__ summ,
+                                                                             float* __restrict__ out) {
+    const BrDesc& d = descs[blockIdx.x];
+    br_walk_body<CN>(d.src, d.w, d.h, d.step, d.n, d.ne, d.nchunks, summ + d.summ_off, out + blockIdx.x);
+}
+
+// views[i] -> results[i], codes[i] (IMP_OK, IMP_ERROR_INVALID_ARGS for a frame launch_brightness refuses, IMP_ERROR_DEVICE
+// for every frame of a launch that failed).  At most two launches per channel count, one wait.
+// One refusal is this function's own: a view without memory, or with a channel count other than 1 / 3 / 4, is
+// IMP_ERROR_INVALID_ARGS here, where launch_brightness would not look at the pointer and would read any other count as 4.
+// No handle the library makes (image_new_album, impgpu_image_wrap) has either, so no caller can see the difference; a
+// descriptor table just is no place for a frame that cannot be read.
+int launch_brightness_mixed(const View* views, int count, float* results, int* codes, hipStream_t s) {
+    if (count <= 0) return IMP_OK;
+    std::vector<int> order;
+    order.reserve((size_t)count);
+    for (int i = 0; i < count; i++) {
+        const View& v = views[i];
+        const bool ok = v.d && (v.c == 1 || v.c == 3 || v.c == 4) && view_fits(v.w, v.h, v.c, v.step);
+        codes[i] = ok ? IMP_OK : IMP_ERROR_INVALID_ARGS;
+        if (ok) order.push_back(i);
+    }
+    if (order.empty()) return IMP_OK;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
+        if (views[a].c != views[b].c) return views[a].c < views[b].c;
+        return (long long)views[a].w * views[a].h > (long long)views[b].w * views[b].h;
+    });
+    const size_t nd = order.size();
+    std::vector<BrDesc> descs(nd);
+    long long summ_total = 0;
+    struct Group { int c, at, count, nf, blocks; };
+    std::vector<Group> groups;
+    for (size_t k = 0; k < nd; k++) {
+        const View& v = views[order[k]];
+        if (groups.empty() || groups.back().c != v.c) groups.push_back(Group{v.c, (int)k, 0, 0, 0});
+        Group& g = groups.back();
+        BrDesc& d = descs[k];
+        d = BrDesc{};
+        d.src = v.d; d.w = v.w; d.h = v.h; d.step = v.step;
+        d.n = (long long)v.w * v.h;
+        d.nchunks = (d.n + BR_WCHUNK - 1) / BR_WCHUNK;
+        int last = 0;                                      // the binades with summaries, as launch_brightness counts them
+        while (last < 32 && (double)d.n * 255.0 >= ldexp(1.0, last + 1)) last++;
+        d.ne = last >= BR_E0 ? last - BR_E0 + 1 : 0;
+        d.summ_off = summ_total;
+        summ_total += (long long)d.ne * d.nchunks;
+        d.first = g.blocks;
+        g.count++;
+        if (d.ne) {
+            g.nf++;
+            g.blocks += (int)((d.nchunks + BR_FOLD_WAVES - 1) / BR_FOLD_WAVES);
+        }
+    }
+    auto fail_all = [&](int rc) {
+        for (int i : order) codes[i] = rc;
+        return IMP_OK;
+    };
+    void *ddesc = nullptr, *summ = nullptr, *out = nullptr, *pin = nullptr, *token = nullptr;
+    if (int rc = stage_begin(nd * sizeof(float), &pin, &token)) return fail_all(rc);
+    if (int rc = upload_small(descs.data(), nd * sizeof(BrDesc), &ddesc, s)) return fail_all(rc);
+    int rc = dev_alloc_on(nd * sizeof(float), &out, s);
+    if (!rc && summ_total) rc = dev_alloc_on((size_t)summ_total * sizeof(ParityFn), &summ, s);
+    if (rc) { dev_free_on(out, s); dev_free_on(ddesc, s); return fail_all(rc); }
+    bool any = false;
+    for (const Group& g : groups) {
+        const BrDesc* dd = (const BrDesc*)ddesc + g.at;
+        float* o = (float*)out + g.at;
+        if (g.blocks) {
+            const dim3 grid((unsigned)g.blocks), block(64 * BR_FOLD_WAVES);
+            if (g.c == 1) hipLaunchKernelGGL((k_brightness_fold_mix<1>), grid, block, 0, s, dd, g.nf, (ParityFn*)summ);
+            else if (g.c == 3) hipLaunchKernelGGL((k_brightness_fold_mix<3>), grid, block, 0, s, dd, g.nf, (ParityFn*)summ);
+            else hipLaunchKernelGGL((k_brightness_fold_mix<4>), grid, block, 0, s, dd, g.nf, (ParityFn*)summ);
+        }
+        const dim3 grid((unsigned)g.count), block(64 * BR_WALK_WAVES);
+        if (g.c == 1) hipLaunchKernelGGL((k_brightness_walk_mix<1>), grid, block, 0, s, dd, (const ParityFn*)summ, o);
+        else if (g.c == 3) hipLaunchKernelGGL((k_brightness_walk_mix<3>), grid, block, 0, s, dd, (const ParityFn*)summ, o);
+        else hipLaunchKernelGGL((k_brightness_walk_mix<4>), grid, block, 0, s, dd, (const ParityFn*)summ, o);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {                             // this channel count's frames alone
+            set_error("brightness (batch)", e);
+            for (int k = 0; k < g.count; k++) codes[order[(size_t)(g.at + k)]] = IMP_ERROR_DEVICE;
+        } else any = true;
+    }
+    hipError_t e = hipSuccess;
+    if (any) e = hipMemcpyAsync(pin, out, nd * sizeof(float), hipMemcpyDeviceToHost, s);
+    dev_free_on(summ, s);
+    dev_free_on(out, s);
+    dev_free_on(ddesc, s);
+    if (e != hipSuccess) { set_error("brightness (batch) readback", e); (void)lane_wait(); return fail_all(IMP_ERROR_DEVICE); }
+    stage_hold(token, true);
+    if (!on_lane_stream(s)) rc = stream_join_back(s);
+    if (!rc) rc = lane_wait();
+    stage_hold(token, false);
+    if (rc) return fail_all(rc);
+    for (size_t k = 0; k < nd; k++) {
+        const int i = order[k];
+        if (codes[i] != IMP_OK) continue;
+        const View& v = views[i];
+        float sum;
+        std::memcpy(&sum, (const uint8_t*)pin + k * sizeof(float), sizeof sum);
+        // filters.c:728, as launch_brightness: float / int -> float, then / 255.0 in double, returned as float
+        const float mean = sum / (float)(v.w * v.h);
+        results[i] = (float)((double)mean / 255.0);
+    }
+    return IMP_OK;
+}
+
+// ------------------------------------------------------------------ ASCII, filters.c:486-522
+// pixel `idx` of one frame: shared by the lone kernel and k_ascii_mix
+template <int CN>
+__device__ __forceinline__ void ascii_px(uint8_t* img, int w, int h, int step, const uint8_t* __restrict__ table, float factor,
+                                         uint8_t* __restrict__ out, long long idx) {
     if (idx >= (long long)w * h) return;
     const int y = (int)(idx / w), x = (int)(idx - (long long)y * w);
     uint8_t* p = img + (size_t)y * step + (size_t)x * CN;
@@ -918,6 +1075,12 @@ __global__ __launch_bounds__(256) void k_ascii(uint8_t* img, int w, int h, int s
     if (x == 0 && ro > 0) out[ro - 1] = '\n';
 }
 
+template <int CN>
+__global__ __launch_bounds__(256) void k_ascii(uint8_t* img, int w, int h, int step, const uint8_t* __restrict__ table,
+                                               float factor, uint8_t* __restrict__ out) {
+    ascii_px<CN>(img, w, h, step, table, factor, out, (long long)blockIdx.x * 256 + threadIdx.x);
+}
+
 int launch_ascii(uint8_t* d, int w, int h, int c, int step, const uint8_t* table, int tablelen, float factor,
                  uint8_t* dev_out, hipStream_t s) {
     (void)tablelen;
@@ -926,6 +1089,117 @@ int launch_ascii(uint8_t* d, int w, int h, int c, int step, const uint8_t* table
     else if (c == 3) hipLaunchKernelGGL((k_ascii<3>), grid, block, 0, s, d, w, h, step, table, factor, dev_out);
     else return IMP_ERROR_INVALID_ARGS;
     IMP_HIP(hipGetLastError());
+    return IMP_OK;
+}
+
+// ------------------------------------------------------------------ ASCII of many frames (impgpu_batch_ascii)
+// One launch per channel count: a descriptor per frame, its 256-pixel blocks consecutive in the grid (a plain prefix table,
+// bisected -- a pixel is read and written once, nothing to keep on one L2), every pixel through ascii_px.  The texts land in
+// ONE device block, each at an offset of its own (bytes are stored one by one, so texts need no alignment among themselves;
+// the offsets are rounded to 64 only to keep two frames' stores out of one cache line).
+struct AsciiDesc {
+    uint8_t* d;
+    int w, h, step;
+    int table;                   // offset of its character table in the launch's table blob
+    float factor;
+    int first;                   // its first workgroup
+    long long out_off;           // its text in the call's output block
+};
+
+template <int CN>
+__global__ __launch_bounds__(256) void k_ascii_mix(const AsciiDesc* __restrict__ descs, int nd, const uint8_t* __restrict__ tables,
+                                                   uint8_t* __restrict__ out) {
+    const int b = (int)blockIdx.x;
+    int lo = 0, hi = nd;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (descs[mid].first <= b) lo = mid; else hi = mid;
+    }
+    const AsciiDesc& d = descs[lo];
+    ascii_px<CN>(d.d, d.w, d.h, d.step, tables + d.table, d.factor, out + d.out_off, (long long)(b - d.first) * 256 + threadIdx.x);
+}
+
+// items[i] -> its text in items[i].out (at least (w + 1) * h - 1 bytes: the caller has checked), codes[i].  Every item is a
+// frame of 3 or 4 channels that view_fits; one launch per channel count, one copy of all texts, one wait.
+int launch_ascii_mixed(const AsciiItem* items, int count, int* codes, hipStream_t s) {
+    static const unsigned char wide[] = "$@B%8&WM#*oahkbdpqwmZO0QLCJUYXzcvunxrjft/\\|()1{}[]?-_+~<>i!lI;:,\"^`'. ";
+    static const unsigned char narrow[] = "@%8#*+=-:. ";
+    if (count <= 0) return IMP_OK;
+    constexpr int NARROW_AT = 0, WIDE_AT = 16, TABLE_BYTES = 96;
+    static_assert(sizeof narrow <= WIDE_AT && WIDE_AT + sizeof wide <= TABLE_BYTES, "character tables");
+    std::vector<int> order;
+    order.reserve((size_t)count);
+    for (int i = 0; i < count; i++) {
+        const AsciiItem& it = items[i];
+        const bool ok = it.d && it.out && (it.c == 3 || it.c == 4) && view_fits(it.w, it.h, it.c, it.step);
+        codes[i] = ok ? IMP_OK : IMP_ERROR_INVALID_ARGS;
+        if (ok) order.push_back(i);
+    }
+    if (order.empty()) return IMP_OK;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return items[a].c < items[b].c; });
+    const size_t nd = order.size();
+    std::vector<AsciiDesc> descs(nd);
+    struct Group { int c, at, count, blocks; };
+    std::vector<Group> groups;
+    size_t total = 0;
+    for (size_t k = 0; k < nd; k++) {
+        const AsciiItem& it = items[order[k]];
+        if (groups.empty() || groups.back().c != it.c) groups.push_back(Group{it.c, (int)k, 0, 0});
+        Group& g = groups.back();
+        AsciiDesc& d = descs[k];
+        d = AsciiDesc{};
+        d.d = it.d; d.w = it.w; d.h = it.h; d.step = it.step;
+        d.table = it.wide ? WIDE_AT : NARROW_AT;
+        const int tablelen = (int)std::strlen((const char*)(it.wide ? wide : narrow));
+        d.factor = (float)(256.0 / tablelen);              // impgpu_ascii's expression
+        d.first = g.blocks;
+        d.out_off = (long long)total;
+        total += ((size_t)(it.w + 1) * it.h + 63) & ~size_t(63);
+        g.blocks += (int)(((long long)it.w * it.h + 255) / 256);
+        g.count++;
+    }
+    auto fail_all = [&](int rc) {
+        for (int i : order) codes[i] = rc;
+        return IMP_OK;
+    };
+    const size_t dbytes = (nd * sizeof(AsciiDesc) + 15) & ~size_t(15);
+    std::vector<uint8_t> blob(dbytes + TABLE_BYTES, 0);
+    std::memcpy(blob.data(), descs.data(), nd * sizeof(AsciiDesc));
+    std::memcpy(blob.data() + dbytes + NARROW_AT, narrow, sizeof narrow);
+    std::memcpy(blob.data() + dbytes + WIDE_AT, wide, sizeof wide);
+    void *dev = nullptr, *dout = nullptr, *pin = nullptr, *token = nullptr;
+    if (int rc = stage_begin(total, &pin, &token)) return fail_all(rc);
+    if (int rc = upload_small(blob.data(), blob.size(), &dev, s)) return fail_all(rc);
+    if (int rc = dev_alloc_on(total, &dout, s)) { dev_free_on(dev, s); return fail_all(rc); }
+    bool any = false;
+    for (const Group& g : groups) {
+        const AsciiDesc* dd = (const AsciiDesc*)dev + g.at;
+        const uint8_t* dt = (const uint8_t*)dev + dbytes;
+        const dim3 grid((unsigned)g.blocks), block(256);
+        if (g.c == 4) hipLaunchKernelGGL((k_ascii_mix<4>), grid, block, 0, s, dd, g.count, dt, (uint8_t*)dout);
+        else hipLaunchKernelGGL((k_ascii_mix<3>), grid, block, 0, s, dd, g.count, dt, (uint8_t*)dout);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {
+            set_error("ascii (batch)", e);
+            for (int k = 0; k < g.count; k++) codes[order[(size_t)(g.at + k)]] = IMP_ERROR_DEVICE;
+        } else any = true;
+    }
+    hipError_t e = hipSuccess;
+    if (any) e = hipMemcpyAsync(pin, dout, total, hipMemcpyDeviceToHost, s);
+    dev_free_on(dout, s);
+    dev_free_on(dev, s);
+    if (e != hipSuccess) { set_error("ascii (batch) readback", e); (void)lane_wait(); return fail_all(IMP_ERROR_DEVICE); }
+    stage_hold(token, true);
+    int rc = IMP_OK;
+    if (!on_lane_stream(s)) rc = stream_join_back(s);
+    if (!rc) rc = lane_wait();
+    if (!rc)
+        for (size_t k = 0; k < nd; k++) {
+            const int i = order[k];
+            if (codes[i] == IMP_OK) std::memcpy(items[i].out, (const uint8_t*)pin + descs[k].out_off, (size_t)(items[i].w + 1) * items[i].h - 1);
+        }
+    stage_hold(token, false);
+    if (rc) return fail_all(rc);
     return IMP_OK;
 }
 

@@ -332,6 +332,54 @@ def batch_run_ops(images, configs, jobs):
     return [(codes[i], steps[i]) for i in range(n)], launches.value
 
 
+def _handle(im):
+    """The handle of an Image, a bare handle (c_void_p / int) or None (a NULL entry)."""
+    if im is None:
+        return None
+    h = getattr(im, "h", im)
+    return getattr(h, "value", h)
+
+
+def batch_calc_perceived_brightness(images):
+    """impgpu_batch_calc_perceived_brightness: Image.calc_perceived_brightness of every frame in one call.  An entry may be
+    None (a NULL handle: its code says so).  Returns (values, codes, launches); values[i] is None where codes[i] != 0."""
+    n = len(images)
+    handles = (C.c_void_p * max(1, n))(*[_handle(im) for im in images])
+    vals = (C.c_float * max(1, n))()
+    codes = (C.c_int * max(1, n))()
+    launches = C.c_int()
+    rc = lib.impgpu_batch_calc_perceived_brightness(handles, n, vals, codes, C.byref(launches))
+    if rc:
+        raise ImpError(rc, "impgpu_batch_calc_perceived_brightness")
+    return [vals[i] if codes[i] == 0 else None for i in range(n)], [codes[i] for i in range(n)], launches.value
+
+
+def batch_ascii(images, args=None, capacities=None):
+    """impgpu_batch_ascii: Image.ascii(args[i]) of every frame in one call; the frames are left in HSV.  `args` may be None
+    (all ""), and so may any args[i]; an entry of `images` may be None.  `capacities` (tests) overrides the buffer sizes the
+    call is told.  Returns (texts, codes, launches); texts[i] is None where codes[i] != 0."""
+    n = len(images)
+    if args is not None and len(args) != n:
+        raise ValueError("images and args differ in length")
+    handles = (C.c_void_p * max(1, n))(*[_handle(im) for im in images])
+    cargs = None if args is None else (C.c_char_p * max(1, n))(*[_b(a) for a in args])
+    need = []
+    for im in images:
+        hh, ww = (im.shape[0], im.shape[1]) if im is not None and hasattr(im, "shape") else (0, 0)
+        need.append(max(1, (ww + 1) * hh))
+    bufs = [(C.c_ubyte * k)() for k in need]
+    outs = (C.c_void_p * max(1, n))(*[C.addressof(b) for b in bufs])
+    caps = (C.c_long * max(1, n))(*(need if capacities is None else capacities))
+    lens = (C.c_long * max(1, n))()
+    codes = (C.c_int * max(1, n))()
+    launches = C.c_int()
+    rc = lib.impgpu_batch_ascii(handles, cargs, n, outs, caps, lens, codes, C.byref(launches))
+    if rc:
+        raise ImpError(rc, "impgpu_batch_ascii")
+    texts = [bytes(bufs[i][: lens[i]]) if codes[i] == 0 else None for i in range(n)]
+    return texts, [codes[i] for i in range(n)], launches.value
+
+
 def batch_decode_jpeg(blobs):
     """impgpu_batch_decode_jpeg -> [(code, Image or None)] in the order of `blobs`."""
     n = len(blobs)
