@@ -475,8 +475,10 @@ int impgpu_run_ops(impgpu_image** pointer, const impgpu_job* job, const impgpu_c
  * -> [watermark] -> [flatten] shares launches in rounds: the resizes first, then round k launches the k-th segment of every
  * chain that has one -- a run of pointwise filters (with the watermark and the flatten when it is the last), a blur, or a
  * flip / turn -- one launch per kind and channel count, so the number of launches follows the chains' length, not the
- * number of requests.  Resizes launch_resize_mixed does not gather (integer factors, enlargements) and blurs outside the
- * one-pass forms (large radii) still take a launch per request inside their round.  Albums, gray frames, requests
+ * number of requests.  Bare resizes with whole factors (resizeAreaFast_: 1280x720 or 1920x1080 at 320 wide) share one
+ * launch per channel count too, and so do the NN resizes of `simple` requests.  Resizes launch_resize_mixed does not
+ * gather (enlargements, extreme ratios) and blurs outside the one-pass forms (large radii) still take a launch per
+ * request inside their round.  Albums, gray frames, requests
  * without a resize and requests whose arguments fail (a bad filter, too many filters, a watermark that does not fit) go
  * through impgpu_run_ops inside the call.  A shared launch that fails gives each of its requests IMP_ERROR_DEVICE with the
  * step of the segment it ran.  launches (may be NULL) receives the number of kernels enqueued.  IMP_ERROR_INVALID_ARGS
@@ -549,13 +551,19 @@ int impgpu_batch_cv_resize(const void* src, long long src_frame_stride, int src_
 /* The per-frame Resize() loop of bridge.c:588-604 over frames that all DIFFER in size (BASELINE configs[4], frames already
  * in HBM): each item is cvResize'd with the interpolation Resize() picks for it -- NN when `simple`, CUBIC when either
  * side grows, AREA otherwise (bridge.c:188-192) -- but frames that share a kernel ride in one launch (a descriptor per
- * frame), so a run of thumbnails costs a handful of launches instead of one per request.  Same bytes as calling
- * impgpu_batch_cv_resize once per item.  Nothing is launched if any item is malformed (IMP_ERROR_INVALID_ARGS). */
+ * frame), so a run of thumbnails costs a handful of launches instead of one per request: one for the general AREA
+ * shrinks (BGR / BGRA), one for the AREA shrinks whose two factors are whole numbers (any channel count), one for the NN
+ * frames.  A frame that is the only one of its kind in the call, and what no descriptor launch gathers -- enlargements
+ * (CUBIC), gray general AREA, extreme ratios (cells wider than the row kernels take) -- take one launch each.  Same bytes
+ * as calling impgpu_batch_cv_resize once per item.  Nothing is launched if any item is malformed
+ * (IMP_ERROR_INVALID_ARGS).  The _ex form also reports the number of kernels it enqueued in *launches (may be NULL). */
 typedef struct impgpu_resize_item {
     const void* src; int src_width, src_height, src_step;
     void*       dst; int dst_width, dst_height, dst_step;
 } impgpu_resize_item;
 int impgpu_batch_resize_mixed(const impgpu_resize_item* items, int count, int channels, int simple, void* stream);
+int impgpu_batch_resize_mixed_ex(const impgpu_resize_item* items, int count, int channels, int simple, void* stream,
+                                 int* launches);
 /* cfg3 chain on a batch: resize (AREA/CUBIC by the reference's rule) -> rotate -> watermark.
  * rotate in {0, 90, 180, 270}; config->watermark may be NULL. dst geometry must match. */
 int impgpu_batch_resize_rotate_watermark(const void* src, long long src_frame_stride, int src_width, int src_height, int src_step,

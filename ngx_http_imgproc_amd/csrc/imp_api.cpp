@@ -843,6 +843,11 @@ int impgpu_batch_cv_resize(const void* src, long long src_frame_stride, int src_
 }
 
 int impgpu_batch_resize_mixed(const impgpu_resize_item* items, int count, int channels, int simple, void* stream) {
+    return impgpu_batch_resize_mixed_ex(items, count, channels, simple, stream, nullptr);
+}
+
+int impgpu_batch_resize_mixed_ex(const impgpu_resize_item* items, int count, int channels, int simple, void* stream, int* launches) {
+    if (launches) *launches = 0;
     if (count < 0 || (count > 0 && !items) || (channels != 1 && channels != 3 && channels != 4)) return IMP_ERROR_INVALID_ARGS;
     for (int i = 0; i < count; i++)                                     // (again in the launcher; here so that it answers without a device)
         if (!items[i].src || !items[i].dst || !view_fits(items[i].src_width, items[i].src_height, channels, items[i].src_step) ||
@@ -851,8 +856,11 @@ int impgpu_batch_resize_mixed(const impgpu_resize_item* items, int count, int ch
     if (int rc = need_env()) return rc;
     static_assert(sizeof(MixFrame) == sizeof(impgpu_resize_item) && offsetof(MixFrame, dst) == offsetof(impgpu_resize_item, dst),
                   "MixFrame mirrors impgpu_resize_item");
-    return launch_resize_mixed(reinterpret_cast<const MixFrame*>(items), count, channels, simple,
-                               stream ? (hipStream_t)stream : env_stream());
+    const unsigned long long launched = t_launches;
+    const int rc = launch_resize_mixed(reinterpret_cast<const MixFrame*>(items), count, channels, simple,
+                                       stream ? (hipStream_t)stream : env_stream());
+    if (launches) *launches = (int)(t_launches - launched);
+    return rc;
 }
 
 int impgpu_batch_resize_rotate_watermark(const void* src, long long src_frame_stride, int src_width, int src_height, int src_step,

@@ -1626,16 +1626,16 @@ __global__ __launch_bounds__(256, 5) void k_resize_2x_dma3(RArgs a, const int* _
 }
 
 // ------------------------------------------------------------------ NN
+// (the body is shared with k_resize_nn_mix: `idx` = the destination pixel, `frame` = the frame of a uniform batch)
 template <int CN>
-__global__ __launch_bounds__(256) void k_resize_nn(RArgs a, double scale_x, double scale_y) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void resize_nn_body(const RArgs& a, double scale_x, double scale_y, long long idx, unsigned frame) {
     if (idx >= (long long)a.dw * a.dh) return;
     const int dy = (int)(idx / a.dw), dx = (int)(idx - (long long)dy * a.dw);
     int sx = (int)floor(dx * scale_x), sy = (int)floor(dy * scale_y);
     sx = sx > a.sw - 1 ? a.sw - 1 : sx;
     sy = sy > a.sh - 1 ? a.sh - 1 : sy;
-    const uint8_t* s = a.src + (long long)blockIdx.y * a.src_stride + (size_t)sy * a.sstep + (size_t)sx * CN;
-    uint8_t* d = a.dst + (long long)blockIdx.y * a.dst_stride + (size_t)dy * a.dstep + (size_t)dx * CN;
+    const uint8_t* s = a.src + (long long)frame * a.src_stride + (size_t)sy * a.sstep + (size_t)sx * CN;
+    uint8_t* d = a.dst + (long long)frame * a.dst_stride + (size_t)dy * a.dstep + (size_t)dx * CN;
     if (CN == 4) *(uint32_t*)d = *(const uint32_t*)s;
     else {
 #pragma unroll
@@ -1643,13 +1643,19 @@ __global__ __launch_bounds__(256) void k_resize_nn(RArgs a, double scale_x, doub
     }
 }
 
-// ------------------------------------------------------------------ AREA, integer scales
 template <int CN>
-__global__ __launch_bounds__(256) void k_resize_area_int(RArgs a, int isx, int isy) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
+__global__ __launch_bounds__(256) void k_resize_nn(RArgs a, double scale_x, double scale_y) {
+    resize_nn_body<CN>(a, scale_x, scale_y, (long long)blockIdx.x * 256 + threadIdx.x, blockIdx.y);
+}
+
+// ------------------------------------------------------------------ AREA, integer scales
+// (the bodies of this kernel and of the streaming forms below are shared with k_area_int_mix: `idx` / `gw` = the work
+// item, `frame` = the frame of a uniform batch)
+template <int CN>
+__device__ __forceinline__ void area_int_body(const RArgs& a, int isx, int isy, int idx, unsigned frame) {
     if (idx >= a.dw * a.dh) return;
     const int dy = idx / a.dw, dx = idx - dy * a.dw;
-    const uint8_t* S = a.src + (long long)blockIdx.y * a.src_stride + (size_t)(dy * isy) * a.sstep + (size_t)(dx * isx) * CN;
+    const uint8_t* S = a.src + (long long)frame * a.src_stride + (size_t)(dy * isy) * a.sstep + (size_t)(dx * isx) * CN;
     int sum[CN];
 #pragma unroll
     for (int c = 0; c < CN; c++) sum[c] = 0;
@@ -1665,7 +1671,7 @@ __global__ __launch_bounds__(256) void k_resize_area_int(RArgs a, int isx, int i
             }
         }
     }
-    uint8_t* d = a.dst + (long long)blockIdx.y * a.dst_stride + (size_t)dy * a.dstep + (size_t)dx * CN;
+    uint8_t* d = a.dst + (long long)frame * a.dst_stride + (size_t)dy * a.dstep + (size_t)dx * CN;
     int out[CN];
     if (isx == 2 && isy == 2) {
 #pragma unroll
@@ -1682,6 +1688,11 @@ __global__ __launch_bounds__(256) void k_resize_area_int(RArgs a, int isx, int i
     }
 }
 
+template <int CN>
+__global__ __launch_bounds__(256) void k_resize_area_int(RArgs a, int isx, int isy) {
+    area_int_body<CN>(a, isx, isy, blockIdx.x * 256 + threadIdx.x, blockIdx.y);
+}
+
 // ------------------------------------------------------------------ AREA, exact 2x2 box, streaming form
 // resizeAreaFast_ with both scales 2: (a + b + c + d + 2) >> 2 per channel -- a pure stream (every source byte read
 // once, a quarter as many written), so it is written like a copy: a lane owns FOUR neighbouring destination pixels of a
@@ -1696,12 +1707,11 @@ __device__ __forceinline__ uint32_t box4_swar(uint32_t a, uint32_t b, uint32_t c
     return ((e >> 2) & M) | (((o >> 2) & M) << 8);
 }
 
-__global__ __launch_bounds__(256) void k_area2x2_v4(RArgs a, int qpr) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void area2x2_v4_body(const RArgs& a, int qpr, int idx, unsigned frame) {
     if (idx >= qpr * a.dh) return;
     const int dy = idx / qpr, q = idx - dy * qpr;
-    const uint8_t* S = a.src + (long long)blockIdx.y * a.src_stride + (size_t)(2 * dy) * a.sstep + (size_t)q * 32;
-    uint8_t* D = a.dst + (long long)blockIdx.y * a.dst_stride + (size_t)dy * a.dstep + (size_t)q * 16;
+    const uint8_t* S = a.src + (long long)frame * a.src_stride + (size_t)(2 * dy) * a.sstep + (size_t)q * 32;
+    uint8_t* D = a.dst + (long long)frame * a.dst_stride + (size_t)dy * a.dstep + (size_t)q * 16;
     const int n = min(4, a.dw - 4 * q);
     if (n == 4) {
         uint32_t r0[8], r1[8];
@@ -1722,14 +1732,17 @@ __global__ __launch_bounds__(256) void k_area2x2_v4(RArgs a, int qpr) {
     }
 }
 
+__global__ __launch_bounds__(256) void k_area2x2_v4(RArgs a, int qpr) {
+    area2x2_v4_body(a, qpr, blockIdx.x * 256 + threadIdx.x, blockIdx.y);
+}
+
 // The same for 3-channel frames (every JPEG): four destination pixels = 12 bytes out, 24 bytes in from each of two rows
 // (dwordx4 + dwordx2, 4-byte aligned because 24 q is); source byte 6 j + c (+3 for the right neighbour) of each row.
-__global__ __launch_bounds__(256) void k_area2x2_v3(RArgs a, int qpr) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void area2x2_v3_body(const RArgs& a, int qpr, int idx, unsigned frame) {
     if (idx >= qpr * a.dh) return;
     const int dy = idx / qpr, q = idx - dy * qpr;
-    const uint8_t* S = a.src + (long long)blockIdx.y * a.src_stride + (size_t)(2 * dy) * a.sstep + (size_t)q * 24;
-    uint8_t* D = a.dst + (long long)blockIdx.y * a.dst_stride + (size_t)dy * a.dstep + (size_t)q * 12;
+    const uint8_t* S = a.src + (long long)frame * a.src_stride + (size_t)(2 * dy) * a.sstep + (size_t)q * 24;
+    uint8_t* D = a.dst + (long long)frame * a.dst_stride + (size_t)dy * a.dstep + (size_t)q * 12;
     const int n = min(4, a.dw - 4 * q);
     if (n == 4) {
         uint32_t r0[6], r1[6];
@@ -1755,6 +1768,10 @@ __global__ __launch_bounds__(256) void k_area2x2_v3(RArgs a, int qpr) {
             for (int c = 0; c < 3; c++)
                 D[3 * j + c] = (uint8_t)((p0[6 * j + c] + p0[6 * j + 3 + c] + p1[6 * j + c] + p1[6 * j + 3 + c] + 2) >> 2);
     }
+}
+
+__global__ __launch_bounds__(256) void k_area2x2_v3(RArgs a, int qpr) {
+    area2x2_v3_body(a, qpr, blockIdx.x * 256 + threadIdx.x, blockIdx.y);
 }
 
 // ------------------------------------------------------------------ AREA, other integer scales (3x3, 4x4, 4x3 ...), streaming form
@@ -1852,19 +1869,16 @@ __global__ __launch_bounds__(256) void k_area2x2_c4(RArgs a, int gpr) {
 // rows of that run as contiguous 16-byte granules and adds them up BYTE COLUMN by byte column (two columns per 32-bit
 // add in 16-bit halves), parks the 16-bit column sums in a wave-private LDS line, and then every lane gathers the
 // ISX x CN columns of four destination pixels from that line: box sums are exact integers whatever the order.
-template <int CN, int ISX>
-__global__ __launch_bounds__(256) void k_area_boxl(RArgs a, int isy, int P, int cpr, float scale) {
-    __shared__ __attribute__((aligned(16))) uint32_t s_cols[4][2048];      // 4096 byte columns x 16 bit per wave
+#define BOXL_LINE 2048     // dwords of a wave's LDS line: 4096 byte columns x 16 bit
+template <int CN, int ISX>     // gw = the wave's run (wave-uniform), cols = the wave's LDS line
+__device__ __forceinline__ void area_boxl_body(const RArgs& a, int isy, int P, int cpr, float scale, int gw, unsigned frame, uint32_t* cols) {
     const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int gw = blockIdx.x * 4 + wv;
     if (gw >= cpr * a.dh) return;
     const int dy = gw / cpr, d0 = (gw - dy * cpr) * P;
     const int np = min(P, a.dw - d0);                            // destination pixels of this run
     const int nbytes = np * CN * ISX;                             // source bytes per row
     const int ndw = (nbytes + 3) >> 2;                           // ... in dwords (rows are 4-byte aligned and padded)
-    const uint8_t* S = a.src + (long long)blockIdx.y * a.src_stride + (size_t)(dy * isy) * a.sstep + (size_t)d0 * CN * ISX;
-    uint32_t* cols = s_cols[wv];
+    const uint8_t* S = a.src + (long long)frame * a.src_stride + (size_t)(dy * isy) * a.sstep + (size_t)d0 * CN * ISX;
     const uint32_t M = 0x00ff00ffu;
     uint32_t e[4][4], o[4][4];
 #pragma unroll
@@ -1901,7 +1915,7 @@ __global__ __launch_bounds__(256) void k_area_boxl(RArgs a, int isy, int P, int 
         *(u32x4a_t*)(cols + g * 8 + 4) = hi;
     }
     asm volatile("" ::: "memory");
-    uint8_t* D = a.dst + (long long)blockIdx.y * a.dst_stride + (size_t)dy * a.dstep + (size_t)d0 * CN;
+    uint8_t* D = a.dst + (long long)frame * a.dst_stride + (size_t)dy * a.dstep + (size_t)d0 * CN;
     for (int q = lane; q * 4 < np; q += 64) {                    // four destination pixels = 4 * CN * ISX columns, two per dword
         uint32_t r[2 * CN * ISX];
         typedef unsigned int u32x2a_t __attribute__((ext_vector_type(2), aligned(8)));
@@ -1935,6 +1949,13 @@ __global__ __launch_bounds__(256) void k_area_boxl(RArgs a, int isy, int P, int 
             for (int bidx = 0; bidx < (np - q * 4) * CN; bidx++) dq[bidx] = (uint8_t)(out[bidx >> 2] >> (8 * (bidx & 3)));
         }
     }
+}
+
+template <int CN, int ISX>
+__global__ __launch_bounds__(256) void k_area_boxl(RArgs a, int isy, int P, int cpr, float scale) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_cols[4][BOXL_LINE];
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    area_boxl_body<CN, ISX>(a, isy, P, cpr, scale, blockIdx.x * 4 + wv, blockIdx.y, s_cols[wv]);
 }
 
 // ------------------------------------------------------------------ AREA, general (float tables)
@@ -2566,6 +2587,62 @@ __global__ __launch_bounds__(256) void k_resize_area_mix_tail(const MixTailDesc*
 #undef IMP_TAIL_W
         default: area_rows_body<CN, 20, true>(m.a, m.gm, 0, item, m.nstrips, m.rows, s_line[wv], t.tail, s_tile[wv], flat); break;
     }
+}
+
+// ------------------------------------------------------------------ whole-factor AREA and NN over frames of DIFFERENT geometry
+// resizeAreaFast_ (both factors integers: 640x480, 1280x720, 1920x1080 ... at 320 wide) for a run of requests in one
+// launch: the descriptor scheme of k_resize_area_mix around the bodies of the lone kernels above, so the bytes are the
+// lone launch's.  A descriptor names its body (block-uniform: scalar branches) and how that body splits the frame:
+//   IM_2X2    k_area2x2_v4 / k_area2x2_v3: a lane per four destination pixels, per_row = lanes per destination row
+//   IM_BOXL   k_area_boxl<CN, isx>, isx = 2..8, at most 257 source pixels a box, 4-byte aligned rows and pointers:
+//             a wave per run of P destination pixels, per_row = runs per destination row.  BGRA 8x, which alone runs
+//             k_area_boxc<8>, takes area_boxl_body<4, 8> here: with it the BGRA kernel wanted 65 VGPRs (7 waves per
+//             SIMD against BGR's 8), so the kernel is bounded to 8 waves -- 63 VGPRs, no scratch.
+//   IM_PIXEL  k_resize_area_int: a lane per destination pixel -- factors of 1 or above 8, boxes over 257 pixels, BGR
+//             rows that are not 4-byte aligned, gray
+// The wave-private LDS lines of IM_BOXL are dynamic: a launch without such a frame asks for none.
+enum { IM_PIXEL = 0, IM_2X2 = 1, IM_BOXL = 2 };
+struct IntMixDesc { RArgs a; int isx, isy, cls, per_row, P, first, nblk; float scale; };
+
+template <int CN>
+__global__ __launch_bounds__(256, 8) void k_area_int_mix(const IntMixDesc* __restrict__ d, MixIndex ix) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_int_mix[];      // IM_BOXL: 4 lines of BOXL_LINE dwords
+    int blk;
+    const int di = mix_pick(d, ix, &blk);
+    if (di < 0) return;
+    const IntMixDesc& m = d[di];
+    if constexpr (CN != 1) {
+        if (m.cls == IM_BOXL) {
+            const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+            uint32_t* cols = s_int_mix + wv * BOXL_LINE;
+            const int gw = blk * 4 + wv;
+            switch (m.isx) {
+#define IMP_BOXL(I_) case I_: area_boxl_body<CN, I_>(m.a, m.isy, m.P, m.per_row, m.scale, gw, 0, cols); break;
+                IMP_BOXL(2) IMP_BOXL(3) IMP_BOXL(4) IMP_BOXL(5) IMP_BOXL(6) IMP_BOXL(7)
+#undef IMP_BOXL
+                default: area_boxl_body<CN, 8>(m.a, m.isy, m.P, m.per_row, m.scale, gw, 0, cols); break;
+            }
+            return;
+        }
+        if (m.cls == IM_2X2) {
+            if constexpr (CN == 4) area2x2_v4_body(m.a, m.per_row, blk * 256 + (int)threadIdx.x, 0);
+            else area2x2_v3_body(m.a, m.per_row, blk * 256 + (int)threadIdx.x, 0);
+            return;
+        }
+    }
+    area_int_body<CN>(m.a, m.isx, m.isy, blk * 256 + (int)threadIdx.x, 0);
+}
+
+// cvResize INTER_NN (the `simple` requests: GIF answers) the same way: k_resize_nn's body per destination pixel.
+struct NnMixDesc { RArgs a; double scale_x, scale_y; int first, nblk; };
+
+template <int CN>
+__global__ __launch_bounds__(256) void k_resize_nn_mix(const NnMixDesc* __restrict__ d, MixIndex ix) {
+    int blk;
+    const int di = mix_pick(d, ix, &blk);
+    if (di < 0) return;
+    const NnMixDesc& m = d[di];
+    resize_nn_body<CN>(m.a, m.scale_x, m.scale_y, (long long)blk * 256 + threadIdx.x, 0);
 }
 
 // ------------------------------------------------------------------ per-geometry table cache
@@ -3310,9 +3387,10 @@ int launch_cv_resize(const Frames& f, int interp, hipStream_t s) {
 
 // Resize() over `count` frames of different geometry with as few launches as the mix allows.  Per frame the
 // interpolation is the reference's (bridge.c:183-193) and the arithmetic is launch_cv_resize's: frames that take the
-// general AREA path (every non-integer shrink whose cells span at most 16 source columns) are gathered into descriptor
-// launches, one per window width class, with their weights computed in the kernel; the rest (integer factors,
-// enlargements, NN, extreme ratios) go one launch each on the same stream.
+// general AREA path (every non-integer shrink whose cells span at most 16 source columns) are gathered into a descriptor
+// launch with their weights computed in the kernel, whole-factor AREA frames (any channel count) into a k_area_int_mix
+// launch and NN frames into a k_resize_nn_mix launch; a frame that is the only one of its kind, and the rest
+// (enlargements, gray general AREA, extreme ratios) go one launch each on the same stream.
 // Blocks differ a hundredfold in work (a 4K source against a 256-pixel one, same 224-wide output): the frames go
 // longest first to the XCD list with the least source bytes so far, so each list starts with its heavy frames and
 // the launch's tail is made of light ones.  `v` is consumed; *sorted holds the descriptors list by list, *most = the
@@ -3339,6 +3417,77 @@ static int launch_mix(std::vector<MixDesc>& v, int cn, hipStream_t s) {
     return IMP_OK;
 }
 
+// The descriptor of one whole-factor AREA frame.  Its body is the one launch_cn picks for the frame alone, with three
+// exceptions (same bytes, the bodies being generic in CN and ISX): BGRA 2 x k (k != 2) and BGRA 8 x k run
+// area_boxl_body<4, 2> / <4, 8>, instances no lone kernel has (alone: k_resize_area_int, k_area_boxc<8>), and BGRA 2 x 2
+// of an even width runs k_area2x2_v4's body, not k_area2x2_c4's.
+static IntMixDesc int_mix_desc(const MixFrame& f, int cn, int isx, int isy) {
+    IntMixDesc d{};
+    d.a = RArgs{f.src, 0, f.sstep, f.sw, f.sh, f.dst, 0, f.dstep, f.dw, f.dh};
+    d.isx = isx;
+    d.isy = isy;
+    d.scale = 1.f / (float)(isx * isy);
+    const bool rows4 = !(((uintptr_t)f.src | (uintptr_t)f.dst | (uintptr_t)f.sstep | (uintptr_t)f.dstep) & 3);
+    if (cn != 1 && rows4 && isx == 2 && isy == 2) {
+        d.cls = IM_2X2;
+        d.per_row = (f.dw + 3) / 4;
+        d.nblk = (int)(((long long)d.per_row * f.dh + 255) / 256);
+    } else if (cn != 1 && rows4 && isx >= 2 && isx <= 8 && (long long)isx * isy <= 257) {
+        d.cls = IM_BOXL;
+        d.P = (4096 / (cn * isx)) & ~3;
+        d.per_row = (f.dw + d.P - 1) / d.P;
+        d.nblk = (int)(((long long)d.per_row * f.dh + 3) / 4);
+    } else {
+        d.cls = IM_PIXEL;
+        d.nblk = (int)(((long long)f.dw * f.dh + 255) / 256);
+    }
+    return d;
+}
+
+// Deals the descriptors (longest source first) and uploads the table; the caller launches over *grid and frees *dev on `s`.
+template <class D>
+static int mix_table(std::vector<D>& v, hipStream_t s, void** dev, MixIndex* ix, dim3* grid) {
+    std::vector<D> sorted;
+    int most = 0;
+    imp::mix_deal(v, [](D& d) -> D& { return d; }, [](D& d) { return (long long)d.a.sw * d.a.sh; }, &sorted, ix, &most);
+    if (int rc = upload_small(sorted.data(), sorted.size() * sizeof(D), dev, s)) return rc;
+    *grid = dim3((unsigned)most * 8);
+    return IMP_OK;
+}
+
+static int launch_int_mix(std::vector<IntMixDesc>& v, int cn, hipStream_t s) {
+    size_t lds = 0;                                        // the largest any class present needs
+    for (const IntMixDesc& d : v)
+        if (d.cls == IM_BOXL) lds = 4 * BOXL_LINE * sizeof(uint32_t);
+    void* dev = nullptr;
+    MixIndex ix{};
+    dim3 grid;
+    if (int rc = mix_table(v, s, &dev, &ix, &grid)) return rc;
+    const dim3 block(256);
+    if (cn == 4) hipLaunchKernelGGL((k_area_int_mix<4>), grid, block, lds, s, (const IntMixDesc*)dev, ix);
+    else if (cn == 3) hipLaunchKernelGGL((k_area_int_mix<3>), grid, block, lds, s, (const IntMixDesc*)dev, ix);
+    else hipLaunchKernelGGL((k_area_int_mix<1>), grid, block, lds, s, (const IntMixDesc*)dev, ix);
+    const hipError_t e = hipGetLastError();
+    dev_free_on(dev, s);
+    IMP_HIP(e);
+    return IMP_OK;
+}
+
+static int launch_nn_mix(std::vector<NnMixDesc>& v, int cn, hipStream_t s) {
+    void* dev = nullptr;
+    MixIndex ix{};
+    dim3 grid;
+    if (int rc = mix_table(v, s, &dev, &ix, &grid)) return rc;
+    const dim3 block(256);
+    if (cn == 4) hipLaunchKernelGGL((k_resize_nn_mix<4>), grid, block, 0, s, (const NnMixDesc*)dev, ix);
+    else if (cn == 3) hipLaunchKernelGGL((k_resize_nn_mix<3>), grid, block, 0, s, (const NnMixDesc*)dev, ix);
+    else hipLaunchKernelGGL((k_resize_nn_mix<1>), grid, block, 0, s, (const NnMixDesc*)dev, ix);
+    const hipError_t e = hipGetLastError();
+    dev_free_on(dev, s);
+    IMP_HIP(e);
+    return IMP_OK;
+}
+
 int launch_resize_mixed(const MixFrame* fr, int count, int cn, int simple, hipStream_t s) {
     if (count <= 0) return IMP_OK;
     if (!fr || (cn != 1 && cn != 3 && cn != 4)) return IMP_ERROR_INVALID_ARGS;
@@ -3348,13 +3497,40 @@ int launch_resize_mixed(const MixFrame* fr, int count, int cn, int simple, hipSt
         if (cn == 4 && (((uintptr_t)f.src | (uintptr_t)f.dst | (uintptr_t)f.sstep | (uintptr_t)f.dstep) & 3)) return IMP_ERROR_INVALID_ARGS;
     }
     std::vector<MixDesc> gathered_frames;
+    std::vector<IntMixDesc> int_frames;                    // whole-factor AREA (resizeAreaFast_), any channel count
+    std::vector<NnMixDesc> nn_frames;
+    int int_one = -1, nn_one = -1;                         // the frame of a vector that holds exactly one
     gathered_frames.reserve(count);
+    auto lone = [&](const MixFrame& f, int interp) {
+        Frames one{};
+        one.src = f.src; one.src_stride = 0; one.v = View{f.src, f.sw, f.sh, cn, f.sstep};
+        one.dst = f.dst; one.dst_stride = 0; one.dw = f.dw; one.dh = f.dh; one.dstep = f.dstep; one.count = 1;
+        return launch_cv_resize(one, interp, s);
+    };
     for (int i = 0; i < count; i++) {
         const MixFrame& f = fr[i];
         const int interp = simple ? IMP_INTER_NN : ((f.dw > f.sw || f.dh > f.sh) ? IMP_INTER_CUBIC : IMP_INTER_AREA);   // bridge.c:188-192
         const double scale_x = 1. / ((double)f.dw / f.sw), scale_y = 1. / ((double)f.dh / f.sh);
         const bool whole = std::fabs(scale_x - std::lrint(scale_x)) < 2.220446049250313e-16 &&
                            std::fabs(scale_y - std::lrint(scale_y)) < 2.220446049250313e-16;
+        if (interp == IMP_INTER_NN) {
+            NnMixDesc d{};
+            d.a = RArgs{f.src, 0, f.sstep, f.sw, f.sh, f.dst, 0, f.dstep, f.dw, f.dh};
+            d.scale_x = scale_x;
+            d.scale_y = scale_y;
+            d.nblk = (int)(((long long)f.dw * f.dh + 255) / 256);
+            nn_frames.push_back(d);
+            nn_one = i;
+            continue;
+        }
+        if (interp == IMP_INTER_AREA && whole) {
+            const int isx = (int)std::lrint(scale_x), isy = (int)std::lrint(scale_y);
+            if ((long long)isx * f.dw == f.sw && (long long)isy * f.dh == f.sh) {      // (what `whole` means; the bodies' reads rest on it)
+                int_frames.push_back(int_mix_desc(f, cn, isx, isy));
+                int_one = i;
+                continue;
+            }
+        }
         bool gathered = false;
         if (interp == IMP_INTER_AREA && !whole && cn != 1) {
             MixDesc d{};
@@ -3391,12 +3567,19 @@ int launch_resize_mixed(const MixFrame* fr, int count, int cn, int simple, hipSt
             }
             if (gathered) gathered_frames.push_back(d);
         }
-        if (!gathered) {
-            Frames one{};
-            one.src = f.src; one.src_stride = 0; one.v = View{f.src, f.sw, f.sh, cn, f.sstep};
-            one.dst = f.dst; one.dst_stride = 0; one.dw = f.dw; one.dh = f.dh; one.dstep = f.dstep; one.count = 1;
-            if (int rc = launch_cv_resize(one, interp, s)) return rc;
-        }
+        if (!gathered)
+            if (int rc = lone(f, interp)) return rc;
+    }
+    // a vector of one keeps the lone launch and its tuned kernel; two or more share a descriptor launch
+    if (int_frames.size() == 1) {
+        if (int rc = lone(fr[int_one], IMP_INTER_AREA)) return rc;
+    } else if (!int_frames.empty()) {
+        if (int rc = launch_int_mix(int_frames, cn, s)) return rc;
+    }
+    if (nn_frames.size() == 1) {
+        if (int rc = lone(fr[nn_one], IMP_INTER_NN)) return rc;
+    } else if (!nn_frames.empty()) {
+        if (int rc = launch_nn_mix(nn_frames, cn, s)) return rc;
     }
     return launch_mix(gathered_frames, cn, s);
 }

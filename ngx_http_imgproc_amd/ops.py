@@ -720,10 +720,15 @@ class ResizeItem(C.Structure):
                 ("dst", C.c_void_p), ("dst_width", C.c_int), ("dst_height", C.c_int), ("dst_step", C.c_int)]
 
 
-def batch_resize_mixed(items, channels, simple=False, stream=None):
-    """items: [(src_ptr, sw, sh, sstep, dst_ptr, dw, dh, dstep)] of frames resident in HBM; returns the IMP_* code."""
+def batch_resize_mixed(items, channels, simple=False, stream=None, count_launches=False):
+    """items: [(src_ptr, sw, sh, sstep, dst_ptr, dw, dh, dstep)] of frames resident in HBM; returns the IMP_* code, or
+    (code, kernels enqueued) with count_launches=True."""
     arr = (ResizeItem * len(items))(*[ResizeItem(*it) for it in items])
-    return lib.impgpu_batch_resize_mixed(arr, len(items), channels, int(simple), C.c_void_p(stream or 0))
+    if not count_launches:
+        return lib.impgpu_batch_resize_mixed(arr, len(items), channels, int(simple), C.c_void_p(stream or 0))
+    launches = C.c_int(-1)
+    rc = lib.impgpu_batch_resize_mixed_ex(arr, len(items), channels, int(simple), C.c_void_p(stream or 0), C.byref(launches))
+    return rc, launches.value
 
 
 def batch_resize_rotate_watermark(src_ptr, src_stride, sw, sh, sstep, dst_ptr, dst_stride, dstep, rw, rh, rotate,
