@@ -126,7 +126,7 @@ int do_watermark(Work& wk, const impgpu_config* cfg) {
 }
 
 // What impgpu_batch_run_ops needs to know to run a request in shared launches instead of through impgpu_run_ops: a single
-// colour frame whose chain is [crop ->] resize -> any filters -> [watermark] -> [flatten], every decision made here on the
+// colour or gray frame whose chain is [crop ->] resize -> any filters -> [watermark] -> [flatten], every decision made here on the
 // host.  Host-only, no fault point entered: a request this refuses goes to impgpu_run_ops whole.
 // The resize is launch_resize_mixed, or the row-streaming AREA kernel with a tail on its stores (k_resize_area_mix_tail,
 // the one acceptance test area_tail_plan) when something rides there: the first filter when it is a turn, as impgpu_run_ops
@@ -152,6 +152,7 @@ struct ChainPlan {
     bool fold_wm, fold_flat;    // the tail (watermark, flatten) folded onto the resize's stores
     std::vector<Segment> segs;
     OverlayArgs wm;             // the overlay's placement on the final frame
+    bool gray;                  // a gray frame: resized as gray, promoted (bridge.c:613-618), then a BGR frame's segments
 };
 
 static bool bgra_overlay(const impgpu_image* ov) {                    // what the resize tail's overlay path takes
@@ -159,7 +160,7 @@ static bool bgra_overlay(const impgpu_image* ov) {                    // what th
 }
 
 bool chain_plan(const impgpu_image* im, const impgpu_job* job, const impgpu_config* cfg, ChainPlan* p) {
-    if (!im || !job || !cfg || im->frames != 1 || (im->c != 3 && im->c != 4) || !job->resize || job->filter_count < 0) return false;
+    if (!im || !job || !cfg || im->frames != 1 || (im->c != 1 && im->c != 3 && im->c != 4) || !job->resize || job->filter_count < 0) return false;
     if (cfg->max_filters_count > 0 && job->filter_count > cfg->max_filters_count) return false;
     if (job->filter_count > 0 && !job->filters) return false;
     for (int i = 0; i < job->filter_count; i++) if (!job->filters[i]) return false;
@@ -171,15 +172,19 @@ bool chain_plan(const impgpu_image* im, const impgpu_job* job, const impgpu_conf
     }
     int w, h, interp;
     if (resize_geometry(v.w, v.h, job->resize, cfg->max_target_w, cfg->max_target_h, job->simple, &w, &h, &interp) != IMP_OK) return false;
-    const int c = v.c;
+    // a gray frame is BGR from the filtering step on (impgpu_run_ops promotes it there): its filters and its overlay are
+    // planned for 3 channels, and nothing rides its resize -- impgpu_run_ops fuses no turn into a gray resize either
+    const bool gray = v.c == 1;
+    const int c = gray ? 3 : v.c;
     const impgpu_image* ov = cfg->watermark;
+    p->gray = gray;
     p->v = v; p->w = w; p->h = h; p->interp = interp; p->rot = 0;
     p->wm_turn = p->fold_wm = p->fold_flat = false;
     p->wm = OverlayArgs{};
     p->segs.clear();
     // does the AREA kernel with a tail take this resize, turned by `rot`?
     auto tail_takes = [&](int rot) {
-        if (interp != IMP_INTER_AREA) return false;
+        if (interp != IMP_INTER_AREA || gray) return false;
         const bool swap = rot == 90 || rot == 270;
         Frames f{};
         f.src = v.d; f.v = v; f.dw = w; f.dh = h; f.dstep = aligned_step(swap ? h : w, c); f.count = 1;
@@ -187,7 +192,7 @@ bool chain_plan(const impgpu_image* im, const impgpu_job* job, const impgpu_conf
         return area_tail_plan(f, &ww, &bh);
     };
     int cw = w, ch = h, i0 = 0;
-    if (job->filter_count >= 1 && interp == IMP_INTER_AREA) {          // impgpu_run_ops' first-filter rule
+    if (job->filter_count >= 1 && interp == IMP_INTER_AREA && !gray) { // impgpu_run_ops' first-filter rule
         FilterPlan first;
         PixelProgram none;
         if (filter_plan(job->filters[0], cfg->allow_experiments, c, w, h, &first, &none) == IMP_OK && first.cls == FC_ROTATE &&
@@ -663,11 +668,14 @@ int impgpu_batch_run_ops(impgpu_image** images, const impgpu_job* jobs, const im
     }
     const unsigned long long launched = t_launches;
     hipStream_t s = env_stream();
-    // per channel count (index c - 3): requests with a tail -> k_resize_area_mix_tail, bare resizes -> launch_resize_mixed
-    // (NN resizes of `simple` requests: a launch_resize_mixed of their own)
+    // per channel count (slot c - 3, gray: slot 2): requests with a tail -> k_resize_area_mix_tail, bare resizes ->
+    // launch_resize_mixed (NN resizes of `simple` requests: a launch_resize_mixed of their own).  Gray has no tails.
+    static const int slot_cn[3] = {3, 4, 1};
     std::vector<TailItem> tails[2];
-    std::vector<MixFrame> bares[2], nns[2];
-    std::vector<int> tail_who[2], bare_who[2], nn_who[2];
+    std::vector<MixFrame> bares[3], nns[3];
+    std::vector<int> tail_who[2], bare_who[3], nn_who[3];
+    std::vector<int> promote_who;                                      // gray requests that reach the promotion
+    std::vector<char> resized((size_t)count, 0);
     std::vector<impgpu_image*> outs((size_t)count, nullptr);
     std::vector<int> final_code((size_t)count, IMP_OK), final_step((size_t)count, IMP_STEP_INFO);
     std::vector<ChainPlan> chains((size_t)count);
@@ -688,7 +696,7 @@ int impgpu_batch_run_ops(impgpu_image** images, const impgpu_job* jobs, const im
         steps[i] = IMP_STEP_RESIZE;
         if (fault_hit(IMP_STEP_RESIZE)) continue;
         int failed = -1;
-        if (job->filter_count > 0 && fault_hit(IMP_STEP_FILTERING)) failed = IMP_STEP_FILTERING;
+        if ((cp.gray || job->filter_count > 0) && fault_hit(IMP_STEP_FILTERING)) failed = IMP_STEP_FILTERING;   // (a gray frame enters it for its promotion)
         else if (cfg->watermark && fault_hit(IMP_STEP_WATERMARK)) failed = IMP_STEP_WATERMARK;
         int n = (int)cp.segs.size();
         if (failed >= 0) {
@@ -710,7 +718,8 @@ int impgpu_batch_run_ops(impgpu_image** images, const impgpu_job* jobs, const im
         impgpu_image* out = nullptr;
         if (int rc = image_new_album(cp.fw, cp.fh, cp.v.c, 1, &out)) { codes[i] = rc; nsegs[(size_t)i] = 0; continue; }   // (as Work::fresh)
         outs[(size_t)i] = out;
-        const int k = images[i]->c - 3;
+        const int k = cp.gray ? 2 : images[i]->c - 3;
+        if (cp.gray && failed != IMP_STEP_FILTERING) promote_who.push_back(i);     // (failed there: it keeps the resized gray frame)
         const bool on_stores = cp.wm_turn || cp.fold_wm;
         if (cp.rot || on_stores || cp.fold_flat) {
             tails[k].push_back(TailItem{cp.v, out->d, cp.w, cp.h, out->step, cp.rot, on_stores, on_stores ? cp.wm : OverlayArgs{}, cp.fold_flat});
@@ -739,12 +748,13 @@ int impgpu_batch_run_ops(impgpu_image** images, const impgpu_job* jobs, const im
             outs[(size_t)i] = nullptr;
             codes[i] = final_code[(size_t)i];
             steps[i] = final_step[(size_t)i];
+            resized[(size_t)i] = 1;
         }
     };
-    for (int k = 0; k < 2; k++) {
-        if (!bares[k].empty()) settle(bare_who[k], launch_resize_mixed(bares[k].data(), (int)bares[k].size(), k + 3, 0, s));
-        if (!nns[k].empty()) settle(nn_who[k], launch_resize_mixed(nns[k].data(), (int)nns[k].size(), k + 3, 1, s));
-        if (!tails[k].empty()) settle(tail_who[k], launch_area_tail_mixed(tails[k].data(), (int)tails[k].size(), k + 3, s));
+    for (int k = 0; k < 3; k++) {
+        if (!bares[k].empty()) settle(bare_who[k], launch_resize_mixed(bares[k].data(), (int)bares[k].size(), slot_cn[k], 0, s));
+        if (!nns[k].empty()) settle(nn_who[k], launch_resize_mixed(nns[k].data(), (int)nns[k].size(), slot_cn[k], 1, s));
+        if (k < 2 && !tails[k].empty()) settle(tail_who[k], launch_area_tail_mixed(tails[k].data(), (int)tails[k].size(), k + 3, s));
     }
     // rounds 1 ..: segment r of every chain that has one, one launch per (kind, channel count) -- and the blur forms no mixed
     // kernel takes one request at a time.  Barriers write fresh frames (pool memory, released in stream order behind the
@@ -754,6 +764,35 @@ int impgpu_batch_run_ops(impgpu_image** images, const impgpu_job* jobs, const im
         steps[i] = step;
         nsegs[(size_t)i] = 0;
     };
+    // the promotion of every gray request whose resize went through (bridge.c:613-618), ONE launch: fresh BGR frames, the
+    // gray ones released in stream order.  A failure is reported as impgpu_run_ops reports its launch_gray2bgr: at
+    // IMP_STEP_FILTERING, the request keeping its resized gray frame.  From here on the frames are BGR requests' frames.
+    {
+        std::vector<Gray2BgrItem> g2b;
+        std::vector<int> g2b_who;
+        for (int i : promote_who) {
+            impgpu_image* cur = images[i];
+            if (!resized[(size_t)i]) continue;                          // (its resize launch failed)
+            impgpu_image* out = nullptr;
+            if (int rc = image_new_album(cur->w, cur->h, 3, 1, &out)) { fail(i, rc, IMP_STEP_FILTERING); continue; }
+            outs[(size_t)i] = out;
+            g2b.push_back(Gray2BgrItem{cur->d, out->d, cur->w, cur->h, cur->step, out->step});
+            g2b_who.push_back(i);
+        }
+        if (!g2b.empty()) {
+            const int rc = launch_gray2bgr_mixed(g2b.data(), (int)g2b.size(), s);
+            for (int i : g2b_who) {
+                if (rc != IMP_OK) {
+                    image_delete(outs[(size_t)i]);
+                    fail(i, IMP_ERROR_DEVICE, IMP_STEP_FILTERING);
+                } else {
+                    image_delete(images[i]);
+                    images[i] = outs[(size_t)i];
+                }
+                outs[(size_t)i] = nullptr;
+            }
+        }
+    }
     for (size_t r = 0; r < rounds; r++) {
         std::vector<PixelTailItem> pix[2];
         std::vector<GeomItem> geo[2];

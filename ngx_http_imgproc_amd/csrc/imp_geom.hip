@@ -375,6 +375,75 @@ int launch_geom_mixed(const GeomItem* items, int count, int cn, hipStream_t s) {
     return IMP_OK;
 }
 
+// ---- cvCvtColor(GRAY2BGR) of frames of different geometry (the gray requests of impgpu_batch_run_ops) ----
+// k_gray2bgr's bytes through a descriptor per frame: a lane takes four adjacent pixels of one row -- one dword in, three
+// out when both rows are 4-byte aligned (pool frames are), bytes otherwise and at a row's ragged end.
+#define G2B_GROUPS (256 * 4)                               // groups of four pixels a workgroup covers
+struct Gray2BgrDesc {
+    const uint8_t* src; uint8_t* dst;
+    int w, h, sstep, dstep;
+    int first, nblk;
+};
+
+__global__ __launch_bounds__(256) void k_gray2bgr_mix(const Gray2BgrDesc* __restrict__ descs, MixIndex ix) {
+    int blk;
+    const int di = mix_pick(descs, ix, &blk);
+    if (di < 0) return;
+    const Gray2BgrDesc* m = descs + di;
+    const int w = m->w, gpr = (w + 3) >> 2;                // groups per row
+    const long long ngroups = (long long)gpr * m->h;
+    const bool words = !(((uintptr_t)m->src | (uintptr_t)m->dst | (uintptr_t)m->sstep | (uintptr_t)m->dstep) & 3);
+    const long long first = (long long)blk * G2B_GROUPS + threadIdx.x;
+#pragma unroll 1
+    for (int it = 0; it < G2B_GROUPS / 256; it++) {
+        const long long idx = first + (long long)it * 256;
+        if (idx >= ngroups) break;
+        const int y = (int)(idx / gpr), x = (int)(idx - (long long)y * gpr) * 4;
+        const uint8_t* sp = m->src + (size_t)y * m->sstep + x;
+        uint8_t* d = m->dst + (size_t)y * m->dstep + (size_t)x * 3;
+        if (words && x + 4 <= w) {
+            const uint32_t v = *(const uint32_t*)sp;
+            const uint32_t b0 = v & 0xff, b1 = (v >> 8) & 0xff, b2 = (v >> 16) & 0xff, b3 = v >> 24;
+            uint32_t* q = (uint32_t*)d;
+            q[0] = b0 * 0x010101u | (b1 << 24);
+            q[1] = b1 * 0x0101u | (b2 * 0x01010000u);
+            q[2] = b2 | (b3 * 0x01010100u);
+        } else {
+            const int n = min(4, w - x);
+            for (int k = 0; k < n; k++) {
+                const uint8_t g = sp[k];
+                d[3 * k] = g; d[3 * k + 1] = g; d[3 * k + 2] = g;
+            }
+        }
+    }
+}
+
+int launch_gray2bgr_mixed(const Gray2BgrItem* items, int count, hipStream_t s) {
+    if (count <= 0) return IMP_OK;
+    if (!items) return IMP_ERROR_INVALID_ARGS;
+    std::vector<Gray2BgrDesc> v;
+    v.reserve((size_t)count);
+    for (int i = 0; i < count; i++) {                      // nothing is launched unless every item is well-formed
+        const Gray2BgrItem& it = items[i];
+        if (!it.src || !it.dst || !view_fits(it.w, it.h, 1, it.sstep) || !view_fits(it.w, it.h, 3, it.dstep)) return IMP_ERROR_INVALID_ARGS;
+        Gray2BgrDesc d{};
+        d.src = it.src; d.dst = it.dst; d.w = it.w; d.h = it.h; d.sstep = it.sstep; d.dstep = it.dstep;
+        d.nblk = (int)(((long long)((it.w + 3) / 4) * it.h + G2B_GROUPS - 1) / G2B_GROUPS);
+        v.push_back(d);
+    }
+    std::vector<Gray2BgrDesc> sorted;
+    MixIndex ix{};
+    int most = 0;
+    mix_deal(v, [](Gray2BgrDesc& d) -> Gray2BgrDesc& { return d; }, [](Gray2BgrDesc& d) { return (long long)d.w * d.h; }, &sorted, &ix, &most);
+    void* dev = nullptr;
+    if (int rc = upload_small(sorted.data(), sorted.size() * sizeof(Gray2BgrDesc), &dev, s)) return rc;
+    hipLaunchKernelGGL(k_gray2bgr_mix, dim3((unsigned)most * 8), dim3(256), 0, s, (const Gray2BgrDesc*)dev, ix);
+    const hipError_t e = hipGetLastError();
+    dev_free_on(dev, s);
+    IMP_HIP(e);
+    return IMP_OK;
+}
+
 int launch_gray2bgr(const Frames& f, hipStream_t s) {
     if (f.count <= 0) return IMP_OK;
     if (f.v.c != 1 || f.dw != f.v.w || f.dh != f.v.h || f.count > 65535) return IMP_ERROR_INVALID_ARGS;

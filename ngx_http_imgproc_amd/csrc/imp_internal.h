@@ -379,6 +379,9 @@ void split_program(const PixelProgram& prog, std::vector<PixelProgram>* parts);
 // imp_geom.hip: cvFlip (kind 0, mode = flip mode) or a quarter / half turn (kind 1, mode = 90 / 180 / 270) into a fresh frame
 struct GeomItem { const uint8_t* src; int sw, sh, sstep; uint8_t* dst; int dw, dh, dstep; int kind, mode; };
 int launch_geom_mixed(const GeomItem* items, int count, int channels, hipStream_t s);
+// imp_geom.hip: cvCvtColor(GRAY2BGR) of many gray frames into fresh 3-channel frames of the same size, ONE launch
+struct Gray2BgrItem { const uint8_t* src; uint8_t* dst; int w, h, sstep, dstep; };
+int launch_gray2bgr_mixed(const Gray2BgrItem* items, int count, hipStream_t s);
 // imp_blur.hip: which form launch_gaussian_fused gives a frame of this geometry and sigma -- BLUR_MIXABLE when it is one of
 // the one-pass forms k_blur_mix takes (k_blur_fused4, k_blur_mfma_fused), BLUR_LONE for the others.  `aligned`: the
 // dword alignment launch_gaussian_fused asks of BGRA pointers and steps holds.

@@ -2502,12 +2502,141 @@ __global__ __launch_bounds__(256) void k_resize_area_rows4(RArgs a, AreaGeom gm,
     if (item < nitems) area_rows4_body<CN, W>(a, gm, frame, item, nstrips, bh, s_line[wv]);
 }
 
+// Gray frames (one byte a pixel): the same walk with windows counted in BYTES.  A lane owns P adjacent destination columns
+// (P = 4 while the windows are at most five pixels, as above; P = 1 past that), a wave 64 * P.  Nothing is asked of the
+// source: a crop window starts at any byte and a gray pitch is any number, so every source row is fetched as the ALIGNED
+// 16-byte granules that cover the wave's segment of it -- contiguous, 1 KB per instruction, and an aligned granule that
+// holds one byte of the frame never leaves the frame's pages -- and the segment's offset inside its first granule (`dl`,
+// the same for the whole wave, different from row to row when the pitch is no multiple of 16) is added to every window's
+// place in the parked line.  Windows are read as aligned dwords + v_alignbyte_b32, like the BGR body's.
+// The launcher (gray_rows_plan) guarantees 64 * P lanes' windows plus the 30 bytes of granule rounding fit NV KB.
+constexpr int GRAY_W_MAX = 4 * MIX_NV;                         // the widest window, as for colour
+constexpr int gray_rows_nv(int w, int p) { return (64 * p * w + 30 + 1023) / 1024; }
+constexpr int GRAY_NV_MAX = 2;                                 // gray_rows_nv(20, 1) = gray_rows_nv(5, 4)
+template <int W, int P>
+__device__ __forceinline__ void area_rows_gray_body(const RArgs& a, const AreaGeom& gm, int item, int nstrips, int bh,
+                                                    uint32_t* __restrict__ line) {
+    static_assert((P == 1 && W <= GRAY_W_MAX) || (P == 4 && W <= 5), "four columns per lane for small windows only");
+    constexpr int NV = gray_rows_nv(W, P);                       // 16-byte granules a lane fetches per source row
+    static_assert(NV <= GRAY_NV_MAX, "the line holds GRAY_NV_MAX KB");
+    const int lane = threadIdx.x & 63;
+    const int band = item / nstrips, strip = item - band * nstrips;
+    const int dy0 = band * bh;
+    if (dy0 >= a.dh) return;
+    const int dy1 = min(dy0 + bh, a.dh);
+    const int dxf = (strip * 64 + lane) * P;                     // this lane's first column
+    int xs[P];
+    float al[P][W];
+#pragma unroll
+    for (int p = 0; p < P; p++) {
+        const AreaCell cx = area_cell(min(dxf + p, a.dw - 1), a.sw, gm.scale_x);   // idle columns shadow the last one
+        xs[p] = max(min(cx.first(), a.sw - W), 0);               // (a row narrower than the window: the window hangs over its end)
+#pragma unroll
+        for (int k = 0; k < W; k++) al[p][k] = cx.weight(xs[p] + k);             // zero past the cell, so past the row too
+    }
+    // the wave's segment of a source row: from lane 0's first window to the end of lane 63's last, in bytes
+    const int x0 = __builtin_amdgcn_readlane(xs[0], 0);
+    const int seglen = __builtin_amdgcn_readlane(xs[P - 1], 63) + W - x0;          // + 30 <= 1024 * NV (gray_rows_plan)
+    const int segrow = min(seglen, a.sw - x0);                   // what of it lies inside the row: only that is fetched
+    int wrel[P];
+#pragma unroll
+    for (int p = 0; p < P; p++) wrel[p] = xs[p] - x0;
+    const uint8_t* S = a.src + (size_t)x0;
+    // Every lane fetches NV granules and parks them, with no predication: lanes past the segment repeat its last granule
+    // (same address, same LDS slot, same data).
+    uint32_t nxt[NV][4];
+    int nofs[NV];                                                // where the fetched granules go in the line, in dwords
+    int dnxt = 0, dcur = 0;                                      // `dl` of the row in flight / of the parked row
+    auto fetch = [&](int sy) {
+        const uint8_t* row = S + (size_t)sy * a.sstep;
+        dnxt = (int)((uintptr_t)row & 15);
+        const int ngran = (dnxt + segrow + 15) >> 4;             // (bytes of the line past it keep old values: weight zero)
+        const uint8_t* base = row - dnxt;
+#pragma unroll
+        for (int j = 0; j < NV; j++) {
+            const int gi = min(j * 64 + lane, ngran - 1);
+            nofs[j] = gi * 4;
+            load_stream<4>(nxt[j], base + (size_t)gi * 16);
+        }
+    };
+    float b[P];
+    auto reduce = [&]() {                                        // park the fetched row
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int j = 0; j < NV; j++) {
+            typedef unsigned int u32x4a_t __attribute__((ext_vector_type(4), aligned(16)));
+            const u32x4a_t q = {nxt[j][0], nxt[j][1], nxt[j][2], nxt[j][3]};
+            *(u32x4a_t*)(line + nofs[j]) = q;
+        }
+        dcur = dnxt;
+        asm volatile("" ::: "memory");
+    };
+    auto hsum = [&]() {
+        constexpr int ND = (W + 3) / 4;
+#pragma unroll
+        for (int p = 0; p < P; p++) {
+            const int wofs = wrel[p] + dcur;                     // this window in the parked line, in bytes
+            const uint32_t* win = line + (wofs >> 2);
+            const unsigned sh = (unsigned)wofs & 3u;
+            uint32_t t[ND + 1], w[ND];
+#pragma unroll
+            for (int i = 0; i <= ND; i++) t[i] = win[i];
+#pragma unroll
+            for (int i = 0; i < ND; i++) w[i] = __builtin_amdgcn_alignbyte(t[i + 1], t[i], sh);
+            b[p] = 0.f;
+#pragma unroll
+            for (int k = 0; k < W; k++) b[p] = __fadd_rn(b[p], __fmul_rn((float)((w[k >> 2] >> (8 * (k & 3))) & 0xff), al[p][k]));
+        }
+        asm volatile("" ::: "memory");
+    };
+    const AreaCell mine = area_cell(min(dy0 + lane, dy1 - 1), a.sh, gm.scale_y);
+    const int sy_end = __builtin_amdgcn_readlane(mine.end(), dy1 - 1 - dy0);
+    uint8_t* D = a.dst + (size_t)dxf;
+    const int nlive = min(P, a.dw - dxf);                        // columns of this lane inside the frame (<= 0: none)
+    int cur = -1;
+    for (int dy = dy0; dy < dy1; dy++) {
+        const int r = dy - dy0;
+        const int s1 = __builtin_amdgcn_readlane(mine.s1, r), s2 = __builtin_amdgcn_readlane(mine.s2, r);
+        const int hf = __builtin_amdgcn_readlane((int)mine.hf, r), hl = __builtin_amdgcn_readlane((int)mine.hl, r);
+        const float yaf = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mine.af), r));
+        const float yam = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mine.am), r));
+        const float yal = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mine.al), r));
+        const int first = hf ? s1 - 1 : s1, end = hl ? s2 + 1 : s2;
+        if (cur < 0) { fetch(first); cur = first - 1; }
+        float acc[P];
+#pragma unroll
+        for (int p = 0; p < P; p++) acc[p] = 0.f;
+        for (int sy = first; sy < end; sy++) {
+            while (cur < sy) {
+                cur++;
+                reduce();
+                if (cur + 1 < sy_end) fetch(cur + 1);
+                hsum();
+            }
+            const float be = (hf && sy == s1 - 1) ? yaf : ((hl && sy == s2) ? yal : yam);
+#pragma unroll
+            for (int p = 0; p < P; p++) acc[p] = __fadd_rn(acc[p], __fmul_rn(be, b[p]));
+        }
+        uint32_t out = 0;
+#pragma unroll
+        for (int p = 0; p < P; p++) out = cvt_pk_u8(acc[p], out, p);
+        uint8_t* q = D + (size_t)dy * a.dstep;
+        if (P == 4 && nlive == 4 && !(((uintptr_t)q) & 3)) *(uint32_t*)q = out;
+        else
+            for (int p = 0; p < nlive; p++) q[p] = (uint8_t)(out >> (8 * p));
+    }
+}
+
 // ------------------------------------------------------------------ AREA over frames of DIFFERENT geometry (BASELINE configs[4])
 // One launch for a run of requests whose frames all differ in size (bridge.c:588-604 calls Resize() on whatever arrives):
 // a descriptor per frame -- its views and its two scale factors -- instead of launch arguments.  Blocks are dealt to the
 // XCDs like frame_block deals them (block id mod 8 = XCD): descriptor list g holds the frames of XCD g back to back, each
 // with the number of the first block it owns inside that list, and a block finds its frame by bisection over those.
-struct MixDesc { RArgs a; AreaGeom gm; int first, nblk, nv, rows, nstrips, nitems; };   // nitems > 0: row-streaming body, nv = window W (negative: four columns per lane, window -nv), rows = band height
+// What `nv` means depends on the kernel and the body that reads the descriptor:
+//   k_resize_area_mix<3 / 4>, nitems > 0   the window W in pixels (even); negative: four columns per lane, window -nv (2..5)
+//   k_resize_area_mix<3>, nitems == 0      area_cells_body's NV: 16-byte granules of a lane's run
+//   k_resize_area_mix<1>                   always nitems > 0: W in pixels = bytes (even, 2..20), or -W (2..5) with four columns per lane
+struct MixDesc { RArgs a; AreaGeom gm; int first, nblk, nv, rows, nstrips, nitems; };   // rows = band height (nitems > 0) or rows per lane group
 
 template <int CN>
 __global__ __launch_bounds__(256) void k_resize_area_mix(const MixDesc* __restrict__ d, MixIndex ix) {
@@ -2555,6 +2684,30 @@ __global__ __launch_bounds__(256) void k_resize_area_mix(const MixDesc* __restri
             case 10: area_cells_body<3, 5, AREA_ROWS>(m.a, m.gm, 0, blk); break;
             default: area_cells_body<3, 5, 1>(m.a, m.gm, 0, blk); break;
         }
+    }
+}
+
+// Gray frames: every descriptor is a row-streaming one (nitems > 0) of area_rows_gray_body -- nv = the window W (even, 2..20)
+// with one column per lane, or -W (2..5) with four.
+template <>
+__global__ __launch_bounds__(256) void k_resize_area_mix<1>(const MixDesc* __restrict__ d, MixIndex ix) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_line[4][64 * GRAY_NV_MAX * 4 + 4];   // + 4: a window's look-ahead dword
+    int blk;
+    const int di = mix_pick(d, ix, &blk);
+    if (di < 0) return;
+    const MixDesc& m = d[di];
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int item = blk * 4 + wv;
+    if (item >= m.nitems) return;
+    switch (m.nv) {                                    // (block-uniform: a scalar branch)
+        case -2: area_rows_gray_body<2, 4>(m.a, m.gm, item, m.nstrips, m.rows, s_line[wv]); break;
+        case -3: area_rows_gray_body<3, 4>(m.a, m.gm, item, m.nstrips, m.rows, s_line[wv]); break;
+        case -4: area_rows_gray_body<4, 4>(m.a, m.gm, item, m.nstrips, m.rows, s_line[wv]); break;
+        case -5: area_rows_gray_body<5, 4>(m.a, m.gm, item, m.nstrips, m.rows, s_line[wv]); break;
+#define IMP_GRAY_W(W_) case W_: area_rows_gray_body<W_, 1>(m.a, m.gm, item, m.nstrips, m.rows, s_line[wv]); break;
+        IMP_GRAY_W(2) IMP_GRAY_W(4) IMP_GRAY_W(6) IMP_GRAY_W(8) IMP_GRAY_W(10) IMP_GRAY_W(12) IMP_GRAY_W(14) IMP_GRAY_W(16) IMP_GRAY_W(18)
+#undef IMP_GRAY_W
+        default: area_rows_gray_body<20, 1>(m.a, m.gm, item, m.nstrips, m.rows, s_line[wv]); break;
     }
 }
 
@@ -2833,6 +2986,28 @@ static bool area_rows_plan(int sw, int sh, int dw, int dh, double scale_x, long 
     while (b > 4 && frames * nstrips * ((dh + b - 1) / b) < 4096) b /= 2;
     while (b > 1 && frames * nstrips * ((dh + b - 1) / b) < 1024) b /= 2;
     *w = ww;
+    *bh = b;
+    return true;
+}
+
+// area_rows_gray_body for this gray geometry?  *w = the window: the widest horizontal cell (even with one column per lane:
+// the kernel carries those), widened until a wave's segment fits its granules; *p = columns per lane; *bh as area_rows_plan.
+static bool gray_rows_plan(int sw, int dw, int dh, double scale_x, long long frames, int* w, int* p, int* bh) {
+    auto fits = [&](int ww, int pp) { return (64 * pp - 1) * scale_x + ww + 2 + 30 <= 1024.0 * gray_rows_nv(ww, pp); };
+    const int widest = std::max(area_max_count(sw, dw, scale_x), 2);
+    int ww = widest, pp = 4;                               // four columns per lane while the windows are small and the rows long
+    if (dw < 160 || ww > 5 || !fits(ww, 4)) {              // (fits(w, 4) holds for every w <= 5 whose scale is at most w: a guard, not a search)
+        pp = 1;
+        ww = widest + (widest & 1);
+        while (ww <= GRAY_W_MAX && !fits(ww, 1)) ww += 2;
+    }
+    if (ww > GRAY_W_MAX) return false;                     // (a row narrower than the window is fine: the body clips its fetch)
+    int b = 16;
+    const long long nstrips = (dw + 64 * pp - 1) / (64 * pp);
+    while (b > 4 && frames * nstrips * ((dh + b - 1) / b) < 4096) b /= 2;
+    while (b > 1 && frames * nstrips * ((dh + b - 1) / b) < 1024) b /= 2;
+    *w = ww;
+    *p = pp;
     *bh = b;
     return true;
 }
@@ -3390,7 +3565,8 @@ int launch_cv_resize(const Frames& f, int interp, hipStream_t s) {
 // general AREA path (every non-integer shrink whose cells span at most 16 source columns) are gathered into a descriptor
 // launch with their weights computed in the kernel, whole-factor AREA frames (any channel count) into a k_area_int_mix
 // launch and NN frames into a k_resize_nn_mix launch; a frame that is the only one of its kind, and the rest
-// (enlargements, gray general AREA, extreme ratios) go one launch each on the same stream.
+// (enlargements, extreme ratios) go one launch each on the same stream.  Gray frames are gathered like colour ones:
+// their general AREA shrinks ride k_resize_area_mix<1> whatever their pointers and pitches are.
 // Blocks differ a hundredfold in work (a 4K source against a 256-pixel one, same 224-wide output): the frames go
 // longest first to the XCD list with the least source bytes so far, so each list starts with its heavy frames and
 // the launch's tail is made of light ones.  `v` is consumed; *sorted holds the descriptors list by list, *most = the
@@ -3410,7 +3586,8 @@ static int launch_mix(std::vector<MixDesc>& v, int cn, hipStream_t s) {
     if (int rc = upload_small(sorted.data(), sorted.size() * sizeof(MixDesc), &dev, s)) return rc;
     const dim3 grid((unsigned)most * 8), block(256);
     if (cn == 4) hipLaunchKernelGGL((k_resize_area_mix<4>), grid, block, 0, s, (const MixDesc*)dev, ix);
-    else hipLaunchKernelGGL((k_resize_area_mix<3>), grid, block, 0, s, (const MixDesc*)dev, ix);
+    else if (cn == 3) hipLaunchKernelGGL((k_resize_area_mix<3>), grid, block, 0, s, (const MixDesc*)dev, ix);
+    else hipLaunchKernelGGL((k_resize_area_mix<1>), grid, block, 0, s, (const MixDesc*)dev, ix);
     const hipError_t e = hipGetLastError();
     dev_free_on(dev, s);
     IMP_HIP(e);
@@ -3499,7 +3676,7 @@ int launch_resize_mixed(const MixFrame* fr, int count, int cn, int simple, hipSt
     std::vector<MixDesc> gathered_frames;
     std::vector<IntMixDesc> int_frames;                    // whole-factor AREA (resizeAreaFast_), any channel count
     std::vector<NnMixDesc> nn_frames;
-    int int_one = -1, nn_one = -1;                         // the frame of a vector that holds exactly one
+    int int_one = -1, nn_one = -1, gray_one = -1;          // the frame of a vector that holds exactly one
     gathered_frames.reserve(count);
     auto lone = [&](const MixFrame& f, int interp) {
         Frames one{};
@@ -3567,6 +3744,22 @@ int launch_resize_mixed(const MixFrame* fr, int count, int cn, int simple, hipSt
             }
             if (gathered) gathered_frames.push_back(d);
         }
+        if (interp == IMP_INTER_AREA && !whole && cn == 1) {
+            // gray: any pointer, any pitch (the body aligns its own fetches); the window decides
+            MixDesc d{};
+            d.a = RArgs{f.src, 0, f.sstep, f.sw, f.sh, f.dst, 0, f.dstep, f.dw, f.dh};
+            d.gm = AreaGeom{scale_x, scale_y};
+            int w1 = 0, p1 = 0;
+            if (gray_rows_plan(f.sw, f.dw, f.dh, scale_x, count, &w1, &p1, &d.rows)) {
+                d.nv = p1 == 4 ? -w1 : w1;
+                d.nstrips = (f.dw + 64 * p1 - 1) / (64 * p1);
+                d.nitems = d.nstrips * ((f.dh + d.rows - 1) / d.rows);
+                d.nblk = (d.nitems + 3) / 4;
+                gathered_frames.push_back(d);
+                gray_one = i;
+                gathered = true;
+            }
+        }
         if (!gathered)
             if (int rc = lone(f, interp)) return rc;
     }
@@ -3581,6 +3774,7 @@ int launch_resize_mixed(const MixFrame* fr, int count, int cn, int simple, hipSt
     } else if (!nn_frames.empty()) {
         if (int rc = launch_nn_mix(nn_frames, cn, s)) return rc;
     }
+    if (cn == 1 && gathered_frames.size() == 1) return lone(fr[gray_one], IMP_INTER_AREA);      // (k_resize_area<1> and its tables)
     return launch_mix(gathered_frames, cn, s);
 }
 
