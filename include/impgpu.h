@@ -483,10 +483,22 @@ int impgpu_run_ops(impgpu_image** pointer, const impgpu_job* job, const impgpu_c
  * (bridge.c:613-618, the filtering step -- entered for a gray frame even without filters; a request whose fault point fires
  * there keeps its resized gray frame), and from there its chain's segments run in the 3-channel groups with the call's BGR
  * requests: no turn rides a gray resize, the overlay (3 or 4 channels) is always the tail's, there is never a flatten.  A
- * call of gray bare resizes is at most three resize launches plus the promotion.  Albums, requests
- * without a resize and requests whose arguments fail (a bad filter, too many filters, a watermark that does not fit) go
- * through impgpu_run_ops inside the call.  A shared launch that fails gives each of its requests IMP_ERROR_DEVICE with the
- * step of the segment it ran.  launches (may be NULL) receives the number of kernels enqueued.  IMP_ERROR_INVALID_ARGS
+ * call of gray bare resizes is at most three resize launches plus the promotion.  A single frame WITHOUT a resize -- a
+ * crop alone, a watermark-only location, filters on an original -- shares launches too: its chain [crop ->] any filters ->
+ * [watermark] -> [flatten] is the same list of segments, and its first segment reads the crop window.  A gray one is
+ * promoted from its window by the call's single promotion launch (shared with the resized gray requests).  A colour one
+ * whose first segment is pointwise (or the watermark / flatten tail) leaves its window through ONE window launch per
+ * channel count -- two when some programs have a vignette stage -- that reads the window, runs that segment and writes the
+ * fresh frame; the bare crop is an item of the same launch whose rows move as 16-byte runs; a flip, turn or one-pass blur
+ * takes the window as its source in its round's launch.  Later segments run in the rounds above.  When the window is the
+ * whole frame everything runs in place and the handle stays, as impgpu_run_ops leaves it; with no segment at all nothing is
+ * launched.  For its requests without a resize a call therefore makes at most one promotion, two window launches per colour
+ * channel count and what their later rounds cost, whatever `count` is (a request that still stands on its window after a
+ * blur that worked in place is copied out by one more window launch behind its last round).  A request cut by a fault
+ * point keeps what impgpu_run_ops leaves: its uncropped frame, with the pointwise filters applied inside the window when
+ * the watermark step was the one that fired.  Albums and requests whose arguments fail (a bad crop, an unknown filter, too
+ * many filters, a watermark that does not fit) go through impgpu_run_ops inside the call.  A shared launch that fails gives
+ * each of its requests IMP_ERROR_DEVICE with the step of the segment it ran, and each keeps the frame it had.  launches (may be NULL) receives the number of kernels enqueued.  IMP_ERROR_INVALID_ARGS
  * with nothing enqueued when the arguments are malformed (NULL arrays, count < 0 or > 4096, the same handle twice); IMP_ERROR_DEVICE without an env (every codes[i] says so too);
  * otherwise IMP_OK, and the verdicts are in codes[].  Asynchronous on the env stream, like impgpu_run_ops. */
 int impgpu_batch_run_ops(impgpu_image** images, const impgpu_job* jobs, const impgpu_config* const* configs,

@@ -126,8 +126,10 @@ int do_watermark(Work& wk, const impgpu_config* cfg) {
 }
 
 // What impgpu_batch_run_ops needs to know to run a request in shared launches instead of through impgpu_run_ops: a single
-// colour or gray frame whose chain is [crop ->] resize -> any filters -> [watermark] -> [flatten], every decision made here on the
-// host.  Host-only, no fault point entered: a request this refuses goes to impgpu_run_ops whole.
+// colour or gray frame whose chain is [crop ->] [resize ->] any filters -> [watermark] -> [flatten], every decision made here on
+// the host.  Host-only, no fault point entered: a request this refuses goes to impgpu_run_ops whole.
+// Without a resize (`sized` false) nothing rides a resize launch -- rot, wm_turn and the folds stay clear -- and the chain is
+// the segment list alone, its first segment reading the window `v`.
 // The resize is launch_resize_mixed, or the row-streaming AREA kernel with a tail on its stores (k_resize_area_mix_tail,
 // the one acceptance test area_tail_plan) when something rides there: the first filter when it is a turn, as impgpu_run_ops
 // fuses it (with the overlay when the turn is the only filter and the overlay is BGRA, as that launch carries it too), and
@@ -153,6 +155,7 @@ struct ChainPlan {
     std::vector<Segment> segs;
     OverlayArgs wm;             // the overlay's placement on the final frame
     bool gray;                  // a gray frame: resized as gray, promoted (bridge.c:613-618), then a BGR frame's segments
+    bool sized;                 // the request has a resize
 };
 
 static bool bgra_overlay(const impgpu_image* ov) {                    // what the resize tail's overlay path takes
@@ -160,7 +163,7 @@ static bool bgra_overlay(const impgpu_image* ov) {                    // what th
 }
 
 bool chain_plan(const impgpu_image* im, const impgpu_job* job, const impgpu_config* cfg, ChainPlan* p) {
-    if (!im || !job || !cfg || im->frames != 1 || (im->c != 1 && im->c != 3 && im->c != 4) || !job->resize || job->filter_count < 0) return false;
+    if (!im || !job || !cfg || im->frames != 1 || (im->c != 1 && im->c != 3 && im->c != 4) || job->filter_count < 0) return false;
     if (cfg->max_filters_count > 0 && job->filter_count > cfg->max_filters_count) return false;
     if (job->filter_count > 0 && !job->filters) return false;
     for (int i = 0; i < job->filter_count; i++) if (!job->filters[i]) return false;
@@ -170,21 +173,23 @@ bool chain_plan(const impgpu_image* im, const impgpu_job* job, const impgpu_conf
         if (crop_geometry(v.w, v.h, job->crop, job->gravity, &x, &y, &w, &h) != IMP_OK) return false;
         v = view_sub(v, x, y, w, h);
     }
-    int w, h, interp;
-    if (resize_geometry(v.w, v.h, job->resize, cfg->max_target_w, cfg->max_target_h, job->simple, &w, &h, &interp) != IMP_OK) return false;
+    const bool sized = job->resize != nullptr;
+    int w = v.w, h = v.h, interp = IMP_INTER_AREA;
+    if (sized && resize_geometry(v.w, v.h, job->resize, cfg->max_target_w, cfg->max_target_h, job->simple, &w, &h, &interp) != IMP_OK) return false;
     // a gray frame is BGR from the filtering step on (impgpu_run_ops promotes it there): its filters and its overlay are
     // planned for 3 channels, and nothing rides its resize -- impgpu_run_ops fuses no turn into a gray resize either
     const bool gray = v.c == 1;
     const int c = gray ? 3 : v.c;
     const impgpu_image* ov = cfg->watermark;
     p->gray = gray;
+    p->sized = sized;
     p->v = v; p->w = w; p->h = h; p->interp = interp; p->rot = 0;
     p->wm_turn = p->fold_wm = p->fold_flat = false;
     p->wm = OverlayArgs{};
     p->segs.clear();
     // does the AREA kernel with a tail take this resize, turned by `rot`?
     auto tail_takes = [&](int rot) {
-        if (interp != IMP_INTER_AREA || gray) return false;
+        if (!sized || interp != IMP_INTER_AREA || gray) return false;
         const bool swap = rot == 90 || rot == 270;
         Frames f{};
         f.src = v.d; f.v = v; f.dw = w; f.dh = h; f.dstep = aligned_step(swap ? h : w, c); f.count = 1;
@@ -192,7 +197,7 @@ bool chain_plan(const impgpu_image* im, const impgpu_job* job, const impgpu_conf
         return area_tail_plan(f, &ww, &bh);
     };
     int cw = w, ch = h, i0 = 0;
-    if (job->filter_count >= 1 && interp == IMP_INTER_AREA && !gray) { // impgpu_run_ops' first-filter rule
+    if (sized && job->filter_count >= 1 && interp == IMP_INTER_AREA && !gray) { // impgpu_run_ops' first-filter rule
         FilterPlan first;
         PixelProgram none;
         if (filter_plan(job->filters[0], cfg->allow_experiments, c, w, h, &first, &none) == IMP_OK && first.cls == FC_ROTATE &&
@@ -675,11 +680,20 @@ int impgpu_batch_run_ops(impgpu_image** images, const impgpu_job* jobs, const im
     std::vector<MixFrame> bares[3], nns[3];
     std::vector<int> tail_who[2], bare_who[3], nn_who[3];
     std::vector<int> promote_who;                                      // gray requests that reach the promotion
-    std::vector<char> resized((size_t)count, 0);
     std::vector<impgpu_image*> outs((size_t)count, nullptr);
     std::vector<int> final_code((size_t)count, IMP_OK), final_step((size_t)count, IMP_STEP_INFO);
     std::vector<ChainPlan> chains((size_t)count);
     std::vector<int> nsegs((size_t)count, 0);                          // segments a chain request runs (fewer when a fault cuts it)
+    // The frame a chain request stands on: a window of images[i] until something writes a fresh frame (a request without a
+    // resize starts on its crop window, as impgpu_run_ops' Work does), the whole of images[i] from then on.  `live`: the request
+    // runs in the shared launches; `cut`: a fault point fired -- impgpu_run_ops' `done:` exit, which never materializes and
+    // whose pointwise runs have worked in place on the window.
+    std::vector<View> win((size_t)count);
+    std::vector<char> live((size_t)count, 0), cut((size_t)count, 0);
+    auto is_view = [&](int i) {
+        const View& v = win[(size_t)i];
+        return v.d != images[i]->d || v.w != images[i]->w || v.h != images[i]->h;
+    };
     size_t rounds = 0;
     for (int i = 0; i < count; i++) {
         const impgpu_job* job = &jobs[i];
@@ -693,8 +707,10 @@ int impgpu_batch_run_ops(impgpu_image** images, const impgpu_job* jobs, const im
         codes[i] = IMP_ERROR_DEVICE;
         steps[i] = IMP_STEP_CROP;
         if (job->crop && fault_hit(IMP_STEP_CROP)) continue;
-        steps[i] = IMP_STEP_RESIZE;
-        if (fault_hit(IMP_STEP_RESIZE)) continue;
+        if (cp.sized) {
+            steps[i] = IMP_STEP_RESIZE;
+            if (fault_hit(IMP_STEP_RESIZE)) continue;
+        }
         int failed = -1;
         if ((cp.gray || job->filter_count > 0) && fault_hit(IMP_STEP_FILTERING)) failed = IMP_STEP_FILTERING;   // (a gray frame enters it for its promotion)
         else if (cfg->watermark && fault_hit(IMP_STEP_WATERMARK)) failed = IMP_STEP_WATERMARK;
@@ -715,6 +731,17 @@ int impgpu_batch_run_ops(impgpu_image** images, const impgpu_job* jobs, const im
         }
         nsegs[(size_t)i] = n;
         rounds = std::max(rounds, (size_t)n);
+        cut[(size_t)i] = failed >= 0;
+        if (!cp.sized) {
+            // no resize launch to wait for: the request stands on its window, and its verdict is known.  Cut at FILTERING it
+            // keeps its frame untouched (a gray one unpromoted); otherwise a gray one joins the call's promotion.
+            live[(size_t)i] = 1;
+            win[(size_t)i] = cp.v;
+            codes[i] = final_code[(size_t)i];
+            steps[i] = final_step[(size_t)i];
+            if (cp.gray && failed != IMP_STEP_FILTERING) promote_who.push_back(i);
+            continue;
+        }
         impgpu_image* out = nullptr;
         if (int rc = image_new_album(cp.fw, cp.fh, cp.v.c, 1, &out)) { codes[i] = rc; nsegs[(size_t)i] = 0; continue; }   // (as Work::fresh)
         outs[(size_t)i] = out;
@@ -748,7 +775,8 @@ int impgpu_batch_run_ops(impgpu_image** images, const impgpu_job* jobs, const im
             outs[(size_t)i] = nullptr;
             codes[i] = final_code[(size_t)i];
             steps[i] = final_step[(size_t)i];
-            resized[(size_t)i] = 1;
+            live[(size_t)i] = 1;
+            win[(size_t)i] = view_of(images[i]);
         }
     };
     for (int k = 0; k < 3; k++) {
@@ -764,19 +792,19 @@ int impgpu_batch_run_ops(impgpu_image** images, const impgpu_job* jobs, const im
         steps[i] = step;
         nsegs[(size_t)i] = 0;
     };
-    // the promotion of every gray request whose resize went through (bridge.c:613-618), ONE launch: fresh BGR frames, the
-    // gray ones released in stream order.  A failure is reported as impgpu_run_ops reports its launch_gray2bgr: at
+    // the promotion of every gray request whose resize went through, or that has none and is promoted from its window
+    // (bridge.c:613-618), ONE launch: fresh BGR frames, the gray ones released in stream order.  A failure is reported as impgpu_run_ops reports its launch_gray2bgr: at
     // IMP_STEP_FILTERING, the request keeping its resized gray frame.  From here on the frames are BGR requests' frames.
     {
         std::vector<Gray2BgrItem> g2b;
         std::vector<int> g2b_who;
         for (int i : promote_who) {
-            impgpu_image* cur = images[i];
-            if (!resized[(size_t)i]) continue;                          // (its resize launch failed)
+            if (!live[(size_t)i]) continue;                             // (its resize launch failed)
+            const View cur = win[(size_t)i];
             impgpu_image* out = nullptr;
-            if (int rc = image_new_album(cur->w, cur->h, 3, 1, &out)) { fail(i, rc, IMP_STEP_FILTERING); continue; }
+            if (int rc = image_new_album(cur.w, cur.h, 3, 1, &out)) { fail(i, rc, IMP_STEP_FILTERING); continue; }
             outs[(size_t)i] = out;
-            g2b.push_back(Gray2BgrItem{cur->d, out->d, cur->w, cur->h, cur->step, out->step});
+            g2b.push_back(Gray2BgrItem{cur.d, out->d, cur.w, cur.h, cur.step, out->step});
             g2b_who.push_back(i);
         }
         if (!g2b.empty()) {
@@ -788,70 +816,102 @@ int impgpu_batch_run_ops(impgpu_image** images, const impgpu_job* jobs, const im
                 } else {
                     image_delete(images[i]);
                     images[i] = outs[(size_t)i];
+                    win[(size_t)i] = view_of(images[i]);
                 }
                 outs[(size_t)i] = nullptr;
             }
         }
     }
-    for (size_t r = 0; r < rounds; r++) {
+    // A request that has run its segments and still stands on a window (no segment at all: the bare crop; or nothing but blurs
+    // that worked in place) leaves it as materialize() does, as a bare item of the window launch of the round after its last
+    // segment -- round 0 for the bare crop, next to the requests whose first pointwise segment reads their window.  Hence
+    // one round more than the longest chain; it launches nothing unless such a request exists.
+    for (size_t r = 0; r <= rounds; r++) {
         std::vector<PixelTailItem> pix[2];
+        std::vector<WindowItem> wnd[2];
         std::vector<GeomItem> geo[2];
         std::vector<BlurItem> blu[2];
-        std::vector<int> pix_who[2], geo_who[2], blu_who[2];
+        std::vector<int> pix_who[2], wnd_who[2], geo_who[2], blu_who[2];
         for (int i = 0; i < count; i++) {
-            if ((size_t)nsegs[(size_t)i] <= r) continue;
+            if (!live[(size_t)i] || codes[i] != final_code[(size_t)i]) continue;    // (not a chain, or a launch of its failed)
             const ChainPlan& cp = chains[(size_t)i];
+            const View cur = win[(size_t)i];
+            const int k = cur.c - 3;
+            if ((size_t)nsegs[(size_t)i] <= r) {
+                if ((size_t)nsegs[(size_t)i] != r || cut[(size_t)i] || cur.c < 3 || !is_view(i)) continue;
+                impgpu_image* out = nullptr;
+                if (int rc = image_new_album(cur.w, cur.h, cur.c, 1, &out)) { fail(i, rc, IMP_STEP_WATERMARK); continue; }
+                outs[(size_t)i] = out;
+                WindowItem it{};
+                it.src = cur.d; it.sstep = cur.step;
+                it.t.d = out->d; it.t.w = out->w; it.t.h = out->h; it.t.step = out->step;
+                wnd[k].push_back(it);
+                wnd_who[k].push_back(i);
+                continue;
+            }
             const Segment& sg = cp.segs[r];
-            impgpu_image* cur = images[i];
-            const int k = cur->c - 3;
             if (sg.kind == SEG_PIXEL) {
                 PixelTailItem it{};
-                it.d = cur->d; it.w = cur->w; it.h = cur->h; it.step = cur->step; it.prog = &sg.prog;
+                it.d = const_cast<uint8_t*>(cur.d); it.w = cur.w; it.h = cur.h; it.step = cur.step; it.prog = &sg.prog;
                 if (sg.has_wm) {
                     it.has_wm = true; it.ov = configs[i]->watermark;
                     it.rx = cp.wm.rx; it.ry = cp.wm.ry; it.maxcol = cp.wm.maxcol; it.maxrow = cp.wm.maxrow; it.alpha = cp.wm.alpha;
                 }
                 it.flatten = sg.flat;
-                pix[k].push_back(it);
+                if (is_view(i) && !cut[(size_t)i]) {                    // out of the window into a fresh frame
+                    impgpu_image* out = nullptr;
+                    if (int rc = image_new_album(cur.w, cur.h, cur.c, 1, &out)) { fail(i, rc, sg.step); continue; }
+                    outs[(size_t)i] = out;
+                    it.d = out->d; it.step = out->step;
+                    wnd[k].push_back(WindowItem{cur.d, cur.step, it});
+                    wnd_who[k].push_back(i);
+                    continue;
+                }
+                pix[k].push_back(it);                                   // in place (on the window when a fault point cut the request)
                 pix_who[k].push_back(i);
                 continue;
             }
             const bool mixable = sg.kind == SEG_GEOM ||
-                                 blur_form(cur->w, cur->h, cur->c, !(((uintptr_t)cur->d | (uintptr_t)cur->step) & 3), sg.plan.sigma) == BLUR_MIXABLE;
+                                 blur_form(cur.w, cur.h, cur.c, !(((uintptr_t)cur.d | (uintptr_t)cur.step) & 3), sg.plan.sigma) == BLUR_MIXABLE;
             if (!mixable) {                                             // a blur form of its own: launched alone, as apply_plan does
-                Work wk{cur, view_of(cur)};
+                Work wk{images[i], cur};
                 const int rc = apply_plan(wk, sg.plan);
                 images[i] = wk.owner;
+                win[(size_t)i] = wk.v;
                 if (rc) fail(i, rc, sg.step);
                 continue;
             }
             const bool swap = sg.kind == SEG_GEOM && sg.plan.cls == FC_ROTATE && sg.plan.rotate != 180;
             impgpu_image* out = nullptr;
-            if (int rc = image_new_album(swap ? cur->h : cur->w, swap ? cur->w : cur->h, cur->c, 1, &out)) { fail(i, rc, sg.step); continue; }
+            if (int rc = image_new_album(swap ? cur.h : cur.w, swap ? cur.w : cur.h, cur.c, 1, &out)) { fail(i, rc, sg.step); continue; }
             outs[(size_t)i] = out;
             if (sg.kind == SEG_GEOM) {
                 const bool turn = sg.plan.cls == FC_ROTATE;
-                geo[k].push_back(GeomItem{cur->d, cur->w, cur->h, cur->step, out->d, out->w, out->h, out->step, turn ? 1 : 0,
+                geo[k].push_back(GeomItem{cur.d, cur.w, cur.h, cur.step, out->d, out->w, out->h, out->step, turn ? 1 : 0,
                                           turn ? sg.plan.rotate : sg.plan.flip_mode});
                 geo_who[k].push_back(i);
             } else {
-                blu[k].push_back(BlurItem{cur->d, out->d, cur->w, cur->h, cur->step, out->step, (double)sg.plan.sigma});
+                blu[k].push_back(BlurItem{cur.d, out->d, cur.w, cur.h, cur.step, out->step, (double)sg.plan.sigma});
                 blu_who[k].push_back(i);
             }
         }
-        auto adopt = [&](const std::vector<int>& who, int rc) {        // a barrier's launch is done: its fresh frames replace the old
+        // a launch into fresh frames is done: they replace the old ones.  Failed, each request keeps the frame it had and
+        // reports the step of the segment the launch ran (the bare crop: impgpu_run_ops' materialize, behind its last step).
+        auto adopt = [&](const std::vector<int>& who, int rc) {
             for (int i : who) {
                 if (rc != IMP_OK) {
                     image_delete(outs[(size_t)i]);
-                    fail(i, IMP_ERROR_DEVICE, chains[(size_t)i].segs[r].step);
+                    fail(i, IMP_ERROR_DEVICE, (size_t)nsegs[(size_t)i] > r ? chains[(size_t)i].segs[r].step : IMP_STEP_WATERMARK);
                 } else {
                     image_delete(images[i]);
                     images[i] = outs[(size_t)i];
+                    win[(size_t)i] = view_of(images[i]);
                 }
                 outs[(size_t)i] = nullptr;
             }
         };
         for (int k = 0; k < 2; k++) {
+            if (!wnd[k].empty()) adopt(wnd_who[k], launch_window_mixed(wnd[k].data(), (int)wnd[k].size(), k + 3, s));
             if (!pix[k].empty()) {
                 const int rc = launch_pixel_tail_mixed(pix[k].data(), (int)pix[k].size(), k + 3, s);
                 if (rc) for (int i : pix_who[k]) fail(i, IMP_ERROR_DEVICE, chains[(size_t)i].segs[r].step);

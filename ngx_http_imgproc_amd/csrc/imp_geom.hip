@@ -15,7 +15,8 @@ struct GArgs {
     uint8_t* dst; long long dst_stride; int dstep, dw, dh;
 };
 
-// ---- copy: `unit` bytes per thread (4 when everything is dword aligned, else 1) ----
+// ---- copy: a dword per thread when everything is dword aligned (k_copy<4>); 16-byte runs of each row when only the
+// destination is (k_copy_run); a byte per thread otherwise (k_copy<1>) ----
 template <int UNIT>
 __global__ __launch_bounds__(256) void k_copy(GArgs a, int row_units) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -25,6 +26,16 @@ __global__ __launch_bounds__(256) void k_copy(GArgs a, int row_units) {
     uint8_t* d = a.dst + (long long)blockIdx.y * a.dst_stride + (size_t)y * a.dstep + (size_t)u * UNIT;
     if (UNIT == 4) *(uint32_t*)d = *(const uint32_t*)s;
     else *d = *s;
+}
+
+// Windows that start or end off the dword grid (a BGR crop at x = 1, 2, 3 mod 4; a row of w * c bytes that is no multiple of
+// 4): a lane moves 16 destination bytes of one row through copy_run16 instead of one byte.
+__global__ __launch_bounds__(256) void k_copy_run(GArgs a, int rowbytes, int chunks) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)chunks * a.dh) return;
+    const int y = (int)(idx / chunks), k = (int)(idx - (long long)y * chunks);
+    copy_run16(a.src + (long long)blockIdx.y * a.src_stride + (size_t)y * a.sstep,
+               a.dst + (long long)blockIdx.y * a.dst_stride + (size_t)y * a.dstep, rowbytes, k);
 }
 
 // ---- cvFlip: mode 0 = vertical (around x axis), > 0 = horizontal, < 0 = both ----
@@ -254,7 +265,13 @@ int launch_copy(const Frames& f, hipStream_t s) {
     if (dword_ok(f) && rowbytes % 4 == 0) {
         const int units = rowbytes / 4;
         hipLaunchKernelGGL((k_copy<4>), dim3(blocks_for((long long)units * f.dh), f.count), dim3(256), 0, s, a, units);
+    } else if (!(((uintptr_t)f.dst | (uintptr_t)f.dstep | (uintptr_t)f.dst_stride) & 3)) {
+        // dword-aligned destination rows (every pool frame): the source may start anywhere
+        const int chunks = (rowbytes + 15) / 16;
+        hipLaunchKernelGGL(k_copy_run, dim3(blocks_for((long long)chunks * f.dh), f.count), dim3(256), 0, s, a, rowbytes, chunks);
     } else {
+        // destination rows off the dword grid -- the re-pitching copies into a caller's tight BGR pitch
+        // (impgpu_image_download_pinned): a byte per thread, 64 contiguous bytes per wave instruction, as before
         hipLaunchKernelGGL((k_copy<1>), dim3(blocks_for((long long)rowbytes * f.dh), f.count), dim3(256), 0, s, a, rowbytes);
     }
     IMP_HIP(hipGetLastError());

@@ -177,6 +177,62 @@ __device__ __forceinline__ uint32_t blend_paper_bgra(uint32_t u) {
     const int tr = (int)__fadd_rn((float)diff, __fmul_rn((float)((u >> 16) & 0xff), prod));
     return (uint32_t)(tb & 0xff) | ((uint32_t)(tg & 0xff) << 8) | ((uint32_t)(tr & 0xff) << 16) | 0xff000000u;
 }
+
+// ---------------------------------------------------------------- a window row as a run of bytes (Crop's copy, bridge.c:130-135)
+// Shared by k_copy_run (imp_geom.hip) and the bare items of k_window_mix (imp_pixel.hip).  Lane `k` of a row moves bytes
+// [16k, 16k + 16) of the row's `n` (= w * channels; nothing here knows the channel count): four dwords out in one store, the
+// source as the aligned dwords around them, shifted into place by (source & 3) with v_alignbyte.  A row's ragged end moves as
+// dwords while four bytes are left, then bytewise.
+// The aligned dword at `p`, reading no byte outside [lo, hi): a window of a BGR frame starts and ends at any byte, and what
+// lies around it may be another row, pitch padding -- or, in a caller's wrapped buffer, nothing at all.
+__device__ __forceinline__ uint32_t row_dword(const uint8_t* p, const uint8_t* lo, const uint8_t* hi) {
+    if (p >= lo && p + 4 <= hi) return *(const uint32_t*)p;
+    uint32_t v = 0;
+#pragma unroll
+    for (int b = 0; b < 4; b++)
+        if (p + b >= lo && p + b < hi) v |= (uint32_t)p[b] << (8 * b);
+    return v;
+}
+typedef uint32_t row_u32x4 __attribute__((ext_vector_type(4), aligned(4)));   // four dwords at a dword-aligned address
+__device__ __forceinline__ void copy_run16(const uint8_t* __restrict__ s, uint8_t* __restrict__ d, int n, int k) {
+    const int o = 16 * k, left = n - o;
+    if (left <= 0) return;
+    const uint8_t* sa = s + o;
+    uint8_t* da = d + o;
+    if ((uintptr_t)d & 3) {                                 // a destination row off the dword grid: bytes.  Kept for safety only:
+                                                            // both callers hand over dword-aligned destination rows (launch_copy
+                                                            // sends the others to k_copy<1>, launch_window_mixed writes pool frames)
+        const int m = left < 16 ? left : 16;
+        for (int b = 0; b < m; b++) da[b] = sa[b];
+        return;
+    }
+    const unsigned a = (unsigned)((uintptr_t)sa & 3);
+    const uint8_t* base = sa - a;                           // (base + 4 .. base + 16 of a whole chunk lie inside the row)
+    const uint8_t* hi = s + n;
+    if (left >= 16) {
+        row_u32x4 q;
+        if (base >= s) q = *(const row_u32x4*)base;
+        else {
+            q.x = row_dword(base, s, hi);
+            q.y = *(const uint32_t*)(base + 4); q.z = *(const uint32_t*)(base + 8); q.w = *(const uint32_t*)(base + 12);
+        }
+        if (a) {
+            const uint32_t q4 = row_dword(base + 16, s, hi);
+            q.x = __builtin_amdgcn_alignbyte(q.y, q.x, a);
+            q.y = __builtin_amdgcn_alignbyte(q.z, q.y, a);
+            q.z = __builtin_amdgcn_alignbyte(q.w, q.z, a);
+            q.w = __builtin_amdgcn_alignbyte(q4, q.w, a);
+        }
+        *(row_u32x4*)da = q;
+        return;
+    }
+    int b = 0;
+    for (; b + 4 <= left; b += 4) {
+        const uint32_t lo = row_dword(base + b, s, hi);
+        *(uint32_t*)(da + b) = a ? __builtin_amdgcn_alignbyte(row_dword(base + b + 4, s, hi), lo, a) : lo;
+    }
+    for (; b < left; b++) da[b] = sa[b];
+}
 #endif
 
 // ---------------------------------------------------------------- host grammar (imp_args.cpp)
@@ -373,6 +429,12 @@ struct PixelTailItem {
     bool flatten;
 };
 int launch_pixel_tail_mixed(const PixelTailItem* items, int count, int channels, hipStream_t s);
+// imp_pixel.hip: the same pass out of place, from a window of a larger frame (a View after view_sub: any byte address for
+// BGR; BGRA windows are dword aligned) into a fresh frame of the window's size -- how a request WITHOUT a resize leaves its
+// crop.  `t.d`, `t.step` name the destination, `t.w` x `t.h` both.  An item with no program, no overlay and no flatten is
+// the bare crop: its rows move as runs of bytes (copy_run16).  One launch per channel count and vignette group, as above.
+struct WindowItem { const uint8_t* src; int sstep; PixelTailItem t; };
+int launch_window_mixed(const WindowItem* items, int count, int channels, hipStream_t s);
 // A program past one launch's stage / table limits, cut where launch_pixel_program cuts it (exact anywhere: every stage
 // already rounds to 8 bits per channel).  One part when it fits.
 void split_program(const PixelProgram& prog, std::vector<PixelProgram>* parts);

@@ -457,18 +457,18 @@ struct PixTailDesc {
     ProgDev prog;
 };
 
-template <int CN, bool VIG>
-__global__ __launch_bounds__(256) void k_pixel_tail_mix(const PixTailDesc* __restrict__ descs, MixIndex ix, const uint8_t* __restrict__ tables) {
-    __shared__ __attribute__((aligned(16))) uint8_t lut[IMP_MAX_TABLE_BYTES];
-    int blk;
-    const int di = mix_pick(descs, ix, &blk);
-    if (di < 0) return;
-    const PixTailDesc* m = descs + di;
-    const ProgDev& prog = m->prog;
-    const uint8_t* tb = tables + m->tab_off;
-    for (int i = threadIdx.x * 4; i < prog.table_bytes; i += 256 * 4)
+// the frame's tables into LDS, once per workgroup
+__device__ __forceinline__ void stage_tables(uint8_t* lut, const uint8_t* __restrict__ tb, int table_bytes) {
+    for (int i = threadIdx.x * 4; i < table_bytes; i += 256 * 4)
         *(uint32_t*)(lut + i) = *(const uint32_t*)(tb + i);
     __syncthreads();
+}
+
+// The TAIL_PIX pixels of workgroup `blk` of one frame: read at `src` (row pitch `sstep`), written at m->d.  In place when
+// the two are the same frame (k_pixel_tail_mix); from a window of a larger frame into a fresh one in k_window_mix.
+template <int CN, bool VIG>
+__device__ __forceinline__ void pixel_tail_block(const PixTailDesc* __restrict__ m, const uint8_t* src, int sstep, int blk, const uint8_t* lut) {
+    const ProgDev& prog = m->prog;
     const int w = m->w, step = m->step;
     const long long npix = (long long)w * m->h;
     const long long first = (long long)blk * TAIL_PIX + threadIdx.x;
@@ -478,13 +478,14 @@ __global__ __launch_bounds__(256) void k_pixel_tail_mix(const PixTailDesc* __res
         const long long idx = first + (long long)it * 256;
         if (idx >= npix) break;
         const int y = (int)(idx / w), x = (int)(idx - (long long)y * w);
+        const uint8_t* sp0 = src + (size_t)y * sstep + (size_t)x * CN;
         uint8_t* p = m->d + (size_t)y * step + (size_t)x * CN;
         int c0, c1, c2, c3 = 255;
         if (CN == 4) {
-            const uint32_t u = *(const uint32_t*)p;
+            const uint32_t u = *(const uint32_t*)sp0;
             c0 = u & 0xff; c1 = (u >> 8) & 0xff; c2 = (u >> 16) & 0xff; c3 = u >> 24;
         } else {
-            c0 = p[0]; c1 = p[1]; c2 = p[2];
+            c0 = sp0[0]; c1 = sp0[1]; c2 = sp0[2];
         }
         run_stages<CN, VIG>(c0, c1, c2, c3, x, y, prog, lut);
         uint32_t u = (uint32_t)(c0 & 0xff) | ((uint32_t)(c1 & 0xff) << 8) | ((uint32_t)(c2 & 0xff) << 16) | ((uint32_t)(c3 & 0xff) << 24);
@@ -500,45 +501,112 @@ __global__ __launch_bounds__(256) void k_pixel_tail_mix(const PixTailDesc* __res
     }
 }
 
+template <int CN, bool VIG>
+__global__ __launch_bounds__(256) void k_pixel_tail_mix(const PixTailDesc* __restrict__ descs, MixIndex ix, const uint8_t* __restrict__ tables) {
+    __shared__ __attribute__((aligned(16))) uint8_t lut[IMP_MAX_TABLE_BYTES];
+    int blk;
+    const int di = mix_pick(descs, ix, &blk);
+    if (di < 0) return;
+    const PixTailDesc* m = descs + di;
+    stage_tables(lut, tables + m->tab_off, m->prog.table_bytes);
+    pixel_tail_block<CN, VIG>(m, m->d, m->step, blk, lut);
+}
+
+// ------------------------------------------------------------------ the same pass out of a window: requests without a resize
+// impgpu_batch_run_ops' requests whose crop is followed by no resize: each item reads a window of its (larger) frame and
+// writes a fresh frame of the window's size -- per pixel exactly pixel_tail_block's sequence, or, for the bare crop (no
+// program, no overlay, no flatten), the rows as runs of bytes: WIN_CHUNKS 16-byte chunks per workgroup through copy_run16.
+#define WIN_CHUNKS (256 * 4)
+struct WindowDesc {
+    PixTailDesc t;               // destination frame, program, overlay, flatten; first / nblk
+    const uint8_t* src; int sstep;
+    int bare;
+};
+
+template <int CN, bool VIG>
+__global__ __launch_bounds__(256) void k_window_mix(const WindowDesc* __restrict__ descs, MixIndex ix, const uint8_t* __restrict__ tables) {
+    __shared__ __attribute__((aligned(16))) uint8_t lut[IMP_MAX_TABLE_BYTES];
+    int blk;
+    const int di = mix_pick(descs, ix, &blk, [](const WindowDesc& d) -> const PixTailDesc& { return d.t; });
+    if (di < 0) return;
+    const WindowDesc* m = descs + di;
+    if (m->bare) {                                         // (the whole workgroup: a descriptor's workgroups are one frame's)
+        const int n = m->t.w * CN, chunks = (n + 15) >> 4;
+        const long long total = (long long)chunks * m->t.h;
+        const long long first = (long long)blk * WIN_CHUNKS + threadIdx.x;
+#pragma unroll 1
+        for (int it = 0; it < WIN_CHUNKS / 256; it++) {
+            const long long idx = first + (long long)it * 256;
+            if (idx >= total) break;
+            const int y = (int)(idx / chunks), k = (int)(idx - (long long)y * chunks);
+            copy_run16(m->src + (size_t)y * m->sstep, m->t.d + (size_t)y * m->t.step, n, k);
+        }
+        return;
+    }
+    stage_tables(lut, tables + m->t.tab_off, m->t.prog.table_bytes);
+    pixel_tail_block<CN, VIG>(&m->t, m->src, m->sstep, blk, lut);
+}
+
+// A well-formed item's descriptor, its tables appended to `tables`.  *vig: the program has a vignette stage; *work: there is
+// something to do on the pixels (a program, an overlay inside the frame, a flatten).
+static int tail_desc(const PixelTailItem& it, int cn, std::vector<uint8_t>* tables, PixTailDesc* out, bool* vig, bool* work) {
+    if (!it.d || !view_fits(it.w, it.h, cn, it.step)) return IMP_ERROR_INVALID_ARGS;
+    if (cn == 4 && (((uintptr_t)it.d | (uintptr_t)it.step) & 3)) return IMP_ERROR_INVALID_ARGS;
+    const bool has_prog = it.prog && !it.prog->empty();
+    if (has_prog && !program_fits(*it.prog)) return IMP_ERROR_INVALID_ARGS;
+    const bool wm = it.has_wm && it.maxcol > 0 && it.maxrow > 0;
+    if (wm && (!it.ov || it.ov->c < 3 || it.rx < 0 || it.ry < 0 || it.rx + it.maxcol > it.w || it.ry + it.maxrow > it.h ||
+               it.maxcol > it.ov->w || it.maxrow > it.ov->h))
+        return IMP_ERROR_INVALID_ARGS;
+    const bool flat = it.flatten && cn == 4;
+    *work = has_prog || wm || flat;
+    *vig = false;
+    PixTailDesc d{};
+    d.d = it.d; d.w = it.w; d.h = it.h; d.step = it.step;
+    d.nblk = (int)(((long long)it.w * it.h + TAIL_PIX - 1) / TAIL_PIX);
+    d.tab_off = (int)tables->size();
+    if (has_prog) {
+        d.prog.n = (int)it.prog->stages.size();
+        for (int k = 0; k < d.prog.n; k++) {
+            d.prog.st[k] = it.prog->stages[(size_t)k];
+            *vig = *vig || d.prog.st[k].kind == ST_VIGNETTE;
+        }
+        d.prog.table_bytes = ((int)it.prog->tables.size() + 3) & ~3;
+        tables->insert(tables->end(), it.prog->tables.begin(), it.prog->tables.end());
+        tables->resize((tables->size() + 15) & ~size_t(15), 0);
+    }
+    if (wm) {
+        d.has_wm = 1;
+        d.ov = it.ov->d; d.ostep = it.ov->step; d.oc = it.ov->c;
+        d.rx = it.rx; d.ry = it.ry; d.maxcol = it.maxcol; d.maxrow = it.maxrow; d.alpha = it.alpha;
+    }
+    d.flat = flat ? 1 : 0;
+    *out = d;
+    return IMP_OK;
+}
+
+// descriptors | tables as one blob in pool memory
+template <class D>
+static int upload_descs(const std::vector<D>& sorted, const std::vector<uint8_t>& tables, void** dev, const uint8_t** dt, hipStream_t s) {
+    const size_t dbytes = (sorted.size() * sizeof(D) + 15) & ~size_t(15);
+    std::vector<uint8_t> blob(dbytes + tables.size(), 0);
+    std::memcpy(blob.data(), sorted.data(), sorted.size() * sizeof(D));
+    std::memcpy(blob.data() + dbytes, tables.data(), tables.size());
+    if (int rc = upload_small(blob.data(), blob.size(), dev, s)) return rc;
+    *dt = (const uint8_t*)*dev + dbytes;
+    return IMP_OK;
+}
+
 int launch_pixel_tail_mixed(const PixelTailItem* items, int count, int cn, hipStream_t s) {
     if (count <= 0) return IMP_OK;
     if (!items || (cn != 3 && cn != 4)) return IMP_ERROR_INVALID_ARGS;
     std::vector<PixTailDesc> v[2];                         // without / with a vignette stage
     std::vector<uint8_t> tables;
     for (int i = 0; i < count; i++) {                      // nothing is launched unless every item is well-formed
-        const PixelTailItem& it = items[i];
-        if (!it.d || !view_fits(it.w, it.h, cn, it.step)) return IMP_ERROR_INVALID_ARGS;
-        if (cn == 4 && (((uintptr_t)it.d | (uintptr_t)it.step) & 3)) return IMP_ERROR_INVALID_ARGS;
-        const bool has_prog = it.prog && !it.prog->empty();
-        if (has_prog && !program_fits(*it.prog)) return IMP_ERROR_INVALID_ARGS;
-        const bool wm = it.has_wm && it.maxcol > 0 && it.maxrow > 0;
-        if (wm && (!it.ov || it.ov->c < 3 || it.rx < 0 || it.ry < 0 || it.rx + it.maxcol > it.w || it.ry + it.maxrow > it.h ||
-                   it.maxcol > it.ov->w || it.maxrow > it.ov->h))
-            return IMP_ERROR_INVALID_ARGS;
-        const bool flat = it.flatten && cn == 4;
-        if (!has_prog && !wm && !flat) continue;
-        PixTailDesc d{};
-        d.d = it.d; d.w = it.w; d.h = it.h; d.step = it.step;
-        d.nblk = (int)(((long long)it.w * it.h + TAIL_PIX - 1) / TAIL_PIX);
-        d.tab_off = (int)tables.size();
-        bool vig = false;
-        if (has_prog) {
-            d.prog.n = (int)it.prog->stages.size();
-            for (int k = 0; k < d.prog.n; k++) {
-                d.prog.st[k] = it.prog->stages[(size_t)k];
-                vig = vig || d.prog.st[k].kind == ST_VIGNETTE;
-            }
-            d.prog.table_bytes = ((int)it.prog->tables.size() + 3) & ~3;
-            tables.insert(tables.end(), it.prog->tables.begin(), it.prog->tables.end());
-            tables.resize((tables.size() + 15) & ~size_t(15), 0);
-        }
-        if (wm) {
-            d.has_wm = 1;
-            d.ov = it.ov->d; d.ostep = it.ov->step; d.oc = it.ov->c;
-            d.rx = it.rx; d.ry = it.ry; d.maxcol = it.maxcol; d.maxrow = it.maxrow; d.alpha = it.alpha;
-        }
-        d.flat = flat ? 1 : 0;
-        v[vig ? 1 : 0].push_back(d);
+        PixTailDesc d;
+        bool vig, work;
+        if (int rc = tail_desc(items[i], cn, &tables, &d, &vig, &work)) return rc;
+        if (work) v[vig ? 1 : 0].push_back(d);
     }
     if (tables.empty()) tables.resize(16, 0);
     for (int vig = 0; vig < 2; vig++) {
@@ -548,14 +616,10 @@ int launch_pixel_tail_mixed(const PixelTailItem* items, int count, int cn, hipSt
         int most = 0;
         mix_deal(v[vig], [](PixTailDesc& d) -> PixTailDesc& { return d; }, [](PixTailDesc& d) { return (long long)d.w * d.h; },
                  &sorted, &ix, &most);
-        const size_t dbytes = (sorted.size() * sizeof(PixTailDesc) + 15) & ~size_t(15);
-        std::vector<uint8_t> blob(dbytes + tables.size(), 0);
-        std::memcpy(blob.data(), sorted.data(), sorted.size() * sizeof(PixTailDesc));
-        std::memcpy(blob.data() + dbytes, tables.data(), tables.size());
         void* dev = nullptr;
-        if (int rc = upload_small(blob.data(), blob.size(), &dev, s)) return rc;
+        const uint8_t* dt = nullptr;
+        if (int rc = upload_descs(sorted, tables, &dev, &dt, s)) return rc;
         const PixTailDesc* dd = (const PixTailDesc*)dev;
-        const uint8_t* dt = (const uint8_t*)dev + dbytes;
         const dim3 grid((unsigned)most * 8), block(256);
         if (cn == 4 && vig) hipLaunchKernelGGL((k_pixel_tail_mix<4, true>), grid, block, 0, s, dd, ix, dt);
         else if (cn == 4) hipLaunchKernelGGL((k_pixel_tail_mix<4, false>), grid, block, 0, s, dd, ix, dt);
@@ -564,6 +628,47 @@ int launch_pixel_tail_mixed(const PixelTailItem* items, int count, int cn, hipSt
         const hipError_t e = hipGetLastError();
         dev_free_on(dev, s);
         if (e != hipSuccess) { set_error("k_pixel_tail_mix", e); return IMP_ERROR_DEVICE; }
+    }
+    return IMP_OK;
+}
+
+int launch_window_mixed(const WindowItem* items, int count, int cn, hipStream_t s) {
+    if (count <= 0) return IMP_OK;
+    if (!items || (cn != 3 && cn != 4)) return IMP_ERROR_INVALID_ARGS;
+    std::vector<WindowDesc> v[2];                          // without / with a vignette stage; bare crops ride the first
+    std::vector<uint8_t> tables;
+    for (int i = 0; i < count; i++) {                      // nothing is launched unless every item is well-formed
+        const WindowItem& it = items[i];
+        if (!it.src || it.src == it.t.d || !view_fits(it.t.w, it.t.h, cn, it.sstep)) return IMP_ERROR_INVALID_ARGS;
+        if (cn == 4 && (((uintptr_t)it.src | (uintptr_t)it.sstep) & 3)) return IMP_ERROR_INVALID_ARGS;
+        WindowDesc d{};
+        bool vig, work;
+        if (int rc = tail_desc(it.t, cn, &tables, &d.t, &vig, &work)) return rc;
+        d.src = it.src; d.sstep = it.sstep;
+        d.bare = work ? 0 : 1;
+        if (d.bare) d.t.nblk = (int)(((long long)((it.t.w * cn + 15) / 16) * it.t.h + WIN_CHUNKS - 1) / WIN_CHUNKS);
+        v[vig ? 1 : 0].push_back(d);
+    }
+    if (tables.empty()) tables.resize(16, 0);
+    for (int vig = 0; vig < 2; vig++) {
+        if (v[vig].empty()) continue;
+        std::vector<WindowDesc> sorted;
+        MixIndex ix{};
+        int most = 0;
+        mix_deal(v[vig], [](WindowDesc& d) -> PixTailDesc& { return d.t; }, [](WindowDesc& d) { return (long long)d.t.w * d.t.h; },
+                 &sorted, &ix, &most);
+        void* dev = nullptr;
+        const uint8_t* dt = nullptr;
+        if (int rc = upload_descs(sorted, tables, &dev, &dt, s)) return rc;
+        const WindowDesc* dd = (const WindowDesc*)dev;
+        const dim3 grid((unsigned)most * 8), block(256);
+        if (cn == 4 && vig) hipLaunchKernelGGL((k_window_mix<4, true>), grid, block, 0, s, dd, ix, dt);
+        else if (cn == 4) hipLaunchKernelGGL((k_window_mix<4, false>), grid, block, 0, s, dd, ix, dt);
+        else if (vig) hipLaunchKernelGGL((k_window_mix<3, true>), grid, block, 0, s, dd, ix, dt);
+        else hipLaunchKernelGGL((k_window_mix<3, false>), grid, block, 0, s, dd, ix, dt);
+        const hipError_t e = hipGetLastError();
+        dev_free_on(dev, s);
+        if (e != hipSuccess) { set_error("k_window_mix", e); return IMP_ERROR_DEVICE; }
     }
     return IMP_OK;
 }

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """VGPRs / SGPRs / scratch / LDS / occupancy of every gfx950 kernel in the library (hipcc -S, no GPU needed).
-    python tools/kernel_resources.py > profiles/r01_kernel_resources.txt"""
+    python tools/kernel_resources.py > profiles/r01_kernel_resources.txt
+    python tools/kernel_resources.py imp_geom.hip imp_pixel.hip      # those files only"""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "ngx_http_imgproc_amd", "csrc")
 rows = []
 for f in sorted(os.listdir(CSRC)):
-    if not f.endswith(".hip"):
+    if not f.endswith(".hip") or (sys.argv[1:] and f not in sys.argv[1:]):
         continue
     with tempfile.NamedTemporaryFile(suffix=".s") as tmp:
         subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
