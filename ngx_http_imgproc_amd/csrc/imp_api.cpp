@@ -114,15 +114,51 @@ int do_filter(Work& wk, const char* request, int allow, PixelProgram& prog) {
     return apply_plan(wk, plan);
 }
 
-int do_watermark(Work& wk, const impgpu_config* cfg) {
+// The overlay of `cfg` on a frame of w x h, as every launch that blends it takes it: the rectangle (watermark_rect), the
+// overlay's pixels, and alpha = 1 - opacity / 100 (bridge.c:275, filters.c:620).  cfg->watermark must be set.
+int overlay_args(const impgpu_config* cfg, int w, int h, OverlayArgs* a) {
     const impgpu_image* ov = cfg->watermark;
-    if (wk.v.c < 3 || ov->c < 3) return IMP_ERROR_INVALID_ARGS;   // reference indexes B,G,R unconditionally
-    int rx, ry, maxcol, maxrow;
-    if (int rc = watermark_rect(wk.v.w, wk.v.h, ov->w, ov->h, cfg, &rx, &ry, &maxcol, &maxrow)) return rc;
-    const float opacity = (float)(cfg->watermark_opacity / 100.0);   // bridge.c:275
-    const float alpha = 1 - opacity;                                  // filters.c:620
-    return launch_blend_over(wk.px(), wk.stride(), wk.v.w, wk.v.h, wk.v.c, wk.v.step, wk.count(), ov,
-                             rx, ry, maxcol, maxrow, alpha, env_stream());
+    if (int rc = watermark_rect(w, h, ov->w, ov->h, cfg, &a->rx, &a->ry, &a->maxcol, &a->maxrow)) return rc;
+    a->ov = ov->d; a->ostep = ov->step;
+    a->alpha = 1 - (float)(cfg->watermark_opacity / 100.0);
+    return IMP_OK;
+}
+
+bool bgra_overlay(const impgpu_image* ov) {                           // what the resize tail's overlay path takes
+    return ov && ov->c == 4 && !(((uintptr_t)ov->d | (uintptr_t)ov->step) & 3);
+}
+
+int do_watermark(Work& wk, const impgpu_config* cfg) {
+    if (wk.v.c < 3 || cfg->watermark->c < 3) return IMP_ERROR_INVALID_ARGS;   // reference indexes B,G,R unconditionally
+    OverlayArgs a{};
+    if (int rc = overlay_args(cfg, wk.v.w, wk.v.h, &a)) return rc;
+    return launch_blend_over(wk.px(), wk.stride(), wk.v.w, wk.v.h, wk.v.c, wk.v.step, wk.count(), cfg->watermark,
+                             a.rx, a.ry, a.maxcol, a.maxrow, a.alpha, env_stream());
+}
+
+// Does the row-streaming AREA kernel with a tail on its stores (area_tail_plan) take the resize of `count` frames at `v` to
+// w x h, the frame turned by `rot` as it is stored?
+bool area_tail_takes(const View& v, int count, int w, int h, int rot) {
+    const bool swap = rot == 90 || rot == 270;
+    Frames f{};
+    f.src = v.d; f.v = v; f.dw = w; f.dh = h; f.dstep = aligned_step(swap ? h : w, v.c); f.count = count;
+    int ww, bh;
+    return area_tail_plan(f, &ww, &bh);
+}
+
+// The fused-turn rule, stated once for impgpu_run_ops and chain_plan, which must agree on it: the first filter of a colour
+// request rides the stores of its INTER_AREA resize to w x h when it is a turn and area_tail_plan takes that resize; the
+// overlay rides along (the watermark step is then done) when the turn is the only filter and the overlay is BGRA.  Returns
+// the turn, 0 when nothing rides.  Whether the overlay's rectangle can be computed is the caller's to ask (overlay_args).
+int fused_turn(const View& v, int count, int w, int h, int interp, const impgpu_job* job, const impgpu_config* cfg, bool* with_wm) {
+    *with_wm = false;
+    if (interp != IMP_INTER_AREA || (v.c != 4 && v.c != 3) || job->filter_count < 1) return 0;    // BGRA, and BGR: every JPEG
+    FilterPlan first;
+    PixelProgram none;
+    if (filter_plan(job->filters[0], cfg->allow_experiments, v.c, w, h, &first, &none) != IMP_OK || first.cls != FC_ROTATE) return 0;
+    if (!area_tail_takes(v, count, w, h, first.rotate)) return 0;
+    *with_wm = job->filter_count == 1 && bgra_overlay(cfg->watermark);
+    return first.rotate;
 }
 
 // What impgpu_batch_run_ops needs to know to run a request in shared launches instead of through impgpu_run_ops: a single
@@ -158,10 +194,6 @@ struct ChainPlan {
     bool sized;                 // the request has a resize
 };
 
-static bool bgra_overlay(const impgpu_image* ov) {                    // what the resize tail's overlay path takes
-    return ov && ov->c == 4 && !(((uintptr_t)ov->d | (uintptr_t)ov->step) & 3);
-}
-
 bool chain_plan(const impgpu_image* im, const impgpu_job* job, const impgpu_config* cfg, ChainPlan* p) {
     if (!im || !job || !cfg || im->frames != 1 || (im->c != 1 && im->c != 3 && im->c != 4) || job->filter_count < 0) return false;
     if (cfg->max_filters_count > 0 && job->filter_count > cfg->max_filters_count) return false;
@@ -177,37 +209,20 @@ bool chain_plan(const impgpu_image* im, const impgpu_job* job, const impgpu_conf
     int w = v.w, h = v.h, interp = IMP_INTER_AREA;
     if (sized && resize_geometry(v.w, v.h, job->resize, cfg->max_target_w, cfg->max_target_h, job->simple, &w, &h, &interp) != IMP_OK) return false;
     // a gray frame is BGR from the filtering step on (impgpu_run_ops promotes it there): its filters and its overlay are
-    // planned for 3 channels, and nothing rides its resize -- impgpu_run_ops fuses no turn into a gray resize either
+    // planned for 3 channels, and nothing rides its resize -- fused_turn and area_tail_plan take colour frames only
     const bool gray = v.c == 1;
     const int c = gray ? 3 : v.c;
     const impgpu_image* ov = cfg->watermark;
     p->gray = gray;
     p->sized = sized;
-    p->v = v; p->w = w; p->h = h; p->interp = interp; p->rot = 0;
+    p->v = v; p->w = w; p->h = h; p->interp = interp;
     p->wm_turn = p->fold_wm = p->fold_flat = false;
     p->wm = OverlayArgs{};
     p->segs.clear();
-    // does the AREA kernel with a tail take this resize, turned by `rot`?
-    auto tail_takes = [&](int rot) {
-        if (!sized || interp != IMP_INTER_AREA || gray) return false;
-        const bool swap = rot == 90 || rot == 270;
-        Frames f{};
-        f.src = v.d; f.v = v; f.dw = w; f.dh = h; f.dstep = aligned_step(swap ? h : w, c); f.count = 1;
-        int ww, bh;
-        return area_tail_plan(f, &ww, &bh);
-    };
-    int cw = w, ch = h, i0 = 0;
-    if (sized && job->filter_count >= 1 && interp == IMP_INTER_AREA && !gray) { // impgpu_run_ops' first-filter rule
-        FilterPlan first;
-        PixelProgram none;
-        if (filter_plan(job->filters[0], cfg->allow_experiments, c, w, h, &first, &none) == IMP_OK && first.cls == FC_ROTATE &&
-            tail_takes(first.rotate)) {
-            const bool swap = first.rotate != 180;
-            p->rot = first.rotate;
-            cw = swap ? h : w; ch = swap ? w : h;
-            i0 = 1;
-        }
-    }
+    p->rot = sized ? fused_turn(v, 1, w, h, interp, job, cfg, &p->wm_turn) : 0;
+    const bool swap = p->rot == 90 || p->rot == 270;
+    int cw = swap ? h : w, ch = swap ? w : h;
+    const int i0 = p->rot ? 1 : 0;
     p->fw = cw; p->fh = ch;
     auto push_runs = [&](const PixelProgram& prog, PixelProgram* tail) {
         std::vector<PixelProgram> parts;
@@ -237,17 +252,14 @@ bool chain_plan(const impgpu_image* im, const impgpu_job* job, const impgpu_conf
     push_runs(prog, &tail.prog);
     if (ov) {                                                          // do_watermark, planned
         if (c < 3 || ov->c < 3) return false;
-        if (watermark_rect(cw, ch, ov->w, ov->h, cfg, &p->wm.rx, &p->wm.ry, &p->wm.maxcol, &p->wm.maxrow) != IMP_OK) return false;
-        p->wm.ov = ov->d; p->wm.ostep = ov->step;
-        p->wm.alpha = 1 - (float)(cfg->watermark_opacity / 100.0);    // bridge.c:275, filters.c:620
-        // impgpu_run_ops' turn launch carries the overlay when the turn is the only filter (its watermark step is then done)
-        p->wm_turn = p->rot != 0 && job->filter_count == 1 && bgra_overlay(ov);
-        tail.has_wm = !p->wm_turn;
+        // (impgpu_run_ops goes on without the fused overlay and fails at its watermark step: refused, so that it takes that route)
+        if (overlay_args(cfg, cw, ch, &p->wm) != IMP_OK) return false;
+        tail.has_wm = !p->wm_turn;                                     // (on the turn's launch: the watermark step is done there)
     }
     tail.flat = job->need_flatten && c == 4;
     // nothing but the watermark and the flatten after the resize: they ride the resize's stores
     if (p->segs.empty() && tail.prog.empty() && (tail.has_wm || tail.flat) && (!tail.has_wm || bgra_overlay(ov)) &&
-        (p->rot != 0 || tail_takes(0))) {
+        (p->rot != 0 || (sized && interp == IMP_INTER_AREA && area_tail_takes(v, 1, w, h, 0)))) {
         p->fold_wm = tail.has_wm;
         p->fold_flat = tail.flat;
         return true;
@@ -255,6 +267,237 @@ bool chain_plan(const impgpu_image* im, const impgpu_job* job, const impgpu_conf
     tail.step = tail.prog.empty() ? IMP_STEP_WATERMARK : IMP_STEP_FILTERING;
     if (!tail.prog.empty() || tail.has_wm || tail.flat) p->segs.push_back(tail);
     return true;
+}
+
+// ------------------------------------------------------------------ impgpu_batch_run_ops: requests in shared launches
+// The items of one launch and the requests they belong to.
+template <class Item> struct Group {
+    std::vector<Item> items;
+    std::vector<int> who;
+    void add(int i, Item it) { items.push_back(it); who.push_back(i); }
+    bool empty() const { return items.empty(); }
+    int size() const { return (int)items.size(); }
+};
+
+// One request of the call.
+struct ChainRun {
+    ChainPlan plan;
+    View cur{};                      // the frame it stands on: a window of images[i] until something writes a fresh frame (without
+                                     // a resize it starts on its crop window, as impgpu_run_ops' Work does), then the whole of it
+    impgpu_image* pending = nullptr; // the fresh frame of its launch in flight
+    int nsegs = 0;                   // segments it runs (fewer than the plan's when a fault point cut it)
+    int code = IMP_OK, step = IMP_STEP_INFO;   // the verdict it reports if every launch of its succeeds
+    int at = IMP_STEP_START;         // the step it is working on: what a failed allocation or launch of its reports
+    // LONE: answered by impgpu_run_ops.  WAITING: its resize has not landed.  RUNNING: in the rounds, its verdict published.
+    // STOPPED: a fault point before its first launch, an allocation or a launch failed it; codes[i] / steps[i] say so.
+    enum { LONE, WAITING, RUNNING, STOPPED } state = LONE;
+    bool cut = false;                // a fault point fired behind the resize: impgpu_run_ops' `done:` exit, which never
+                                     // materializes and whose pointwise runs have worked in place on the window
+};
+
+struct Batch {
+    impgpu_image** images; const impgpu_job* jobs; const impgpu_config* const* configs; int count; int* codes; int* steps;
+    hipStream_t s;
+    std::vector<ChainRun> runs;
+    // round 0, per channel slot (c - 3; gray: 2, which has no tails): requests with something on the resize's stores ->
+    // k_resize_area_mix_tail, bare resizes -> launch_resize_mixed, NN resizes of `simple` requests -> one of their own
+    Group<TailItem> tails[2];
+    Group<MixFrame> bares[3], nns[3];
+    std::vector<int> promote;        // gray requests that reach the promotion
+    size_t rounds = 0;               // the longest chain
+
+    bool on_window(int i) const {
+        const View& v = runs[(size_t)i].cur;
+        return v.d != images[i]->d || v.w != images[i]->w || v.h != images[i]->h;
+    }
+    void stop(int i, int rc) {
+        codes[i] = rc;
+        steps[i] = runs[(size_t)i].at;
+        runs[(size_t)i].state = ChainRun::STOPPED;
+    }
+    void publish(int i) {
+        codes[i] = runs[(size_t)i].code;
+        steps[i] = runs[(size_t)i].step;
+        runs[(size_t)i].state = ChainRun::RUNNING;
+    }
+    // the destination of request i's next launch (as Work::fresh); failed, the request stops with the allocator's code
+    impgpu_image* fresh(int i, int w, int h, int c) {
+        if (int rc = image_new_album(w, h, c, 1, &runs[(size_t)i].pending)) { stop(i, rc); return nullptr; }
+        return runs[(size_t)i].pending;
+    }
+    // A launch is done.  Its fresh frames replace the old ones (pool memory: recycled in stream order, behind the launch); failed,
+    // every request of it keeps the frame it had and stops with IMP_ERROR_DEVICE at its step.  `landed`: the launch was the
+    // request's resize -- it joins the rounds and its verdict is published.  (An in-place launch has no fresh frames.)
+    void adopt(const std::vector<int>& who, int rc, bool landed = false) {
+        for (int i : who) {
+            ChainRun& run = runs[(size_t)i];
+            impgpu_image* out = run.pending;
+            run.pending = nullptr;
+            if (rc != IMP_OK) { image_delete(out); stop(i, IMP_ERROR_DEVICE); continue; }
+            if (out) {
+                image_delete(images[i]);
+                images[i] = out;
+                run.cur = view_of(out);
+            }
+            if (landed) publish(i);
+        }
+    }
+    void admit(int i);
+    void resize_round();
+    void promote_gray();
+    void segment_round(size_t r);
+};
+
+// The contract with impgpu_run_ops, for every kind of request.  Fault points: request i enters its own before request i + 1
+// does, in impgpu_run_ops' order (bridge.c:574-640) and before any shared launch of the call -- CROP with a crop, RESIZE
+// with a resize, FILTERING with filters or a gray frame (its promotion belongs to that step), WATERMARK with an overlay; a
+// request the planner refuses is answered by impgpu_run_ops right here, so that its points fall between its neighbours'.
+// The frame a request keeps: cut at CROP or RESIZE it keeps its own, untouched.  Cut behind the resize it runs what
+// impgpu_run_ops has run by then: at FILTERING the resized frame (with what rides that launch: the turn, and the overlay of
+// a lone turn) or, without a resize, its uncropped frame, a gray one unpromoted; at WATERMARK the filtered one, never
+// overlaid after the filters, never flattened -- and never copied out of its window.  A failed allocation reports the
+// allocator's code, a failed launch IMP_ERROR_DEVICE, both at the step the launch belongs to (ChainRun::at: the resize
+// step, FILTERING for the promotion, the segment's own step, WATERMARK for the copy out of the window behind the last
+// segment, as impgpu_run_ops' materialize); the request keeps the frame it stood on.
+void Batch::admit(int i) {
+    const impgpu_job* job = &jobs[i];
+    const impgpu_config* cfg = configs[i];
+    ChainRun& run = runs[(size_t)i];
+    ChainPlan& cp = run.plan;
+    if (!chain_plan(images[i], job, cfg, &cp)) {
+        codes[i] = impgpu_run_ops(&images[i], job, cfg, &steps[i]);
+        return;
+    }
+    run.at = IMP_STEP_CROP;
+    if (job->crop && fault_hit(IMP_STEP_CROP)) return stop(i, IMP_ERROR_DEVICE);
+    if (cp.sized) {
+        run.at = IMP_STEP_RESIZE;
+        if (fault_hit(IMP_STEP_RESIZE)) return stop(i, IMP_ERROR_DEVICE);
+    }
+    int failed = -1;
+    if ((cp.gray || job->filter_count > 0) && fault_hit(IMP_STEP_FILTERING)) failed = IMP_STEP_FILTERING;
+    else if (cfg->watermark && fault_hit(IMP_STEP_WATERMARK)) failed = IMP_STEP_WATERMARK;
+    run.nsegs = (int)cp.segs.size();
+    if (failed >= 0) {                                              // trim the plan to what impgpu_run_ops has run by then
+        run.code = IMP_ERROR_DEVICE;
+        run.step = failed;
+        run.cut = true;
+        cp.fold_wm = cp.fold_flat = false;
+        if (failed == IMP_STEP_FILTERING) run.nsegs = 0;
+        else if (run.nsegs > 0 && cp.segs.back().kind == SEG_PIXEL && (cp.segs.back().has_wm || cp.segs.back().flat)) {
+            Segment& t = cp.segs.back();
+            t.has_wm = t.flat = false;
+            if (t.prog.empty()) run.nsegs--;
+        }
+    }
+    rounds = std::max(rounds, (size_t)run.nsegs);
+    if (cp.gray && failed != IMP_STEP_FILTERING) promote.push_back(i);
+    if (!cp.sized) {                                                // no resize launch to wait for: it starts on its window
+        run.cur = cp.v;
+        return publish(i);
+    }
+    impgpu_image* out = fresh(i, cp.fw, cp.fh, cp.v.c);
+    if (!out) return;
+    run.state = ChainRun::WAITING;
+    const int k = cp.gray ? 2 : cp.v.c - 3;
+    const bool on_stores = cp.wm_turn || cp.fold_wm;
+    if (cp.rot || on_stores || cp.fold_flat)
+        tails[k].add(i, TailItem{cp.v, out->d, cp.w, cp.h, out->step, cp.rot, on_stores, on_stores ? cp.wm : OverlayArgs{}, cp.fold_flat});
+    else
+        (job->simple ? nns : bares)[k].add(i, MixFrame{cp.v.d, cp.v.w, cp.v.h, cp.v.step, out->d, cp.w, cp.h, out->step});
+}
+
+// Round 0: every resize, per slot bare, NN, tail.  A request whose launch fails keeps its frame and stops there.
+void Batch::resize_round() {
+    static const int slot_cn[3] = {3, 4, 1};
+    for (int k = 0; k < 3; k++) {
+        if (!bares[k].empty()) adopt(bares[k].who, launch_resize_mixed(bares[k].items.data(), bares[k].size(), slot_cn[k], 0, s), true);
+        if (!nns[k].empty()) adopt(nns[k].who, launch_resize_mixed(nns[k].items.data(), nns[k].size(), slot_cn[k], 1, s), true);
+        if (k < 2 && !tails[k].empty()) adopt(tails[k].who, launch_area_tail_mixed(tails[k].items.data(), tails[k].size(), k + 3, s), true);
+    }
+}
+
+// The promotion of every gray request whose resize went through, or that has none and is promoted from its window
+// (bridge.c:613-618), ONE launch into fresh BGR frames.  From here on the frames are BGR requests' frames.
+void Batch::promote_gray() {
+    Group<Gray2BgrItem> g2b;
+    for (int i : promote) {
+        ChainRun& run = runs[(size_t)i];
+        if (run.state != ChainRun::RUNNING) continue;               // (its resize failed)
+        run.at = IMP_STEP_FILTERING;
+        const View cur = run.cur;
+        if (impgpu_image* out = fresh(i, cur.w, cur.h, 3)) g2b.add(i, Gray2BgrItem{cur.d, out->d, cur.w, cur.h, cur.step, out->step});
+    }
+    if (!g2b.empty()) adopt(g2b.who, launch_gray2bgr_mixed(g2b.items.data(), g2b.size(), s));
+}
+
+// Round r: segment r of every chain that has one, one launch per (kind, channel count) in the order window, pixel, geom, blur
+// -- and the blur forms no mixed kernel takes one request at a time, as apply_plan runs them.  Barriers write fresh frames;
+// pointwise segments work in place, or out of the window into a fresh frame when the request still stands on one.  A request
+// that has run its segments and still stands on a window (no segment at all: the bare crop; or nothing but blurs that worked in
+// place) leaves it as materialize() does, as a bare item of the window launch of the round after its last segment.
+void Batch::segment_round(size_t r) {
+    Group<WindowItem> wnd[2];
+    Group<PixelTailItem> pix[2];
+    Group<GeomItem> geo[2];
+    Group<BlurItem> blu[2];
+    for (int i = 0; i < count; i++) {
+        ChainRun& run = runs[(size_t)i];
+        if (run.state != ChainRun::RUNNING || (size_t)run.nsegs < r) continue;
+        const View cur = run.cur;
+        const int k = cur.c - 3;
+        if ((size_t)run.nsegs == r) {                               // behind its last segment: out of the window
+            if (run.cut || cur.c < 3 || !on_window(i)) continue;
+            run.at = IMP_STEP_WATERMARK;
+            impgpu_image* out = fresh(i, cur.w, cur.h, cur.c);
+            if (!out) continue;
+            WindowItem it{};
+            it.src = cur.d; it.sstep = cur.step;
+            it.t.d = out->d; it.t.w = out->w; it.t.h = out->h; it.t.step = out->step;
+            wnd[k].add(i, it);
+            continue;
+        }
+        const Segment& sg = run.plan.segs[r];
+        run.at = sg.step;
+        if (sg.kind == SEG_PIXEL) {
+            PixelTailItem it{};
+            it.d = const_cast<uint8_t*>(cur.d); it.w = cur.w; it.h = cur.h; it.step = cur.step; it.prog = &sg.prog;
+            if (sg.has_wm) {
+                const OverlayArgs& wm = run.plan.wm;
+                it.has_wm = true; it.ov = configs[i]->watermark;
+                it.rx = wm.rx; it.ry = wm.ry; it.maxcol = wm.maxcol; it.maxrow = wm.maxrow; it.alpha = wm.alpha;
+            }
+            it.flatten = sg.flat;
+            if (!on_window(i) || run.cut) { pix[k].add(i, it); continue; }    // in place (on the window when a fault point cut the request)
+            impgpu_image* out = fresh(i, cur.w, cur.h, cur.c);       // out of the window into a fresh frame
+            if (!out) continue;
+            it.d = out->d; it.step = out->step;
+            wnd[k].add(i, WindowItem{cur.d, cur.step, it});
+            continue;
+        }
+        if (sg.kind == SEG_BLUR && blur_form(cur.w, cur.h, cur.c, !(((uintptr_t)cur.d | (uintptr_t)cur.step) & 3), sg.plan.sigma) != BLUR_MIXABLE) {
+            Work wk{images[i], cur};                                // a blur form of its own: launched alone, as apply_plan does
+            const int rc = apply_plan(wk, sg.plan);
+            images[i] = wk.owner;
+            run.cur = wk.v;
+            if (rc) stop(i, rc);
+            continue;
+        }
+        const bool turn = sg.kind == SEG_GEOM && sg.plan.cls == FC_ROTATE, swap = turn && sg.plan.rotate != 180;
+        impgpu_image* out = fresh(i, swap ? cur.h : cur.w, swap ? cur.w : cur.h, cur.c);
+        if (!out) continue;
+        if (sg.kind == SEG_GEOM)
+            geo[k].add(i, GeomItem{cur.d, cur.w, cur.h, cur.step, out->d, out->w, out->h, out->step, turn ? 1 : 0,
+                                   turn ? sg.plan.rotate : sg.plan.flip_mode});
+        else
+            blu[k].add(i, BlurItem{cur.d, out->d, cur.w, cur.h, cur.step, out->step, (double)sg.plan.sigma});
+    }
+    for (int k = 0; k < 2; k++) {
+        if (!wnd[k].empty()) adopt(wnd[k].who, launch_window_mixed(wnd[k].items.data(), wnd[k].size(), k + 3, s));
+        if (!pix[k].empty()) adopt(pix[k].who, launch_pixel_tail_mixed(pix[k].items.data(), pix[k].size(), k + 3, s));
+        if (!geo[k].empty()) adopt(geo[k].who, launch_geom_mixed(geo[k].items.data(), geo[k].size(), k + 3, s));
+        if (!blu[k].empty()) adopt(blu[k].who, launch_blur_mixed(blu[k].items.data(), blu[k].size(), k + 3, s));
+    }
 }
 
 }  // namespace
@@ -596,29 +839,20 @@ int impgpu_run_ops(impgpu_image** pointer, const impgpu_job* job, const impgpu_c
         // ONE launch: both ride on the stores of the row-streaming AREA kernel (a lone request is launch-bound: this is a
         // third of its launches and two intermediate frames).  Anything the fused kernel does not take goes step by step.
         rc = IMP_ERROR_UNSUPPORTED;
-        if (interp == IMP_INTER_AREA && (wk.v.c == 4 || wk.v.c == 3) && job->filter_count >= 1) {    // BGRA, and BGR: every JPEG
-            FilterPlan first;
-            PixelProgram none;
-            if (filter_plan(job->filters[0], config->allow_experiments, wk.v.c, w, h, &first, &none) == IMP_OK && first.cls == FC_ROTATE) {
-                const bool swap = first.rotate != 180;
-                const int fw = swap ? h : w, fh = swap ? w : h;
-                const impgpu_image* ov = config->watermark;
-                OverlayArgs wm{};
-                bool with_wm = job->filter_count == 1 && ov && ov->c == 4 && !(((uintptr_t)ov->d | (uintptr_t)ov->step) & 3);
-                if (with_wm && watermark_rect(fw, fh, ov->w, ov->h, config, &wm.rx, &wm.ry, &wm.maxcol, &wm.maxrow) != IMP_OK) with_wm = false;
-                if (with_wm) {
-                    wm.ov = ov->d; wm.ostep = ov->step;
-                    wm.alpha = 1 - (float)(config->watermark_opacity / 100.0);     // bridge.c:275, filters.c:620
-                }
-                impgpu_image* out = nullptr;
-                rc = wk.fresh(fw, fh, wk.v.c, &out);
-                if (rc) goto done;
-                Frames f = wk.to(out);
-                f.dw = w; f.dh = h;                                    // the resized geometry; `out` is the turned frame
-                rc = launch_area_rotate(f, first.rotate, with_wm ? &wm : nullptr, env_stream());
-                if (rc == IMP_OK) { wk.adopt(out); fused_filters = 1; watermark_done = with_wm; }
-                else image_delete(out);
-            }
+        bool with_wm = false;
+        if (const int rot = fused_turn(wk.v, wk.count(), w, h, interp, job, config, &with_wm)) {
+            const bool swap = rot != 180;
+            const int fw = swap ? h : w, fh = swap ? w : h;
+            OverlayArgs wm{};
+            if (with_wm && overlay_args(config, fw, fh, &wm) != IMP_OK) with_wm = false;   // (it fails at the watermark step)
+            impgpu_image* out = nullptr;
+            rc = wk.fresh(fw, fh, wk.v.c, &out);
+            if (rc) goto done;
+            Frames f = wk.to(out);
+            f.dw = w; f.dh = h;                                        // the resized geometry; `out` is the turned frame
+            rc = launch_area_rotate(f, rot, with_wm ? &wm : nullptr, env_stream());
+            if (rc == IMP_OK) { wk.adopt(out); fused_filters = 1; watermark_done = with_wm; }
+            else image_delete(out);
         }
         if (rc == IMP_ERROR_UNSUPPORTED) rc = do_resize(wk, w, h, interp);
         if (rc) goto done;
@@ -672,254 +906,13 @@ int impgpu_batch_run_ops(impgpu_image** images, const impgpu_job* jobs, const im
         return rc;
     }
     const unsigned long long launched = t_launches;
-    hipStream_t s = env_stream();
-    // per channel count (slot c - 3, gray: slot 2): requests with a tail -> k_resize_area_mix_tail, bare resizes ->
-    // launch_resize_mixed (NN resizes of `simple` requests: a launch_resize_mixed of their own).  Gray has no tails.
-    static const int slot_cn[3] = {3, 4, 1};
-    std::vector<TailItem> tails[2];
-    std::vector<MixFrame> bares[3], nns[3];
-    std::vector<int> tail_who[2], bare_who[3], nn_who[3];
-    std::vector<int> promote_who;                                      // gray requests that reach the promotion
-    std::vector<impgpu_image*> outs((size_t)count, nullptr);
-    std::vector<int> final_code((size_t)count, IMP_OK), final_step((size_t)count, IMP_STEP_INFO);
-    std::vector<ChainPlan> chains((size_t)count);
-    std::vector<int> nsegs((size_t)count, 0);                          // segments a chain request runs (fewer when a fault cuts it)
-    // The frame a chain request stands on: a window of images[i] until something writes a fresh frame (a request without a
-    // resize starts on its crop window, as impgpu_run_ops' Work does), the whole of images[i] from then on.  `live`: the request
-    // runs in the shared launches; `cut`: a fault point fired -- impgpu_run_ops' `done:` exit, which never materializes and
-    // whose pointwise runs have worked in place on the window.
-    std::vector<View> win((size_t)count);
-    std::vector<char> live((size_t)count, 0), cut((size_t)count, 0);
-    auto is_view = [&](int i) {
-        const View& v = win[(size_t)i];
-        return v.d != images[i]->d || v.w != images[i]->w || v.h != images[i]->h;
-    };
-    size_t rounds = 0;
-    for (int i = 0; i < count; i++) {
-        const impgpu_job* job = &jobs[i];
-        const impgpu_config* cfg = configs[i];
-        ChainPlan& cp = chains[(size_t)i];
-        if (!chain_plan(images[i], job, cfg, &cp)) {
-            codes[i] = impgpu_run_ops(&images[i], job, cfg, &steps[i]);
-            continue;
-        }
-        // the fault points impgpu_run_ops enters for this chain, in its order (bridge.c:574-640)
-        codes[i] = IMP_ERROR_DEVICE;
-        steps[i] = IMP_STEP_CROP;
-        if (job->crop && fault_hit(IMP_STEP_CROP)) continue;
-        if (cp.sized) {
-            steps[i] = IMP_STEP_RESIZE;
-            if (fault_hit(IMP_STEP_RESIZE)) continue;
-        }
-        int failed = -1;
-        if ((cp.gray || job->filter_count > 0) && fault_hit(IMP_STEP_FILTERING)) failed = IMP_STEP_FILTERING;   // (a gray frame enters it for its promotion)
-        else if (cfg->watermark && fault_hit(IMP_STEP_WATERMARK)) failed = IMP_STEP_WATERMARK;
-        int n = (int)cp.segs.size();
-        if (failed >= 0) {
-            // impgpu_run_ops fails behind its resize step (which carries the turn, and the overlay the turn's launch carries):
-            // at FILTERING the frame is the resized one; at WATERMARK the filtered one -- never overlaid after the filters, never
-            // flattened
-            final_code[(size_t)i] = IMP_ERROR_DEVICE;
-            final_step[(size_t)i] = failed;
-            cp.fold_wm = cp.fold_flat = false;
-            if (failed == IMP_STEP_FILTERING) n = 0;
-            else if (n > 0 && cp.segs.back().kind == SEG_PIXEL && (cp.segs.back().has_wm || cp.segs.back().flat)) {
-                Segment& t = cp.segs.back();
-                t.has_wm = t.flat = false;
-                if (t.prog.empty()) n--;
-            }
-        }
-        nsegs[(size_t)i] = n;
-        rounds = std::max(rounds, (size_t)n);
-        cut[(size_t)i] = failed >= 0;
-        if (!cp.sized) {
-            // no resize launch to wait for: the request stands on its window, and its verdict is known.  Cut at FILTERING it
-            // keeps its frame untouched (a gray one unpromoted); otherwise a gray one joins the call's promotion.
-            live[(size_t)i] = 1;
-            win[(size_t)i] = cp.v;
-            codes[i] = final_code[(size_t)i];
-            steps[i] = final_step[(size_t)i];
-            if (cp.gray && failed != IMP_STEP_FILTERING) promote_who.push_back(i);
-            continue;
-        }
-        impgpu_image* out = nullptr;
-        if (int rc = image_new_album(cp.fw, cp.fh, cp.v.c, 1, &out)) { codes[i] = rc; nsegs[(size_t)i] = 0; continue; }   // (as Work::fresh)
-        outs[(size_t)i] = out;
-        const int k = cp.gray ? 2 : images[i]->c - 3;
-        if (cp.gray && failed != IMP_STEP_FILTERING) promote_who.push_back(i);     // (failed there: it keeps the resized gray frame)
-        const bool on_stores = cp.wm_turn || cp.fold_wm;
-        if (cp.rot || on_stores || cp.fold_flat) {
-            tails[k].push_back(TailItem{cp.v, out->d, cp.w, cp.h, out->step, cp.rot, on_stores, on_stores ? cp.wm : OverlayArgs{}, cp.fold_flat});
-            tail_who[k].push_back(i);
-        } else if (job->simple) {
-            nns[k].push_back(MixFrame{cp.v.d, cp.v.w, cp.v.h, cp.v.step, out->d, cp.w, cp.h, out->step});
-            nn_who[k].push_back(i);
-        } else {
-            bares[k].push_back(MixFrame{cp.v.d, cp.v.w, cp.v.h, cp.v.step, out->d, cp.w, cp.h, out->step});
-            bare_who[k].push_back(i);
-        }
-    }
-    // round 0: every resize.  A request whose launch fails keeps its frame and stops there.
-    auto settle = [&](const std::vector<int>& who, int rc) {
-        for (int i : who) {
-            if (rc != IMP_OK) {                                         // the launch failed: the request keeps its frame
-                image_delete(outs[(size_t)i]);
-                outs[(size_t)i] = nullptr;
-                codes[i] = IMP_ERROR_DEVICE;
-                steps[i] = IMP_STEP_RESIZE;
-                nsegs[(size_t)i] = 0;
-                continue;
-            }
-            image_delete(images[i]);                                    // (pool memory: recycled in stream order, behind the launch)
-            images[i] = outs[(size_t)i];
-            outs[(size_t)i] = nullptr;
-            codes[i] = final_code[(size_t)i];
-            steps[i] = final_step[(size_t)i];
-            live[(size_t)i] = 1;
-            win[(size_t)i] = view_of(images[i]);
-        }
-    };
-    for (int k = 0; k < 3; k++) {
-        if (!bares[k].empty()) settle(bare_who[k], launch_resize_mixed(bares[k].data(), (int)bares[k].size(), slot_cn[k], 0, s));
-        if (!nns[k].empty()) settle(nn_who[k], launch_resize_mixed(nns[k].data(), (int)nns[k].size(), slot_cn[k], 1, s));
-        if (k < 2 && !tails[k].empty()) settle(tail_who[k], launch_area_tail_mixed(tails[k].data(), (int)tails[k].size(), k + 3, s));
-    }
-    // rounds 1 ..: segment r of every chain that has one, one launch per (kind, channel count) -- and the blur forms no mixed
-    // kernel takes one request at a time.  Barriers write fresh frames (pool memory, released in stream order behind the
-    // launch); pointwise segments work in place.
-    auto fail = [&](int i, int rc, int step) {
-        codes[i] = rc;
-        steps[i] = step;
-        nsegs[(size_t)i] = 0;
-    };
-    // the promotion of every gray request whose resize went through, or that has none and is promoted from its window
-    // (bridge.c:613-618), ONE launch: fresh BGR frames, the gray ones released in stream order.  A failure is reported as impgpu_run_ops reports its launch_gray2bgr: at
-    // IMP_STEP_FILTERING, the request keeping its resized gray frame.  From here on the frames are BGR requests' frames.
-    {
-        std::vector<Gray2BgrItem> g2b;
-        std::vector<int> g2b_who;
-        for (int i : promote_who) {
-            if (!live[(size_t)i]) continue;                             // (its resize launch failed)
-            const View cur = win[(size_t)i];
-            impgpu_image* out = nullptr;
-            if (int rc = image_new_album(cur.w, cur.h, 3, 1, &out)) { fail(i, rc, IMP_STEP_FILTERING); continue; }
-            outs[(size_t)i] = out;
-            g2b.push_back(Gray2BgrItem{cur.d, out->d, cur.w, cur.h, cur.step, out->step});
-            g2b_who.push_back(i);
-        }
-        if (!g2b.empty()) {
-            const int rc = launch_gray2bgr_mixed(g2b.data(), (int)g2b.size(), s);
-            for (int i : g2b_who) {
-                if (rc != IMP_OK) {
-                    image_delete(outs[(size_t)i]);
-                    fail(i, IMP_ERROR_DEVICE, IMP_STEP_FILTERING);
-                } else {
-                    image_delete(images[i]);
-                    images[i] = outs[(size_t)i];
-                    win[(size_t)i] = view_of(images[i]);
-                }
-                outs[(size_t)i] = nullptr;
-            }
-        }
-    }
-    // A request that has run its segments and still stands on a window (no segment at all: the bare crop; or nothing but blurs
-    // that worked in place) leaves it as materialize() does, as a bare item of the window launch of the round after its last
-    // segment -- round 0 for the bare crop, next to the requests whose first pointwise segment reads their window.  Hence
-    // one round more than the longest chain; it launches nothing unless such a request exists.
-    for (size_t r = 0; r <= rounds; r++) {
-        std::vector<PixelTailItem> pix[2];
-        std::vector<WindowItem> wnd[2];
-        std::vector<GeomItem> geo[2];
-        std::vector<BlurItem> blu[2];
-        std::vector<int> pix_who[2], wnd_who[2], geo_who[2], blu_who[2];
-        for (int i = 0; i < count; i++) {
-            if (!live[(size_t)i] || codes[i] != final_code[(size_t)i]) continue;    // (not a chain, or a launch of its failed)
-            const ChainPlan& cp = chains[(size_t)i];
-            const View cur = win[(size_t)i];
-            const int k = cur.c - 3;
-            if ((size_t)nsegs[(size_t)i] <= r) {
-                if ((size_t)nsegs[(size_t)i] != r || cut[(size_t)i] || cur.c < 3 || !is_view(i)) continue;
-                impgpu_image* out = nullptr;
-                if (int rc = image_new_album(cur.w, cur.h, cur.c, 1, &out)) { fail(i, rc, IMP_STEP_WATERMARK); continue; }
-                outs[(size_t)i] = out;
-                WindowItem it{};
-                it.src = cur.d; it.sstep = cur.step;
-                it.t.d = out->d; it.t.w = out->w; it.t.h = out->h; it.t.step = out->step;
-                wnd[k].push_back(it);
-                wnd_who[k].push_back(i);
-                continue;
-            }
-            const Segment& sg = cp.segs[r];
-            if (sg.kind == SEG_PIXEL) {
-                PixelTailItem it{};
-                it.d = const_cast<uint8_t*>(cur.d); it.w = cur.w; it.h = cur.h; it.step = cur.step; it.prog = &sg.prog;
-                if (sg.has_wm) {
-                    it.has_wm = true; it.ov = configs[i]->watermark;
-                    it.rx = cp.wm.rx; it.ry = cp.wm.ry; it.maxcol = cp.wm.maxcol; it.maxrow = cp.wm.maxrow; it.alpha = cp.wm.alpha;
-                }
-                it.flatten = sg.flat;
-                if (is_view(i) && !cut[(size_t)i]) {                    // out of the window into a fresh frame
-                    impgpu_image* out = nullptr;
-                    if (int rc = image_new_album(cur.w, cur.h, cur.c, 1, &out)) { fail(i, rc, sg.step); continue; }
-                    outs[(size_t)i] = out;
-                    it.d = out->d; it.step = out->step;
-                    wnd[k].push_back(WindowItem{cur.d, cur.step, it});
-                    wnd_who[k].push_back(i);
-                    continue;
-                }
-                pix[k].push_back(it);                                   // in place (on the window when a fault point cut the request)
-                pix_who[k].push_back(i);
-                continue;
-            }
-            const bool mixable = sg.kind == SEG_GEOM ||
-                                 blur_form(cur.w, cur.h, cur.c, !(((uintptr_t)cur.d | (uintptr_t)cur.step) & 3), sg.plan.sigma) == BLUR_MIXABLE;
-            if (!mixable) {                                             // a blur form of its own: launched alone, as apply_plan does
-                Work wk{images[i], cur};
-                const int rc = apply_plan(wk, sg.plan);
-                images[i] = wk.owner;
-                win[(size_t)i] = wk.v;
-                if (rc) fail(i, rc, sg.step);
-                continue;
-            }
-            const bool swap = sg.kind == SEG_GEOM && sg.plan.cls == FC_ROTATE && sg.plan.rotate != 180;
-            impgpu_image* out = nullptr;
-            if (int rc = image_new_album(swap ? cur.h : cur.w, swap ? cur.w : cur.h, cur.c, 1, &out)) { fail(i, rc, sg.step); continue; }
-            outs[(size_t)i] = out;
-            if (sg.kind == SEG_GEOM) {
-                const bool turn = sg.plan.cls == FC_ROTATE;
-                geo[k].push_back(GeomItem{cur.d, cur.w, cur.h, cur.step, out->d, out->w, out->h, out->step, turn ? 1 : 0,
-                                          turn ? sg.plan.rotate : sg.plan.flip_mode});
-                geo_who[k].push_back(i);
-            } else {
-                blu[k].push_back(BlurItem{cur.d, out->d, cur.w, cur.h, cur.step, out->step, (double)sg.plan.sigma});
-                blu_who[k].push_back(i);
-            }
-        }
-        // a launch into fresh frames is done: they replace the old ones.  Failed, each request keeps the frame it had and
-        // reports the step of the segment the launch ran (the bare crop: impgpu_run_ops' materialize, behind its last step).
-        auto adopt = [&](const std::vector<int>& who, int rc) {
-            for (int i : who) {
-                if (rc != IMP_OK) {
-                    image_delete(outs[(size_t)i]);
-                    fail(i, IMP_ERROR_DEVICE, (size_t)nsegs[(size_t)i] > r ? chains[(size_t)i].segs[r].step : IMP_STEP_WATERMARK);
-                } else {
-                    image_delete(images[i]);
-                    images[i] = outs[(size_t)i];
-                    win[(size_t)i] = view_of(images[i]);
-                }
-                outs[(size_t)i] = nullptr;
-            }
-        };
-        for (int k = 0; k < 2; k++) {
-            if (!wnd[k].empty()) adopt(wnd_who[k], launch_window_mixed(wnd[k].data(), (int)wnd[k].size(), k + 3, s));
-            if (!pix[k].empty()) {
-                const int rc = launch_pixel_tail_mixed(pix[k].data(), (int)pix[k].size(), k + 3, s);
-                if (rc) for (int i : pix_who[k]) fail(i, IMP_ERROR_DEVICE, chains[(size_t)i].segs[r].step);
-            }
-            if (!geo[k].empty()) adopt(geo_who[k], launch_geom_mixed(geo[k].data(), (int)geo[k].size(), k + 3, s));
-            if (!blu[k].empty()) adopt(blu_who[k], launch_blur_mixed(blu[k].data(), (int)blu[k].size(), k + 3, s));
-        }
-    }
+    Batch b{images, jobs, configs, count, codes, steps, env_stream()};
+    b.runs.resize((size_t)count);
+    for (int i = 0; i < count; i++) b.admit(i);
+    b.resize_round();
+    b.promote_gray();
+    // one round more than the longest chain: the windows left behind it; it launches nothing unless such a request exists
+    for (size_t r = 0; r <= b.rounds; r++) b.segment_round(r);
     if (launches) *launches = (int)(t_launches - launched);
     return IMP_OK;
 }
@@ -994,14 +987,8 @@ int impgpu_batch_resize_rotate_watermark(const void* src, long long src_frame_st
         Frames fz = rs;
         fz.dst = (uint8_t*)dst; fz.dst_stride = dst_frame_stride; fz.dstep = dst_step; fz.dw = fw; fz.dh = fh;
         OverlayArgs wm{};
-        const impgpu_image* ov = config->watermark;
-        const bool fuse = ov && channels == 4 && ov->c == 4 && !(((uintptr_t)ov->d | (uintptr_t)ov->step) & 3);
-        if (fuse) {
-            rc = watermark_rect(fw, fh, ov->w, ov->h, config, &wm.rx, &wm.ry, &wm.maxcol, &wm.maxrow);
-            if (rc) return rc;
-            wm.ov = ov->d; wm.ostep = ov->step;
-            wm.alpha = 1 - (float)(config->watermark_opacity / 100.0);     // bridge.c:275, filters.c:620
-        }
+        const bool fuse = channels == 4 && bgra_overlay(config->watermark);
+        if (fuse && (rc = overlay_args(config, fw, fh, &wm)) != IMP_OK) return rc;
         rc = launch_area2x2_rotate(fz, rotate, fuse ? &wm : nullptr, s);
         watermark_done = fuse && rc == IMP_OK;
     }
@@ -1010,14 +997,8 @@ int impgpu_batch_resize_rotate_watermark(const void* src, long long src_frame_st
         Frames fz = rs;
         fz.dst = (uint8_t*)dst; fz.dst_stride = dst_frame_stride; fz.dstep = dst_step;
         OverlayArgs wm{};
-        const impgpu_image* ov = config->watermark;
-        const bool fuse = ov && ov->c == 4 && !(((uintptr_t)ov->d | (uintptr_t)ov->step) & 3);
-        if (fuse) {
-            rc = watermark_rect(fw, fh, ov->w, ov->h, config, &wm.rx, &wm.ry, &wm.maxcol, &wm.maxrow);
-            if (rc) return rc;
-            wm.ov = ov->d; wm.ostep = ov->step;
-            wm.alpha = 1 - (float)(config->watermark_opacity / 100.0);     // bridge.c:275, filters.c:620
-        }
+        const bool fuse = bgra_overlay(config->watermark);
+        if (fuse && (rc = overlay_args(config, fw, fh, &wm)) != IMP_OK) return rc;
         rc = launch_area_rotate(fz, rotate, fuse ? &wm : nullptr, s);
         watermark_done = fuse && rc == IMP_OK;
     }
@@ -1043,13 +1024,10 @@ int impgpu_batch_resize_rotate_watermark(const void* src, long long src_frame_st
         }
     }
     if (!rc && config->watermark && !watermark_done) {
-        int rx, ry, maxcol, maxrow;
-        rc = watermark_rect(fw, fh, config->watermark->w, config->watermark->h, config, &rx, &ry, &maxcol, &maxrow);
-        if (!rc) {
-            const float opacity = (float)(config->watermark_opacity / 100.0);
-            rc = launch_blend_over((uint8_t*)dst, dst_frame_stride, fw, fh, channels, dst_step, count, config->watermark,
-                                   rx, ry, maxcol, maxrow, 1 - opacity, s);
-        }
+        OverlayArgs wm{};
+        rc = overlay_args(config, fw, fh, &wm);
+        if (!rc) rc = launch_blend_over((uint8_t*)dst, dst_frame_stride, fw, fh, channels, dst_step, count, config->watermark,
+                                        wm.rx, wm.ry, wm.maxcol, wm.maxrow, wm.alpha, s);
     }
     if (mid) dev_free_on(mid, s);       // no host wait: parked behind an event when `s` is the caller's stream
     return rc;
