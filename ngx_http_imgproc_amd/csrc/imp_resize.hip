@@ -2502,6 +2502,185 @@ __global__ __launch_bounds__(256) void k_resize_area_rows4(RArgs a, AreaGeom gm,
     if (item < nitems) area_rows4_body<CN, W>(a, gm, frame, item, nstrips, bh, s_line[wv]);
 }
 
+// Cells wider than 20 source columns (shrinks past 18x: a 4032-wide photo at 200 and below): area_rows_body's walk with the
+// window W a RUNTIME argument (the widest horizontal cell, 21..66).  What that changes:
+//   * the weights are not held in registers: the horizontal reduction is a loop over the window, four pixels a turn, and
+//     every weight is picked from the cell's first / whole / last split as it is used (zero where the window is wider
+//     than the cell, and for the up to three pixels a turn of four reaches past the window);
+//   * the wave's segment of a source row is 63 * scale_x + W pixels, up to 16.5 KB: the LDS line is dynamic shared memory
+//     sized by the launcher (area_wide_plan), and a row comes in WIDE_PIECE granules per lane at a time -- the first piece
+//     one row ahead of the arithmetic, as there, the rest (segments over 4 KB) when the row is parked;
+//   * no tail: a finished row leaves as it is.
+// The float sequence is resizeArea_'s, as in every body above.  `line_dw` = the line's length in dwords.
+constexpr int WIDE_W_MIN = 4 * MIX_NV + 1, WIDE_W_MAX = 66;   // cells of 21..66 columns: factors up to 64
+constexpr int WIDE_PIECE = 4;                                  // 16-byte granules of a row a lane holds at a time
+template <int CN>
+__device__ __forceinline__ void area_wide_body(const RArgs& a, const AreaGeom& gm, int frame, int item, int nstrips, int bh,
+                                               int W, int line_dw, uint32_t* __restrict__ line) {
+    static_assert(CN == 3 || CN == 4, "interleaved BGR / BGRA");
+    const int lane = threadIdx.x & 63;
+    const int band = item / nstrips, strip = item - band * nstrips;
+    const int dy0 = band * bh;
+    if (dy0 >= a.dh) return;
+    const int dy1 = min(dy0 + bh, a.dh);
+    const bool live = strip * 64 + lane < a.dw;
+    const int dx = min(strip * 64 + lane, a.dw - 1);             // idle lanes shadow the last column
+    const AreaCell cx = area_cell(dx, a.sw, gm.scale_x);
+    const int xs = min(cx.first(), a.sw - W);                    // the window holds the whole cell and never leaves the row
+    // the cell in window places: whole pixels at [k1, k2), the partial ones at kf and kl (-1: none) -- cx.weight(xs + k)
+    const int k1 = cx.s1 - xs, k2 = cx.s2 - xs;
+    const int kf = cx.hf ? k1 - 1 : -1, kl = cx.hl ? k2 : -1;
+    auto weight = [&](int k) {
+        float w = (k >= k1 && k < k2) ? cx.am : 0.f;
+        w = k == kf ? cx.af : w;
+        return k == kl ? cx.al : w;
+    };
+    // the wave's segment in bytes of the source row, as in area_rows_body
+    const int row_end = (a.sw * CN + 3) & ~3;
+    const int b0 = min((__builtin_amdgcn_readlane(xs, 0) * CN) & ~15, (row_end - 16) & ~15);
+    const int ngran = ((__builtin_amdgcn_readlane(xs, 63) + W) * CN - b0 + 15) >> 4;
+    if (ngran * 4 + 4 > line_dw) return;                         // (never: area_wide_plan sizes the line for the longest segment)
+    const int wofs = xs * CN - b0;                               // this lane's window in the parked line, in bytes
+    const uint8_t* S = a.src + (long long)frame * a.src_stride + (size_t)b0;
+    // Every lane fetches whole pieces and parks them, with no predication: lanes past the segment repeat its last granule.
+    // When the last granule would leave the row's padded end it is moved back to end exactly there and the row is parked
+    // dword by dword (wave-uniform branch).
+    const bool ragged = b0 + 16 * ngran > row_end;
+    const int npieces = (ngran + 64 * WIDE_PIECE - 1) / (64 * WIDE_PIECE);
+    auto gran_ofs = [&](int j) {                                 // byte offset of this lane's j-th granule in the segment
+        const int gi = min(j * 64 + lane, ngran - 1);
+        return (ragged && gi == ngran - 1) ? row_end - 16 - b0 : gi * 16;
+    };
+    int gofs[WIDE_PIECE];
+#pragma unroll
+    for (int j = 0; j < WIDE_PIECE; j++) gofs[j] = gran_ofs(j);
+    uint32_t nxt[WIDE_PIECE][4];                                 // the first piece of the row ahead
+    auto fetch = [&](int sy) {
+        const uint8_t* row = S + (size_t)sy * a.sstep;
+#pragma unroll
+        for (int j = 0; j < WIDE_PIECE; j++) load_stream<4>(nxt[j], row + gofs[j]);
+    };
+    auto park = [&](const uint32_t (*q)[4], const int* ofs) {
+        if (!ragged) {
+#pragma unroll
+            for (int j = 0; j < WIDE_PIECE; j++) {
+                typedef unsigned int u32x4a_t __attribute__((ext_vector_type(4), aligned(16)));
+                const u32x4a_t v = {q[j][0], q[j][1], q[j][2], q[j][3]};
+                *(u32x4a_t*)(line + (ofs[j] >> 2)) = v;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < WIDE_PIECE; j++)
+#pragma unroll
+                for (int t = 0; t < 4; t++) line[(ofs[j] >> 2) + t] = q[j][t];
+        }
+    };
+    float b[CN];
+    auto reduce = [&](int sy) {                                  // park row sy: its first piece is in `nxt`, the rest comes now
+        asm volatile("" ::: "memory");
+        park(nxt, gofs);
+        const uint8_t* row = S + (size_t)sy * a.sstep;
+        for (int p = 1; p < npieces; p++) {
+            uint32_t more[WIDE_PIECE][4];
+            int mofs[WIDE_PIECE];
+#pragma unroll
+            for (int j = 0; j < WIDE_PIECE; j++) {
+                mofs[j] = gran_ofs(p * WIDE_PIECE + j);
+                load_stream<4>(more[j], row + mofs[j]);
+            }
+            park(more, mofs);
+        }
+        asm volatile("" ::: "memory");
+    };
+    auto hsum = [&]() {
+#pragma unroll
+        for (int c = 0; c < CN; c++) b[c] = 0.f;
+        if constexpr (CN == 4) {
+            const uint32_t* win = line + (wofs >> 2);
+            for (int k = 0; k < W; k += 4) {
+#pragma unroll
+                for (int t = 0; t < 4; t++) {
+                    const uint32_t px = win[k + t];
+                    const float al = weight(k + t);
+                    b[0] = __fadd_rn(b[0], __fmul_rn((float)(px & 0xff), al));
+                    b[1] = __fadd_rn(b[1], __fmul_rn((float)((px >> 8) & 0xff), al));
+                    b[2] = __fadd_rn(b[2], __fmul_rn((float)((px >> 16) & 0xff), al));
+                    b[3] = __fadd_rn(b[3], __fmul_rn((float)(px >> 24), al));
+                }
+            }
+        } else {
+            // four pixels = 12 bytes at a byte offset: four aligned dwords + v_alignbyte_b32, every (pixel, channel) a compile-time byte
+            const uint32_t* win = line + (wofs >> 2);
+            const unsigned sh = (unsigned)wofs & 3u;
+            for (int k = 0; k < W; k += 4, win += 3) {
+                uint32_t w[3];
+#pragma unroll
+                for (int i = 0; i < 3; i++) w[i] = __builtin_amdgcn_alignbyte(win[i + 1], win[i], sh);
+#pragma unroll
+                for (int t = 0; t < 4; t++) {
+                    const float al = weight(k + t);
+#pragma unroll
+                    for (int c = 0; c < 3; c++) {
+                        const int o = 3 * t + c;
+                        b[c] = __fadd_rn(b[c], __fmul_rn((float)((w[o >> 2] >> (8 * (o & 3))) & 0xff), al));
+                    }
+                }
+            }
+        }
+        asm volatile("" ::: "memory");
+    };
+
+    // rows: as in area_rows_body -- lane k works out the vertical cell of the band's k-th destination row (bh <= 64), the
+    // walk reads them back with v_readlane: scalar registers, scalar branches
+    const AreaCell mine = area_cell(min(dy0 + lane, dy1 - 1), a.sh, gm.scale_y);
+    const int sy_end = __builtin_amdgcn_readlane(mine.end(), dy1 - 1 - dy0);
+    uint8_t* D = a.dst + (long long)frame * a.dst_stride + (size_t)dx * CN;
+    int cur = -1;                                                // the source row `b` holds
+    for (int dy = dy0; dy < dy1; dy++) {
+        const int r = dy - dy0;
+        const int s1 = __builtin_amdgcn_readlane(mine.s1, r), s2 = __builtin_amdgcn_readlane(mine.s2, r);
+        const int hf = __builtin_amdgcn_readlane((int)mine.hf, r), hl = __builtin_amdgcn_readlane((int)mine.hl, r);
+        const float yaf = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mine.af), r));
+        const float yam = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mine.am), r));
+        const float yal = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mine.al), r));
+        const int first = hf ? s1 - 1 : s1, end = hl ? s2 + 1 : s2;
+        if (cur < 0) { fetch(first); cur = first - 1; }
+        float acc[CN];
+#pragma unroll
+        for (int c = 0; c < CN; c++) acc[c] = 0.f;
+        for (int sy = first; sy < end; sy++) {
+            while (cur < sy) {                                   // (cells are contiguous: this runs once, or not at all for a shared row)
+                cur++;
+                reduce(cur);
+                if (cur + 1 < sy_end) fetch(cur + 1);
+                hsum();
+            }
+            const float be = (hf && sy == s1 - 1) ? yaf : ((hl && sy == s2) ? yal : yam);
+#pragma unroll
+            for (int c = 0; c < CN; c++) acc[c] = __fadd_rn(acc[c], __fmul_rn(be, b[c]));
+        }
+        uint32_t px = 0;
+#pragma unroll
+        for (int c = 0; c < CN; c++) px = cvt_pk_u8(acc[c], px, c);
+        if (live) {
+            if constexpr (CN == 4) *(uint32_t*)(D + (size_t)dy * a.dstep) = px;
+            else store_bgr(D + (size_t)dy * a.dstep, px);
+        }
+    }
+}
+
+// `wpb` = waves per block (4; 2 when four of the longest lines would not fit 64 KB): a wave per item, a line per wave.
+template <int CN>
+__global__ __launch_bounds__(256) void k_resize_area_wide(RArgs a, AreaGeom gm, int W, int line_dw, int wpb, int nstrips, int bh, int nitems,
+                                                          int bpf, int count) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_wide[];
+    int frame, blk;
+    if (!frame_block(bpf, count, &frame, &blk)) return;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int item = blk * wpb + wv;
+    if (item < nitems) area_wide_body<CN>(a, gm, frame, item, nstrips, bh, W, line_dw, s_wide + wv * line_dw);
+}
+
 // Gray frames (one byte a pixel): the same walk with windows counted in BYTES.  A lane owns P adjacent destination columns
 // (P = 4 while the windows are at most five pixels, as above; P = 1 past that), a wave 64 * P.  Nothing is asked of the
 // source: a crop window starts at any byte and a gray pitch is any number, so every source row is fetched as the ALIGNED
@@ -2740,6 +2919,23 @@ __global__ __launch_bounds__(256) void k_resize_area_mix_tail(const MixTailDesc*
 #undef IMP_TAIL_W
         default: area_rows_body<CN, 20, true>(m.a, m.gm, 0, item, m.nstrips, m.rows, s_line[wv], t.tail, s_tile[wv], flat); break;
     }
+}
+
+// Colour frames whose cells span 21..66 source columns (area_wide_plan), of different geometry, in one launch: the
+// descriptor scheme around area_wide_body.  nv = the window W, rows = the band height, nblk = ceil(nitems / wpb).  A kernel
+// of its own: its lines are dynamic LDS sized for the longest segment of the launch (`line_dw` dwords each, `wpb` of them),
+// which k_resize_area_mix's frames never pay.
+template <int CN>
+__global__ __launch_bounds__(256) void k_resize_area_wide_mix(const MixDesc* __restrict__ d, MixIndex ix, int line_dw, int wpb) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_wide_mix[];
+    int blk;
+    const int di = mix_pick(d, ix, &blk);
+    if (di < 0) return;
+    const MixDesc& m = d[di];
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int item = blk * wpb + wv;
+    if (item >= m.nitems) return;
+    area_wide_body<CN>(m.a, m.gm, 0, item, m.nstrips, m.rows, m.nv, line_dw, s_wide_mix + wv * line_dw);
 }
 
 // ------------------------------------------------------------------ whole-factor AREA and NN over frames of DIFFERENT geometry
@@ -3012,6 +3208,35 @@ static bool gray_rows_plan(int sw, int dw, int dh, double scale_x, long long fra
     return true;
 }
 
+// area_wide_body for this frame?  The one acceptance rule of k_resize_area_wide (launch_cn) and k_resize_area_wide_mix
+// (launch_resize_mixed): a general INTER_AREA shrink of a colour frame whose source rows are 4-byte aligned and whose
+// widest horizontal cell spans 21..66 source columns (factors up to 64; narrower cells belong to the bodies with
+// compile-time windows, wider ones and gray frames stay with k_resize_area and its tables).  *w = that widest cell, *bh as
+// area_rows_plan picks it, *line_bytes = a wave's LDS line: the longest segment a strip can have -- lane 63's window
+// starts less than 63 * scale_x + 2 pixels after lane 0's -- with the granule rounding at both ends (30 bytes), plus the
+// 16 bytes a last turn of four pixels and a BGR window's look-ahead dword may read past it, rounded up.
+static bool area_wide_plan(int sw, int sh, int dw, int dh, int cn, int interp, const uint8_t* src, int sstep, long long src_stride,
+                           long long frames, int* w, int* bh, int* line_bytes) {
+    (void)sh;
+    if (interp != IMP_INTER_AREA || (cn != 3 && cn != 4) || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || dw > sw || dh > sh) return false;
+    if (((uintptr_t)src | (uintptr_t)sstep | (uintptr_t)src_stride) & 3) return false;
+    const double scale_x = 1. / ((double)dw / sw), scale_y = 1. / ((double)dh / sh);
+    if (std::fabs(scale_x - std::lrint(scale_x)) < 2.220446049250313e-16 && std::fabs(scale_y - std::lrint(scale_y)) < 2.220446049250313e-16)
+        return false;                                      // resizeAreaFast_: the box kernels' arithmetic
+    if (scale_x > 70) return false;                        // (no cell of 66 columns or fewer: the axis need not be walked)
+    const int ww = area_max_count(sw, dw, scale_x);
+    if (ww < WIDE_W_MIN || ww > WIDE_W_MAX || sw < ww) return false;
+    int b = 16;
+    const long long nstrips = (dw + 63) / 64;
+    while (b > 4 && frames * nstrips * ((dh + b - 1) / b) < 4096) b /= 2;
+    while (b > 1 && frames * nstrips * ((dh + b - 1) / b) < 1024) b /= 2;
+    *w = ww;
+    *bh = b;
+    *line_bytes = ((((int)std::ceil(63 * scale_x) + ww + 2) * cn + 30 + 15) & ~15) + 32;
+    return true;
+}
+constexpr int wide_wpb(int line_bytes) { return 4 * line_bytes <= 65536 ? 4 : 2; }   // waves (= lines) per block: 64 KB of LDS at most
+
 template <int CN, int W>
 static void launch_area_rows(int w, dim3 grid, hipStream_t s, const RArgs& a, const AreaGeom& gm, int nstrips, int bh, int nitems,
                              int bpf, int count, const AreaTail& tail) {
@@ -3159,7 +3384,22 @@ static int launch_cn(const RArgs& a, int count, int interp, double scale_x, doub
                 IMP_HIP(hipGetLastError());
                 return IMP_OK;
             }
-            // everything else (gray frames, cells wider than 20 columns): run tables, one output per lane
+            // BGRA / BGR with cells of 21..66 source columns (shrinks past 18x, up to 64x): the same walk with a runtime
+            // window and a dynamic LDS line -- no table either
+            if constexpr (CN == 3 || CN == 4) {
+                int w = 0, bh = 0, line_bytes = 0;
+                if (area_wide_plan(a.sw, a.sh, a.dw, a.dh, CN, interp, a.src, a.sstep, a.src_stride, count, &w, &bh, &line_bytes)) {
+                    const int wpb = wide_wpb(line_bytes);
+                    const int nstrips = (a.dw + 63) / 64, nitems = nstrips * ((a.dh + bh - 1) / bh), wbpf = (nitems + wpb - 1) / wpb;
+                    const dim3 wgrid((unsigned)wbpf, (unsigned)((count + 7) / 8 * 8));
+                    hipLaunchKernelGGL((k_resize_area_wide<CN>), wgrid, dim3(64 * wpb), (size_t)wpb * line_bytes, s, a, gm, w, line_bytes / 4, wpb,
+                                       nstrips, bh, nitems, wbpf, count);
+                    IMP_HIP(hipGetLastError());
+                    return IMP_OK;
+                }
+            }
+            // everything else (gray frames, BGR rows that are not 4-byte aligned, cells wider than 66 columns): run tables,
+            // one output per lane
             TableSet ts;
             if (int rc = get_tables(interp, a.sw, a.sh, a.dw, a.dh, scale_x, scale_y, s, &ts)) return rc;
             hipLaunchKernelGGL((k_resize_area<CN>), grid, block, 0, s, a, ts.area);
@@ -3562,11 +3802,13 @@ int launch_cv_resize(const Frames& f, int interp, hipStream_t s) {
 
 // Resize() over `count` frames of different geometry with as few launches as the mix allows.  Per frame the
 // interpolation is the reference's (bridge.c:183-193) and the arithmetic is launch_cv_resize's: frames that take the
-// general AREA path (every non-integer shrink whose cells span at most 16 source columns) are gathered into a descriptor
-// launch with their weights computed in the kernel, whole-factor AREA frames (any channel count) into a k_area_int_mix
-// launch and NN frames into a k_resize_nn_mix launch; a frame that is the only one of its kind, and the rest
-// (enlargements, extreme ratios) go one launch each on the same stream.  Gray frames are gathered like colour ones:
-// their general AREA shrinks ride k_resize_area_mix<1> whatever their pointers and pitches are.
+// general AREA path (every non-integer shrink whose cells span at most 20 source columns) are gathered into a descriptor
+// launch with their weights computed in the kernel, colour frames whose cells span 21..66 columns (area_wide_plan:
+// shrinks past 18x, up to 64x) into a k_resize_area_wide_mix launch, whole-factor AREA frames (any channel count) into a
+// k_area_int_mix launch and NN frames into a k_resize_nn_mix launch -- four launches at most, three for gray; a frame
+// that is the only one of its kind, and the rest (enlargements; extreme ratios: cells past 20 columns for gray frames and
+// BGR rows that are not 4-byte aligned, past 66 for colour) go one launch each on the same stream.  Gray frames are
+// gathered like colour ones: their general AREA shrinks ride k_resize_area_mix<1> whatever their pointers and pitches are.
 // Blocks differ a hundredfold in work (a 4K source against a 256-pixel one, same 224-wide output): the frames go
 // longest first to the XCD list with the least source bytes so far, so each list starts with its heavy frames and
 // the launch's tail is made of light ones.  `v` is consumed; *sorted holds the descriptors list by list, *most = the
@@ -3665,6 +3907,24 @@ static int launch_nn_mix(std::vector<NnMixDesc>& v, int cn, hipStream_t s) {
     return IMP_OK;
 }
 
+// Frames area_wide_plan accepts, two or more: every line of the launch is as long as the longest one present.
+static int launch_wide_mix(std::vector<MixDesc>& v, int cn, int line_bytes, hipStream_t s) {
+    const int wpb = wide_wpb(line_bytes);
+    for (MixDesc& d : v) d.nblk = (d.nitems + wpb - 1) / wpb;
+    void* dev = nullptr;
+    MixIndex ix{};
+    dim3 grid;
+    if (int rc = mix_table(v, s, &dev, &ix, &grid)) return rc;                // (longest source first)
+    const dim3 block(64 * wpb);
+    const size_t lds = (size_t)wpb * line_bytes;
+    if (cn == 4) hipLaunchKernelGGL((k_resize_area_wide_mix<4>), grid, block, lds, s, (const MixDesc*)dev, ix, line_bytes / 4, wpb);
+    else hipLaunchKernelGGL((k_resize_area_wide_mix<3>), grid, block, lds, s, (const MixDesc*)dev, ix, line_bytes / 4, wpb);
+    const hipError_t e = hipGetLastError();
+    dev_free_on(dev, s);
+    IMP_HIP(e);
+    return IMP_OK;
+}
+
 int launch_resize_mixed(const MixFrame* fr, int count, int cn, int simple, hipStream_t s) {
     if (count <= 0) return IMP_OK;
     if (!fr || (cn != 1 && cn != 3 && cn != 4)) return IMP_ERROR_INVALID_ARGS;
@@ -3676,7 +3936,9 @@ int launch_resize_mixed(const MixFrame* fr, int count, int cn, int simple, hipSt
     std::vector<MixDesc> gathered_frames;
     std::vector<IntMixDesc> int_frames;                    // whole-factor AREA (resizeAreaFast_), any channel count
     std::vector<NnMixDesc> nn_frames;
-    int int_one = -1, nn_one = -1, gray_one = -1;          // the frame of a vector that holds exactly one
+    std::vector<MixDesc> wide_frames;                      // colour, cells of 21..66 source columns (area_wide_plan)
+    int wide_line = 0;                                     // the longest LDS line among them, in bytes
+    int int_one = -1, nn_one = -1, gray_one = -1, wide_one = -1;   // the frame of a vector that holds exactly one
     gathered_frames.reserve(count);
     auto lone = [&](const MixFrame& f, int interp) {
         Frames one{};
@@ -3743,6 +4005,15 @@ int launch_resize_mixed(const MixFrame* fr, int count, int cn, int simple, hipSt
                 }
             }
             if (gathered) gathered_frames.push_back(d);
+            int line_bytes = 0;
+            if (!gathered && area_wide_plan(f.sw, f.sh, f.dw, f.dh, cn, interp, f.src, f.sstep, 0, count, &d.nv, &d.rows, &line_bytes)) {
+                d.nstrips = (f.dw + 63) / 64;
+                d.nitems = d.nstrips * ((f.dh + d.rows - 1) / d.rows);       // (nblk: launch_wide_mix, once the longest line is known)
+                wide_frames.push_back(d);
+                wide_line = std::max(wide_line, line_bytes);
+                wide_one = i;
+                gathered = true;
+            }
         }
         if (interp == IMP_INTER_AREA && !whole && cn == 1) {
             // gray: any pointer, any pitch (the body aligns its own fetches); the window decides
@@ -3773,6 +4044,11 @@ int launch_resize_mixed(const MixFrame* fr, int count, int cn, int simple, hipSt
         if (int rc = lone(fr[nn_one], IMP_INTER_NN)) return rc;
     } else if (!nn_frames.empty()) {
         if (int rc = launch_nn_mix(nn_frames, cn, s)) return rc;
+    }
+    if (wide_frames.size() == 1) {
+        if (int rc = lone(fr[wide_one], IMP_INTER_AREA)) return rc;
+    } else if (!wide_frames.empty()) {
+        if (int rc = launch_wide_mix(wide_frames, cn, wide_line, s)) return rc;
     }
     if (cn == 1 && gathered_frames.size() == 1) return lone(fr[gray_one], IMP_INTER_AREA);      // (k_resize_area<1> and its tables)
     return launch_mix(gathered_frames, cn, s);
