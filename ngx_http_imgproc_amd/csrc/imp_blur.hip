@@ -1084,34 +1084,23 @@ int launch_blur_mixed(const BlurItem* items, int count, int cn, hipStream_t s) {
     void* dev_k = nullptr;
     if (int rc = upload_small(blob.data(), blob.size() * 4, &dev_k, s)) return rc;
     const int* taps = (const int*)dev_k;
-    hipError_t e = hipSuccess;
+    hipError_t e = hipSuccess;                              // lds_limit_once's verdict: no launch without it
     int rc = IMP_OK;
-    for (int k = 0; k < 3 && rc == IMP_OK && e == hipSuccess; k++) {
-        if (v[k].empty()) continue;
-        std::vector<BlurDesc> sorted;
-        MixIndex ix{};
-        int most = 0;
-        mix_deal(v[k], [](BlurDesc& d) -> BlurDesc& { return d; }, [](BlurDesc& d) { return (long long)d.w * d.h * (2 * d.r + 1); },
-                 &sorted, &ix, &most);
-        void* dev_d = nullptr;
-        if ((rc = upload_small(sorted.data(), sorted.size() * sizeof(BlurDesc), &dev_d, s))) break;
-        const dim3 grid((unsigned)most * 8), block(256);
-        const BlurDesc* dd = (const BlurDesc*)dev_d;
-#define IMP_BLUR_MIX(CN_, F_, W_)                                                                                  \
-    do {                                                                                                           \
-        e = lds_limit_once<k_blur_mix<CN_, F_, W_>>();                                                             \
-        if (e == hipSuccess) hipLaunchKernelGGL((k_blur_mix<CN_, F_, W_>), grid, block, lds[k], s, dd, ix, taps);  \
+    for (int k = 0; k < 3 && rc == IMP_OK && e == hipSuccess; k++)
+        rc = mix_launch(v[k], [](BlurDesc& d) { return (long long)d.w * d.h * (2 * d.r + 1); }, s, [&](dim3 grid, const BlurDesc* dd, const MixIndex& ix) {
+#define IMP_BLUR_MIX(CN_, F_, W_)                                                                                      \
+    do {                                                                                                               \
+        e = lds_limit_once<k_blur_mix<CN_, F_, W_>>();                                                                 \
+        if (e == hipSuccess) hipLaunchKernelGGL((k_blur_mix<CN_, F_, W_>), grid, dim3(256), lds[k], s, dd, ix, taps);  \
     } while (0)
-        if (cn == 4) {
-            if (k == 0) IMP_BLUR_MIX(4, BF_FUSED4, false); else if (k == 1) IMP_BLUR_MIX(4, BF_MFMA, false); else IMP_BLUR_MIX(4, BF_MFMA, true);
-        } else {
-            if (k == 0) IMP_BLUR_MIX(3, BF_FUSED4, false); else if (k == 1) IMP_BLUR_MIX(3, BF_MFMA, false); else IMP_BLUR_MIX(3, BF_MFMA, true);
-        }
+            if (cn == 4) {
+                if (k == 0) IMP_BLUR_MIX(4, BF_FUSED4, false); else if (k == 1) IMP_BLUR_MIX(4, BF_MFMA, false); else IMP_BLUR_MIX(4, BF_MFMA, true);
+            } else {
+                if (k == 0) IMP_BLUR_MIX(3, BF_FUSED4, false); else if (k == 1) IMP_BLUR_MIX(3, BF_MFMA, false); else IMP_BLUR_MIX(3, BF_MFMA, true);
+            }
 #undef IMP_BLUR_MIX
-        if (e == hipSuccess) e = hipGetLastError();
-        dev_free_on(dev_d, s);
-    }
-    dev_free_on(dev_k, s);
+        });
+    dev_free_on(dev_k, s);                                  // (the kernel blob the three launches share)
     if (rc) return rc;
     if (e != hipSuccess) { set_error("k_blur_mix", e); return IMP_ERROR_DEVICE; }
     return IMP_OK;

@@ -377,19 +377,10 @@ int launch_geom_mixed(const GeomItem* items, int count, int cn, hipStream_t s) {
         d.nblk = (int)(((long long)it.dw * it.dh + GEOM_PIX - 1) / GEOM_PIX);
         v.push_back(d);
     }
-    std::vector<GeomDesc> sorted;
-    MixIndex ix{};
-    int most = 0;
-    mix_deal(v, [](GeomDesc& d) -> GeomDesc& { return d; }, [](GeomDesc& d) { return (long long)d.dw * d.dh; }, &sorted, &ix, &most);
-    void* dev = nullptr;
-    if (int rc = upload_small(sorted.data(), sorted.size() * sizeof(GeomDesc), &dev, s)) return rc;
-    const dim3 grid((unsigned)most * 8), block(256);
-    if (cn == 4) hipLaunchKernelGGL((k_geom_mix<4>), grid, block, 0, s, (const GeomDesc*)dev, ix);
-    else hipLaunchKernelGGL((k_geom_mix<3>), grid, block, 0, s, (const GeomDesc*)dev, ix);
-    const hipError_t e = hipGetLastError();
-    dev_free_on(dev, s);
-    IMP_HIP(e);
-    return IMP_OK;
+    return mix_launch(v, [](GeomDesc& d) { return (long long)d.dw * d.dh; }, s, [&](dim3 grid, const GeomDesc* dev, const MixIndex& ix) {
+        if (cn == 4) hipLaunchKernelGGL((k_geom_mix<4>), grid, dim3(256), 0, s, dev, ix);
+        else hipLaunchKernelGGL((k_geom_mix<3>), grid, dim3(256), 0, s, dev, ix);
+    });
 }
 
 // ---- cvCvtColor(GRAY2BGR) of frames of different geometry (the gray requests of impgpu_batch_run_ops) ----
@@ -448,17 +439,9 @@ int launch_gray2bgr_mixed(const Gray2BgrItem* items, int count, hipStream_t s) {
         d.nblk = (int)(((long long)((it.w + 3) / 4) * it.h + G2B_GROUPS - 1) / G2B_GROUPS);
         v.push_back(d);
     }
-    std::vector<Gray2BgrDesc> sorted;
-    MixIndex ix{};
-    int most = 0;
-    mix_deal(v, [](Gray2BgrDesc& d) -> Gray2BgrDesc& { return d; }, [](Gray2BgrDesc& d) { return (long long)d.w * d.h; }, &sorted, &ix, &most);
-    void* dev = nullptr;
-    if (int rc = upload_small(sorted.data(), sorted.size() * sizeof(Gray2BgrDesc), &dev, s)) return rc;
-    hipLaunchKernelGGL(k_gray2bgr_mix, dim3((unsigned)most * 8), dim3(256), 0, s, (const Gray2BgrDesc*)dev, ix);
-    const hipError_t e = hipGetLastError();
-    dev_free_on(dev, s);
-    IMP_HIP(e);
-    return IMP_OK;
+    return mix_launch(v, [](Gray2BgrDesc& d) { return (long long)d.w * d.h; }, s, [&](dim3 grid, const Gray2BgrDesc* dev, const MixIndex& ix) {
+        hipLaunchKernelGGL(k_gray2bgr_mix, grid, dim3(256), 0, s, dev, ix);
+    });
 }
 
 int launch_gray2bgr(const Frames& f, hipStream_t s) {

@@ -5,6 +5,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 #include "../../include/impgpu.h"
@@ -397,7 +398,42 @@ void mix_deal(std::vector<D>& v, M desc, C cost, std::vector<D>* sorted_out, Mix
     v.clear();
     *most_out = most;
 }
+// Where a blob that travels behind a table of `n` descriptors starts (mix_launch's `blob`).
+template <class D>
+constexpr size_t mix_blob_offset(size_t n) { return (n * sizeof(D) + 15) & ~size_t(15); }
 #ifdef __HIPCC__
+// One launch over the descriptors `v` (consumed; none: no launch): deal them (mix_deal), upload the table -- with `blob`
+// behind it in the same allocation, at mix_blob_offset, when one is given -- let `launch(grid, table, ix)` issue the
+// kernel on `s` over the grid of 8 * most workgroups, and free the table behind the launch.  The table is freed even
+// when the launch failed, and the launch's error is the one reported: the rule every mixed launch shares, said here once.
+template <class D, class M, class C, class L>
+int mix_launch(std::vector<D>& v, M desc, C cost, hipStream_t s, L launch, const std::vector<uint8_t>* blob = nullptr) {
+    if (v.empty()) return IMP_OK;
+    std::vector<D> sorted;
+    MixIndex ix{};
+    int most = 0;
+    mix_deal(v, desc, cost, &sorted, &ix, &most);
+    void* table = nullptr;
+    if (blob) {
+        const size_t dbytes = mix_blob_offset<D>(sorted.size());
+        std::vector<uint8_t> both(dbytes + blob->size(), 0);
+        std::memcpy(both.data(), sorted.data(), sorted.size() * sizeof(D));
+        std::memcpy(both.data() + dbytes, blob->data(), blob->size());
+        if (int rc = upload_small(both.data(), both.size(), &table, s)) return rc;
+    } else if (int rc = upload_small(sorted.data(), sorted.size() * sizeof(D), &table, s)) {
+        return rc;
+    }
+    launch(dim3((unsigned)most * 8), (const D*)table, ix);
+    const hipError_t e = hipGetLastError();
+    dev_free_on(table, s);
+    IMP_HIP(e);
+    return IMP_OK;
+}
+// the same for descriptors that hold `first` and `nblk` themselves
+template <class D, class C, class L>
+int mix_launch(std::vector<D>& v, C cost, hipStream_t s, L launch, const std::vector<uint8_t>* blob = nullptr) {
+    return mix_launch(v, [](D& d) -> D& { return d; }, cost, s, launch, blob);
+}
 // The descriptor of this workgroup (its index; -1: none, the workgroup returns) and the workgroup's index inside it;
 // `desc(d)` names the part of a descriptor holding `first` and `nblk`, as in mix_deal.  An index rather than a pointer: the
 // callers read the descriptor as d[i], which keeps its fields in scalar registers.

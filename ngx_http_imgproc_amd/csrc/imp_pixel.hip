@@ -585,18 +585,6 @@ static int tail_desc(const PixelTailItem& it, int cn, std::vector<uint8_t>* tabl
     return IMP_OK;
 }
 
-// descriptors | tables as one blob in pool memory
-template <class D>
-static int upload_descs(const std::vector<D>& sorted, const std::vector<uint8_t>& tables, void** dev, const uint8_t** dt, hipStream_t s) {
-    const size_t dbytes = (sorted.size() * sizeof(D) + 15) & ~size_t(15);
-    std::vector<uint8_t> blob(dbytes + tables.size(), 0);
-    std::memcpy(blob.data(), sorted.data(), sorted.size() * sizeof(D));
-    std::memcpy(blob.data() + dbytes, tables.data(), tables.size());
-    if (int rc = upload_small(blob.data(), blob.size(), dev, s)) return rc;
-    *dt = (const uint8_t*)*dev + dbytes;
-    return IMP_OK;
-}
-
 int launch_pixel_tail_mixed(const PixelTailItem* items, int count, int cn, hipStream_t s) {
     if (count <= 0) return IMP_OK;
     if (!items || (cn != 3 && cn != 4)) return IMP_ERROR_INVALID_ARGS;
@@ -609,25 +597,17 @@ int launch_pixel_tail_mixed(const PixelTailItem* items, int count, int cn, hipSt
         if (work) v[vig ? 1 : 0].push_back(d);
     }
     if (tables.empty()) tables.resize(16, 0);
-    for (int vig = 0; vig < 2; vig++) {
-        if (v[vig].empty()) continue;
-        std::vector<PixTailDesc> sorted;
-        MixIndex ix{};
-        int most = 0;
-        mix_deal(v[vig], [](PixTailDesc& d) -> PixTailDesc& { return d; }, [](PixTailDesc& d) { return (long long)d.w * d.h; },
-                 &sorted, &ix, &most);
-        void* dev = nullptr;
-        const uint8_t* dt = nullptr;
-        if (int rc = upload_descs(sorted, tables, &dev, &dt, s)) return rc;
-        const PixTailDesc* dd = (const PixTailDesc*)dev;
-        const dim3 grid((unsigned)most * 8), block(256);
-        if (cn == 4 && vig) hipLaunchKernelGGL((k_pixel_tail_mix<4, true>), grid, block, 0, s, dd, ix, dt);
-        else if (cn == 4) hipLaunchKernelGGL((k_pixel_tail_mix<4, false>), grid, block, 0, s, dd, ix, dt);
-        else if (vig) hipLaunchKernelGGL((k_pixel_tail_mix<3, true>), grid, block, 0, s, dd, ix, dt);
-        else hipLaunchKernelGGL((k_pixel_tail_mix<3, false>), grid, block, 0, s, dd, ix, dt);
-        const hipError_t e = hipGetLastError();
-        dev_free_on(dev, s);
-        if (e != hipSuccess) { set_error("k_pixel_tail_mix", e); return IMP_ERROR_DEVICE; }
+    for (int vig = 0; vig < 2; vig++) {                    // descriptors | tables as one blob in pool memory
+        const size_t dbytes = mix_blob_offset<PixTailDesc>(v[vig].size());
+        const int rc = mix_launch(v[vig], [](PixTailDesc& d) { return (long long)d.w * d.h; }, s, [&](dim3 grid, const PixTailDesc* dd, const MixIndex& ix) {
+            const uint8_t* dt = (const uint8_t*)dd + dbytes;
+            const dim3 block(256);
+            if (cn == 4 && vig) hipLaunchKernelGGL((k_pixel_tail_mix<4, true>), grid, block, 0, s, dd, ix, dt);
+            else if (cn == 4) hipLaunchKernelGGL((k_pixel_tail_mix<4, false>), grid, block, 0, s, dd, ix, dt);
+            else if (vig) hipLaunchKernelGGL((k_pixel_tail_mix<3, true>), grid, block, 0, s, dd, ix, dt);
+            else hipLaunchKernelGGL((k_pixel_tail_mix<3, false>), grid, block, 0, s, dd, ix, dt);
+        }, &tables);
+        if (rc) return rc;
     }
     return IMP_OK;
 }
@@ -650,25 +630,18 @@ int launch_window_mixed(const WindowItem* items, int count, int cn, hipStream_t 
         v[vig ? 1 : 0].push_back(d);
     }
     if (tables.empty()) tables.resize(16, 0);
-    for (int vig = 0; vig < 2; vig++) {
-        if (v[vig].empty()) continue;
-        std::vector<WindowDesc> sorted;
-        MixIndex ix{};
-        int most = 0;
-        mix_deal(v[vig], [](WindowDesc& d) -> PixTailDesc& { return d.t; }, [](WindowDesc& d) { return (long long)d.t.w * d.t.h; },
-                 &sorted, &ix, &most);
-        void* dev = nullptr;
-        const uint8_t* dt = nullptr;
-        if (int rc = upload_descs(sorted, tables, &dev, &dt, s)) return rc;
-        const WindowDesc* dd = (const WindowDesc*)dev;
-        const dim3 grid((unsigned)most * 8), block(256);
-        if (cn == 4 && vig) hipLaunchKernelGGL((k_window_mix<4, true>), grid, block, 0, s, dd, ix, dt);
-        else if (cn == 4) hipLaunchKernelGGL((k_window_mix<4, false>), grid, block, 0, s, dd, ix, dt);
-        else if (vig) hipLaunchKernelGGL((k_window_mix<3, true>), grid, block, 0, s, dd, ix, dt);
-        else hipLaunchKernelGGL((k_window_mix<3, false>), grid, block, 0, s, dd, ix, dt);
-        const hipError_t e = hipGetLastError();
-        dev_free_on(dev, s);
-        if (e != hipSuccess) { set_error("k_window_mix", e); return IMP_ERROR_DEVICE; }
+    for (int vig = 0; vig < 2; vig++) {                    // descriptors | tables as one blob in pool memory
+        const size_t dbytes = mix_blob_offset<WindowDesc>(v[vig].size());
+        const int rc = mix_launch(v[vig], [](WindowDesc& d) -> PixTailDesc& { return d.t; }, [](WindowDesc& d) { return (long long)d.t.w * d.t.h; }, s,
+                                  [&](dim3 grid, const WindowDesc* dd, const MixIndex& ix) {
+            const uint8_t* dt = (const uint8_t*)dd + dbytes;
+            const dim3 block(256);
+            if (cn == 4 && vig) hipLaunchKernelGGL((k_window_mix<4, true>), grid, block, 0, s, dd, ix, dt);
+            else if (cn == 4) hipLaunchKernelGGL((k_window_mix<4, false>), grid, block, 0, s, dd, ix, dt);
+            else if (vig) hipLaunchKernelGGL((k_window_mix<3, true>), grid, block, 0, s, dd, ix, dt);
+            else hipLaunchKernelGGL((k_window_mix<3, false>), grid, block, 0, s, dd, ix, dt);
+        }, &tables);
+        if (rc) return rc;
     }
     return IMP_OK;
 }

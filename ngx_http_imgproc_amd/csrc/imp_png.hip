@@ -390,22 +390,13 @@ __global__ __launch_bounds__(256) void k_png_place(const PngPlaceDesc* __restric
 
 // the descriptors of one channel count: ONE launch
 static int launch_png_place(std::vector<PngPlaceDesc>& v, int c, hipStream_t s) {
-    if (v.empty()) return IMP_OK;
     for (PngPlaceDesc& d : v) d.nblk = (int)(((long long)((d.w + 3) >> 2) * d.h + PLACE_QUADS - 1) / PLACE_QUADS);
-    std::vector<PngPlaceDesc> sorted;
-    MixIndex ix{};
-    int most = 0;
-    mix_deal(v, [](PngPlaceDesc& d) -> PngPlaceDesc& { return d; }, [](PngPlaceDesc& d) { return (long long)d.w * d.h; }, &sorted, &ix, &most);
-    void* dev = nullptr;
-    if (int rc = upload_small(sorted.data(), sorted.size() * sizeof(PngPlaceDesc), &dev, s)) return rc;
-    const dim3 grid((unsigned)most * 8), block(256);
-    if (c == 4) hipLaunchKernelGGL(k_png_place<4>, grid, block, 0, s, (const PngPlaceDesc*)dev, ix);
-    else if (c == 3) hipLaunchKernelGGL(k_png_place<3>, grid, block, 0, s, (const PngPlaceDesc*)dev, ix);
-    else hipLaunchKernelGGL(k_png_place<1>, grid, block, 0, s, (const PngPlaceDesc*)dev, ix);
-    const hipError_t e = hipGetLastError();
-    dev_free(dev);                                                   // (handed out again in lane-stream order)
-    if (e != hipSuccess) { set_error("k_png_place", e); return IMP_ERROR_DEVICE; }
-    return IMP_OK;
+    // (`s` is the lane's stream: the table is handed out again in lane-stream order)
+    return mix_launch(v, [](PngPlaceDesc& d) { return (long long)d.w * d.h; }, s, [&](dim3 grid, const PngPlaceDesc* dev, const MixIndex& ix) {
+        if (c == 4) hipLaunchKernelGGL(k_png_place<4>, grid, dim3(256), 0, s, dev, ix);
+        else if (c == 3) hipLaunchKernelGGL(k_png_place<3>, grid, dim3(256), 0, s, dev, ix);
+        else hipLaunchKernelGGL(k_png_place<1>, grid, dim3(256), 0, s, dev, ix);
+    });
 }
 
 // ---- impgpu_batch_decode_png: many files, one set of launches

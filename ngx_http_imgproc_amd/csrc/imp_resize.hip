@@ -17,12 +17,14 @@
 // row are one (4-byte aligned) 8/16/32-byte vector load per lane.  The per-geometry weight
 // tables (a few KB, built on the host in imp_tables.cpp) stay L1/L2 resident.
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdlib>
 #include <map>
 #include <set>
 #include <mutex>
 #include <tuple>
+#include <type_traits>
 #include "imp_internal.h"
 
 namespace imp {
@@ -3168,21 +3170,55 @@ static int get_tables(int interp, int sw, int sh, int dw, int dh, double scale_x
 }
 
 // ------------------------------------------------------------------ launcher
-// k_resize_area_rows for this geometry?  *w = window (the widest horizontal cell, widened until a wave's segment fits its
-// 64 * ceil(W/4) granules), *bh = destination rows per band: 16, less while that leaves fewer than ~4096 waves (down to 4:
+// Small host-side rules every launcher below shares.
+// resizeAreaFast_'s test in OpenCV's resize: both factors are whole numbers -- the box kernels' arithmetic
+static bool whole_factors(double scale_x, double scale_y) {
+    return std::fabs(scale_x - std::lrint(scale_x)) < DBL_EPSILON && std::fabs(scale_y - std::lrint(scale_y)) < DBL_EPSILON;
+}
+// Destination rows per band of the row-streaming AREA bodies: 16, less while that leaves fewer than ~4096 waves (down to 4:
 // a band re-reads one source row of its neighbour) or, for a lone request, fewer than ~1024 (down to 1: latency first).
+static int area_band_height(long long frames, long long nstrips, int dh) {
+    int b = 16;
+    while (b > 4 && frames * nstrips * ((dh + b - 1) / b) < 4096) b /= 2;
+    while (b > 1 && frames * nstrips * ((dh + b - 1) / b) < 1024) b /= 2;
+    return b;
+}
+// A frame's split for the row-streaming bodies: strips of `cols` destination columns, bands of `bh` rows, an item (a wave's
+// work) per strip and band, `wpb` items per block.
+struct RowSplit { int nstrips, bh, nitems, nblk; };
+static RowSplit row_split(int dw, int dh, int cols, int bh, int wpb = 4) {
+    RowSplit r{};
+    r.nstrips = (dw + cols - 1) / cols;
+    r.bh = bh;
+    r.nitems = r.nstrips * ((dh + bh - 1) / bh);
+    r.nblk = (r.nitems + wpb - 1) / wpb;
+    return r;
+}
+static unsigned round_up8(int count) { return (unsigned)((count + 7) / 8 * 8); }   // whole groups of 8 frames (frame-per-XCD order)
+static RArgs rargs(const Frames& f) { return RArgs{f.src, f.src_stride, f.v.step, f.v.w, f.v.h, f.dst, f.dst_stride, f.dstep, f.dw, f.dh}; }
+static RArgs rargs(const MixFrame& f) { return RArgs{f.src, 0, f.sstep, f.sw, f.sh, f.dst, 0, f.dstep, f.dw, f.dh}; }
+static int launched() {
+    IMP_HIP(hipGetLastError());
+    return IMP_OK;
+}
+// A runtime int in [Lo, Hi] as a compile-time constant: f(K) with K() == v; a value below the range takes Lo, one above it Hi.
+template <int Lo, int Hi, class F>
+static void with_const(int v, F f) {
+    if constexpr (Lo == Hi) f(std::integral_constant<int, Lo>{});
+    else if (v <= Lo) f(std::integral_constant<int, Lo>{});
+    else with_const<Lo + 1, Hi>(v, f);
+}
+
+// k_resize_area_rows for this geometry?  *w = window (the widest horizontal cell, widened until a wave's segment fits its
+// 64 * ceil(W/4) granules), *bh = destination rows per band (area_band_height).
 static bool area_rows_plan(int sw, int sh, int dw, int dh, double scale_x, long long frames, bool even, int* w, int* bh) {
     (void)sh;
     int ww = area_max_count(sw, dw, scale_x);
     if (even) ww += ww & 1;                                // the mixed-geometry kernel carries the even windows only
     while (ww <= 4 * MIX_NV && 63 * scale_x + ww + 8 > 256 * ((ww + 3) / 4)) ww += even ? 2 : 1;
     if (ww < 1 || ww > 4 * MIX_NV || sw < ww || sw < 4) return false;
-    int b = 16;
-    const long long nstrips = (dw + 63) / 64;
-    while (b > 4 && frames * nstrips * ((dh + b - 1) / b) < 4096) b /= 2;
-    while (b > 1 && frames * nstrips * ((dh + b - 1) / b) < 1024) b /= 2;
     *w = ww;
-    *bh = b;
+    *bh = area_band_height(frames, (dw + 63) / 64, dh);
     return true;
 }
 
@@ -3198,13 +3234,9 @@ static bool gray_rows_plan(int sw, int dw, int dh, double scale_x, long long fra
         while (ww <= GRAY_W_MAX && !fits(ww, 1)) ww += 2;
     }
     if (ww > GRAY_W_MAX) return false;                     // (a row narrower than the window is fine: the body clips its fetch)
-    int b = 16;
-    const long long nstrips = (dw + 64 * pp - 1) / (64 * pp);
-    while (b > 4 && frames * nstrips * ((dh + b - 1) / b) < 4096) b /= 2;
-    while (b > 1 && frames * nstrips * ((dh + b - 1) / b) < 1024) b /= 2;
     *w = ww;
     *p = pp;
-    *bh = b;
+    *bh = area_band_height(frames, (dw + 64 * pp - 1) / (64 * pp), dh);
     return true;
 }
 
@@ -3221,29 +3253,23 @@ static bool area_wide_plan(int sw, int sh, int dw, int dh, int cn, int interp, c
     if (interp != IMP_INTER_AREA || (cn != 3 && cn != 4) || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || dw > sw || dh > sh) return false;
     if (((uintptr_t)src | (uintptr_t)sstep | (uintptr_t)src_stride) & 3) return false;
     const double scale_x = 1. / ((double)dw / sw), scale_y = 1. / ((double)dh / sh);
-    if (std::fabs(scale_x - std::lrint(scale_x)) < 2.220446049250313e-16 && std::fabs(scale_y - std::lrint(scale_y)) < 2.220446049250313e-16)
-        return false;                                      // resizeAreaFast_: the box kernels' arithmetic
+    if (whole_factors(scale_x, scale_y)) return false;                                    // resizeAreaFast_: the box kernels' arithmetic
     if (scale_x > 70) return false;                        // (no cell of 66 columns or fewer: the axis need not be walked)
     const int ww = area_max_count(sw, dw, scale_x);
     if (ww < WIDE_W_MIN || ww > WIDE_W_MAX || sw < ww) return false;
-    int b = 16;
-    const long long nstrips = (dw + 63) / 64;
-    while (b > 4 && frames * nstrips * ((dh + b - 1) / b) < 4096) b /= 2;
-    while (b > 1 && frames * nstrips * ((dh + b - 1) / b) < 1024) b /= 2;
     *w = ww;
-    *bh = b;
+    *bh = area_band_height(frames, (dw + 63) / 64, dh);
     *line_bytes = ((((int)std::ceil(63 * scale_x) + ww + 2) * cn + 30 + 15) & ~15) + 32;
     return true;
 }
 constexpr int wide_wpb(int line_bytes) { return 4 * line_bytes <= 65536 ? 4 : 2; }   // waves (= lines) per block: 64 KB of LDS at most
 
-template <int CN, int W>
-static void launch_area_rows(int w, dim3 grid, hipStream_t s, const RArgs& a, const AreaGeom& gm, int nstrips, int bh, int nitems,
-                             int bpf, int count, const AreaTail& tail) {
-    if constexpr (W >= 1) {
-        if (w == W) hipLaunchKernelGGL((k_resize_area_rows<CN, W>), grid, dim3(256), 0, s, a, gm, nstrips, bh, nitems, bpf, count, tail);
-        else launch_area_rows<CN, W - 1>(w, grid, s, a, gm, nstrips, bh, nitems, bpf, count, tail);
-    }
+template <int CN>
+static void launch_area_rows(int w, const RowSplit& r, hipStream_t s, const RArgs& a, const AreaGeom& gm, int count, const AreaTail& tail) {
+    with_const<1, 4 * MIX_NV>(w, [&](auto W) {
+        hipLaunchKernelGGL((k_resize_area_rows<CN, W()>), dim3((unsigned)r.nblk, round_up8(count)), dim3(256), 0, s, a, gm, r.nstrips, r.bh,
+                           r.nitems, r.nblk, count, tail);
+    });
 }
 
 // Resize (general INTER_AREA, BGRA or BGR) + rotate + watermark (a BGRA overlay) in one pass; f.dw x f.dh is the RESIZED geometry, f.dst the final
@@ -3255,8 +3281,7 @@ bool area_tail_plan(const Frames& f, int* w, int* bh) {
     if (((uintptr_t)f.src | (uintptr_t)f.dst | (uintptr_t)v.step | (uintptr_t)f.dstep | (uintptr_t)f.src_stride | (uintptr_t)f.dst_stride) & 3)
         return false;
     const double scale_x = 1. / ((double)f.dw / v.w), scale_y = 1. / ((double)f.dh / v.h);
-    if (std::fabs(scale_x - std::lrint(scale_x)) < 2.220446049250313e-16 && std::fabs(scale_y - std::lrint(scale_y)) < 2.220446049250313e-16)
-        return false;                                      // resizeAreaFast_: the box kernels' arithmetic
+    if (whole_factors(scale_x, scale_y)) return false;                                    // resizeAreaFast_: the box kernels' arithmetic
     if (!area_rows_plan(v.w, v.h, f.dw, f.dh, scale_x, f.count, false, w, bh)) return false;
     *bh = std::min(*bh, 16);                               // (the turned band's LDS tile)
     return true;
@@ -3267,17 +3292,264 @@ int launch_area_rotate(const Frames& f, int amount, const OverlayArgs* overlay, 
     int w = 0, bh = 0;
     if (!area_tail_plan(f, &w, &bh)) return IMP_ERROR_UNSUPPORTED;
     const double scale_x = 1. / ((double)f.dw / v.w), scale_y = 1. / ((double)f.dh / v.h);
-    const RArgs a{f.src, f.src_stride, v.step, v.w, v.h, f.dst, f.dst_stride, f.dstep, f.dw, f.dh};
     const AreaGeom gm{scale_x, scale_y};
     AreaTail tail{};
     tail.rot = amount;
     if (overlay) tail.wm = *overlay;
-    const int nstrips = (f.dw + 63) / 64, nitems = nstrips * ((f.dh + bh - 1) / bh), bpf = (nitems + 3) / 4;
-    const dim3 grid((unsigned)bpf, (unsigned)((f.count + 7) / 8 * 8));
-    if (v.c == 4) launch_area_rows<4, 4 * MIX_NV>(w, grid, s, a, gm, nstrips, bh, nitems, bpf, f.count, tail);
-    else launch_area_rows<3, 4 * MIX_NV>(w, grid, s, a, gm, nstrips, bh, nitems, bpf, f.count, tail);
-    IMP_HIP(hipGetLastError());
-    return IMP_OK;
+    const RowSplit r = row_split(f.dw, f.dh, 64, bh);
+    if (v.c == 4) launch_area_rows<4>(w, r, s, rargs(f), gm, f.count, tail);
+    else launch_area_rows<3>(w, r, s, rargs(f), gm, f.count, tail);
+    return launched();
+}
+
+// launch_cv_resize's launches, by channel count.  `grid`: a lane per destination pixel, a grid row per frame.
+// Whole-factor INTER_AREA (whole_factors: resizeAreaFast_).
+template <int CN>
+static int launch_area_whole(const RArgs& a, int count, double scale_x, double scale_y, dim3 grid, hipStream_t s) {
+    const dim3 block(256);
+    const int isx = (int)std::lrint(scale_x), isy = (int)std::lrint(scale_y);
+    const bool rows4 = !(((uintptr_t)a.src | (uintptr_t)a.dst | (uintptr_t)a.sstep | (uintptr_t)a.dstep |
+                          (uintptr_t)a.src_stride | (uintptr_t)a.dst_stride) & 3);
+    if (isx == 2 && isy == 2 && (CN == 4 || CN == 3) && rows4 && a.sw == 2 * a.dw && a.sh >= 2 * a.dh) {
+        const int qpr = (a.dw + 3) / 4;                  // lanes per destination row
+        const dim3 qgrid((unsigned)(((long long)qpr * a.dh + 255) / 256), (unsigned)count);
+        const int gpr2 = a.sw / 4;
+        const dim3 cgrid2((unsigned)(((long long)gpr2 * a.dh + 511) / 512), (unsigned)count);
+        if (CN == 4 && !(a.dw & 1)) hipLaunchKernelGGL(k_area2x2_c4, cgrid2, block, 0, s, a, gpr2);
+        else if (CN == 4) hipLaunchKernelGGL(k_area2x2_v4, qgrid, block, 0, s, a, qpr);
+        else hipLaunchKernelGGL(k_area2x2_v3, qgrid, block, 0, s, a, qpr);
+    } else if (CN == 4 && rows4 && isx >= 3 && isx <= 8 && isy >= 1 && isx * isy <= 257 && a.sw == isx * a.dw && a.sh >= isy * a.dh) {
+        const float scale = 1.f / (float)(isx * isy);
+        const int cpr = a.sw / 4;                         // 16-byte granules per source row (k_area_boxc)
+        const dim3 cgrid((unsigned)(((long long)cpr * a.dh + 1023) / 1024), (unsigned)count);
+        const int P = (4096 / (4 * isx)) & ~3, lcpr = (a.dw + P - 1) / P;
+        const dim3 lgrid((unsigned)(((long long)lcpr * a.dh + 3) / 4), (unsigned)count);
+        if (isx == 8) hipLaunchKernelGGL((k_area_boxc<8>), cgrid, block, 0, s, a, isy, cpr, scale);
+        else with_const<3, 7>(isx, [&](auto I) { hipLaunchKernelGGL((k_area_boxl<4, I()>), lgrid, block, 0, s, a, isy, P, lcpr, scale); });
+    } else if (CN == 3 && rows4 && isx >= 2 && isx <= 8 && isy >= 1 && isx * isy <= 257 && !(isx == 2 && isy == 2) &&
+               a.sw == isx * a.dw && a.sh >= isy * a.dh) {
+        const int P = (4096 / (3 * isx)) & ~3, cpr = (a.dw + P - 1) / P;
+        const dim3 bgrid((unsigned)(((long long)cpr * a.dh + 3) / 4), (unsigned)count);
+        const float scale = 1.f / (float)(isx * isy);
+        with_const<2, 8>(isx, [&](auto I) { hipLaunchKernelGGL((k_area_boxl<3, I()>), bgrid, block, 0, s, a, isy, P, cpr, scale); });
+    } else
+        hipLaunchKernelGGL((k_resize_area_int<CN>), grid, block, 0, s, a, isx, isy);
+    return launched();
+}
+
+// Every other INTER_AREA shrink.
+template <int CN>
+static int launch_area_general(const RArgs& a, int count, int interp, double scale_x, double scale_y, dim3 grid, hipStream_t s) {
+    const dim3 block(256);
+    // BGRA / BGR with cells of at most 20 source columns (shrinks up to 18x): source rows streamed through wave-private
+    // LDS lines, weights computed in the kernel -- no per-geometry table to build, upload or cache.
+    const AreaGeom gm{scale_x, scale_y};
+    const bool rows4b = !(((uintptr_t)a.src | (uintptr_t)a.sstep | (uintptr_t)a.src_stride) & 3);
+    if (CN == 4 || (CN == 3 && rows4b && a.sw >= 6)) {
+        int w = 0, bh = 0;
+        if (area_rows_plan(a.sw, a.sh, a.dw, a.dh, scale_x, count, false, &w, &bh)) {
+            // four columns per lane while the windows are small and there are enough columns and waves for it
+            const RowSplit r4 = row_split(a.dw, a.dh, 256, bh);
+            const long long waves4 = (long long)count * r4.nitems;
+            if (w >= 2 && w <= 5 && a.dw >= 160 && waves4 >= 2048 && 255 * scale_x + w + 8 <= (CN == 4 ? 1024 : 1340)) {
+                constexpr int C34 = CN == 3 ? 3 : 4;
+                with_const<2, 5>(w, [&](auto W) {
+                    hipLaunchKernelGGL((k_resize_area_rows4<C34, W()>), dim3((unsigned)r4.nblk, round_up8(count)), block, 0, s, a, gm, r4.nstrips,
+                                       bh, r4.nitems, r4.nblk, count);
+                });
+                return launched();
+            }
+            launch_area_rows<(CN == 3 ? 3 : 4)>(w, row_split(a.dw, a.dh, 64, bh), s, a, gm, count, AreaTail{});
+            return launched();
+        }
+    }
+    // BGR frames whose rows are not 4-byte aligned (never cvCreateImage's, but a caller's own buffer may be): a lane
+    // per destination column, windows straight from global memory, weights computed in the kernel too
+    const int bpf = (int)grid.x;                       // blocks per frame
+    const dim3 fgrid(grid.x, round_up8(count));
+    const int ng = (a.dh + AREA_ROWS - 1) / AREA_ROWS;
+    const int gbpf = (int)(((long long)a.dw * ng + 255) / 256);
+    const dim3 ggrid((unsigned)gbpf, round_up8(count));
+    const bool big = (long long)gbpf * count >= 1024;
+    const int nvx = CN == 3 ? (area_max_count(a.sw, a.dw, scale_x) + 3) / 4 : 0;
+    if (nvx >= 1 && nvx <= MIX_NV && a.sw >= 4 * nvx) {
+        with_const<1, MIX_NV>(nvx, [&](auto NV) {
+            if (big) hipLaunchKernelGGL((k_resize_area_cells<3, NV(), AREA_ROWS>), ggrid, block, 0, s, a, gm, gbpf, count);
+            else hipLaunchKernelGGL((k_resize_area_cells<3, NV(), 1>), fgrid, block, 0, s, a, gm, bpf, count);
+        });
+        return launched();
+    }
+    // BGRA / BGR with cells of 21..66 source columns (shrinks past 18x, up to 64x): the same walk with a runtime
+    // window and a dynamic LDS line -- no table either
+    if constexpr (CN == 3 || CN == 4) {
+        int w = 0, bh = 0, line_bytes = 0;
+        if (area_wide_plan(a.sw, a.sh, a.dw, a.dh, CN, interp, a.src, a.sstep, a.src_stride, count, &w, &bh, &line_bytes)) {
+            const int wpb = wide_wpb(line_bytes);
+            const RowSplit r = row_split(a.dw, a.dh, 64, bh, wpb);
+            hipLaunchKernelGGL((k_resize_area_wide<CN>), dim3((unsigned)r.nblk, round_up8(count)), dim3(64 * wpb), (size_t)wpb * line_bytes, s, a, gm, w,
+                               line_bytes / 4, wpb, r.nstrips, bh, r.nitems, r.nblk, count);
+            return launched();
+        }
+    }
+    // everything else (gray frames, BGR rows that are not 4-byte aligned, cells wider than 66 columns): run tables,
+    // one output per lane
+    TableSet ts;
+    if (int rc = get_tables(interp, a.sw, a.sh, a.dw, a.dh, scale_x, scale_y, s, &ts)) return rc;
+    hipLaunchKernelGGL((k_resize_area<CN>), grid, block, 0, s, a, ts.area);
+    return launched();
+}
+
+// The tapped interpolations (LINEAR, CUBIC, LANCZOS4), branch by branch.
+// exact 2x decimation of a 3-channel frame: register-rolling strips
+static void launch_2x_bgr(const RArgs& a, int count, int interp, const TableSet& ts, hipStream_t s) {
+    const dim3 block(256);
+    const int nstrips = (a.dh + ROLL_STRIP - 1) / ROLL_STRIP;
+    const dim3 rgrid((a.dw + 255) / 256, nstrips, (unsigned)count);
+    const bool dma3 = (a.sw & 15) == 0 && (long long)a.sh * a.sstep < (1LL << 32) && (long long)a.dh * a.dstep < (1LL << 32) &&
+                      !(((uintptr_t)a.src | (uintptr_t)a.sstep | (uintptr_t)a.src_stride) & 15);
+    const int nbx = (a.dw + 255) / 256, bpf = nbx * nstrips;
+    const dim3 dgrid((unsigned)(bpf * 8), (unsigned)((count + 7) / 8));
+    if (dma3 && interp == IMP_INTER_CUBIC)
+        hipLaunchKernelGGL((k_resize_2x_dma3<4, M_CUBIC, 3, false>), dgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, (a.dw * 3) & ~7, nbx, bpf, count);
+    else if (dma3 && ts.ysym)
+        hipLaunchKernelGGL((k_resize_2x_dma3<8, M_LANCZOS, 3, true>), dgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0, nbx, bpf, count);
+    else if (dma3)
+        hipLaunchKernelGGL((k_resize_2x_dma3<8, M_LANCZOS, 3, false>), dgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0, nbx, bpf, count);
+    else if (interp == IMP_INTER_CUBIC)
+        hipLaunchKernelGGL((k_resize_2x_roll3<4, M_CUBIC, false>), rgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, (a.dw * 3) & ~7);
+    else if (ts.ysym)
+        hipLaunchKernelGGL((k_resize_2x_roll3<8, M_LANCZOS, true>), rgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0);
+    else
+        hipLaunchKernelGGL((k_resize_2x_roll3<8, M_LANCZOS, false>), rgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0);
+}
+
+// exact 2x decimation: register-rolling kernel, one wave per 64-column x ROLL_STRIP-row strip
+static void launch_2x_bgra(const RArgs& a, int count, int interp, const TableSet& ts, hipStream_t s) {
+    const dim3 block(256);
+    const int nstrips = (a.dh + ROLL_STRIP - 1) / ROLL_STRIP;
+    // LDS-DMA row ring, three iterations prefetched, when the 16-byte DMA granules line up with the rows (otherwise
+    // the register-rolling kernel, which has no alignment demands)
+    const bool dma_ok = interp != IMP_INTER_LINEAR && (a.sw & 3) == 0 &&
+                        (long long)a.sh * a.sstep < (1LL << 32) && (long long)a.dh * a.dstep < (1LL << 32) &&
+                        !(((uintptr_t)a.src | (uintptr_t)a.sstep | (uintptr_t)a.src_stride) & 15);
+    const dim3 rgrid((a.dw + 255) / 256, nstrips, (unsigned)count);
+    // four waves per block; they are independent (no barriers, private LDS rings)
+    const int nbx = (a.dw + 255) / 256, bpf = nbx * nstrips;
+    const dim3 dgrid((unsigned)(bpf * 8), (unsigned)((count + 7) / 8));
+    // the horizontal pass on the matrix unit (k_resize_2x_dma's MF form) where every column has the same taps and the
+    // strips' first tap is dword 1 of its 16-byte granule (xofs[0] = 0: sx00 = 2 dx0 - 3)
+    const bool mf = dma_ok && ts.xuni && ts.ysym && interp == IMP_INTER_LANCZOS4 && ts.x0 == 0;
+    if (mf) hipLaunchKernelGGL((k_resize_2x_dma<8, M_LANCZOS, 3, true, 4, true>), dgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0, nbx, bpf, count);
+    else if (dma_ok && interp == IMP_INTER_CUBIC)
+        hipLaunchKernelGGL((k_resize_2x_dma<4, M_CUBIC, 3, false, 4>), dgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, (a.dw * 4) & ~7, nbx, bpf, count);
+    else if (dma_ok && ts.ysym)
+        hipLaunchKernelGGL((k_resize_2x_dma<8, M_LANCZOS, 3, true, 4>), dgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0, nbx, bpf, count);
+    else if (dma_ok)
+        hipLaunchKernelGGL((k_resize_2x_dma<8, M_LANCZOS, 3, false, 4>), dgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0, nbx, bpf, count);
+    else if (interp == IMP_INTER_LINEAR)
+        hipLaunchKernelGGL((k_resize_2x_roll<2, M_LINEAR>), rgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0);
+    else if (interp == IMP_INTER_CUBIC)
+        hipLaunchKernelGGL((k_resize_2x_roll<4, M_CUBIC>), rgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, (a.dw * 4) & ~7);
+    else
+        hipLaunchKernelGGL((k_resize_2x_roll<8, M_LANCZOS>), rgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0);
+}
+
+// enlargement of a 3-channel frame (every JPEG): the BGRA kernel's structure on bytes
+static void launch_up_cubic_bgr(const RArgs& a, int count, double scale_x, double scale_y, const TableSet& ts, hipStream_t s) {
+    const int nbx = (a.dw + 255) / 256;
+    const int wbmax = ((((int)std::floor(63 * scale_x) + 6) * 3 + 3) & ~3) + 4;
+    int rpw = UP_ROWS;
+    while (rpw > 4 && ((int)std::floor((rpw - 1) * scale_y) + 6) * wbmax > UP_CAP3_BYTES) rpw -= 4;
+    while (rpw > 16 && (long long)nbx * 4 * ((a.dh + rpw - 1) / rpw) * count < 8192) rpw -= rpw > 64 ? 64 : 16;
+    const int ncy = (a.dh + rpw - 1) / rpw;
+    with_const<1, 4>(ts.up_period, [&](auto K) {             // (see launch_up_cubic_bgra)
+        constexpr int PS = K() == 1 ? 0 : K();
+        hipLaunchKernelGGL(k_resize_up_cubic3<PS>, dim3((unsigned)(nbx * ncy), (unsigned)count), dim3(256), 0, s, a, ts.xofs, ts.xco, ts.yco,
+                           (const UpRow*)ts.yrows, (a.dw * 3) & ~7, nbx, rpw);
+    });
+}
+
+// enlargement (bridge.c:190's CUBIC case): wave-private strips, float H sums in a register ring
+static void launch_up_cubic_bgra(const RArgs& a, int count, double scale_x, double scale_y, const TableSet& ts, hipStream_t s) {
+    const int nbx = (a.dw + 255) / 256;                 // four 64-column strips per block, one per wave
+    // rows per wave chunk: as many as keep the chunk's source footprint (strip columns x footprint rows, from the
+    // bound floor(n * scale) + 1 on how far n + 1 sample positions spread, + 3 taps + 1) inside the wave's LDS
+    // patch, at most UP_ROWS; fewer when there are too few frames to fill the chip otherwise
+    const int wmax = (int)std::floor(63 * scale_x) + 6;
+    int rpw = UP_ROWS;
+    while (rpw > 4 && ((int)std::floor((rpw - 1) * scale_y) + 6) * wmax > UP_CAP_PX) rpw -= 4;
+    while (rpw > 16 && (long long)nbx * 4 * ((a.dh + rpw - 1) / rpw) * count < 8192) rpw -= rpw > 64 ? 64 : 16;
+    const int ncy = (a.dh + rpw - 1) / rpw;
+    const dim3 ugrid((unsigned)(nbx * ncy), (unsigned)count);
+    with_const<1, 4>(ts.up_period, [&](auto K) {             // 2, 3, 4 when every per-th row (and no other) advances the footprint; else 0
+        constexpr int PS = K() == 1 ? 0 : K();
+        hipLaunchKernelGGL(k_resize_up_cubic4<PS>, ugrid, dim3(256), 0, s, a, ts.xofs, ts.xco, ts.yco, (const UpRow*)ts.yrows, (a.dw * 4) & ~7, nbx, rpw);
+    });
+}
+
+// every other scale up to 2 and every other enlargement: rolling strips with a dynamic footprint advance
+// (BGR windows are fetched as aligned dwords: rows 4-byte aligned, which every frame of the library has)
+template <int CN>
+static void launch_strips(const RArgs& a, int count, int interp, const TableSet& ts, hipStream_t s) {
+    const dim3 block(256);
+    constexpr int C34 = CN == 3 ? 3 : 4;
+    const int nsx = (a.dw + 255) / 256;
+    int rps = 64;
+    while (rps > 8 && (long long)count * nsx * 4 * ((a.dh + rps - 1) / rps) < 8192) rps /= 2;
+    const dim3 sgrid((unsigned)nsx, (unsigned)((a.dh + rps - 1) / rps), (unsigned)count);
+    const int ks = interp == IMP_INTER_LINEAR ? 2 : interp == IMP_INTER_CUBIC ? 4 : 8;
+    const int pat = ts.strip_a0 * 4 + ts.strip_a1;          // (1,0) 4, (0,1) 1, (1,2) 6, (2,1) 9; rps is a multiple of the 2 * ks row block
+    const bool periodic = ts.strip_a0 >= 0 && rps % (2 * ks) == 0;
+    const int ve = interp == IMP_INTER_CUBIC ? (a.dw * CN) & ~7 : 0;
+    // the patch stores are 16 bytes (BGR: 4) at row start + a multiple of 256 (192): rows and frames aligned to that
+    const int wide = !(((uintptr_t)a.dst | (uintptr_t)a.dstep | (uintptr_t)a.dst_stride) & (CN == 4 ? 15 : 3));
+#define IMP_STRIP2(KS_, MODE_, A0_, A1_) hipLaunchKernelGGL((k_resize_strip2<KS_, MODE_, C34, A0_, A1_>), sgrid, block, 0, s, a, ts.xofs, ts.xco, ts.srows, ve, rps, wide)
+    if (periodic && interp == IMP_INTER_LINEAR && pat == 4) IMP_STRIP2(2, M_LINEAR, 1, 0);
+    else if (periodic && interp == IMP_INTER_LINEAR && pat == 1) IMP_STRIP2(2, M_LINEAR, 0, 1);
+    else if (periodic && interp == IMP_INTER_LINEAR && pat == 6) IMP_STRIP2(2, M_LINEAR, 1, 2);
+    else if (periodic && interp == IMP_INTER_LINEAR && pat == 9) IMP_STRIP2(2, M_LINEAR, 2, 1);
+    else if (periodic && interp == IMP_INTER_LANCZOS4 && pat == 4) IMP_STRIP2(8, M_LANCZOS, 1, 0);
+    else if (periodic && interp == IMP_INTER_LANCZOS4 && pat == 1) IMP_STRIP2(8, M_LANCZOS, 0, 1);
+    else if (periodic && interp == IMP_INTER_LANCZOS4 && pat == 6) IMP_STRIP2(8, M_LANCZOS, 1, 2);
+    else if (periodic && interp == IMP_INTER_LANCZOS4 && pat == 9) IMP_STRIP2(8, M_LANCZOS, 2, 1);
+    else if (periodic && interp == IMP_INTER_CUBIC && pat == 6) IMP_STRIP2(4, M_CUBIC, 1, 2);      // (CUBIC comes here only when y shrinks)
+    else if (periodic && interp == IMP_INTER_CUBIC && pat == 9) IMP_STRIP2(4, M_CUBIC, 2, 1);
+#undef IMP_STRIP2
+    else if (interp == IMP_INTER_LINEAR)
+        hipLaunchKernelGGL((k_resize_strip<2, M_LINEAR, C34>), sgrid, block, 0, s, a, ts.xofs, ts.xco, ts.srows, 0, rps);
+    else if (interp == IMP_INTER_CUBIC)
+        hipLaunchKernelGGL((k_resize_strip<4, M_CUBIC, C34>), sgrid, block, 0, s, a, ts.xofs, ts.xco, ts.srows, ve, rps);
+    else
+        hipLaunchKernelGGL((k_resize_strip<8, M_LANCZOS, C34>), sgrid, block, 0, s, a, ts.xofs, ts.xco, ts.srows, 0, rps);
+}
+
+template <int CN>
+static void launch_taps(const RArgs& a, int interp, const TableSet& ts, dim3 grid, hipStream_t s) {
+    const dim3 block(256);
+    if (interp == IMP_INTER_LINEAR)
+        hipLaunchKernelGGL((k_resize_taps<2, CN, M_LINEAR>), grid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0);
+    else if (interp == IMP_INTER_CUBIC)
+        hipLaunchKernelGGL((k_resize_taps<4, CN, M_CUBIC>), grid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco,
+                           (a.dw * CN) & ~7);
+    else
+        hipLaunchKernelGGL((k_resize_taps<8, CN, M_LANCZOS>), grid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0);
+}
+
+template <int CN>
+static int launch_tapped(const RArgs& a, int count, int interp, double scale_x, double scale_y, dim3 grid, hipStream_t s) {
+    TableSet ts;
+    if (int rc = get_tables(interp, a.sw, a.sh, a.dw, a.dh, scale_x, scale_y, s, &ts)) return rc;
+    // both scales <= 2: neighbouring outputs share taps -> LDS-tiled separable kernel (BGRA)
+    if (CN == 3 && ts.step2 && a.sw >= 8 && interp != IMP_INTER_LINEAR) launch_2x_bgr(a, count, interp, ts, s);
+    else if (CN == 4 && ts.step2 && a.sw >= 8) launch_2x_bgra(a, count, interp, ts, s);
+    else if (CN == 3 && interp == IMP_INTER_CUBIC && scale_y <= 1.0 && scale_x <= 2.0 && a.sw >= 4 &&
+             (long long)a.dh * a.dstep < (1LL << 32)) launch_up_cubic_bgr(a, count, scale_x, scale_y, ts, s);
+    else if (CN == 4 && interp == IMP_INTER_CUBIC && scale_y <= 1.0 && scale_x <= 2.0 && a.sw >= 4 &&
+             (long long)a.dh * a.dstep < (1LL << 32)) launch_up_cubic_bgra(a, count, scale_x, scale_y, ts, s);
+    else if ((CN == 4 || CN == 3) && scale_x <= 2.0 && scale_y <= 2.0 && a.sw >= 8 &&
+             (CN == 4 || !(((uintptr_t)a.src | (uintptr_t)a.sstep | (uintptr_t)a.src_stride) & 3))) launch_strips<CN>(a, count, interp, ts, s);
+    else launch_taps<CN>(a, interp, ts, grid, s);
+    return launched();
 }
 
 template <int CN>
@@ -3285,256 +3557,12 @@ static int launch_cn(const RArgs& a, int count, int interp, double scale_x, doub
     const dim3 block(256), grid((unsigned)(((long long)a.dw * a.dh + 255) / 256), (unsigned)count);
     if (interp == IMP_INTER_NN) {
         hipLaunchKernelGGL((k_resize_nn<CN>), grid, block, 0, s, a, scale_x, scale_y);
-    } else if (interp == IMP_INTER_AREA) {
-        const int isx = (int)std::lrint(scale_x), isy = (int)std::lrint(scale_y);
-        if (std::fabs(scale_x - isx) < 2.220446049250313e-16 && std::fabs(scale_y - isy) < 2.220446049250313e-16) {
-            const bool rows4 = !(((uintptr_t)a.src | (uintptr_t)a.dst | (uintptr_t)a.sstep | (uintptr_t)a.dstep |
-                                  (uintptr_t)a.src_stride | (uintptr_t)a.dst_stride) & 3);
-            if (isx == 2 && isy == 2 && (CN == 4 || CN == 3) && rows4 && a.sw == 2 * a.dw && a.sh >= 2 * a.dh) {
-                const int qpr = (a.dw + 3) / 4;                  // lanes per destination row
-                const dim3 qgrid((unsigned)(((long long)qpr * a.dh + 255) / 256), (unsigned)count);
-                const int gpr2 = a.sw / 4;
-                const dim3 cgrid2((unsigned)(((long long)gpr2 * a.dh + 511) / 512), (unsigned)count);
-                if (CN == 4 && !(a.dw & 1)) hipLaunchKernelGGL(k_area2x2_c4, cgrid2, block, 0, s, a, gpr2);
-                else if (CN == 4) hipLaunchKernelGGL(k_area2x2_v4, qgrid, block, 0, s, a, qpr);
-                else hipLaunchKernelGGL(k_area2x2_v3, qgrid, block, 0, s, a, qpr);
-            } else if (CN == 4 && rows4 && isx >= 3 && isx <= 8 && isy >= 1 && isx * isy <= 257 && a.sw == isx * a.dw && a.sh >= isy * a.dh) {
-                const float scale = 1.f / (float)(isx * isy);
-                const int cpr = a.sw / 4;                         // 16-byte granules per source row (k_area_boxc)
-                const dim3 cgrid((unsigned)(((long long)cpr * a.dh + 1023) / 1024), (unsigned)count);
-                const int P = (4096 / (4 * isx)) & ~3, lcpr = (a.dw + P - 1) / P;
-                const dim3 lgrid((unsigned)(((long long)lcpr * a.dh + 3) / 4), (unsigned)count);
-                switch (isx) {
-                    case 8: hipLaunchKernelGGL((k_area_boxc<8>), cgrid, block, 0, s, a, isy, cpr, scale); break;
-                    case 3: hipLaunchKernelGGL((k_area_boxl<4, 3>), lgrid, block, 0, s, a, isy, P, lcpr, scale); break;
-                    case 5: hipLaunchKernelGGL((k_area_boxl<4, 5>), lgrid, block, 0, s, a, isy, P, lcpr, scale); break;
-                    case 6: hipLaunchKernelGGL((k_area_boxl<4, 6>), lgrid, block, 0, s, a, isy, P, lcpr, scale); break;
-                    case 7: hipLaunchKernelGGL((k_area_boxl<4, 7>), lgrid, block, 0, s, a, isy, P, lcpr, scale); break;
-                    default: hipLaunchKernelGGL((k_area_boxl<4, 4>), lgrid, block, 0, s, a, isy, P, lcpr, scale); break;
-                }
-            } else if (CN == 3 && rows4 && isx >= 2 && isx <= 8 && isy >= 1 && isx * isy <= 257 && !(isx == 2 && isy == 2) &&
-                       a.sw == isx * a.dw && a.sh >= isy * a.dh) {
-                const int P = (4096 / (3 * isx)) & ~3, cpr = (a.dw + P - 1) / P;
-                const dim3 bgrid((unsigned)(((long long)cpr * a.dh + 3) / 4), (unsigned)count);
-                const float scale = 1.f / (float)(isx * isy);
-                switch (isx) {
-                    case 2: hipLaunchKernelGGL((k_area_boxl<3, 2>), bgrid, block, 0, s, a, isy, P, cpr, scale); break;
-                    case 3: hipLaunchKernelGGL((k_area_boxl<3, 3>), bgrid, block, 0, s, a, isy, P, cpr, scale); break;
-                    case 4: hipLaunchKernelGGL((k_area_boxl<3, 4>), bgrid, block, 0, s, a, isy, P, cpr, scale); break;
-                    case 5: hipLaunchKernelGGL((k_area_boxl<3, 5>), bgrid, block, 0, s, a, isy, P, cpr, scale); break;
-                    case 6: hipLaunchKernelGGL((k_area_boxl<3, 6>), bgrid, block, 0, s, a, isy, P, cpr, scale); break;
-                    case 7: hipLaunchKernelGGL((k_area_boxl<3, 7>), bgrid, block, 0, s, a, isy, P, cpr, scale); break;
-                    default: hipLaunchKernelGGL((k_area_boxl<3, 8>), bgrid, block, 0, s, a, isy, P, cpr, scale); break;
-                }
-            } else
-                hipLaunchKernelGGL((k_resize_area_int<CN>), grid, block, 0, s, a, isx, isy);
-        } else {
-            // BGRA / BGR with cells of at most 20 source columns (shrinks up to 18x): source rows streamed through wave-private
-            // LDS lines, weights computed in the kernel -- no per-geometry table to build, upload or cache.
-            const AreaGeom gm{scale_x, scale_y};
-            const bool rows4b = !(((uintptr_t)a.src | (uintptr_t)a.sstep | (uintptr_t)a.src_stride) & 3);
-            if (CN == 4 || (CN == 3 && rows4b && a.sw >= 6)) {
-                int w = 0, bh = 0;
-                if (area_rows_plan(a.sw, a.sh, a.dw, a.dh, scale_x, count, false, &w, &bh)) {
-                    // four columns per lane while the windows are small and there are enough columns and waves for it
-                    const long long waves4 = (long long)count * ((a.dw + 255) / 256) * ((a.dh + bh - 1) / bh);
-                    if (w >= 2 && w <= 5 && a.dw >= 160 && waves4 >= 2048 && 255 * scale_x + w + 8 <= (CN == 4 ? 1024 : 1340)) {
-                        constexpr int C34 = CN == 3 ? 3 : 4;
-                        const int nstrips = (a.dw + 255) / 256, nitems = nstrips * ((a.dh + bh - 1) / bh), rbpf = (nitems + 3) / 4;
-                        const dim3 rgrid((unsigned)rbpf, (unsigned)((count + 7) / 8 * 8));
-                        switch (w) {
-                            case 2: hipLaunchKernelGGL((k_resize_area_rows4<C34, 2>), rgrid, block, 0, s, a, gm, nstrips, bh, nitems, rbpf, count); break;
-                            case 3: hipLaunchKernelGGL((k_resize_area_rows4<C34, 3>), rgrid, block, 0, s, a, gm, nstrips, bh, nitems, rbpf, count); break;
-                            case 4: hipLaunchKernelGGL((k_resize_area_rows4<C34, 4>), rgrid, block, 0, s, a, gm, nstrips, bh, nitems, rbpf, count); break;
-                            default: hipLaunchKernelGGL((k_resize_area_rows4<C34, 5>), rgrid, block, 0, s, a, gm, nstrips, bh, nitems, rbpf, count); break;
-                        }
-                        IMP_HIP(hipGetLastError());
-                        return IMP_OK;
-                    }
-                    const int nstrips = (a.dw + 63) / 64, nitems = nstrips * ((a.dh + bh - 1) / bh), rbpf = (nitems + 3) / 4;
-                    const dim3 rgrid((unsigned)rbpf, (unsigned)((count + 7) / 8 * 8));
-                    launch_area_rows<(CN == 3 ? 3 : 4), 4 * MIX_NV>(w, rgrid, s, a, gm, nstrips, bh, nitems, rbpf, count, AreaTail{});
-                    IMP_HIP(hipGetLastError());
-                    return IMP_OK;
-                }
-            }
-            // BGR frames whose rows are not 4-byte aligned (never cvCreateImage's, but a caller's own buffer may be): a lane
-            // per destination column, windows straight from global memory, weights computed in the kernel too
-            const int bpf = (int)grid.x;                       // blocks per frame
-            const dim3 fgrid(grid.x, (unsigned)((count + 7) / 8 * 8));   // whole groups of 8 frames (frame-per-XCD order)
-            const int ng = (a.dh + AREA_ROWS - 1) / AREA_ROWS;
-            const int gbpf = (int)(((long long)a.dw * ng + 255) / 256);
-            const dim3 ggrid((unsigned)gbpf, (unsigned)((count + 7) / 8 * 8));
-            const bool big = (long long)gbpf * count >= 1024;
-            const int nvx = CN == 3 ? (area_max_count(a.sw, a.dw, scale_x) + 3) / 4 : 0;
-            if (nvx >= 1 && nvx <= MIX_NV && a.sw >= 4 * nvx) {
-#define IMP_CELLS(NV_) \
-    do { \
-        if (big) hipLaunchKernelGGL((k_resize_area_cells<3, NV_, AREA_ROWS>), ggrid, block, 0, s, a, gm, gbpf, count); \
-        else hipLaunchKernelGGL((k_resize_area_cells<3, NV_, 1>), fgrid, block, 0, s, a, gm, bpf, count); \
-    } while (0)
-                switch (nvx) {
-                    case 1: IMP_CELLS(1); break;
-                    case 2: IMP_CELLS(2); break;
-                    case 3: IMP_CELLS(3); break;
-                    case 4: IMP_CELLS(4); break;
-                    default: IMP_CELLS(5); break;
-                }
-#undef IMP_CELLS
-                IMP_HIP(hipGetLastError());
-                return IMP_OK;
-            }
-            // BGRA / BGR with cells of 21..66 source columns (shrinks past 18x, up to 64x): the same walk with a runtime
-            // window and a dynamic LDS line -- no table either
-            if constexpr (CN == 3 || CN == 4) {
-                int w = 0, bh = 0, line_bytes = 0;
-                if (area_wide_plan(a.sw, a.sh, a.dw, a.dh, CN, interp, a.src, a.sstep, a.src_stride, count, &w, &bh, &line_bytes)) {
-                    const int wpb = wide_wpb(line_bytes);
-                    const int nstrips = (a.dw + 63) / 64, nitems = nstrips * ((a.dh + bh - 1) / bh), wbpf = (nitems + wpb - 1) / wpb;
-                    const dim3 wgrid((unsigned)wbpf, (unsigned)((count + 7) / 8 * 8));
-                    hipLaunchKernelGGL((k_resize_area_wide<CN>), wgrid, dim3(64 * wpb), (size_t)wpb * line_bytes, s, a, gm, w, line_bytes / 4, wpb,
-                                       nstrips, bh, nitems, wbpf, count);
-                    IMP_HIP(hipGetLastError());
-                    return IMP_OK;
-                }
-            }
-            // everything else (gray frames, BGR rows that are not 4-byte aligned, cells wider than 66 columns): run tables,
-            // one output per lane
-            TableSet ts;
-            if (int rc = get_tables(interp, a.sw, a.sh, a.dw, a.dh, scale_x, scale_y, s, &ts)) return rc;
-            hipLaunchKernelGGL((k_resize_area<CN>), grid, block, 0, s, a, ts.area);
-        }
-    } else {
-        TableSet ts;
-        if (int rc = get_tables(interp, a.sw, a.sh, a.dw, a.dh, scale_x, scale_y, s, &ts)) return rc;
-        // both scales <= 2: neighbouring outputs share taps -> LDS-tiled separable kernel (BGRA)
-        if (CN == 3 && ts.step2 && a.sw >= 8 && interp != IMP_INTER_LINEAR) {
-            // exact 2x decimation of a 3-channel frame: register-rolling strips
-            const int nstrips = (a.dh + ROLL_STRIP - 1) / ROLL_STRIP;
-            const dim3 rgrid((a.dw + 255) / 256, nstrips, (unsigned)count);
-            const bool dma3 = (a.sw & 15) == 0 && (long long)a.sh * a.sstep < (1LL << 32) && (long long)a.dh * a.dstep < (1LL << 32) &&
-                              !(((uintptr_t)a.src | (uintptr_t)a.sstep | (uintptr_t)a.src_stride) & 15);
-            const int nbx = (a.dw + 255) / 256, bpf = nbx * nstrips;
-            const dim3 dgrid((unsigned)(bpf * 8), (unsigned)((count + 7) / 8));
-            if (dma3 && interp == IMP_INTER_CUBIC)
-                hipLaunchKernelGGL((k_resize_2x_dma3<4, M_CUBIC, 3, false>), dgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, (a.dw * 3) & ~7, nbx, bpf, count);
-            else if (dma3 && ts.ysym)
-                hipLaunchKernelGGL((k_resize_2x_dma3<8, M_LANCZOS, 3, true>), dgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0, nbx, bpf, count);
-            else if (dma3)
-                hipLaunchKernelGGL((k_resize_2x_dma3<8, M_LANCZOS, 3, false>), dgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0, nbx, bpf, count);
-            else if (interp == IMP_INTER_CUBIC)
-                hipLaunchKernelGGL((k_resize_2x_roll3<4, M_CUBIC, false>), rgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, (a.dw * 3) & ~7);
-            else if (ts.ysym)
-                hipLaunchKernelGGL((k_resize_2x_roll3<8, M_LANCZOS, true>), rgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0);
-            else
-                hipLaunchKernelGGL((k_resize_2x_roll3<8, M_LANCZOS, false>), rgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0);
-        } else if (CN == 4 && ts.step2 && a.sw >= 8) {
-            // exact 2x decimation: register-rolling kernel, one wave per 64-column x ROLL_STRIP-row strip
-            const int nstrips = (a.dh + ROLL_STRIP - 1) / ROLL_STRIP;
-            // LDS-DMA row ring, three iterations prefetched, when the 16-byte DMA granules line up with the rows (otherwise
-            // the register-rolling kernel, which has no alignment demands)
-            const bool dma_ok = interp != IMP_INTER_LINEAR && (a.sw & 3) == 0 &&
-                                (long long)a.sh * a.sstep < (1LL << 32) && (long long)a.dh * a.dstep < (1LL << 32) &&
-                                !(((uintptr_t)a.src | (uintptr_t)a.sstep | (uintptr_t)a.src_stride) & 15);
-            const dim3 rgrid((a.dw + 255) / 256, nstrips, (unsigned)count);
-            // four waves per block; they are independent (no barriers, private LDS rings)
-            const int nbx = (a.dw + 255) / 256, bpf = nbx * nstrips;
-            const dim3 dgrid((unsigned)(bpf * 8), (unsigned)((count + 7) / 8));
-            // the horizontal pass on the matrix unit (k_resize_2x_dma's MF form) where every column has the same taps and the
-            // strips' first tap is dword 1 of its 16-byte granule (xofs[0] = 0: sx00 = 2 dx0 - 3)
-            const bool mf = dma_ok && ts.xuni && ts.ysym && interp == IMP_INTER_LANCZOS4 && ts.x0 == 0;
-            if (mf) hipLaunchKernelGGL((k_resize_2x_dma<8, M_LANCZOS, 3, true, 4, true>), dgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0, nbx, bpf, count);
-            else if (dma_ok && interp == IMP_INTER_CUBIC)
-                hipLaunchKernelGGL((k_resize_2x_dma<4, M_CUBIC, 3, false, 4>), dgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, (a.dw * 4) & ~7, nbx, bpf, count);
-            else if (dma_ok && ts.ysym)
-                hipLaunchKernelGGL((k_resize_2x_dma<8, M_LANCZOS, 3, true, 4>), dgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0, nbx, bpf, count);
-            else if (dma_ok)
-                hipLaunchKernelGGL((k_resize_2x_dma<8, M_LANCZOS, 3, false, 4>), dgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0, nbx, bpf, count);
-            else if (interp == IMP_INTER_LINEAR)
-                hipLaunchKernelGGL((k_resize_2x_roll<2, M_LINEAR>), rgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0);
-            else if (interp == IMP_INTER_CUBIC)
-                hipLaunchKernelGGL((k_resize_2x_roll<4, M_CUBIC>), rgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, (a.dw * 4) & ~7);
-            else
-                hipLaunchKernelGGL((k_resize_2x_roll<8, M_LANCZOS>), rgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0);
-        } else if (CN == 3 && interp == IMP_INTER_CUBIC && scale_y <= 1.0 && scale_x <= 2.0 && a.sw >= 4 &&
-                   (long long)a.dh * a.dstep < (1LL << 32)) {
-            // enlargement of a 3-channel frame (every JPEG): the BGRA kernel's structure on bytes
-            const int nbx = (a.dw + 255) / 256;
-            const int wbmax = ((((int)std::floor(63 * scale_x) + 6) * 3 + 3) & ~3) + 4;
-            int rpw = UP_ROWS;
-            while (rpw > 4 && ((int)std::floor((rpw - 1) * scale_y) + 6) * wbmax > UP_CAP3_BYTES) rpw -= 4;
-            while (rpw > 16 && (long long)nbx * 4 * ((a.dh + rpw - 1) / rpw) * count < 8192) rpw -= rpw > 64 ? 64 : 16;
-            const int ncy = (a.dh + rpw - 1) / rpw;
-            { const int per = ts.up_period;
-              if (per == 2) hipLaunchKernelGGL(k_resize_up_cubic3<2>, dim3((unsigned)(nbx * ncy), (unsigned)count), block, 0, s, a,
-                               ts.xofs, ts.xco, ts.yco, (const UpRow*)ts.yrows, (a.dw * 3) & ~7, nbx, rpw);
-              else if (per == 3) hipLaunchKernelGGL(k_resize_up_cubic3<3>, dim3((unsigned)(nbx * ncy), (unsigned)count), block, 0, s, a,
-                               ts.xofs, ts.xco, ts.yco, (const UpRow*)ts.yrows, (a.dw * 3) & ~7, nbx, rpw);
-              else if (per == 4) hipLaunchKernelGGL(k_resize_up_cubic3<4>, dim3((unsigned)(nbx * ncy), (unsigned)count), block, 0, s, a,
-                               ts.xofs, ts.xco, ts.yco, (const UpRow*)ts.yrows, (a.dw * 3) & ~7, nbx, rpw);
-              else hipLaunchKernelGGL(k_resize_up_cubic3<0>, dim3((unsigned)(nbx * ncy), (unsigned)count), block, 0, s, a,
-                               ts.xofs, ts.xco, ts.yco, (const UpRow*)ts.yrows, (a.dw * 3) & ~7, nbx, rpw); }
-        } else if (CN == 4 && interp == IMP_INTER_CUBIC && scale_y <= 1.0 && scale_x <= 2.0 && a.sw >= 4 &&
-                   (long long)a.dh * a.dstep < (1LL << 32)) {
-            // enlargement (bridge.c:190's CUBIC case): wave-private strips, float H sums in a register ring
-            const int nbx = (a.dw + 255) / 256;                 // four 64-column strips per block, one per wave
-            // rows per wave chunk: as many as keep the chunk's source footprint (strip columns x footprint rows, from the
-            // bound floor(n * scale) + 1 on how far n + 1 sample positions spread, + 3 taps + 1) inside the wave's LDS
-            // patch, at most UP_ROWS; fewer when there are too few frames to fill the chip otherwise
-            const int wmax = (int)std::floor(63 * scale_x) + 6;
-            int rpw = UP_ROWS;
-            while (rpw > 4 && ((int)std::floor((rpw - 1) * scale_y) + 6) * wmax > UP_CAP_PX) rpw -= 4;
-            while (rpw > 16 && (long long)nbx * 4 * ((a.dh + rpw - 1) / rpw) * count < 8192) rpw -= rpw > 64 ? 64 : 16;
-            const int ncy = (a.dh + rpw - 1) / rpw;
-            const dim3 ugrid((unsigned)(nbx * ncy), (unsigned)count);
-            const int per = ts.up_period;                  // 2, 3, 4 when every per-th row (and no other) advances the footprint
-            if (per == 2) hipLaunchKernelGGL(k_resize_up_cubic4<2>, ugrid, block, 0, s, a, ts.xofs, ts.xco, ts.yco, (const UpRow*)ts.yrows, (a.dw * 4) & ~7, nbx, rpw);
-            else if (per == 3) hipLaunchKernelGGL(k_resize_up_cubic4<3>, ugrid, block, 0, s, a, ts.xofs, ts.xco, ts.yco, (const UpRow*)ts.yrows, (a.dw * 4) & ~7, nbx, rpw);
-            else if (per == 4) hipLaunchKernelGGL(k_resize_up_cubic4<4>, ugrid, block, 0, s, a, ts.xofs, ts.xco, ts.yco, (const UpRow*)ts.yrows, (a.dw * 4) & ~7, nbx, rpw);
-            else hipLaunchKernelGGL(k_resize_up_cubic4<0>, ugrid, block, 0, s, a, ts.xofs, ts.xco, ts.yco, (const UpRow*)ts.yrows, (a.dw * 4) & ~7, nbx, rpw);
-        } else if ((CN == 4 || CN == 3) && scale_x <= 2.0 && scale_y <= 2.0 && a.sw >= 8 &&
-                   (CN == 4 || !(((uintptr_t)a.src | (uintptr_t)a.sstep | (uintptr_t)a.src_stride) & 3))) {
-            // every other scale up to 2 and every other enlargement: rolling strips with a dynamic footprint advance
-            // (BGR windows are fetched as aligned dwords: rows 4-byte aligned, which every frame of the library has)
-            constexpr int C34 = CN == 3 ? 3 : 4;
-            const int nsx = (a.dw + 255) / 256;
-            int rps = 64;
-            while (rps > 8 && (long long)count * nsx * 4 * ((a.dh + rps - 1) / rps) < 8192) rps /= 2;
-            const dim3 sgrid((unsigned)nsx, (unsigned)((a.dh + rps - 1) / rps), (unsigned)count);
-            const int ks = interp == IMP_INTER_LINEAR ? 2 : interp == IMP_INTER_CUBIC ? 4 : 8;
-            const int pat = ts.strip_a0 * 4 + ts.strip_a1;          // (1,0) 4, (0,1) 1, (1,2) 6, (2,1) 9; rps is a multiple of the 2 * ks row block
-            const bool periodic = ts.strip_a0 >= 0 && rps % (2 * ks) == 0;
-            const int ve = interp == IMP_INTER_CUBIC ? (a.dw * CN) & ~7 : 0;
-            // the patch stores are 16 bytes (BGR: 4) at row start + a multiple of 256 (192): rows and frames aligned to that
-            const int wide = !(((uintptr_t)a.dst | (uintptr_t)a.dstep | (uintptr_t)a.dst_stride) & (CN == 4 ? 15 : 3));
-#define IMP_STRIP2(KS_, MODE_, A0_, A1_) hipLaunchKernelGGL((k_resize_strip2<KS_, MODE_, C34, A0_, A1_>), sgrid, block, 0, s, a, ts.xofs, ts.xco, ts.srows, ve, rps, wide)
-            if (periodic && interp == IMP_INTER_LINEAR && pat == 4) IMP_STRIP2(2, M_LINEAR, 1, 0);
-            else if (periodic && interp == IMP_INTER_LINEAR && pat == 1) IMP_STRIP2(2, M_LINEAR, 0, 1);
-            else if (periodic && interp == IMP_INTER_LINEAR && pat == 6) IMP_STRIP2(2, M_LINEAR, 1, 2);
-            else if (periodic && interp == IMP_INTER_LINEAR && pat == 9) IMP_STRIP2(2, M_LINEAR, 2, 1);
-            else if (periodic && interp == IMP_INTER_LANCZOS4 && pat == 4) IMP_STRIP2(8, M_LANCZOS, 1, 0);
-            else if (periodic && interp == IMP_INTER_LANCZOS4 && pat == 1) IMP_STRIP2(8, M_LANCZOS, 0, 1);
-            else if (periodic && interp == IMP_INTER_LANCZOS4 && pat == 6) IMP_STRIP2(8, M_LANCZOS, 1, 2);
-            else if (periodic && interp == IMP_INTER_LANCZOS4 && pat == 9) IMP_STRIP2(8, M_LANCZOS, 2, 1);
-            else if (periodic && interp == IMP_INTER_CUBIC && pat == 6) IMP_STRIP2(4, M_CUBIC, 1, 2);      // (CUBIC comes here only when y shrinks)
-            else if (periodic && interp == IMP_INTER_CUBIC && pat == 9) IMP_STRIP2(4, M_CUBIC, 2, 1);
-#undef IMP_STRIP2
-            else if (interp == IMP_INTER_LINEAR)
-                hipLaunchKernelGGL((k_resize_strip<2, M_LINEAR, C34>), sgrid, block, 0, s, a, ts.xofs, ts.xco, ts.srows, 0, rps);
-            else if (interp == IMP_INTER_CUBIC)
-                hipLaunchKernelGGL((k_resize_strip<4, M_CUBIC, C34>), sgrid, block, 0, s, a, ts.xofs, ts.xco, ts.srows, ve, rps);
-            else
-                hipLaunchKernelGGL((k_resize_strip<8, M_LANCZOS, C34>), sgrid, block, 0, s, a, ts.xofs, ts.xco, ts.srows, 0, rps);
-        } else if (interp == IMP_INTER_LINEAR)
-            hipLaunchKernelGGL((k_resize_taps<2, CN, M_LINEAR>), grid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0);
-        else if (interp == IMP_INTER_CUBIC)
-            hipLaunchKernelGGL((k_resize_taps<4, CN, M_CUBIC>), grid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco,
-                               (a.dw * CN) & ~7);
-        else
-            hipLaunchKernelGGL((k_resize_taps<8, CN, M_LANCZOS>), grid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0);
+        return launched();
     }
-    IMP_HIP(hipGetLastError());
-    return IMP_OK;
+    if (interp == IMP_INTER_AREA)
+        return whole_factors(scale_x, scale_y) ? launch_area_whole<CN>(a, count, scale_x, scale_y, grid, s)
+                                               : launch_area_general<CN>(a, count, interp, scale_x, scale_y, grid, s);
+    return launch_tapped<CN>(a, count, interp, scale_x, scale_y, grid, s);
 }
 
 // ------------------------------------------------------------------ fused AREA 2x2 + rotate 90/270 (BGRA)
@@ -3750,14 +3778,14 @@ int launch_area2x2_rotate(const Frames& f, int amount, const OverlayArgs* overla
     if (f.dw != rh || f.dh != rw || f.count <= 0 || f.count > 65535) return IMP_ERROR_UNSUPPORTED;
     if (((uintptr_t)f.src | (uintptr_t)v.step | (uintptr_t)f.src_stride) & 15) return IMP_ERROR_UNSUPPORTED;   // 16-byte loads
     if (((uintptr_t)f.dst | (uintptr_t)f.dstep | (uintptr_t)f.dst_stride) & 3) return IMP_ERROR_UNSUPPORTED;
-    RArgs a{f.src, f.src_stride, v.step, v.w, v.h, f.dst, f.dst_stride, f.dstep, f.dw, f.dh};
+    const RArgs a = rargs(f);
     const dim3 block(256);
     OverlayArgs wm{};
     if (overlay) wm = *overlay;
     if (!(rw & 1)) {
         constexpr int sw = 128, bh = 32;
         const int nstrips = (rw + sw - 1) / sw, nbands = (rh + bh - 1) / bh, bpf = (nstrips * nbands + 3) / 4;
-        const dim3 sgrid((unsigned)bpf, (unsigned)((f.count + 7) / 8 * 8));
+        const dim3 sgrid((unsigned)bpf, round_up8(f.count));
         const size_t lds = (size_t)4 * bh * (sw + 1) * 4;
         hipError_t e = lds_limit_once<k_area2x2_turn<sw, bh>>();
         if (e == hipSuccess) {
@@ -3769,7 +3797,7 @@ int launch_area2x2_rotate(const Frames& f, int amount, const OverlayArgs* overla
     }
     // odd halved widths: 64x64 block tiles, walked one tile column at a time (profiles/r01_chain_tiles.txt)
     const int ntx = (rw + 63) / 64, nty = (rh + 63) / 64;
-    const dim3 grid((unsigned)(ntx * nty), (unsigned)((f.count + 7) / 8 * 8));
+    const dim3 grid((unsigned)(ntx * nty), round_up8(f.count));
     hipLaunchKernelGGL((k_area2x2_rotate_bgra<64, 64>), grid, block, 0, s, a, amount, rw, rh, ntx, nty, f.count, wm);
     IMP_HIP(hipGetLastError());
     return IMP_OK;
@@ -3791,7 +3819,7 @@ int launch_cv_resize(const Frames& f, int interp, hipStream_t s) {
     if (v.c == 4 && (((uintptr_t)f.src | (uintptr_t)f.dst | (uintptr_t)v.step | (uintptr_t)f.dstep |
                       (uintptr_t)f.src_stride | (uintptr_t)f.dst_stride) & 3))
         return IMP_ERROR_INVALID_ARGS;    // BGRA rows must be 4-byte aligned (cvCreateImage guarantees it)
-    RArgs a{f.src, f.src_stride, v.step, v.w, v.h, f.dst, f.dst_stride, f.dstep, f.dw, f.dh};
+    const RArgs a = rargs(f);
     switch (v.c) {
         case 1: return launch_cn<1>(a, f.count, interp, scale_x, scale_y, s);
         case 3: return launch_cn<3>(a, f.count, interp, scale_x, scale_y, s);
@@ -3801,39 +3829,29 @@ int launch_cv_resize(const Frames& f, int interp, hipStream_t s) {
 }
 
 // Resize() over `count` frames of different geometry with as few launches as the mix allows.  Per frame the
-// interpolation is the reference's (bridge.c:183-193) and the arithmetic is launch_cv_resize's: frames that take the
-// general AREA path (every non-integer shrink whose cells span at most 20 source columns) are gathered into a descriptor
-// launch with their weights computed in the kernel, colour frames whose cells span 21..66 columns (area_wide_plan:
-// shrinks past 18x, up to 64x) into a k_resize_area_wide_mix launch, whole-factor AREA frames (any channel count) into a
-// k_area_int_mix launch and NN frames into a k_resize_nn_mix launch -- four launches at most, three for gray; a frame
-// that is the only one of its kind, and the rest (enlargements; extreme ratios: cells past 20 columns for gray frames and
-// BGR rows that are not 4-byte aligned, past 66 for colour) go one launch each on the same stream.  Gray frames are
-// gathered like colour ones: their general AREA shrinks ride k_resize_area_mix<1> whatever their pointers and pitches are.
-// Blocks differ a hundredfold in work (a 4K source against a 256-pixel one, same 224-wide output): the frames go
-// longest first to the XCD list with the least source bytes so far, so each list starts with its heavy frames and
-// the launch's tail is made of light ones.  `v` is consumed; *sorted holds the descriptors list by list, *most = the
-// blocks of the longest list (the grid is 8 * most).
-template <class D, class M>
-static void mix_deal_area(std::vector<D>& v, M desc, std::vector<D>* sorted_out, MixIndex* ix_out, int* most_out) {
-    imp::mix_deal(v, desc, [&](D& d) { return (long long)desc(d).a.sw * desc(d).a.sh; }, sorted_out, ix_out, most_out);
+// interpolation is the reference's (bridge.c:183-193) and the arithmetic is launch_cv_resize's.  classify_mixed names a
+// frame's class and fills its descriptor: frames that take the general AREA path (every non-integer shrink whose cells
+// span at most 20 source columns) are gathered into a k_resize_area_mix launch with their weights computed in the kernel,
+// colour frames whose cells span 21..66 columns (area_wide_plan: shrinks past 18x, up to 64x) into a
+// k_resize_area_wide_mix launch, whole-factor AREA frames (any channel count) into a k_area_int_mix launch and NN frames
+// into a k_resize_nn_mix launch -- four launches at most, three for gray; a frame that is the only one of its class, and
+// the rest (enlargements; extreme ratios: cells past 20 columns for gray frames and BGR rows that are not 4-byte aligned,
+// past 66 for colour) go one launch each on the same stream.  Gray frames are gathered like colour ones: their general
+// AREA shrinks ride k_resize_area_mix<1> whatever their pointers and pitches are.
+// Blocks differ a hundredfold in work (a 4K source against a 256-pixel one, same 224-wide output): each launch deals its
+// frames longest source first to the XCD list with the least source bytes so far (mix_launch), so each list starts with
+// its heavy frames and the launch's tail is made of light ones.
+template <class D, class L>
+static int launch_by_source(std::vector<D>& v, hipStream_t s, L launch) {
+    return mix_launch(v, [](D& d) { return (long long)d.a.sw * d.a.sh; }, s, launch);
 }
 
 static int launch_mix(std::vector<MixDesc>& v, int cn, hipStream_t s) {
-    if (v.empty()) return IMP_OK;
-    std::vector<MixDesc> sorted;
-    MixIndex ix{};
-    int most = 0;
-    mix_deal_area(v, [](MixDesc& d) -> MixDesc& { return d; }, &sorted, &ix, &most);
-    void* dev = nullptr;
-    if (int rc = upload_small(sorted.data(), sorted.size() * sizeof(MixDesc), &dev, s)) return rc;
-    const dim3 grid((unsigned)most * 8), block(256);
-    if (cn == 4) hipLaunchKernelGGL((k_resize_area_mix<4>), grid, block, 0, s, (const MixDesc*)dev, ix);
-    else if (cn == 3) hipLaunchKernelGGL((k_resize_area_mix<3>), grid, block, 0, s, (const MixDesc*)dev, ix);
-    else hipLaunchKernelGGL((k_resize_area_mix<1>), grid, block, 0, s, (const MixDesc*)dev, ix);
-    const hipError_t e = hipGetLastError();
-    dev_free_on(dev, s);
-    IMP_HIP(e);
-    return IMP_OK;
+    return launch_by_source(v, s, [&](dim3 grid, const MixDesc* dev, const MixIndex& ix) {
+        if (cn == 4) hipLaunchKernelGGL((k_resize_area_mix<4>), grid, dim3(256), 0, s, dev, ix);
+        else if (cn == 3) hipLaunchKernelGGL((k_resize_area_mix<3>), grid, dim3(256), 0, s, dev, ix);
+        else hipLaunchKernelGGL((k_resize_area_mix<1>), grid, dim3(256), 0, s, dev, ix);
+    });
 }
 
 // The descriptor of one whole-factor AREA frame.  Its body is the one launch_cn picks for the frame alone, with three
@@ -3842,7 +3860,7 @@ static int launch_mix(std::vector<MixDesc>& v, int cn, hipStream_t s) {
 // of an even width runs k_area2x2_v4's body, not k_area2x2_c4's.
 static IntMixDesc int_mix_desc(const MixFrame& f, int cn, int isx, int isy) {
     IntMixDesc d{};
-    d.a = RArgs{f.src, 0, f.sstep, f.sw, f.sh, f.dst, 0, f.dstep, f.dw, f.dh};
+    d.a = rargs(f);
     d.isx = isx;
     d.isy = isy;
     d.scale = 1.f / (float)(isx * isy);
@@ -3863,66 +3881,118 @@ static IntMixDesc int_mix_desc(const MixFrame& f, int cn, int isx, int isy) {
     return d;
 }
 
-// Deals the descriptors (longest source first) and uploads the table; the caller launches over *grid and frees *dev on `s`.
-template <class D>
-static int mix_table(std::vector<D>& v, hipStream_t s, void** dev, MixIndex* ix, dim3* grid) {
-    std::vector<D> sorted;
-    int most = 0;
-    imp::mix_deal(v, [](D& d) -> D& { return d; }, [](D& d) { return (long long)d.a.sw * d.a.sh; }, &sorted, ix, &most);
-    if (int rc = upload_small(sorted.data(), sorted.size() * sizeof(D), dev, s)) return rc;
-    *grid = dim3((unsigned)most * 8);
-    return IMP_OK;
-}
-
 static int launch_int_mix(std::vector<IntMixDesc>& v, int cn, hipStream_t s) {
     size_t lds = 0;                                        // the largest any class present needs
     for (const IntMixDesc& d : v)
         if (d.cls == IM_BOXL) lds = 4 * BOXL_LINE * sizeof(uint32_t);
-    void* dev = nullptr;
-    MixIndex ix{};
-    dim3 grid;
-    if (int rc = mix_table(v, s, &dev, &ix, &grid)) return rc;
-    const dim3 block(256);
-    if (cn == 4) hipLaunchKernelGGL((k_area_int_mix<4>), grid, block, lds, s, (const IntMixDesc*)dev, ix);
-    else if (cn == 3) hipLaunchKernelGGL((k_area_int_mix<3>), grid, block, lds, s, (const IntMixDesc*)dev, ix);
-    else hipLaunchKernelGGL((k_area_int_mix<1>), grid, block, lds, s, (const IntMixDesc*)dev, ix);
-    const hipError_t e = hipGetLastError();
-    dev_free_on(dev, s);
-    IMP_HIP(e);
-    return IMP_OK;
+    return launch_by_source(v, s, [&](dim3 grid, const IntMixDesc* dev, const MixIndex& ix) {
+        if (cn == 4) hipLaunchKernelGGL((k_area_int_mix<4>), grid, dim3(256), lds, s, dev, ix);
+        else if (cn == 3) hipLaunchKernelGGL((k_area_int_mix<3>), grid, dim3(256), lds, s, dev, ix);
+        else hipLaunchKernelGGL((k_area_int_mix<1>), grid, dim3(256), lds, s, dev, ix);
+    });
 }
 
 static int launch_nn_mix(std::vector<NnMixDesc>& v, int cn, hipStream_t s) {
-    void* dev = nullptr;
-    MixIndex ix{};
-    dim3 grid;
-    if (int rc = mix_table(v, s, &dev, &ix, &grid)) return rc;
-    const dim3 block(256);
-    if (cn == 4) hipLaunchKernelGGL((k_resize_nn_mix<4>), grid, block, 0, s, (const NnMixDesc*)dev, ix);
-    else if (cn == 3) hipLaunchKernelGGL((k_resize_nn_mix<3>), grid, block, 0, s, (const NnMixDesc*)dev, ix);
-    else hipLaunchKernelGGL((k_resize_nn_mix<1>), grid, block, 0, s, (const NnMixDesc*)dev, ix);
-    const hipError_t e = hipGetLastError();
-    dev_free_on(dev, s);
-    IMP_HIP(e);
-    return IMP_OK;
+    return launch_by_source(v, s, [&](dim3 grid, const NnMixDesc* dev, const MixIndex& ix) {
+        if (cn == 4) hipLaunchKernelGGL((k_resize_nn_mix<4>), grid, dim3(256), 0, s, dev, ix);
+        else if (cn == 3) hipLaunchKernelGGL((k_resize_nn_mix<3>), grid, dim3(256), 0, s, dev, ix);
+        else hipLaunchKernelGGL((k_resize_nn_mix<1>), grid, dim3(256), 0, s, dev, ix);
+    });
 }
 
 // Frames area_wide_plan accepts, two or more: every line of the launch is as long as the longest one present.
 static int launch_wide_mix(std::vector<MixDesc>& v, int cn, int line_bytes, hipStream_t s) {
     const int wpb = wide_wpb(line_bytes);
     for (MixDesc& d : v) d.nblk = (d.nitems + wpb - 1) / wpb;
-    void* dev = nullptr;
-    MixIndex ix{};
-    dim3 grid;
-    if (int rc = mix_table(v, s, &dev, &ix, &grid)) return rc;                // (longest source first)
-    const dim3 block(64 * wpb);
     const size_t lds = (size_t)wpb * line_bytes;
-    if (cn == 4) hipLaunchKernelGGL((k_resize_area_wide_mix<4>), grid, block, lds, s, (const MixDesc*)dev, ix, line_bytes / 4, wpb);
-    else hipLaunchKernelGGL((k_resize_area_wide_mix<3>), grid, block, lds, s, (const MixDesc*)dev, ix, line_bytes / 4, wpb);
-    const hipError_t e = hipGetLastError();
-    dev_free_on(dev, s);
-    IMP_HIP(e);
-    return IMP_OK;
+    return launch_by_source(v, s, [&](dim3 grid, const MixDesc* dev, const MixIndex& ix) {
+        if (cn == 4) hipLaunchKernelGGL((k_resize_area_wide_mix<4>), grid, dim3(64 * wpb), lds, s, dev, ix, line_bytes / 4, wpb);
+        else hipLaunchKernelGGL((k_resize_area_wide_mix<3>), grid, dim3(64 * wpb), lds, s, dev, ix, line_bytes / 4, wpb);
+    });
+}
+
+// one frame of a mix through launch_cv_resize
+static int launch_lone(const MixFrame& f, int cn, int interp, hipStream_t s) {
+    Frames one{};
+    one.src = f.src; one.src_stride = 0; one.v = View{f.src, f.sw, f.sh, cn, f.sstep};
+    one.dst = f.dst; one.dst_stride = 0; one.dw = f.dw; one.dh = f.dh; one.dstep = f.dstep; one.count = 1;
+    return launch_cv_resize(one, interp, s);
+}
+
+static void set_split(MixDesc* d, const RowSplit& r) { d->rows = r.bh; d->nstrips = r.nstrips; d->nitems = r.nitems; d->nblk = r.nblk; }
+
+// The classes of a mixed launch, in the order they are launched, and the descriptor of a frame: the member its class names.
+enum { MIX_LONE = -1, MIX_WHOLE = 0, MIX_NN, MIX_WIDE, MIX_ROWS, MIX_CLASSES };
+struct MixVerdict { MixDesc m; IntMixDesc whole; NnMixDesc nn; int line_bytes; };
+
+// The class of one frame of a mix of `count`, and its descriptor.  The rules are launch_cn's, except where a mix differs on
+// purpose:
+//  - four columns per lane needs `waves4 >= 2048` alone; a mix does not ask (its other frames fill the chip);
+//  - the mix carries the even windows only (`even` of area_rows_plan): half the instances in one kernel;
+//  - BGR rows that are not 4-byte aligned pick AREA_ROWS by `big` (blocks in the launch) alone and by `scale_y < 8` in a mix;
+//  - the three whole-factor exceptions above int_mix_desc;
+//  - a wide frame's `nblk` waits for launch_wide_mix: it follows the launch's longest line, known only once every frame is in.
+static int classify_mixed(const MixFrame& f, int cn, int interp, int count, MixVerdict* out) {
+    const double scale_x = 1. / ((double)f.dw / f.sw), scale_y = 1. / ((double)f.dh / f.sh);
+    const bool whole = whole_factors(scale_x, scale_y);
+    if (interp == IMP_INTER_NN) {
+        NnMixDesc& d = out->nn = NnMixDesc{};
+        d.a = rargs(f);
+        d.scale_x = scale_x;
+        d.scale_y = scale_y;
+        d.nblk = (int)(((long long)f.dw * f.dh + 255) / 256);
+        return MIX_NN;
+    }
+    if (interp == IMP_INTER_AREA && whole) {
+        const int isx = (int)std::lrint(scale_x), isy = (int)std::lrint(scale_y);
+        if ((long long)isx * f.dw == f.sw && (long long)isy * f.dh == f.sh) {      // (what `whole` means; the bodies' reads rest on it)
+            out->whole = int_mix_desc(f, cn, isx, isy);
+            return MIX_WHOLE;
+        }
+    }
+    if (interp != IMP_INTER_AREA || whole) return MIX_LONE;
+    MixDesc& d = out->m = MixDesc{};
+    d.a = rargs(f);
+    d.gm = AreaGeom{scale_x, scale_y};
+    if (cn == 1) {
+        // gray: any pointer, any pitch (the body aligns its own fetches); the window decides
+        int w1 = 0, p1 = 0, bh1 = 0;
+        if (!gray_rows_plan(f.sw, f.dw, f.dh, scale_x, count, &w1, &p1, &bh1)) return MIX_LONE;
+        d.nv = p1 == 4 ? -w1 : w1;
+        set_split(&d, row_split(f.dw, f.dh, 64 * p1, bh1));
+        return MIX_ROWS;
+    }
+    const bool aligned = !(((uintptr_t)f.src | (uintptr_t)f.sstep) & 3);
+    int w4 = 0, bh4 = 0;
+    if ((cn == 4 || (aligned && f.sw >= 6)) && f.dw >= 160 && area_rows_plan(f.sw, f.sh, f.dw, f.dh, scale_x, count, false, &w4, &bh4) &&
+        w4 >= 2 && w4 <= 5 && 255 * scale_x + w4 + 8 <= (cn == 4 ? 1024 : 1340)) {
+        // windows of at most five pixels (factors below ~3.9): four destination columns per lane, like the uniform batches
+        d.nv = -w4;
+        set_split(&d, row_split(f.dw, f.dh, 256, bh4));
+        return MIX_ROWS;
+    }
+    if ((cn == 4 || (aligned && f.sw >= 6)) && area_rows_plan(f.sw, f.sh, f.dw, f.dh, scale_x, count, true, &d.nv, &d.rows)) {
+        set_split(&d, row_split(f.dw, f.dh, 64, d.rows));
+        return MIX_ROWS;
+    }
+    if (cn == 3) {
+        // the widest cell decides the window: ceil(scale) <= widest <= floor(scale) + 2; the axis is walked only
+        // when those two ends name different windows (a wider window than needed is still exact, only slower)
+        const int nv_lo = ((int)std::ceil(scale_x) + 3) / 4, nv_hi = ((int)std::floor(scale_x) + 2 + 3) / 4;
+        const int nv = nv_lo == nv_hi ? nv_hi : (area_max_count(f.sw, f.dw, scale_x) + 3) / 4;
+        if (nv >= 1 && nv <= MIX_NV && f.sw >= 4 * nv) {
+            d.nv = nv;
+            d.rows = scale_y < 8 ? AREA_ROWS : 1;   // tall cells: sharing one boundary row in nine is not worth a quarter of the blocks
+            d.nblk = (int)(((long long)f.dw * ((f.dh + d.rows - 1) / d.rows) + 255) / 256);
+            d.nitems = 0;
+            return MIX_ROWS;
+        }
+    }
+    if (area_wide_plan(f.sw, f.sh, f.dw, f.dh, cn, interp, f.src, f.sstep, 0, count, &d.nv, &d.rows, &out->line_bytes)) {
+        set_split(&d, row_split(f.dw, f.dh, 64, d.rows));
+        return MIX_WIDE;
+    }
+    return MIX_LONE;
 }
 
 int launch_resize_mixed(const MixFrame* fr, int count, int cn, int simple, hipStream_t s) {
@@ -3933,125 +4003,44 @@ int launch_resize_mixed(const MixFrame* fr, int count, int cn, int simple, hipSt
         if (!f.src || !f.dst || !view_fits(f.sw, f.sh, cn, f.sstep) || !view_fits(f.dw, f.dh, cn, f.dstep)) return IMP_ERROR_INVALID_ARGS;
         if (cn == 4 && (((uintptr_t)f.src | (uintptr_t)f.dst | (uintptr_t)f.sstep | (uintptr_t)f.dstep) & 3)) return IMP_ERROR_INVALID_ARGS;
     }
-    std::vector<MixDesc> gathered_frames;
-    std::vector<IntMixDesc> int_frames;                    // whole-factor AREA (resizeAreaFast_), any channel count
+    std::vector<IntMixDesc> whole_frames;                  // whole-factor AREA (resizeAreaFast_), any channel count
     std::vector<NnMixDesc> nn_frames;
     std::vector<MixDesc> wide_frames;                      // colour, cells of 21..66 source columns (area_wide_plan)
-    int wide_line = 0;                                     // the longest LDS line among them, in bytes
-    int int_one = -1, nn_one = -1, gray_one = -1, wide_one = -1;   // the frame of a vector that holds exactly one
-    gathered_frames.reserve(count);
-    auto lone = [&](const MixFrame& f, int interp) {
-        Frames one{};
-        one.src = f.src; one.src_stride = 0; one.v = View{f.src, f.sw, f.sh, cn, f.sstep};
-        one.dst = f.dst; one.dst_stride = 0; one.dw = f.dw; one.dh = f.dh; one.dstep = f.dstep; one.count = 1;
-        return launch_cv_resize(one, interp, s);
-    };
+    std::vector<MixDesc> rows_frames;                      // general AREA, cells of at most 20 columns
+    int wide_line = 0;                                     // the longest LDS line among the wide frames, in bytes
+    int members[MIX_CLASSES] = {0, 0, 0, 0}, last[MIX_CLASSES] = {-1, -1, -1, -1};   // frames of a class, and the latest of them
+    rows_frames.reserve(count);
     for (int i = 0; i < count; i++) {
         const MixFrame& f = fr[i];
         const int interp = simple ? IMP_INTER_NN : ((f.dw > f.sw || f.dh > f.sh) ? IMP_INTER_CUBIC : IMP_INTER_AREA);   // bridge.c:188-192
-        const double scale_x = 1. / ((double)f.dw / f.sw), scale_y = 1. / ((double)f.dh / f.sh);
-        const bool whole = std::fabs(scale_x - std::lrint(scale_x)) < 2.220446049250313e-16 &&
-                           std::fabs(scale_y - std::lrint(scale_y)) < 2.220446049250313e-16;
-        if (interp == IMP_INTER_NN) {
-            NnMixDesc d{};
-            d.a = RArgs{f.src, 0, f.sstep, f.sw, f.sh, f.dst, 0, f.dstep, f.dw, f.dh};
-            d.scale_x = scale_x;
-            d.scale_y = scale_y;
-            d.nblk = (int)(((long long)f.dw * f.dh + 255) / 256);
-            nn_frames.push_back(d);
-            nn_one = i;
+        MixVerdict d;
+        const int k = classify_mixed(f, cn, interp, count, &d);
+        if (k == MIX_LONE) {
+            if (int rc = launch_lone(f, cn, interp, s)) return rc;
             continue;
         }
-        if (interp == IMP_INTER_AREA && whole) {
-            const int isx = (int)std::lrint(scale_x), isy = (int)std::lrint(scale_y);
-            if ((long long)isx * f.dw == f.sw && (long long)isy * f.dh == f.sh) {      // (what `whole` means; the bodies' reads rest on it)
-                int_frames.push_back(int_mix_desc(f, cn, isx, isy));
-                int_one = i;
-                continue;
-            }
+        members[k]++;
+        last[k] = i;
+        if (k == MIX_WHOLE) whole_frames.push_back(d.whole);
+        else if (k == MIX_NN) nn_frames.push_back(d.nn);
+        else if (k == MIX_ROWS) rows_frames.push_back(d.m);
+        else {
+            wide_frames.push_back(d.m);
+            wide_line = std::max(wide_line, d.line_bytes);
         }
-        bool gathered = false;
-        if (interp == IMP_INTER_AREA && !whole && cn != 1) {
-            MixDesc d{};
-            d.a = RArgs{f.src, 0, f.sstep, f.sw, f.sh, f.dst, 0, f.dstep, f.dw, f.dh};
-            d.gm = AreaGeom{scale_x, scale_y};
-            const bool aligned = !(((uintptr_t)f.src | (uintptr_t)f.sstep) & 3);
-            int w4 = 0, bh4 = 0;
-            if ((cn == 4 || (aligned && f.sw >= 6)) && f.dw >= 160 && area_rows_plan(f.sw, f.sh, f.dw, f.dh, scale_x, count, false, &w4, &bh4) &&
-                w4 >= 2 && w4 <= 5 && 255 * scale_x + w4 + 8 <= (cn == 4 ? 1024 : 1340)) {
-                // windows of at most five pixels (factors below ~3.9): four destination columns per lane, like the uniform batches
-                d.nv = -w4;
-                d.rows = bh4;
-                d.nstrips = (f.dw + 255) / 256;
-                d.nitems = d.nstrips * ((f.dh + d.rows - 1) / d.rows);
-                d.nblk = (d.nitems + 3) / 4;
-                gathered = true;
-            } else if ((cn == 4 || (aligned && f.sw >= 6)) && area_rows_plan(f.sw, f.sh, f.dw, f.dh, scale_x, count, true, &d.nv, &d.rows)) {
-                d.nstrips = (f.dw + 63) / 64;
-                d.nitems = d.nstrips * ((f.dh + d.rows - 1) / d.rows);
-                d.nblk = (d.nitems + 3) / 4;
-                gathered = true;
-            } else if (cn == 3) {
-                // the widest cell decides the window: ceil(scale) <= widest <= floor(scale) + 2; the axis is walked only
-                // when those two ends name different windows (a wider window than needed is still exact, only slower)
-                const int nv_lo = ((int)std::ceil(scale_x) + 3) / 4, nv_hi = ((int)std::floor(scale_x) + 2 + 3) / 4;
-                const int nv = nv_lo == nv_hi ? nv_hi : (area_max_count(f.sw, f.dw, scale_x) + 3) / 4;
-                if (nv >= 1 && nv <= MIX_NV && f.sw >= 4 * nv) {
-                    d.nv = nv;
-                    d.rows = scale_y < 8 ? AREA_ROWS : 1;   // tall cells: sharing one boundary row in nine is not worth a quarter of the blocks
-                    d.nblk = (int)(((long long)f.dw * ((f.dh + d.rows - 1) / d.rows) + 255) / 256);
-                    d.nitems = 0;
-                    gathered = true;
-                }
-            }
-            if (gathered) gathered_frames.push_back(d);
-            int line_bytes = 0;
-            if (!gathered && area_wide_plan(f.sw, f.sh, f.dw, f.dh, cn, interp, f.src, f.sstep, 0, count, &d.nv, &d.rows, &line_bytes)) {
-                d.nstrips = (f.dw + 63) / 64;
-                d.nitems = d.nstrips * ((f.dh + d.rows - 1) / d.rows);       // (nblk: launch_wide_mix, once the longest line is known)
-                wide_frames.push_back(d);
-                wide_line = std::max(wide_line, line_bytes);
-                wide_one = i;
-                gathered = true;
-            }
-        }
-        if (interp == IMP_INTER_AREA && !whole && cn == 1) {
-            // gray: any pointer, any pitch (the body aligns its own fetches); the window decides
-            MixDesc d{};
-            d.a = RArgs{f.src, 0, f.sstep, f.sw, f.sh, f.dst, 0, f.dstep, f.dw, f.dh};
-            d.gm = AreaGeom{scale_x, scale_y};
-            int w1 = 0, p1 = 0;
-            if (gray_rows_plan(f.sw, f.dw, f.dh, scale_x, count, &w1, &p1, &d.rows)) {
-                d.nv = p1 == 4 ? -w1 : w1;
-                d.nstrips = (f.dw + 64 * p1 - 1) / (64 * p1);
-                d.nitems = d.nstrips * ((f.dh + d.rows - 1) / d.rows);
-                d.nblk = (d.nitems + 3) / 4;
-                gathered_frames.push_back(d);
-                gray_one = i;
-                gathered = true;
-            }
-        }
-        if (!gathered)
-            if (int rc = lone(f, interp)) return rc;
     }
-    // a vector of one keeps the lone launch and its tuned kernel; two or more share a descriptor launch
-    if (int_frames.size() == 1) {
-        if (int rc = lone(fr[int_one], IMP_INTER_AREA)) return rc;
-    } else if (!int_frames.empty()) {
-        if (int rc = launch_int_mix(int_frames, cn, s)) return rc;
+    // a class of one keeps the lone launch and its tuned kernel; two or more share a descriptor launch.  The exception: a
+    // single colour frame of MIX_ROWS rides k_resize_area_mix all the same (a gray one goes to k_resize_area<1> and its tables).
+    for (int k = 0; k < MIX_CLASSES; k++) {
+        int rc = IMP_OK;
+        if (members[k] == 1 && (k != MIX_ROWS || cn == 1)) rc = launch_lone(fr[last[k]], cn, k == MIX_NN ? IMP_INTER_NN : IMP_INTER_AREA, s);
+        else if (k == MIX_WHOLE) rc = launch_int_mix(whole_frames, cn, s);
+        else if (k == MIX_NN) rc = launch_nn_mix(nn_frames, cn, s);
+        else if (k == MIX_WIDE) rc = launch_wide_mix(wide_frames, cn, wide_line, s);
+        else rc = launch_mix(rows_frames, cn, s);
+        if (rc) return rc;
     }
-    if (nn_frames.size() == 1) {
-        if (int rc = lone(fr[nn_one], IMP_INTER_NN)) return rc;
-    } else if (!nn_frames.empty()) {
-        if (int rc = launch_nn_mix(nn_frames, cn, s)) return rc;
-    }
-    if (wide_frames.size() == 1) {
-        if (int rc = lone(fr[wide_one], IMP_INTER_AREA)) return rc;
-    } else if (!wide_frames.empty()) {
-        if (int rc = launch_wide_mix(wide_frames, cn, wide_line, s)) return rc;
-    }
-    if (cn == 1 && gathered_frames.size() == 1) return lone(fr[gray_one], IMP_INTER_AREA);      // (k_resize_area<1> and its tables)
-    return launch_mix(gathered_frames, cn, s);
+    return IMP_OK;
 }
 
 int launch_area_tail_mixed(const TailItem* items, int count, int cn, hipStream_t s) {
@@ -4072,30 +4061,19 @@ int launch_area_tail_mixed(const TailItem* items, int count, int cn, hipStream_t
         if (!area_tail_plan(f, &w, &bh)) return IMP_ERROR_INVALID_ARGS;
         MixTailDesc& d = v[(size_t)i];
         d = MixTailDesc{};
-        d.m.a = RArgs{it.v.d, 0, it.v.step, it.v.w, it.v.h, it.dst, 0, it.dstep, it.dw, it.dh};
+        d.m.a = rargs(f);                                  // (strides 0: a frame per descriptor)
         d.m.gm = AreaGeom{1. / ((double)it.dw / it.v.w), 1. / ((double)it.dh / it.v.h)};
         d.m.nv = w;
-        d.m.rows = bh;
-        d.m.nstrips = (it.dw + 63) / 64;
-        d.m.nitems = d.m.nstrips * ((it.dh + bh - 1) / bh);
-        d.m.nblk = (d.m.nitems + 3) / 4;
+        set_split(&d.m, row_split(it.dw, it.dh, 64, bh));
         d.tail.rot = it.rot;
         if (it.has_wm) d.tail.wm = it.wm;
         d.flat = it.flatten && cn == 4;
     }
-    std::vector<MixTailDesc> sorted;
-    MixIndex ix{};
-    int most = 0;
-    mix_deal_area(v, [](MixTailDesc& d) -> MixDesc& { return d.m; }, &sorted, &ix, &most);
-    void* dev = nullptr;
-    if (int rc = upload_small(sorted.data(), sorted.size() * sizeof(MixTailDesc), &dev, s)) return rc;
-    const dim3 grid((unsigned)most * 8), block(256);
-    if (cn == 4) hipLaunchKernelGGL((k_resize_area_mix_tail<4>), grid, block, 0, s, (const MixTailDesc*)dev, ix);
-    else hipLaunchKernelGGL((k_resize_area_mix_tail<3>), grid, block, 0, s, (const MixTailDesc*)dev, ix);
-    const hipError_t e = hipGetLastError();
-    dev_free_on(dev, s);
-    IMP_HIP(e);
-    return IMP_OK;
+    return mix_launch(v, [](MixTailDesc& d) -> MixDesc& { return d.m; }, [](MixTailDesc& d) { return (long long)d.m.a.sw * d.m.a.sh; }, s,
+                      [&](dim3 grid, const MixTailDesc* dev, const MixIndex& ix) {
+        if (cn == 4) hipLaunchKernelGGL((k_resize_area_mix_tail<4>), grid, dim3(256), 0, s, dev, ix);
+        else hipLaunchKernelGGL((k_resize_area_mix_tail<3>), grid, dim3(256), 0, s, dev, ix);
+    });
 }
 
 }  // namespace imp
