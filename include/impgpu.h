@@ -477,7 +477,7 @@ int impgpu_run_ops(impgpu_image** pointer, const impgpu_job* job, const impgpu_c
  * flip / turn -- one launch per kind and channel count, so the number of launches follows the chains' length, not the
  * number of requests.  Bare resizes with whole factors (resizeAreaFast_: 1280x720 or 1920x1080 at 320 wide) share one
  * launch per channel count too, and so do the NN resizes of `simple` requests.  Resizes launch_resize_mixed does not
- * gather (enlargements, extreme ratios: cells past 20 source columns for gray, past 66 for colour) and blurs outside
+ * gather (enlargements, extreme ratios: cells past 66 source columns) and blurs outside
  * the one-pass forms (large radii) still take a launch per request inside their round.  A single GRAY frame with a resize rides the same launches: its resize joins the gray
  * group of impgpu_batch_resize_mixed (channels = 1), ONE k_gray2bgr_mix launch then promotes every gray request of the call
  * (bridge.c:613-618, the filtering step -- entered for a gray frame even without filters; a request whose fault point fires
@@ -569,15 +569,15 @@ int impgpu_batch_cv_resize(const void* src, long long src_frame_stride, int src_
  * in HBM): each item is cvResize'd with the interpolation Resize() picks for it -- NN when `simple`, CUBIC when either
  * side grows, AREA otherwise (bridge.c:188-192) -- but frames that share a kernel ride in one launch (a descriptor per
  * frame), so a run of thumbnails costs a handful of launches instead of one per request: one for the general AREA
- * shrinks whose cells span at most 20 source columns (factors up to about 18), one for the BGR / BGRA shrinks past that
- * with cells of 21..66 columns (factors up to 64: a 4032-wide photo at 200 wide and below; source rows and pointers
- * 4-byte aligned), one for the AREA shrinks whose two factors are whole numbers, one for the NN frames -- at most four
- * for 3 / 4 channels, three for gray.  Gray general AREA shrinks (cells of up to 20 source columns: every geometry with both
- * factors up to 16) are gathered whatever their source pointer, pitch and destination alignment are: a crop window of a
+ * shrinks whose cells span at most 20 source columns (factors up to about 18), one for the shrinks past that
+ * with cells of 21..66 columns (factors up to 64: a 4032-wide photo at 200 wide and below, a 600 dpi A4 scan at 150 wide;
+ * any channel count, source pointer and pitch -- a BGR crop window may start at any column), one for the AREA shrinks
+ * whose two factors are whole numbers, one for the NN frames -- at most four per channel count.  Gray general AREA
+ * shrinks are gathered whatever their source pointer, pitch and destination alignment are: a crop window of a
  * gray scan starts at any byte (launch counts are tested; the gray launch has not yet been timed against the per-frame
  * loop: DESIGN section 4).  A frame that is the only one of its kind in the call, and what no descriptor launch
- * gathers -- enlargements (CUBIC), extreme ratios (cells wider than the row kernels take: past 20 source columns for gray
- * frames and for BGR rows that are not 4-byte aligned, past 66 for colour) -- take one launch each.  Same bytes
+ * gathers -- enlargements (CUBIC), extreme ratios (cells past 66 source columns, whatever the channel count) -- take
+ * one launch each.  Same bytes
  * as calling impgpu_batch_cv_resize once per item.  Nothing is launched if any item is malformed
  * (IMP_ERROR_INVALID_ARGS).  The _ex form also reports the number of kernels it enqueued in *launches (may be NULL). */
 typedef struct impgpu_resize_item {

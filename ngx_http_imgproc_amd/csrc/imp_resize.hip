@@ -2514,12 +2514,22 @@ __global__ __launch_bounds__(256) void k_resize_area_rows4(RArgs a, AreaGeom gm,
 //     one row ahead of the arithmetic, as there, the rest (segments over 4 KB) when the row is parked;
 //   * no tail: a finished row leaves as it is.
 // The float sequence is resizeArea_'s, as in every body above.  `line_dw` = the line's length in dwords.
+// Two ways to fetch a row (COVER, wave-uniform, area_wide_plan's verdict):
+//   * aligned (BGRA; BGR whose pointer and pitch are 4-byte aligned): granules counted from a.src, the last one moved
+//     back when it would pass the row's padded end (`ragged`);
+//   * covering (gray; BGR off the 4-byte grid): area_rows_gray_body's scheme, which asks nothing of the source -- the
+//     16-byte granules, aligned by absolute address, that cover the wave's segment of the row, and the segment's offset
+//     inside its first granule (`dl`, wave-uniform, different from row to row when the pitch is no multiple of 16) added
+//     to every lane's window place.  An aligned granule that holds one byte of the frame never leaves the frame's pages,
+//     so no granule is moved.  A row's granule count follows its `dl`.
 constexpr int WIDE_W_MIN = 4 * MIX_NV + 1, WIDE_W_MAX = 66;   // cells of 21..66 columns: factors up to 64
 constexpr int WIDE_PIECE = 4;                                  // 16-byte granules of a row a lane holds at a time
-template <int CN>
-__device__ __forceinline__ void area_wide_body(const RArgs& a, const AreaGeom& gm, int frame, int item, int nstrips, int bh,
+template <int CN, bool COVER>
+__device__ __forceinline__ void area_wide_impl(const RArgs& a, const AreaGeom& gm, int frame, int item, int nstrips, int bh,
                                                int W, int line_dw, uint32_t* __restrict__ line) {
-    static_assert(CN == 3 || CN == 4, "interleaved BGR / BGRA");
+    static_assert(CN == 1 || CN == 3 || CN == 4, "gray, or interleaved BGR / BGRA");
+    static_assert(CN != 1 || COVER, "gray rows are always fetched by covering granules");
+    static_assert(CN != 4 || !COVER, "BGRA rows are always 4-byte aligned");
     const int lane = threadIdx.x & 63;
     const int band = item / nstrips, strip = item - band * nstrips;
     const int dy0 = band * bh;
@@ -2537,30 +2547,43 @@ __device__ __forceinline__ void area_wide_body(const RArgs& a, const AreaGeom& g
         w = k == kf ? cx.af : w;
         return k == kl ? cx.al : w;
     };
-    // the wave's segment in bytes of the source row, as in area_rows_body
+    // the wave's segment in bytes of the source row, as in area_rows_body; covering: from lane 0's window to the end of
+    // lane 63's, wherever that lies (a window never leaves the row, so neither does the segment)
     const int row_end = (a.sw * CN + 3) & ~3;
-    const int b0 = min((__builtin_amdgcn_readlane(xs, 0) * CN) & ~15, (row_end - 16) & ~15);
-    const int ngran = ((__builtin_amdgcn_readlane(xs, 63) + W) * CN - b0 + 15) >> 4;
+    const int x0b = __builtin_amdgcn_readlane(xs, 0) * CN;
+    const int b0 = COVER ? x0b : min(x0b & ~15, (row_end - 16) & ~15);
+    const int seglen = (__builtin_amdgcn_readlane(xs, 63) + W) * CN - b0;
+    int ngran = ((COVER ? 15 : 0) + seglen + 15) >> 4;           // covering: the most a row can need (dl = 15); each row's own below
     if (ngran * 4 + 4 > line_dw) return;                         // (never: area_wide_plan sizes the line for the longest segment)
-    const int wofs = xs * CN - b0;                               // this lane's window in the parked line, in bytes
+    const int wrel = xs * CN - b0;                               // this lane's window in the segment, in bytes
     const uint8_t* S = a.src + (long long)frame * a.src_stride + (size_t)b0;
     // Every lane fetches whole pieces and parks them, with no predication: lanes past the segment repeat its last granule.
-    // When the last granule would leave the row's padded end it is moved back to end exactly there and the row is parked
-    // dword by dword (wave-uniform branch).
-    const bool ragged = b0 + 16 * ngran > row_end;
-    const int npieces = (ngran + 64 * WIDE_PIECE - 1) / (64 * WIDE_PIECE);
-    auto gran_ofs = [&](int j) {                                 // byte offset of this lane's j-th granule in the segment
+    // Aligned: when the last granule would leave the row's padded end it is moved back to end exactly there and the row is
+    // parked dword by dword (wave-uniform branch).
+    const bool ragged = !COVER && b0 + 16 * ngran > row_end;
+    auto gran_ofs = [&](int j) {                                 // byte offset of this lane's j-th granule in the line
         const int gi = min(j * 64 + lane, ngran - 1);
         return (ragged && gi == ngran - 1) ? row_end - 16 - b0 : gi * 16;
     };
     int gofs[WIDE_PIECE];
+    if constexpr (!COVER) {
 #pragma unroll
-    for (int j = 0; j < WIDE_PIECE; j++) gofs[j] = gran_ofs(j);
+        for (int j = 0; j < WIDE_PIECE; j++) gofs[j] = gran_ofs(j);
+    }
     uint32_t nxt[WIDE_PIECE][4];                                 // the first piece of the row ahead
+    int dnxt = 0, dcur = 0;                                      // covering: `dl` of the row in flight / of the parked row
     auto fetch = [&](int sy) {
         const uint8_t* row = S + (size_t)sy * a.sstep;
+        if constexpr (COVER) {                                   // this row's granules: `ngran` holds until the row is parked
+            dnxt = __builtin_amdgcn_readfirstlane((int)((uintptr_t)row & 15));
+            ngran = (dnxt + seglen + 15) >> 4;
+            row -= dnxt;
 #pragma unroll
-        for (int j = 0; j < WIDE_PIECE; j++) load_stream<4>(nxt[j], row + gofs[j]);
+            for (int j = 0; j < WIDE_PIECE; j++) load_stream<4>(nxt[j], row + gran_ofs(j));
+        } else {
+#pragma unroll
+            for (int j = 0; j < WIDE_PIECE; j++) load_stream<4>(nxt[j], row + gofs[j]);
+        }
     };
     auto park = [&](const uint32_t (*q)[4], const int* ofs) {
         if (!ragged) {
@@ -2580,8 +2603,14 @@ __device__ __forceinline__ void area_wide_body(const RArgs& a, const AreaGeom& g
     float b[CN];
     auto reduce = [&](int sy) {                                  // park row sy: its first piece is in `nxt`, the rest comes now
         asm volatile("" ::: "memory");
+        if constexpr (COVER) {                                   // (worked out again: four registers fewer across the row sum)
+#pragma unroll
+            for (int j = 0; j < WIDE_PIECE; j++) gofs[j] = gran_ofs(j);
+        }
         park(nxt, gofs);
-        const uint8_t* row = S + (size_t)sy * a.sstep;
+        dcur = dnxt;
+        const uint8_t* row = S + (size_t)sy * a.sstep - dcur;
+        const int npieces = (ngran + 64 * WIDE_PIECE - 1) / (64 * WIDE_PIECE);
         for (int p = 1; p < npieces; p++) {
             uint32_t more[WIDE_PIECE][4];
             int mofs[WIDE_PIECE];
@@ -2597,7 +2626,17 @@ __device__ __forceinline__ void area_wide_body(const RArgs& a, const AreaGeom& g
     auto hsum = [&]() {
 #pragma unroll
         for (int c = 0; c < CN; c++) b[c] = 0.f;
-        if constexpr (CN == 4) {
+        const int wofs = wrel + dcur;                            // this lane's window in the parked line, in bytes
+        if constexpr (CN == 1) {
+            // four pixels = one dword at a byte offset: two aligned dwords + v_alignbyte_b32
+            const uint32_t* win = line + (wofs >> 2);
+            const unsigned sh = (unsigned)wofs & 3u;
+            for (int k = 0; k < W; k += 4, win++) {
+                const uint32_t w = __builtin_amdgcn_alignbyte(win[1], win[0], sh);
+#pragma unroll
+                for (int t = 0; t < 4; t++) b[0] = __fadd_rn(b[0], __fmul_rn((float)((w >> (8 * t)) & 0xff), weight(k + t)));
+            }
+        } else if constexpr (CN == 4) {
             const uint32_t* win = line + (wofs >> 2);
             for (int k = 0; k < W; k += 4) {
 #pragma unroll
@@ -2666,9 +2705,20 @@ __device__ __forceinline__ void area_wide_body(const RArgs& a, const AreaGeom& g
         for (int c = 0; c < CN; c++) px = cvt_pk_u8(acc[c], px, c);
         if (live) {
             if constexpr (CN == 4) *(uint32_t*)(D + (size_t)dy * a.dstep) = px;
-            else store_bgr(D + (size_t)dy * a.dstep, px);
+            else if constexpr (CN == 3) store_bgr(D + (size_t)dy * a.dstep, px);
+            else D[(size_t)dy * a.dstep] = (uint8_t)px;
         }
     }
+}
+
+// `W` = the window; negative: a BGR frame that needs the covering fetch (gray always takes it, BGRA never).
+template <int CN>
+__device__ __forceinline__ void area_wide_body(const RArgs& a, const AreaGeom& gm, int frame, int item, int nstrips, int bh,
+                                               int W, int line_dw, uint32_t* __restrict__ line) {
+    if constexpr (CN == 1) area_wide_impl<1, true>(a, gm, frame, item, nstrips, bh, W, line_dw, line);
+    else if constexpr (CN == 4) area_wide_impl<4, false>(a, gm, frame, item, nstrips, bh, W, line_dw, line);
+    else if (W < 0) area_wide_impl<3, true>(a, gm, frame, item, nstrips, bh, -W, line_dw, line);   // (wave-uniform: a scalar branch)
+    else area_wide_impl<3, false>(a, gm, frame, item, nstrips, bh, W, line_dw, line);
 }
 
 // `wpb` = waves per block (4; 2 when four of the longest lines would not fit 64 KB): a wave per item, a line per wave.
@@ -2817,6 +2867,7 @@ __device__ __forceinline__ void area_rows_gray_body(const RArgs& a, const AreaGe
 //   k_resize_area_mix<3 / 4>, nitems > 0   the window W in pixels (even); negative: four columns per lane, window -nv (2..5)
 //   k_resize_area_mix<3>, nitems == 0      area_cells_body's NV: 16-byte granules of a lane's run
 //   k_resize_area_mix<1>                   always nitems > 0: W in pixels = bytes (even, 2..20), or -W (2..5) with four columns per lane
+//   k_resize_area_wide_mix<1 / 3 / 4>      W in pixels (21..66); <3>: -W when the frame needs the covering fetch
 struct MixDesc { RArgs a; AreaGeom gm; int first, nblk, nv, rows, nstrips, nitems; };   // rows = band height (nitems > 0) or rows per lane group
 
 template <int CN>
@@ -2923,8 +2974,9 @@ __global__ __launch_bounds__(256) void k_resize_area_mix_tail(const MixTailDesc*
     }
 }
 
-// Colour frames whose cells span 21..66 source columns (area_wide_plan), of different geometry, in one launch: the
-// descriptor scheme around area_wide_body.  nv = the window W, rows = the band height, nblk = ceil(nitems / wpb).  A kernel
+// Frames whose cells span 21..66 source columns (area_wide_plan), of different geometry, in one launch: the descriptor
+// scheme around area_wide_body.  nv = the window W (negative: a BGR frame off the 4-byte grid, fetched by covering
+// granules: wide_nv), rows = the band height, nblk = ceil(nitems / wpb).  A kernel
 // of its own: its lines are dynamic LDS sized for the longest segment of the launch (`line_dw` dwords each, `wpb` of them),
 // which k_resize_area_mix's frames never pay.
 template <int CN>
@@ -3241,17 +3293,21 @@ static bool gray_rows_plan(int sw, int dw, int dh, double scale_x, long long fra
 }
 
 // area_wide_body for this frame?  The one acceptance rule of k_resize_area_wide (launch_cn) and k_resize_area_wide_mix
-// (launch_resize_mixed): a general INTER_AREA shrink of a colour frame whose source rows are 4-byte aligned and whose
+// (launch_resize_mixed): a general INTER_AREA shrink, of a gray, BGR or BGRA frame with any pointer and pitch, whose
 // widest horizontal cell spans 21..66 source columns (factors up to 64; narrower cells belong to the bodies with
-// compile-time windows, wider ones and gray frames stay with k_resize_area and its tables).  *w = that widest cell, *bh as
-// area_rows_plan picks it, *line_bytes = a wave's LDS line: the longest segment a strip can have -- lane 63's window
-// starts less than 63 * scale_x + 2 pixels after lane 0's -- with the granule rounding at both ends (30 bytes), plus the
-// 16 bytes a last turn of four pixels and a BGR window's look-ahead dword may read past it, rounded up.
+// compile-time windows, wider ones stay with k_resize_area and its tables).  *w = that widest cell, *bh as
+// area_rows_plan picks it, *cover = the frame needs the covering fetch (gray; BGR off the 4-byte grid), *line_bytes = a
+// wave's LDS line: the longest segment a strip can have -- lane 63's window starts less than 63 * scale_x + 2 pixels
+// after lane 0's -- with the granule rounding at both ends (30 bytes: aligned, up to 15 in front of the segment and 15
+// after it; covering, `dl` <= 15 and the same 15), plus the 16 bytes a last turn of four pixels and a window's look-ahead
+// dword may read past it, rounded up.
 static bool area_wide_plan(int sw, int sh, int dw, int dh, int cn, int interp, const uint8_t* src, int sstep, long long src_stride,
-                           long long frames, int* w, int* bh, int* line_bytes) {
+                           long long frames, int* w, int* bh, int* line_bytes, bool* cover) {
     (void)sh;
-    if (interp != IMP_INTER_AREA || (cn != 3 && cn != 4) || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || dw > sw || dh > sh) return false;
-    if (((uintptr_t)src | (uintptr_t)sstep | (uintptr_t)src_stride) & 3) return false;
+    if (interp != IMP_INTER_AREA || (cn != 1 && cn != 3 && cn != 4) || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || dw > sw || dh > sh)
+        return false;
+    const bool off_grid = (((uintptr_t)src | (uintptr_t)sstep | (uintptr_t)src_stride) & 3) != 0;
+    if (cn == 4 && off_grid) return false;                 // (no caller passes one: BGRA pixels are dwords)
     const double scale_x = 1. / ((double)dw / sw), scale_y = 1. / ((double)dh / sh);
     if (whole_factors(scale_x, scale_y)) return false;                                    // resizeAreaFast_: the box kernels' arithmetic
     if (scale_x > 70) return false;                        // (no cell of 66 columns or fewer: the axis need not be walked)
@@ -3260,9 +3316,11 @@ static bool area_wide_plan(int sw, int sh, int dw, int dh, int cn, int interp, c
     *w = ww;
     *bh = area_band_height(frames, (dw + 63) / 64, dh);
     *line_bytes = ((((int)std::ceil(63 * scale_x) + ww + 2) * cn + 30 + 15) & ~15) + 32;
+    *cover = cn == 1 || off_grid;
     return true;
 }
 constexpr int wide_wpb(int line_bytes) { return 4 * line_bytes <= 65536 ? 4 : 2; }   // waves (= lines) per block: 64 KB of LDS at most
+constexpr int wide_nv(int cn, int w, bool cover) { return cn == 3 && cover ? -w : w; }   // the window as area_wide_body reads it
 
 template <int CN>
 static void launch_area_rows(int w, const RowSplit& r, hipStream_t s, const RArgs& a, const AreaGeom& gm, int count, const AreaTail& tail) {
@@ -3379,20 +3437,20 @@ static int launch_area_general(const RArgs& a, int count, int interp, double sca
         });
         return launched();
     }
-    // BGRA / BGR with cells of 21..66 source columns (shrinks past 18x, up to 64x): the same walk with a runtime
-    // window and a dynamic LDS line -- no table either
-    if constexpr (CN == 3 || CN == 4) {
+    // cells of 21..66 source columns (shrinks past 18x, up to 64x), any channel count, pointer and pitch: the same walk
+    // with a runtime window and a dynamic LDS line -- no table either
+    {
         int w = 0, bh = 0, line_bytes = 0;
-        if (area_wide_plan(a.sw, a.sh, a.dw, a.dh, CN, interp, a.src, a.sstep, a.src_stride, count, &w, &bh, &line_bytes)) {
+        bool cover = false;
+        if (area_wide_plan(a.sw, a.sh, a.dw, a.dh, CN, interp, a.src, a.sstep, a.src_stride, count, &w, &bh, &line_bytes, &cover)) {
             const int wpb = wide_wpb(line_bytes);
             const RowSplit r = row_split(a.dw, a.dh, 64, bh, wpb);
-            hipLaunchKernelGGL((k_resize_area_wide<CN>), dim3((unsigned)r.nblk, round_up8(count)), dim3(64 * wpb), (size_t)wpb * line_bytes, s, a, gm, w,
-                               line_bytes / 4, wpb, r.nstrips, bh, r.nitems, r.nblk, count);
+            hipLaunchKernelGGL((k_resize_area_wide<CN>), dim3((unsigned)r.nblk, round_up8(count)), dim3(64 * wpb), (size_t)wpb * line_bytes, s, a, gm,
+                               wide_nv(CN, w, cover), line_bytes / 4, wpb, r.nstrips, bh, r.nitems, r.nblk, count);
             return launched();
         }
     }
-    // everything else (gray frames, BGR rows that are not 4-byte aligned, cells wider than 66 columns): run tables,
-    // one output per lane
+    // everything else (cells wider than 66 columns): run tables, one output per lane
     TableSet ts;
     if (int rc = get_tables(interp, a.sw, a.sh, a.dw, a.dh, scale_x, scale_y, s, &ts)) return rc;
     hipLaunchKernelGGL((k_resize_area<CN>), grid, block, 0, s, a, ts.area);
@@ -3832,12 +3890,13 @@ int launch_cv_resize(const Frames& f, int interp, hipStream_t s) {
 // interpolation is the reference's (bridge.c:183-193) and the arithmetic is launch_cv_resize's.  classify_mixed names a
 // frame's class and fills its descriptor: frames that take the general AREA path (every non-integer shrink whose cells
 // span at most 20 source columns) are gathered into a k_resize_area_mix launch with their weights computed in the kernel,
-// colour frames whose cells span 21..66 columns (area_wide_plan: shrinks past 18x, up to 64x) into a
+// frames whose cells span 21..66 columns (area_wide_plan: shrinks past 18x, up to 64x; any channel count, pointer and
+// pitch -- aligned and off-grid BGR frames ride the same launch, the fetch mode travels in the descriptor) into a
 // k_resize_area_wide_mix launch, whole-factor AREA frames (any channel count) into a k_area_int_mix launch and NN frames
-// into a k_resize_nn_mix launch -- four launches at most, three for gray; a frame that is the only one of its class, and
-// the rest (enlargements; extreme ratios: cells past 20 columns for gray frames and BGR rows that are not 4-byte aligned,
-// past 66 for colour) go one launch each on the same stream.  Gray frames are gathered like colour ones: their general
-// AREA shrinks ride k_resize_area_mix<1> whatever their pointers and pitches are.
+// into a k_resize_nn_mix launch -- four launches at most per channel count; a frame that is the only one of its class,
+// and the rest (enlargements; extreme ratios: cells past 66 columns) go one launch each on the same stream.  Gray frames
+// are gathered like colour ones: their general AREA shrinks ride k_resize_area_mix<1> whatever their pointers and
+// pitches are.
 // Blocks differ a hundredfold in work (a 4K source against a 256-pixel one, same 224-wide output): each launch deals its
 // frames longest source first to the XCD list with the least source bytes so far (mix_launch), so each list starts with
 // its heavy frames and the launch's tail is made of light ones.
@@ -3907,7 +3966,8 @@ static int launch_wide_mix(std::vector<MixDesc>& v, int cn, int line_bytes, hipS
     const size_t lds = (size_t)wpb * line_bytes;
     return launch_by_source(v, s, [&](dim3 grid, const MixDesc* dev, const MixIndex& ix) {
         if (cn == 4) hipLaunchKernelGGL((k_resize_area_wide_mix<4>), grid, dim3(64 * wpb), lds, s, dev, ix, line_bytes / 4, wpb);
-        else hipLaunchKernelGGL((k_resize_area_wide_mix<3>), grid, dim3(64 * wpb), lds, s, dev, ix, line_bytes / 4, wpb);
+        else if (cn == 3) hipLaunchKernelGGL((k_resize_area_wide_mix<3>), grid, dim3(64 * wpb), lds, s, dev, ix, line_bytes / 4, wpb);
+        else hipLaunchKernelGGL((k_resize_area_wide_mix<1>), grid, dim3(64 * wpb), lds, s, dev, ix, line_bytes / 4, wpb);
     });
 }
 
@@ -3955,23 +4015,26 @@ static int classify_mixed(const MixFrame& f, int cn, int interp, int count, MixV
     d.a = rargs(f);
     d.gm = AreaGeom{scale_x, scale_y};
     if (cn == 1) {
-        // gray: any pointer, any pitch (the body aligns its own fetches); the window decides
+        // gray: any pointer, any pitch (the bodies align their own fetches); the window decides -- up to 20 columns here,
+        // past them area_wide_plan below
         int w1 = 0, p1 = 0, bh1 = 0;
-        if (!gray_rows_plan(f.sw, f.dw, f.dh, scale_x, count, &w1, &p1, &bh1)) return MIX_LONE;
-        d.nv = p1 == 4 ? -w1 : w1;
-        set_split(&d, row_split(f.dw, f.dh, 64 * p1, bh1));
-        return MIX_ROWS;
+        if (gray_rows_plan(f.sw, f.dw, f.dh, scale_x, count, &w1, &p1, &bh1)) {
+            d.nv = p1 == 4 ? -w1 : w1;
+            set_split(&d, row_split(f.dw, f.dh, 64 * p1, bh1));
+            return MIX_ROWS;
+        }
     }
     const bool aligned = !(((uintptr_t)f.src | (uintptr_t)f.sstep) & 3);
+    const bool streams = cn == 4 || (cn == 3 && aligned && f.sw >= 6);      // area_rows_body / area_rows4_body take the frame
     int w4 = 0, bh4 = 0;
-    if ((cn == 4 || (aligned && f.sw >= 6)) && f.dw >= 160 && area_rows_plan(f.sw, f.sh, f.dw, f.dh, scale_x, count, false, &w4, &bh4) &&
+    if (streams && f.dw >= 160 && area_rows_plan(f.sw, f.sh, f.dw, f.dh, scale_x, count, false, &w4, &bh4) &&
         w4 >= 2 && w4 <= 5 && 255 * scale_x + w4 + 8 <= (cn == 4 ? 1024 : 1340)) {
         // windows of at most five pixels (factors below ~3.9): four destination columns per lane, like the uniform batches
         d.nv = -w4;
         set_split(&d, row_split(f.dw, f.dh, 256, bh4));
         return MIX_ROWS;
     }
-    if ((cn == 4 || (aligned && f.sw >= 6)) && area_rows_plan(f.sw, f.sh, f.dw, f.dh, scale_x, count, true, &d.nv, &d.rows)) {
+    if (streams && area_rows_plan(f.sw, f.sh, f.dw, f.dh, scale_x, count, true, &d.nv, &d.rows)) {
         set_split(&d, row_split(f.dw, f.dh, 64, d.rows));
         return MIX_ROWS;
     }
@@ -3988,7 +4051,9 @@ static int classify_mixed(const MixFrame& f, int cn, int interp, int count, MixV
             return MIX_ROWS;
         }
     }
-    if (area_wide_plan(f.sw, f.sh, f.dw, f.dh, cn, interp, f.src, f.sstep, 0, count, &d.nv, &d.rows, &out->line_bytes)) {
+    bool cover = false;
+    if (area_wide_plan(f.sw, f.sh, f.dw, f.dh, cn, interp, f.src, f.sstep, 0, count, &d.nv, &d.rows, &out->line_bytes, &cover)) {
+        d.nv = wide_nv(cn, d.nv, cover);
         set_split(&d, row_split(f.dw, f.dh, 64, d.rows));
         return MIX_WIDE;
     }
@@ -4005,7 +4070,7 @@ int launch_resize_mixed(const MixFrame* fr, int count, int cn, int simple, hipSt
     }
     std::vector<IntMixDesc> whole_frames;                  // whole-factor AREA (resizeAreaFast_), any channel count
     std::vector<NnMixDesc> nn_frames;
-    std::vector<MixDesc> wide_frames;                      // colour, cells of 21..66 source columns (area_wide_plan)
+    std::vector<MixDesc> wide_frames;                      // cells of 21..66 source columns (area_wide_plan)
     std::vector<MixDesc> rows_frames;                      // general AREA, cells of at most 20 columns
     int wide_line = 0;                                     // the longest LDS line among the wide frames, in bytes
     int members[MIX_CLASSES] = {0, 0, 0, 0}, last[MIX_CLASSES] = {-1, -1, -1, -1};   // frames of a class, and the latest of them
