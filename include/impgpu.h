@@ -476,8 +476,10 @@ int impgpu_run_ops(impgpu_image** pointer, const impgpu_job* job, const impgpu_c
  * chain that has one -- a run of pointwise filters (with the watermark and the flatten when it is the last), a blur, or a
  * flip / turn -- one launch per kind and channel count, so the number of launches follows the chains' length, not the
  * number of requests.  Bare resizes with whole factors (resizeAreaFast_: 1280x720 or 1920x1080 at 320 wide) share one
- * launch per channel count too, and so do the NN resizes of `simple` requests.  Resizes launch_resize_mixed does not
- * gather (enlargements, extreme ratios: cells past 66 source columns) and blurs outside
+ * launch per channel count too, and so do the NN resizes of `simple` requests and the BGR / BGRA enlargements (CUBIC) -- at
+ * most five resize launches per channel count.  Resizes launch_resize_mixed does not gather (gray enlargements, frames of
+ * which one axis grows while y shrinks, enlargements whose x shrinks past 2x, extreme ratios: cells past 66 source
+ * columns) and blurs outside
  * the one-pass forms (large radii) still take a launch per request inside their round.  A single GRAY frame with a resize rides the same launches: its resize joins the gray
  * group of impgpu_batch_resize_mixed (channels = 1), ONE k_gray2bgr_mix launch then promotes every gray request of the call
  * (bridge.c:613-618, the filtering step -- entered for a gray frame even without filters; a request whose fault point fires
@@ -572,12 +574,19 @@ int impgpu_batch_cv_resize(const void* src, long long src_frame_stride, int src_
  * shrinks whose cells span at most 20 source columns (factors up to about 18), one for the shrinks past that
  * with cells of 21..66 columns (factors up to 64: a 4032-wide photo at 200 wide and below, a 600 dpi A4 scan at 150 wide;
  * any channel count, source pointer and pitch -- a BGR crop window may start at any column), one for the AREA shrinks
- * whose two factors are whole numbers, one for the NN frames -- at most four per channel count.  Gray general AREA
+ * whose two factors are whole numbers, one for the NN frames, one for the BGR / BGRA enlargements (CUBIC with y not
+ * shrinking, x shrinking by at most 2 and a source at least 4 columns wide; their coefficient tables travel with the
+ * launch and never enter the per-thread table cache; a launch whose tables would pass 4 MB is split) -- at most five
+ * per channel count.  In that launch a frame with a whole factor of 2, 3 or 4 runs the generic row loop, not the
+ * unrolled form it takes alone.  Timed against one launch per frame: 64 avatars of 64 sizes to 640
+ * wide 0.48 -> 0.10 ms, 1024 of them 35 -> 1.2 ms, 64 frames of 480x270 -> 1920x1080 0.58 -> 0.20 ms.  The built
+ * tables of an axis are kept in host memory per thread (16 MB at most), so sizes a worker has seen cost a copy.  Gray general AREA
  * shrinks are gathered whatever their source pointer, pitch and destination alignment are: a crop window of a
  * gray scan starts at any byte (launch counts are tested; the gray launch has not yet been timed against the per-frame
  * loop: DESIGN section 4).  A frame that is the only one of its kind in the call, and what no descriptor launch
- * gathers -- enlargements (CUBIC), extreme ratios (cells past 66 source columns, whatever the channel count) -- take
- * one launch each.  Same bytes
+ * gathers -- gray enlargements, frames of which one axis grows while y shrinks, enlargements whose x shrinks past 2x
+ * or whose source is narrower than 4 columns, extreme ratios (cells past 66 source columns, whatever the channel
+ * count) -- take one launch each.  Same bytes
  * as calling impgpu_batch_cv_resize once per item.  Nothing is launched if any item is malformed
  * (IMP_ERROR_INVALID_ARGS).  The _ex form also reports the number of kernels it enqueued in *launches (may be NULL). */
 typedef struct impgpu_resize_item {

@@ -406,15 +406,22 @@ constexpr size_t mix_blob_offset(size_t n) { return (n * sizeof(D) + 15) & ~size
 // behind it in the same allocation, at mix_blob_offset, when one is given -- let `launch(grid, table, ix)` issue the
 // kernel on `s` over the grid of 8 * most workgroups, and free the table behind the launch.  The table is freed even
 // when the launch failed, and the launch's error is the one reported: the rule every mixed launch shares, said here once.
+// `whole`, for blobs of megabytes (the enlargements' tables): the blob with mix_blob_offset<D>(v.size()) bytes left free
+// in front of it -- the table is written there and `whole` is what is uploaded, with no second host copy of the blob.
 template <class D, class M, class C, class L>
-int mix_launch(std::vector<D>& v, M desc, C cost, hipStream_t s, L launch, const std::vector<uint8_t>* blob = nullptr) {
+int mix_launch(std::vector<D>& v, M desc, C cost, hipStream_t s, L launch, const std::vector<uint8_t>* blob = nullptr,
+               std::vector<uint8_t>* whole = nullptr) {
     if (v.empty()) return IMP_OK;
     std::vector<D> sorted;
     MixIndex ix{};
     int most = 0;
     mix_deal(v, desc, cost, &sorted, &ix, &most);
     void* table = nullptr;
-    if (blob) {
+    if (whole) {
+        if (whole->size() < mix_blob_offset<D>(sorted.size())) return IMP_ERROR_INVALID_ARGS;
+        std::memcpy(whole->data(), sorted.data(), sorted.size() * sizeof(D));
+        if (int rc = upload_small(whole->data(), whole->size(), &table, s)) return rc;
+    } else if (blob) {
         const size_t dbytes = mix_blob_offset<D>(sorted.size());
         std::vector<uint8_t> both(dbytes + blob->size(), 0);
         std::memcpy(both.data(), sorted.data(), sorted.size() * sizeof(D));
@@ -431,8 +438,9 @@ int mix_launch(std::vector<D>& v, M desc, C cost, hipStream_t s, L launch, const
 }
 // the same for descriptors that hold `first` and `nblk` themselves
 template <class D, class C, class L>
-int mix_launch(std::vector<D>& v, C cost, hipStream_t s, L launch, const std::vector<uint8_t>* blob = nullptr) {
-    return mix_launch(v, [](D& d) -> D& { return d; }, cost, s, launch, blob);
+int mix_launch(std::vector<D>& v, C cost, hipStream_t s, L launch, const std::vector<uint8_t>* blob = nullptr,
+               std::vector<uint8_t>* whole = nullptr) {
+    return mix_launch(v, [](D& d) -> D& { return d; }, cost, s, launch, blob, whole);
 }
 // The descriptor of this workgroup (its index; -1: none, the workgroup returns) and the workgroup's index inside it;
 // `desc(d)` names the part of a descriptor holding `first` and `nblk`, as in mix_deal.  An index rather than a pointer: the

@@ -311,24 +311,38 @@ __device__ __forceinline__ uint32_t cvt_pk_u8(float x, uint32_t acc, int byte) {
 // per destination row, 32 bytes: how far the footprint moves before this row, then the four weights b * 2^-22
 struct UpRow { int adv; float bf[4]; int first; int pad[2]; };      // first = first footprint row (yofs - 1); adv = first - previous row's first
 
-template <int PS>     // PS = 2, 3, 4: scale_y is exactly 1/PS (host-checked: every PS-th row advances the footprint); 0: anything
-__global__ __launch_bounds__(256) void k_resize_up_cubic4(RArgs a, const int* __restrict__ xofs, const short* __restrict__ xco,
-                                                          const short* __restrict__ yco, const UpRow* __restrict__ rows,
-                                                          int vec_end, int nbx, int rows_per_wave) {
+// The body of one workgroup, shared by the lone kernel (k_resize_up_cubic4: launch arguments) and the mixed launch
+// (k_resize_up_cubic_mix<4>: a descriptor per frame).  `frame` = the frame of a uniform batch (a descriptor: 0, strides 0),
+// `blk` = the workgroup's index inside its frame; GLOBAL: the frame's pointers were read from memory (a descriptor), where
+// the compiler takes them for generic ones -- said to be global, the body's loads and stores are global_* as in the lone
+// kernels (a flat_store counts against the LDS counter too: the row loop would wait for its stores at every LDS read).
+// The LDS patches are declared HERE, not handed in: indexed through a pointer parameter the reads lose
+// their address space (see `fetch`); a kernel that calls the body owns one copy of each.
+template <bool GLOBAL, class T>
+__device__ __forceinline__ auto up_mem(T* p) {
+    if constexpr (GLOBAL) return (__attribute__((address_space(1))) T*)p;
+    else return p;
+}
+
+template <int PS, bool GLOBAL>     // PS = 2, 3, 4: scale_y is exactly 1/PS (host-checked: every PS-th row advances the footprint); 0: anything
+__device__ __forceinline__ void up_cubic4_body(const RArgs& a, unsigned frame, unsigned blk,
+                                               const int* __restrict__ xofs, const short* __restrict__ xco,
+                                               const short* __restrict__ yco, const UpRow* __restrict__ rows,
+                                               int vec_end, int nbx, int rows_per_wave) {
     // a wave's own 4 rows x 64 pixels, used only to turn four row-wise dword results per lane into one 16-byte store per lane
     __shared__ __attribute__((aligned(16))) uint32_t s_tr[4][4][64];
     __shared__ __attribute__((aligned(16))) uint32_t s_src[4][UP_CAP_PX];
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int cy = blockIdx.x / nbx, bx = blockIdx.x - cy * nbx;
+    const int cy = blk / nbx, bx = blk - cy * nbx;
     const int tx0 = (bx * 4 + wv) * 64;
     if (tx0 >= a.dw) return;                                   // waves are independent: no barrier follows
     const int txn = min(64, a.dw - tx0);
     const bool live = lane < txn;
     const int dx = tx0 + min(lane, txn - 1);                   // idle lanes of a partial strip shadow its last column
     const int row0 = cy * rows_per_wave, row_end = min(a.dh, row0 + rows_per_wave);
-    const uint8_t* S = a.src + (long long)blockIdx.y * a.src_stride;
-    uint8_t* D = a.dst + (long long)blockIdx.y * a.dst_stride;   // wave-uniform base; lanes add a 32-bit offset
+    const auto* S = up_mem<GLOBAL>(a.src) + (long long)frame * a.src_stride;
+    auto* D = up_mem<GLOBAL>(a.dst) + (long long)frame * a.dst_stride;        // wave-uniform base; lanes add a 32-bit offset
 
     short2_t axp[2];
     axp[0].x = xco[dx * 4]; axp[0].y = xco[dx * 4 + 1]; axp[1].x = xco[dx * 4 + 2]; axp[1].y = xco[dx * 4 + 3];
@@ -439,7 +453,7 @@ __global__ __launch_bounds__(256) void k_resize_up_cubic4(RArgs a, const int* __
             const size_t group_bytes = (size_t)a.dstep * 4;
             for (; dy + 4 * PS <= row_end; dy += 4 * PS) {
                 const UpRow* rq = rows + dy;
-                uint8_t* Dg = D + (size_t)dy * a.dstep;
+                auto* Dg = D + (size_t)dy * a.dstep;
 #pragma unroll
                 for (int r = 0; r < 4 * PS; r++) {
                     const UpRow rc = rq[r];
@@ -462,7 +476,7 @@ __global__ __launch_bounds__(256) void k_resize_up_cubic4(RArgs a, const int* __
         const UpRow* rq = rows + row0;
         UpRow rc = *rq;
         rc.adv = 0;                                            // the first row's footprint is already in place
-        uint8_t* Dg = D + (size_t)dy * a.dstep;
+        auto* Dg = D + (size_t)dy * a.dstep;
         const size_t group_bytes = (size_t)a.dstep * 4;
         for (; dy + 4 <= row_end; dy += 4, Dg += group_bytes) {
 #pragma unroll
@@ -485,6 +499,13 @@ __global__ __launch_bounds__(256) void k_resize_up_cubic4(RArgs a, const int* __
     for (; dy < row_end; dy++) slow_row(dy);
 }
 
+template <int PS>     // see up_cubic4_body
+__global__ __launch_bounds__(256) void k_resize_up_cubic4(RArgs a, const int* __restrict__ xofs, const short* __restrict__ xco,
+                                                          const short* __restrict__ yco, const UpRow* __restrict__ rows,
+                                                          int vec_end, int nbx, int rows_per_wave) {
+    up_cubic4_body<PS, false>(a, blockIdx.y, blockIdx.x, xofs, xco, yco, rows, vec_end, nbx, rows_per_wave);
+}
+
 // The same for 3-channel frames -- what cvDecodeImage hands Resize() for every JPEG, so every JPEG enlargement
 // (k_resize_taps<4,3> re-did the whole 4 x 4 footprint per output pixel: 0.056 of the roofline).  Differences from the
 // BGRA kernel: the LDS patch holds the strip's source bytes (3 per pixel, rows padded to dwords); a lane's window is the
@@ -497,23 +518,24 @@ __device__ __forceinline__ void hpass_bgr(const uint32_t* w, const short2_t* axp
 
 #define UP_CAP3_BYTES 6144   // bytes of source a wave stages in LDS
 
-template <int PS>     // see k_resize_up_cubic4
-__global__ __launch_bounds__(256) void k_resize_up_cubic3(RArgs a, const int* __restrict__ xofs, const short* __restrict__ xco,
-                                                          const short* __restrict__ yco, const UpRow* __restrict__ rows,
-                                                          int vec_end, int nbx, int rows_per_wave) {
+template <int PS, bool GLOBAL>     // see up_cubic4_body, also for the parameters
+__device__ __forceinline__ void up_cubic3_body(const RArgs& a, unsigned frame, unsigned blk,
+                                               const int* __restrict__ xofs, const short* __restrict__ xco,
+                                               const short* __restrict__ yco, const UpRow* __restrict__ rows,
+                                               int vec_end, int nbx, int rows_per_wave) {
     __shared__ __attribute__((aligned(16))) uint8_t s_tr[4][4 * 192];
     __shared__ __attribute__((aligned(16))) uint8_t s_src[4][UP_CAP3_BYTES];
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int cy = blockIdx.x / nbx, bx = blockIdx.x - cy * nbx;
+    const int cy = blk / nbx, bx = blk - cy * nbx;
     const int tx0 = (bx * 4 + wv) * 64;
     if (tx0 >= a.dw) return;                                   // waves are independent: no barrier follows
     const int txn = min(64, a.dw - tx0);
     const bool live = lane < txn;
     const int dx = tx0 + min(lane, txn - 1);                   // idle lanes of a partial strip shadow its last column
     const int row0 = cy * rows_per_wave, row_end = min(a.dh, row0 + rows_per_wave);
-    const uint8_t* S = a.src + (long long)blockIdx.y * a.src_stride;
-    uint8_t* D = a.dst + (long long)blockIdx.y * a.dst_stride;
+    const auto* S = up_mem<GLOBAL>(a.src) + (long long)frame * a.src_stride;
+    auto* D = up_mem<GLOBAL>(a.dst) + (long long)frame * a.dst_stride;
 
     short2_t axp[2];
     axp[0].x = xco[dx * 4]; axp[0].y = xco[dx * 4 + 1]; axp[1].x = xco[dx * 4 + 2]; axp[1].y = xco[dx * 4 + 3];
@@ -526,7 +548,7 @@ __global__ __launch_bounds__(256) void k_resize_up_cubic3(RArgs a, const int* __
     if (NR * WB > UP_CAP3_BYTES) return;   // cannot happen: the launcher sizes chunks from the same bounds; keeps LDS sound
     for (int i = lane; i < NR * W; i += 64) {                  // border replication happens here, once: clamped row / column
         const int r = i / W, c = i - r * W;
-        const uint8_t* q = S + (size_t)clampi(f0 + r, 0, a.sh - 1) * a.sstep + (size_t)clampi(sxmin + c, 0, a.sw - 1) * 3;
+        const auto* q = S + (size_t)clampi(f0 + r, 0, a.sh - 1) * a.sstep + (size_t)clampi(sxmin + c, 0, a.sw - 1) * 3;
         uint8_t* o = &s_src[wv][r * WB + c * 3];
         o[0] = q[0]; o[1] = q[1]; o[2] = q[2];
     }
@@ -591,7 +613,7 @@ __global__ __launch_bounds__(256) void k_resize_up_cubic3(RArgs a, const int* __
                 }
         }
         if (live) {
-            uint8_t* o = D + (size_t)y * a.dstep + (size_t)dx * 3;
+            auto* o = D + (size_t)y * a.dstep + (size_t)dx * 3;
             o[0] = (uint8_t)px; o[1] = (uint8_t)(px >> 8); o[2] = (uint8_t)(px >> 16);
         }
     };
@@ -611,7 +633,7 @@ __global__ __launch_bounds__(256) void k_resize_up_cubic3(RArgs a, const int* __
             }
             for (; dy + 4 * PS <= row_end; dy += 4 * PS) {
                 const UpRow* rq = rows + dy;
-                uint8_t* Dg = D + (size_t)dy * a.dstep + (size_t)tx0 * 3;
+                auto* Dg = D + (size_t)dy * a.dstep + (size_t)tx0 * 3;
 #pragma unroll
                 for (int r = 0; r < 4 * PS; r++) {
                     const UpRow rc = rq[r];
@@ -636,7 +658,7 @@ __global__ __launch_bounds__(256) void k_resize_up_cubic3(RArgs a, const int* __
         const UpRow* rq = rows + row0;
         UpRow rc = *rq;
         rc.adv = 0;
-        uint8_t* Dg = D + (size_t)dy * a.dstep + (size_t)tx0 * 3;
+        auto* Dg = D + (size_t)dy * a.dstep + (size_t)tx0 * 3;
         const size_t group_bytes = (size_t)a.dstep * 4;
         // the 4 x 48 dwords of a group go out as three dword stores per lane: dword n = lane + 64 j -> row n / 48, column n % 48
         unsigned voff[3];
@@ -665,6 +687,42 @@ __global__ __launch_bounds__(256) void k_resize_up_cubic3(RArgs a, const int* __
     }
 
     for (; dy < row_end; dy++) slow_row(dy);                   // partial strips, unaligned destinations, a chunk's last rows
+}
+
+template <int PS>     // see up_cubic4_body
+__global__ __launch_bounds__(256) void k_resize_up_cubic3(RArgs a, const int* __restrict__ xofs, const short* __restrict__ xco,
+                                                          const short* __restrict__ yco, const UpRow* __restrict__ rows,
+                                                          int vec_end, int nbx, int rows_per_wave) {
+    up_cubic3_body<PS, false>(a, blockIdx.y, blockIdx.x, xofs, xco, yco, rows, vec_end, nbx, rows_per_wave);
+}
+
+// Enlargements of DIFFERENT geometry in one launch (launch_resize_mixed's MIX_UP class): the descriptor scheme of
+// k_resize_area_mix around the two bodies above, so the bytes are the lone launch's.  A descriptor is one frame: its views,
+// where its four tables lie in the blob that travels behind the descriptor table (byte offsets from `blob`; `rows` -- the
+// UpRow array with its sentinel -- at a 32-byte multiple of the allocation, read as 32-byte scalar rows), and the lone
+// kernels' three launch arguments.  The workgroup's index inside its descriptor is the lone kernels' blockIdx.x:
+// nblk = nbx * (chunks of rows_per_wave rows).  Only the generic footprint advance is carried (PS = 0): a frame with a
+// whole factor, which alone runs the unrolled PS form, pays the ring's register moves here -- 8 % of the instructions at
+// 4x, 16 % at 2x -- for one kernel instead of four in the launch.  Same registers and LDS as the lone <0> kernels; the
+// descriptor's fields arrive by scalar loads (d[di]: block-uniform) where the lone kernels read launch arguments.
+struct alignas(32) UpMixDesc { RArgs a; unsigned xofs, xco, yco, rows; int vec_end, nbx, rows_per_wave, first, nblk; };
+static_assert(sizeof(UpMixDesc) % 32 == 0, "the blob behind n descriptors starts at a 32-byte multiple (UpRow rows)");
+
+template <int CN>
+__global__ __launch_bounds__(256) void k_resize_up_cubic_mix(const UpMixDesc* __restrict__ d, MixIndex ix, const uint8_t* __restrict__ blob) {
+    static_assert(CN == 3 || CN == 4, "BGR and BGRA");
+    int blk;
+    const int di = mix_pick(d, ix, &blk);
+    if (di < 0) return;
+    const UpMixDesc& m = d[di];
+    RArgs a = m.a;
+    a.src_stride = a.dst_stride = 0;                   // a descriptor is one frame: the fast path's alignment test is its pointer and pitch
+    const int* xofs = (const int*)(blob + m.xofs);
+    const short* xco = (const short*)(blob + m.xco);
+    const short* yco = (const short*)(blob + m.yco);
+    const UpRow* rows = (const UpRow*)(blob + m.rows);
+    if constexpr (CN == 4) up_cubic4_body<0, true>(a, 0u, (unsigned)blk, xofs, xco, yco, rows, m.vec_end, m.nbx, m.rows_per_wave);
+    else up_cubic3_body<0, true>(a, 0u, (unsigned)blk, xofs, xco, yco, rows, m.vec_end, m.nbx, m.rows_per_wave);
 }
 
 // vertical pass over the register ring at phase U of its period; returns the packed BGRA destination pixel
@@ -3101,6 +3159,33 @@ static int table_use(TableEntry& e, hipStream_t s) {     // order `s` behind the
     return stream_join(s);
 }
 
+// The CUBIC enlargement kernels' row constants from the vertical axis of a geometry: an UpRow per destination row and a
+// sentinel the kernels' one-row look-ahead may read.  *period = P when exactly every P-th row (P = 2, 3, 4) advances the
+// footprint, else 0 (null: not asked for -- the walks over the axis that find it are skipped).  The one place they are made: get_tables (the lone launches, cached) and launch_up_mix (the mixed
+// launch, whose tables travel with it) both call it.
+static std::vector<UpRow> up_rows(const TapAxis& ty, int dh, int* period) {
+    std::vector<UpRow> yr((size_t)dh + 1);
+    for (int d = 0; d < dh; d++) {
+        yr[d].first = ty.ofs[d] - 1;
+        yr[d].adv = d ? ty.ofs[d] - ty.ofs[d - 1] : 0;
+        for (int k = 0; k < 4; k++)     // the constants of VResizeCubicVec_32s8u's multiplies: one IEEE multiply each
+            yr[d].bf[k] = (float)ty.coef[(size_t)d * 4 + k] * (1.f / (2048.f * 2048.f));
+        yr[d].pad[0] = yr[d].pad[1] = 0;
+    }
+    yr[dh] = yr[dh - 1];
+    yr[dh].adv = 0;
+    if (!period) return yr;
+    *period = 0;
+    for (int per = 2; per <= 4 && !*period; per++) {   // rows p, p + per, p + 2 per ... advance by one, the others not at all
+        int p0 = 1;
+        while (p0 < dh && yr[p0].adv == 0) p0++;
+        bool ok = p0 < dh;
+        for (int d = 1; d < dh && ok; d++) ok = yr[d].adv == ((d >= p0 && (d - p0) % per == 0) ? 1 : 0);
+        if (ok) *period = per;
+    }
+    return yr;
+}
+
 static int get_tables(int interp, int sw, int sh, int dw, int dh, double scale_x, double scale_y, hipStream_t s, TableSet* out) {
     LaneCache** slot = lane_cache_slot(0);
     if (!slot) { set_error("impgpu_env_start has not been called", hipErrorNotInitialized); return IMP_ERROR_DEVICE; }
@@ -3138,23 +3223,7 @@ static int get_tables(int interp, int sw, int sh, int dw, int dh, double scale_x
         build_tap_axis(sh, dh, scale_y, interp, false, &ty);
         o[0] = put(blob, tx.ofs); o[1] = put(blob, tx.coef); o[2] = put(blob, ty.ofs); o[3] = put(blob, ty.coef);
         if (interp == IMP_INTER_CUBIC) {
-            std::vector<UpRow> yr((size_t)dh + 1);          // + a sentinel the kernel's one-row look-ahead may read
-            for (int d = 0; d < dh; d++) {
-                yr[d].first = ty.ofs[d] - 1;
-                yr[d].adv = d ? ty.ofs[d] - ty.ofs[d - 1] : 0;
-                for (int k = 0; k < 4; k++)     // the constants of VResizeCubicVec_32s8u's multiplies: one IEEE multiply each
-                    yr[d].bf[k] = (float)ty.coef[(size_t)d * 4 + k] * (1.f / (2048.f * 2048.f));
-                yr[d].pad[0] = yr[d].pad[1] = 0;
-            }
-            yr[dh] = yr[dh - 1];
-            yr[dh].adv = 0;
-            for (int per = 2; per <= 4 && !ts.up_period; per++) {   // rows p, p + per, p + 2 per ... advance by one, the others not at all
-                int p0 = 1;
-                while (p0 < dh && yr[p0].adv == 0) p0++;
-                bool ok = p0 < dh;
-                for (int d = 1; d < dh && ok; d++) ok = yr[d].adv == ((d >= p0 && (d - p0) % per == 0) ? 1 : 0);
-                if (ok) ts.up_period = per;
-            }
+            const std::vector<UpRow> yr = up_rows(ty, dh, &ts.up_period);
             while (blob.size() % 32) blob.push_back(0);
             o[4] = put(blob, yr);
         }
@@ -3512,13 +3581,33 @@ static void launch_2x_bgra(const RArgs& a, int count, int interp, const TableSet
         hipLaunchKernelGGL((k_resize_2x_roll<8, M_LANCZOS>), rgrid, block, 0, s, a, ts.xofs, ts.xco, ts.yofs, ts.yco, 0);
 }
 
+// Does the frame take the CUBIC enlargement kernels (k_resize_up_cubic3 / 4, alone or in a mixed launch)?  The one test:
+// launch_tapped and classify_mixed both ask it.  y must not shrink (the footprint advances by at most one row per
+// destination row), x may shrink up to 2x (a strip's source columns fit the LDS patch), and the kernels index a frame's
+// destination bytes in 32 bits.
+static bool up_cubic_takes(int cn, int interp, double scale_x, double scale_y, int sw, int dh, int dstep) {
+    return (cn == 3 || cn == 4) && interp == IMP_INTER_CUBIC && scale_y <= 1.0 && scale_x <= 2.0 && sw >= 4 &&
+           (long long)dh * dstep < (1LL << 32);
+}
+
+// Rows per wave chunk of the CUBIC enlargement kernels: as many as keep the chunk's source footprint (strip columns x
+// footprint rows, from the bound floor(n * scale) + 1 on how far n + 1 sample positions spread, + 3 taps + 1) inside the
+// wave's LDS patch, at most UP_ROWS -- mandatory, per frame; fewer when `frames` frames like this one would not fill the
+// chip otherwise (a lone launch: its frame count; a mixed launch: the frames of the call).
+static int up_rows_per_wave(int cn, int dw, int dh, double scale_x, double scale_y, long long frames) {
+    const int nbx = (dw + 255) / 256;                   // four 64-column strips per block, one per wave
+    const int wmax = (int)std::floor(63 * scale_x) + 6;
+    const int pitch = cn == 3 ? ((wmax * 3 + 3) & ~3) + 4 : wmax, cap = cn == 3 ? UP_CAP3_BYTES : UP_CAP_PX;
+    int rpw = UP_ROWS;
+    while (rpw > 4 && ((int)std::floor((rpw - 1) * scale_y) + 6) * pitch > cap) rpw -= 4;
+    while (rpw > 16 && (long long)nbx * 4 * ((dh + rpw - 1) / rpw) * frames < 8192) rpw -= rpw > 64 ? 64 : 16;
+    return rpw;
+}
+
 // enlargement of a 3-channel frame (every JPEG): the BGRA kernel's structure on bytes
 static void launch_up_cubic_bgr(const RArgs& a, int count, double scale_x, double scale_y, const TableSet& ts, hipStream_t s) {
     const int nbx = (a.dw + 255) / 256;
-    const int wbmax = ((((int)std::floor(63 * scale_x) + 6) * 3 + 3) & ~3) + 4;
-    int rpw = UP_ROWS;
-    while (rpw > 4 && ((int)std::floor((rpw - 1) * scale_y) + 6) * wbmax > UP_CAP3_BYTES) rpw -= 4;
-    while (rpw > 16 && (long long)nbx * 4 * ((a.dh + rpw - 1) / rpw) * count < 8192) rpw -= rpw > 64 ? 64 : 16;
+    const int rpw = up_rows_per_wave(3, a.dw, a.dh, scale_x, scale_y, count);
     const int ncy = (a.dh + rpw - 1) / rpw;
     with_const<1, 4>(ts.up_period, [&](auto K) {             // (see launch_up_cubic_bgra)
         constexpr int PS = K() == 1 ? 0 : K();
@@ -3530,13 +3619,7 @@ static void launch_up_cubic_bgr(const RArgs& a, int count, double scale_x, doubl
 // enlargement (bridge.c:190's CUBIC case): wave-private strips, float H sums in a register ring
 static void launch_up_cubic_bgra(const RArgs& a, int count, double scale_x, double scale_y, const TableSet& ts, hipStream_t s) {
     const int nbx = (a.dw + 255) / 256;                 // four 64-column strips per block, one per wave
-    // rows per wave chunk: as many as keep the chunk's source footprint (strip columns x footprint rows, from the
-    // bound floor(n * scale) + 1 on how far n + 1 sample positions spread, + 3 taps + 1) inside the wave's LDS
-    // patch, at most UP_ROWS; fewer when there are too few frames to fill the chip otherwise
-    const int wmax = (int)std::floor(63 * scale_x) + 6;
-    int rpw = UP_ROWS;
-    while (rpw > 4 && ((int)std::floor((rpw - 1) * scale_y) + 6) * wmax > UP_CAP_PX) rpw -= 4;
-    while (rpw > 16 && (long long)nbx * 4 * ((a.dh + rpw - 1) / rpw) * count < 8192) rpw -= rpw > 64 ? 64 : 16;
+    const int rpw = up_rows_per_wave(4, a.dw, a.dh, scale_x, scale_y, count);
     const int ncy = (a.dh + rpw - 1) / rpw;
     const dim3 ugrid((unsigned)(nbx * ncy), (unsigned)count);
     with_const<1, 4>(ts.up_period, [&](auto K) {             // 2, 3, 4 when every per-th row (and no other) advances the footprint; else 0
@@ -3600,10 +3683,8 @@ static int launch_tapped(const RArgs& a, int count, int interp, double scale_x, 
     // both scales <= 2: neighbouring outputs share taps -> LDS-tiled separable kernel (BGRA)
     if (CN == 3 && ts.step2 && a.sw >= 8 && interp != IMP_INTER_LINEAR) launch_2x_bgr(a, count, interp, ts, s);
     else if (CN == 4 && ts.step2 && a.sw >= 8) launch_2x_bgra(a, count, interp, ts, s);
-    else if (CN == 3 && interp == IMP_INTER_CUBIC && scale_y <= 1.0 && scale_x <= 2.0 && a.sw >= 4 &&
-             (long long)a.dh * a.dstep < (1LL << 32)) launch_up_cubic_bgr(a, count, scale_x, scale_y, ts, s);
-    else if (CN == 4 && interp == IMP_INTER_CUBIC && scale_y <= 1.0 && scale_x <= 2.0 && a.sw >= 4 &&
-             (long long)a.dh * a.dstep < (1LL << 32)) launch_up_cubic_bgra(a, count, scale_x, scale_y, ts, s);
+    else if (CN == 3 && up_cubic_takes(CN, interp, scale_x, scale_y, a.sw, a.dh, a.dstep)) launch_up_cubic_bgr(a, count, scale_x, scale_y, ts, s);
+    else if (CN == 4 && up_cubic_takes(CN, interp, scale_x, scale_y, a.sw, a.dh, a.dstep)) launch_up_cubic_bgra(a, count, scale_x, scale_y, ts, s);
     else if ((CN == 4 || CN == 3) && scale_x <= 2.0 && scale_y <= 2.0 && a.sw >= 8 &&
              (CN == 4 || !(((uintptr_t)a.src | (uintptr_t)a.sstep | (uintptr_t)a.src_stride) & 3))) launch_strips<CN>(a, count, interp, ts, s);
     else launch_taps<CN>(a, interp, ts, grid, s);
@@ -3893,10 +3974,12 @@ int launch_cv_resize(const Frames& f, int interp, hipStream_t s) {
 // frames whose cells span 21..66 columns (area_wide_plan: shrinks past 18x, up to 64x; any channel count, pointer and
 // pitch -- aligned and off-grid BGR frames ride the same launch, the fetch mode travels in the descriptor) into a
 // k_resize_area_wide_mix launch, whole-factor AREA frames (any channel count) into a k_area_int_mix launch and NN frames
-// into a k_resize_nn_mix launch -- four launches at most per channel count; a frame that is the only one of its class,
-// and the rest (enlargements; extreme ratios: cells past 66 columns) go one launch each on the same stream.  Gray frames
-// are gathered like colour ones: their general AREA shrinks ride k_resize_area_mix<1> whatever their pointers and
-// pitches are.
+// into a k_resize_nn_mix launch, and BGR / BGRA enlargements (CUBIC, neither axis shrinking in y: up_cubic_takes) into a
+// k_resize_up_cubic_mix launch that carries their tables -- five launches at most per channel count (an enlargement
+// launch splits when its tables pass UP_MIX_BLOB_BYTES); a frame that is the only one of its class, and the rest (gray
+// enlargements, frames of which one axis grows while y shrinks, enlargements whose x shrinks past 2x; extreme ratios:
+// cells past 66 columns) go one launch each on the same stream.  Gray frames are gathered like colour ones: their
+// general AREA shrinks ride k_resize_area_mix<1> whatever their pointers and pitches are.
 // Blocks differ a hundredfold in work (a 4K source against a 256-pixel one, same 224-wide output): each launch deals its
 // frames longest source first to the XCD list with the least source bytes so far (mix_launch), so each list starts with
 // its heavy frames and the launch's tail is made of light ones.
@@ -3971,6 +4054,116 @@ static int launch_wide_mix(std::vector<MixDesc>& v, int cn, int line_bytes, hipS
     });
 }
 
+// Enlargements up_cubic_takes accepts, two or more.  Their tables TRAVEL WITH THE LAUNCH, in the blob behind the descriptor
+// table, and are freed with it: nothing is put into, looked up in or evicted from the lane's TableCache, so a mixed stream
+// of never-seen sizes costs no cache slot and no pool block per frame.  They are built exactly as get_tables builds them
+// (build_tap_axis, up_rows; the built bytes of an axis are kept on the host: UpAxisMemo).  Within a launch frames share
+// axes: one x table per (sw, dw), one y table per (sh, dh) -- a queue of same-size avatars uploads its tables once.
+// UP_MIX_BLOB_BYTES bounds what one launch uploads, descriptors and tables together (a call holds up to 4096 requests and
+// a 1080p destination's tables weigh 66 KB): when the next frame's tables would pass it, the frames gathered so far are
+// launched and another launch begins.  Uploads past a ring segment (128 KB) go through the lane's staging buffers
+// (upload_to), which start at 8 MB and wait for the device when they have to grow: half of that keeps every launch's
+// upload inside a buffer that never regrows.  The launch's bytes are laid out before anything is built (a table's size
+// follows from its axis), so every axis image is copied once into its place behind the space left for the descriptors and
+// the whole leaves the host through one copy (mix_launch's `whole`).  A single frame whose own tables pass the bound (destinations past ~250 000 rows + columns) still goes, alone in its launch.
+constexpr size_t UP_MIX_BLOB_BYTES = size_t(4) << 20;
+
+// One axis of an enlargement as the bytes the mix kernel reads, in one piece: x -> xofs, then xco; y -> the UpRow rows
+// (with their sentinel), then yco; every part a multiple of 16 bytes, the rows first so that a y image placed at a 32-byte
+// multiple has them there.  Building one (build_tap_axis, up_rows: the float arithmetic of ~400 rows) is ~10 us, which for a
+// call of a few dozen avatars was more than the launches it saved; a worker sees the same sizes again and again, so the
+// images are kept per lane, HOST memory only (dropped with the lane; nothing on the device outlives a launch).  Bounded
+// by UP_MEMO_BYTES: past it everything is dropped and the memo starts over -- a miss costs one build, as before.
+constexpr size_t UP_MEMO_BYTES = size_t(16) << 20;
+struct UpAxisMemo : LaneCache {
+    std::map<std::tuple<int, int, bool>, std::vector<uint8_t>> m;
+    size_t bytes = 0;
+};
+constexpr size_t up16(size_t n) { return (n + 15) & ~size_t(15); }
+static size_t up_axis_bytes(int dsize, bool is_x) {
+    return is_x ? up16((size_t)dsize * sizeof(int)) + up16((size_t)dsize * 4 * sizeof(short))
+                : ((size_t)dsize + 1) * sizeof(UpRow) + up16((size_t)dsize * 4 * sizeof(short));
+}
+static void up_axis_build(int ssize, int dsize, bool is_x, std::vector<uint8_t>* out) {
+    TapAxis ta;
+    build_tap_axis(ssize, dsize, 1. / ((double)dsize / ssize), IMP_INTER_CUBIC, is_x, &ta);
+    out->assign(up_axis_bytes(dsize, is_x), 0);
+    if (is_x) {
+        std::memcpy(out->data(), ta.ofs.data(), ta.ofs.size() * sizeof(int));
+        std::memcpy(out->data() + up16((size_t)dsize * sizeof(int)), ta.coef.data(), ta.coef.size() * sizeof(short));
+    } else {
+        const std::vector<UpRow> yr = up_rows(ta, dsize, nullptr);     // (the mix kernel carries the generic advance only)
+        std::memcpy(out->data(), yr.data(), yr.size() * sizeof(UpRow));
+        std::memcpy(out->data() + yr.size() * sizeof(UpRow), ta.coef.data(), ta.coef.size() * sizeof(short));
+    }
+}
+// copies the axis' image to `dst` (up_axis_bytes of it)
+static void up_axis_put(int ssize, int dsize, bool is_x, uint8_t* dst) {
+    LaneCache** slot = lane_cache_slot(1);
+    if (!slot) {                                           // no lane: the upload will say so; build and forget
+        std::vector<uint8_t> once;
+        up_axis_build(ssize, dsize, is_x, &once);
+        std::memcpy(dst, once.data(), once.size());
+        return;
+    }
+    if (!*slot) *slot = new UpAxisMemo();
+    UpAxisMemo& M = *static_cast<UpAxisMemo*>(*slot);
+    auto it = M.m.find({ssize, dsize, is_x});
+    if (it == M.m.end()) {
+        const size_t n = up_axis_bytes(dsize, is_x);
+        if (M.bytes + n > UP_MEMO_BYTES) { M.m.clear(); M.bytes = 0; }
+        it = M.m.emplace(std::make_tuple(ssize, dsize, is_x), std::vector<uint8_t>()).first;
+        up_axis_build(ssize, dsize, is_x, &it->second);
+        M.bytes += n;
+    }
+    std::memcpy(dst, it->second.data(), it->second.size());
+}
+
+static int launch_up_mix(const std::vector<UpMixDesc>& frames, int cn, hipStream_t s) {
+    size_t next = 0;
+    while (next < frames.size()) {
+        // the frames of this launch and where their axes will lie (sizes follow from the geometry: nothing is built yet)
+        std::map<std::pair<int, int>, unsigned> xs, ys;    // (ssize, dsize) -> byte offset of the axis' image in the launch's tables
+        std::vector<UpMixDesc> v;
+        size_t tables = 0;
+        for (; next < frames.size(); next++) {
+            UpMixDesc d = frames[next];
+            const std::pair<int, int> kx{d.a.sw, d.a.dw}, ky{d.a.sh, d.a.dh};
+            auto ix = xs.find(kx), iy = ys.find(ky);
+            size_t t = tables, xat = 0, yat = 0;
+            if (ix == xs.end()) { xat = t; t += up_axis_bytes(d.a.dw, true); }
+            if (iy == ys.end()) {
+                t = (t + 31) & ~size_t(31);                // UpRow rows are read as 32-byte scalar rows (sizeof(UpMixDesc) % 32 == 0)
+                yat = t;
+                t += up_axis_bytes(d.a.dh, false);
+            }
+            if (!v.empty() && (v.size() + 1) * sizeof(UpMixDesc) + t > UP_MIX_BLOB_BYTES) break;
+            if (ix == xs.end()) ix = xs.emplace(kx, (unsigned)xat).first;
+            if (iy == ys.end()) iy = ys.emplace(ky, (unsigned)yat).first;
+            tables = t;
+            d.xofs = ix->second;
+            d.xco = ix->second + (unsigned)up16((size_t)d.a.dw * sizeof(int));
+            d.rows = iy->second;
+            d.yco = iy->second + (unsigned)(((size_t)d.a.dh + 1) * sizeof(UpRow));
+            v.push_back(d);
+        }
+        // descriptors in front (mix_launch writes them), every distinct axis once, straight into its place
+        const size_t dbytes = mix_blob_offset<UpMixDesc>(v.size());
+        std::vector<uint8_t> whole(dbytes + tables, 0);
+        uint8_t* t = whole.data() + dbytes;
+        for (const auto& x : xs) up_axis_put(x.first.first, x.first.second, true, t + x.second);
+        for (const auto& y : ys) up_axis_put(y.first.first, y.first.second, false, t + y.second);
+        const int rc = mix_launch(v, [](UpMixDesc& d) { return (long long)d.a.dw * d.a.dh; }, s,      // store- and VALU-bound: destination pixels
+                                  [&](dim3 grid, const UpMixDesc* dev, const MixIndex& mi) {
+            const uint8_t* dev_tables = (const uint8_t*)dev + dbytes;
+            if (cn == 4) hipLaunchKernelGGL((k_resize_up_cubic_mix<4>), grid, dim3(256), 0, s, dev, mi, dev_tables);
+            else hipLaunchKernelGGL((k_resize_up_cubic_mix<3>), grid, dim3(256), 0, s, dev, mi, dev_tables);
+        }, nullptr, &whole);
+        if (rc) return rc;
+    }
+    return IMP_OK;
+}
+
 // one frame of a mix through launch_cv_resize
 static int launch_lone(const MixFrame& f, int cn, int interp, hipStream_t s) {
     Frames one{};
@@ -3982,8 +4175,8 @@ static int launch_lone(const MixFrame& f, int cn, int interp, hipStream_t s) {
 static void set_split(MixDesc* d, const RowSplit& r) { d->rows = r.bh; d->nstrips = r.nstrips; d->nitems = r.nitems; d->nblk = r.nblk; }
 
 // The classes of a mixed launch, in the order they are launched, and the descriptor of a frame: the member its class names.
-enum { MIX_LONE = -1, MIX_WHOLE = 0, MIX_NN, MIX_WIDE, MIX_ROWS, MIX_CLASSES };
-struct MixVerdict { MixDesc m; IntMixDesc whole; NnMixDesc nn; int line_bytes; };
+enum { MIX_LONE = -1, MIX_WHOLE = 0, MIX_NN, MIX_WIDE, MIX_ROWS, MIX_UP, MIX_CLASSES };
+struct MixVerdict { MixDesc m; IntMixDesc whole; NnMixDesc nn; UpMixDesc up; int line_bytes; };
 
 // The class of one frame of a mix of `count`, and its descriptor.  The rules are launch_cn's, except where a mix differs on
 // purpose:
@@ -3991,7 +4184,12 @@ struct MixVerdict { MixDesc m; IntMixDesc whole; NnMixDesc nn; int line_bytes; }
 //  - the mix carries the even windows only (`even` of area_rows_plan): half the instances in one kernel;
 //  - BGR rows that are not 4-byte aligned pick AREA_ROWS by `big` (blocks in the launch) alone and by `scale_y < 8` in a mix;
 //  - the three whole-factor exceptions above int_mix_desc;
-//  - a wide frame's `nblk` waits for launch_wide_mix: it follows the launch's longest line, known only once every frame is in.
+//  - a wide frame's `nblk` waits for launch_wide_mix: it follows the launch's longest line, known only once every frame is in;
+//  - an enlargement (MIX_UP: exactly the frames launch_tapped sends to the CUBIC enlargement kernels, up_cubic_takes) runs
+//    the generic footprint advance whatever its factor, and its table offsets wait for launch_up_mix, which builds the tables.
+//    Its rows per wave are the lone launch's: the LDS bound per frame, the chip-fill reduction over the `count` frames of the call.
+// MIX_LONE is what no descriptor launch takes: gray enlargements, frames of which one axis grows while y shrinks (the strip
+// kernels), x shrinking past 2x beside a growing y, sources narrower than 4 columns, AREA cells past 66 columns.
 static int classify_mixed(const MixFrame& f, int cn, int interp, int count, MixVerdict* out) {
     const double scale_x = 1. / ((double)f.dw / f.sw), scale_y = 1. / ((double)f.dh / f.sh);
     const bool whole = whole_factors(scale_x, scale_y);
@@ -4009,6 +4207,15 @@ static int classify_mixed(const MixFrame& f, int cn, int interp, int count, MixV
             out->whole = int_mix_desc(f, cn, isx, isy);
             return MIX_WHOLE;
         }
+    }
+    if (up_cubic_takes(cn, interp, scale_x, scale_y, f.sw, f.dh, f.dstep)) {
+        UpMixDesc& u = out->up = UpMixDesc{};
+        u.a = rargs(f);
+        u.vec_end = (f.dw * cn) & ~7;
+        u.nbx = (f.dw + 255) / 256;
+        u.rows_per_wave = up_rows_per_wave(cn, f.dw, f.dh, scale_x, scale_y, count);
+        u.nblk = u.nbx * ((f.dh + u.rows_per_wave - 1) / u.rows_per_wave);
+        return MIX_UP;
     }
     if (interp != IMP_INTER_AREA || whole) return MIX_LONE;
     MixDesc& d = out->m = MixDesc{};
@@ -4073,7 +4280,8 @@ int launch_resize_mixed(const MixFrame* fr, int count, int cn, int simple, hipSt
     std::vector<MixDesc> wide_frames;                      // cells of 21..66 source columns (area_wide_plan)
     std::vector<MixDesc> rows_frames;                      // general AREA, cells of at most 20 columns
     int wide_line = 0;                                     // the longest LDS line among the wide frames, in bytes
-    int members[MIX_CLASSES] = {0, 0, 0, 0}, last[MIX_CLASSES] = {-1, -1, -1, -1};   // frames of a class, and the latest of them
+    std::vector<UpMixDesc> up_frames;                      // CUBIC enlargements (up_cubic_takes)
+    int members[MIX_CLASSES] = {0, 0, 0, 0, 0}, last[MIX_CLASSES] = {-1, -1, -1, -1, -1};   // frames of a class, and the latest of them
     rows_frames.reserve(count);
     for (int i = 0; i < count; i++) {
         const MixFrame& f = fr[i];
@@ -4089,6 +4297,7 @@ int launch_resize_mixed(const MixFrame* fr, int count, int cn, int simple, hipSt
         if (k == MIX_WHOLE) whole_frames.push_back(d.whole);
         else if (k == MIX_NN) nn_frames.push_back(d.nn);
         else if (k == MIX_ROWS) rows_frames.push_back(d.m);
+        else if (k == MIX_UP) up_frames.push_back(d.up);
         else {
             wide_frames.push_back(d.m);
             wide_line = std::max(wide_line, d.line_bytes);
@@ -4098,10 +4307,12 @@ int launch_resize_mixed(const MixFrame* fr, int count, int cn, int simple, hipSt
     // single colour frame of MIX_ROWS rides k_resize_area_mix all the same (a gray one goes to k_resize_area<1> and its tables).
     for (int k = 0; k < MIX_CLASSES; k++) {
         int rc = IMP_OK;
-        if (members[k] == 1 && (k != MIX_ROWS || cn == 1)) rc = launch_lone(fr[last[k]], cn, k == MIX_NN ? IMP_INTER_NN : IMP_INTER_AREA, s);
+        if (members[k] == 1 && (k != MIX_ROWS || cn == 1))
+            rc = launch_lone(fr[last[k]], cn, k == MIX_NN ? IMP_INTER_NN : k == MIX_UP ? IMP_INTER_CUBIC : IMP_INTER_AREA, s);
         else if (k == MIX_WHOLE) rc = launch_int_mix(whole_frames, cn, s);
         else if (k == MIX_NN) rc = launch_nn_mix(nn_frames, cn, s);
         else if (k == MIX_WIDE) rc = launch_wide_mix(wide_frames, cn, wide_line, s);
+        else if (k == MIX_UP) rc = launch_up_mix(up_frames, cn, s);
         else rc = launch_mix(rows_frames, cn, s);
         if (rc) return rc;
     }
