@@ -479,8 +479,12 @@ int impgpu_run_ops(impgpu_image** pointer, const impgpu_job* job, const impgpu_c
  * launch per channel count too, and so do the NN resizes of `simple` requests and the BGR / BGRA enlargements (CUBIC) -- at
  * most five resize launches per channel count.  Resizes launch_resize_mixed does not gather (gray enlargements, frames of
  * which one axis grows while y shrinks, enlargements whose x shrinks past 2x, extreme ratios: cells past 66 source
- * columns) and blurs outside
- * the one-pass forms (large radii) still take a launch per request inside their round.  A single GRAY frame with a resize rides the same launches: its resize joins the gray
+ * columns) still take a launch per request inside their round.  Blurs share launches by form: the one-pass forms (small
+ * radii) one launch per form and byte-plane count, the two-pass matrix-unit form (impgpu_blur_form 3: from sigma 5.6 / 6.6
+ * for BGRA / BGR up, through sigma 25 and beyond while the trimmed radius stays within 56; blur=8 among them) ONE launch pair and one planes buffer per channel count and plane count -- unless the
+ * round holds a single such frame, which runs alone as in impgpu_run_ops; the remaining forms (impgpu_blur_form 0: radii past
+ * 56, tap sums no matrix-unit form takes, 1-pixel axes, BGRA windows off the dword grid) take their launches per request.
+ * A single GRAY frame with a resize rides the same launches: its resize joins the gray
  * group of impgpu_batch_resize_mixed (channels = 1), ONE k_gray2bgr_mix launch then promotes every gray request of the call
  * (bridge.c:613-618, the filtering step -- entered for a gray frame even without filters; a request whose fault point fires
  * there keeps its resized gray frame), and from there its chain's segments run in the 3-channel groups with the call's BGR
@@ -514,6 +518,12 @@ int impgpu_resize_geometry(int width, int height, const char* args, const impgpu
                            int simple, int* w, int* h, int* interpolation);   /* bridge.c:143-190 */
 int impgpu_filter_check(const char* request, int allow_experiments);           /* filters.c:43-70 + per-filter arg checks */
 int impgpu_check_destructive(const char* request);                             /* filters.c:32-40 */
+/* Which Gaussian form a dword-aligned width x height frame of 3 or 4 channels gets for filter-blur=sigma (host, no device):
+ * 1 = k_blur_fused4, 2 = the one-pass matrix-unit form, 3 = the two-pass matrix-unit form (rows, planes buffer, columns) --
+ * the forms whose frames share launches in impgpu_batch_run_ops -- 0 = any other form (other channel counts and 1-pixel axes
+ * included).  *planes (may be NULL) = the byte planes of the row sums for forms 2 and 3 (2, or 3 when the fixed-point taps sum
+ * to 258..260), else 0: frames share a launch only with frames of the same form and plane count. */
+int impgpu_blur_form(int width, int height, int channels, double sigma, int* planes);
 
 /* ---- request front end (host, no device): the part of RunJob above the operators.
  *      URI unescape + GET grammar of bridge.c:304-372 ('?' split, '&' tokens, prefix-matched keys,

@@ -195,6 +195,7 @@ SIGNATURES = {
     "impgpu_resize_geometry": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.POINTER(CConfig), C.c_int, IP, IP, IP]),
     "impgpu_filter_check": (C.c_int, [C.c_char_p, C.c_int]),
     "impgpu_check_destructive": (C.c_int, [C.c_char_p]),
+    "impgpu_blur_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, IP]),
     "impgpu_parse_request": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(CConfig), PP]),
     "impgpu_request_job": (C.POINTER(CJob), [P]),
     "impgpu_request_quality": (C.c_char_p, [P]),

@@ -432,7 +432,8 @@ void Batch::promote_gray() {
 }
 
 // Round r: segment r of every chain that has one, one launch per (kind, channel count) in the order window, pixel, geom, blur
-// -- and the blur forms no mixed kernel takes one request at a time, as apply_plan runs them.  Barriers write fresh frames;
+// -- and the blur forms no mixed kernel takes one request at a time, as apply_plan runs them; so does a two-pass blur that is
+// the only one of its channel and plane count in the round (a shared launch pair would save it nothing).  Barriers write fresh frames;
 // pointwise segments work in place, or out of the window into a fresh frame when the request still stands on one.  A request
 // that has run its segments and still stands on a window (no segment at all: the bare crop; or nothing but blurs that worked in
 // place) leaves it as materialize() does, as a bare item of the window launch of the round after its last segment.
@@ -441,6 +442,14 @@ void Batch::segment_round(size_t r) {
     Group<PixelTailItem> pix[2];
     Group<GeomItem> geo[2];
     Group<BlurItem> blu[2];
+    std::vector<int> pairs[2][2];                                   // two-pass blurs by channel count and plane count (2, 3)
+    auto lone_blur = [&](int i, const Segment& sg) {                // a blur form of its own: launched alone, as apply_plan does
+        Work wk{images[i], runs[(size_t)i].cur};
+        const int rc = apply_plan(wk, sg.plan);
+        images[i] = wk.owner;
+        runs[(size_t)i].cur = wk.v;
+        if (rc) stop(i, rc);
+    };
     for (int i = 0; i < count; i++) {
         ChainRun& run = runs[(size_t)i];
         if (run.state != ChainRun::RUNNING || (size_t)run.nsegs < r) continue;
@@ -475,13 +484,11 @@ void Batch::segment_round(size_t r) {
             wnd[k].add(i, WindowItem{cur.d, cur.step, it});
             continue;
         }
-        if (sg.kind == SEG_BLUR && blur_form(cur.w, cur.h, cur.c, !(((uintptr_t)cur.d | (uintptr_t)cur.step) & 3), sg.plan.sigma) != BLUR_MIXABLE) {
-            Work wk{images[i], cur};                                // a blur form of its own: launched alone, as apply_plan does
-            const int rc = apply_plan(wk, sg.plan);
-            images[i] = wk.owner;
-            run.cur = wk.v;
-            if (rc) stop(i, rc);
-            continue;
+        if (sg.kind == SEG_BLUR) {
+            int planes = 0;
+            const int form = blur_form(cur.w, cur.h, cur.c, !(((uintptr_t)cur.d | (uintptr_t)cur.step) & 3), sg.plan.sigma, &planes);
+            if (form == BLUR_LONE) { lone_blur(i, sg); continue; }
+            if (form == BLUR_MIXABLE_PAIR) { pairs[k][planes - 2].push_back(i); continue; }     // (placed behind the loop)
         }
         const bool turn = sg.kind == SEG_GEOM && sg.plan.cls == FC_ROTATE, swap = turn && sg.plan.rotate != 180;
         impgpu_image* out = fresh(i, swap ? cur.h : cur.w, swap ? cur.w : cur.h, cur.c);
@@ -492,6 +499,15 @@ void Batch::segment_round(size_t r) {
         else
             blu[k].add(i, BlurItem{cur.d, out->d, cur.w, cur.h, cur.step, out->step, (double)sg.plan.sigma});
     }
+    for (int k = 0; k < 2; k++)
+        for (const std::vector<int>& cls : pairs[k])
+            for (int i : cls) {
+                const Segment& sg = runs[(size_t)i].plan.segs[r];
+                if (cls.size() == 1) { lone_blur(i, sg); continue; }
+                const View cur = runs[(size_t)i].cur;
+                if (impgpu_image* out = fresh(i, cur.w, cur.h, cur.c))
+                    blu[k].add(i, BlurItem{cur.d, out->d, cur.w, cur.h, cur.step, out->step, (double)sg.plan.sigma});
+            }
     for (int k = 0; k < 2; k++) {
         if (!wnd[k].empty()) adopt(wnd[k].who, launch_window_mixed(wnd[k].items.data(), wnd[k].size(), k + 3, s));
         if (!pix[k].empty()) adopt(pix[k].who, launch_pixel_tail_mixed(pix[k].items.data(), pix[k].size(), k + 3, s));
@@ -524,6 +540,12 @@ int impgpu_filter_check(const char* request, int allow_experiments) {
 }
 
 int impgpu_check_destructive(const char* request) { return check_destructive(request); }
+
+int impgpu_blur_form(int width, int height, int channels, double sigma, int* planes) {
+    int kernel = 0;
+    blur_form(width, height, channels, true, sigma, planes, &kernel);
+    return kernel;
+}
 
 int impgpu_image_clone(const impgpu_image* src, impgpu_image** out) {
     if (!src || !out) return IMP_ERROR_INVALID_ARGS;

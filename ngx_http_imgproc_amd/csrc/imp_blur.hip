@@ -11,7 +11,9 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <map>
 #include <type_traits>
+#include <utility>
 #include "imp_internal.h"
 
 namespace imp {
@@ -509,20 +511,18 @@ static void bm_band_host(const std::vector<int>& ik, int r, int dil, int nchunk,
             }
 }
 
+// The row pass's tile body: tile (tbx, tby) of frame `frame` -> its planes `pl`.  k_blur_mfma_rows (a grid over equal frames)
+// and k_blur_rows_mix (a descriptor per frame) both run it.
 template <int CN, bool WIDE>
-__global__ __launch_bounds__(256) void k_blur_mfma_rows(const uint8_t* __restrict__ src, long long sstride, int sstep, int w, int h,
-                                                        uint8_t* __restrict__ planes, long long pstride, int hp, int roww_pad,
-                                                        const bm_v4i* __restrict__ bands, int r, int nchunk, int pitch_s, int bias) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t bm_smem[];
+__device__ __forceinline__ void blur_mfma_rows_tile(const uint8_t* __restrict__ frame, int sstep, int w, int h, uint8_t* __restrict__ pl, int hp,
+                                                    int roww_pad, const bm_v4i* __restrict__ bands, int r, int nchunk, int pitch_s, int bias,
+                                                    int tbx, int tby, uint8_t* bm_smem) {
     uint8_t* s_src = bm_smem;                                       // [BM_H][pitch_s]: source bytes - 128, window column 0 = byte x0b - CN r
     uint8_t* s_pl = bm_smem + (size_t)BM_H * pitch_s;               // [2 or 3][BM_W][BM_H + 16]: the row sums' low / high bytes - 128 (WIDE: and bit 16), transposed
     constexpr int NPL = WIDE ? 3 : 2;
     constexpr int PT = BM_H + 16;
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    int tbx, tby, tbz;
-    bm_xcd_tile<false>(&tbx, &tby, &tbz);
     const int x0b = tbx * BM_W, y0 = tby * BM_H, roww = w * CN;
-    const uint8_t* frame = src + (long long)tbz * sstride;
     // stage the rows: replicated borders; sixteen bytes at a time where they are inside the row (a byte-aligned address is fine)
     const int wbytes = BM_W + 2 * CN * r, wq = (wbytes + 15) >> 4;
     for (int idx = t; idx < BM_H * wq; idx += 256) {
@@ -573,7 +573,6 @@ __global__ __launch_bounds__(256) void k_blur_mfma_rows(const uint8_t* __restric
     }
     __syncthreads();
     // the tile's planes out, 64 contiguous bytes (64 rows) per byte column
-    uint8_t* pl = planes + (long long)tbz * pstride;
     for (int idx = t; idx < NPL * BM_W * 4; idx += 256) {
         const int q = idx & 3, xb = (idx >> 2) & (BM_W - 1), p = idx >> 8;
         const uint4 v = *(const uint4*)(s_pl + (size_t)(p * BM_W + xb) * PT + q * 16);
@@ -582,17 +581,25 @@ __global__ __launch_bounds__(256) void k_blur_mfma_rows(const uint8_t* __restric
 }
 
 template <int CN, bool WIDE>
-__global__ __launch_bounds__(256) void k_blur_mfma_cols(const uint8_t* __restrict__ planes, long long pstride, int hp, int roww_pad,
-                                                        uint8_t* __restrict__ dst, long long dstride, int dstep, int w, int h,
-                                                        const bm_v4i* __restrict__ bands, int r, int nchunk, int pitch_p, int bias) {
+__global__ __launch_bounds__(256) void k_blur_mfma_rows(const uint8_t* __restrict__ src, long long sstride, int sstep, int w, int h,
+                                                        uint8_t* __restrict__ planes, long long pstride, int hp, int roww_pad,
+                                                        const bm_v4i* __restrict__ bands, int r, int nchunk, int pitch_s, int bias) {
     extern __shared__ __attribute__((aligned(16))) uint8_t bm_smem[];
+    int tbx, tby, tbz;
+    bm_xcd_tile<false>(&tbx, &tby, &tbz);
+    blur_mfma_rows_tile<CN, WIDE>(src + (long long)tbz * sstride, sstep, w, h, planes + (long long)tbz * pstride, hp, roww_pad, bands, r, nchunk,
+                                  pitch_s, bias, tbx, tby, bm_smem);
+}
+
+// The column pass's tile body: tile (tbx, tby) of a frame's planes `pl` -> `out`.  k_blur_mfma_cols and k_blur_cols_mix run it.
+template <int CN, bool WIDE>
+__device__ __forceinline__ void blur_mfma_cols_tile(const uint8_t* __restrict__ pl, int hp, int roww_pad, uint8_t* __restrict__ out, int dstep, int w,
+                                                    int h, const bm_v4i* __restrict__ bands, int r, int nchunk, int pitch_p, int bias, int tbx,
+                                                    int tby, uint8_t* bm_smem) {
     uint8_t* s_pl = bm_smem;                                        // [2 or 3][BM_W][pitch_p]: row 0 = image row y0 - r
     constexpr int NPL = WIDE ? 3 : 2;
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    int tbx, tby, tbz;
-    bm_xcd_tile<true>(&tbx, &tby, &tbz);
     const int x0b = tbx * BM_W, y0 = tby * BM_H, roww = w * CN;
-    const uint8_t* pl = planes + (long long)tbz * pstride;
     const int nrows = BM_H + 2 * r, n16 = (nrows + 15) >> 4;
     for (int idx = t; idx < NPL * BM_W * n16; idx += 256) {
         const int piece = idx % n16, xb = (idx / n16) & (BM_W - 1), p = idx / (n16 * BM_W);
@@ -613,7 +620,6 @@ __global__ __launch_bounds__(256) void k_blur_mfma_cols(const uint8_t* __restric
 #pragma unroll
     for (int c = 0; c < 3; c++) band[c] = c < nchunk ? bands[c * 64 + lane] : bm_v4i{0, 0, 0, 0};
     __syncthreads();
-    uint8_t* out = dst + (long long)tbz * dstride;
     const int vec_end = roww & ~3;                                  // OpenCV's SSE2 column loop; behind it the scalar template
     for (int tile = wv; tile < (BM_W / 16) * (BM_H / 16); tile += 4) {
         const int xg = tile & 3, og = tile >> 2;
@@ -642,6 +648,17 @@ __global__ __launch_bounds__(256) void k_blur_mfma_cols(const uint8_t* __restric
         if (xb + 3 < roww) *(uint32_t*)o = px;
         else for (int i = 0; xb + i < roww; i++) o[i] = (uint8_t)(px >> (8 * i));
     }
+}
+
+template <int CN, bool WIDE>
+__global__ __launch_bounds__(256) void k_blur_mfma_cols(const uint8_t* __restrict__ planes, long long pstride, int hp, int roww_pad,
+                                                        uint8_t* __restrict__ dst, long long dstride, int dstep, int w, int h,
+                                                        const bm_v4i* __restrict__ bands, int r, int nchunk, int pitch_p, int bias) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t bm_smem[];
+    int tbx, tby, tbz;
+    bm_xcd_tile<true>(&tbx, &tby, &tbz);
+    blur_mfma_cols_tile<CN, WIDE>(planes + (long long)tbz * pstride, hp, roww_pad, dst + (long long)tbz * dstride, dstep, w, h, bands, r, nchunk,
+                                  pitch_p, bias, tbx, tby, bm_smem);
 }
 
 // Both passes in ONE launch for the radii whose tile fits LDS twice per compute unit: the rows of the tile AND its 2r halo rows
@@ -1014,14 +1031,53 @@ __global__ __launch_bounds__(256) void k_blur_mix(const BlurDesc* __restrict__ d
     }
 }
 
+// The two-pass matrix-unit form (k_blur_mfma_rows + k_blur_mfma_cols: the radii past the one-pass form's LDS) over frames of
+// different geometry, in ONE launch pair per (channel count, plane count).  A descriptor serves both passes: it names the
+// frame's source, its region of the launch pair's planes buffer and its destination, and is dealt once.  A workgroup takes
+// one 64 x 64-byte tile of one frame; a descriptor's tiles go row-major in the row pass and column-major in the column pass
+// and stay on one XCD list, so the halos neighbouring tiles share (along x, then along y) meet in one L2, as bm_xcd_tile
+// arranges for the lone kernels.
+struct BlurPairDesc {
+    const uint8_t* src; uint8_t* planes; uint8_t* dst; int w, h, sstep, dstep;
+    int hp, roww_pad;            // the planes region: [2 or 3][roww_pad][hp]
+    int r, ntx, nty;             // radius, tiles across / down
+    int kr, kc;                  // row bands, column bands (int offsets into the blob)
+    int nrc, ncc, pitch_s, pitch_p, bias_r, bias_c;
+    int first, nblk;
+};
+
+template <int CN, bool WIDE>
+__global__ __launch_bounds__(256) void k_blur_rows_mix(const BlurPairDesc* __restrict__ descs, MixIndex ix, const int* __restrict__ bands) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t bm_smem[];
+    int blk;
+    const int di = mix_pick(descs, ix, &blk);
+    if (di < 0) return;
+    const BlurPairDesc* m = descs + di;
+    const int ty = blk / m->ntx, tx = blk - ty * m->ntx;
+    blur_mfma_rows_tile<CN, WIDE>(m->src, m->sstep, m->w, m->h, m->planes, m->hp, m->roww_pad, (const bm_v4i*)(bands + m->kr), m->r, m->nrc,
+                                  m->pitch_s, m->bias_r, tx, ty, bm_smem);
+}
+
+template <int CN, bool WIDE>
+__global__ __launch_bounds__(256) void k_blur_cols_mix(const BlurPairDesc* __restrict__ descs, MixIndex ix, const int* __restrict__ bands) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t bm_smem[];
+    int blk;
+    const int di = mix_pick(descs, ix, &blk);
+    if (di < 0) return;
+    const BlurPairDesc* m = descs + di;
+    const int tx = blk / m->nty, ty = blk - tx * m->nty;
+    blur_mfma_cols_tile<CN, WIDE>(m->planes, m->hp, m->roww_pad, m->dst, m->dstep, m->w, m->h, (const bm_v4i*)(bands + m->kc), m->r, m->ncc,
+                                  m->pitch_p, m->bias_c, tx, ty, bm_smem);
+}
+
 // launch_gaussian_fused's choice of form for a frame (its order of tests), without launching anything
 static int blur_form_of(int w, int h, int c, bool aligned, double sigma, std::vector<int>* ik, int* r, int* form, MfmaGeom* g) {
     if ((c != 4 && c != 3) || w < 2 || h < 2 || (c == 4 && !aligned)) return BLUR_LONE;
     bool fits16;
     if (!blur_taps(sigma, ik, r, &fits16)) return BLUR_LONE;
     if (*r >= 3 && mfma_geom(*ik, *r, c, g)) {             // (a fresh frame's pointer and step are dword aligned: launch_gaussian_mfma's last test holds)
-        *form = BF_MFMA;
-        return g->fused ? BLUR_MIXABLE : BLUR_LONE;
+        *form = BF_MFMA;                                       // (launch_gaussian_mfma asks the same g->fused)
+        return g->fused ? BLUR_MIXABLE : BLUR_MIXABLE_PAIR;
     }
     if (*r > 16 || !fits16) return BLUR_LONE;              // (k_blur_strip4, or nothing)
     if ((h + 31) / 32 > 65535) return BLUR_LONE;
@@ -1029,11 +1085,84 @@ static int blur_form_of(int w, int h, int c, bool aligned, double sigma, std::ve
     return BLUR_MIXABLE;
 }
 
-int blur_form(int w, int h, int c, bool aligned, double sigma) {
+int blur_form(int w, int h, int c, bool aligned, double sigma, int* planes, int* kernel) {
     std::vector<int> ik;
     int r = 0, form = 0;
     MfmaGeom g{};
-    return blur_form_of(w, h, c, aligned, sigma, &ik, &r, &form, &g);
+    const int verdict = blur_form_of(w, h, c, aligned, sigma, &ik, &r, &form, &g);
+    const bool mfma = verdict != BLUR_LONE && form == BF_MFMA;
+    if (planes) *planes = mfma ? g.npl : 0;
+    if (kernel) *kernel = verdict == BLUR_LONE ? 0 : !mfma ? 1 : verdict == BLUR_MIXABLE ? 2 : 3;
+    return verdict;
+}
+
+// The two-pass items of launch_blur_mixed in launch pairs: one planes allocation per pair with every frame's region in it, a
+// new pair where the regions would pass 1 GiB (launch_gaussian_mfma's chunk bound; a larger single frame has a pair of its
+// own), the band operands of each set of taps once per pair, one deal for both passes.
+struct BlurPairItem { BlurItem it; std::vector<int> ik; int r; MfmaGeom g; };
+static int launch_blur_pairs(const std::vector<BlurPairItem>& items, int cn, bool wide, hipStream_t s) {
+    for (size_t i0 = 0; i0 < items.size();) {
+        std::vector<BlurPairDesc> v;
+        std::vector<size_t> region_at;                              // where each frame's planes start in the pair's buffer
+        std::vector<int> blob;
+        std::map<std::vector<int>, std::pair<int, int>> bands;      // taps -> where their two operands start
+        size_t bytes = 0, lds_r = 0, lds_c = 0, i1 = i0;
+        for (; i1 < items.size(); i1++) {
+            const BlurPairItem& p = items[i1];
+            BlurPairDesc d{};
+            d.roww_pad = (p.it.w * cn + BM_W - 1) / BM_W * BM_W;
+            d.hp = (p.it.h + BM_H - 1) / BM_H * BM_H;
+            const size_t region = (size_t)p.g.npl * d.roww_pad * d.hp;
+            if (i1 > i0 && bytes + region > ((size_t)1 << 30)) break;
+            d.src = p.it.src; d.dst = p.it.dst; d.w = p.it.w; d.h = p.it.h; d.sstep = p.it.sstep; d.dstep = p.it.dstep; d.r = p.r;
+            region_at.push_back(bytes);
+            bytes += region;
+            auto at = bands.find(p.ik);
+            if (at == bands.end()) {
+                std::pair<int, int> k;
+                k.first = (int)blob.size();
+                bm_band_host(p.ik, p.r, cn, p.g.nrc, &blob);
+                k.second = (int)blob.size();
+                bm_band_host(p.ik, p.r, 1, p.g.ncc, &blob);
+                at = bands.emplace(p.ik, k).first;
+            }
+            d.kr = at->second.first; d.kc = at->second.second;
+            d.nrc = p.g.nrc; d.ncc = p.g.ncc; d.pitch_s = p.g.pitch_s; d.pitch_p = p.g.pitch_p;
+            d.bias_r = (int)(128 * p.g.sum); d.bias_c = (int)(128 * p.g.sum * 257);
+            d.ntx = d.roww_pad / BM_W; d.nty = d.hp / BM_H;
+            d.nblk = d.ntx * d.nty;
+            lds_r = std::max(lds_r, (size_t)BM_H * p.g.pitch_s + (size_t)p.g.npl * BM_W * (BM_H + 16));
+            lds_c = std::max(lds_c, (size_t)p.g.npl * BM_W * p.g.pitch_p);
+            v.push_back(d);
+        }
+        i0 = i1;
+        void* planes = nullptr;
+        if (int rc = dev_alloc_on(bytes, &planes, s)) return rc;
+        for (size_t i = 0; i < v.size(); i++) v[i].planes = (uint8_t*)planes + region_at[i];
+        const std::vector<uint8_t> bytes_of((const uint8_t*)blob.data(), (const uint8_t*)blob.data() + blob.size() * 4);
+        const size_t blob_at = mix_blob_offset<BlurPairDesc>(v.size());
+        hipError_t e = hipSuccess;                              // lds_limit_once's verdict: no launch without it
+        const int rc = mix_launch(v, [](BlurPairDesc& d) { return (long long)d.w * d.h * (2 * d.r + 1); }, s,
+                                  [&](dim3 grid, const BlurPairDesc* dd, const MixIndex& ix) {
+            const int* bd = (const int*)((const uint8_t*)dd + blob_at);
+#define IMP_BLUR_PAIR(CN_, W_)                                                                                          \
+    do {                                                                                                                \
+        e = lds_limit_once<k_blur_rows_mix<CN_, W_>>();                                                                 \
+        if (e == hipSuccess) e = lds_limit_once<k_blur_cols_mix<CN_, W_>>();                                            \
+        if (e == hipSuccess) {                                                                                          \
+            hipLaunchKernelGGL((k_blur_rows_mix<CN_, W_>), grid, dim3(256), lds_r, s, dd, ix, bd);                      \
+            hipLaunchKernelGGL((k_blur_cols_mix<CN_, W_>), grid, dim3(256), lds_c, s, dd, ix, bd);                      \
+        }                                                                                                               \
+    } while (0)
+            if (cn == 4) { if (wide) IMP_BLUR_PAIR(4, true); else IMP_BLUR_PAIR(4, false); }
+            else { if (wide) IMP_BLUR_PAIR(3, true); else IMP_BLUR_PAIR(3, false); }
+#undef IMP_BLUR_PAIR
+        }, &bytes_of);
+        dev_free_on(planes, s);
+        if (rc) return rc;
+        if (e != hipSuccess) { set_error("k_blur_rows_mix", e); return IMP_ERROR_DEVICE; }
+    }
+    return IMP_OK;
 }
 
 int launch_blur_mixed(const BlurItem* items, int count, int cn, hipStream_t s) {
@@ -1041,6 +1170,7 @@ int launch_blur_mixed(const BlurItem* items, int count, int cn, hipStream_t s) {
     if (!items || (cn != 3 && cn != 4)) return IMP_ERROR_INVALID_ARGS;
     std::vector<BlurDesc> v[3];                             // FUSED4, MFMA, MFMA wide
     size_t lds[3] = {0, 0, 0};
+    std::vector<BlurPairItem> pairs[2];                     // the two-pass form, two / three planes
     std::vector<int> blob;
     for (int i = 0; i < count; i++) {                      // nothing is launched unless every item is well-formed and mixable
         const BlurItem& it = items[i];
@@ -1051,7 +1181,9 @@ int launch_blur_mixed(const BlurItem* items, int count, int cn, hipStream_t s) {
         std::vector<int> ik;
         int r = 0, form = 0;
         MfmaGeom g{};
-        if (blur_form_of(it.w, it.h, cn, aligned, it.sigma, &ik, &r, &form, &g) != BLUR_MIXABLE) return IMP_ERROR_INVALID_ARGS;
+        const int verdict = blur_form_of(it.w, it.h, cn, aligned, it.sigma, &ik, &r, &form, &g);
+        if (verdict == BLUR_LONE) return IMP_ERROR_INVALID_ARGS;
+        if (verdict == BLUR_MIXABLE_PAIR) { pairs[g.wide ? 1 : 0].push_back(BlurPairItem{it, ik, r, g}); continue; }
         BlurDesc d{};
         d.src = it.src; d.dst = it.dst; d.w = it.w; d.h = it.h; d.sstep = it.sstep; d.dstep = it.dstep; d.r = r;
         while (blob.size() % 4) blob.push_back(0);          // (16-byte aligned operands)
@@ -1080,9 +1212,9 @@ int launch_blur_mixed(const BlurItem* items, int count, int cn, hipStream_t s) {
         }
         v[k].push_back(d);
     }
-    if (blob.empty()) blob.resize(4, 0);
-    void* dev_k = nullptr;
-    if (int rc = upload_small(blob.data(), blob.size() * 4, &dev_k, s)) return rc;
+    void* dev_k = nullptr;                                  // (nothing to upload when every item is of the two-pass form)
+    if (!blob.empty())
+        if (int rc = upload_small(blob.data(), blob.size() * 4, &dev_k, s)) return rc;
     const int* taps = (const int*)dev_k;
     hipError_t e = hipSuccess;                              // lds_limit_once's verdict: no launch without it
     int rc = IMP_OK;
@@ -1103,6 +1235,8 @@ int launch_blur_mixed(const BlurItem* items, int count, int cn, hipStream_t s) {
     dev_free_on(dev_k, s);                                  // (the kernel blob the three launches share)
     if (rc) return rc;
     if (e != hipSuccess) { set_error("k_blur_mix", e); return IMP_ERROR_DEVICE; }
+    for (int k = 0; k < 2; k++)
+        if (int rc2 = launch_blur_pairs(pairs[k], cn, k == 1, s)) return rc2;
     return IMP_OK;
 }
 

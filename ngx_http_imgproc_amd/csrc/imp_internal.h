@@ -489,12 +489,16 @@ int launch_geom_mixed(const GeomItem* items, int count, int channels, hipStream_
 struct Gray2BgrItem { const uint8_t* src; uint8_t* dst; int w, h, sstep, dstep; };
 int launch_gray2bgr_mixed(const Gray2BgrItem* items, int count, hipStream_t s);
 // imp_blur.hip: which form launch_gaussian_fused gives a frame of this geometry and sigma -- BLUR_MIXABLE when it is one of
-// the one-pass forms k_blur_mix takes (k_blur_fused4, k_blur_mfma_fused), BLUR_LONE for the others.  `aligned`: the
-// dword alignment launch_gaussian_fused asks of BGRA pointers and steps holds.
-enum { BLUR_LONE = 0, BLUR_MIXABLE = 1 };
-int blur_form(int w, int h, int c, bool aligned, double sigma);
+// the one-pass forms k_blur_mix takes (k_blur_fused4, k_blur_mfma_fused), BLUR_MIXABLE_PAIR for the two-pass matrix-unit form
+// (k_blur_mfma_rows + k_blur_mfma_cols), which k_blur_rows_mix + k_blur_cols_mix take, BLUR_LONE for the others.  `aligned`:
+// the dword alignment launch_gaussian_fused asks of BGRA pointers and steps holds.  *planes (may be NULL): the byte planes of
+// a matrix-unit form's row sums, 2 or 3 (0 for the other forms) -- frames of different plane counts never share a launch.
+// *kernel (may be NULL): impgpu_blur_form's code.
+enum { BLUR_LONE = 0, BLUR_MIXABLE = 1, BLUR_MIXABLE_PAIR = 2 };
+int blur_form(int w, int h, int c, bool aligned, double sigma, int* planes = nullptr, int* kernel = nullptr);
 struct BlurItem { const uint8_t* src; uint8_t* dst; int w, h, sstep, dstep; double sigma; };   // out of place, same geometry
-// every item must be BLUR_MIXABLE (IMP_ERROR_INVALID_ARGS otherwise, nothing launched)
+// every item must be BLUR_MIXABLE or BLUR_MIXABLE_PAIR (IMP_ERROR_INVALID_ARGS otherwise, nothing launched): one launch per
+// one-pass form and plane count, one launch pair per plane count of the two-pass form
 int launch_blur_mixed(const BlurItem* items, int count, int channels, hipStream_t s);
 
 // Watermark placement (bridge.c:254-274 + cvSetImageROI clipping). Returns IMP_* code.

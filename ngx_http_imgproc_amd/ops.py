@@ -706,6 +706,12 @@ def check_destructive(request):
     return lib.impgpu_check_destructive(_b(request))
 
 
+def blur_form(width, height, channels, sigma):
+    """impgpu_blur_form -> (form, planes): 0 a lone form, 1 k_blur_fused4, 2 / 3 the one- / two-pass matrix-unit form."""
+    planes = C.c_int()
+    return lib.impgpu_blur_form(width, height, channels, float(sigma), planes), planes.value
+
+
 def batch_cv_resize(src_ptr, src_stride, sw, sh, sstep, dst_ptr, dst_stride, dw, dh, dstep, channels, count,
                     interpolation, stream=None):
     rc = lib.impgpu_batch_cv_resize(C.c_void_p(src_ptr), src_stride, sw, sh, sstep, C.c_void_p(dst_ptr), dst_stride,
