@@ -40,6 +40,11 @@ sed -i '681a\
 	#ifdef IMP_FEATURE_ADVANCED_IO\
 		if (encodeAdvancedIO \&\& encodeAdvancedIO != FIF_GIF \&\& album.Count == 1) {\
 			album.Device = gpu.Handle;\
+			if (!album.Device) {\
+				album.Device = ImpGpuSaveSource(\&gpu, 0);\
+			}\
+		} else if (encodeAdvancedIO == FIF_GIF) {\
+			album.Device = ImpGpuSaveSource(\&gpu, 1);\
 		}\
 	#endif\
 	if (!album.Device \&\& (encodeAdvancedIO || answer->MIME != IMP_MIME_JPG)) {\
@@ -126,6 +131,27 @@ sed -i '428,429c\
         IplImage* image = source->Frames[0].Image;\
         frame = FiSupports32bit(format) ? IplToFI32(image) : IplToFI24(image);\
     }' "$A"
+# SaveGIF (advancedio.c:349-350, :371, :374): a frame of an album that has a source (broker mode) arrives as the 32-bit bitmap
+# IplToFI32 would have made of it; the loop that restores transparency takes its bounds from that bitmap
+sed -i '374s/image->width/(int)FreeImage_GetWidth(frame32b)/' "$A"
+sed -i '371s/image->height/(int)FreeImage_GetHeight(frame32b)/' "$A"
+sed -i '349,350c\
+        FIBITMAP* frame32b;\
+        if (source->Device) {\
+            frame32b = FreeImage_Allocate(ImpGpuFrameWidth(source->Device), ImpGpuFrameHeight(source->Device), 32, 0, 0, 0);\
+            if (!frame32b || ImpGpuFetchFiFrame(source->Device, frameid, 32, FreeImage_GetBits(frame32b), FreeImage_GetPitch(frame32b))) {\
+                result->Error = IMP_ERROR_ENCODE_FAILED;\
+                if (frame32b) {\
+                    FreeImage_Unload(frame32b);\
+                }\
+                free(palette);\
+                FreeImage_CloseMemory(mem);\
+                FreeImage_CloseMultiBitmap(container, 0);\
+                return;\
+            }\
+        } else {\
+            frame32b = IplToFI32(source->Frames[frameid].Image);\
+        }' "$A"
 # FiLoadFrames (advancedio.c:325-326): no device frames yet
 sed -i '326a\
     result.Device = NULL;' "$A"

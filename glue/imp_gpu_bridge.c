@@ -18,6 +18,20 @@ static int            g_broker_nmarks;
 
 static int BrokerMode(void) { return g_broker_name != NULL; }
 
+/* Broker mode, frames from FreeImage: what LoadGIF / LoadSingle have for the request that is running (RunJob is synchronous,
+ * one request at a time per worker).  The hooks get no ImpGpuAlbum, so it is noted here; the request's exit sends it and
+ * ImpGpuRelease forgets it.  The page copies and the bits live in the request pool until then.  They are NOT put into the
+ * slot at decode time: between the decode and the exit FillConfig may register the location's overlay, and the client
+ * registers overlays again after a broker restart -- both round trips use the same input buffer. */
+static struct {
+    int Kind;                                   /* 0, IMPB_IN_GIF or IMPB_IN_FI32 */
+    const impgpu_gif_page* Pages;               /* IMPB_IN_GIF */
+    int Count, Destructive, Page;
+    const unsigned char* Bits;                  /* IMPB_IN_FI32 */
+    int W, H, Pitch;
+} g_pending;
+static ImpGpuAlbum* g_save;                     /* the request SaveSingle fetches from (ImpGpuSaveSource) */
+
 static int OwnEnv(void) {
     /* HIP is initialised here, in the worker, never in the master before fork.  A failure is not fatal for nginx:
      * every later call then answers IMP_ERROR_DEVICE, which BodyFilter maps to 500 (module.c:305). */
@@ -101,8 +115,22 @@ static int BrokerRun(ImpGpuAlbum* gpu, Album* album, int outKind, int quality, c
         } else {
             goto answered;
         }
+    } else if (g_pending.Kind == IMPB_IN_GIF) {
+        /* LoadGIF's pages: packed into the slot now, composed in the broker with the other GIFs of its batch */
+        r.in_kind = IMPB_IN_GIF;
+        r.pages = g_pending.Pages;
+        r.page_count = g_pending.Count; r.destructive = g_pending.Destructive; r.page = g_pending.Page;
+        rc = impgpu_client_run(g_client, &r, a);
+        goto answered;
+    } else if (g_pending.Kind == IMPB_IN_FI32) {
+        r.in_kind = IMPB_IN_FI32;                /* LoadSingle's bitmap as FreeImage held it: the flip happens in the broker */
+        r.input = g_pending.Bits;
+        r.input_bytes = (size_t)g_pending.Pitch * g_pending.H;
+        r.width = g_pending.W; r.height = g_pending.H; r.channels = 4; r.step = g_pending.Pitch;
+        rc = impgpu_client_run(g_client, &r, a);
+        goto answered;
     } else if (album->Count != 1 || !album->Frames[0].Image) {
-        return IMP_ERROR_UNSUPPORTED;       /* (albums of several frames come from FreeImage: the in-process path) */
+        return IMP_ERROR_INVALID_ARGS;      /* (no file, no pages, no bits, no decoded frame: not an album any decoder makes) */
     }
     {
         IplImage* image = decoded ? decoded : album->Frames[0].Image;
@@ -267,10 +295,6 @@ int ImpGpuOperators(Album* album, ImpGpuAlbum* gpu, ngx_pool_t* pool, char* crop
         *step = IMP_STEP_INFO;
         return IMP_OK;
     }
-    if (BrokerMode() && OwnEnv() != IMP_OK) {       /* frames from FreeImage: this worker needs a device of its own after all */
-        *step = IMP_STEP_DECODE;
-        return IMP_ERROR_DEVICE;
-    }
     int rc = FillConfig(config, &gcfg, NULL);
     if (rc) {
         return rc;
@@ -373,23 +397,26 @@ int ImpGpuDownload(ImpGpuAlbum* gpu, Album* album, ngx_pool_t* pool) {
         /* the answer's pixels come back in the worker's slot: into a fresh IplImage with the header rules of every
          * cvCreateImage in bridge.c, for the host encoder that asked */
         impgpu_client_answer a;
-        IplImage* fresh;
         int y;
         rc = BrokerRun(gpu, album, IMPB_OUT_FRAME, 0, NULL, &a);
         if (rc) {
             return rc;
         }
-        fresh = cvCreateImage(cvSize(a.width, a.height), IPL_DEPTH_8U, a.channels);
-        if (!fresh || !fresh->imageData) {
-            return IMP_ERROR_MALLOC_FAILED;
+        if (a.frames != album->Count) {         /* (an album comes back with all of its frames, a page request with one) */
+            return IMP_ERROR_INVALID_ARGS;
         }
-        for (y = 0; y < a.height; y++) {
-            memcpy(fresh->imageData + (size_t)y * fresh->widthStep, a.data + (size_t)y * a.row_step, (size_t)a.width * a.channels);
-        }
-        {
-            IplImage* old = album->Frames[0].Image;
+        for (fid = 0; fid < a.frames; fid++) {
+            const unsigned char* from = a.data + (size_t)fid * a.frame_stride;
+            IplImage* old = album->Frames[fid].Image;
+            IplImage* fresh = cvCreateImage(cvSize(a.width, a.height), IPL_DEPTH_8U, a.channels);
+            if (!fresh || !fresh->imageData) {
+                return IMP_ERROR_MALLOC_FAILED;
+            }
+            for (y = 0; y < a.height; y++) {
+                memcpy(fresh->imageData + (size_t)y * fresh->widthStep, from + (size_t)y * a.row_step, (size_t)a.width * a.channels);
+            }
             cvReleaseImage(&old);
-            album->Frames[0].Image = fresh;
+            album->Frames[fid].Image = fresh;
         }
         return IMP_OK;
     }
@@ -478,6 +505,8 @@ int ImpGpuEncodeJpeg(ImpGpuAlbum* gpu, int quality, ngx_pool_t* pool, u_char** b
 
 void ImpGpuRelease(ImpGpuAlbum* gpu) {
     impgpu_image_release(&gpu->Handle);
+    memset(&g_pending, 0, sizeof(g_pending));
+    g_save = NULL;
 }
 
 #ifdef IMP_FEATURE_ADVANCED_IO
@@ -522,8 +551,13 @@ int ImpGpuGifCompose(ImpGpuGif* gif, int isdestructive, int page, Album* result)
     if (!gif->Pages || gif->Count < 1) {
         return IMP_ERROR_DECODE_FAILED;
     }
-    if (BrokerMode() && OwnEnv() != IMP_OK) {       /* FreeImage's frames need a device in this worker (imp_gpu_bridge.h) */
-        return IMP_ERROR_DEVICE;
+    if (BrokerMode()) {
+        /* noted, like a file: the pages (copies in the request pool, ImpGpuGifPage) travel with the request's one round trip */
+        memset(&g_pending, 0, sizeof(g_pending));
+        g_pending.Kind = IMPB_IN_GIF;
+        g_pending.Pages = gif->Pages;
+        g_pending.Count = gif->Count; g_pending.Destructive = isdestructive; g_pending.Page = page;
+        return IMP_OK;
     }
     rc = impgpu_gif_compose_album(gif->Pages, gif->Count, isdestructive, page, &frames);
     if (rc == IMP_OK) {
@@ -536,7 +570,21 @@ int ImpGpuGifCompose(ImpGpuGif* gif, int isdestructive, int page, Album* result)
  * 4-channel frame (advancedio.c:310-318) happens there */
 int ImpGpuLoadSingle(Album* result, ngx_pool_t* pool, const unsigned char* bits, int w, int h, int pitch) {
     impgpu_image* frame = NULL;
-    int rc = (BrokerMode() && OwnEnv() != IMP_OK) ? IMP_ERROR_DEVICE : impgpu_image_upload_fi32(bits, w, h, pitch, &frame);
+    int rc = IMP_OK;
+    if (BrokerMode()) {
+        /* noted: FreeImage unloads the bitmap when LoadSingle returns, so the bits are kept in the request pool */
+        unsigned char* copy = (w > 0 && h > 0 && pitch >= w * 4) ? ngx_palloc(pool, (size_t)pitch * h) : NULL;
+        if (!copy) {
+            return IMP_ERROR_MALLOC_FAILED;
+        }
+        memcpy(copy, bits, (size_t)pitch * h);
+        memset(&g_pending, 0, sizeof(g_pending));
+        g_pending.Kind = IMPB_IN_FI32;
+        g_pending.Bits = copy;
+        g_pending.W = w; g_pending.H = h; g_pending.Pitch = pitch;
+    } else {
+        rc = impgpu_image_upload_fi32(bits, w, h, pitch, &frame);
+    }
     if (rc) {
         return rc;
     }
@@ -552,12 +600,67 @@ int ImpGpuLoadSingle(Album* result, ngx_pool_t* pool, const unsigned char* bits,
     return IMP_OK;
 }
 
-int ImpGpuFrameWidth(void* device)  { return impgpu_image_width((impgpu_image*)device); }
-int ImpGpuFrameHeight(void* device) { return impgpu_image_height((impgpu_image*)device); }
+/* Broker mode: what SaveSingle fetches from is the request itself (ImpGpuSaveSource), and the geometry it asks for first
+ * is the answer's.  The one round trip is made when the width is asked for, with both bitmaps FreeImage may want
+ * unknown yet -- so for 32 bits, which holds everything; a 24-bit fetch drops the fourth byte on the way out. */
+void* ImpGpuSaveSource(ImpGpuAlbum* gpu, int frames) {
+    if (gpu->Handle || !BrokerMode() || !gpu->Deferred) {
+        return frames ? NULL : gpu->Handle;     /* (in process SaveGIF keeps its IplImages: ImpGpuDownload) */
+    }
+    g_save = gpu;
+    gpu->Fi.code = -1;
+    return gpu;
+}
+
+static int BrokerFi(ImpGpuAlbum* gpu) {
+    if (gpu->Fi.code == -1) {
+        int rc = gpu->Source ? BrokerRun(gpu, gpu->Source, IMPB_OUT_FI, 32, NULL, &gpu->Fi) : IMP_ERROR_INVALID_ARGS;
+        gpu->Fi.code = rc ? rc : IMP_OK;
+    }
+    return gpu->Fi.code;
+}
+
+int ImpGpuFrameWidth(void* device) {
+    if (BrokerMode() && device == (void*)g_save) {
+        return BrokerFi(g_save) ? 0 : g_save->Fi.width;
+    }
+    return impgpu_image_width((impgpu_image*)device);
+}
+
+int ImpGpuFrameHeight(void* device) {
+    if (BrokerMode() && device == (void*)g_save) {
+        return BrokerFi(g_save) ? 0 : g_save->Fi.height;
+    }
+    return impgpu_image_height((impgpu_image*)device);
+}
 
 /* SaveSingle (advancedio.c:427-446): IplToFI32 / IplToFI24 (advancedio.c:65-101) -- the flip and the 32 / 24-bit repack -- run
  * on the device and land in the bitmap FreeImage is about to encode */
 int ImpGpuFetchFi(void* device, int bpp, unsigned char* bits, int pitch) {
-    return impgpu_image_download_fi((impgpu_image*)device, bpp, bits, pitch);
+    return ImpGpuFetchFiFrame(device, 0, bpp, bits, pitch);
+}
+
+/* ... and SaveGIF's per-frame IplToFI32 (advancedio.c:350), broker mode only: frame `frame` of the same IMPB_OUT_FI answer */
+int ImpGpuFetchFiFrame(void* device, int frame, int bpp, unsigned char* bits, int pitch) {
+    if (BrokerMode() && device == (void*)g_save) {
+        const impgpu_client_answer* a = &g_save->Fi;
+        int x, y;
+        if (BrokerFi(g_save) || (bpp != 24 && bpp != 32) || pitch < a->width * (bpp / 8) || frame < 0 || frame >= a->frames) {
+            return IMP_ERROR_ENCODE_FAILED;
+        }
+        for (y = 0; y < a->height; y++) {
+            const unsigned char* from = a->data + (size_t)frame * a->frame_stride + (size_t)y * a->row_step;
+            unsigned char* to = bits + (size_t)y * pitch;
+            if (bpp == 32) {
+                memcpy(to, from, (size_t)a->width * 4);
+            } else {
+                for (x = 0; x < a->width; x++) {
+                    to[3 * x] = from[4 * x]; to[3 * x + 1] = from[4 * x + 1]; to[3 * x + 2] = from[4 * x + 2];
+                }
+            }
+        }
+        return IMP_OK;
+    }
+    return frame ? IMP_ERROR_INVALID_ARGS : impgpu_image_download_fi((impgpu_image*)device, bpp, bits, pitch);
 }
 #endif

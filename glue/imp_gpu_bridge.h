@@ -17,6 +17,8 @@
  *   advancedio.c:187-248  LoadGIF's per-pixel compositing loop  -> ImpGpuGifPage (collect) + ImpGpuGifCompose at :260
  *   advancedio.c:295-318  LoadSingle's flip-and-copy loop       -> ImpGpuLoadSingle
  *   advancedio.c:428-429  SaveSingle's IplToFI32 / IplToFI24    -> ImpGpuFetchFi into the bitmap FreeImage encodes
+ *                         (bridge.c:681 names the source: ImpGpuSaveSource)
+ *   advancedio.c:349-350  SaveGIF's per-frame IplToFI32         -> ImpGpuFetchFiFrame when the album has a source (broker mode)
  * Needs nginx, OpenCV 2.4 and FreeImage headers exactly like the files around it, so it is not BUILT in this repository;
  * tests/test_glue.py compiles it (and the patched bridge.c) with -fsyntax-only against declaration-only stand-ins for
  * those headers (tests/c/decls/, a compile check of this glue and nothing else), and the C ABI underneath it is exercised
@@ -36,9 +38,11 @@
  * touches HIP.  ImpGpuDecode and ImpGpuOperators only NOTE the file and the job; the request's exit -- ImpGpuEncodeJpeg,
  * ImpGpuDownload, ImpGpuInfo, ImpGpuASCII -- knows what kind of answer is wanted and makes the ONE round trip that
  * carries {file, job, config} to the process that owns the GPU, where it rides a launch with whatever other workers
- * have queued.  A failure comes back with the answer and names its own step (JobResult.Step through `Step`).  Requests
- * whose frames come from FreeImage (IMP_FEATURE_ADVANCED_IO: GIF albums, LoadSingle) still need a device in the worker:
- * their first occurrence starts an in-process env (ImpGpuEnvStart's other branch), everything else goes to the broker. */
+ * have queued.  A failure comes back with the answer and names its own step (JobResult.Step through `Step`).  Frames that
+ * come from FreeImage (IMP_FEATURE_ADVANCED_IO) go the same way: LoadGIF's pages (IMPB_IN_GIF, composed in the broker with
+ * the other GIFs of the batch) and LoadSingle's bits (IMPB_IN_FI32) are noted by their hooks and sent by the exit;
+ * ImpGpuDownload takes every frame of the answer, SaveSingle fetches its bitmap through IMPB_OUT_FI.  A worker in broker
+ * mode never starts a device of its own. */
 typedef struct {
     impgpu_image* Handle;
     /* ---- broker mode only (zero otherwise) ---- */
@@ -50,6 +54,7 @@ typedef struct {
     int           WatermarkId;
     int*          Step;                 /* &answer->Step */
     Album*        Source;               /* the request's album (frames decoded on the host go as pixels) */
+    impgpu_client_answer Fi;            /* SaveSingle's IMPB_OUT_FI answer (ImpGpuSaveSource; code -1: not asked for yet) */
 } ImpGpuAlbum;
 
 /* once per worker process, after fork (module.c:100-107).  worker = ngx_worker (nginx >= 1.9.1) or ngx_process_slot:
@@ -90,8 +95,13 @@ int    ImpGpuGifPage(ImpGpuGif* gif, ngx_pool_t* pool, int frameid, int framecou
                      int left, int top, int dispose, int key, const void* palette, int canvasW, int canvasH);
 int    ImpGpuGifCompose(ImpGpuGif* gif, int isdestructive, int page, Album* result);     /* advancedio.c:204-247 on the device */
 int    ImpGpuLoadSingle(Album* result, ngx_pool_t* pool, const unsigned char* bits, int w, int h, int pitch);   /* advancedio.c:295-318 */
+/* what SaveSingle (frames = 0) or SaveGIF (frames = 1) fetch their bitmaps from (album.Device at bridge.c:681): the device
+ * frame, or in broker mode the request, whose one round trip then asks for IMPB_OUT_FI; NULL: download IplImages as before
+ * (in process SaveGIF always does) */
+void*  ImpGpuSaveSource(ImpGpuAlbum* gpu, int frames);
 int    ImpGpuFrameWidth(void* device);
 int    ImpGpuFrameHeight(void* device);
 int    ImpGpuFetchFi(void* device, int bpp, unsigned char* bits, int pitch);              /* advancedio.c:65-101 */
+int    ImpGpuFetchFiFrame(void* device, int frame, int bpp, unsigned char* bits, int pitch);   /* the same for SaveGIF's frame (advancedio.c:350) */
 
 #endif

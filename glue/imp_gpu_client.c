@@ -307,12 +307,61 @@ int impgpu_jpeg_unstuff(const unsigned char* f, size_t size, unsigned char* out,
     return 1;
 }
 
+/* the pitch a page's index plane gets in the slot (impgpu_broker.h, impgpu_client_pack_gif) */
+static int gif_pitch(const impgpu_gif_page* p) {
+    const long long tight = ((long long)p->width + 1 + 3) & ~3LL;
+    return (long long)p->pitch < tight ? p->pitch : (int)tight;
+}
+
+/* the layout first (nothing is written unless all of it fits), then the records, palettes and planes */
+static int pack_gif(impgpu_client* c, const impgpu_gif_page* pages, int count, size_t* bytes) {
+    if (!pages || !bytes || count < 1 || count > IMPB_MAX_GIF_PAGES) return IMP_ERROR_INVALID_ARGS;
+    const uint64_t cap = c->hdr->f.slot_data_bytes;
+    impb_gif_page* rec = (impb_gif_page*)c->data;
+    uint64_t at = ((uint64_t)count * sizeof(impb_gif_page) + 15) & ~(uint64_t)15;
+    if (at > cap) { snprintf(t_err, sizeof t_err, "input larger than a slot"); return IMP_ERROR_MALLOC_FAILED; }
+    for (int pass = 0; pass < 2; pass++) {
+        uint64_t end = at;
+        for (int i = 0; i < count; i++) {
+            const impgpu_gif_page* p = &pages[i];
+            if (!p->indices || !p->palette || p->width <= 0 || p->height <= 0 || p->pitch < p->width) return IMP_ERROR_INVALID_ARGS;
+            const int pitch = gif_pitch(p);
+            const uint64_t plane = (uint64_t)pitch * (uint64_t)p->height;
+            int same = -1;                              /* the page whose palette this one shares (the one before it, mostly) */
+            for (int k = i - 1; k >= 0 && same < 0; k--) if (pages[k].palette == p->palette) same = k;
+            const uint64_t pal_at = same >= 0 ? 0 : end;
+            if (same < 0) end += 1024;
+            const uint64_t idx_at = end;
+            end += (plane + 15) & ~(uint64_t)15;
+            if (end > cap) { snprintf(t_err, sizeof t_err, "input larger than a slot"); return IMP_ERROR_MALLOC_FAILED; }
+            if (!pass) continue;
+            rec[i].palette_at = same >= 0 ? rec[same].palette_at : pal_at;
+            rec[i].indices_at = idx_at;
+            rec[i].width = p->width; rec[i].height = p->height; rec[i].pitch = pitch;
+            rec[i].left = p->left; rec[i].top = p->top; rec[i].dispose = p->dispose;
+            rec[i].transparency_key = p->transparency_key; rec[i].pad = 0;
+            if (same < 0) memcpy(c->data + pal_at, p->palette, 1024);
+            if (pitch == p->pitch) memcpy(c->data + idx_at, p->indices, (size_t)plane);
+            else for (int y = 0; y < p->height; y++) memcpy(c->data + idx_at + (uint64_t)y * pitch, p->indices + (size_t)y * p->pitch, (size_t)pitch);
+        }
+        *bytes = (size_t)end;
+    }
+    return IMP_OK;
+}
+
+int impgpu_client_pack_gif(impgpu_client* c, const impgpu_gif_page* pages, int count, size_t* bytes) {
+    if (!c) return IMP_ERROR_INVALID_ARGS;
+    int rc = ready(c);
+    if (rc != IMP_OK) return rc;
+    return pack_gif(c, pages, count, bytes);
+}
+
 int impgpu_client_run(impgpu_client* c, const impgpu_client_request* r, impgpu_client_answer* a) {
     if (!c || !r || !a) return IMP_ERROR_INVALID_ARGS;
     memset(a, 0, sizeof *a);
     a->error = "";
-    if (r->in_kind != IMPB_IN_FILE && r->in_kind != IMPB_IN_FRAME) return IMP_ERROR_INVALID_ARGS;
-    if (r->out_kind < IMPB_OUT_JPEG || r->out_kind > IMPB_OUT_PNG) return IMP_ERROR_INVALID_ARGS;
+    if (r->in_kind != IMPB_IN_FILE && r->in_kind != IMPB_IN_FRAME && r->in_kind != IMPB_IN_GIF && r->in_kind != IMPB_IN_FI32) return IMP_ERROR_INVALID_ARGS;
+    if (r->out_kind < IMPB_OUT_JPEG || r->out_kind > IMPB_OUT_FI) return IMP_ERROR_INVALID_ARGS;
     if (r->watermark_id < 0 || r->watermark_id > c->nmarks) return IMP_ERROR_INVALID_ARGS;
     int rc = ready(c);
     if (rc != IMP_OK) return rc;
@@ -329,7 +378,16 @@ int impgpu_client_run(impgpu_client* c, const impgpu_client_request* r, impgpu_c
     if (r->input_bytes > c->hdr->f.slot_data_bytes) { snprintf(t_err, sizeof t_err, "input larger than a slot"); return IMP_ERROR_MALLOC_FAILED; }
     s->in_bytes = r->input_bytes;
     s->in_head_bytes = s->in_scan_at = s->in_scan_bytes = 0;
-    if (r->input) {
+    s->in_pages = s->in_page = s->in_destructive = 0;
+    if (r->in_kind == IMPB_IN_GIF) {
+        s->in_pages = r->page_count; s->in_page = r->page; s->in_destructive = r->destructive;
+    }
+    if (r->in_kind == IMPB_IN_GIF && r->pages) {
+        size_t packed = 0;
+        rc = pack_gif(c, r->pages, r->page_count, &packed);
+        if (rc != IMP_OK) return rc;
+        s->in_bytes = packed;
+    } else if (r->input) {
         /* a JPEG goes in with its scan out of the byte stuffing (the broker's lanes then make no pass over it: its bytes
          * go to the device from this slot); $IMPGPU_BROKER_PREPARE=0 copies every file as it is */
         size_t head = 0, sat = 0, sn = 0, total = 0;
@@ -383,6 +441,12 @@ int impgpu_client_run(impgpu_client* c, const impgpu_client_request* r, impgpu_c
     a->data = c->data + s->out_offset; a->bytes = (size_t)s->out_bytes;
     a->width = s->out_w; a->height = s->out_h; a->channels = s->out_c; a->row_step = s->out_step;
     a->brightness = s->brightness; a->batch_size = s->batch_size; a->broker_us = s->broker_us;
+    a->frames = s->out_frames > 1 ? s->out_frames : 1;
+    a->frame_stride = (size_t)s->out_frame_stride;
+    if (a->frames > 1 && (s->out_frame_stride > s->out_bytes || (uint64_t)(a->frames - 1) > s->out_bytes / (s->out_frame_stride ? s->out_frame_stride : 1))) {
+        unmap(c);
+        return fail("the broker's answer does not fit its slot");
+    }
     s->error[sizeof s->error - 1] = 0;
     a->error = s->error;
     return IMP_OK;

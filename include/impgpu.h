@@ -137,6 +137,9 @@ int   impgpu_image_download_pinned(const impgpu_image* image, unsigned char* dat
  * (bpp 32) or B,G,R with alpha dropped (bpp 24), written into the encoder's bitmap; the repack runs on the device. */
 int   impgpu_image_upload_fi32(const unsigned char* bits, int width, int height, int pitch, impgpu_image** out);
 int   impgpu_image_download_fi(const impgpu_image* image, int bpp, unsigned char* bits, int pitch);   /* syncs */
+/* download_fi for every frame of an album (SaveGIF's per-frame IplToFI32, advancedio.c:350): frame i into bits[i] with
+ * pitches[i] bytes per row; all repacks and the copy are enqueued, then ONE wait.  A single image is an album of one. */
+int   impgpu_album_download_fi(const impgpu_image* album, int bpp, unsigned char* const* bits, const int* pitches);
 /* The decode itself moved in front of the operators: IplImage* image = cvDecodeImage(&rawencoded, -1)   bridge.c:545-552
  * for a JPEG blob (SIG_JPG, bridge.c:376-378), i.e. libjpeg with its default parameters (ISLOW IDCT, fancy upsampling)
  * and OpenCV's R/B swap.  The compressed bytes cross the link instead of the pixels; Huffman decoding, dequantisation,
@@ -569,6 +572,18 @@ typedef struct impgpu_gif_page {
 int impgpu_gif_compose(const impgpu_gif_page* pages, int count, int destructive, int page, impgpu_image** frames);
 /* the same frames as ONE album handle (see impgpu_album_upload): what RunJob's operator segment then runs on */
 int impgpu_gif_compose_album(const impgpu_gif_page* pages, int count, int destructive, int page, impgpu_image** album);
+/* MANY files, ONE compose launch (what the broker does with the GIF uploads of a batch).  albums[i] / codes[i] are exactly
+ * what impgpu_gif_compose_album(sets[i].pages, sets[i].count, sets[i].destructive, sets[i].page, &albums[i]) gives alone,
+ * pixel for pixel; an entry that call refuses gets its code alone (albums[i] = NULL) and changes no other entry.  All
+ * accepted entries' page tables, palettes and indices travel in one staging blob -- one upload, built in pinned memory and
+ * sent in pieces while the rest is still being copied in -- and one launch
+ * (k_gif_compose_mix, a descriptor per album) composes them: *launches (may be NULL) is 1 when any entry was accepted and
+ * 0 otherwise.  Only a blob that would pass $IMPGPU_STAGE_CAP_MB is cut, at an entry: one upload and launch per group, in
+ * entry order.  count is 0..256; NULL arrays with count > 0 or a count outside the range return IMP_ERROR_INVALID_ARGS
+ * with nothing enqueued; without an env the call returns IMP_ERROR_DEVICE and so does every codes[i].  Asynchronous like
+ * the lone call: the page memory is read before it returns. */
+typedef struct impgpu_gif_set { const impgpu_gif_page* pages; int count, destructive, page; } impgpu_gif_set;
+int impgpu_batch_gif_compose(const impgpu_gif_set* sets, int count, impgpu_image** albums, int* codes, int* launches);
 
 /* ---- batch entry points (benchmark / multi-frame albums: bridge.c:578,591,608,632).
  *      `count` frames of identical geometry, frame i at base + i*frame_stride bytes,

@@ -39,7 +39,10 @@ extern "C" {
 #endif
 
 #define IMPB_MAGIC        0x42504D49u     /* "IMPB" */
-#define IMPB_VERSION      2u              /* 2: a JPEG file may arrive with its scan unstuffed (in_head_bytes, in_scan_at, in_scan_bytes) */
+#define IMPB_VERSION      3u              /* 2: a JPEG file may arrive with its scan unstuffed (in_head_bytes, in_scan_at, in_scan_bytes);
+                                           * 3: GIF pages and FreeImage bits come in, albums and FreeImage bitmaps go out (IMPB_IN_GIF, IMPB_IN_FI32,
+                                           *    IMPB_OUT_FI, out_frames) -- additive: every request of version 2 is written and answered as before */
+#define IMPB_MAX_GIF_PAGES 4096
 #define IMPB_MAX_SLOTS    256
 #define IMPB_TEXT_BYTES   3072            /* the job's strings, NUL-separated */
 #define IMPB_MAX_FILTERS  32
@@ -49,11 +52,30 @@ extern "C" {
 enum { IMPB_FREE = 0, IMPB_CLAIMED = 1, IMPB_SUBMITTED = 2, IMPB_TAKEN = 3, IMPB_DONE = 4 };
 /* what the worker hands over / wants back */
 enum { IMPB_IN_FILE = 0 /* a JPEG or PNG file */, IMPB_IN_FRAME = 1 /* decoded pixels (host fallback decoders) */,
-       IMPB_IN_WATERMARK = 2 /* pixels of a location's overlay: registered, answer = its id */ };
-enum { IMPB_OUT_JPEG = 0 /* cvEncodeImage(".jpg"), bridge.c:704 */, IMPB_OUT_FRAME = 1 /* pixels for a host encoder */,
+       IMPB_IN_WATERMARK = 2 /* pixels of a location's overlay: registered, answer = its id */,
+       IMPB_IN_GIF = 3 /* the pages of a GIF as LoadGIF walks them (advancedio.c:128-259): in_pages impb_gif_page records
+                        * at the front of the data area, then the index planes and palettes they point to; in_page and
+                        * in_destructive are impgpu_gif_compose_album's arguments.  The answer's image is the ALBUM */,
+       IMPB_IN_FI32 = 4 /* LoadSingle's 32-bit bitmap (advancedio.c:295-318), bottom-up as FreeImage holds it: in_w, in_h,
+                         * in_step = its pitch; uploaded with impgpu_image_upload_fi32 */ };
+enum { IMPB_OUT_JPEG = 0 /* cvEncodeImage(".jpg"), bridge.c:704 */,
+       IMPB_OUT_FRAME = 1 /* pixels for a host encoder: EVERY frame of an album, top-down, out_step bytes per row,
+                           * out_frame_stride bytes apart (out_frames of them; 1 for a single frame, placed as always) */,
        IMPB_OUT_INFO = 2 /* width, height, brightness (bridge.c:283-300) */,
        IMPB_OUT_ASCII = 3 /* the text exit, ASCII() of filters.c:486-522 (bridge.c:669-670) */,
-       IMPB_OUT_PNG = 4 /* cvEncodeImage(".png"), bridge.c:704; `quality` = the compression level */ };
+       IMPB_OUT_PNG = 4 /* cvEncodeImage(".png"), bridge.c:704; `quality` = the compression level */,
+       IMPB_OUT_FI = 5 /* every frame as IplToFI32 / IplToFI24 leave it (advancedio.c:65-101): `quality` = the bpp (24 or
+                        * 32), bottom-up, out_step = (out_w * bpp / 8 + 3) & ~3 bytes per row, out_c = bpp / 8,
+                        * out_frame_stride apart (impgpu_album_download_fi) */ };
+/* JPEG, PNG, INFO and ASCII answers of an album mean its frame 0, as the library defines (impgpu.h, "An ALBUM"). */
+
+/* One page of an IMPB_IN_GIF request.  Offsets count from the start of the slot's data area; the index plane is
+ * pitch * height bytes in FreeImage's scanline order, the palette 1024 bytes (256 RGBQUADs), both inside in_bytes.
+ * The broker copies the table out once and checks every record (csrc/imp_broker_check.h) before anything reads through it. */
+typedef struct {
+    uint64_t indices_at, palette_at;
+    int32_t  width, height, pitch, left, top, dispose, transparency_key, pad;
+} impb_gif_page;
 /* answer codes besides IMP_*: the broker did not take the file (not a JPEG/PNG the device decodes, or damaged) -- the
  * worker decodes on the host as before and comes back with IMPB_IN_FRAME.  Which files the device decodes is the
  * broker's to say: `impgpu_broker --jpeg-accept progressive` takes progressive (SOF2) JPEG uploads too -- they reach it
@@ -110,6 +132,10 @@ typedef struct {
     float    brightness;
     int32_t  batch_size;                /* how many requests shared the launches this one rode in (diagnostic) */
     uint32_t broker_us;                 /* TAKEN -> DONE, microseconds (diagnostic) */
+    /* ---- version 3 (request: IMPB_IN_GIF; answer: frames) ---- */
+    int32_t  in_pages, in_page, in_destructive;
+    int32_t  out_frames;                /* frames in the answer (IMPB_OUT_FRAME / IMPB_OUT_FI of an album: all of them; else 1) */
+    uint64_t out_frame_stride;          /* bytes from one frame of the answer to the next */
     char     error[120];
     char     text[IMPB_TEXT_BYTES];
 } impb_slot_fields;
@@ -131,6 +157,12 @@ typedef struct {
     int                  out_kind;      /* IMPB_OUT_* */
     int                  quality;
     const char*          ascii_args;    /* IMPB_OUT_ASCII (NULL = "") */
+    /* IMPB_IN_GIF (at the end: a zero-initialised request of an older caller is what it was).  pages != NULL: the client
+     * packs them into the slot (impgpu_client_pack_gif).  pages == NULL and input == NULL: the caller has packed them ahead of
+     * time, input_bytes is what impgpu_client_pack_gif returned and page_count its count.  IMPB_IN_FI32 uses input,
+     * input_bytes, width, height and step (= the FreeImage pitch) like a frame. */
+    const impgpu_gif_page* pages;
+    int                  page_count, destructive, page;
 } impgpu_client_request;
 
 typedef struct {
@@ -142,6 +174,8 @@ typedef struct {
     int                  batch_size;
     unsigned             broker_us;
     const char*          error;
+    int                  frames;        /* IMPB_OUT_FRAME / IMPB_OUT_FI: frames at data, frame_stride bytes apart (1 otherwise) */
+    size_t               frame_stride;
 } impgpu_client_answer;
 
 /* name = NULL: $IMPGPU_BROKER, else IMPB_DEFAULT_NAME.  IMP_ERROR_DEVICE when no live broker serves the segment (the
@@ -151,6 +185,14 @@ void        impgpu_client_detach(impgpu_client** client);
 /* where a caller that can read its input straight into shared memory puts it (request.input = NULL then); NULL when
  * `bytes` does not fit a slot */
 void*       impgpu_client_input_buffer(impgpu_client* client, size_t bytes);
+/* The pages of a GIF into the input buffer, as an IMPB_IN_GIF request carries them: `count` impb_gif_page records, then
+ * the palettes (each distinct palette POINTER once) and the index planes.  A plane keeps its rows and is re-pitched to the
+ * smaller of its own pitch and the 4-byte multiple that holds width + 1 bytes -- FreeImage's pitch as it is; the byte at
+ * column `width` stays because the compositing walk reads it (impgpu.h, GIF hand-over).  *bytes = the input's size.  For
+ * callers whose page memory does not live until the round trip (LoadGIF unlocks its pages); impgpu_client_run does the
+ * same for request.pages.  IMP_ERROR_MALLOC_FAILED when it does not fit a slot, IMP_ERROR_INVALID_ARGS for pages no
+ * compose call takes (NULL pointers, sizes <= 0, pitch < width, count outside 1..IMPB_MAX_GIF_PAGES). */
+int         impgpu_client_pack_gif(impgpu_client* client, const impgpu_gif_page* pages, int count, size_t* bytes);
 /* One request, synchronously (RunJob, bridge.c:302): returns IMP_OK when the broker answered -- the request's own verdict
  * is answer->code -- and IMP_ERROR_DEVICE when it could not be reached, died meanwhile, or did not answer within
  * $IMPGPU_BROKER_TIMEOUT_MS (default 10000); IMP_ERROR_MALLOC_FAILED when the input does not fit a slot (the worker then takes its in-process path). */

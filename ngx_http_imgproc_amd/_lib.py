@@ -97,6 +97,10 @@ class CGifPage(C.Structure):
     ]
 
 
+class CGifSet(C.Structure):                            # impgpu_gif_set
+    _fields_ = [("pages", C.POINTER(CGifPage)), ("count", C.c_int), ("destructive", C.c_int), ("page", C.c_int)]
+
+
 P = C.c_void_p
 PP = C.POINTER(C.c_void_p)
 IP = C.POINTER(C.c_int)
@@ -156,6 +160,8 @@ SIGNATURES = {
     "impgpu_image_download_fi": (C.c_int, [P, C.c_int, P, C.c_int]),
     "impgpu_gif_compose": (C.c_int, [C.POINTER(CGifPage), C.c_int, C.c_int, C.c_int, PP]),
     "impgpu_gif_compose_album": (C.c_int, [C.POINTER(CGifPage), C.c_int, C.c_int, C.c_int, PP]),
+    "impgpu_batch_gif_compose": (C.c_int, [C.POINTER(CGifSet), C.c_int, PP, IP, IP]),
+    "impgpu_album_download_fi": (C.c_int, [P, C.c_int, PP, IP]),
     "impgpu_image_clone": (C.c_int, [P, PP]),
     "impgpu_image_download": (C.c_int, [P, P, C.c_int]),
     "impgpu_batch_download": (C.c_int, [PP, C.c_int, PP, IP]),

@@ -132,7 +132,7 @@ def build_broker(force=False, verbose=False):
             print(" ".join(cmd))
         subprocess.check_call(cmd)
 
-    hdrs = [os.path.join(INCLUDE, "impgpu_broker.h"), os.path.join(INCLUDE, "impgpu.h")]
+    hdrs = [os.path.join(INCLUDE, "impgpu_broker.h"), os.path.join(INCLUDE, "impgpu.h"), os.path.join(CSRC, "imp_broker_check.h")]
     if force or _stale(CLIENT_LIB, [CLIENT_SRC] + hdrs):
         run(["gcc", "-std=gnu99", "-O2", "-Wall", "-Wextra", "-fPIC", "-shared", "-I", INCLUDE, CLIENT_SRC, "-o", CLIENT_LIB, "-lrt"])
     src = os.path.join(CSRC, "imp_broker.cpp")

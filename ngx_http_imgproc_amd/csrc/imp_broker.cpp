@@ -8,16 +8,21 @@
 // A batch is one straight pass: take, prepare, decode, operators, answers, finish --
 //     files          impgpu_batch_decode_jpeg_prepared   cvDecodeImage, bridge.c:545-552
 //                    impgpu_batch_decode_png (_ex with --png-accept all)
+//     GIF pages      impgpu_batch_gif_compose            LoadGIF's compositing, advancedio.c:204-247: all GIFs of the batch
+//                                                        in one upload and one launch; each becomes an album
+//     FreeImage bits impgpu_image_upload_fi32            LoadSingle, advancedio.c:295-318 (one by one, like frames)
 //     operators      impgpu_batch_run_ops                bridge.c:574-656: crop -> resize -> rotate -> watermark -> flatten
 //                                                        chains share one launch per channel count; anything else runs
 //                                                        request by request (impgpu_run_ops) inside the same call
 //     JPEG answers   impgpu_batch_encode_jpeg            cvEncodeImage(".jpg"), bridge.c:704
 //     PNG answers    impgpu_batch_encode_png             cvEncodeImage(".png"), bridge.c:704
 //     pixel answers  impgpu_batch_download               for the host encoders (PNG, WebP, FreeImage formats)
+//     album answers  impgpu_album_download               every frame of an album, per request
+//     FreeImage ans. impgpu_album_download_fi            IplToFI32 / IplToFI24, advancedio.c:65-101, every frame
 //     json answers   impgpu_batch_calc_perceived_brightness   Info(), bridge.c:283-300 (two or more; one: the lone call)
 //     text answers   impgpu_batch_ascii                  ASCII(), bridge.c:668-676 (likewise)
 // Nothing a worker writes into its slot is trusted further than a request is: the request record is copied out of shared
-// memory once and validated (sizes against the slot, offsets against the text area, frame geometry against the bytes), and
+// memory once and validated (sizes against the slot, offsets against the text area, frame geometry and GIF page records against the bytes), and
 // the answer's placement is the broker's own: it is written to the slot for the worker and never read back from there.
 //
 //   impgpu_broker [--name /impgpu-broker-0] [--device 0] [--slots 64] [--slot-mb 32] [--register-mb 8] [--threads 2] [--batch 64]
@@ -25,6 +30,7 @@
 // --supervise: this process only forks and watches; the child is the broker.  A child that dies (a lost device, a bug) is
 // replaced by a FRESH child -- fork() from a parent that never touched the GPU, no exec of a process that did.
 #include <impgpu_broker.h>
+#include "imp_broker_check.h"
 
 #include <errno.h>
 #include <fcntl.h>
@@ -189,7 +195,11 @@ struct Req {
     uint64_t out_offset = 0, out_bytes = 0;
     uint64_t cap = 0;                   // bytes from out_offset to the end of the slot's data area (0: none)
     int32_t out_w = 0, out_h = 0, out_c = 0, out_step = 0;
+    int32_t out_frames = 0;
+    uint64_t out_frame_stride = 0;
     float brightness = 0;
+    std::vector<impb_gif_page> pages;   // IMPB_IN_GIF: the record table, copied out and checked (imp_broker_check.h)
+    std::vector<impgpu_gif_page> gif;   // ... and as the library takes it: pointers into the slot's input
     bool fits(uint64_t need) const { return cap > 0 && cap >= need; }
 };
 
@@ -210,7 +220,7 @@ void prepare(Req& r, const Segment& S) {
     impb_slot_fields& q = r.q;
     q.text[IMPB_TEXT_BYTES - 1] = 0;
     if (q.in_bytes > S.slot_bytes) return fail(r, IMP_ERROR_INVALID_ARGS, IMP_STEP_VALIDATE, "in_bytes past the slot");
-    if (q.in_kind > IMPB_IN_WATERMARK || q.out_kind > IMPB_OUT_PNG) return fail(r, IMP_ERROR_INVALID_ARGS, IMP_STEP_VALIDATE, "unknown kind");
+    if (q.in_kind > IMPB_IN_FI32 || q.out_kind > IMPB_OUT_FI) return fail(r, IMP_ERROR_INVALID_ARGS, IMP_STEP_VALIDATE, "unknown kind");
     if (q.filter_count < 0 || q.filter_count > IMPB_MAX_FILTERS || !text_ok(q, q.crop_at) || !text_ok(q, q.gravity_at) || !text_ok(q, q.resize_at) || !text_ok(q, q.ascii_at))
         return fail(r, IMP_ERROR_INVALID_ARGS, IMP_STEP_VALIDATE, "bad text offsets");
     for (int i = 0; i < q.filter_count; i++) {
@@ -222,7 +232,23 @@ void prepare(Req& r, const Segment& S) {
             q.in_scan_bytes > q.in_bytes - q.in_scan_at || q.in_bytes - q.in_scan_at - q.in_scan_bytes < IMPGPU_JPEG_SCAN_TAIL)
             return fail(r, IMP_ERROR_INVALID_ARGS, IMP_STEP_VALIDATE, "prepared file: offsets past its bytes");
     }
-    if (q.in_kind != IMPB_IN_FILE) {
+    if (q.out_kind == IMPB_OUT_FI && q.quality != 24 && q.quality != 32) return fail(r, IMP_ERROR_INVALID_ARGS, IMP_STEP_VALIDATE, "a FreeImage answer is 24 or 32 bits");
+    if (q.in_kind == IMPB_IN_GIF) {
+        int frames = 0;
+        uint64_t frame_bytes = 0;
+        const impb::GifVerdict v = impb::check_gif(r.in, q.in_bytes, S.slot_bytes, q.in_pages, q.in_page, &r.pages, &frames, &frame_bytes);
+        if (v == impb::GIF_INVALID) return fail(r, IMP_ERROR_INVALID_ARGS, IMP_STEP_DECODE, "GIF pages: a record does not match the input's bytes");
+        if (v == impb::GIF_TOO_LARGE) return fail(r, IMP_ERROR_MALLOC_FAILED, IMP_STEP_ENCODE, "answer does not fit the slot");
+        r.gif.resize(r.pages.size());
+        for (size_t f = 0; f < r.pages.size(); f++) {
+            const impb_gif_page& p = r.pages[f];
+            r.gif[f] = impgpu_gif_page{r.in + p.indices_at, p.width, p.height, p.pitch, p.left, p.top, p.dispose, p.transparency_key, r.in + p.palette_at};
+        }
+    } else if (q.in_kind == IMPB_IN_FI32) {
+        const long long need = (long long)q.in_step * q.in_h;
+        if (q.in_w <= 0 || q.in_h <= 0 || (long long)q.in_step < (long long)q.in_w * 4 || need <= 0 || (unsigned long long)need > q.in_bytes)
+            return fail(r, IMP_ERROR_INVALID_ARGS, IMP_STEP_VALIDATE, "bitmap geometry does not match its bytes");
+    } else if (q.in_kind != IMPB_IN_FILE) {
         const long long need = (long long)q.in_step * q.in_h;
         if (q.in_w <= 0 || q.in_h <= 0 || (q.in_c != 1 && q.in_c != 3 && q.in_c != 4) || (long long)q.in_step < (long long)q.in_w * q.in_c ||
             need <= 0 || (unsigned long long)need > q.in_bytes)
@@ -266,6 +292,8 @@ struct Worker {
     std::vector<size_t> png_sizes;
     std::vector<impgpu_job> jobs;
     std::vector<const impgpu_config*> cfgs;
+    std::vector<size_t> gifs;
+    std::vector<impgpu_gif_set> gif_sets;
 
     Worker(const Segment& s, const Options& o, int i) : S(s), O(o), id(i) {}
 
@@ -291,6 +319,7 @@ struct Worker {
         s->out_offset = r.out_offset; s->out_bytes = r.out_bytes;
         s->out_w = r.out_w; s->out_h = r.out_h; s->out_c = r.out_c; s->out_step = r.out_step;
         s->brightness = r.brightness;
+        s->out_frames = r.out_frames; s->out_frame_stride = r.out_frame_stride;
         s->batch_size = (int32_t)batch_size;
         std::snprintf(s->error, sizeof s->error, "%s", r.err.c_str());
         s->broker_us = (uint32_t)(now_us() - r.t_taken);
@@ -481,12 +510,35 @@ struct Worker {
             }
             decoded(pngs, impgpu_batch_decode_png_ex(png_blobs.data(), png_sizes.data(), (int)m, O.png_accept, imgs.data(), codes.data(), nullptr));
         }
+        // every GIF of the batch: one upload of all their pages and ONE compose launch (advancedio.c:204-247), behind the file
+        // decodes on the lane's stream.  The answer's image is the album; a page request (in_page >= 0) makes an album of one.
+        gifs.clear();
+        for (size_t k = 0; k < n; k++) if (!reqs[k].done && reqs[k].q.in_kind == IMPB_IN_GIF) gifs.push_back(k);
+        if (!gifs.empty()) {
+            const size_t m = gifs.size();
+            gif_sets.resize(m);
+            imgs.assign(m, nullptr);
+            codes.assign(m, IMP_OK);
+            for (size_t j = 0; j < m; j++) {
+                const Req& r = reqs[gifs[j]];
+                gif_sets[j] = impgpu_gif_set{r.gif.data(), (int)r.gif.size(), r.q.in_destructive, r.q.in_page};
+            }
+            // (a lane's batch is at most --batch <= 256 requests, which is what the call takes)
+            const int rc = impgpu_batch_gif_compose(gif_sets.data(), (int)m, imgs.data(), codes.data(), nullptr);
+            for (size_t j = 0; j < m; j++) {
+                Req& r = reqs[gifs[j]];
+                const int c = rc != IMP_OK ? rc : codes[j];
+                if (c == IMP_OK) r.img = imgs[j];
+                else fail(r, c, IMP_STEP_DECODE, c == IMP_ERROR_DEVICE ? impgpu_last_error() : "pages the compose call does not take");
+            }
+        }
         for (size_t k = 0; k < n; k++) {
             Req& r = reqs[k];
             if (r.done || r.img) continue;
             int rc = IMP_OK;
             if (r.q.in_kind == IMPB_IN_FILE) { fail(r, IMPB_NOT_TAKEN, IMP_STEP_DECODE, "neither JPEG nor PNG"); continue; }
-            rc = impgpu_image_upload(r.in, r.q.in_w, r.q.in_h, r.q.in_c, r.q.in_step, &r.img);
+            if (r.q.in_kind == IMPB_IN_FI32) rc = impgpu_image_upload_fi32(r.in, r.q.in_w, r.q.in_h, r.q.in_step, &r.img);      // LoadSingle, advancedio.c:310-318
+            else rc = impgpu_image_upload(r.in, r.q.in_w, r.q.in_h, r.q.in_c, r.q.in_step, &r.img);
             if (rc != IMP_OK) { fail(r, rc, IMP_STEP_DECODE, impgpu_last_error()); continue; }
             if (r.q.in_kind == IMPB_IN_WATERMARK) {             // PrepareWatermark (bridge.c:199-237): kept, answered with its id
                 std::lock_guard<std::mutex> lk(g_marks.mu);
@@ -529,7 +581,7 @@ struct Worker {
         g_us_ops += (uint64_t)(t3 - t2);
         // ---- answers (bridge.c:659-710): placed right behind the request's input in its slot
         std::map<int, std::vector<size_t>> by_quality;
-        std::vector<size_t> raw, png, info, text;
+        std::vector<size_t> raw, many, png, info, text;
         for (size_t k = 0; k < n; k++) {
             Req& r = reqs[k];
             if (r.done) continue;
@@ -559,12 +611,20 @@ struct Worker {
                 if (!r.fits(bound)) { fail(r, IMP_ERROR_MALLOC_FAILED, IMP_STEP_ENCODE, "answer does not fit the slot"); continue; }
                 png.push_back(k);
             } else {
+                // pixels: every frame of an album (an album of one, a single frame and a FreeImage answer alike: `many`),
+                // a single frame for a host encoder as before (`raw`)
                 r.step = IMP_STEP_ENCODE;
-                const uint64_t need = (uint64_t)impgpu_image_step(r.img) * (uint64_t)r.out_h;
-                if (!r.fits(need)) { fail(r, IMP_ERROR_MALLOC_FAILED, IMP_STEP_ENCODE, "answer does not fit the slot"); continue; }
-                r.out_step = impgpu_image_step(r.img);
-                r.out_bytes = need;
-                raw.push_back(k);
+                const bool fi = r.q.out_kind == IMPB_OUT_FI;
+                const uint64_t frames = (uint64_t)impgpu_album_count(r.img);
+                const uint64_t row = fi ? (((uint64_t)r.out_w * (uint64_t)(r.q.quality / 8) + 3) & ~uint64_t(3)) : (uint64_t)impgpu_image_step(r.img);
+                const uint64_t each = row * (uint64_t)r.out_h;
+                if (!frames || !each || !r.fits(each) || frames > r.cap / each) { fail(r, IMP_ERROR_MALLOC_FAILED, IMP_STEP_ENCODE, "answer does not fit the slot"); continue; }
+                r.out_step = (int32_t)row;
+                r.out_bytes = each * frames;
+                r.out_frames = (int32_t)frames; r.out_frame_stride = each;
+                if (fi) r.out_c = r.q.quality / 8;
+                if (fi || frames > 1) many.push_back(k);
+                else raw.push_back(k);
             }
         }
         // one call per JPEG quality, the batch's most common one last; then the PNG answers, then pixels for host encoders
@@ -584,6 +644,17 @@ struct Worker {
         answer(raw, [](const impgpu_image* const* im, int m, unsigned char* const* outs, const size_t*, const int* row_steps, size_t*, int*) {
             return impgpu_batch_download(im, m, outs, row_steps);
         });
+        // album and FreeImage answers: per request, every frame in one transfer and one wait (impgpu_album_download[_fi])
+        for (size_t k : many) {
+            Req& r = reqs[k];
+            std::vector<unsigned char*> at((size_t)r.out_frames);
+            std::vector<int> row_steps((size_t)r.out_frames, r.out_step);
+            for (size_t f = 0; f < at.size(); f++) at[f] = S.slot_data(r.slot) + r.out_offset + f * r.out_frame_stride;
+            const int rc = r.q.out_kind == IMPB_OUT_FI ? impgpu_album_download_fi(r.img, r.q.quality, at.data(), row_steps.data())
+                                                       : impgpu_album_download(r.img, at.data(), row_steps.data());
+            if (rc != IMP_OK) { fail(r, rc, IMP_STEP_ENCODE, impgpu_last_error()); continue; }
+            r.code = IMP_OK; r.done = true;
+        }
         if (most) answer(by_quality[common], jpeg(common));
         // The json and text exits go LAST.  Each of the calls above and below ends in a wait of its own, and the lane's stream
         // is in order, so the order changes nobody's device time -- only how long the host sits in each wait.  The encoders'

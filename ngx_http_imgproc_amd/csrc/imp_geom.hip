@@ -200,15 +200,13 @@ int launch_pack_fi(const View& v, int bpp, uint8_t* dst, int dpitch, hipStream_t
     return IMP_OK;
 }
 
-// LoadGIF's compositing loop (advancedio.c:204-247), one lane per canvas pixel walking the pages in order: the
-// `master` index canvas of the destructive mode is that pixel's register.  Same definitions as the oracle where the
-// reference is undefined (read one byte past the frame row at x == left + w; index < 0 -> colour 0).
-__global__ __launch_bounds__(256) void k_gif_compose(const uint8_t* __restrict__ blob, const GifPageDev* __restrict__ pg,
-                                                     uint8_t* const* __restrict__ outs, int npages, int cw, int ch,
-                                                     int ostep, int destructive, int only) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)cw * ch) return;
-    const int y = (int)(idx / cw), x = (int)(idx - (long long)y * cw);
+// LoadGIF's compositing loop (advancedio.c:204-247) for the canvas pixel (x, y), walking the pages in order: the `master`
+// index canvas of the destructive mode is that pixel's register.  Same definitions as the oracle where the reference is
+// undefined (read one byte past the frame row at x == left + w; index < 0 -> colour 0).  Shared by k_gif_compose (one file)
+// and k_gif_compose_mix (many): `blob` is what the pages' idx_off / pal_off count from.
+__device__ __forceinline__ void gif_walk(const uint8_t* __restrict__ blob, const GifPageDev* __restrict__ pg,
+                                         uint8_t* const* __restrict__ outs, int npages, int ostep, int destructive, int only,
+                                         int x, int y) {
     int master = 0;
     for (int f = 0; f < npages; f++) {
         const GifPageDev p = pg[f];
@@ -240,12 +238,73 @@ __global__ __launch_bounds__(256) void k_gif_compose(const uint8_t* __restrict__
     }
 }
 
+// one file: one lane per canvas pixel
+__global__ __launch_bounds__(256) void k_gif_compose(const uint8_t* __restrict__ blob, const GifPageDev* __restrict__ pg,
+                                                     uint8_t* const* __restrict__ outs, int npages, int cw, int ch,
+                                                     int ostep, int destructive, int only) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)cw * ch) return;
+    const int y = (int)(idx / cw), x = (int)(idx - (long long)y * cw);
+    gif_walk(blob, pg, outs, npages, ostep, destructive, only, x, y);
+}
+
 int launch_gif_compose(const uint8_t* blob, const GifPageDev* pages, uint8_t* const* outs, int npages, int cw, int ch,
                        int ostep, int destructive, int only, hipStream_t s) {
     const dim3 grid((unsigned)(((long long)cw * ch + 255) / 256)), block(256);
     hipLaunchKernelGGL(k_gif_compose, grid, block, 0, s, blob, pages, outs, npages, cw, ch, ostep, destructive, only);
     IMP_HIP(hipGetLastError());
     return IMP_OK;
+}
+
+// ---- many files, one launch (impgpu_batch_gif_compose) ----
+// A descriptor per album, dealt like k_geom_mix's; a workgroup covers 256 canvas pixels of ONE album and runs gif_walk for
+// each.  Everything the walk reads travels behind the descriptor table in the same allocation (mix_launch's `staged`), so
+// the table's address is what every offset -- the descriptors' and the pages' -- counts from.
+struct GifMixDesc {
+    long long pages_off, outs_off;       // GifPageDev[npages], uint8_t*[frames written]
+    int npages, cw, ch, ostep, destructive, only;
+    int first, nblk;
+};
+
+__global__ __launch_bounds__(256) void k_gif_compose_mix(const GifMixDesc* __restrict__ d, MixIndex ix) {
+    int blk;
+    const int i = mix_pick(d, ix, &blk);
+    if (i < 0) return;
+    const int cw = d[i].cw;
+    const long long idx = (long long)blk * 256 + threadIdx.x;
+    if (idx >= (long long)cw * d[i].ch) return;
+    const int y = (int)(idx / cw), x = (int)(idx - (long long)y * cw);
+    const uint8_t* base = (const uint8_t*)d;
+    gif_walk(base, (const GifPageDev*)(base + d[i].pages_off), (uint8_t* const*)(base + d[i].outs_off), d[i].npages,
+             d[i].ostep, d[i].destructive, d[i].only, x, y);
+}
+
+size_t gif_mix_table_bytes(int count) { return mix_blob_offset<GifMixDesc>((size_t)count); }
+
+int launch_gif_compose_mixed(const GifMixItem* items, int count, const MixStaged& staged, size_t bytes, hipStream_t s) {
+    // (whatever is refused here: the pieces already sent are fenced and the block goes back)
+    auto refuse = [&]() { (void)stage_upload_part(staged.token, 0, staged.dev, 0, true); dev_free(staged.dev); return IMP_ERROR_INVALID_ARGS; };
+    if (count <= 0 || !items || bytes < gif_mix_table_bytes(count)) return refuse();
+    std::vector<GifMixDesc> v;
+    v.reserve((size_t)count);
+    long long blocks = 0;
+    for (int i = 0; i < count; i++) {                      // nothing is launched unless every item is well-formed
+        const GifMixItem& it = items[i];
+        const size_t nout = it.only >= 0 ? 1 : (size_t)it.npages;
+        if (it.npages <= 0 || it.only >= it.npages || !view_fits(it.cw, it.ch, 4, it.ostep) || (it.ostep & 3) || ((it.pages_off | it.outs_off) & 7) ||
+            it.pages_off + (size_t)it.npages * sizeof(GifPageDev) > bytes || it.outs_off + nout * sizeof(uint8_t*) > bytes)
+            return refuse();
+        GifMixDesc d{};
+        d.pages_off = (long long)it.pages_off; d.outs_off = (long long)it.outs_off;
+        d.npages = it.npages; d.cw = it.cw; d.ch = it.ch; d.ostep = it.ostep; d.destructive = it.destructive ? 1 : 0; d.only = it.only;
+        d.nblk = (int)(((long long)it.cw * it.ch + 255) / 256);
+        blocks += d.nblk;
+        v.push_back(d);
+    }
+    if (blocks * 8 > 0x7fffffffLL) return refuse();                    // (the grid is 8 x the longest list: the caller splits first)
+    return mix_launch(v, [](GifMixDesc& d) { return (long long)d.cw * d.ch * d.npages; }, s, [&](dim3 grid, const GifMixDesc* dev, const MixIndex& ix) {
+        hipLaunchKernelGGL(k_gif_compose_mix, grid, dim3(256), 0, s, dev, ix);
+    }, nullptr, nullptr, &staged);
 }
 
 static GArgs gargs(const Frames& f) {

@@ -72,7 +72,8 @@ int  upload_to(void* dev, const void* host, size_t bytes, hipStream_t s);   // t
 int  stage_begin(size_t bytes, void** host, void** token);
 int  stage_upload(void* token, void* dev, size_t bytes);
 void stage_hold(void* token, bool held);                   // a download enqueued into the buffer is read by a later call: keep it out of circulation until then
-size_t stage_capacity(void* token);                       // bytes the buffer behind `token` really holds (>= what stage_begin was asked for)
+size_t stage_cap();                                       // $IMPGPU_STAGE_CAP_MB in bytes (0: none)
+size_t stage_capacity(void* token);                     // bytes the buffer behind `token` really holds (>= what stage_begin was asked for)
 int  stage_upload_part(void* token, size_t offset, void* dev, size_t bytes, bool last);   // pieces of the same buffer; `last` fences it
 // Pool memory and caller-supplied ("foreign") streams -- the batch entry points.  The pool recycles blocks in the order
 // of the lane's own stream; these keep that sound without a host wait:
@@ -334,6 +335,15 @@ int launch_pack_fi(const View& v, int bpp, uint8_t* dst, int dpitch, hipStream_t
 struct GifPageDev { long long idx_off, pal_off; int w, h, pitch, left, top, dispose, key, pad; };   // offsets into one device blob
 int launch_gif_compose(const uint8_t* blob, const GifPageDev* pages, uint8_t* const* outs, int npages, int cw, int ch,
                        int ostep, int destructive, int only, hipStream_t s);                 // LoadGIF's compositing loop
+// The same for many files in ONE launch (impgpu_batch_gif_compose).  The upload is `bytes` of a pinned staging buffer
+// (MixStaged, below): gif_mix_table_bytes(count) bytes left free in front for the descriptor table, then every item's
+// GifPageDev[npages] at pages_off, its output pointers (one when only >= 0, else npages) at outs_off, and the palettes and
+// index planes the pages' pal_off / idx_off name -- all offsets from the buffer's start.  Everything behind the table is on
+// its way to staged.dev when this is called; the table goes last.  staged.dev is freed here whatever happens.
+struct GifMixItem { size_t pages_off, outs_off; int npages, cw, ch, ostep, destructive, only; };
+struct MixStaged;
+size_t gif_mix_table_bytes(int count);
+int launch_gif_compose_mixed(const GifMixItem* items, int count, const MixStaged& staged, size_t bytes, hipStream_t s);
 // imp_pixel.hip
 int launch_pixel_program(uint8_t* d, long long stride, int w, int h, int c, int step, int count,
                          const PixelProgram& prog, hipStream_t s);
@@ -408,16 +418,27 @@ constexpr size_t mix_blob_offset(size_t n) { return (n * sizeof(D) + 15) & ~size
 // when the launch failed, and the launch's error is the one reported: the rule every mixed launch shares, said here once.
 // `whole`, for blobs of megabytes (the enlargements' tables): the blob with mix_blob_offset<D>(v.size()) bytes left free
 // in front of it -- the table is written there and `whole` is what is uploaded, with no second host copy of the blob.
+// `staged`, for blobs the caller builds in a pinned staging buffer (stage_begin) and sends piece by piece while it builds
+// them (stage_upload_part into `dev`, its own pool block of the whole size): `host` is the buffer, with
+// mix_blob_offset<D>(v.size()) bytes left free in front for the table, which is written there and sent as the LAST piece --
+// the one that fences the buffer.  `dev` is freed behind the launch like any table, also when something failed.
+struct MixStaged { void* host; void* token; void* dev; };
 template <class D, class M, class C, class L>
 int mix_launch(std::vector<D>& v, M desc, C cost, hipStream_t s, L launch, const std::vector<uint8_t>* blob = nullptr,
-               std::vector<uint8_t>* whole = nullptr) {
+               std::vector<uint8_t>* whole = nullptr, const MixStaged* staged = nullptr) {
     if (v.empty()) return IMP_OK;
     std::vector<D> sorted;
     MixIndex ix{};
     int most = 0;
     mix_deal(v, desc, cost, &sorted, &ix, &most);
     void* table = nullptr;
-    if (whole) {
+    if (staged) {
+        std::memcpy(staged->host, sorted.data(), sorted.size() * sizeof(D));
+        int rc = stage_upload_part(staged->token, 0, staged->dev, sorted.size() * sizeof(D), true);
+        if (!rc && !on_lane_stream(s)) rc = stream_join(s);
+        if (rc) { dev_free(staged->dev); return rc; }
+        table = staged->dev;
+    } else if (whole) {
         if (whole->size() < mix_blob_offset<D>(sorted.size())) return IMP_ERROR_INVALID_ARGS;
         std::memcpy(whole->data(), sorted.data(), sorted.size() * sizeof(D));
         if (int rc = upload_small(whole->data(), whole->size(), &table, s)) return rc;
@@ -439,8 +460,8 @@ int mix_launch(std::vector<D>& v, M desc, C cost, hipStream_t s, L launch, const
 // the same for descriptors that hold `first` and `nblk` themselves
 template <class D, class C, class L>
 int mix_launch(std::vector<D>& v, C cost, hipStream_t s, L launch, const std::vector<uint8_t>* blob = nullptr,
-               std::vector<uint8_t>* whole = nullptr) {
-    return mix_launch(v, [](D& d) -> D& { return d; }, cost, s, launch, blob, whole);
+               std::vector<uint8_t>* whole = nullptr, const MixStaged* staged = nullptr) {
+    return mix_launch(v, [](D& d) -> D& { return d; }, cost, s, launch, blob, whole, staged);
 }
 // The descriptor of this workgroup (its index; -1: none, the workgroup returns) and the workgroup's index inside it;
 // `desc(d)` names the part of a descriptor holding `first` and `nblk`, as in mix_deal.  An index rather than a pointer: the

@@ -547,6 +547,13 @@ void image_delete(impgpu_image* im) {
     delete im;
 }
 
+// $IMPGPU_STAGE_CAP_MB in bytes (default 512 MB; 0: no cap): what stage_reserve below trims a buffer back from, and what a
+// batch call keeps one staging blob under (impgpu_batch_gif_compose).
+size_t stage_cap() {
+    const char* s = std::getenv("IMPGPU_STAGE_CAP_MB");
+    return (size_t)(s ? std::atoll(s) : 512) << 20;
+}
+
 // The next staging buffer, free to overwrite and at least `bytes` large.  Two buffers alternate: while the DMA of
 // one request still reads buffer A the host fills buffer B for the next.
 static int stage_reserve(Lane* L, size_t bytes, Staging** out) {
@@ -565,10 +572,7 @@ static int stage_reserve(Lane* L, size_t bytes, Staging** out) {
     // 112 MB) goes back when it is next taken for something a quarter of that cap would hold: a worker does not keep an
     // unswappable gigabyte for life because of one request.  (Here and not after a wait: the caller still reads a download
     // out of the buffer then.)
-    static const size_t trim_cap = [] {
-        const char* s = std::getenv("IMPGPU_STAGE_CAP_MB");
-        return (size_t)(s ? std::atoll(s) : 512) << 20;
-    }();
+    static const size_t trim_cap = stage_cap();
     bool outsized = trim_cap && S->cap > trim_cap && bytes <= trim_cap / 4;
     // ... and below that cap: a buffer of more than 64 MB (one PNG of 4096 x 16384 stages 268 MB for a file that may weigh
     // 260 KB) that the last sixteen requests each used less than an eighth of goes back too -- N workers x lanes x two

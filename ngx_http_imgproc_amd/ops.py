@@ -178,6 +178,16 @@ class Image:
             raise ImpError(rc, "impgpu_album_download")
         return outs
 
+    def frames_fi(self, bpp, pitch=None, fill=0):
+        """Every frame in FreeImage layout (impgpu_album_download_fi: bottom-up, `pitch` bytes per row -- FreeImage's own
+        rule when None) -> (code, list of h x pitch arrays that held `fill` before)."""
+        hh, ww, cc = self.shape
+        pitch = (ww * bpp // 8 + 3) & ~3 if pitch is None else pitch
+        outs = [np.full((hh, pitch), fill, dtype=np.uint8) for _ in range(self.count)]
+        ptrs = (C.c_void_p * len(outs))(*[o.ctypes.data for o in outs])
+        rc = lib.impgpu_album_download_fi(self.h, int(bpp), ptrs, (C.c_int * len(outs))(*[pitch] * len(outs)))
+        return rc, outs
+
     def encode_jpeg(self, quality=95):
         """cvEncodeImage(".jpg", frame, {CV_IMWRITE_JPEG_QUALITY, quality}) (bridge.c:704) on the device -> (code, file bytes or None)."""
         hh, ww, cc = self.shape
@@ -746,10 +756,8 @@ def batch_resize_rotate_watermark(src_ptr, src_stride, sw, sh, sstep, dst_ptr, d
         raise ImpError(rc, "impgpu_batch_resize_rotate_watermark")
 
 
-def gif_compose(pages, destructive=False, page=-1, album=False):
-    """LoadGIF's compositing loop (advancedio.c:204-247) on the device.  pages: dicts with `indices` (h x pitch uint8,
-    FreeImage scanline order), `width`, `left`, `top`, `dispose`, `key`, `palette` (256 x 4 uint8, B,G,R,reserved).
-    Returns (code, [Image ...]): every page, or just the requested one; album=True -> (code, one album Image)."""
+def gif_page_array(pages):
+    """Page dicts (see gif_compose) -> (impgpu_gif_page array, the arrays it points into)."""
     from ._lib import CGifPage
     keep = []
     arr = (CGifPage * max(1, len(pages)))()
@@ -762,6 +770,36 @@ def gif_compose(pages, destructive=False, page=-1, album=False):
         arr[i].left = int(p.get("left", 0)); arr[i].top = int(p.get("top", 0))
         arr[i].dispose = int(p.get("dispose", 0)); arr[i].transparency_key = int(p.get("key", -1))
         arr[i].palette = pal.ctypes.data
+    return arr, keep
+
+
+def batch_gif_compose(sets, count=None):
+    """impgpu_batch_gif_compose: sets = [(pages, destructive, page), ...] (pages as for gif_compose) -> (code, [album Image or
+    None ...], [codes], launches).  `count` overrides the count passed to the library (its argument checks)."""
+    from ._lib import CGifSet
+    n = len(sets)
+    arr = (CGifSet * max(1, n))()
+    keep = []
+    for i, (pages, destructive, page) in enumerate(sets):
+        if pages is not None:
+            pa, k = gif_page_array(pages)
+            keep += [pa, k]
+            arr[i].pages = pa
+            arr[i].count = len(pages)
+        arr[i].destructive, arr[i].page = int(bool(destructive)), int(page)
+    m = max(1, n if count is None else count)
+    outs = (C.c_void_p * m)()
+    codes = (C.c_int * m)(*([-1] * m))
+    launches = C.c_int(-1)
+    rc = lib.impgpu_batch_gif_compose(arr, n if count is None else count, outs, codes, C.byref(launches))
+    return rc, [Image(handle=outs[i]) if outs[i] else None for i in range(n)], list(codes[:n]), launches.value
+
+
+def gif_compose(pages, destructive=False, page=-1, album=False):
+    """LoadGIF's compositing loop (advancedio.c:204-247) on the device.  pages: dicts with `indices` (h x pitch uint8,
+    FreeImage scanline order), `width`, `left`, `top`, `dispose`, `key`, `palette` (256 x 4 uint8, B,G,R,reserved).
+    Returns (code, [Image ...]): every page, or just the requested one; album=True -> (code, one album Image)."""
+    arr, keep = gif_page_array(pages)
     nout = 1 if page >= 0 else len(pages)
     outs = (C.c_void_p * max(1, nout))()
     if album:
