@@ -140,6 +140,19 @@ int   impgpu_image_download_fi(const impgpu_image* image, int bpp, unsigned char
 /* download_fi for every frame of an album (SaveGIF's per-frame IplToFI32, advancedio.c:350): frame i into bits[i] with
  * pitches[i] bytes per row; all repacks and the copy are enqueued, then ONE wait.  A single image is an album of one. */
 int   impgpu_album_download_fi(const impgpu_image* album, int bpp, unsigned char* const* bits, const int* pitches);
+/* impgpu_album_download_fi for `count` handles (0..256; albums and single images mixed) behind ONE wait.
+ * bits[] / pitches[] have one entry per FRAME: handle 0's frames first, in frame order, then handle 1's ...
+ * (sum of impgpu_album_count).  bpps[i] is 24 or 32 per handle.  Every frame of the call is flipped and repacked into one
+ * device block by ONE launch per (source channels, bpp) pair present -- at most four, one when the call is uniform;
+ * *launches (may be NULL) receives the number -- then one copy into pinned staging and one wait (a call whose bitmaps
+ * pass $IMPGPU_STAGE_CAP_MB is cut at a handle into groups in handle order, each with its own copy and wait).  An entry
+ * impgpu_album_download_fi refuses (a NULL handle, which owns no entries of bits[]; fewer than 3 channels; a bpp other
+ * than 24 or 32; a NULL bits entry; a pitch below width * bpp / 8) gets IMP_ERROR_INVALID_ARGS in codes[i] alone and
+ * nothing of it is touched.  Returns IMP_ERROR_INVALID_ARGS for NULL arrays with count > 0 or a count outside 0..256
+ * (before any device is looked for; count = 0 is IMP_OK there too), IMP_ERROR_DEVICE without an env (every codes[i] says so too), otherwise IMP_OK with
+ * the verdicts in codes[].  Only the first width * bpp / 8 bytes of each of the caller's rows are written. */
+int   impgpu_batch_download_fi(const impgpu_image* const* images, const int* bpps, int count,
+                               unsigned char* const* bits, const int* pitches, int* codes, int* launches);
 /* The decode itself moved in front of the operators: IplImage* image = cvDecodeImage(&rawencoded, -1)   bridge.c:545-552
  * for a JPEG blob (SIG_JPG, bridge.c:376-378), i.e. libjpeg with its default parameters (ISLOW IDCT, fancy upsampling)
  * and OpenCV's R/B swap.  The compressed bytes cross the link instead of the pixels; Huffman decoding, dequantisation,
@@ -402,6 +415,13 @@ int   impgpu_batch_download(const impgpu_image* const* images, int count, unsign
 int   impgpu_album_upload(const unsigned char* const* datas, int count, int width, int height, int channels,
                           const int* steps, impgpu_image** out);
 int   impgpu_album_download(const impgpu_image* album, unsigned char* const* datas, const int* steps);   /* one wait */
+/* impgpu_album_download for `count` handles (0..256; albums and single images mixed) the same way: all copies enqueued,
+ * ONE wait.  datas[] / steps[] have one entry per FRAME, handle 0's frames first (sum of impgpu_album_count); steps must
+ * be given.  A handle that call refuses gets IMP_ERROR_INVALID_ARGS in codes[i] alone; the fault point it enters
+ * (IMP_STEP_ENCODE) is entered per accepted handle, in handle order, before anything is enqueued.  The staging cap cuts
+ * the call as it cuts impgpu_batch_download_fi; the return values are that call's too. */
+int   impgpu_batch_album_download(const impgpu_image* const* images, int count,
+                                  unsigned char* const* datas, const int* steps, int* codes);
 int   impgpu_album_count(const impgpu_image* image);        /* 1 for a single image */
 int   impgpu_image_width(const impgpu_image* image);
 int   impgpu_image_height(const impgpu_image* image);
@@ -505,8 +525,17 @@ int impgpu_run_ops(impgpu_image** pointer, const impgpu_job* job, const impgpu_c
  * channel count and what their later rounds cost, whatever `count` is (a request that still stands on its window after a
  * blur that worked in place is copied out by one more window launch behind its last round).  A request cut by a fault
  * point keeps what impgpu_run_ops leaves: its uncropped frame, with the pointwise filters applied inside the window when
- * the watermark step was the one that fired.  Albums and requests whose arguments fail (a bad crop, an unknown filter, too
- * many filters, a watermark that does not fit) go through impgpu_run_ops inside the call.  A shared launch that fails gives
+ * the watermark step was the one that fired.  A BGR / BGRA ALBUM (GIF composes and FreeImage frames are BGRA) rides the same
+ * launches: it is planned once per request -- crop, resize geometry, filter plans and overlay placement are the same for all
+ * its frames -- and every frame is an item of its own in each launch its request takes part in, so N albums cost the
+ * launches their frames would cost as single images, not N times the chain's length.  The handle stays ONE album in one block
+ * with the same frame count, as impgpu_run_ops leaves it; its fault points are entered once per request and step, never per
+ * frame; a blur form that runs alone, and a two-pass blur that is the only REQUEST of its class in its round, is one launch
+ * (pair) over all frames of the album, as in impgpu_run_ops.  A call takes at most 4096 album frames into its shared launches:
+ * the albums past that bound, in request order, go through impgpu_run_ops inside the call, and so does every GRAY album
+ * (1 channel), and an album that is the only colour album of its call (its operators are one launch each over all its
+ * frames there already).  Requests whose arguments fail (a bad crop, an unknown filter, too
+ * many filters, a watermark that does not fit) go through impgpu_run_ops inside the call too.  A shared launch that fails gives
  * each of its requests IMP_ERROR_DEVICE with the step of the segment it ran, and each keeps the frame it had.  launches (may be NULL) receives the number of kernels enqueued.  IMP_ERROR_INVALID_ARGS
  * with nothing enqueued when the arguments are malformed (NULL arrays, count < 0 or > 4096, the same handle twice); IMP_ERROR_DEVICE without an env (every codes[i] says so too);
  * otherwise IMP_OK, and the verdicts are in codes[].  Asynchronous on the env stream, like impgpu_run_ops. */

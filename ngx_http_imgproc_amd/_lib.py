@@ -162,6 +162,8 @@ SIGNATURES = {
     "impgpu_gif_compose_album": (C.c_int, [C.POINTER(CGifPage), C.c_int, C.c_int, C.c_int, PP]),
     "impgpu_batch_gif_compose": (C.c_int, [C.POINTER(CGifSet), C.c_int, PP, IP, IP]),
     "impgpu_album_download_fi": (C.c_int, [P, C.c_int, PP, IP]),
+    "impgpu_batch_download_fi": (C.c_int, [PP, IP, C.c_int, PP, IP, IP, IP]),
+    "impgpu_batch_album_download": (C.c_int, [PP, C.c_int, PP, IP, IP]),
     "impgpu_image_clone": (C.c_int, [P, PP]),
     "impgpu_image_download": (C.c_int, [P, P, C.c_int]),
     "impgpu_batch_download": (C.c_int, [PP, C.c_int, PP, IP]),

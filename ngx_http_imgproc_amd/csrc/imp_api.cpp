@@ -162,8 +162,9 @@ int fused_turn(const View& v, int count, int w, int h, int interp, const impgpu_
 }
 
 // What impgpu_batch_run_ops needs to know to run a request in shared launches instead of through impgpu_run_ops: a single
-// colour or gray frame whose chain is [crop ->] [resize ->] any filters -> [watermark] -> [flatten], every decision made here on
-// the host.  Host-only, no fault point entered: a request this refuses goes to impgpu_run_ops whole.
+// colour or gray frame, or a colour album (planned ONCE: crop, resize geometry, filter plans and overlay placement are the
+// same for all its frames; every frame then is an item of its own), whose chain is [crop ->] [resize ->] any filters ->
+// [watermark] -> [flatten], every decision made here on the host.  Host-only, no fault point entered: a request this refuses goes to impgpu_run_ops whole.
 // Without a resize (`sized` false) nothing rides a resize launch -- rot, wm_turn and the folds stay clear -- and the chain is
 // the segment list alone, its first segment reading the window `v`.
 // The resize is launch_resize_mixed, or the row-streaming AREA kernel with a tail on its stores (k_resize_area_mix_tail,
@@ -195,7 +196,8 @@ struct ChainPlan {
 };
 
 bool chain_plan(const impgpu_image* im, const impgpu_job* job, const impgpu_config* cfg, ChainPlan* p) {
-    if (!im || !job || !cfg || im->frames != 1 || (im->c != 1 && im->c != 3 && im->c != 4) || job->filter_count < 0) return false;
+    if (!im || !job || !cfg || im->frames < 1 || (im->c != 1 && im->c != 3 && im->c != 4) || job->filter_count < 0) return false;
+    if (im->c == 1 && im->frames != 1) return false;                   // gray albums: impgpu_run_ops (composes and FreeImage frames are BGRA)
     if (cfg->max_filters_count > 0 && job->filter_count > cfg->max_filters_count) return false;
     if (job->filter_count > 0 && !job->filters) return false;
     for (int i = 0; i < job->filter_count; i++) if (!job->filters[i]) return false;
@@ -219,7 +221,7 @@ bool chain_plan(const impgpu_image* im, const impgpu_job* job, const impgpu_conf
     p->wm_turn = p->fold_wm = p->fold_flat = false;
     p->wm = OverlayArgs{};
     p->segs.clear();
-    p->rot = sized ? fused_turn(v, 1, w, h, interp, job, cfg, &p->wm_turn) : 0;
+    p->rot = sized ? fused_turn(v, 1, w, h, interp, job, cfg, &p->wm_turn) : 0;        // (count 1: every frame is an item of its own)
     const bool swap = p->rot == 90 || p->rot == 270;
     int cw = swap ? h : w, ch = swap ? w : h;
     const int i0 = p->rot ? 1 : 0;
@@ -305,6 +307,18 @@ struct Batch {
     Group<MixFrame> bares[3], nns[3];
     std::vector<int> promote;        // gray requests that reach the promotion
     size_t rounds = 0;               // the longest chain
+    // An album that is the only colour album of its call stays with impgpu_run_ops, whose launches are one per operator over
+    // all its frames already (the rule of the lone blur forms: sharing is for what comes in numbers).
+    bool share_albums = false;
+    int album_frames = 0;            // frames of albums admitted to the shared launches so far (at most MAX_ALBUM_FRAMES)
+    static constexpr int MAX_ALBUM_FRAMES = 4096;
+
+    // Frame f of request i as its launches see it: `src` bytes on from the frame it stands on (run.cur, a window of frame 0
+    // of images[i]), `dst` bytes on from frame 0 of `out` (nullptr: in place).  A single image is an album of one.
+    template <class F> void each_frame(int i, const impgpu_image* out, F item) const {
+        const impgpu_image* im = images[i];
+        for (int f = 0; f < im->frames; f++) item((size_t)f * im->fstride, out ? (size_t)f * out->fstride : (size_t)f * im->fstride);
+    }
 
     bool on_window(int i) const {
         const View& v = runs[(size_t)i].cur;
@@ -322,14 +336,17 @@ struct Batch {
     }
     // the destination of request i's next launch (as Work::fresh); failed, the request stops with the allocator's code
     impgpu_image* fresh(int i, int w, int h, int c) {
-        if (int rc = image_new_album(w, h, c, 1, &runs[(size_t)i].pending)) { stop(i, rc); return nullptr; }
+        if (int rc = image_new_album(w, h, c, images[i]->frames, &runs[(size_t)i].pending)) { stop(i, rc); return nullptr; }
         return runs[(size_t)i].pending;
     }
     // A launch is done.  Its fresh frames replace the old ones (pool memory: recycled in stream order, behind the launch); failed,
     // every request of it keeps the frame it had and stops with IMP_ERROR_DEVICE at its step.  `landed`: the launch was the
     // request's resize -- it joins the rounds and its verdict is published.  (An in-place launch has no fresh frames.)
+    // Once per request: an album's frames are items of their own, next to each other in `who`.
     void adopt(const std::vector<int>& who, int rc, bool landed = false) {
-        for (int i : who) {
+        for (size_t k = 0; k < who.size(); k++) {
+            const int i = who[k];
+            if (k > 0 && who[k - 1] == i) continue;
             ChainRun& run = runs[(size_t)i];
             impgpu_image* out = run.pending;
             run.pending = nullptr;
@@ -358,16 +375,20 @@ struct Batch {
 // overlaid after the filters, never flattened -- and never copied out of its window.  A failed allocation reports the
 // allocator's code, a failed launch IMP_ERROR_DEVICE, both at the step the launch belongs to (ChainRun::at: the resize
 // step, FILTERING for the promotion, the segment's own step, WATERMARK for the copy out of the window behind the last
-// segment, as impgpu_run_ops' materialize); the request keeps the frame it stood on.
+// segment, as impgpu_run_ops' materialize); the request keeps the frame it stood on.  An album is ONE request in all of
+// this: its points are entered once per step, never per frame, and what it keeps is the whole album.
 void Batch::admit(int i) {
     const impgpu_job* job = &jobs[i];
     const impgpu_config* cfg = configs[i];
     ChainRun& run = runs[(size_t)i];
     ChainPlan& cp = run.plan;
-    if (!chain_plan(images[i], job, cfg, &cp)) {
+    // (an album past the call's frame bound is answered like a request the planner refuses: right here, in request order)
+    const int nframes = images[i] ? images[i]->frames : 1;
+    if ((nframes > 1 && (!share_albums || album_frames + nframes > MAX_ALBUM_FRAMES)) || !chain_plan(images[i], job, cfg, &cp)) {
         codes[i] = impgpu_run_ops(&images[i], job, cfg, &steps[i]);
         return;
     }
+    if (nframes > 1) album_frames += nframes;
     run.at = IMP_STEP_CROP;
     if (job->crop && fault_hit(IMP_STEP_CROP)) return stop(i, IMP_ERROR_DEVICE);
     if (cp.sized) {
@@ -401,10 +422,14 @@ void Batch::admit(int i) {
     run.state = ChainRun::WAITING;
     const int k = cp.gray ? 2 : cp.v.c - 3;
     const bool on_stores = cp.wm_turn || cp.fold_wm;
-    if (cp.rot || on_stores || cp.fold_flat)
-        tails[k].add(i, TailItem{cp.v, out->d, cp.w, cp.h, out->step, cp.rot, on_stores, on_stores ? cp.wm : OverlayArgs{}, cp.fold_flat});
-    else
-        (job->simple ? nns : bares)[k].add(i, MixFrame{cp.v.d, cp.v.w, cp.v.h, cp.v.step, out->d, cp.w, cp.h, out->step});
+    each_frame(i, out, [&](size_t so, size_t dn) {
+        View v = cp.v;
+        v.d += so;
+        if (cp.rot || on_stores || cp.fold_flat)
+            tails[k].add(i, TailItem{v, out->d + dn, cp.w, cp.h, out->step, cp.rot, on_stores, on_stores ? cp.wm : OverlayArgs{}, cp.fold_flat});
+        else
+            (job->simple ? nns : bares)[k].add(i, MixFrame{v.d, v.w, v.h, v.step, out->d + dn, cp.w, cp.h, out->step});
+    });
 }
 
 // Round 0: every resize, per slot bare, NN, tail.  A request whose launch fails keeps its frame and stops there.
@@ -432,9 +457,10 @@ void Batch::promote_gray() {
 }
 
 // Round r: segment r of every chain that has one, one launch per (kind, channel count) in the order window, pixel, geom, blur
-// -- and the blur forms no mixed kernel takes one request at a time, as apply_plan runs them; so does a two-pass blur that is
-// the only one of its channel and plane count in the round (a shared launch pair would save it nothing).  Barriers write fresh frames;
-// pointwise segments work in place, or out of the window into a fresh frame when the request still stands on one.  A request
+// -- and the blur forms no mixed kernel takes one request at a time, as apply_plan runs them (an album: one launch or launch
+// pair over all its frames); so does a two-pass blur that is the only REQUEST of its channel and plane count in the round (a
+// shared launch pair would save it nothing).  Every frame of an album is an item of its own in its request's group.
+// Barriers write fresh frames; pointwise segments work in place, or out of the window into a fresh frame when the request still stands on one.  A request
 // that has run its segments and still stands on a window (no segment at all: the bare crop; or nothing but blurs that worked in
 // place) leaves it as materialize() does, as a bare item of the window launch of the round after its last segment.
 void Batch::segment_round(size_t r) {
@@ -460,10 +486,12 @@ void Batch::segment_round(size_t r) {
             run.at = IMP_STEP_WATERMARK;
             impgpu_image* out = fresh(i, cur.w, cur.h, cur.c);
             if (!out) continue;
-            WindowItem it{};
-            it.src = cur.d; it.sstep = cur.step;
-            it.t.d = out->d; it.t.w = out->w; it.t.h = out->h; it.t.step = out->step;
-            wnd[k].add(i, it);
+            each_frame(i, out, [&](size_t so, size_t dn) {
+                WindowItem it{};
+                it.src = cur.d + so; it.sstep = cur.step;
+                it.t.d = out->d + dn; it.t.w = out->w; it.t.h = out->h; it.t.step = out->step;
+                wnd[k].add(i, it);
+            });
             continue;
         }
         const Segment& sg = run.plan.segs[r];
@@ -477,11 +505,22 @@ void Batch::segment_round(size_t r) {
                 it.rx = wm.rx; it.ry = wm.ry; it.maxcol = wm.maxcol; it.maxrow = wm.maxrow; it.alpha = wm.alpha;
             }
             it.flatten = sg.flat;
-            if (!on_window(i) || run.cut) { pix[k].add(i, it); continue; }    // in place (on the window when a fault point cut the request)
+            if (!on_window(i) || run.cut) {                          // in place (on the window when a fault point cut the request)
+                each_frame(i, nullptr, [&](size_t so, size_t) {
+                    PixelTailItem at = it;
+                    at.d += so;
+                    pix[k].add(i, at);
+                });
+                continue;
+            }
             impgpu_image* out = fresh(i, cur.w, cur.h, cur.c);       // out of the window into a fresh frame
             if (!out) continue;
-            it.d = out->d; it.step = out->step;
-            wnd[k].add(i, WindowItem{cur.d, cur.step, it});
+            it.step = out->step;
+            each_frame(i, out, [&](size_t so, size_t dn) {
+                PixelTailItem at = it;
+                at.d = out->d + dn;
+                wnd[k].add(i, WindowItem{cur.d + so, cur.step, at});
+            });
             continue;
         }
         if (sg.kind == SEG_BLUR) {
@@ -493,11 +532,13 @@ void Batch::segment_round(size_t r) {
         const bool turn = sg.kind == SEG_GEOM && sg.plan.cls == FC_ROTATE, swap = turn && sg.plan.rotate != 180;
         impgpu_image* out = fresh(i, swap ? cur.h : cur.w, swap ? cur.w : cur.h, cur.c);
         if (!out) continue;
-        if (sg.kind == SEG_GEOM)
-            geo[k].add(i, GeomItem{cur.d, cur.w, cur.h, cur.step, out->d, out->w, out->h, out->step, turn ? 1 : 0,
-                                   turn ? sg.plan.rotate : sg.plan.flip_mode});
-        else
-            blu[k].add(i, BlurItem{cur.d, out->d, cur.w, cur.h, cur.step, out->step, (double)sg.plan.sigma});
+        each_frame(i, out, [&](size_t so, size_t dn) {
+            if (sg.kind == SEG_GEOM)
+                geo[k].add(i, GeomItem{cur.d + so, cur.w, cur.h, cur.step, out->d + dn, out->w, out->h, out->step, turn ? 1 : 0,
+                                       turn ? sg.plan.rotate : sg.plan.flip_mode});
+            else
+                blu[k].add(i, BlurItem{cur.d + so, out->d + dn, cur.w, cur.h, cur.step, out->step, (double)sg.plan.sigma});
+        });
     }
     for (int k = 0; k < 2; k++)
         for (const std::vector<int>& cls : pairs[k])
@@ -506,7 +547,9 @@ void Batch::segment_round(size_t r) {
                 if (cls.size() == 1) { lone_blur(i, sg); continue; }
                 const View cur = runs[(size_t)i].cur;
                 if (impgpu_image* out = fresh(i, cur.w, cur.h, cur.c))
-                    blu[k].add(i, BlurItem{cur.d, out->d, cur.w, cur.h, cur.step, out->step, (double)sg.plan.sigma});
+                    each_frame(i, out, [&](size_t so, size_t dn) {
+                        blu[k].add(i, BlurItem{cur.d + so, out->d + dn, cur.w, cur.h, cur.step, out->step, (double)sg.plan.sigma});
+                    });
             }
     for (int k = 0; k < 2; k++) {
         if (!wnd[k].empty()) adopt(wnd[k].who, launch_window_mixed(wnd[k].items.data(), wnd[k].size(), k + 3, s));
@@ -832,6 +875,174 @@ int impgpu_album_download_fi(const impgpu_image* album, int bpp, unsigned char* 
     return IMP_OK;
 }
 
+// Handles [g0, g1) of a call that answers many handles out of one pinned staging buffer: as many as the staging cap takes,
+// cut at a handle (a handle past the cap by itself goes alone, as its lone call would) -- impgpu_batch_gif_compose's rule.
+// `bytes[k]` is what handle k puts into the buffer (0: refused, it rides along for nothing).
+static size_t stage_group_end(const std::vector<size_t>& bytes, size_t g0, size_t cap, size_t* total) {
+    size_t g1 = g0, sum = 0;
+    while (g1 < bytes.size() && (sum == 0 || !cap || sum + bytes[g1] <= cap)) sum += bytes[g1++];
+    *total = sum;
+    return g1;
+}
+
+// impgpu_album_download_fi for many handles: every accepted frame's flip and repack goes into ONE device block through
+// k_pack_fi_mix, one launch per (source channels, bpp) pair present; then one copy into pinned staging, one wait, and the
+// rows into the callers' bitmaps.
+int impgpu_batch_download_fi(const impgpu_image* const* images, const int* bpps, int count, unsigned char* const* bits,
+                             const int* pitches, int* codes, int* launches) {
+    if (launches) *launches = 0;
+    if (count < 0 || count > 256 || (count > 0 && (!images || !bpps || !bits || !pitches || !codes))) return IMP_ERROR_INVALID_ARGS;
+    if (count == 0) return IMP_OK;                                     // nothing asked: answered without a device
+    if (int rc = need_env()) {
+        for (int i = 0; i < count; i++) codes[i] = rc;
+        return rc;
+    }
+    const unsigned long long launched = t_launches;
+    // impgpu_album_download_fi's refusals per handle: nothing of a refused entry is touched
+    std::vector<size_t> first((size_t)count), bytes((size_t)count, 0);    // the handle's first frame in bits[]; its bytes in the block
+    std::vector<int> dpitch((size_t)count, 0);
+    size_t frame0 = 0;
+    for (int i = 0; i < count; i++) {
+        const impgpu_image* im = images[i];
+        first[(size_t)i] = frame0;
+        codes[i] = IMP_ERROR_INVALID_ARGS;
+        if (!im) continue;
+        frame0 += (size_t)im->frames;
+        const int bpp = bpps[i];
+        if ((bpp != 24 && bpp != 32) || im->c < 3) continue;
+        const size_t rowbytes = (size_t)im->w * (bpp / 8);
+        bool ok = true;
+        for (int f = 0; f < im->frames && ok; f++) {
+            const size_t at = first[(size_t)i] + (size_t)f;
+            ok = bits[at] && pitches[at] >= 0 && (size_t)pitches[at] >= rowbytes;
+        }
+        dpitch[(size_t)i] = (int)((rowbytes + 3) & ~size_t(3));    // FreeImage's own pitch rule
+        // (what launch_pack_fi refuses of a wrapped BGRA frame: rows off the dword grid)
+        if (im->c == 4 && bpp == 32 && (((uintptr_t)im->d | (uintptr_t)im->step | (uintptr_t)im->fstride) & 3)) ok = false;
+        if (!ok) continue;
+        codes[i] = IMP_OK;
+        bytes[(size_t)i] = (((size_t)dpitch[(size_t)i] * im->h + 63) & ~size_t(63)) * (size_t)im->frames;
+    }
+    const size_t cap = stage_cap();
+    hipStream_t s = env_stream();
+    for (size_t g0 = 0; g0 < (size_t)count;) {
+        size_t total = 0;
+        const size_t g1 = stage_group_end(bytes, g0, cap, &total);
+        if (total) {
+            void *tmp = nullptr, *host = nullptr, *token = nullptr;
+            int rc = dev_alloc(total, &tmp);
+            if (!rc) {
+                Group<PackFiItem> packs[2][2];                              // by source channels (3, 4) and bpp (24, 32)
+                size_t at = 0;
+                for (size_t i = g0; i < g1; i++) {
+                    if (!bytes[i]) continue;
+                    const impgpu_image* im = images[i];
+                    const size_t each = bytes[i] / (size_t)im->frames;
+                    for (int f = 0; f < im->frames; f++, at += each)
+                        packs[im->c - 3][bpps[i] == 32].add((int)i, PackFiItem{im->d + (size_t)f * im->fstride, im->w, im->h, im->step,
+                                                                              (uint8_t*)tmp + at, dpitch[i]});
+                }
+                for (int c = 0; c < 2 && !rc; c++)
+                    for (int b = 0; b < 2 && !rc; b++)
+                        rc = launch_pack_fi_mixed(packs[c][b].items.data(), packs[c][b].size(), c + 3, b ? 32 : 24, s);
+                if (!rc) rc = stage_begin(total, &host, &token);
+                if (!rc) {
+                    const hipError_t e = hipMemcpyAsync(host, tmp, total, hipMemcpyDeviceToHost, s);
+                    if (e != hipSuccess) { set_error("hipMemcpyAsync(batch_download_fi)", e); rc = IMP_ERROR_DEVICE; }
+                }
+                dev_free(tmp);
+                const int rcw = lane_wait();
+                if (!rc) rc = rcw;
+            }
+            size_t at = 0;
+            for (size_t i = g0; i < g1; i++) {                            // this group's handles fail together; the others stand
+                if (!bytes[i]) continue;
+                const impgpu_image* im = images[i];
+                const size_t each = bytes[i] / (size_t)im->frames, rowbytes = (size_t)im->w * (bpps[i] / 8);
+                if (rc) { codes[i] = rc; continue; }
+                for (int f = 0; f < im->frames; f++, at += each) {
+                    unsigned char* to = bits[first[i] + (size_t)f];
+                    const size_t pitch = (size_t)pitches[first[i] + (size_t)f];
+                    for (int y = 0; y < im->h; y++) std::memcpy(to + (size_t)y * pitch, (const uint8_t*)host + at + (size_t)y * dpitch[i], rowbytes);
+                }
+            }
+        }
+        g0 = g1;
+    }
+    if (launches) *launches = (int)(t_launches - launched);
+    return IMP_OK;
+}
+
+// impgpu_album_download for many handles: each handle's block is one copy into its part of ONE pinned staging buffer, all
+// of them enqueued before ONE wait; then the rows into the callers' frames.  The fault point impgpu_album_download enters
+// is entered per handle that call would take, in handle order, before anything is enqueued.
+int impgpu_batch_album_download(const impgpu_image* const* images, int count, unsigned char* const* datas, const int* steps, int* codes) {
+    if (count < 0 || count > 256 || (count > 0 && (!images || !datas || !steps || !codes))) return IMP_ERROR_INVALID_ARGS;
+    if (count == 0) return IMP_OK;
+    if (int rc = need_env()) {
+        for (int i = 0; i < count; i++) codes[i] = rc;
+        return rc;
+    }
+    TraceRange tr("IMP_STEP_ENCODE");
+    std::vector<size_t> first((size_t)count), bytes((size_t)count, 0);
+    size_t frame0 = 0;
+    for (int i = 0; i < count; i++) {
+        const impgpu_image* im = images[i];
+        first[(size_t)i] = frame0;
+        codes[i] = IMP_ERROR_INVALID_ARGS;
+        if (!im) continue;
+        frame0 += (size_t)im->frames;
+        const size_t rowbytes = (size_t)im->w * im->c;
+        bool ok = true;
+        for (int f = 0; f < im->frames && ok; f++) {
+            const size_t at = first[(size_t)i] + (size_t)f;
+            ok = datas[at] && steps[at] >= 0 && (size_t)steps[at] >= rowbytes;
+        }
+        if (!ok) continue;
+        if (fault_hit(IMP_STEP_ENCODE)) { codes[i] = IMP_ERROR_DEVICE; continue; }
+        codes[i] = IMP_OK;
+        const size_t frame = (size_t)im->step * im->h;
+        bytes[(size_t)i] = (((im->frames > 1 ? im->fstride * (size_t)(im->frames - 1) : 0) + frame) + 63) & ~size_t(63);
+    }
+    const size_t cap = stage_cap();
+    hipStream_t s = env_stream();
+    for (size_t g0 = 0; g0 < (size_t)count;) {
+        size_t total = 0;
+        const size_t g1 = stage_group_end(bytes, g0, cap, &total);
+        if (total) {
+            void *host = nullptr, *token = nullptr;
+            int rc = stage_begin(total, &host, &token);
+            size_t at = 0;
+            for (size_t i = g0; i < g1 && !rc; i++) {
+                if (!bytes[i]) continue;
+                const impgpu_image* im = images[i];
+                const size_t block = (im->frames > 1 ? im->fstride * (size_t)(im->frames - 1) : 0) + (size_t)im->step * im->h;
+                const hipError_t e = hipMemcpyAsync((uint8_t*)host + at, im->d, block, hipMemcpyDeviceToHost, s);
+                if (e != hipSuccess) { set_error("hipMemcpyAsync(batch_album_download)", e); rc = IMP_ERROR_DEVICE; }
+                at += bytes[i];
+            }
+            const int rcw = lane_wait();
+            if (!rc) rc = rcw;
+            at = 0;
+            for (size_t i = g0; i < g1; i++) {
+                if (!bytes[i]) continue;
+                const impgpu_image* im = images[i];
+                if (rc) { codes[i] = rc; continue; }
+                const size_t rowbytes = (size_t)im->w * im->c;
+                for (int f = 0; f < im->frames; f++) {
+                    unsigned char* to = datas[first[i] + (size_t)f];
+                    const size_t dstep = (size_t)steps[first[i] + (size_t)f];
+                    const uint8_t* from = (const uint8_t*)host + at + (size_t)f * im->fstride;
+                    for (int y = 0; y < im->h; y++) std::memcpy(to + (size_t)y * dstep, from + (size_t)y * im->step, rowbytes);
+                }
+                at += bytes[i];
+            }
+        }
+        g0 = g1;
+    }
+    return IMP_OK;
+}
+
 int impgpu_calc_perceived_brightness(const impgpu_image* image, float* brightness) {
     if (!image || !brightness) return IMP_ERROR_INVALID_ARGS;
     if (int rc = need_env()) return rc;
@@ -1072,6 +1283,9 @@ int impgpu_batch_run_ops(impgpu_image** images, const impgpu_job* jobs, const im
     const unsigned long long launched = t_launches;
     Batch b{images, jobs, configs, count, codes, steps, env_stream()};
     b.runs.resize((size_t)count);
+    int albums = 0;
+    for (int i = 0; i < count; i++) albums += images[i] && images[i]->frames > 1 && images[i]->c >= 3;
+    b.share_albums = albums >= 2;
     for (int i = 0; i < count; i++) b.admit(i);
     b.resize_round();
     b.promote_gray();

@@ -17,8 +17,9 @@
 //     JPEG answers   impgpu_batch_encode_jpeg            cvEncodeImage(".jpg"), bridge.c:704
 //     PNG answers    impgpu_batch_encode_png             cvEncodeImage(".png"), bridge.c:704
 //     pixel answers  impgpu_batch_download               for the host encoders (PNG, WebP, FreeImage formats)
-//     album answers  impgpu_album_download               every frame of an album, per request
-//     FreeImage ans. impgpu_album_download_fi            IplToFI32 / IplToFI24, advancedio.c:65-101, every frame
+//     album answers  impgpu_batch_album_download         every frame of every many-frame answer of the batch, one wait
+//     FreeImage ans. impgpu_batch_download_fi            IplToFI32 / IplToFI24, advancedio.c:65-101, every frame of every
+//                                                        such answer of the batch: a launch per (channels, bpp), one wait
 //     json answers   impgpu_batch_calc_perceived_brightness   Info(), bridge.c:283-300 (two or more; one: the lone call)
 //     text answers   impgpu_batch_ascii                  ASCII(), bridge.c:668-676 (likewise)
 // Nothing a worker writes into its slot is trusted further than a request is: the request record is copied out of shared
@@ -644,16 +645,35 @@ struct Worker {
         answer(raw, [](const impgpu_image* const* im, int m, unsigned char* const* outs, const size_t*, const int* row_steps, size_t*, int*) {
             return impgpu_batch_download(im, m, outs, row_steps);
         });
-        // album and FreeImage answers: per request, every frame in one transfer and one wait (impgpu_album_download[_fi])
-        for (size_t k : many) {
-            Req& r = reqs[k];
-            std::vector<unsigned char*> at((size_t)r.out_frames);
-            std::vector<int> row_steps((size_t)r.out_frames, r.out_step);
-            for (size_t f = 0; f < at.size(); f++) at[f] = S.slot_data(r.slot) + r.out_offset + f * r.out_frame_stride;
-            const int rc = r.q.out_kind == IMPB_OUT_FI ? impgpu_album_download_fi(r.img, r.q.quality, at.data(), row_steps.data())
-                                                       : impgpu_album_download(r.img, at.data(), row_steps.data());
-            if (rc != IMP_OK) { fail(r, rc, IMP_STEP_ENCODE, impgpu_last_error()); continue; }
-            r.code = IMP_OK; r.done = true;
+        // album and FreeImage answers: the batch's FreeImage answers in one call, its many-frame albums in another -- every
+        // frame of every request behind one transfer and one wait each (impgpu_batch_download_fi, impgpu_batch_album_download;
+        // at most 256 handles a call)
+        for (const bool fi : {true, false}) {
+            std::vector<size_t> ks;
+            for (size_t k : many) if ((reqs[k].q.out_kind == IMPB_OUT_FI) == fi) ks.push_back(k);
+            for (size_t k0 = 0; k0 < ks.size(); k0 += 256) {
+                const size_t m = std::min(ks.size() - k0, (size_t)256);
+                std::vector<const impgpu_image*> imgs(m);
+                std::vector<int> bpps(m), codes(m, IMP_OK), row_steps;
+                std::vector<unsigned char*> at;
+                for (size_t j = 0; j < m; j++) {
+                    const Req& r = reqs[ks[k0 + j]];
+                    imgs[j] = r.img;
+                    bpps[j] = r.q.quality;
+                    for (int32_t f = 0; f < r.out_frames; f++) {
+                        at.push_back(S.slot_data(r.slot) + r.out_offset + (uint64_t)f * r.out_frame_stride);
+                        row_steps.push_back(r.out_step);
+                    }
+                }
+                const int rc = fi ? impgpu_batch_download_fi(imgs.data(), bpps.data(), (int)m, at.data(), row_steps.data(), codes.data(), nullptr)
+                                  : impgpu_batch_album_download(imgs.data(), (int)m, at.data(), row_steps.data(), codes.data());
+                for (size_t j = 0; j < m; j++) {
+                    Req& r = reqs[ks[k0 + j]];
+                    const int code = rc != IMP_OK ? rc : codes[j];
+                    if (code != IMP_OK) { fail(r, code, IMP_STEP_ENCODE, impgpu_last_error()); continue; }
+                    r.code = IMP_OK; r.done = true;
+                }
+            }
         }
         if (most) answer(by_quality[common], jpeg(common));
         // The json and text exits go LAST.  Each of the calls above and below ends in a wait of its own, and the lane's stream

@@ -174,10 +174,11 @@ __global__ __launch_bounds__(256) void k_gray2bgr(GArgs a) {
     d[0] = v; d[1] = v; d[2] = v;
 }
 
-// IplToFI32 / IplToFI24 (advancedio.c:65-101): vertical flip + channel repack into FreeImage's row pitch
+// IplToFI32 / IplToFI24 (advancedio.c:65-101): vertical flip + channel repack into FreeImage's row pitch.  The pixel `idx`
+// (row-major in the bitmap) of a w x h frame: shared by k_pack_fi (one frame) and k_pack_fi_mix (many).
 template <int SC, int DC>
-__global__ __launch_bounds__(256) void k_pack_fi(const uint8_t* __restrict__ src, int sstep, int w, int h, uint8_t* __restrict__ dst, int dpitch) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void pack_fi_pixel(const uint8_t* __restrict__ src, int sstep, int w, int h, uint8_t* __restrict__ dst,
+                                              int dpitch, long long idx) {
     if (idx >= (long long)w * h) return;
     const int y = (int)(idx / w), x = (int)(idx - (long long)y * w);
     const uint8_t* s = src + (size_t)(h - 1 - y) * sstep + (size_t)x * SC;
@@ -185,6 +186,11 @@ __global__ __launch_bounds__(256) void k_pack_fi(const uint8_t* __restrict__ src
     if (SC == 4 && DC == 4) { *(uint32_t*)d = *(const uint32_t*)s; return; }
     d[0] = s[0]; d[1] = s[1]; d[2] = s[2];
     if (DC == 4) d[3] = SC == 4 ? s[3] : 255;
+}
+
+template <int SC, int DC>
+__global__ __launch_bounds__(256) void k_pack_fi(const uint8_t* __restrict__ src, int sstep, int w, int h, uint8_t* __restrict__ dst, int dpitch) {
+    pack_fi_pixel<SC, DC>(src, sstep, w, h, dst, dpitch, (long long)blockIdx.x * 256 + threadIdx.x);
 }
 
 int launch_pack_fi(const View& v, int bpp, uint8_t* dst, int dpitch, hipStream_t s) {
@@ -198,6 +204,48 @@ int launch_pack_fi(const View& v, int bpp, uint8_t* dst, int dpitch, hipStream_t
     else hipLaunchKernelGGL((k_pack_fi<3, 3>), grid, block, 0, s, v.d, v.step, v.w, v.h, dst, dpitch);
     IMP_HIP(hipGetLastError());
     return IMP_OK;
+}
+
+// ---- many frames, one launch (impgpu_batch_download_fi) ----
+// A descriptor per frame, dealt like k_geom_mix's; a workgroup covers 256 bitmap pixels of ONE frame, a lane one pixel
+// through pack_fi_pixel -- a dword in and out for BGRA -> 32 bits, bytes otherwise, exactly k_pack_fi's accesses.
+struct PackFiDesc {
+    const uint8_t* src; uint8_t* dst;
+    int w, h, sstep, dpitch;
+    int first, nblk;
+};
+
+template <int SC, int DC>
+__global__ __launch_bounds__(256) void k_pack_fi_mix(const PackFiDesc* __restrict__ d, MixIndex ix) {
+    int blk;
+    const int i = mix_pick(d, ix, &blk);
+    if (i < 0) return;
+    pack_fi_pixel<SC, DC>(d[i].src, d[i].sstep, d[i].w, d[i].h, d[i].dst, d[i].dpitch, (long long)blk * 256 + threadIdx.x);
+}
+
+int launch_pack_fi_mixed(const PackFiItem* items, int count, int channels, int bpp, hipStream_t s) {
+    if (count <= 0) return IMP_OK;
+    if (!items || (channels != 3 && channels != 4) || (bpp != 24 && bpp != 32)) return IMP_ERROR_INVALID_ARGS;
+    std::vector<PackFiDesc> v;
+    v.reserve((size_t)count);
+    long long blocks = 0;
+    for (int i = 0; i < count; i++) {                      // nothing is launched unless every item is well-formed
+        const PackFiItem& it = items[i];
+        if (!it.src || !it.dst || !view_fits(it.w, it.h, channels, it.sstep) || !view_fits(it.w, it.h, bpp / 8, it.dpitch)) return IMP_ERROR_INVALID_ARGS;
+        if (channels == 4 && bpp == 32 && (((uintptr_t)it.src | (uintptr_t)it.sstep | (uintptr_t)it.dst | (uintptr_t)it.dpitch) & 3)) return IMP_ERROR_INVALID_ARGS;
+        PackFiDesc d{};
+        d.src = it.src; d.dst = it.dst; d.w = it.w; d.h = it.h; d.sstep = it.sstep; d.dpitch = it.dpitch;
+        d.nblk = (int)(((long long)it.w * it.h + 255) / 256);
+        blocks += d.nblk;
+        v.push_back(d);
+    }
+    if (blocks * 8 > 0x7fffffffLL) return IMP_ERROR_INVALID_ARGS;     // (the grid is 8 x the longest list: the caller splits first)
+    return mix_launch(v, [](PackFiDesc& d) { return (long long)d.w * d.h; }, s, [&](dim3 grid, const PackFiDesc* dev, const MixIndex& ix) {
+        if (channels == 4 && bpp == 32) hipLaunchKernelGGL((k_pack_fi_mix<4, 4>), grid, dim3(256), 0, s, dev, ix);
+        else if (channels == 4) hipLaunchKernelGGL((k_pack_fi_mix<4, 3>), grid, dim3(256), 0, s, dev, ix);
+        else if (bpp == 32) hipLaunchKernelGGL((k_pack_fi_mix<3, 4>), grid, dim3(256), 0, s, dev, ix);
+        else hipLaunchKernelGGL((k_pack_fi_mix<3, 3>), grid, dim3(256), 0, s, dev, ix);
+    });
 }
 
 // LoadGIF's compositing loop (advancedio.c:204-247) for the canvas pixel (x, y), walking the pages in order: the `master`

@@ -390,6 +390,57 @@ def batch_ascii(images, args=None, capacities=None):
     return texts, [codes[i] for i in range(n)], launches.value
 
 
+def _frame_count(im):
+    return 0 if _handle(im) is None else lib.impgpu_album_count(C.c_void_p(_handle(im)))
+
+
+def batch_download_fi(images, bpps, pitches=None, fill=0):
+    """impgpu_batch_download_fi: Image.frames_fi(bpps[i], pitches[i]) of every handle (albums and single images) in one call
+    behind one wait.  An entry of `images` may be None; pitches[i] (None: FreeImage's own rule) is the row pitch of every
+    bitmap of handle i.  Returns (bitmaps, codes, launches): bitmaps[i] is the list of handle i's h x pitch arrays, which
+    held `fill` before."""
+    n = len(images)
+    if len(bpps) != n or (pitches is not None and len(pitches) != n):
+        raise ValueError("images, bpps and pitches differ in length")
+    outs, ptrs, rows = [], [], []
+    for i, im in enumerate(images):
+        hh, ww = (im.shape[0], im.shape[1]) if _handle(im) is not None else (0, 0)
+        pitch = pitches[i] if pitches is not None and pitches[i] is not None else (ww * (int(bpps[i]) // 8) + 3) & ~3
+        mine = [np.full((hh, max(0, pitch)), fill, dtype=np.uint8) for _ in range(_frame_count(im))]
+        outs.append(mine)
+        ptrs += [o.ctypes.data for o in mine]
+        rows += [pitch] * len(mine)
+    m = len(ptrs)
+    handles = (C.c_void_p * max(1, n))(*[_handle(im) for im in images])
+    codes = (C.c_int * max(1, n))()
+    launches = C.c_int()
+    rc = lib.impgpu_batch_download_fi(handles, (C.c_int * max(1, n))(*[int(b) for b in bpps]), n, (C.c_void_p * max(1, m))(*ptrs),
+                                      (C.c_int * max(1, m))(*rows), codes, C.byref(launches))
+    if rc:
+        raise ImpError(rc, "impgpu_batch_download_fi")
+    return outs, [codes[i] for i in range(n)], launches.value
+
+
+def batch_album_download(images):
+    """impgpu_batch_album_download: Image.frames() of every handle in one call behind one wait.  An entry may be None.
+    Returns (frames, codes): frames[i] is the list of handle i's HxWxC arrays."""
+    n = len(images)
+    outs, ptrs, rows = [], [], []
+    for im in images:
+        hh, ww, cc = im.shape if _handle(im) is not None else (0, 0, 0)
+        mine = [np.empty((hh, ww, cc), dtype=np.uint8) for _ in range(_frame_count(im))]
+        outs.append(mine)
+        ptrs += [o.ctypes.data for o in mine]
+        rows += [ww * cc] * len(mine)
+    m = len(ptrs)
+    handles = (C.c_void_p * max(1, n))(*[_handle(im) for im in images])
+    codes = (C.c_int * max(1, n))()
+    rc = lib.impgpu_batch_album_download(handles, n, (C.c_void_p * max(1, m))(*ptrs), (C.c_int * max(1, m))(*rows), codes)
+    if rc:
+        raise ImpError(rc, "impgpu_batch_album_download")
+    return outs, [codes[i] for i in range(n)]
+
+
 def batch_decode_jpeg(blobs):
     """impgpu_batch_decode_jpeg -> [(code, Image or None)] in the order of `blobs`."""
     n = len(blobs)
