@@ -577,7 +577,8 @@ int               impgpu_request_mime(const impgpu_request* request);       /* I
 int               impgpu_request_destructive(const impgpu_request* request); /* CheckDestructive over the filters */
 void              impgpu_request_free(impgpu_request** request);
 
-/* ---- GIF album hand-over: LoadGIF (advancedio.c:103-262).  FreeImage keeps decoding the pages on the host; the
+/* ---- GIF album hand-over: LoadGIF (advancedio.c:103-262).  Here FreeImage decodes the pages on the host (the calls
+ *      that take the FILE follow below); the
  *      per-pixel compositing loop of advancedio.c:204-247 -- the frame placed at FrameLeft/FrameTop on the first
  *      page's canvas, the transparent index, the `master` index canvas carried from page to page when the request
  *      is destructive (advancedio.c:195-240), the RGBQUAD palette lookup into a 4-channel frame (:242-246) -- runs
@@ -613,6 +614,46 @@ int impgpu_gif_compose_album(const impgpu_gif_page* pages, int count, int destru
  * the lone call: the page memory is read before it returns. */
 typedef struct impgpu_gif_set { const impgpu_gif_page* pages; int count, destructive, page; } impgpu_gif_set;
 int impgpu_batch_gif_compose(const impgpu_gif_set* sets, int count, impgpu_image** albums, int* codes, int* launches);
+
+/* ---- GIF FILES in: the hand-over above still has FreeImage LZW-decode every page on a host core and ship index planes
+ *      of 2-5x the file's size.  These calls take the file.  The host walks the container (include/impgpu_gif.h:
+ *      impgpu_gif_walk, which decompresses nothing); the compressed sub-block payloads are uploaded, k_gif_lzw decodes
+ *      every page -- one wavefront per page, the table in LDS, rounds of 64 codes whose bit offsets are a closed form of
+ *      the round's start state -- straight into the index planes the compositing loop reads (8-bit, bottom-up, pitch =
+ *      (width + 3) & ~3, pad bytes 0: what FreeImage would hold), and k_gif_compose_mix follows on the same stream.
+ *      *album is what impgpu_gif_compose_album gives for the file's pages (`destructive` and `page` as there; pages
+ *      behind a requested page are neither decoded nor judged; page < -1: IMP_ERROR_INVALID_ARGS).
+ *      TAKEN: GIF87a / GIF89a, local and global colour tables of 2..256 entries, min_code_size 2..8, interlaced pages,
+ *      clear codes anywhere including none after the table filled (deferred clear), sides up to 4096, up to 4096 pages.
+ *      REFUSED, IMP_ERROR_UNSUPPORTED (the host decoder's): another signature, a page with no colour table,
+ *      min_code_size outside 2..8, a side above 4096, more than 4096 pages, no page, index planes past 1 GB, a page of
+ *      256 MB or more compressed.
+ *      IMP_ERROR_DECODE_FAILED: a block or sub-block chain past the file's end, a page of zero size, an unknown block
+ *      introducer, no trailer -- and, by the DEVICE's verdict (a status word per page), a code above the next free code, a
+ *      first code after a clear that is not a literal, data that ends before width x height indices, indices beyond them.
+ *      A damaged stream never writes outside its page's plane.  The call waits ONCE, for the status words; no album is
+ *      returned for a damaged file.  The canvas is page 0's size (advancedio.c:134-137), not the logical screen.
+ *      MEASURED (profiles/gif_decode_probe.json; the host side is the library's own plain decoder on
+ *      one thread, impgpu_gif_pages(how = 0), NOT FreeImage, which is not installed): one wave per page is slow for one
+ *      page -- a lone 640x480 page 8.3 ms against 1.0 ms, 320x240 1.9 against 0.26 -- level with the host at about 8
+ *      pages in the call, ahead beyond: a 64-page 640x480 file 9.7 against 63 ms, 64 albums of 8 pages at 320x240 3.0
+ *      against 121 ms.  Not measured: FreeImage's decoder, many host workers decoding side by side, the broker (which
+ *      does not call this path; it has no option for it yet). ---- */
+int impgpu_image_decode_gif(const unsigned char* blob, size_t size, int destructive, int page, impgpu_image** album);
+/* MANY files: one upload, ONE k_gif_lzw launch and ONE k_gif_compose_mix launch for the whole call -- *launches (may be
+ * NULL) is 2, or 0 when no file was accepted.  codes[i] / albums[i] are exactly the lone call's; a refused or damaged
+ * file gets its code alone and changes no other file.  Cut at a file only by $IMPGPU_STAGE_CAP_MB (two launches per
+ * group, in file order).  count is 0..256; NULL arrays with count > 0 or a count outside the range return
+ * IMP_ERROR_INVALID_ARGS with nothing enqueued; without an env the call returns IMP_ERROR_DEVICE and so does every codes[i]. */
+int impgpu_batch_decode_gif(const unsigned char* const* blobs, const size_t* sizes, const int* destructive, const int* page,
+                            int count, impgpu_image** albums, int* codes, int* launches);
+/* host only: the page count and the canvas (page 0's size) of a file these calls would take; impgpu_gif_walk's verdict */
+int impgpu_gif_info(const unsigned char* blob, size_t size, int* count, int* canvas_width, int* canvas_height);
+/* host only, a diagnostic: the index planes of every page in the layout above, one after the other, into `out`
+ * (*length = their bytes; IMP_ERROR_MALLOC_FAILED when `capacity` is less, or `out` is NULL).  how = 0: a plain
+ * sequential LZW decoder; how = 1: the wave's rounds (csrc/imp_gif.h, the kernel's own lane code) one lane after the
+ * other.  A damaged page makes the call IMP_ERROR_DECODE_FAILED; nothing outside the planes is written. */
+int impgpu_gif_pages(const unsigned char* blob, size_t size, int how, unsigned char* out, size_t capacity, size_t* length);
 
 /* ---- batch entry points (benchmark / multi-frame albums: bridge.c:578,591,608,632).
  *      `count` frames of identical geometry, frame i at base + i*frame_stride bytes,

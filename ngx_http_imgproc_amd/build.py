@@ -25,6 +25,7 @@ SOURCES = [
     "imp_jpeg_prog.hip",
     "imp_png.hip",
     "imp_png_enc.hip",
+    "imp_gif.hip",
     "imp_api.cpp",
     "imp_args.cpp",
     "imp_request.cpp",
@@ -34,8 +35,10 @@ SOURCES = [
     "imp_jpeg_prog.cpp",
     "imp_png.cpp",
     "imp_inflate.cpp",
+    "imp_gif.cpp",
 ]
-HEADERS = ["imp_internal.h", "imp_host_pool.h", "imp_jpeg.h", "imp_jpeg_core.h", "imp_jpeg_prog.h", "imp_jpeg_std.h", "imp_png.h", "imp_png_deflate.h", "imp_inflate.h", os.path.join("..", "..", "include", "impgpu.h")]
+HEADERS = ["imp_internal.h", "imp_host_pool.h", "imp_jpeg.h", "imp_jpeg_core.h", "imp_jpeg_prog.h", "imp_jpeg_std.h", "imp_png.h", "imp_png_deflate.h", "imp_inflate.h", "imp_gif.h", os.path.join("..", "..", "include", "impgpu.h"), os.path.join("..", "..", "include", "impgpu_gif.h"),
+           os.path.join("..", "..", "include", "impgpu_broker.h")]
 FLAGS = [
     "--offload-arch=gfx950",
     "-O3",

@@ -488,6 +488,19 @@ __device__ __forceinline__ int mix_pick(const D* __restrict__ d, const MixIndex&
 }
 #endif
 
+// imp_gif.hip: the LZW pages of a call's GIF files, one wavefront per page (impgpu_batch_decode_gif).  A descriptor per
+// page, dealt like every mixed launch's (mix_deal; nblk is 1); the table lies INSIDE the call's device block at `table_off`,
+// and data_off / plane_off count from that block's start: the compressed bytes (the sub-block payloads, concatenated) and
+// the page's index plane, which the kernel writes whole, pad bytes included.  status[slot] gets the page's verdict
+// (imp_gif.h: GIF_LZW_*).
+struct GifLzwDesc {
+    long long data_off, plane_off;
+    uint32_t data_bytes;
+    int w, h, pitch, mcs, interlaced, slot;
+    int first, nblk;
+};
+int launch_gif_lzw(uint8_t* blob, size_t table_off, const MixIndex& ix, int most, uint32_t* status, hipStream_t s);
+
 // The chain kernels of impgpu_batch_run_ops: one launch per channel count over frames of different geometry.
 // imp_pixel.hip: a run of pointwise stages [-> watermark] [-> flatten] on a frame in place.  `prog` must fit one
 // k_pixel_program launch (split_program); an overlay of 3 or 4 channels.

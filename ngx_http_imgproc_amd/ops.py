@@ -862,6 +862,52 @@ def gif_compose(pages, destructive=False, page=-1, album=False):
     return 0, [Image(handle=outs[i]) for i in range(nout)]
 
 
+def decode_gif(blob, destructive=False, page=-1):
+    """impgpu_image_decode_gif: the GIF FILE -> (code, album Image or None): the container walk on the host, the LZW pages
+    (k_gif_lzw) and LoadGIF's compositing loop on the device."""
+    blob = bytes(blob)
+    out = C.c_void_p()
+    rc = lib.impgpu_image_decode_gif(blob, len(blob), int(bool(destructive)), int(page), C.byref(out))
+    return rc, (Image(handle=out.value) if rc == 0 and out.value else None)
+
+
+def batch_decode_gif(files, count=None):
+    """impgpu_batch_decode_gif: files = [(blob, destructive, page), ...] -> (code, [album Image or None ...], [codes],
+    launches).  `count` overrides the count passed to the library (its argument checks)."""
+    n = len(files)
+    m = max(1, n if count is None else count)
+    keep = [bytes(f[0]) for f in files]
+    blobs = (C.c_char_p * m)(*keep)
+    sizes = (C.c_size_t * m)(*[len(b) for b in keep])
+    destr = (C.c_int * m)(*[int(bool(f[1])) for f in files])
+    pages = (C.c_int * m)(*[int(f[2]) for f in files])
+    outs = (C.c_void_p * m)()
+    codes = (C.c_int * m)(*([-1] * m))
+    launches = C.c_int(-1)
+    rc = lib.impgpu_batch_decode_gif(blobs, sizes, destr, pages, n if count is None else count, outs, codes, C.byref(launches))
+    return rc, [Image(handle=outs[i]) if outs[i] else None for i in range(n)], list(codes[:n]), launches.value
+
+
+def gif_info(blob):
+    """impgpu_gif_info (host, no device) -> (code, (pages, canvas width, canvas height))"""
+    n, w, h = C.c_int(), C.c_int(), C.c_int()
+    rc = lib.impgpu_gif_info(bytes(blob), len(blob), n, w, h)
+    return rc, (n.value, w.value, h.value)
+
+
+def gif_pages(blob, how=0):
+    """impgpu_gif_pages (host, no device): every page's index plane (bottom-up, pitch (w + 3) & ~3), one after the other
+    -> (code, bytes or None).  how = 0: a plain sequential LZW decoder; 1: the kernel's rounds run on the host."""
+    blob = bytes(blob)
+    n = C.c_size_t(0)
+    rc = lib.impgpu_gif_pages(blob, len(blob), int(how), None, 0, C.byref(n))
+    if rc != IMP_ERROR_MALLOC_FAILED:
+        return rc, None
+    buf = np.full(max(1, n.value), 0xA5, np.uint8)
+    rc = lib.impgpu_gif_pages(blob, len(blob), int(how), buf.ctypes.data, n.value, C.byref(n))
+    return rc, (buf[: n.value].tobytes() if rc == 0 else None)
+
+
 def batch_filters(ptr, stride, w, h, c, step, count, filters, allow_experiments=1, stream=None):
     """Pointwise filter-* requests on every frame of a resident batch, one fused launch. Returns the IMP_* code."""
     arr = (C.c_char_p * max(1, len(filters)))(*[_b(f) for f in filters])
