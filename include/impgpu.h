@@ -400,6 +400,31 @@ int   impgpu_png_info_ex(const unsigned char* blob, size_t size, int accept, int
 /* Diagnostic (host, no device): the filtered bytes of every non-empty pass in pass order (one item when not interlaced), each
  * pass's rows of (1 filter byte + ceil(pass width * bits per pixel / 8) bytes).  *length as impgpu_png_scanlines. */
 int   impgpu_png_scanlines_ex(const unsigned char* blob, size_t size, int accept, unsigned char* out, size_t capacity, size_t* length);
+/* ---- PNG in, inflated on the device (opt-in: DESIGN.md "PNG decode", the device inflate) ----
+ * IMPGPU_PNG_DEVICE_INFLATE is a further bit of `accept`, NOT part of IMPGPU_PNG_ALL.  It selects HOW files are decoded, not
+ * WHICH: codes[i] / images[i] are what the same call without the bit gives -- the same pixels, refusals and damage verdicts.
+ * impgpu_batch_decode_png_ex with the bit: the host still reads the headers, walks the chunks, checks every CRC and gathers
+ * each accepted file's IDAT payloads into one stream (side by side on the helper threads), but straight into the pinned
+ * buffer, which now holds the COMPRESSED bytes, the palettes and the descriptors; there is one upload; k_png_inflate (one
+ * workgroup of one wavefront per zlib stream: csrc/imp_inflate_lanes.h) inflates every stream into its scanline region,
+ * which exists only on the device, checks every row's filter byte (and clears one above 4); then the launches of the call without the
+ * bit follow unchanged.  *launches is that call's count plus exactly one per group that has a stream to inflate; the groups
+ * are the same (IMPGPU_STAGE_CAP_MB counts the device's scanline bytes).  THIS ROUTE WAITS for the device, once per call,
+ * for the streams' status words: a stream that is damaged or short, or a filter byte above 4, is IMP_ERROR_DECODE_FAILED
+ * with images[i] = NULL, and no other file's result changes.  The calls without the bit still do not wait.  A file whose
+ * IDAT payloads exceed 4 GB - 4 KB is IMP_ERROR_UNSUPPORTED on this route.
+ * impgpu_image_decode_png_ex with the bit decodes through a batch of one: it does NOT stream rows while inflating (and waits).
+ * impgpu_png_info_ex and impgpu_png_scanlines_ex ignore the bit.
+ * One wave per stream is slow for one file and pays with many: the measured crossover is in DESIGN.md and README.md. */
+#define IMPGPU_PNG_DEVICE_INFLATE 8
+/* Diagnostic (host, no device): the wave's own rounds of csrc/imp_inflate_lanes.h, one lane after the other, on one zlib
+ * stream in[0, in_size) into exactly out_size bytes of `out`; never reads outside in[], never writes outside out[].
+ * IMP_OK, or IMP_ERROR_DECODE_FAILED with *status (may be NULL) the stream's status word: 0 = out_size bytes produced,
+ * 1 = damaged, 2 = the input or the final block ended early.  IMP_ERROR_INVALID_ARGS: a NULL buffer, in_size or out_size
+ * of 4 GB - 4 KB or more.  The verdict (zero or not) is the host inflate's (impgpu_png_scanlines) on every input but one:
+ * a stored block that promises more bytes than the input holds is refused when its header is read, where the host inflate
+ * may already have taken up to seven whole bytes its bit buffer held and found the image complete. */
+int   impgpu_png_inflate_lanes(const unsigned char* in, size_t in_size, unsigned char* out, size_t out_size, int* status);
 int   impgpu_image_wrap(void* device_ptr, int width, int height, int channels, int step,
                         impgpu_image** out);               /* borrow memory already in HBM */
 int   impgpu_image_clone(const impgpu_image* src, impgpu_image** out);

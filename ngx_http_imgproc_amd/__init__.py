@@ -15,7 +15,7 @@ from .ops import (  # noqa: F401
     Config, Image, env_start, env_destroy, sync,
     jpeg_info, png_info, png_stage_times, batch_decode_jpeg, batch_decode_jpeg_prepared, batch_decode_png, jpeg_unstuff, jpeg_request_one_wait, batch_encode_jpeg, batch_encode_png, png_deflate, crop_geometry, resize_geometry, filter_check, check_destructive, blur_form,
     JPEG_PROGRESSIVE, batch_decode_jpeg_ex, batch_decode_jpeg_begin_finish_ex, jpeg_info_ex, jpeg_counters,
-    PNG_PALETTE, PNG_LOW_GRAY, PNG_ADAM7, PNG_ALL, png_info_ex, png_scanlines_ex, batch_decode_png_ex,
+    PNG_PALETTE, PNG_LOW_GRAY, PNG_ADAM7, PNG_ALL, PNG_DEVICE_INFLATE, png_inflate_lanes, png_info_ex, png_scanlines_ex, batch_decode_png_ex,
     batch_cv_resize, batch_resize_mixed, ResizeItem, batch_resize_rotate_watermark, batch_filters, run_ops, batch_run_ops, Request, gif_compose,
     batch_calc_perceived_brightness, batch_ascii, batch_gif_compose, gif_page_array, batch_download_fi, batch_album_download,
     decode_gif, batch_decode_gif, gif_info, gif_pages,

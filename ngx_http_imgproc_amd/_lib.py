@@ -140,6 +140,7 @@ SIGNATURES = {
     "impgpu_batch_decode_png_ex": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, PP, IP, IP]),
     "impgpu_png_info_ex": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, IP, IP, IP]),
     "impgpu_png_scanlines_ex": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "impgpu_png_inflate_lanes": (C.c_int, [C.c_char_p, C.c_size_t, P, C.c_size_t, IP]),
     "impgpu_jpeg_coefficients": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, P, C.c_size_t, IP]),
     "impgpu_image_decode_jpeg_ex": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, PP]),
     "impgpu_batch_decode_jpeg_ex": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, PP, IP]),

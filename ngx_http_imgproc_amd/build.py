@@ -24,6 +24,7 @@ SOURCES = [
     "imp_jpeg_enc.hip",
     "imp_jpeg_prog.hip",
     "imp_png.hip",
+    "imp_png_inflate.hip",
     "imp_png_enc.hip",
     "imp_gif.hip",
     "imp_api.cpp",
@@ -37,7 +38,7 @@ SOURCES = [
     "imp_inflate.cpp",
     "imp_gif.cpp",
 ]
-HEADERS = ["imp_internal.h", "imp_host_pool.h", "imp_jpeg.h", "imp_jpeg_core.h", "imp_jpeg_prog.h", "imp_jpeg_std.h", "imp_png.h", "imp_png_deflate.h", "imp_inflate.h", "imp_gif.h", os.path.join("..", "..", "include", "impgpu.h"), os.path.join("..", "..", "include", "impgpu_gif.h"),
+HEADERS = ["imp_internal.h", "imp_host_pool.h", "imp_jpeg.h", "imp_jpeg_core.h", "imp_jpeg_prog.h", "imp_jpeg_std.h", "imp_png.h", "imp_png_deflate.h", "imp_inflate.h", "imp_inflate_lanes.h", "imp_gif.h", os.path.join("..", "..", "include", "impgpu.h"), os.path.join("..", "..", "include", "impgpu_gif.h"),
            os.path.join("..", "..", "include", "impgpu_broker.h")]
 FLAGS = [
     "--offload-arch=gfx950",

@@ -7,7 +7,8 @@
 // gets a batch of one (the latency of the in-process path plus two futex hops), 32 busy workers ride 16-32 to a launch.
 // A batch is one straight pass: take, prepare, decode, operators, answers, finish --
 //     files          impgpu_batch_decode_jpeg_prepared   cvDecodeImage, bridge.c:545-552
-//                    impgpu_batch_decode_png (_ex with --png-accept all)
+//                    impgpu_batch_decode_png (_ex with --png-accept all; --png-inflate device ORs
+//                                                        IMPGPU_PNG_DEVICE_INFLATE into its mask: k_png_inflate)
 //     GIF pages      impgpu_batch_gif_compose            LoadGIF's compositing, advancedio.c:204-247: all GIFs of the batch
 //                                                        in one upload and one launch; each becomes an album
 //     FreeImage bits impgpu_image_upload_fi32            LoadSingle, advancedio.c:295-318 (one by one, like frames)
@@ -27,7 +28,8 @@
 // the answer's placement is the broker's own: it is written to the slot for the worker and never read back from there.
 //
 //   impgpu_broker [--name /impgpu-broker-0] [--device 0] [--slots 64] [--slot-mb 32] [--register-mb 8] [--threads 2] [--batch 64]
-//                 [--gather-us 0] [--png-accept none|all] [--jpeg-accept none|progressive] [--supervise] [--ready-file PATH]
+//                 [--gather-us 0] [--png-accept none|all] [--png-inflate host|device] [--jpeg-accept none|progressive] [--supervise]
+//                 [--ready-file PATH]
 // --supervise: this process only forks and watches; the child is the broker.  A child that dies (a lost device, a bug) is
 // replaced by a FRESH child -- fork() from a parent that never touched the GPU, no exec of a process that did.
 #include <impgpu_broker.h>
@@ -77,6 +79,11 @@ struct Options {
     // --png-accept all: the batch's PNG uploads go through impgpu_batch_decode_png_ex with IMPGPU_PNG_ALL (palette, 1/2/4-bit
     // gray, Adam7); none (the default) keeps the kinds impgpu_batch_decode_png takes.  Refusals are NOT_TAKEN either way.
     int png_accept = 0;
+    // --png-inflate device: IMPGPU_PNG_DEVICE_INFLATE is ORed into that mask -- the uploads' zlib streams are inflated on the
+    // device (one wavefront per stream) instead of on this thread and its helpers; the same files are taken and the same
+    // answers given (the call then waits for the streams' verdicts).  host (the default) keeps the host inflate.  Independent
+    // of --png-accept.
+    int png_inflate = 0;
     // --jpeg-accept progressive: the batch's JPEG uploads go through impgpu_batch_decode_jpeg_prepared_begin_ex with
     // IMPGPU_JPEG_PROGRESSIVE, so a progressive upload (which the workers pass on whole) is answered instead of NOT_TAKEN;
     // none (the default) keeps impgpu_batch_decode_jpeg_prepared.
@@ -509,7 +516,7 @@ struct Worker {
                 png_blobs[j] = reqs[pngs[j]].in;
                 png_sizes[j] = (size_t)reqs[pngs[j]].q.in_bytes;
             }
-            decoded(pngs, impgpu_batch_decode_png_ex(png_blobs.data(), png_sizes.data(), (int)m, O.png_accept, imgs.data(), codes.data(), nullptr));
+            decoded(pngs, impgpu_batch_decode_png_ex(png_blobs.data(), png_sizes.data(), (int)m, O.png_accept | O.png_inflate, imgs.data(), codes.data(), nullptr));
         }
         // every GIF of the batch: one upload of all their pages and ONE compose launch (advancedio.c:204-247), behind the file
         // decodes on the lane's stream.  The answer's image is the album; a page request (in_page >= 0) makes an album of one.
@@ -825,6 +832,10 @@ int supervise(const Options& o) {
 
 }  // namespace
 
+static const char USAGE[] =
+    "usage: impgpu_broker [--name /impgpu-broker-0] [--device 0] [--slots 64] [--slot-mb 32] [--register-mb 8] [--threads 2] [--batch 64] "
+    "[--gather-us 0] [--png-accept none|all] [--png-inflate host|device] [--jpeg-accept none|progressive] [--supervise] [--ready-file PATH]\n";
+
 int main(int argc, char** argv) {
     Options o;
     for (int i = 1; i < argc; i++) {
@@ -848,6 +859,12 @@ int main(int argc, char** argv) {
             else if (v == "none") o.png_accept = 0;
             else { std::fprintf(stderr, "impgpu_broker: --png-accept takes all or none\n"); return 2; }
         }
+        else if (a == "--png-inflate") {
+            const std::string v = val("--png-inflate");
+            if (v == "device") o.png_inflate = IMPGPU_PNG_DEVICE_INFLATE;
+            else if (v == "host") o.png_inflate = 0;
+            else { std::fprintf(stderr, "impgpu_broker: --png-inflate takes host or device\n"); std::fputs(USAGE, stderr); return 2; }
+        }
         else if (a == "--jpeg-accept") {
             const std::string v = val("--jpeg-accept");
             if (v == "progressive") o.jpeg_accept = IMPGPU_JPEG_PROGRESSIVE;
@@ -855,7 +872,7 @@ int main(int argc, char** argv) {
             else { std::fprintf(stderr, "impgpu_broker: --jpeg-accept takes progressive or none\n"); return 2; }
         }
         else if (a == "--supervise") o.supervise = true;
-        else { std::fprintf(stderr, "usage: impgpu_broker [--name /impgpu-broker-0] [--device 0] [--slots 64] [--slot-mb 32] [--register-mb 8] [--threads 2] [--batch 64] [--gather-us 0] [--png-accept none|all] [--jpeg-accept none|progressive] [--supervise] [--ready-file PATH]\n"); return 2; }
+        else { std::fputs(USAGE, stderr); return 2; }
     }
     if (o.slots < 1 || o.slots > IMPB_MAX_SLOTS || o.slot_mb < 1 || o.slot_mb > 4096 || o.threads < 1 || o.threads > 32 || o.batch < 1 || o.batch > 256 ||
         o.name.empty() || o.name[0] != '/') {

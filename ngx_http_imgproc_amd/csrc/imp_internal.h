@@ -501,6 +501,11 @@ struct GifLzwDesc {
 };
 int launch_gif_lzw(uint8_t* blob, size_t table_off, const MixIndex& ix, int most, uint32_t* status, hipStream_t s);
 
+// imp_png_inflate.hip: the zlib streams of a call's PNG files, one workgroup of one wavefront per stream (impgpu_batch_decode_png_ex
+// with IMPGPU_PNG_DEVICE_INFLATE).  `descs` (imp_png.h) lie in device memory; descriptor k is workgroup k's.
+struct PngInflateDesc;
+int launch_png_inflate(const PngInflateDesc* descs, int count, hipStream_t s);
+
 // The chain kernels of impgpu_batch_run_ops: one launch per channel count over frames of different geometry.
 // imp_pixel.hip: a run of pointwise stages [-> watermark] [-> flatten] on a frame in place.  `prog` must fit one
 // k_pixel_program launch (split_program); an overlay of 3 or 4 channels.

@@ -2,14 +2,16 @@
 // chunk layout, CRC; 11.2.2 IHDR; 10.1 the zlib stream across IDAT chunks; 9.2 filter types).  Host code only -- no HIP
 // call -- so that tests/c/fuzz_host.cpp can run it under AddressSanitizer / UBSan on damaged files
 // (tests/test_host_sanitizers.py); impgpu_image_decode_png (imp_png.hip) calls png_scanlines with the pinned staging buffer
-// as its destination.  The inflate is imp_inflate.cpp's (1.6-1.9 x zlib 1.2.11 on scanlines); there is no device inflate in this
-// library.
+// as its destination.  The inflate is imp_inflate.cpp's (1.6-1.9 x zlib 1.2.11 on scanlines).  The opt-in device inflate
+// (IMPGPU_PNG_DEVICE_INFLATE, imp_png_inflate.hip) shares the chunk walk (png_gather_idat); its lanes' logic runs here on
+// the host as a diagnostic (impgpu_png_inflate_lanes).
 #include <zlib.h>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 #include "../../include/impgpu.h"
 #include "imp_inflate.h"
+#include "imp_inflate_lanes.h"
 #include "imp_png.h"
 
 namespace imp {
@@ -57,15 +59,11 @@ bool watch_rows(void* p, size_t produced) {
 }
 }  // namespace
 
-// The IDAT payloads gathered and inflated into exactly raw_bytes of dst; watch(ctx, produced) as rows become final (see
-// RowWatch), its false return ending the inflate with *code (or IMP_ERROR_DECODE_FAILED)
-static int png_inflate(const unsigned char* blob, size_t size, unsigned char* dst, size_t raw_bytes, bool (*watch)(void*, size_t),
-                       void* ctx, const int* code) {
-    // the IDAT payloads are ONE zlib stream (10.1): gathered (a copy of the compressed bytes: 0.3 ms per 3 MB) so that the
-    // inflate can run over one piece of memory
-    static thread_local std::vector<unsigned char> stream;
-    stream.clear();
+// The chunk walk behind the header: every CRC, the chunk rules, the IDAT payloads appended to `vec` or, when that is null,
+// written to dst[0, cap)
+static int png_walk(const unsigned char* blob, size_t size, std::vector<unsigned char>* vec, unsigned char* dst, size_t cap, size_t* length) {
     bool bad = false, seen_idat = false, seen_iend = false;
+    size_t n = 0;
     for (size_t at = 8 + 25; !bad && !seen_iend;) {
         if (size - at < 12) { bad = true; break; }
         const unsigned len = be32(blob + at);
@@ -76,7 +74,10 @@ static int png_inflate(const unsigned char* blob, size_t size, unsigned char* ds
         if (crc32_ieee(kind, 4 + (size_t)len) != be32(blob + at + 8 + len)) { bad = true; break; }
         if (!std::memcmp(kind, "IDAT", 4)) {
             seen_idat = true;
-            stream.insert(stream.end(), blob + at + 8, blob + at + 8 + len);
+            if (vec) vec->insert(vec->end(), blob + at + 8, blob + at + 8 + len);
+            else if (cap - n < len) { bad = true; break; }
+            else std::memcpy(dst + n, blob + at + 8, len);
+            n += len;
         } else if (!std::memcmp(kind, "IEND", 4)) {
             seen_iend = true;
         } else if (critical && std::memcmp(kind, "PLTE", 4) != 0) {
@@ -85,6 +86,24 @@ static int png_inflate(const unsigned char* blob, size_t size, unsigned char* ds
         at += 12 + (size_t)len;
     }
     if (bad || !seen_idat) return IMP_ERROR_DECODE_FAILED;
+    if (length) *length = n;
+    return IMP_OK;
+}
+
+int png_gather_idat(const unsigned char* blob, size_t size, unsigned char* dst, size_t cap, size_t* length) {
+    if (size < 8 + 25) return IMP_ERROR_DECODE_FAILED;
+    return png_walk(blob, size, nullptr, dst, cap, length);
+}
+
+// The IDAT payloads gathered and inflated into exactly raw_bytes of dst; watch(ctx, produced) as rows become final (see
+// RowWatch), its false return ending the inflate with *code (or IMP_ERROR_DECODE_FAILED)
+static int png_inflate(const unsigned char* blob, size_t size, unsigned char* dst, size_t raw_bytes, bool (*watch)(void*, size_t),
+                       void* ctx, const int* code) {
+    // the IDAT payloads are ONE zlib stream (10.1): gathered (a copy of the compressed bytes: 0.3 ms per 3 MB) so that the
+    // inflate can run over one piece of memory
+    static thread_local std::vector<unsigned char> stream;
+    stream.clear();
+    if (png_walk(blob, size, &stream, nullptr, 0, nullptr)) return IMP_ERROR_DECODE_FAILED;
     // exactly the image's bytes: a stream that ends early fails, whatever follows the last scanline is not read (libpng's rule)
     // IMPGPU_PNG_INFLATE=zlib (read per call): the audited library instead of this repository's one-shot inflate -- an operator's
     // choice for a worker that decompresses untrusted input; 1.3-1.6 x slower (profiles/r04_png_probe_zlib.json), same bytes
@@ -262,6 +281,7 @@ int impgpu_png_scanlines(const unsigned char* blob, size_t size, unsigned char* 
 }
 
 int impgpu_png_info_ex(const unsigned char* blob, size_t size, int accept, int* width, int* height, int* channels) {
+    accept &= ~IMPGPU_PNG_DEVICE_INFLATE;                            // (how a file is decoded, not which: nothing to do with its header)
     if (!accept) return impgpu_png_info(blob, size, width, height, channels);
     PngHeader H;
     int rc = png_header(blob, size, &H);
@@ -275,6 +295,7 @@ int impgpu_png_info_ex(const unsigned char* blob, size_t size, int accept, int* 
 }
 
 int impgpu_png_scanlines_ex(const unsigned char* blob, size_t size, int accept, unsigned char* out, size_t capacity, size_t* length) {
+    accept &= ~IMPGPU_PNG_DEVICE_INFLATE;
     if (!accept) return impgpu_png_scanlines(blob, size, out, capacity, length);
     PngHeader H;
     int rc = png_header(blob, size, &H);
@@ -285,6 +306,19 @@ int impgpu_png_scanlines_ex(const unsigned char* blob, size_t size, int accept, 
     if (L.raw / 1032 > size) return IMP_ERROR_DECODE_FAILED;
     if (!out || capacity < L.raw) return IMP_ERROR_MALLOC_FAILED;
     return png_scanlines_items(blob, size, L, out);
+}
+
+int impgpu_png_inflate_lanes(const unsigned char* in, size_t in_size, unsigned char* out, size_t out_size, int* status) {
+    if (status) *status = INF_DAMAGED;
+    if ((!in && in_size) || (!out && out_size) || in_size >= INF_MAX_IN || out_size >= INF_MAX_OUT) return IMP_ERROR_INVALID_ARGS;
+    // the stream as the device holds it: word aligned, zero behind its last byte
+    const uint32_t cap = (uint32_t)((in_size + 3) & ~(size_t)3);
+    std::vector<uint32_t> staged(cap / 4 + 1, 0u);
+    if (in_size) std::memcpy(staged.data(), in, in_size);
+    std::vector<InfMem> mem(1);
+    const int st = inf_lanes_host((const uint8_t*)staged.data(), cap, (uint32_t)in_size, out, (uint32_t)out_size, mem.data());
+    if (status) *status = st;
+    return st == INF_OK ? IMP_OK : IMP_ERROR_DECODE_FAILED;
 }
 
 }  // extern "C"

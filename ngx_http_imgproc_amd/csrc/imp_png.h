@@ -23,6 +23,26 @@ int png_header(const unsigned char* blob, size_t size, PngHeader* H);
 typedef int (*png_rows_fn)(void* ctx, int complete);
 int png_scanlines(const unsigned char* blob, size_t size, const PngHeader& H, unsigned char* dst, png_rows_fn rows = nullptr, void* ctx = nullptr);
 
+// The part of a decode before the inflate, shared by the host route (png_scanlines*) and the device route (imp_png.hip,
+// IMPGPU_PNG_DEVICE_INFLATE): the chunk walk of a file whose header png_header read, every CRC checked, and the IDAT payloads
+// gathered, in order, into dst[0, cap) -- they are ONE zlib stream (PNG specification 10.1).  IMP_OK with *length, or
+// IMP_ERROR_DECODE_FAILED (a damaged chunk, an unknown critical chunk, no IDAT, no IEND; cap too small cannot happen for
+// cap >= size).
+int png_gather_idat(const unsigned char* blob, size_t size, unsigned char* dst, size_t cap, size_t* length);
+
+// ---- the device inflate (imp_png_inflate.hip): one descriptor per zlib stream, one workgroup of one wavefront each
+struct PngInflateDesc {
+    const uint8_t* in;                   // the compressed bytes: 16-byte aligned, in_cap (a multiple of 4) bytes readable, zero behind in_size
+    uint32_t in_size, in_cap;
+    uint8_t* out;                        // the scanline region: out_size bytes are inflated, `slack` more are cleared
+    uint32_t out_size, slack;
+    const uint32_t* pal;                 // a palette file: 256 words to copy to pal_dst (the end of its region); else null
+    uint32_t* pal_dst;
+    int nitems;                          // the stream's row layout: per item its rows and rowbytes + 1
+    uint32_t rows[7], stride[7];
+    uint32_t* status;                    // the stream's status word (imp_inflate_lanes.h: INF_*)
+};
+
 // ---- the kinds the _ex calls take besides (impgpu_*_png_ex: palette, 1/2/4-bit gray, Adam7)
 // An ITEM is a run of filtered rows that the unfilter kernels take as one job: the whole file when it is not interlaced, one
 // non-empty Adam7 pass otherwise (PNG specification 8.2: an empty pass has no rows at all, not even filter bytes).

@@ -4,8 +4,9 @@
 // filtering section 9, zlib stream section 10) and what OpenCV asks libpng for with the "unchanged" flag: 8-bit gray stays
 // one channel, RGB becomes BGR, RGBA becomes BGRA, a tRNS chunk is not expanded.
 //
-// ROUND 4, A BOUNDED EXPERIMENT: the zlib stream is inflated ON THE HOST (imp_png.cpp / imp_inflate.cpp:
-// there is no device inflate here) into the pinned staging buffer, the filtered scanlines cross the link as they are -- in
+// ROUND 4, A BOUNDED EXPERIMENT: the zlib stream is inflated ON THE HOST (imp_png.cpp / imp_inflate.cpp;
+// the batch call's opt-in device route, IMPGPU_PNG_DEVICE_INFLATE, is png_group's `status` branch and imp_png_inflate.hip) into
+// the pinned staging buffer, the filtered scanlines cross the link as they are -- in
 // slices of 128 rows, WHILE the inflate is still running -- and k_png_unfilter undoes the five scanline filters and swaps R/B on
 // the device.  Unfiltering is a recurrence along x (Sub, Average, Paeth read the pixel to the left) and along y (Up, Average,
 // Paeth read the row above), so a slice is ONE workgroup that walks it as a wavefront: lane l of a wave owns row 64 * band + l
@@ -19,6 +20,7 @@
 #include <cstring>
 #include "imp_host_pool.h"
 #include "imp_internal.h"
+#include "imp_inflate_lanes.h"
 #include "imp_png.h"
 
 namespace imp {
@@ -410,6 +412,7 @@ struct PngBatchFile {
     size_t raw = 0, off = 0;                 // scanline bytes; their region in the group's buffer
     size_t region = 0;                       // bytes of that region: scanlines, slack, the palette of a palette file
     size_t poff = 0;                         // an item file's planes: their place in the group's plane buffer
+    size_t coff = 0, ccap = 0, clen = 0;     // the device route: the compressed stream's place, room and length in the pinned buffer
 };
 // the plane of an item: its unfiltered rows, 4-byte aligned
 size_t png_plane_step(const PngItem& it) { return (it.rowbytes + 3) & ~(size_t)3; }
@@ -438,8 +441,12 @@ static size_t png_group_cap() {
 // planes of a second device buffer (rows of bytes: the filter unit is the launch's bpp, the R/B swap of 3 / 4 makes the
 // planes B,G,R(,A)), and k_png_place then writes those files' frames, one launch per channel count.  A group of plain files
 // alone makes exactly the launches it made before the item files existed.
+// `status` (device words, one per file of the call; null: the host route): the DEVICE route -- the files' chunks are walked and
+// their IDAT payloads gathered side by side into the pinned buffer, which then holds the compressed streams, the palettes
+// and the k_png_inflate descriptors and is uploaded once; k_png_inflate fills the scanline regions, which keep their layout
+// but exist only on the device, and leaves every stream's verdict in status[file]; everything behind is the host route's.
 static int png_group(const unsigned char* const* blobs, const size_t* sizes, std::vector<PngBatchFile>& F, const std::vector<int>& idx,
-                     impgpu_image** images, int* codes) {
+                     impgpu_image** images, int* codes, uint32_t* status = nullptr) {
     size_t total = 0, ptotal = 0;
     for (int i : idx) {
         PngBatchFile& f = F[(size_t)i];
@@ -451,21 +458,76 @@ static int png_group(const unsigned char* const* blobs, const size_t* sizes, std
         }
     }
     void *host = nullptr, *token = nullptr;
-    int rc = stage_begin(total, &host, &token);
-    if (rc) return rc;
-    uint8_t* hb = (uint8_t*)host;
-    auto inflate = [&](int i) {
-        PngBatchFile& f = F[(size_t)i];
-        std::memset(hb + f.off + f.raw, 0, PNG_RAW_SLACK);
-        if (f.L.palette) std::memcpy(hb + f.off + f.region - sizeof f.L.pal, f.L.pal, sizeof f.L.pal);
-        codes[i] = f.L.plain ? png_scanlines(blobs[i], sizes[i], f.H, hb + f.off) : png_scanlines_items(blobs[i], sizes[i], f.L, hb + f.off);
-    };
-    host_parallel(idx, total, inflate);
+    int rc = IMP_OK;
     void* dev = nullptr;
-    rc = dev_alloc(total, &dev);
-    if (rc) { (void)stage_upload(token, nullptr, 0); return rc; }
-    rc = stage_upload(token, dev, total);
-    if (rc) { dev_free(dev); return rc; }
+    if (!status) {
+        rc = stage_begin(total, &host, &token);
+        if (rc) return rc;
+        uint8_t* hb = (uint8_t*)host;
+        auto inflate = [&](int i) {
+            PngBatchFile& f = F[(size_t)i];
+            std::memset(hb + f.off + f.raw, 0, PNG_RAW_SLACK);
+            if (f.L.palette) std::memcpy(hb + f.off + f.region - sizeof f.L.pal, f.L.pal, sizeof f.L.pal);
+            codes[i] = f.L.plain ? png_scanlines(blobs[i], sizes[i], f.H, hb + f.off) : png_scanlines_items(blobs[i], sizes[i], f.L, hb + f.off);
+        };
+        host_parallel(idx, total, inflate);
+        rc = dev_alloc(total, &dev);
+        if (rc) { (void)stage_upload(token, nullptr, 0); return rc; }
+        rc = stage_upload(token, dev, total);
+        if (rc) { dev_free(dev); return rc; }
+    } else {
+        // the pinned buffer: per file its compressed stream (no longer than the file) with zeroed slack to a 16-byte boundary
+        // and, for a palette file, its palette; the descriptors behind them
+        size_t ctotal = 0;
+        for (int i : idx) {
+            PngBatchFile& f = F[(size_t)i];
+            f.coff = ctotal;
+            f.ccap = (sizes[i] + 16 + 15) & ~(size_t)15;
+            ctotal += f.ccap + (f.L.palette ? sizeof f.L.pal : 0);
+        }
+        const size_t desc_off = ctotal;
+        ctotal += idx.size() * sizeof(PngInflateDesc);
+        rc = stage_begin(ctotal, &host, &token);
+        if (rc) return rc;
+        uint8_t* hb = (uint8_t*)host;
+        auto gather = [&](int i) {
+            PngBatchFile& f = F[(size_t)i];
+            f.clen = 0;
+            codes[i] = png_gather_idat(blobs[i], sizes[i], hb + f.coff, f.ccap - 16, &f.clen);
+            if (codes[i] == IMP_OK && f.clen >= INF_MAX_IN) codes[i] = IMP_ERROR_UNSUPPORTED;
+            if (codes[i] != IMP_OK) return;
+            std::memset(hb + f.coff + f.clen, 0, f.ccap - f.clen);
+            if (f.L.palette) std::memcpy(hb + f.coff + f.ccap, f.L.pal, sizeof f.L.pal);
+        };
+        host_parallel(idx, total, gather);
+        void* cdev = nullptr;
+        rc = dev_alloc(total, &dev);
+        if (!rc && (rc = dev_alloc(ctotal, &cdev)) != IMP_OK) dev_free(dev);
+        if (rc) { (void)stage_upload(token, nullptr, 0); return rc; }
+        PngInflateDesc* descs = (PngInflateDesc*)(hb + desc_off);
+        int nd = 0;
+        for (int i : idx) {
+            if (codes[i] != IMP_OK) continue;
+            const PngBatchFile& f = F[(size_t)i];
+            PngInflateDesc d{};
+            d.in = (const uint8_t*)cdev + f.coff;
+            d.in_size = (uint32_t)f.clen; d.in_cap = (uint32_t)f.ccap;
+            d.out = (uint8_t*)dev + f.off;
+            d.out_size = (uint32_t)f.raw; d.slack = PNG_RAW_SLACK;
+            if (f.L.palette) {
+                d.pal = (const uint32_t*)((const uint8_t*)cdev + f.coff + f.ccap);
+                d.pal_dst = (uint32_t*)((uint8_t*)dev + f.off + f.region - sizeof f.L.pal);
+            }
+            d.nitems = f.L.n;
+            for (int k = 0; k < f.L.n; k++) { d.rows[k] = (uint32_t)f.L.item[k].h; d.stride[k] = (uint32_t)(f.L.item[k].rowbytes + 1); }
+            d.status = status + i;
+            descs[nd++] = d;
+        }
+        rc = stage_upload(token, cdev, ctotal);
+        if (!rc) rc = launch_png_inflate((const PngInflateDesc*)((const uint8_t*)cdev + desc_off), nd, env_stream());
+        dev_free(cdev);                                              // (handed out again in lane-stream order)
+        if (rc) { dev_free(dev); return rc; }
+    }
     void* planes = nullptr;
     if (ptotal && (rc = dev_alloc(ptotal, &planes))) { dev_free(dev); return rc; }
     std::vector<PngJob> jobs[5];
@@ -553,6 +615,9 @@ int impgpu_batch_decode_png_ex(const unsigned char* const* blobs, const size_t* 
     const unsigned long long launched = t_launches;
     TraceRange tr("IMP_STEP_DECODE");
     IMP_FAULT_POINT(IMP_STEP_DECODE);
+    // IMPGPU_PNG_DEVICE_INFLATE selects how the taken files are decoded, not which are taken
+    const int kinds = accept & ~IMPGPU_PNG_DEVICE_INFLATE;
+    const bool dev_inflate = (accept & IMPGPU_PNG_DEVICE_INFLATE) != 0;
     // headers on the calling thread: what impgpu_image_decode_png refuses before it stages anything is refused here alike
     std::vector<PngBatchFile> F((size_t)count);
     std::vector<int> taken;
@@ -561,7 +626,7 @@ int impgpu_batch_decode_png_ex(const unsigned char* const* blobs, const size_t* 
         PngBatchFile& f = F[(size_t)i];
         codes[i] = png_header(blobs[i], sizes[i], &f.H);
         if (codes[i]) continue;
-        if ((codes[i] = png_layout(blobs[i], sizes[i], f.H, accept, &f.L))) continue;
+        if ((codes[i] = png_layout(blobs[i], sizes[i], f.H, kinds, &f.L))) continue;
         f.raw = f.L.raw;
         if (f.raw / 1032 > sizes[i]) { codes[i] = IMP_ERROR_DECODE_FAILED; continue; }
         f.region = (f.raw + PNG_RAW_SLACK + PNG_REGION_ALIGN - 1) / PNG_REGION_ALIGN * PNG_REGION_ALIGN + (f.L.palette ? sizeof f.L.pal : 0);
@@ -570,6 +635,12 @@ int impgpu_batch_decode_png_ex(const unsigned char* const* blobs, const size_t* 
     // groups in file order, each within the staging cap
     const size_t cap = png_group_cap();
     int rc = IMP_OK;
+    void* status = nullptr;                                          // the device route: a status word per file of the call
+    if (dev_inflate && !taken.empty() && (rc = dev_alloc((size_t)count * sizeof(uint32_t), &status))) {
+        for (int i : taken) codes[i] = rc;
+        return rc;
+    }
+    std::vector<int> ran;
     for (size_t a = 0; a < taken.size() && !rc;) {
         std::vector<int> idx;
         size_t bytes = 0;
@@ -580,11 +651,33 @@ int impgpu_batch_decode_png_ex(const unsigned char* const* blobs, const size_t* 
             idx.push_back(taken[a]);
             bytes += need;
         }
-        rc = png_group(blobs, sizes, F, idx, images, codes);
+        rc = png_group(blobs, sizes, F, idx, images, codes, (uint32_t*)status);
+        if (!rc && status) ran.insert(ran.end(), idx.begin(), idx.end());
         if (rc) {                                                    // (a device error: no frame of this group or a later one)
             for (int i : idx) if (codes[i] == IMP_OK) codes[i] = rc;
             for (size_t b = a; b < taken.size(); b++) codes[taken[b]] = rc;
         }
+    }
+    if (status) {
+        // the ONE wait of the device route: every stream's status word (the groups' launches are all enqueued by now)
+        uint32_t* box = lane_mailbox();
+        int rcs = box ? IMP_OK : IMP_ERROR_DEVICE;
+        if (!rcs) {
+            const hipError_t e = hipMemcpyAsync(box, status, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost, env_stream());
+            if (e != hipSuccess) { set_error("hipMemcpyAsync(batch_decode_png status)", e); rcs = IMP_ERROR_DEVICE; }
+        }
+        dev_free(status);
+        const int rcw = lane_wait();
+        if (!rcs) rcs = rcw;
+        for (int i : ran) {
+            if (codes[i] != IMP_OK) continue;
+            const int code = rcs ? rcs : box[i] != INF_OK ? IMP_ERROR_DECODE_FAILED : IMP_OK;
+            if (!code) continue;
+            image_delete(images[i]);                                 // (the frame of a damaged stream is released; no other file changes)
+            images[i] = nullptr;
+            codes[i] = code;
+        }
+        if (!rc) rc = rcs;
     }
     if (launches) *launches = (int)(t_launches - launched);
     return rc;
@@ -597,7 +690,8 @@ int impgpu_image_decode_png_ex(const unsigned char* blob, size_t size, int accep
     PngHeader H;
     int rc = png_header(blob, size, &H);
     if (rc) return rc;
-    if (H.taken || !accept) return impgpu_image_decode_png(blob, size, out);       // (today's kinds stream their rows)
+    const bool dev_inflate = (accept & IMPGPU_PNG_DEVICE_INFLATE) != 0;          // (a batch of one: nothing streams while the device inflates)
+    if (!dev_inflate && (H.taken || !accept)) return impgpu_image_decode_png(blob, size, out);       // (today's kinds stream their rows)
     // every other kind: a batch of one (its items are the launch's workgroups)
     int code = IMP_OK;
     rc = impgpu_batch_decode_png_ex(&blob, &size, 1, accept, out, &code, nullptr);

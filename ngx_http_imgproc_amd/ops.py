@@ -31,6 +31,7 @@ PNG_PALETTE = 1
 PNG_LOW_GRAY = 2
 PNG_ADAM7 = 4
 PNG_ALL = PNG_PALETTE | PNG_LOW_GRAY | PNG_ADAM7
+PNG_DEVICE_INFLATE = 8          # not part of PNG_ALL: how files are decoded (k_png_inflate), not which are taken
 
 
 def _b(s):
@@ -737,6 +738,16 @@ def png_scanlines_ex(blob, accept):
     buf = np.zeros(max(1, n.value), np.uint8)
     rc = lib.impgpu_png_scanlines_ex(bytes(blob), len(blob), int(accept), buf.ctypes.data, buf.size, C.byref(n))
     return rc, (buf[: n.value].tobytes() if rc == 0 else None)
+
+
+def png_inflate_lanes(stream, out_size):
+    """impgpu_png_inflate_lanes (host, no device): the device inflate's rounds, lane after lane, on one zlib stream into exactly
+    out_size bytes -> (code, status word, bytes or None)"""
+    stream = bytes(stream)
+    buf = np.zeros(max(int(out_size), 1), np.uint8)
+    st = C.c_int(-1)
+    rc = lib.impgpu_png_inflate_lanes(stream, len(stream), buf.ctypes.data, int(out_size), C.byref(st))
+    return rc, st.value, (buf[:int(out_size)].tobytes() if rc == 0 else None)
 
 
 def png_stage_times():
