@@ -679,6 +679,53 @@ int impgpu_gif_info(const unsigned char* blob, size_t size, int* count, int* can
  * sequential LZW decoder; how = 1: the wave's rounds (csrc/imp_gif.h, the kernel's own lane code) one lane after the
  * other.  A damaged page makes the call IMP_ERROR_DECODE_FAILED; nothing outside the planes is written. */
 int impgpu_gif_pages(const unsigned char* blob, size_t size, int how, unsigned char* out, size_t capacity, size_t* length);
+/* ---- the same calls with `flags`.  flags == 0 is the call above in every respect: answers, codes, *launches == 2.  Any bit
+ *      other than IMPGPU_GIF_SPLIT is IMP_ERROR_INVALID_ARGS before a device is looked for.
+ *      IMPGPU_GIF_SPLIT (opt-in; the route never switches by size on its own): LZW is sequential only BETWEEN clear codes --
+ *      behind one the decoder's state is known (an empty table, codes of min_code_size + 1 bits), and every mainstream
+ *      encoder clears when the table fills, every 5.4 KB of noise at min_code_size 8.  So a page is cut at its clear
+ *      codes and a wavefront decodes every SEGMENT.  Four launches per group where the call above makes two:
+ *        k_gif_lzw_scan  a wavefront per page walks the codes WITHOUT a table (a code's width depends only on the count
+ *                        of codes since the last clear; rounds of 1024 codes, 16 per lane, their loads in flight
+ *                        together) and writes the page's segments {start bit, end bit}.  Segment 0
+ *                        starts at bit 0.  THE CUT RULE: a clear code is a cut -- the segment ends just behind it and
+ *                        the next starts there -- when at least IMPGPU_GIF_SPLIT_MIN_BYTES of stream lie between the
+ *                        segment's start and the bit behind the clear (and the page's table of data_bytes /
+ *                        IMPGPU_GIF_SPLIT_MIN_BYTES + 1 segments has room, which it always has); any other clear stays
+ *                        inside its segment and is handled by that segment's decoder like in the one-wave route.  The
+ *                        scan stops where a decoder would stop for a reason visible without a table: end-of-information,
+ *                        no data, a code above the free code, a first-after-clear code that is no literal.
+ *        k_gif_lzw_len   a wavefront per segment SLOT (the grid is the host's bound, the sum of the pages' table sizes;
+ *                        a slot at or past the page's count returns at once): the rounds without their stores -- how
+ *                        many indices the segment holds, and whether it ended on an invalid code.
+ *        k_gif_lzw_emit  a wavefront per slot: the same rounds with their stores, at the sum of the earlier segments'
+ *                        lengths; segment 0's wavefront writes the pad bytes and the page's status word, folded from
+ *                        the segments' records in stream order to exactly the one-wave decoder's verdict.  (A page of
+ *                        ONE segment skips the length pass: its emit wavefront runs the one-wave loop.)
+ *        k_gif_compose_mix  as above.
+ *      Every stage reads what the stage before wrote across a kernel boundary of one stream: no wavefront waits for
+ *      another workgroup.  Upload, plane layout, grouping by $IMPGPU_STAGE_CAP_MB, the status word per page, the one
+ *      wait, refusals, codes and albums are the flag-less call's, file by file; the segment tables lie in the same
+ *      device block behind the planes.  Which clears become cuts changes no answer.
+ *      MEASURED (profiles/gif_split_probe.json, one session, the one-wave route and the library's plain
+ *      host decoder on one thread beside it; ms per call): a lone 640x480 page of 33 segments 1.09 against 6.43 one-wave and
+ *      0.65 host; a photo-like 640x480 page of 52 segments 1.48 / 9.87 / 1.18; a 1920x1080 page of 407 segments 9.0 / 77.3 /
+ *      8.7; an 8-page 640x480 file 1.20 / 6.62 / 5.28; 64 single-page 640x480 files 1.97 / 6.90 / 41.2.  The split route
+ *      is 2-8.5x the one-wave route wherever a page has several segments and a call has fewer segments than the device
+ *      runs side by side; it is level (within 10 %) for single-segment pages and for calls of 512 pages, and
+ *      BEHIND at 64 albums of 64 pages at 320x240 (18.3 against 15.9 ms: the rounds run twice).  A LONE page is still
+ *      behind one host core (1.7x at 640x480, level at 1080p): k_gif_lzw_scan, the one sequential walk that is left, takes
+ *      0.67 of the 1.09 ms (len 0.16, emit 0.20).  IMPGPU_GIF_SPLIT_MIN_BYTES has not been tuned. ---- */
+#define IMPGPU_GIF_SPLIT 1
+#define IMPGPU_GIF_SPLIT_MIN_BYTES 2048
+int impgpu_image_decode_gif_ex(const unsigned char* blob, size_t size, int destructive, int page, int flags, impgpu_image** album);
+/* *launches (may be NULL): 4 per group with IMPGPU_GIF_SPLIT, 2 without, 0 when no file was accepted */
+int impgpu_batch_decode_gif_ex(const unsigned char* const* blobs, const size_t* sizes, const int* destructive, const int* page,
+                               int count, int flags, impgpu_image** albums, int* codes, int* launches);
+/* host, no device: the planes as impgpu_gif_pages lays them out, made by the three passes' own lane code run one lane after
+ * the other; segments[f] (may be NULL; pages_capacity entries) = the number of segments page f was cut into */
+int impgpu_gif_pages_split(const unsigned char* blob, size_t size, unsigned char* out, size_t capacity, size_t* length,
+                           int* segments, int pages_capacity);
 
 /* ---- batch entry points (benchmark / multi-frame albums: bridge.c:578,591,608,632).
  *      `count` frames of identical geometry, frame i at base + i*frame_stride bytes,

@@ -166,6 +166,9 @@ SIGNATURES = {
     "impgpu_batch_decode_gif": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), IP, IP, C.c_int, PP, IP, IP]),
     "impgpu_gif_info": (C.c_int, [C.c_char_p, C.c_size_t, IP, IP, IP]),
     "impgpu_gif_pages": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "impgpu_image_decode_gif_ex": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int, PP]),
+    "impgpu_batch_decode_gif_ex": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), IP, IP, C.c_int, C.c_int, PP, IP, IP]),
+    "impgpu_gif_pages_split": (C.c_int, [C.c_char_p, C.c_size_t, P, C.c_size_t, C.POINTER(C.c_size_t), IP, C.c_int]),
     "impgpu_album_download_fi": (C.c_int, [P, C.c_int, PP, IP]),
     "impgpu_batch_download_fi": (C.c_int, [PP, IP, C.c_int, PP, IP, IP, IP]),
     "impgpu_batch_album_download": (C.c_int, [PP, C.c_int, PP, IP, IP]),

@@ -3,7 +3,8 @@
 // palettes and COMPRESSED pages out in one staging blob -- impgpu_batch_gif_compose's layout with the sub-block payloads
 // where the index planes were -- and reserves the planes behind it in the same device block: one upload, k_gif_lzw
 // (imp_gif.hip) decodes every page into its plane, k_gif_compose_mix (imp_geom.hip) follows on the same stream, and the
-// call waits once, for the pages' status words.
+// call waits once, for the pages' status words.  With IMPGPU_GIF_SPLIT three launches stand where k_gif_lzw is one: the
+// pages are cut at their clear codes and a wavefront decodes every segment; the segment tables lie behind the planes.
 #include "imp_internal.h"
 #include "imp_gif.h"
 #include "../../include/impgpu_gif.h"
@@ -31,6 +32,7 @@ struct GifPlan {
     size_t first_desc;               // its pages in `descs`
     size_t up_bytes, plane_bytes;    // what it puts into the upload, and behind it
     int slot0;                       // its first status word
+    long long seg_slots;             // IMPGPU_GIF_SPLIT: the segment slots of its pages (gif_seg_cap each)
 };
 
 }  // namespace imp
@@ -47,9 +49,16 @@ int impgpu_gif_pages(const unsigned char* blob, size_t size, int how, unsigned c
     return gif_pages_host(blob, size, how, out, capacity, length);
 }
 
-int impgpu_batch_decode_gif(const unsigned char* const* blobs, const size_t* sizes, const int* destructive, const int* page,
-                            int count, impgpu_image** albums, int* codes, int* launches) {
+int impgpu_gif_pages_split(const unsigned char* blob, size_t size, unsigned char* out, size_t capacity, size_t* length,
+                           int* segments, int pages_capacity) {
+    return gif_pages_split_host(blob, size, out, capacity, length, segments, pages_capacity);
+}
+
+int impgpu_batch_decode_gif_ex(const unsigned char* const* blobs, const size_t* sizes, const int* destructive, const int* page,
+                               int count, int flags, impgpu_image** albums, int* codes, int* launches) {
     if (launches) *launches = 0;
+    if (flags & ~IMPGPU_GIF_SPLIT) return IMP_ERROR_INVALID_ARGS;
+    const bool split = (flags & IMPGPU_GIF_SPLIT) != 0;
     if (count < 0 || count > 256 || (count > 0 && (!blobs || !sizes || !destructive || !page || !albums || !codes))) return IMP_ERROR_INVALID_ARGS;
     for (int i = 0; i < count; i++) albums[i] = nullptr;
     if (int rc = need_env()) {
@@ -72,13 +81,14 @@ int impgpu_batch_decode_gif(const unsigned char* const* blobs, const size_t* siz
             destr = 1;
             if (only > n - 1) only = 0;
         }
-        GifPlan pl{i, only >= 0 ? only + 1 : n, only >= 0 ? 1 : n, destr, only, cw, ch, descs.size(), 0, 0, slots};
+        GifPlan pl{i, only >= 0 ? only + 1 : n, only >= 0 ? 1 : n, destr, only, cw, ch, descs.size(), 0, 0, slots, 0};
         pl.up_bytes = head_bytes(pl.npages, pl.nout);
         bool huge = false;
         for (int f = 0; f < pl.npages; f++) {                      // pages behind the requested one are neither decoded nor judged
             huge = huge || walked[f].data_bytes >= GIF_DATA_MAX;
             pl.up_bytes += 1024 + up16(walked[f].data_bytes);
             pl.plane_bytes += up16((size_t)gif_pitch(walked[f].width) * walked[f].height);
+            if (!huge) pl.seg_slots += gif_seg_cap((uint32_t)walked[f].data_bytes);
         }
         if (huge || pl.plane_bytes > GIF_PLANES_MAX) { codes[i] = IMP_ERROR_UNSUPPORTED; continue; }
         codes[i] = image_new_album(cw, ch, 4, pl.nout, &albums[i]);
@@ -96,29 +106,38 @@ int impgpu_batch_decode_gif(const unsigned char* const* blobs, const size_t* siz
     for (size_t g0 = 0; g0 < plans.size();) {
         // the group [g0, g1): as many files as the staging cap and the grid take (impgpu_batch_gif_compose's cut)
         size_t g1 = g0, bytes = 0, planes = 0;
-        long long blocks = 0;
+        long long blocks = 0, nslots = 0;
         int npages = 0;
-        auto front = [&](int n, int pages) { return gif_mix_table_bytes(n) + up16((size_t)pages * sizeof(GifLzwDesc)); };
+        // (IMPGPU_GIF_SPLIT: the pages' GifSplitPage and the slot table travel behind the LZW descriptors)
+        auto split_off = [&](int n, int pages) { return gif_mix_table_bytes(n) + up16((size_t)pages * sizeof(GifLzwDesc)); };
+        auto front = [&](int n, int pages, long long nsl) {
+            return split_off(n, pages) + (split ? up16((size_t)pages * sizeof(GifSplitPage)) + up16((size_t)nsl * sizeof(GifSegSlot)) : 0);
+        };
         while (g1 < plans.size()) {
             const GifPlan& pl = plans[g1];
             const long long nb = ((long long)pl.cw * pl.ch + 255) / 256;
-            if (g1 > g0 && ((cap && front((int)(g1 - g0 + 1), npages + pl.npages) + bytes + pl.up_bytes > cap) || (blocks + nb) * 8 > 0x7fffffffLL)) break;
+            if (g1 > g0 && ((cap && front((int)(g1 - g0 + 1), npages + pl.npages, nslots + pl.seg_slots) + bytes + pl.up_bytes > cap) ||
+                            (blocks + nb) * 8 > 0x7fffffffLL || (split && nslots + pl.seg_slots > 0x7fffffffLL))) break;
             bytes += pl.up_bytes;
             planes += pl.plane_bytes;
             npages += pl.npages;
             blocks += nb;
+            nslots += pl.seg_slots;
             g1++;
         }
         const int n = (int)(g1 - g0);
         const size_t lzw_off = gif_mix_table_bytes(n);
-        const size_t upload = front(n, npages) + bytes, total = upload + planes;
+        const size_t pages_off = split_off(n, npages), slots_off = pages_off + up16((size_t)npages * sizeof(GifSplitPage));
+        const size_t upload = front(n, npages, nslots) + bytes;
+        // behind the planes, with the flag: every page's segment block, GifSeg[cap + 1] (the device's own; never uploaded)
+        const size_t total = upload + planes + (split ? ((size_t)nslots + (size_t)npages) * sizeof(GifSeg) : 0);
         int rc = rc_all;
         // pass 1: where everything goes; the LZW descriptors, dealt
         std::vector<GifMixItem> items((size_t)n);
         std::vector<GifLzwDesc> lzw;
         lzw.reserve((size_t)npages);
         std::vector<size_t> pal_at((size_t)npages), data_at((size_t)npages), plane_at((size_t)npages);
-        size_t off = front(n, npages), poff = upload;
+        size_t off = front(n, npages, nslots), poff = upload;
         int q = 0;
         for (int k = 0; k < n; k++) {
             const GifPlan& pl = plans[g0 + (size_t)k];
@@ -154,6 +173,16 @@ int impgpu_batch_decode_gif(const unsigned char* const* blobs, const size_t* siz
         uint8_t* const whole = (uint8_t*)up.host;
         size_t sent = lzw_off;
         if (!rc) std::memcpy(whole + lzw_off, sorted.data(), sorted.size() * sizeof(GifLzwDesc));
+        if (!rc && split) {                                         // per dealt descriptor: its segment block and its slots
+            GifSplitPage* sp = (GifSplitPage*)(whole + pages_off);
+            GifSegSlot* slot = (GifSegSlot*)(whole + slots_off);
+            for (size_t i = 0; i < sorted.size(); i++) {
+                const uint32_t scap = gif_seg_cap(sorted[i].data_bytes);
+                sp[i] = GifSplitPage{(long long)poff, scap, 0};
+                poff += ((size_t)scap + 1) * sizeof(GifSeg);
+                for (uint32_t k = 0; k < scap; k++) *slot++ = GifSegSlot{(int)i, (int)k};
+            }
+        }
         q = 0;
         for (int k = 0; k < n && !rc; k++) {
             const GifPlan& pl = plans[g0 + (size_t)k];
@@ -180,7 +209,8 @@ int impgpu_batch_decode_gif(const unsigned char* const* blobs, const size_t* siz
             }
         }
         if (!rc) {
-            rc = launch_gif_lzw((uint8_t*)up.dev, lzw_off, ix, most, (uint32_t*)status_dev, s);
+            rc = split ? launch_gif_lzw_split((uint8_t*)up.dev, lzw_off, pages_off, slots_off, ix, most, nslots, (uint32_t*)status_dev, s)
+                       : launch_gif_lzw((uint8_t*)up.dev, lzw_off, ix, most, (uint32_t*)status_dev, s);
             if (rc) { (void)stage_upload_part(up.token, 0, up.dev, 0, true); dev_free(up.dev); }
         }
         if (!rc) rc = launch_gif_compose_mixed(items.data(), n, up, total, s);     // (sends its table, fences the buffer, frees up.dev)
@@ -219,12 +249,21 @@ int impgpu_batch_decode_gif(const unsigned char* const* blobs, const size_t* siz
     return IMP_OK;
 }
 
-int impgpu_image_decode_gif(const unsigned char* blob, size_t size, int destructive, int page, impgpu_image** album) {
+int impgpu_batch_decode_gif(const unsigned char* const* blobs, const size_t* sizes, const int* destructive, const int* page,
+                            int count, impgpu_image** albums, int* codes, int* launches) {
+    return impgpu_batch_decode_gif_ex(blobs, sizes, destructive, page, count, 0, albums, codes, launches);
+}
+
+int impgpu_image_decode_gif_ex(const unsigned char* blob, size_t size, int destructive, int page, int flags, impgpu_image** album) {
     if (!blob || !album) return IMP_ERROR_INVALID_ARGS;
     *album = nullptr;
     int code = IMP_ERROR_INVALID_ARGS;
-    const int rc = impgpu_batch_decode_gif(&blob, &size, &destructive, &page, 1, album, &code, nullptr);
+    const int rc = impgpu_batch_decode_gif_ex(&blob, &size, &destructive, &page, 1, flags, album, &code, nullptr);
     return rc ? rc : code;
+}
+
+int impgpu_image_decode_gif(const unsigned char* blob, size_t size, int destructive, int page, impgpu_image** album) {
+    return impgpu_image_decode_gif_ex(blob, size, destructive, page, 0, album);
 }
 
 }  // extern "C"

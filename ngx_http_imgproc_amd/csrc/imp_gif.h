@@ -9,6 +9,10 @@
 // length and first byte from that prefix, which may itself be an entry of this round), a scan of the string lengths
 // gives every code's output offset, and every lane writes its string by walking the prefix chain backwards (gif_emit).
 //
+// IMPGPU_GIF_SPLIT cuts a page at its clear codes and gives every segment a wavefront of its own: the scan, the length
+// pass and the emit pass further down (k_gif_lzw_scan / _len / _emit; on the host impgpu_gif_pages_split and
+// tests/c/gif_split_fuzz.cpp).
+//
 // Safe by construction: a store goes through gif_store, which drops every index at or past width x height; a round
 // consumes at least one code or ends the page; every chain walk is bounded by the entry's stored length.
 #pragma once
@@ -16,6 +20,7 @@
 #if !defined(__HIP_DEVICE_COMPILE__)
 #include <vector>
 #endif
+#include "../../include/impgpu.h"      // IMPGPU_GIF_SPLIT_MIN_BYTES
 #include "../../include/impgpu_gif.h"
 
 #if defined(__HIPCC__)
@@ -114,9 +119,8 @@ IMP_GIF_HD void gif_table_start(GifLzwMem* m, int lane) {
 }
 
 IMP_GIF_HD int gif_width_of(int next) {               // the width a code is read with when `next` is the next free code
-    int w = 1;
-    while ((1 << w) <= next && w < 12) w++;
-    return w;
+    const int w = 32 - __builtin_clz((unsigned)next | 1u);             // (the smallest w with (1 << w) > next, without a loop)
+    return w > 12 ? 12 : w;
 }
 
 // Code j of a round: *free_code = the next free code when it is read (the entry it adds, if it adds one), *width its
@@ -125,9 +129,9 @@ IMP_GIF_HD uint32_t gif_code_at(const GifLzwState& s, int j, int* free_code, int
     const int a = s.prev < 0 ? 1 : 0;
     const int w0 = gif_width_of(s.next);
     uint32_t bits = (uint32_t)j * (uint32_t)w0;
-    for (int t = w0 + 1; t <= 12; t++) {              // codes from index i_t on are at least t bits wide
-        const int it = a + (1 << (t - 1)) - s.next;
-        if (j > it) bits += (uint32_t)(j - it);
+    for (int t = 2; t <= 12; t++) {                   // codes from index i_t on are at least t bits wide (t > w0; a fixed
+        const int it = a + (1 << (t - 1)) - s.next;   // trip count: the scan wants this free of branches)
+        if (t > w0 && j > it) bits += (uint32_t)(j - it);
     }
     int n = s.next + (j > a ? j - a : 0);
     if (n > GIF_TABLE) n = GIF_TABLE;
@@ -136,6 +140,15 @@ IMP_GIF_HD uint32_t gif_code_at(const GifLzwState& s, int j, int* free_code, int
     return s.bitpos + bits;
 }
 
+// What code c is, read as code j of a round with n the next free code (gif_code_at): nothing here needs a table.
+IMP_GIF_HD int gif_kind_of(const GifLzwState& s, int mcs, int j, int c, int n) {
+    const int clear = 1 << mcs;
+    if (c == clear) return GIF_K_CLEAR;
+    if (c == clear + 1) return GIF_K_EOI;
+    if (j == 0 && s.prev < 0) return c < clear ? GIF_K_CODE : GIF_K_INVALID;
+    if (c > n || (c == n && n >= GIF_TABLE)) return GIF_K_INVALID;
+    return GIF_K_CODE;
+}
 // Lane j reads its code (into m->code[j]) and says what it is.  `data` holds `nbytes` bytes; nothing outside is read.
 IMP_GIF_HD int gif_extract(GifLzwMem* m, const GifLzwState& s, int mcs, const uint8_t* data, uint32_t nbytes, int j) {
     int n, width;
@@ -148,12 +161,7 @@ IMP_GIF_HD int gif_extract(GifLzwMem* m, const GifLzwState& s, int mcs, const ui
     if (b + 2 < nbytes) v |= (uint32_t)data[b + 2] << 16;
     const int c = (int)((v >> (at & 7)) & ((1u << width) - 1u));
     m->code[j] = (uint16_t)c;
-    const int clear = 1 << mcs;
-    if (c == clear) return GIF_K_CLEAR;
-    if (c == clear + 1) return GIF_K_EOI;
-    if (j == 0 && s.prev < 0) return c < clear ? GIF_K_CODE : GIF_K_INVALID;
-    if (c > n || (c == n && n >= GIF_TABLE)) return GIF_K_INVALID;
-    return GIF_K_CODE;
+    return gif_kind_of(s, mcs, j, c, n);
 }
 
 // Does code j of a round of `ncodes` codes add an entry, and which?  (-1: none)
@@ -225,15 +233,15 @@ IMP_GIF_HD void gif_emit(const GifLzwMem* m, const GifPlane& p, int j, int ncode
 }
 
 // The state behind a round of `ncodes` codes that produced `produced` indices and ended on a code of kind `kind`
-// (GIF_K_CODE: all 64 lanes held codes).
-IMP_GIF_HD void gif_round_end(GifLzwState* s, const GifLzwMem* m, int mcs, int ncodes, int kind, uint32_t produced, uint32_t total) {
+// (GIF_K_CODE: all 64 lanes held codes); `last` is the round's last code (read only when ncodes > 0).
+IMP_GIF_HD void gif_round_advance(GifLzwState* s, int mcs, int ncodes, int kind, int last, uint32_t produced, uint32_t total) {
     int n, width;
     const uint32_t at = gif_code_at(*s, ncodes, &n, &width);    // where the code behind the last one lies
     if (ncodes > 0) {
         const int a = s->prev < 0 ? 1 : 0;
         int nx = s->next + (ncodes - a);
         s->next = nx > GIF_TABLE ? GIF_TABLE : nx;
-        s->prev = m->code[ncodes - 1];
+        s->prev = last;
     }
     s->bitpos = at;
     s->outpos += produced;
@@ -246,6 +254,119 @@ IMP_GIF_HD void gif_round_end(GifLzwState* s, const GifLzwMem* m, int mcs, int n
     else if (kind == GIF_K_INVALID) { s->status = GIF_LZW_INVALID; s->done = 1; }
     else if (kind == GIF_K_EOI || kind == GIF_K_NODATA) { s->done = 1; }
     if (s->done && s->status == GIF_LZW_OK && s->outpos < total) s->status = GIF_LZW_SHORT;
+}
+IMP_GIF_HD void gif_round_end(GifLzwState* s, const GifLzwMem* m, int mcs, int ncodes, int kind, uint32_t produced, uint32_t total) {
+    gif_round_advance(s, mcs, ncodes, kind, ncodes > 0 ? (int)m->code[ncodes - 1] : 0, produced, total);
+}
+
+// ---------------------------------------------------------------- a page cut at its clear codes (IMPGPU_GIF_SPLIT)
+// LZW is sequential only between clear codes: behind one the decoder's state is known (an empty table, the first code
+// width), so the stretch up to the next clear can be decoded by a wavefront of its own.  Three passes:
+//   SCAN    the round loop WITHOUT a table (gif_scan_fetch / gif_scan_kind: gif_extract's rules; gif_round_advance with
+//           produced = 0) finds the clears.  Its rounds are GIF_SCAN_CODES codes, 16 per lane: with no table to build a
+//           round's length is free, and a round costs one memory latency whatever its length.  It stops
+//           where any decoder would stop for a reason that needs no table: end-of-information, no data, a code above the
+//           free code, a first-after-clear code that is no literal.  (Indices beyond the page it cannot see.)  Its output
+//           is the page's SEGMENTS.  Segment 0 starts at bit 0; a clear is a CUT -- the segment ends just behind it, the
+//           next one starts there -- when at least IMPGPU_GIF_SPLIT_MIN_BYTES of stream lie between the segment's start
+//           and the bit behind the clear and the page's table (gif_seg_cap entries) has room; any other clear stays
+//           inside its segment and is the segment decoder's, as in the one-wave route.  The last segment is open
+//           (GIF_SEG_OPEN): the stream ends it.  Which clears are cuts changes no answer.
+//   LENGTH  per segment, from the fresh state at its start: the rounds without gif_emit, until bitpos IS the segment's end
+//           (the scan walked the same code grid from the same state) or the round ends the stream; how many indices
+//           the segment holds (saturating at width x height + 1) and whether it ended on an invalid code.
+//   EMIT    per segment: the same rounds with gif_emit, at the sum of the earlier segments' lengths; nothing when that
+//           sum is at or past width x height.  gif_split_status folds the records into the one-wave decoder's word.
+constexpr uint32_t GIF_SEG_OPEN = 0xFFFFFFFFu;
+enum : uint32_t { GIF_SEG_RAN = 0, GIF_SEG_ENDED = 1, GIF_SEG_INVALID = 2 };     // ran to its end / EOI or no data / invalid
+struct GifSeg { uint32_t start, end, produced, ended; };     // bit offsets (the scan's), then the length pass's record
+// A page's segment block in device memory: GifSeg[0].start holds the COUNT (its other words are free), the segments follow.
+IMP_GIF_HD uint32_t gif_seg_cap(uint32_t data_bytes) { return data_bytes / (uint32_t)IMPGPU_GIF_SPLIT_MIN_BYTES + 1u; }
+
+// The scan's rounds: lane l holds codes l, l + 64, ... of GIF_SCAN_CODES.  gif_code_at's closed form holds for any j.
+constexpr int GIF_SCAN_PER_LANE = 16;
+constexpr int GIF_SCAN_CODES = GIF_LANES * GIF_SCAN_PER_LANE;
+struct GifScanCode { uint32_t at, v; int n, width; };
+// Code j's three bytes, read WITHOUT a branch, so that the loads of a lane's 16 codes are in flight together: every index
+// is clamped into the data, and a clamped byte only ever supplies bits that lie past the data's end -- a code that
+// reaches there is GIF_K_NODATA whatever was read.  Nothing outside `data` is read.  nbytes >= 1: an empty stream has
+// no round (gif_scan_empty).
+IMP_GIF_HD GifScanCode gif_scan_fetch(const GifLzwState& s, const uint8_t* data, uint32_t nbytes, int j) {
+    GifScanCode c;
+    c.at = gif_code_at(s, j, &c.n, &c.width);
+    const uint32_t last = nbytes - 1, b = c.at >> 3;
+    const uint32_t b0 = b < last ? b : last, b1 = b + 1 < last ? b + 1 : last, b2 = b + 2 < last ? b + 2 : last;
+    c.v = (uint32_t)data[b0] | (uint32_t)data[b1] << 8 | (uint32_t)data[b2] << 16;
+    return c;
+}
+IMP_GIF_HD int gif_scan_kind(const GifLzwState& s, int mcs, uint32_t nbytes, int j, const GifScanCode& c) {
+    if ((uint64_t)c.at + (uint64_t)c.width > (uint64_t)nbytes * 8u) return GIF_K_NODATA;
+    return gif_kind_of(s, mcs, j, (int)((c.v >> (c.at & 7)) & ((1u << c.width) - 1u)), c.n);
+}
+
+// the scan's state between two rounds
+struct GifScan { GifLzwState s; uint32_t nseg, seg_start; };
+IMP_GIF_HD void gif_scan_start(GifScan* sc, int mcs) {
+    gif_state_start(&sc->s, mcs);
+    sc->nseg = 0;
+    sc->seg_start = 0;
+}
+// Behind a round of the scan (wave-uniform): the state moves on, and a clear that is a cut closes segs[nseg].  When the
+// scan is done the last segment is left open.
+IMP_GIF_HD void gif_scan_round_end(GifScan* sc, int mcs, int ncodes, int kind, GifSeg* segs, uint32_t cap, bool writer) {
+    gif_round_advance(&sc->s, mcs, ncodes, kind, 0, 0u, 0u);
+    if (kind == GIF_K_CLEAR && sc->s.bitpos - sc->seg_start >= (uint32_t)IMPGPU_GIF_SPLIT_MIN_BYTES * 8u && sc->nseg + 1 < cap) {
+        if (writer) { segs[sc->nseg].start = sc->seg_start; segs[sc->nseg].end = sc->s.bitpos; }
+        sc->nseg++;
+        sc->seg_start = sc->s.bitpos;
+    }
+    if (sc->s.done) {
+        if (writer) { segs[sc->nseg].start = sc->seg_start; segs[sc->nseg].end = GIF_SEG_OPEN; }
+        sc->nseg++;
+    }
+}
+
+// the scan of a stream of no bytes: one open segment at bit 0
+IMP_GIF_HD uint32_t gif_scan_empty(GifSeg* segs, bool writer) {
+    if (writer) { segs[0].start = 0; segs[0].end = GIF_SEG_OPEN; }
+    return 1;
+}
+
+// a segment's decoder before its first round
+IMP_GIF_HD void gif_segment_start(GifLzwState* s, int mcs, uint32_t start) {
+    gif_state_start(s, mcs);
+    s->bitpos = start;
+}
+// ... and whether it goes on: not past its end, not once the count has saturated (the length pass may stop there)
+IMP_GIF_HD bool gif_segment_goes_on(const GifLzwState& s, uint32_t end) { return !s.done && s.bitpos < end; }
+// what the length pass records for a segment whose decoder stopped in state `s` (total = width x height)
+IMP_GIF_HD void gif_segment_record(GifSeg* seg, const GifLzwState& s, uint32_t total) {
+    seg->produced = s.outpos > total ? total + 1u : s.outpos;
+    seg->ended = s.status == GIF_LZW_INVALID ? GIF_SEG_INVALID : s.done ? GIF_SEG_ENDED : GIF_SEG_RAN;
+}
+// Segment k's base: the indices in front of it (saturating at total + 1); *live = it emits: nothing in front of it went
+// past the page or ended invalid.
+IMP_GIF_HD uint32_t gif_split_base(const GifSeg* segs, uint32_t k, uint32_t total, bool* live) {
+    uint64_t sum = 0;
+    *live = true;
+    for (uint32_t i = 0; i < k; i++) {
+        sum += segs[i].produced;
+        if (sum > total) { *live = false; return total + 1u; }
+        if (segs[i].ended == GIF_SEG_INVALID) *live = false;
+    }
+    if (sum >= total) *live = false;
+    return (uint32_t)sum;
+}
+// The page's status word, from the records in stream order: the one-wave decoder's for every stream (it checks LONG
+// before INVALID at a round's end, and everything before the first problem is the same).
+IMP_GIF_HD int gif_split_status(const GifSeg* segs, uint32_t count, uint32_t total) {
+    uint64_t sum = 0;
+    for (uint32_t i = 0; i < count; i++) {
+        sum += segs[i].produced;
+        if (sum > total) return GIF_LZW_LONG;
+        if (segs[i].ended == GIF_SEG_INVALID) return GIF_LZW_INVALID;
+    }
+    return sum < total ? GIF_LZW_SHORT : GIF_LZW_OK;
 }
 
 // ---------------------------------------------------------------- the host's two decoders (impgpu_gif_pages)
@@ -322,14 +443,75 @@ inline int gif_lzw_plain_host(const uint8_t* data, uint32_t nbytes, int mcs, con
     return status;
 }
 
+// the three passes of a cut page, one lane after the other: the scan ...
+inline uint32_t gif_scan_host(const uint8_t* data, uint32_t nbytes, int mcs, GifSeg* segs, uint32_t cap) {
+    if (nbytes == 0) return gif_scan_empty(segs, true);
+    GifScan sc;
+    gif_scan_start(&sc, mcs);
+    while (!sc.s.done) {
+        int ncodes = GIF_SCAN_CODES, kind = GIF_K_CODE;
+        for (int j = GIF_SCAN_CODES - 1; j >= 0; j--) {
+            const int k = gif_scan_kind(sc.s, mcs, nbytes, j, gif_scan_fetch(sc.s, data, nbytes, j));
+            if (k != GIF_K_CODE) { ncodes = j; kind = k; }
+        }
+        gif_scan_round_end(&sc, mcs, ncodes, kind, segs, cap, true);
+    }
+    return sc.nseg;
+}
+// ... and a segment's rounds from `base`, with gif_emit (the emit pass) or without (the length pass, base 0); the
+// decoder's state where it stopped
+inline GifLzwState gif_segment_host(const uint8_t* data, uint32_t nbytes, int mcs, const GifPlane& p, GifLzwMem* m, const GifSeg& seg,
+                                    uint32_t base, bool emit) {
+    GifLzwState s;
+    gif_segment_start(&s, mcs, seg.start);
+    s.outpos = base;
+    for (int j = 0; j < GIF_LANES; j++) gif_table_start(m, j);
+    while (gif_segment_goes_on(s, seg.end)) {
+        int ncodes = GIF_LANES, kind = GIF_K_CODE;
+        for (int j = GIF_LANES - 1; j >= 0; j--) {
+            const int k = gif_extract(m, s, mcs, data, nbytes, j);
+            if (k != GIF_K_CODE) { ncodes = j; kind = k; }
+        }
+        for (int j = 0; j < GIF_LANES; j++) gif_link_start(m, s, j, ncodes);
+        for (int it = 0; it < 6; it++) {
+            for (int j = 0; j < GIF_LANES; j++) gif_link_read(m, j);
+            for (int j = 0; j < GIF_LANES; j++) gif_link_write(m, j);
+        }
+        for (int j = 0; j < GIF_LANES; j++) gif_link_finish(m, s, j, ncodes);
+        uint32_t at = s.outpos;
+        for (int j = 0; j < GIF_LANES; j++) {
+            if (emit) gif_emit(m, p, j, ncodes, at);
+            at += gif_string_len(m, j, ncodes);
+        }
+        gif_round_end(&s, m, mcs, ncodes, kind, at - s.outpos, p.total);
+    }
+    return s;
+}
+// how = 2 (impgpu_gif_pages_split): scan, length pass and emit pass as k_gif_lzw_scan / _len / _emit run them
+inline int gif_lzw_split_host(const uint8_t* data, uint32_t nbytes, int mcs, const GifPlane& p, GifLzwMem* m, int* nseg) {
+    std::vector<GifSeg> segs(gif_seg_cap(nbytes));
+    const uint32_t count = gif_scan_host(data, nbytes, mcs, segs.data(), (uint32_t)segs.size());
+    if (nseg) *nseg = (int)count;
+    for (int row = 0; row < p.h; row++) gif_pad_row(p, row);
+    if (count == 1) return gif_segment_host(data, nbytes, mcs, p, m, segs[0], 0, true).status;     // (no length pass: today's loop)
+    for (uint32_t k = 0; k < count; k++) gif_segment_record(&segs[k], gif_segment_host(data, nbytes, mcs, p, m, segs[k], 0, false), p.total);
+    for (uint32_t k = 0; k < count; k++) {
+        bool live;
+        const uint32_t base = gif_split_base(segs.data(), k, p.total, &live);
+        if (live) (void)gif_segment_host(data, nbytes, mcs, p, m, segs[k], base, true);
+    }
+    return gif_split_status(segs.data(), count, p.total);
+}
+
 inline int gif_pitch(int w) { return (w + 3) & ~3; }
 // a page's bit offsets are 32-bit words: compressed pages of 256 MB and more go back to the host decoder
 constexpr size_t GIF_DATA_MAX = size_t(1) << 28;
 
-// impgpu_gif_pages: every page's plane, one after the other, by one of the two decoders above
-inline int gif_pages_host(const unsigned char* blob, size_t size, int how, unsigned char* out, size_t capacity, size_t* length) {
+// impgpu_gif_pages / impgpu_gif_pages_split: every page's plane, one after the other, by one of the decoders above
+// (how = 2: the split route's passes; segments[f], when given, = page f's segment count)
+inline int gif_pages_any(const unsigned char* blob, size_t size, int how, unsigned char* out, size_t capacity, size_t* length,
+                         int* segments, int pages_capacity) {
     if (length) *length = 0;
-    if (how != 0 && how != 1) return IMP_ERROR_INVALID_ARGS;
     std::vector<impgpu_gif_desc> pages(64);
     int count = 0, cw = 0, ch = 0;
     int rc = impgpu_gif_walk(blob, size, pages.data(), (int)pages.size(), &count, &cw, &ch);
@@ -345,7 +527,7 @@ inline int gif_pages_host(const unsigned char* blob, size_t size, int how, unsig
     if (length) *length = need;
     if (!out || capacity < need) return IMP_ERROR_MALLOC_FAILED;
     std::vector<uint8_t> data;
-    std::vector<GifLzwMem> mem(how == 1 ? 1 : 0);
+    std::vector<GifLzwMem> mem(how != 0 ? 1 : 0);
     size_t at = 0;
     int bad = 0;
     for (int f = 0; f < count; f++) {
@@ -356,12 +538,25 @@ inline int gif_pages_host(const unsigned char* blob, size_t size, int how, unsig
         p.plane = out + at;
         p.w = d.width; p.h = d.height; p.pitch = gif_pitch(d.width); p.interlaced = d.interlaced;
         p.total = (uint32_t)d.width * (uint32_t)d.height;
-        const int st = how == 1 ? gif_lzw_rounds_host(data.data(), (uint32_t)d.data_bytes, d.min_code_size, p, mem.data())
+        int nseg = 0;
+        const int st = how == 2 ? gif_lzw_split_host(data.data(), (uint32_t)d.data_bytes, d.min_code_size, p, mem.data(), &nseg)
+                     : how == 1 ? gif_lzw_rounds_host(data.data(), (uint32_t)d.data_bytes, d.min_code_size, p, mem.data())
                                 : gif_lzw_plain_host(data.data(), (uint32_t)d.data_bytes, d.min_code_size, p);
+        if (segments && f < pages_capacity) segments[f] = nseg;
         if (st != GIF_LZW_OK) bad = 1;
         at += (size_t)p.pitch * p.h;
     }
     return bad ? IMP_ERROR_DECODE_FAILED : IMP_OK;
+}
+inline int gif_pages_host(const unsigned char* blob, size_t size, int how, unsigned char* out, size_t capacity, size_t* length) {
+    if (length) *length = 0;
+    if (how != 0 && how != 1) return IMP_ERROR_INVALID_ARGS;
+    return gif_pages_any(blob, size, how, out, capacity, length, nullptr, 0);
+}
+inline int gif_pages_split_host(const unsigned char* blob, size_t size, unsigned char* out, size_t capacity, size_t* length,
+                                int* segments, int pages_capacity) {
+    if (segments && pages_capacity < 0) { if (length) *length = 0; return IMP_ERROR_INVALID_ARGS; }
+    return gif_pages_any(blob, size, 2, out, capacity, length, segments, pages_capacity);
 }
 
 }  // namespace imp

@@ -500,6 +500,16 @@ struct GifLzwDesc {
     int first, nblk;
 };
 int launch_gif_lzw(uint8_t* blob, size_t table_off, const MixIndex& ix, int most, uint32_t* status, hipStream_t s);
+// IMPGPU_GIF_SPLIT: the same pages cut at their clear codes, three launches (k_gif_lzw_scan, one wavefront per page over
+// the same dealt table; k_gif_lzw_len and k_gif_lzw_emit, one wavefront per segment SLOT).  Beside the table, in the same
+// block: GifSplitPage[pages] at `split_off`, entry i belonging to descriptor i of the dealt table -- where the page's
+// segment block lies (GifSeg[cap + 1], imp_gif.h; device-written, behind the planes) -- and GifSegSlot[nslots] at
+// `slots_off`: workgroup b of the slot launches works on segment k of page `page` (an index into the dealt table), every
+// page owning cap consecutive slots, of which those at or past the count the scan found return at once.
+struct GifSplitPage { long long seg_off; uint32_t cap, pad; };
+struct GifSegSlot { int page, k; };
+int launch_gif_lzw_split(uint8_t* blob, size_t table_off, size_t split_off, size_t slots_off, const MixIndex& ix, int most, long long nslots,
+                         uint32_t* status, hipStream_t s);
 
 // imp_png_inflate.hip: the zlib streams of a call's PNG files, one workgroup of one wavefront per stream (impgpu_batch_decode_png_ex
 // with IMPGPU_PNG_DEVICE_INFLATE).  `descs` (imp_png.h) lie in device memory; descriptor k is workgroup k's.

@@ -32,6 +32,9 @@ PNG_LOW_GRAY = 2
 PNG_ADAM7 = 4
 PNG_ALL = PNG_PALETTE | PNG_LOW_GRAY | PNG_ADAM7
 PNG_DEVICE_INFLATE = 8          # not part of PNG_ALL: how files are decoded (k_png_inflate), not which are taken
+# impgpu_*_decode_gif_ex flags (include/impgpu.h)
+GIF_SPLIT = 1                   # cut every page at its clear codes, a wavefront per segment (k_gif_lzw_scan / _len / _emit)
+GIF_SPLIT_MIN_BYTES = 2048      # IMPGPU_GIF_SPLIT_MIN_BYTES: a clear code nearer than this to its segment's start is no cut
 
 
 def _b(s):
@@ -873,18 +876,19 @@ def gif_compose(pages, destructive=False, page=-1, album=False):
     return 0, [Image(handle=outs[i]) for i in range(nout)]
 
 
-def decode_gif(blob, destructive=False, page=-1):
-    """impgpu_image_decode_gif: the GIF FILE -> (code, album Image or None): the container walk on the host, the LZW pages
-    (k_gif_lzw) and LoadGIF's compositing loop on the device."""
+def decode_gif(blob, destructive=False, page=-1, flags=0):
+    """impgpu_image_decode_gif_ex: the GIF FILE -> (code, album Image or None): the container walk on the host, the LZW pages
+    (k_gif_lzw; with flags = GIF_SPLIT cut at their clear codes, a wavefront per segment) and LoadGIF's compositing loop on
+    the device."""
     blob = bytes(blob)
     out = C.c_void_p()
-    rc = lib.impgpu_image_decode_gif(blob, len(blob), int(bool(destructive)), int(page), C.byref(out))
+    rc = lib.impgpu_image_decode_gif_ex(blob, len(blob), int(bool(destructive)), int(page), int(flags), C.byref(out))
     return rc, (Image(handle=out.value) if rc == 0 and out.value else None)
 
 
-def batch_decode_gif(files, count=None):
-    """impgpu_batch_decode_gif: files = [(blob, destructive, page), ...] -> (code, [album Image or None ...], [codes],
-    launches).  `count` overrides the count passed to the library (its argument checks)."""
+def batch_decode_gif(files, count=None, flags=0):
+    """impgpu_batch_decode_gif_ex: files = [(blob, destructive, page), ...] -> (code, [album Image or None ...], [codes],
+    launches).  `count` overrides the count passed to the library (its argument checks); flags: 0 or GIF_SPLIT."""
     n = len(files)
     m = max(1, n if count is None else count)
     keep = [bytes(f[0]) for f in files]
@@ -895,7 +899,7 @@ def batch_decode_gif(files, count=None):
     outs = (C.c_void_p * m)()
     codes = (C.c_int * m)(*([-1] * m))
     launches = C.c_int(-1)
-    rc = lib.impgpu_batch_decode_gif(blobs, sizes, destr, pages, n if count is None else count, outs, codes, C.byref(launches))
+    rc = lib.impgpu_batch_decode_gif_ex(blobs, sizes, destr, pages, n if count is None else count, int(flags), outs, codes, C.byref(launches))
     return rc, [Image(handle=outs[i]) if outs[i] else None for i in range(n)], list(codes[:n]), launches.value
 
 
@@ -917,6 +921,22 @@ def gif_pages(blob, how=0):
     buf = np.full(max(1, n.value), 0xA5, np.uint8)
     rc = lib.impgpu_gif_pages(blob, len(blob), int(how), buf.ctypes.data, n.value, C.byref(n))
     return rc, (buf[: n.value].tobytes() if rc == 0 else None)
+
+
+def gif_pages_split(blob):
+    """impgpu_gif_pages_split (host, no device): gif_pages' planes made by the GIF_SPLIT route's three passes, the kernels'
+    own lane code run one lane after the other -> (code, bytes or None, [segments per page] or None when the container
+    was not taken)."""
+    blob = bytes(blob)
+    n = C.c_size_t(0)
+    rc = lib.impgpu_gif_pages_split(blob, len(blob), None, 0, C.byref(n), None, 0)
+    if rc != IMP_ERROR_MALLOC_FAILED:
+        return rc, None, None
+    pages = gif_info(blob)[1][0]
+    buf = np.full(max(1, n.value), 0xA5, np.uint8)
+    segs = (C.c_int * max(1, pages))()
+    rc = lib.impgpu_gif_pages_split(blob, len(blob), buf.ctypes.data, n.value, C.byref(n), segs, pages)
+    return rc, (buf[: n.value].tobytes() if rc == 0 else None), list(segs[:pages])
 
 
 def batch_filters(ptr, stride, w, h, c, step, count, filters, allow_experiments=1, stream=None):
