@@ -727,6 +727,62 @@ int impgpu_batch_decode_gif_ex(const unsigned char* const* blobs, const size_t* 
 int impgpu_gif_pages_split(const unsigned char* blob, size_t size, unsigned char* out, size_t capacity, size_t* length,
                            int* segments, int pages_capacity);
 
+/* ---- GIF FILES out: SaveGIF (advancedio.c:340-425) has a host core quantise and LZW-encode every page of the 32-bit
+ *      frames impgpu_batch_album_download ships.  These calls write the FILE on the device.  The reference's GIF resize is
+ *      nearest-neighbour, and crop, flips, turns and every pointwise filter give a frame no colour its source page did not
+ *      have: for those requests the palette is EXACT and nothing is quantised.  The file is not FreeImage's bytes (its
+ *      NNQUANT palette cannot be pinned where FreeImage is not installed) but defined here, deterministically:
+ *      a pixel is TRANSPARENT when its frame has 4 channels and its alpha byte is 0 (any other alpha is ignored); a frame's
+ *      colour set is the distinct (R,G,B) of its other pixels.  With U the union of the sets and T = some frame has a
+ *      transparent pixel: |U| + T <= 256 gives ONE global table and no local ones; otherwise no global table and a local
+ *      table per frame, of its own set.  A table lists its colours ascending by R<<16 | G<<8 | B, then the transparent entry
+ *      (stored 0,0,0) when it has one, padded with 0,0,0 to a power of two >= 2; min_code_size = max(2, log2(size)).
+ *      Indices in top-down raster order, no interlace.  LZW: greedy, 12 bits, a clear code at the start, in front of pixel
+ *      k * segment (the pending code first) and whenever the table is full and another entry is due; widths as the decoder
+ *      sees them; end-of-information.  Container: GIF89a, the w x h screen, flags 0xF0 | bits with a global table and 0x70
+ *      without, NETSCAPE2.0 when loop_count >= 0, per frame a graphic control extension (dispose[i], the transparency flag
+ *      and index iff the frame has a transparent pixel, delay min(65535, time_ms[i] / 10)), the image descriptor at 0,0,
+ *      255-byte sub-blocks; the trailer.  tests/gif_writer.py writes the same bytes.
+ *      time_ms / dispose: Frame.Time / Frame.Dispose (required.h:129-140; the handle does not carry them), NULL = all 0.
+ *      A single image is an album of one.  segment = 0 means IMPGPU_GIF_ENC_SEGMENT.
+ *      TAKEN: 3- and 4-channel frames up to 4096 x 4096, up to 4096 frames (what impgpu_image_decode_gif takes back).
+ *      REFUSED, IMP_ERROR_INVALID_ARGS before a device is looked for: a segment outside {0} and [256, 2^24], a dispose
+ *      outside 0..3, loop_count > 65535.  IMP_ERROR_UNSUPPORTED, *length = 0, nothing written: 1- or 2-channel frames, a
+ *      larger side, more frames, a frame whose colours (and transparency) fit no table of 256 -- blur, vignette or a
+ *      watermark do that: download the frames and quantise on the host as before.  IMP_ERROR_MALLOC_FAILED: `capacity`
+ *      is too small; nothing is written, *length is the size needed; impgpu_gif_encode_bound is always enough.
+ *      FIVE launches for a call, whatever it holds: k_gif_enc_sets (a colour set per frame: an LDS hash set per workgroup,
+ *      then compare-and-swap into the frame's), k_gif_enc_tables (a workgroup per album sorts the sets, unites them and
+ *      decides), k_gif_enc_index (table in LDS, a bisection per pixel), k_gif_enc_lzw (a wavefront per SEGMENT: the greedy
+ *      walk is sequential and wave-uniform over an LDS hash table, 64 lanes pack 64 codes at a time) and k_gif_enc_pack
+ *      (prefix sum of the segments' bit lengths, whole bytes into 255-byte sub-blocks).  TWO waits: the frames' records
+ *      (verdict, table size, stream length), then the tables and streams of the files that fit.
+ *      MEASURED (profiles/gif_encode_probe.json, one session, dithered 256-colour frames; the host side
+ *      is impgpu_gif_encode_host on one thread, NOT FreeImage, which is not installed): a lone 640x480 frame 2.01 ms, 8
+ *      frames 2.29 ms, 64 albums of 8 frames at 320x240 21.2 ms -- against 0.08 / 0.51 / 11.3 ms for impgpu_batch_album_download
+ *      of the 32-bit frames alone and 7.0 / 56.8 / 818 ms for that plus the host encoder: 3.5x / 25x / 39x the host route,
+ *      4.3-4.8x fewer bytes across the link, but BEHIND the bare download.  Correct, not fast: k_gif_enc_lzw is 1.90 of the
+ *      2.29 ms (a segment's walk costs about 230 ns a pixel); the other four launches together 0.11 ms.  The cut at 8192
+ *      costs x0.99 (noise), x1.02 (dither), x1.5 (flat colour) in file size; 3584 and 32768 were measured too. ---- */
+#define IMPGPU_GIF_ENC_SEGMENT 8192
+int impgpu_album_encode_gif(const impgpu_image* album, const int* time_ms, const int* dispose, int loop_count, int segment,
+                            unsigned char* out, size_t capacity, size_t* length);
+/* MANY albums (count 0..256): codes[i] / lengths[i] / the file are exactly the lone call's; a refused album gets its code
+ * alone and changes no other entry.  time_ms / dispose may be NULL, and so may their entries.  *launches (may be NULL): the
+ * kernels enqueued -- 5 for a call under $IMPGPU_STAGE_CAP_MB (measured by impgpu_gif_encode_bound), whatever count and the
+ * frame counts are; 0 when no album was accepted.  IMP_ERROR_INVALID_ARGS for NULL arrays with count > 0, a count outside
+ * 0..256 or a bad segment; IMP_ERROR_DEVICE without an env (every codes[i] says so too). */
+int impgpu_batch_encode_gif(const impgpu_image* const* albums, const int* const* time_ms, const int* const* dispose,
+                            const int* loop_counts, int count, int segment, unsigned char* const* outs,
+                            const size_t* capacities, size_t* lengths, int* codes, int* launches);
+/* a size no file of `frames` frames of width x height exceeds (0: a geometry the calls refuse) */
+size_t impgpu_gif_encode_bound(int width, int height, int frames);
+/* host, no device: the same file from frames in host memory (B,G,R[,A] rows `step` bytes apart), made by the launches'
+ * own lane code (csrc/imp_gif_enc.h) run one lane after the other on one thread */
+int impgpu_gif_encode_host(const unsigned char* const* frames, int count, int width, int height, int channels, int step,
+                           const int* time_ms, const int* dispose, int loop_count, int segment,
+                           unsigned char* out, size_t capacity, size_t* length);
+
 /* ---- batch entry points (benchmark / multi-frame albums: bridge.c:578,591,608,632).
  *      `count` frames of identical geometry, frame i at base + i*frame_stride bytes,
  *      already resident in HBM.  stream = hipStream_t to launch on (NULL = env stream).

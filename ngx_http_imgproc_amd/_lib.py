@@ -169,6 +169,12 @@ SIGNATURES = {
     "impgpu_image_decode_gif_ex": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int, PP]),
     "impgpu_batch_decode_gif_ex": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), IP, IP, C.c_int, C.c_int, PP, IP, IP]),
     "impgpu_gif_pages_split": (C.c_int, [C.c_char_p, C.c_size_t, P, C.c_size_t, C.POINTER(C.c_size_t), IP, C.c_int]),
+    "impgpu_album_encode_gif": (C.c_int, [P, IP, IP, C.c_int, C.c_int, P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "impgpu_batch_encode_gif": (C.c_int, [PP, C.POINTER(IP), C.POINTER(IP), IP, C.c_int, C.c_int, PP, C.POINTER(C.c_size_t),
+                                          C.POINTER(C.c_size_t), IP, IP]),
+    "impgpu_gif_encode_bound": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "impgpu_gif_encode_host": (C.c_int, [PP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, IP, IP, C.c_int, C.c_int, P, C.c_size_t,
+                                         C.POINTER(C.c_size_t)]),
     "impgpu_album_download_fi": (C.c_int, [P, C.c_int, PP, IP]),
     "impgpu_batch_download_fi": (C.c_int, [PP, IP, C.c_int, PP, IP, IP, IP]),
     "impgpu_batch_album_download": (C.c_int, [PP, C.c_int, PP, IP, IP]),

@@ -1,0 +1,239 @@
+// imp_gif_enc.cpp -- GIF answers out: impgpu_batch_encode_gif lays the frames of every accepted album out in one device
+// block (descriptors and item tables in front, uploaded once; records, colour sets, tables, index planes, segment slots
+// and framed streams behind), runs the five launches of imp_gif_enc.hip on it and waits twice: once for the frames'
+// records (the verdicts, the table sizes, the streams' lengths -- what the files' sizes depend on), once for the tables
+// and streams of the files that fit their callers' buffers.  The host writes only the container around them
+// (gif_enc_write_file).  impgpu_gif_encode_host is the same pipeline with no device: imp_gif_enc.h's lane code on one thread.
+#include "imp_internal.h"
+#include "imp_gif_enc.h"
+
+namespace imp {
+namespace {
+
+size_t up256(size_t v) { return (v + 255) & ~size_t(255); }
+
+int need_env() {
+    if (!env_ready()) { set_error("impgpu_env_start has not been called", hipErrorNotInitialized); return IMP_ERROR_DEVICE; }
+    return IMP_OK;
+}
+
+// ---------------------------------------------------------------- the device route: one group of albums
+struct EncPlan { int entry, first, frames; };
+
+int encode_group(const std::vector<EncPlan>& plans, const impgpu_image* const* albums, const int* const* time_ms, const int* const* dispose,
+                 const int* loop_counts, uint32_t segment, unsigned char* const* outs, const size_t* caps, size_t* lens, int* codes) {
+    hipStream_t s = env_stream();
+    const int na = (int)plans.size();
+    int nf = 0;
+    for (const EncPlan& p : plans) nf += p.frames;
+    std::vector<GifEncFrameDesc> fd((size_t)nf);
+    std::vector<GifEncAlbumDesc> ad((size_t)na);
+    std::vector<GifEncItem> px_items, seg_items, pack_items;
+    size_t planes = 0, scratch = 0, outb = 0;
+    uint64_t nsegs = 0;
+    for (int a = 0; a < na; a++) {
+        const impgpu_image* im = albums[plans[(size_t)a].entry];
+        ad[(size_t)a] = GifEncAlbumDesc{plans[(size_t)a].first, plans[(size_t)a].frames};
+        const uint32_t total = (uint32_t)im->w * (uint32_t)im->h;
+        const uint32_t out_cap = gif_enc_framed_size((uint32_t)gif_enc_stream_bound(total));
+        for (int q = 0; q < im->frames; q++) {
+            const int f = plans[(size_t)a].first + q;
+            GifEncFrameDesc& d = fd[(size_t)f];
+            d.src = im->d + (size_t)q * im->fstride;
+            d.w = im->w; d.h = im->h; d.c = im->c; d.step = im->step; d.album = a;
+            d.wide = (im->c == 4 && (((uintptr_t)d.src | (uintptr_t)im->step) & 3) == 0) ? 1 : 0;
+            d.total = total; d.segment = segment;
+            d.nseg = gif_enc_segments(total, segment);
+            d.seg0 = (uint32_t)nsegs; nsegs += d.nseg;
+            d.slot_words = gif_enc_slot_words(segment < total ? segment : total);
+            d.out_cap = out_cap;
+            d.plane_off = (long long)planes; planes += up256(total);
+            d.scratch_off = (long long)scratch; scratch += up256((size_t)d.nseg * d.slot_words * 4u);
+            d.out_off = (long long)outb; outb += up256(out_cap);
+            for (uint32_t k = 0; k < (total + GIF_ENC_PX_BLOCK - 1) / GIF_ENC_PX_BLOCK; k++) px_items.push_back(GifEncItem{f, (int)k});
+            for (uint32_t k = 0; k < d.nseg; k++) seg_items.push_back(GifEncItem{f, (int)k});
+            const uint32_t sb = (uint32_t)gif_enc_stream_bound(total);
+            for (uint32_t k = 0; k < (sb + GIF_ENC_PACK_BLOCK - 1) / GIF_ENC_PACK_BLOCK; k++) pack_items.push_back(GifEncItem{f, (int)k});
+        }
+    }
+    if (nsegs > 0x7fffffffull) return IMP_ERROR_UNSUPPORTED;
+    // the block: what is uploaded | records + sets (zeroed) | tables | segment lengths | planes | slots | streams
+    const size_t o_fd = 0, o_ad = o_fd + up256(fd.size() * sizeof(GifEncFrameDesc)), o_px = o_ad + up256(ad.size() * sizeof(GifEncAlbumDesc)),
+                 o_seg = o_px + up256(px_items.size() * sizeof(GifEncItem)), o_pack = o_seg + up256(seg_items.size() * sizeof(GifEncItem)),
+                 o_rec = o_pack + up256(pack_items.size() * sizeof(GifEncItem)), o_set = o_rec + up256((size_t)nf * sizeof(GifEncRec)),
+                 o_tab = o_set + up256((size_t)nf * sizeof(GifColourSet)), o_bits = o_tab + up256((size_t)nf * 1024),
+                 o_plane = o_bits + up256((size_t)nsegs * 4), o_scr = o_plane + planes, o_out = o_scr + scratch, o_end = o_out + outb;
+    for (GifEncFrameDesc& d : fd) { d.plane_off += (long long)o_plane; d.scratch_off += (long long)o_scr; d.out_off += (long long)o_out; }
+    void* mem = nullptr;
+    if (int rc = dev_alloc(o_end, &mem)) return rc;
+    uint8_t* m = (uint8_t*)mem;
+    std::vector<uint8_t> head(o_rec, 0);
+    std::memcpy(head.data() + o_fd, fd.data(), fd.size() * sizeof(GifEncFrameDesc));
+    std::memcpy(head.data() + o_ad, ad.data(), ad.size() * sizeof(GifEncAlbumDesc));
+    std::memcpy(head.data() + o_px, px_items.data(), px_items.size() * sizeof(GifEncItem));
+    std::memcpy(head.data() + o_seg, seg_items.data(), seg_items.size() * sizeof(GifEncItem));
+    std::memcpy(head.data() + o_pack, pack_items.data(), pack_items.size() * sizeof(GifEncItem));
+    int rc = upload_to(m, head.data(), head.size(), s);
+    if (!rc) {
+        const hipError_t e = hipMemsetAsync(m + o_rec, 0, o_tab - o_rec, s);
+        if (e != hipSuccess) { set_error("hipMemsetAsync(gif encode)", e); rc = IMP_ERROR_DEVICE; }
+    }
+    GifEncDev D;
+    D.mem = m;
+    D.frames = (const GifEncFrameDesc*)(m + o_fd); D.albums = (const GifEncAlbumDesc*)(m + o_ad);
+    D.px_items = (const GifEncItem*)(m + o_px); D.seg_items = (const GifEncItem*)(m + o_seg); D.pack_items = (const GifEncItem*)(m + o_pack);
+    D.sets = (GifColourSet*)(m + o_set); D.tabs = (uint32_t*)(m + o_tab); D.recs = (GifEncRec*)(m + o_rec); D.segbits = (uint32_t*)(m + o_bits);
+    if (!rc) rc = launch_gif_encode(D, (long long)px_items.size(), (long long)seg_items.size(), (long long)pack_items.size(), na, s);
+    // the first wait: the records
+    std::vector<GifEncRec> recs((size_t)nf);
+    void *pin = nullptr, *token = nullptr;
+    if (!rc) rc = stage_begin(recs.size() * sizeof(GifEncRec), &pin, &token);
+    if (!rc) {
+        const hipError_t e = hipMemcpyAsync(pin, D.recs, recs.size() * sizeof(GifEncRec), hipMemcpyDeviceToHost, s);
+        if (e != hipSuccess) { set_error("hipMemcpyAsync(gif encode records)", e); rc = IMP_ERROR_DEVICE; }
+    }
+    if (rc) { (void)hipStreamSynchronize(s); dev_free(mem); return rc; }
+    stage_hold(token, true);
+    rc = lane_wait();
+    if (!rc) std::memcpy(recs.data(), pin, recs.size() * sizeof(GifEncRec));
+    stage_hold(token, false);
+    if (rc) { dev_free(mem); return rc; }
+    // the files' sizes; what fits is fetched: per frame its table (local tables; the first frame's for a global one) and its stream
+    std::vector<size_t> tab_at((size_t)nf, 0), str_at((size_t)nf, 0);
+    std::vector<char> fetch((size_t)na, 0);
+    size_t total = 0;
+    for (int a = 0; a < na; a++) {
+        const EncPlan& p = plans[(size_t)a];
+        const int i = p.entry;
+        const GifEncRec* r0 = &recs[(size_t)p.first];
+        if (r0->mode == GIF_ENC_REFUSED) { codes[i] = IMP_ERROR_UNSUPPORTED; lens[i] = 0; continue; }
+        bool sane = true;
+        size_t need = 13 + (loop_counts[i] >= 0 ? 19 : 0) + 1 + (r0->mode == GIF_ENC_GLOBAL ? gif_enc_table_bytes(r0->nkeys) : 0);
+        for (int q = 0; q < p.frames; q++) {
+            const GifEncRec& r = r0[q];
+            sane = sane && r.nkeys >= 1 && r.nkeys <= GIF_SET_MAX && gif_enc_framed_size(r.stream_bytes) <= fd[(size_t)(p.first + q)].out_cap;
+            need += 8 + 10 + 1 + gif_enc_framed_size(r.stream_bytes) + (r.mode == GIF_ENC_LOCAL ? gif_enc_table_bytes(r.nkeys) : 0);
+        }
+        if (!sane) { codes[i] = IMP_ERROR_DEVICE; lens[i] = 0; set_error_text("gif encode: a stream outgrew its bound"); continue; }
+        lens[i] = need;
+        if (need > caps[i]) { codes[i] = IMP_ERROR_MALLOC_FAILED; continue; }
+        codes[i] = IMP_OK;
+        fetch[(size_t)a] = 1;
+        for (int q = 0; q < p.frames; q++) {
+            const size_t f = (size_t)(p.first + q);
+            if (r0->mode == GIF_ENC_LOCAL || q == 0) { tab_at[f] = total; total += 1024; }
+            str_at[f] = total;
+            total += (gif_enc_framed_size(r0[q].stream_bytes) + 63) & ~size_t(63);
+        }
+    }
+    if (total) {
+        if ((rc = stage_begin(total, &pin, &token))) { dev_free(mem); return rc; }
+        hipError_t e = hipSuccess;
+        for (int a = 0; a < na && e == hipSuccess; a++) {
+            if (!fetch[(size_t)a]) continue;
+            const EncPlan& p = plans[(size_t)a];
+            for (int q = 0; q < p.frames && e == hipSuccess; q++) {
+                const size_t f = (size_t)(p.first + q);
+                const GifEncRec& r = recs[f];
+                if (r.mode == GIF_ENC_LOCAL || q == 0)
+                    e = hipMemcpyAsync((uint8_t*)pin + tab_at[f], D.tabs + f * 256, (size_t)r.nkeys * 4, hipMemcpyDeviceToHost, s);
+                if (e == hipSuccess)
+                    e = hipMemcpyAsync((uint8_t*)pin + str_at[f], m + fd[f].out_off, gif_enc_framed_size(r.stream_bytes), hipMemcpyDeviceToHost, s);
+            }
+        }
+        if (e != hipSuccess) { set_error("hipMemcpyAsync(gif encode download)", e); (void)hipStreamSynchronize(s); dev_free(mem); return IMP_ERROR_DEVICE; }
+        stage_hold(token, true);
+        rc = lane_wait();                                               // the second wait: the files
+        if (!rc) {
+            std::vector<GifEncPage> pages;
+            for (int a = 0; a < na; a++) {
+                if (!fetch[(size_t)a]) continue;
+                const EncPlan& p = plans[(size_t)a];
+                const int i = p.entry;
+                pages.clear();
+                for (int q = 0; q < p.frames; q++) {
+                    const size_t f = (size_t)(p.first + q), tf = recs[f].mode == GIF_ENC_LOCAL ? f : (size_t)p.first;
+                    pages.push_back(GifEncPage{&recs[f], (const uint32_t*)((const uint8_t*)pin + tab_at[tf]), (const uint8_t*)pin + str_at[f]});
+                }
+                gif_enc_write_file(outs[i], pages.data(), p.frames, albums[i]->w, albums[i]->h, time_ms ? time_ms[i] : nullptr,
+                                   dispose ? dispose[i] : nullptr, loop_counts[i]);
+            }
+        }
+        stage_hold(token, false);
+    }
+    dev_free(mem);
+    return rc;
+}
+
+}  // namespace
+}  // namespace imp
+
+using namespace imp;
+
+extern "C" {
+
+size_t impgpu_gif_encode_bound(int width, int height, int frames) { return gif_enc_file_bound(width, height, frames); }
+
+int impgpu_gif_encode_host(const unsigned char* const* frames, int count, int width, int height, int channels, int step,
+                           const int* time_ms, const int* dispose, int loop_count, int segment, unsigned char* out, size_t capacity,
+                           size_t* length) {
+    return gif_encode_host(frames, count, width, height, channels, step, time_ms, dispose, loop_count, segment, out, capacity, length);
+}
+
+int impgpu_batch_encode_gif(const impgpu_image* const* albums, const int* const* time_ms, const int* const* dispose,
+                            const int* loop_counts, int count, int segment, unsigned char* const* outs, const size_t* capacities,
+                            size_t* lengths, int* codes, int* launches) {
+    if (launches) *launches = 0;
+    if (count < 0 || count > 256 || (count > 0 && (!albums || !loop_counts || !outs || !capacities || !lengths || !codes))) return IMP_ERROR_INVALID_ARGS;
+    if (int rc = gif_enc_check_args(0, nullptr, 0, segment)) return rc;
+    for (int i = 0; i < count; i++) lengths[i] = 0;
+    if (count == 0) return IMP_OK;
+    if (int rc = need_env()) {
+        for (int i = 0; i < count; i++) codes[i] = rc;
+        return rc;
+    }
+    TraceRange tr("IMP_STEP_ENCODE");
+    const unsigned long long launched = t_launches;
+    const uint32_t seg = segment ? (uint32_t)segment : (uint32_t)IMPGPU_GIF_ENC_SEGMENT;
+    const size_t cap = stage_cap();
+    std::vector<EncPlan> group;
+    size_t bytes = 0;
+    int first = 0;
+    auto run = [&]() {
+        if (group.empty()) return;
+        const int rc = encode_group(group, albums, time_ms, dispose, loop_counts, seg, outs, capacities, lengths, codes);
+        if (rc)
+            for (const EncPlan& p : group) { codes[p.entry] = rc; lengths[p.entry] = 0; }
+        group.clear();
+        bytes = 0;
+        first = 0;
+    };
+    for (int i = 0; i < count; i++) {
+        const impgpu_image* im = albums[i];
+        codes[i] = IMP_ERROR_INVALID_ARGS;
+        if (!im || !outs[i]) continue;
+        if ((codes[i] = gif_enc_check_geometry(im->w, im->h, im->c, im->frames)) != IMP_OK) continue;
+        if ((codes[i] = gif_enc_check_args(im->frames, dispose ? dispose[i] : nullptr, loop_counts[i], segment)) != IMP_OK) continue;
+        if (fault_hit(IMP_STEP_ENCODE)) { codes[i] = IMP_ERROR_DEVICE; continue; }
+        const size_t bound = gif_enc_file_bound(im->w, im->h, im->frames);
+        if (!group.empty() && cap && bytes + bound > cap) run();        // a call past the staging cap goes in groups
+        group.push_back(EncPlan{i, first, im->frames});
+        first += im->frames;
+        bytes += bound;
+    }
+    run();
+    if (launches) *launches = (int)(t_launches - launched);
+    return IMP_OK;
+}
+
+int impgpu_album_encode_gif(const impgpu_image* album, const int* time_ms, const int* dispose, int loop_count, int segment,
+                            unsigned char* out, size_t capacity, size_t* length) {
+    if (length) *length = 0;
+    if (!album || !out || !length) return IMP_ERROR_INVALID_ARGS;
+    if (int rc = gif_enc_check_args(album->frames <= GIF_ENC_MAX_FRAMES ? album->frames : 0, dispose, loop_count, segment)) return rc;
+    int code = IMP_OK;
+    if (int rc = impgpu_batch_encode_gif(&album, &time_ms, &dispose, &loop_count, 1, segment, &out, &capacity, length, &code, nullptr)) return rc;
+    return code;
+}
+
+}  // extern "C"

@@ -1,0 +1,258 @@
+// imp_gif_enc.hip -- the five launches that turn the albums of a call into GIF streams (impgpu_batch_encode_gif):
+// k_gif_enc_sets, _tables, _index, _lzw and _pack.  The lanes' logic is imp_gif_enc.h's, which the host encoder
+// (impgpu_gif_encode_host) runs too.  Each launch reads what the one before wrote across the kernel boundary of one
+// stream; no wavefront waits for another workgroup.  Workgroup b of a launch finds its work in an item table
+// (GifEncItem: a frame of the call and the part of it), so the launches do not depend on how many albums there are.
+#include "imp_internal.h"
+#include "imp_gif_enc.h"
+
+namespace imp {
+
+__device__ __forceinline__ GifEncFrame gif_enc_frame_of(const GifEncFrameDesc& f) { return GifEncFrame{f.src, f.w, f.h, f.c, f.step, f.wide}; }
+
+// SETS: 4096 pixels a workgroup, 16 consecutive ones a lane (a lane skips a key equal to its last one).  The LDS set
+// holds 1024 keys: a workgroup that fills it has seen four times what any table takes, and says so in the frame's flag.
+__global__ __launch_bounds__(256) void k_gif_enc_sets(GifEncDev D) {
+    __shared__ uint32_t lset[GIF_SET_SLOTS];
+    __shared__ uint32_t flag[2];
+    const GifEncItem it = D.px_items[blockIdx.x];
+    const GifEncFrameDesc& f = D.frames[it.frame];
+    GifColourSet* fs = &D.sets[it.frame];
+    const int tid = (int)threadIdx.x;
+    for (int i = tid; i < GIF_SET_SLOTS; i += 256) lset[i] = 0;
+    if (tid == 0) { flag[0] = *(volatile uint32_t*)&fs->overflow; flag[1] = 0; }
+    __syncthreads();
+    if (flag[0]) return;                                               // the frame is lost already
+    const GifEncFrame fr = gif_enc_frame_of(f);
+    const uint32_t p0 = (uint32_t)it.k * GIF_ENC_PX_BLOCK + (uint32_t)tid * 16u;
+    uint32_t last = 0;
+    for (uint32_t j = 0; j < 16u; j++) {
+        if (p0 + j >= f.total) break;
+        const uint32_t key = gif_enc_key_at(fr, p0 + j);
+        if (key == last) continue;
+        last = key;
+        if (gif_set_insert(lset, key) < 0) flag[1] = 1;
+    }
+    __syncthreads();
+    if (flag[1]) {
+        if (tid == 0) *(volatile uint32_t*)&fs->overflow = 1u;
+        return;
+    }
+    for (int i = tid; i < GIF_SET_SLOTS; i += 256)
+        if (lset[i]) gif_frame_set_add(fs, lset[i]);
+}
+
+// `n` keys (<= 256) of `list` into tabs[0 .. n), ascending: every lane ranks its own
+__device__ __forceinline__ void gif_enc_sort_out(const uint32_t* list, uint32_t n, uint32_t* tab, int tid) {
+    if ((uint32_t)tid < n) tab[gif_rank(list, n, (uint32_t)tid)] = list[tid];
+}
+
+// TABLES: a workgroup per album walks its frames: the frame's keys out of its set, sorted into the frame's table slot,
+// and into the album's union (an LDS set; past 256 keys it is of no more use and takes no more).  Then the verdict.
+__global__ __launch_bounds__(256) void k_gif_enc_tables(GifEncDev D) {
+    __shared__ uint32_t list[GIF_SET_MAX];
+    __shared__ uint32_t uset[GIF_SET_SLOTS];
+    __shared__ uint32_t n, ucount, gtrans;
+    const GifEncAlbumDesc a = D.albums[blockIdx.x];
+    const int tid = (int)threadIdx.x;
+    for (int i = tid; i < GIF_SET_SLOTS; i += 256) uset[i] = 0;
+    if (tid == 0) { n = 0; ucount = 0; gtrans = 0; }
+    __syncthreads();
+    for (int q = 0; q < a.count; q++)                                  // (the sets are final: every lane reads the same)
+        if (D.sets[a.first + q].overflow) return;                      // a frame fits no table: every record stays REFUSED
+    for (int q = 0; q < a.count; q++) {
+        const int f = a.first + q;
+        const GifColourSet* fs = &D.sets[f];
+        const bool ufull = ucount > GIF_SET_MAX;
+        for (int i = tid; i < GIF_SET_SLOTS; i += 256) {
+            const uint32_t k = fs->slot[i];
+            if (!k) continue;
+            const uint32_t at = atomicAdd(&n, 1u);
+            if (at < GIF_SET_MAX) list[at] = k;
+        }
+        __syncthreads();
+        const uint32_t cnt = n < GIF_SET_MAX ? n : GIF_SET_MAX;
+        gif_enc_sort_out(list, cnt, D.tabs + (size_t)f * 256, tid);
+        if ((uint32_t)tid < cnt) {
+            if (list[tid] == GIF_KEY_TRANSPARENT) D.recs[f].has_trans = 1u;
+            if (!ufull) {
+                const int r = gif_set_insert(uset, list[tid]);
+                if (r) atomicAdd(&ucount, r > 0 ? 1u : (uint32_t)GIF_SET_SLOTS);
+            }
+        }
+        if (tid == 0) D.recs[f].nkeys = cnt;
+        __syncthreads();
+        if (tid == 0) n = 0;
+        __syncthreads();
+    }
+    if (ucount <= GIF_SET_MAX) {                                       // one global table: the union, sorted, in the first frame's slot
+        for (int i = tid; i < GIF_SET_SLOTS; i += 256) {
+            const uint32_t k = uset[i];
+            if (!k) continue;
+            const uint32_t at = atomicAdd(&n, 1u);
+            if (at < GIF_SET_MAX) list[at] = k;
+            if (k == GIF_KEY_TRANSPARENT) gtrans = 1u;
+        }
+        __syncthreads();
+        const uint32_t cnt = n < GIF_SET_MAX ? n : GIF_SET_MAX;
+        gif_enc_sort_out(list, cnt, D.tabs + (size_t)a.first * 256, tid);
+        for (int q = tid; q < a.count; q += 256) gif_rec_fill(&D.recs[a.first + q], GIF_ENC_GLOBAL, (uint32_t)a.first, cnt, gtrans != 0);
+    } else {
+        for (int q = tid; q < a.count; q += 256) {
+            GifEncRec* r = &D.recs[a.first + q];
+            gif_rec_fill(r, GIF_ENC_LOCAL, (uint32_t)(a.first + q), r->nkeys, r->has_trans != 0);
+        }
+    }
+}
+
+// INDEX: the frame's table in LDS, four pixels a lane at a time, a dword of indices out
+__global__ __launch_bounds__(256) void k_gif_enc_index(GifEncDev D) {
+    __shared__ uint32_t tab[256];
+    const GifEncItem it = D.px_items[blockIdx.x];
+    const GifEncFrameDesc& f = D.frames[it.frame];
+    const GifEncRec& rec = D.recs[it.frame];
+    if (rec.mode == GIF_ENC_REFUSED) return;
+    const int tid = (int)threadIdx.x;
+    tab[tid] = (uint32_t)tid < rec.nkeys ? D.tabs[(size_t)rec.table_frame * 256 + tid] : 0xFFFFFFFFu;
+    __syncthreads();
+    const GifEncFrame fr = gif_enc_frame_of(f);
+    uint8_t* plane = D.mem + f.plane_off;
+#pragma unroll 1
+    for (int j = 0; j < GIF_ENC_PX_BLOCK / 1024; j++) {
+        const uint32_t pos = (uint32_t)it.k * GIF_ENC_PX_BLOCK + 4u * (uint32_t)(tid + 256 * j);
+        if (pos >= f.total) break;
+        const uint32_t cnt = f.total - pos < 4u ? f.total - pos : 4u;
+        uint32_t v = 0;
+        for (uint32_t q = 0; q < cnt; q++) v |= gif_table_find(tab, gif_enc_key_at(fr, pos + q)) << (8u * q);
+        if (cnt == 4u) *(uint32_t*)(plane + pos) = v;
+        else for (uint32_t q = 0; q < cnt; q++) plane[pos + q] = (uint8_t)(v >> (8u * q));
+    }
+}
+
+// a due batch: packed by the lanes, its whole words out, the rest carried
+__device__ __forceinline__ void gif_enc_flush_wave(GifEncMem& m, GifEncState& e, int mcs, uint32_t* words, uint32_t cap, int lane) {
+    __syncthreads();
+    gif_enc_pack_lane(&m, e, lane);
+    __syncthreads();
+    gif_enc_drain_lane(&m, e, words, cap, lane);
+    const uint32_t carry = gif_enc_carry(&m, e);
+    __syncthreads();
+    gif_enc_rewind_lane(&m, carry, lane);
+    if (e.tail == 1) gif_enc_clear_lane(&m, lane);
+    gif_enc_batch_end(&e, mcs);
+    __syncthreads();
+}
+
+// LZW: a workgroup IS one wavefront and owns one segment; its barriers are that wave's own
+__global__ __launch_bounds__(GIF_LANES) void k_gif_enc_lzw(GifEncDev D) {
+    __shared__ GifEncMem m;
+    const GifEncItem it = D.seg_items[blockIdx.x];
+    const GifEncFrameDesc& f = D.frames[it.frame];
+    const GifEncRec& rec = D.recs[it.frame];
+    if (rec.mode == GIF_ENC_REFUSED) return;
+    const int lane = (int)threadIdx.x;
+    const int mcs = (int)rec.mcs;
+    const uint32_t k = (uint32_t)it.k;
+    if (k >= f.nseg) return;
+    const uint32_t begin = k * f.segment, end = f.total - begin < f.segment ? f.total : begin + f.segment;
+    const uint8_t* px = D.mem + f.plane_off;
+    const uint32_t cap = f.slot_words;
+    uint32_t* words = (uint32_t*)(D.mem + f.scratch_off) + (size_t)k * cap;
+    GifEncState e;
+    gif_enc_start(&e, mcs);
+    gif_enc_rewind_lane(&m, 0u, lane);
+    if (k == 0) {
+        gif_enc_push_tail(&m, &e, mcs, 1);                             // the stream's opening clear (the flush empties the table)
+        gif_enc_flush_wave(m, e, mcs, words, cap, lane);
+    } else {
+        gif_enc_clear_lane(&m, lane);
+        __syncthreads();
+    }
+    for (uint32_t c0 = begin; c0 < end; c0 += GIF_ENC_CHUNK) {
+        const uint32_t cn = end - c0 < (uint32_t)GIF_ENC_CHUNK ? end - c0 : (uint32_t)GIF_ENC_CHUNK;
+        const uint32_t o = (uint32_t)lane * 16u;
+        if (o + 16u <= cn && ((c0 + o) & 15u) == 0u) *(uint4*)&m.px[o] = *(const uint4*)(px + c0 + o);
+        else for (uint32_t b = o; b < o + 16u && b < cn; b++) m.px[b] = px[c0 + b];
+        __syncthreads();
+        for (uint32_t i = 0; i < cn; i += 4u) {                         // four indices per LDS read: the walk waits for one load less
+            const uint32_t quad = GIF_ENC_UNI(*(const uint32_t*)&m.px[i]);
+#pragma unroll 1
+            for (uint32_t q = 0; q < 4u && i + q < cn; q++)
+                if (gif_enc_step(&m, &e, mcs, (quad >> (8u * q)) & 255u)) gif_enc_flush_wave(m, e, mcs, words, cap, lane);
+        }
+        __syncthreads();
+    }
+    gif_enc_finish(&m, &e, mcs, k + 1u == f.nseg);
+    gif_enc_flush_wave(m, e, mcs, words, cap, lane);
+    if (lane == 0) {
+        gif_enc_last_word(&m, e, words, cap);
+        D.segbits[f.seg0 + k] = e.s.bitpos;
+    }
+}
+
+// PACK: 4096 bytes of a frame's stream a workgroup, 16 a lane.  The segments' bit lengths are summed 256 at a time
+// (every workgroup of a frame does that again: the lengths are a few words); a lane whose first bit falls into the chunk
+// finds its segment there by bisection.
+__global__ __launch_bounds__(256) void k_gif_enc_pack(GifEncDev D) {
+    __shared__ uint32_t pre[256];
+    const GifEncItem it = D.pack_items[blockIdx.x];
+    const GifEncFrameDesc& f = D.frames[it.frame];
+    GifEncRec* rec = &D.recs[it.frame];
+    if (rec->mode == GIF_ENC_REFUSED) return;
+    const int tid = (int)threadIdx.x;
+    const uint32_t* segbits = D.segbits + f.seg0;
+    const uint32_t k0 = (uint32_t)it.k * GIF_ENC_PACK_BLOCK + (uint32_t)tid * 16u;
+    const uint64_t first_bit = (uint64_t)k0 * 8u;
+    uint32_t run = 0;
+    GifPackCursor c{f.nseg, 0};
+    bool found = false;
+    for (uint32_t c0 = 0; c0 < f.nseg; c0 += 256u) {
+        pre[tid] = c0 + (uint32_t)tid < f.nseg ? segbits[c0 + tid] : 0u;
+        __syncthreads();
+        for (int d = 1; d < 256; d <<= 1) {
+            const uint32_t t = tid >= d ? pre[tid - d] : 0u;
+            __syncthreads();
+            pre[tid] += t;
+            __syncthreads();
+        }
+        const uint32_t tot = pre[255];
+        if (!found && first_bit < (uint64_t)run + tot) {
+            const uint32_t rel = (uint32_t)first_bit - run;
+            uint32_t lo = 0;
+            for (uint32_t step = 128; step; step >>= 1)
+                if (pre[lo + step - 1] <= rel) lo += step;
+            c.seg = c0 + lo;
+            c.start = run + (lo ? pre[lo - 1] : 0u);
+            found = true;
+        }
+        run += tot;
+        __syncthreads();
+    }
+    const uint32_t nbytes = (run + 7u) >> 3;
+    if (it.k == 0 && tid == 0) rec->stream_bytes = nbytes;
+    if (!found) return;
+    uint8_t* out = D.mem + f.out_off;
+    const uint8_t* scratch = D.mem + f.scratch_off;
+    for (uint32_t j = 0; j < 16u && k0 + j < nbytes; j++) {
+        const uint32_t v = gif_enc_stream_byte(segbits, f.nseg, scratch, (size_t)f.slot_words * 4u, &c, (k0 + j) * 8u);
+        gif_enc_put_byte(out, f.out_cap, k0 + j, nbytes, v);
+    }
+}
+
+int launch_gif_encode(const GifEncDev& D, long long npx, long long nseg, long long npack, int nalbums, hipStream_t s) {
+    if (!D.mem || npx <= 0 || nseg <= 0 || npack <= 0 || nalbums <= 0 || npx > 0x7fffffffLL || nseg > 0x7fffffffLL || npack > 0x7fffffffLL)
+        return IMP_ERROR_INVALID_ARGS;
+    hipLaunchKernelGGL(k_gif_enc_sets, dim3((unsigned)npx), dim3(256), 0, s, D);
+    IMP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_gif_enc_tables, dim3((unsigned)nalbums), dim3(256), 0, s, D);
+    IMP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_gif_enc_index, dim3((unsigned)npx), dim3(256), 0, s, D);
+    IMP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_gif_enc_lzw, dim3((unsigned)nseg), dim3(GIF_LANES), 0, s, D);
+    IMP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_gif_enc_pack, dim3((unsigned)npack), dim3(256), 0, s, D);
+    IMP_HIP(hipGetLastError());
+    return IMP_OK;
+}
+
+}  // namespace imp

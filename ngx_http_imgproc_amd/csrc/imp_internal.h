@@ -511,6 +511,12 @@ struct GifSegSlot { int page, k; };
 int launch_gif_lzw_split(uint8_t* blob, size_t table_off, size_t split_off, size_t slots_off, const MixIndex& ix, int most, long long nslots,
                          uint32_t* status, hipStream_t s);
 
+// imp_gif_enc.hip: the albums of a call into GIF streams (impgpu_batch_encode_gif): k_gif_enc_sets and k_gif_enc_index over
+// `npx` pixel items, k_gif_enc_tables over the albums, k_gif_enc_lzw over `nseg` segment items, k_gif_enc_pack over `npack`
+// items; the descriptors (imp_gif_enc.h) lie in the call's device block.
+struct GifEncDev;
+int launch_gif_encode(const GifEncDev& D, long long npx, long long nseg, long long npack, int nalbums, hipStream_t s);
+
 // imp_png_inflate.hip: the zlib streams of a call's PNG files, one workgroup of one wavefront per stream (impgpu_batch_decode_png_ex
 // with IMPGPU_PNG_DEVICE_INFLATE).  `descs` (imp_png.h) lie in device memory; descriptor k is workgroup k's.
 struct PngInflateDesc;

@@ -35,6 +35,7 @@ PNG_DEVICE_INFLATE = 8          # not part of PNG_ALL: how files are decoded (k_
 # impgpu_*_decode_gif_ex flags (include/impgpu.h)
 GIF_SPLIT = 1                   # cut every page at its clear codes, a wavefront per segment (k_gif_lzw_scan / _len / _emit)
 GIF_SPLIT_MIN_BYTES = 2048      # IMPGPU_GIF_SPLIT_MIN_BYTES: a clear code nearer than this to its segment's start is no cut
+GIF_ENC_SEGMENT = 8192          # IMPGPU_GIF_ENC_SEGMENT: the pixels between two clear codes of an encoded page (segment = 0)
 
 
 def _b(s):
@@ -937,6 +938,77 @@ def gif_pages_split(blob):
     segs = (C.c_int * max(1, pages))()
     rc = lib.impgpu_gif_pages_split(blob, len(blob), buf.ctypes.data, n.value, C.byref(n), segs, pages)
     return rc, (buf[: n.value].tobytes() if rc == 0 else None), list(segs[:pages])
+
+
+IP_ = C.POINTER(C.c_int)
+
+
+def _ints(values):
+    return None if values is None else (C.c_int * max(1, len(values)))(*[int(v) for v in values])
+
+
+def _gif_out(rc, buf, length):
+    """(code, the file or None, *length, whether every byte the call had no business writing still holds the fill)"""
+    n = length.value
+    written = n if rc == 0 else 0
+    return rc, (buf[:n].tobytes() if rc == 0 else None), n, bool((buf[written:] == 0xA5).all())
+
+
+def gif_encode_bound(width, height, frames):
+    """impgpu_gif_encode_bound: a size no GIF file of that album exceeds (0: a geometry the encoder refuses)"""
+    return lib.impgpu_gif_encode_bound(int(width), int(height), int(frames))
+
+
+def encode_gif(album, time_ms=None, dispose=None, loop_count=-1, segment=0, capacity=None, guard=64):
+    """impgpu_album_encode_gif: the album (or single image) as a GIF file written on the device -- exact palette, LZW cut into
+    segments of `segment` pixels, a wavefront each -> (code, bytes or None, length, intact).  `capacity` defaults to
+    gif_encode_bound; `guard` bytes behind it are checked: intact = nothing at or behind out[length] (out[0] when the call
+    failed) was written."""
+    cap = gif_encode_bound(album.shape[1], album.shape[0], album.count) if capacity is None else int(capacity)
+    buf = np.full(cap + guard, 0xA5, np.uint8)
+    n = C.c_size_t(0)
+    rc = lib.impgpu_album_encode_gif(album.h, _ints(time_ms), _ints(dispose), int(loop_count), int(segment), buf.ctypes.data, cap, C.byref(n))
+    return _gif_out(rc, buf, n)
+
+
+def encode_gif_host(frames, time_ms=None, dispose=None, loop_count=-1, segment=0, capacity=None, guard=64, channels=None):
+    """impgpu_gif_encode_host (no device): frames = HxWxC uint8 arrays of one geometry and one row pitch (views with padded
+    rows are fine) -> (code, bytes or None, length, intact), as encode_gif."""
+    first = frames[0]
+    hh, ww, cc = first.shape
+    step = first.strides[0]
+    assert all(f.shape == first.shape and f.strides == (step, cc, 1) and f.dtype == np.uint8 for f in frames)
+    ptrs = (C.c_void_p * len(frames))(*[f.ctypes.data for f in frames])
+    cap = gif_encode_bound(ww, hh, len(frames)) if capacity is None else int(capacity)
+    buf = np.full(cap + guard, 0xA5, np.uint8)
+    n = C.c_size_t(0)
+    rc = lib.impgpu_gif_encode_host(ptrs, len(frames), ww, hh, cc if channels is None else channels, step, _ints(time_ms), _ints(dispose),
+                                    int(loop_count), int(segment), buf.ctypes.data, cap, C.byref(n))
+    return _gif_out(rc, buf, n)
+
+
+def batch_encode_gif(albums, time_ms=None, dispose=None, loop_counts=None, segment=0, capacities=None, count=None, guard=64):
+    """impgpu_batch_encode_gif: albums (Images; an entry may be None) -> (code, [(code, bytes or None, length, intact) ...],
+    launches).  time_ms / dispose: per album a list or None; loop_counts default to -1; capacities to gif_encode_bound."""
+    n = len(albums)
+    m = max(1, n)
+    handles = (C.c_void_p * m)(*[_handle(a) for a in albums])
+    keep_t = [_ints(None if time_ms is None else time_ms[i]) for i in range(n)]
+    keep_d = [_ints(None if dispose is None else dispose[i]) for i in range(n)]
+    tarr = (IP_ * m)(*[C.cast(t, IP_) if t is not None else IP_() for t in keep_t])
+    darr = (IP_ * m)(*[C.cast(d, IP_) if d is not None else IP_() for d in keep_d])
+    loops = (C.c_int * m)(*[-1 if loop_counts is None else int(loop_counts[i]) for i in range(n)])
+    caps = [(gif_encode_bound(a.shape[1], a.shape[0], a.count) if a is not None else 0) if capacities is None or capacities[i] is None else int(capacities[i])
+            for i, a in enumerate(albums)]
+    bufs = [np.full(max(1, c) + guard, 0xA5, np.uint8) for c in caps]
+    outs = (C.c_void_p * m)(*[b.ctypes.data for b in bufs])
+    carr = (C.c_size_t * m)(*caps)
+    lens = (C.c_size_t * m)()
+    codes = (C.c_int * m)(*([-1] * m))
+    launches = C.c_int(-1)
+    rc = lib.impgpu_batch_encode_gif(handles, tarr, darr, loops, n if count is None else count, int(segment), outs, carr, lens, codes,
+                                     C.byref(launches))
+    return rc, [_gif_out(codes[i], bufs[i], C.c_size_t(lens[i])) for i in range(n)], launches.value
 
 
 def batch_filters(ptr, stride, w, h, c, step, count, filters, allow_experiments=1, stream=None):
