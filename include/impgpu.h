@@ -749,7 +749,8 @@ int impgpu_gif_pages_split(const unsigned char* blob, size_t size, unsigned char
  *      REFUSED, IMP_ERROR_INVALID_ARGS before a device is looked for: a segment outside {0} and [256, 2^24], a dispose
  *      outside 0..3, loop_count > 65535.  IMP_ERROR_UNSUPPORTED, *length = 0, nothing written: 1- or 2-channel frames, a
  *      larger side, more frames, a frame whose colours (and transparency) fit no table of 256 -- blur, vignette or a
- *      watermark do that: download the frames and quantise on the host as before.  IMP_ERROR_MALLOC_FAILED: `capacity`
+ *      watermark do that: use the _ex calls with IMPGPU_GIF_ENC_QUANTIZE (below), or download the frames and quantise on
+ *      the host as before.  IMP_ERROR_MALLOC_FAILED: `capacity`
  *      is too small; nothing is written, *length is the size needed; impgpu_gif_encode_bound is always enough.
  *      FIVE launches for a call, whatever it holds: k_gif_enc_sets (a colour set per frame: an LDS hash set per workgroup,
  *      then compare-and-swap into the frame's), k_gif_enc_tables (a workgroup per album sorts the sets, unites them and
@@ -782,6 +783,58 @@ size_t impgpu_gif_encode_bound(int width, int height, int frames);
 int impgpu_gif_encode_host(const unsigned char* const* frames, int count, int width, int height, int channels, int step,
                            const int* time_ms, const int* dispose, int loop_count, int segment,
                            unsigned char* out, size_t capacity, size_t* length);
+
+/* ---- GIF FILES out, PAST 256 COLOURS (opt-in): the calls above with a `flags` argument.  flags = 0 IS the call without
+ *      _ex in every respect -- files, codes, refusals, launches, waits -- and the calls without _ex keep refusing.  A flag
+ *      bit other than IMPGPU_GIF_ENC_QUANTIZE: IMP_ERROR_INVALID_ARGS before a device is looked for.
+ *      IMPGPU_GIF_ENC_QUANTIZE extends the file's definition above to a frame whose OWN key set (its colours, plus
+ *      "transparent") exceeds 256 -- a watermark, a blur, a vignette, an overlay, a non-NN resize do that.  An album with
+ *      such a frame has no global table; its other frames keep the exact local tables of their own sets; such a frame's
+ *      local table and indices are, all in integers, with no dithering and no nearest-colour search:
+ *      1. KEYS.  T = 1 if the frame has a transparent pixel, else 0; K = 256 - T.  Transparent pixels take no part in 2-5.
+ *      2. HISTOGRAM.  A pixel's cell is (R>>3, G>>3, B>>3).  Each of the 32768 cells holds four unsigned 32-bit sums over
+ *         its pixels: the count n and the sums of R, G and B (full 8-bit values).  4096 x 4096 pixels keep them below 2^32.
+ *      3. BOXES.  A box is an inclusive cell range on each axis, always shrunk to the tight bounds of its non-empty cells.
+ *         Start with one box around all non-empty cells.  While there are fewer than K boxes: among the boxes whose longest
+ *         side s = max(r1-r0, g1-g0, b1-b0) is > 0 take the one with the largest n * s (ties: the lowest box number; none:
+ *         stop) and cut it across its longest axis (ties: R, then G, then B).  With m[j] the box's pixels in plane j of
+ *         that axis (j = 0..s), t = the smallest j with m[0] + ... + m[j] >= ceil(n / 2), at most s - 1.  Planes 0..t keep
+ *         the box's number, planes t+1..s become box number (current box count); both are shrunk to tight bounds.
+ *      4. COLOURS.  A box's colour per channel is (2 * sum + n) / (2 * n) in integer division, from the box's sums.  Boxes
+ *         are disjoint and a mean lies inside its box, so the colours are distinct.
+ *      5. TABLE AND INDICES.  The table lists the box colours ascending by R<<16 | G<<8 | B, then the transparent entry
+ *         when T; padding, min_code_size and the rest as above; nkeys = boxes + T.  A pixel's index is the rank of the box
+ *         its cell lies in; a transparent pixel's is nkeys - 1.
+ *      The sums do not depend on the order of the additions: the device's atomics give the same file on every run.  An
+ *      album whose frames all fit gets exactly the file it gets without the flag.
+ *      EIGHT launches for a group of albums under the flag, whatever it holds: k_gif_enc_sets, k_gif_enc_claim (one
+ *      workgroup hands the pool's histogram slots to the frames that overflowed, a whole album or none of it),
+ *      k_gif_enc_hist (the 4096-pixel items again; equal cells are combined in a lane's registers and in an LDS table
+ *      before they reach device memory), k_gif_enc_cut (a workgroup per slot: a summed-volume table of the counts in 128 KB
+ *      of LDS, up to 255 cuts, the table, the record and a 32768-byte cell -> index table), k_gif_enc_tables,
+ *      k_gif_enc_index (a quantised frame's pixels go through the cell -> index table, staged in LDS), k_gif_enc_lzw and
+ *      k_gif_enc_pack.  A slot is 544 KB; the pool holds as many as fit under $IMPGPU_STAGE_CAP_MB (at least one, at most
+ *      one per frame of the group).  An album that got no slots is encoded by the same call in a FURTHER group of eight
+ *      launches, whose pool holds what its albums need; *launches is 8 x the groups.  Two waits per group.
+ *      impgpu_gif_encode_bound holds unchanged: the stream's bound does not depend on the table.
+ *      MEASURED (profiles/gif_quant_probe.json, one session, photo frames of 189 k colours): a lone
+ *      640x480 frame 2.75 ms, 8 frames 3.08 ms, 64 albums of 8 frames at 320x240 25.2 ms -- against 0.10 / 0.67 / 12.7 ms for
+ *      the frames' download alone and 7.7 / 61.5 / 1386 ms for that plus impgpu_gif_encode_host_ex on one thread.  Per launch
+ *      for the 8 frames: k_gif_enc_lzw 1735 us, k_gif_enc_cut 931, k_gif_enc_hist 106, the other five 46 together. ---- */
+#define IMPGPU_GIF_ENC_QUANTIZE 1
+int impgpu_album_encode_gif_ex(const impgpu_image* album, const int* time_ms, const int* dispose, int loop_count, int segment,
+                               int flags, unsigned char* out, size_t capacity, size_t* length);
+int impgpu_batch_encode_gif_ex(const impgpu_image* const* albums, const int* const* time_ms, const int* const* dispose,
+                               const int* loop_counts, int count, int segment, int flags, unsigned char* const* outs,
+                               const size_t* capacities, size_t* lengths, int* codes, int* launches);
+int impgpu_gif_encode_host_ex(const unsigned char* const* frames, int count, int width, int height, int channels, int step,
+                              const int* time_ms, const int* dispose, int loop_count, int segment, int flags,
+                              unsigned char* out, size_t capacity, size_t* length);
+/* diagnostic, host, no device: steps 1-5 on ONE frame, whatever its colour count: table = *entries x (R,G,B) bytes (room
+ * for 768; the transparent entry is 0,0,0), *entries = nkeys, *transparent_index = nkeys - 1 or -1, indices = width x height
+ * bytes in raster order.  Geometry and step are checked as by impgpu_gif_encode_host. */
+int impgpu_gif_quantize_host(const unsigned char* frame, int width, int height, int channels, int step,
+                             unsigned char* table, int* entries, int* transparent_index, unsigned char* indices);
 
 /* ---- batch entry points (benchmark / multi-frame albums: bridge.c:578,591,608,632).
  *      `count` frames of identical geometry, frame i at base + i*frame_stride bytes,

@@ -175,6 +175,12 @@ SIGNATURES = {
     "impgpu_gif_encode_bound": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "impgpu_gif_encode_host": (C.c_int, [PP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, IP, IP, C.c_int, C.c_int, P, C.c_size_t,
                                          C.POINTER(C.c_size_t)]),
+    "impgpu_album_encode_gif_ex": (C.c_int, [P, IP, IP, C.c_int, C.c_int, C.c_int, P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "impgpu_batch_encode_gif_ex": (C.c_int, [PP, C.POINTER(IP), C.POINTER(IP), IP, C.c_int, C.c_int, C.c_int, PP, C.POINTER(C.c_size_t),
+                                             C.POINTER(C.c_size_t), IP, IP]),
+    "impgpu_gif_encode_host_ex": (C.c_int, [PP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, IP, IP, C.c_int, C.c_int, C.c_int, P, C.c_size_t,
+                                            C.POINTER(C.c_size_t)]),
+    "impgpu_gif_quantize_host": (C.c_int, [P, C.c_int, C.c_int, C.c_int, C.c_int, P, IP, IP, P]),
     "impgpu_album_download_fi": (C.c_int, [P, C.c_int, PP, IP]),
     "impgpu_batch_download_fi": (C.c_int, [PP, IP, C.c_int, PP, IP, IP, IP]),
     "impgpu_batch_album_download": (C.c_int, [PP, C.c_int, PP, IP, IP]),

@@ -4,6 +4,8 @@
 // records (the verdicts, the table sizes, the streams' lengths -- what the files' sizes depend on), once for the tables
 // and streams of the files that fit their callers' buffers.  The host writes only the container around them
 // (gif_enc_write_file).  impgpu_gif_encode_host is the same pipeline with no device: imp_gif_enc.h's lane code on one thread.
+// The _ex calls take flags: under IMPGPU_GIF_ENC_QUANTIZE a group's block also holds a pool of histogram slots, eight launches
+// run, and the albums the pool had no room for are encoded in further groups (impgpu_batch_encode_gif_ex).
 #include "imp_internal.h"
 #include "imp_gif_enc.h"
 
@@ -19,9 +21,13 @@ int need_env() {
 
 // ---------------------------------------------------------------- the device route: one group of albums
 struct EncPlan { int entry, first, frames; };
+struct EncDeferred { int entry; uint32_t need; };        // an album whose overflowed frames got no histogram slots, and how many it wants
 
+// flags & IMPGPU_GIF_ENC_QUANTIZE: a pool of `nslots` histogram slots lies in the block, and three launches more run
+// (claim, hist, cut); an album the pool had no room for comes back in `deferred` with nothing written for it.
 int encode_group(const std::vector<EncPlan>& plans, const impgpu_image* const* albums, const int* const* time_ms, const int* const* dispose,
-                 const int* loop_counts, uint32_t segment, unsigned char* const* outs, const size_t* caps, size_t* lens, int* codes) {
+                 const int* loop_counts, uint32_t segment, int flags, int nslots, std::vector<EncDeferred>* deferred, unsigned char* const* outs,
+                 const size_t* caps, size_t* lens, int* codes) {
     hipStream_t s = env_stream();
     const int na = (int)plans.size();
     int nf = 0;
@@ -57,11 +63,15 @@ int encode_group(const std::vector<EncPlan>& plans, const impgpu_image* const* a
         }
     }
     if (nsegs > 0x7fffffffull) return IMP_ERROR_UNSUPPORTED;
-    // the block: what is uploaded | records + sets (zeroed) | tables | segment lengths | planes | slots | streams
+    // the block: what is uploaded | records + album words + sets + pool (zeroed) | tables | segment lengths | planes | slots | streams
+    const bool quant = (flags & IMPGPU_GIF_ENC_QUANTIZE) != 0;
+    const size_t ns = quant ? (size_t)nslots : 0;
     const size_t o_fd = 0, o_ad = o_fd + up256(fd.size() * sizeof(GifEncFrameDesc)), o_px = o_ad + up256(ad.size() * sizeof(GifEncAlbumDesc)),
                  o_seg = o_px + up256(px_items.size() * sizeof(GifEncItem)), o_pack = o_seg + up256(seg_items.size() * sizeof(GifEncItem)),
-                 o_rec = o_pack + up256(pack_items.size() * sizeof(GifEncItem)), o_set = o_rec + up256((size_t)nf * sizeof(GifEncRec)),
-                 o_tab = o_set + up256((size_t)nf * sizeof(GifColourSet)), o_bits = o_tab + up256((size_t)nf * 1024),
+                 o_rec = o_pack + up256(pack_items.size() * sizeof(GifEncItem)), o_need = o_rec + up256((size_t)nf * sizeof(GifEncRec)),
+                 o_set = o_need + (quant ? up256((size_t)na * 4) : 0), o_sframe = o_set + up256((size_t)nf * sizeof(GifColourSet)),
+                 o_strans = o_sframe + up256(ns * 4), o_hist = o_strans + up256(ns * 4), o_slotof = o_hist + ns * GIF_Q_HIST_WORDS * 4,
+                 o_cmap = o_slotof + (quant ? up256((size_t)nf * 4) : 0), o_tab = o_cmap + ns * GIF_Q_CELLS, o_bits = o_tab + up256((size_t)nf * 1024),
                  o_plane = o_bits + up256((size_t)nsegs * 4), o_scr = o_plane + planes, o_out = o_scr + scratch, o_end = o_out + outb;
     for (GifEncFrameDesc& d : fd) { d.plane_off += (long long)o_plane; d.scratch_off += (long long)o_scr; d.out_off += (long long)o_out; }
     void* mem = nullptr;
@@ -75,27 +85,34 @@ int encode_group(const std::vector<EncPlan>& plans, const impgpu_image* const* a
     std::memcpy(head.data() + o_pack, pack_items.data(), pack_items.size() * sizeof(GifEncItem));
     int rc = upload_to(m, head.data(), head.size(), s);
     if (!rc) {
-        const hipError_t e = hipMemsetAsync(m + o_rec, 0, o_tab - o_rec, s);
+        const hipError_t e = hipMemsetAsync(m + o_rec, 0, (quant ? o_slotof : o_tab) - o_rec, s);
         if (e != hipSuccess) { set_error("hipMemsetAsync(gif encode)", e); rc = IMP_ERROR_DEVICE; }
     }
     GifEncDev D;
     D.mem = m;
     D.frames = (const GifEncFrameDesc*)(m + o_fd); D.albums = (const GifEncAlbumDesc*)(m + o_ad);
     D.px_items = (const GifEncItem*)(m + o_px); D.seg_items = (const GifEncItem*)(m + o_seg); D.pack_items = (const GifEncItem*)(m + o_pack);
+    D.flags = flags; D.nslots = (int)ns;
+    D.slot_of = quant ? (int*)(m + o_slotof) : nullptr; D.slot_frame = quant ? (uint32_t*)(m + o_sframe) : nullptr;
+    D.slot_trans = quant ? (uint32_t*)(m + o_strans) : nullptr; D.hist = quant ? (uint32_t*)(m + o_hist) : nullptr;
+    D.cmaps = quant ? m + o_cmap : nullptr; D.album_need = quant ? (uint32_t*)(m + o_need) : nullptr;
     D.sets = (GifColourSet*)(m + o_set); D.tabs = (uint32_t*)(m + o_tab); D.recs = (GifEncRec*)(m + o_rec); D.segbits = (uint32_t*)(m + o_bits);
     if (!rc) rc = launch_gif_encode(D, (long long)px_items.size(), (long long)seg_items.size(), (long long)pack_items.size(), na, s);
-    // the first wait: the records
+    // the first wait: the records (and, behind them, the albums' words)
     std::vector<GifEncRec> recs((size_t)nf);
+    std::vector<uint32_t> need((size_t)na, 0u);
+    const size_t rec_bytes = quant ? (o_need - o_rec) + need.size() * 4 : recs.size() * sizeof(GifEncRec);
     void *pin = nullptr, *token = nullptr;
-    if (!rc) rc = stage_begin(recs.size() * sizeof(GifEncRec), &pin, &token);
+    if (!rc) rc = stage_begin(rec_bytes, &pin, &token);
     if (!rc) {
-        const hipError_t e = hipMemcpyAsync(pin, D.recs, recs.size() * sizeof(GifEncRec), hipMemcpyDeviceToHost, s);
+        const hipError_t e = hipMemcpyAsync(pin, D.recs, rec_bytes, hipMemcpyDeviceToHost, s);
         if (e != hipSuccess) { set_error("hipMemcpyAsync(gif encode records)", e); rc = IMP_ERROR_DEVICE; }
     }
     if (rc) { (void)hipStreamSynchronize(s); dev_free(mem); return rc; }
     stage_hold(token, true);
     rc = lane_wait();
     if (!rc) std::memcpy(recs.data(), pin, recs.size() * sizeof(GifEncRec));
+    if (!rc && quant) std::memcpy(need.data(), (const uint8_t*)pin + (o_need - o_rec), need.size() * 4);
     stage_hold(token, false);
     if (rc) { dev_free(mem); return rc; }
     // the files' sizes; what fits is fetched: per frame its table (local tables; the first frame's for a global one) and its stream
@@ -106,6 +123,7 @@ int encode_group(const std::vector<EncPlan>& plans, const impgpu_image* const* a
         const EncPlan& p = plans[(size_t)a];
         const int i = p.entry;
         const GifEncRec* r0 = &recs[(size_t)p.first];
+        if (r0->mode == GIF_ENC_REFUSED && need[(size_t)a]) { deferred->push_back(EncDeferred{i, need[(size_t)a]}); continue; }
         if (r0->mode == GIF_ENC_REFUSED) { codes[i] = IMP_ERROR_UNSUPPORTED; lens[i] = 0; continue; }
         bool sane = true;
         size_t need = 13 + (loop_counts[i] >= 0 ? 19 : 0) + 1 + (r0->mode == GIF_ENC_GLOBAL ? gif_enc_table_bytes(r0->nkeys) : 0);
@@ -180,10 +198,28 @@ int impgpu_gif_encode_host(const unsigned char* const* frames, int count, int wi
     return gif_encode_host(frames, count, width, height, channels, step, time_ms, dispose, loop_count, segment, out, capacity, length);
 }
 
+int impgpu_gif_encode_host_ex(const unsigned char* const* frames, int count, int width, int height, int channels, int step,
+                              const int* time_ms, const int* dispose, int loop_count, int segment, int flags, unsigned char* out,
+                              size_t capacity, size_t* length) {
+    return gif_encode_host_ex(frames, count, width, height, channels, step, time_ms, dispose, loop_count, segment, flags, out, capacity, length);
+}
+
+int impgpu_gif_quantize_host(const unsigned char* frame, int width, int height, int channels, int step, unsigned char* table,
+                             int* entries, int* transparent_index, unsigned char* indices) {
+    return gif_quantize_host(frame, width, height, channels, step, table, entries, transparent_index, indices);
+}
+
 int impgpu_batch_encode_gif(const impgpu_image* const* albums, const int* const* time_ms, const int* const* dispose,
                             const int* loop_counts, int count, int segment, unsigned char* const* outs, const size_t* capacities,
                             size_t* lengths, int* codes, int* launches) {
+    return impgpu_batch_encode_gif_ex(albums, time_ms, dispose, loop_counts, count, segment, 0, outs, capacities, lengths, codes, launches);
+}
+
+int impgpu_batch_encode_gif_ex(const impgpu_image* const* albums, const int* const* time_ms, const int* const* dispose,
+                               const int* loop_counts, int count, int segment, int flags, unsigned char* const* outs,
+                               const size_t* capacities, size_t* lengths, int* codes, int* launches) {
     if (launches) *launches = 0;
+    if (flags & ~IMPGPU_GIF_ENC_QUANTIZE) return IMP_ERROR_INVALID_ARGS;
     if (count < 0 || count > 256 || (count > 0 && (!albums || !loop_counts || !outs || !capacities || !lengths || !codes))) return IMP_ERROR_INVALID_ARGS;
     if (int rc = gif_enc_check_args(0, nullptr, 0, segment)) return rc;
     for (int i = 0; i < count; i++) lengths[i] = 0;
@@ -196,16 +232,22 @@ int impgpu_batch_encode_gif(const impgpu_image* const* albums, const int* const*
     const unsigned long long launched = t_launches;
     const uint32_t seg = segment ? (uint32_t)segment : (uint32_t)IMPGPU_GIF_ENC_SEGMENT;
     const size_t cap = stage_cap();
+    // the pool of a group: the histogram slots that fit under the cap (256 MB where there is none), one at least, never
+    // more than the group has frames; a group of deferred albums gets what they need
+    const size_t pool = std::max<size_t>(1, (cap ? cap : (size_t)256 << 20) / GIF_Q_SLOT_BYTES);
     std::vector<EncPlan> group;
-    size_t bytes = 0;
+    std::vector<EncDeferred> deferred, again;
+    size_t bytes = 0, want = 0;
     int first = 0;
-    auto run = [&]() {
+    auto run = [&](std::vector<EncDeferred>* left, size_t slots) {
         if (group.empty()) return;
-        const int rc = encode_group(group, albums, time_ms, dispose, loop_counts, seg, outs, capacities, lengths, codes);
+        const int rc = encode_group(group, albums, time_ms, dispose, loop_counts, seg, flags, (int)std::min<size_t>(slots, (size_t)first), left, outs,
+                                    capacities, lengths, codes);
         if (rc)
             for (const EncPlan& p : group) { codes[p.entry] = rc; lengths[p.entry] = 0; }
         group.clear();
         bytes = 0;
+        want = 0;
         first = 0;
     };
     for (int i = 0; i < count; i++) {
@@ -216,12 +258,26 @@ int impgpu_batch_encode_gif(const impgpu_image* const* albums, const int* const*
         if ((codes[i] = gif_enc_check_args(im->frames, dispose ? dispose[i] : nullptr, loop_counts[i], segment)) != IMP_OK) continue;
         if (fault_hit(IMP_STEP_ENCODE)) { codes[i] = IMP_ERROR_DEVICE; continue; }
         const size_t bound = gif_enc_file_bound(im->w, im->h, im->frames);
-        if (!group.empty() && cap && bytes + bound > cap) run();        // a call past the staging cap goes in groups
+        if (!group.empty() && cap && bytes + bound > cap) run(&deferred, pool);    // a call past the staging cap goes in groups
         group.push_back(EncPlan{i, first, im->frames});
         first += im->frames;
         bytes += bound;
     }
-    run();
+    run(&deferred, pool);
+    for (const EncDeferred& d : deferred) {                             // the albums the pools had no room for: further groups
+        const impgpu_image* im = albums[d.entry];
+        const size_t bound = gif_enc_file_bound(im->w, im->h, im->frames);
+        if (!group.empty() && ((cap && bytes + bound > cap) || want + d.need > pool)) run(&again, want);
+        group.push_back(EncPlan{d.entry, first, im->frames});
+        first += im->frames;
+        bytes += bound;
+        want += d.need;
+    }
+    run(&again, want);
+    for (const EncDeferred& d : again) {                                // (a group that holds what its albums need defers none)
+        codes[d.entry] = IMP_ERROR_DEVICE; lengths[d.entry] = 0;
+        set_error_text("gif encode: an album was deferred twice");
+    }
     if (launches) *launches = (int)(t_launches - launched);
     return IMP_OK;
 }
@@ -233,6 +289,17 @@ int impgpu_album_encode_gif(const impgpu_image* album, const int* time_ms, const
     if (int rc = gif_enc_check_args(album->frames <= GIF_ENC_MAX_FRAMES ? album->frames : 0, dispose, loop_count, segment)) return rc;
     int code = IMP_OK;
     if (int rc = impgpu_batch_encode_gif(&album, &time_ms, &dispose, &loop_count, 1, segment, &out, &capacity, length, &code, nullptr)) return rc;
+    return code;
+}
+
+int impgpu_album_encode_gif_ex(const impgpu_image* album, const int* time_ms, const int* dispose, int loop_count, int segment, int flags,
+                               unsigned char* out, size_t capacity, size_t* length) {
+    if (length) *length = 0;
+    if (flags & ~IMPGPU_GIF_ENC_QUANTIZE) return IMP_ERROR_INVALID_ARGS;
+    if (!album || !out || !length) return IMP_ERROR_INVALID_ARGS;
+    if (int rc = gif_enc_check_args(album->frames <= GIF_ENC_MAX_FRAMES ? album->frames : 0, dispose, loop_count, segment)) return rc;
+    int code = IMP_OK;
+    if (int rc = impgpu_batch_encode_gif_ex(&album, &time_ms, &dispose, &loop_count, 1, segment, flags, &out, &capacity, length, &code, nullptr)) return rc;
     return code;
 }
 

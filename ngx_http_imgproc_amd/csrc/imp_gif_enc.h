@@ -62,6 +62,28 @@ IMP_GIF_HD void gif_or(uint32_t* p, uint32_t v) {
     *p |= v;
 #endif
 }
+// *p = min / max of *p and the `v` of the lanes that `take`.  EVERY lane of a group of 32 consecutive lanes calls it with
+// the same p: on the device the group folds its values with five exchanges and one lane goes to memory.
+IMP_GIF_HD void gif_group_min(uint32_t* p, uint32_t v, bool take, int lane) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t x = take ? v : 0xFFFFFFFFu;
+    for (int d = 16; d; d >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)x, d); x = o < x ? o : x; }
+    if ((lane & 31) == 0 && x != 0xFFFFFFFFu) atomicMin(p, x);
+#else
+    (void)lane;
+    if (take && v < *p) *p = v;
+#endif
+}
+IMP_GIF_HD void gif_group_max(uint32_t* p, uint32_t v, bool take, int lane) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t x = take ? v + 1u : 0u;
+    for (int d = 16; d; d >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)x, d); x = o > x ? o : x; }
+    if ((lane & 31) == 0 && x != 0u) atomicMax(p, x - 1u);
+#else
+    (void)lane;
+    if (take && v > *p) *p = v;
+#endif
+}
 
 // ---------------------------------------------------------------- keys and colour sets
 constexpr uint32_t GIF_KEY_COLOUR = 0x01000000u;          // | R << 16 | G << 8 | B
@@ -96,6 +118,12 @@ IMP_GIF_HD int gif_set_insert(uint32_t* slot, uint32_t key) {
     }
     return -1;
 }
+// a key into a workgroup's set, whose new keys `count` counts; true: the set is full, or holds more keys than a table --
+// the workgroup's pixels alone are too many colours, and it need not look at the rest
+IMP_GIF_HD bool gif_set_count(uint32_t* slot, uint32_t* count, uint32_t key) {
+    const int r = gif_set_insert(slot, key);
+    return r < 0 || (r > 0 && gif_add(count, 1u) + 1u > GIF_SET_MAX);
+}
 // a key into the frame's set; past GIF_SET_MAX keys the flag goes up and the set takes no more
 IMP_GIF_HD void gif_frame_set_add(GifColourSet* fs, uint32_t key) {
     if (*(volatile uint32_t*)&fs->overflow) return;
@@ -115,7 +143,7 @@ struct GifEncRec {
     uint32_t trans_index;    // the table's transparent index (nkeys - 1), or 0xFFFFFFFF when it has none
     uint32_t mcs;
     uint32_t stream_bytes;   // PACK: the LZW stream's length
-    uint32_t pad;
+    uint32_t quant;          // 1: the table is the quantiser's (k_gif_enc_cut), the indices come through its cell -> index table
 };
 // the rank of list[i] among `n` distinct keys
 IMP_GIF_HD uint32_t gif_rank(const uint32_t* list, uint32_t n, uint32_t i) {
@@ -149,8 +177,257 @@ IMP_GIF_HD uint32_t gif_table_find(const uint32_t* tab, uint32_t key) {
     return lo;
 }
 
+// ---------------------------------------------------------------- the quantiser (IMPGPU_GIF_ENC_QUANTIZE; include/impgpu.h has the definition)
+// A frame whose keys outgrow a table is cut to K = 256 - T colours: a median cut over the 32 x 32 x 32 cells of its 5:5:5
+// histogram, all in integers.
+//   HIST    4096 pixels a workgroup, 16 a lane: a lane sums a run of pixels of one cell in registers, the workgroup
+//           combines equal cells in a direct-mapped LDS table (gif_q_wg_add: a cell whose place another cell holds goes
+//           to device memory at once), and what the table holds leaves as one add per sum (gif_q_wg_flush_slot).
+//   CUT     one workgroup a frame.  The counts become a summed-volume table (gif_q_svt_line along B, G, R), so the pixels
+//           of any cell range are eight reads (gif_q_box_sum).  A cut is five steps with a barrier between them: every lane
+//           scores its box (gif_q_score_lane), the best scorers name the lowest of them (gif_q_pick_lane), lanes 0 .. s sum
+//           planes 0 .. lane across the longest axis and name the plane t (gif_q_marginal_lane), 192 lanes sum the planes
+//           of both halves on every axis and shrink them to their non-empty ones (gif_q_shrink_lane), lane 0 files the two
+//           boxes (gif_q_commit).  Then the boxes' cells are named (gif_q_map_lane), their sums added up
+//           (gif_q_sums_lane), the colours made and ranked (gif_q_colour_lane, gif_q_rank_lane) and every cell's index
+//           written (gif_q_cellmap_lane).
+// Every loop's bound is a constant: 255 cuts, 32 planes, 256 boxes, 32768 cells.
+constexpr int GIF_Q_CELLS = 32768;
+constexpr int GIF_Q_WG_SLOTS = 2048;
+constexpr uint32_t GIF_Q_NONE = 0xFFFFFFFFu;
+constexpr int GIF_Q_HIST_WORDS = 4 * GIF_Q_CELLS;          // planes n, sum R, sum G, sum B: 512 KB
+struct GifQuantWg { uint32_t cell[GIF_Q_WG_SLOTS]; uint32_t sum[4][GIF_Q_WG_SLOTS]; };     // 40 KB
+// A box's corners are packed r | g << 8 | b << 16 (axis 0, 1, 2).
+struct GifQuantCut {
+    uint32_t lo[256], hi[256], n[256];                     // the boxes
+    uint32_t key[256], rank[256];
+    uint32_t acc[3][256];                                  // a box's sums of R, G, B
+    uint32_t m[32];                                        // the picked box's pixels per plane of its longest axis
+    uint32_t nb, K, total, best, pick, tcut;               // boxes, their limit, the opaque pixels; a cut's best score, box and plane
+    uint32_t tlo[2][3], thi[2][3];                         // the tight bounds of the cut's two halves
+};
+
+IMP_GIF_HD uint32_t gif_q_cell(uint32_t key) { return ((key >> 19) & 31u) << 10 | ((key >> 11) & 31u) << 5 | ((key >> 3) & 31u); }
+IMP_GIF_HD uint32_t gif_q_get(uint32_t corner, int axis) { return (corner >> (8 * axis)) & 255u; }
+IMP_GIF_HD uint32_t gif_q_set(uint32_t corner, int axis, uint32_t v) { return (corner & ~(255u << (8 * axis))) | v << (8 * axis); }
+IMP_GIF_HD uint32_t gif_q_cell_of(uint32_t corner) { return gif_q_get(corner, 0) << 10 | gif_q_get(corner, 1) << 5 | gif_q_get(corner, 2); }
+
+IMP_GIF_HD void gif_q_hist_add(uint32_t* hist, uint32_t cell, uint32_t n, uint32_t r, uint32_t g, uint32_t b) {
+    gif_add(hist + cell, n);
+    gif_add(hist + GIF_Q_CELLS + cell, r);
+    gif_add(hist + 2 * GIF_Q_CELLS + cell, g);
+    gif_add(hist + 3 * GIF_Q_CELLS + cell, b);
+}
+IMP_GIF_HD void gif_q_wg_clear_lane(GifQuantWg* t, int lane) {
+    for (int i = lane; i < GIF_Q_WG_SLOTS; i += 256) { t->cell[i] = GIF_Q_NONE; t->sum[0][i] = 0; t->sum[1][i] = 0; t->sum[2][i] = 0; t->sum[3][i] = 0; }
+}
+// `n` pixels of one cell: into the workgroup's table where the cell's place is free or its own, else straight to `hist`
+IMP_GIF_HD void gif_q_wg_add(GifQuantWg* t, uint32_t* hist, uint32_t cell, uint32_t n, uint32_t r, uint32_t g, uint32_t b) {
+    const uint32_t h = (cell * 2654435761u) >> 21;
+    uint32_t old = *(volatile uint32_t*)&t->cell[h];
+    if (old == GIF_Q_NONE) old = gif_cas(&t->cell[h], GIF_Q_NONE, cell);
+    if (old == GIF_Q_NONE || old == cell) {
+        gif_add(&t->sum[0][h], n); gif_add(&t->sum[1][h], r); gif_add(&t->sum[2][h], g); gif_add(&t->sum[3][h], b);
+    } else {
+        gif_q_hist_add(hist, cell, n, r, g, b);
+    }
+}
+IMP_GIF_HD void gif_q_wg_flush_slot(const GifQuantWg* t, uint32_t* hist, int i) {
+    if (t->cell[i] != GIF_Q_NONE) gif_q_hist_add(hist, t->cell[i], t->sum[0][i], t->sum[1][i], t->sum[2][i], t->sum[3][i]);
+}
+// a lane's 16 pixels from stream position p0; true: one of them is transparent
+IMP_GIF_HD bool gif_q_lane_pixels(const GifEncFrame& fr, uint32_t p0, uint32_t total, GifQuantWg* t, uint32_t* hist) {
+    uint32_t cur = GIF_Q_NONE, n = 0, r = 0, g = 0, b = 0;
+    bool trans = false;
+    for (uint32_t j = 0; j < 16u; j++) {
+        if (p0 + j >= total) break;
+        const uint32_t key = gif_enc_key_at(fr, p0 + j);
+        if (key & GIF_KEY_TRANSPARENT) { trans = true; continue; }
+        const uint32_t cell = gif_q_cell(key);
+        if (cell != cur) {
+            if (n) gif_q_wg_add(t, hist, cur, n, r, g, b);
+            cur = cell; n = 0; r = 0; g = 0; b = 0;
+        }
+        n++; r += (key >> 16) & 255u; g += (key >> 8) & 255u; b += key & 255u;
+    }
+    if (n) gif_q_wg_add(t, hist, cur, n, r, g, b);
+    return trans;
+}
+
+// the summed-volume table S: S[r][g][b] = the pixels of the cells (<= r, <= g, <= b).  One of 1024 lines along `axis`.
+IMP_GIF_HD void gif_q_svt_line(uint32_t* S, int axis, int line) {
+    const int base = axis == 2 ? line << 5 : axis == 1 ? (line >> 5) << 10 | (line & 31) : line;
+    const int stride = axis == 2 ? 1 : axis == 1 ? 32 : 1024;
+    uint32_t run = 0;
+    for (int j = 0; j < 32; j++) { run += S[base + j * stride]; S[base + j * stride] = run; }
+}
+IMP_GIF_HD uint32_t gif_q_svt_at(const uint32_t* S, int r, int g, int b) { return (r | g | b) < 0 ? 0u : S[r << 10 | g << 5 | b]; }
+// the pixels of the cells lo .. hi (corners, inclusive)
+IMP_GIF_HD uint32_t gif_q_box_sum(const uint32_t* S, uint32_t lo, uint32_t hi) {
+    const int r0 = (int)gif_q_get(lo, 0) - 1, g0 = (int)gif_q_get(lo, 1) - 1, b0 = (int)gif_q_get(lo, 2) - 1;
+    const int r1 = (int)gif_q_get(hi, 0), g1 = (int)gif_q_get(hi, 1), b1 = (int)gif_q_get(hi, 2);
+    return gif_q_svt_at(S, r1, g1, b1) - gif_q_svt_at(S, r0, g1, b1) - gif_q_svt_at(S, r1, g0, b1) - gif_q_svt_at(S, r1, g1, b0)
+         + gif_q_svt_at(S, r0, g0, b1) + gif_q_svt_at(S, r0, g1, b0) + gif_q_svt_at(S, r1, g0, b0) - gif_q_svt_at(S, r0, g0, b0);
+}
+// the pixels of plane `p` (a coordinate) across `axis` of the box lo .. hi
+IMP_GIF_HD uint32_t gif_q_plane_sum(const uint32_t* S, uint32_t lo, uint32_t hi, int axis, uint32_t p) {
+    return gif_q_box_sum(S, gif_q_set(lo, axis, p), gif_q_set(hi, axis, p));
+}
+// a box's longest side and its axis (ties: R, then G, then B)
+IMP_GIF_HD uint32_t gif_q_side(uint32_t lo, uint32_t hi, int* axis) {
+    const uint32_t sr = gif_q_get(hi, 0) - gif_q_get(lo, 0), sg = gif_q_get(hi, 1) - gif_q_get(lo, 1), sb = gif_q_get(hi, 2) - gif_q_get(lo, 2);
+    *axis = sr >= sg && sr >= sb ? 0 : sg >= sb ? 1 : 2;
+    return *axis == 0 ? sr : *axis == 1 ? sg : sb;
+}
+IMP_GIF_HD uint32_t gif_q_score(const GifQuantCut* Q, uint32_t box) {      // n * s: below 2^24 * 32
+    int axis;
+    return Q->n[box] * gif_q_side(Q->lo[box], Q->hi[box], &axis);
+}
+// lane 0: the words a cut's steps meet in, as the next cut wants to find them
+IMP_GIF_HD void gif_q_reset(GifQuantCut* Q) {
+    Q->best = 0; Q->pick = GIF_Q_NONE; Q->tcut = GIF_Q_NONE;
+    for (int c = 0; c < 2; c++)
+        for (int a = 0; a < 3; a++) { Q->tlo[c][a] = 31u; Q->thi[c][a] = 0u; }
+}
+// lane 0: no box yet
+IMP_GIF_HD void gif_q_start(GifQuantCut* Q, const uint32_t* S, uint32_t K) {
+    Q->nb = 0; Q->K = K; Q->total = S[GIF_Q_CELLS - 1];
+    gif_q_reset(Q);
+}
+IMP_GIF_HD void gif_q_score_lane(GifQuantCut* Q, int lane) {
+    const bool take = (uint32_t)lane < Q->nb;
+    gif_group_max(&Q->best, take ? gif_q_score(Q, (uint32_t)lane) : 0u, take, lane);
+}
+IMP_GIF_HD void gif_q_pick_lane(GifQuantCut* Q, int lane) {
+    const bool take = (uint32_t)lane < Q->nb && Q->best != 0u && gif_q_score(Q, (uint32_t)lane) == Q->best;
+    gif_group_min(&Q->pick, (uint32_t)lane, take, lane);
+}
+// lanes 0 .. s: the picked box's pixels in planes 0 .. lane of its longest axis (one box sum); the lanes at which that
+// reaches ceil(n / 2) name the first of them
+IMP_GIF_HD void gif_q_marginal_lane(GifQuantCut* Q, const uint32_t* S, int lane) {
+    if (lane >= 32) return;
+    int axis;
+    const uint32_t box = Q->pick & 255u, lo = Q->lo[box], hi = Q->hi[box], n = Q->n[box], s = gif_q_side(lo, hi, &axis);
+    const uint32_t run = (uint32_t)lane <= s ? gif_q_box_sum(S, lo, gif_q_set(hi, axis, gif_q_get(lo, axis) + (uint32_t)lane)) : 0u;
+    Q->m[lane] = run;
+    gif_group_min(&Q->tcut, (uint32_t)lane, (uint32_t)lane <= s && run >= (n + 1u) / 2u, lane);
+}
+// the halves [0] and [1] of the cut before the shrink: planes 0 .. t and t + 1 .. s of the picked box, t = the plane the
+// marginal named, s - 1 at the most.  Before there is a box: the whole cube, and nothing (corners out of order: no plane
+// lies in it).  Every lane works this out for itself from the same words.
+struct GifQuantHalves { uint32_t lo[2], hi[2], n[2]; };
+IMP_GIF_HD GifQuantHalves gif_q_halves(const GifQuantCut* Q) {
+    GifQuantHalves H;
+    if (Q->nb == 0u) {
+        H.lo[0] = 0u; H.hi[0] = 31u | 31u << 8 | 31u << 16; H.n[0] = Q->total;
+        H.lo[1] = 1u | 1u << 8 | 1u << 16; H.hi[1] = 0u; H.n[1] = 0u;
+        return H;
+    }
+    int axis;
+    const uint32_t box = Q->pick & 255u, lo = Q->lo[box], hi = Q->hi[box], s = gif_q_side(lo, hi, &axis);
+    const uint32_t t = (Q->tcut < s ? Q->tcut : s - 1u) & 31u, a0 = gif_q_get(lo, axis);
+    H.lo[0] = lo; H.hi[0] = gif_q_set(hi, axis, a0 + t); H.n[0] = Q->m[t];
+    H.lo[1] = gif_q_set(lo, axis, a0 + t + 1u); H.hi[1] = hi; H.n[1] = Q->n[box] - Q->m[t];
+    return H;
+}
+// lanes 0 .. 191: plane (lane & 31) across axis (lane / 32 % 3) of half (lane / 96), where it lies in that half
+IMP_GIF_HD void gif_q_shrink_lane(GifQuantCut* Q, const uint32_t* S, int lane) {
+    if (lane >= 192) return;
+    const GifQuantHalves H = gif_q_halves(Q);
+    const int c = lane / 96, axis = (lane % 96) / 32;
+    const uint32_t p = (uint32_t)lane & 31u, lo = H.lo[c], hi = H.hi[c];
+    bool hit = p >= gif_q_get(lo, axis) && p <= gif_q_get(hi, axis);
+    for (int a = 0; a < 3; a++) hit = hit && gif_q_get(lo, a) <= gif_q_get(hi, a) && gif_q_get(hi, a) <= 31u;
+    hit = hit && gif_q_plane_sum(S, lo, hi, axis, p) != 0u;
+    gif_group_min(&Q->tlo[c][axis], p, hit, lane);
+    gif_group_max(&Q->thi[c][axis], p, hit, lane);
+}
+IMP_GIF_HD void gif_q_file(GifQuantCut* Q, uint32_t box, int c, uint32_t n) {
+    Q->lo[box] = Q->tlo[c][0] | Q->tlo[c][1] << 8 | Q->tlo[c][2] << 16;
+    Q->hi[box] = Q->thi[c][0] | Q->thi[c][1] << 8 | Q->thi[c][2] << 16;
+    Q->n[box] = n;
+}
+// lane 0, behind the first shrink: the first box (none when the frame has no opaque pixel)
+IMP_GIF_HD void gif_q_commit_first(GifQuantCut* Q) {
+    if (Q->total != 0u) {
+        gif_q_file(Q, 0u, 0, Q->total);
+        Q->nb = 1u;
+    }
+    gif_q_reset(Q);
+}
+// lane 0, behind a cut's shrink: planes 0 .. t keep the box's number, the rest is the next box
+IMP_GIF_HD void gif_q_commit(GifQuantCut* Q) {
+    const GifQuantHalves H = gif_q_halves(Q);
+    gif_q_file(Q, Q->pick & 255u, 0, H.n[0]);
+    gif_q_file(Q, Q->nb & 255u, 1, H.n[1]);
+    Q->nb++;
+    gif_q_reset(Q);
+}
+// every cell of every box gets the box's number (`map`: 32768 bytes)
+IMP_GIF_HD void gif_q_map_lane(GifQuantCut* Q, uint8_t* map, int lane) {
+    for (int a = 0; a < 3; a++) Q->acc[a][lane] = 0u;
+    for (uint32_t box = 0; box < 256u && box < Q->nb; box++) {
+        const uint32_t lo = Q->lo[box], hi = Q->hi[box];
+        const uint32_t dg = gif_q_get(hi, 1) - gif_q_get(lo, 1) + 1u, db = gif_q_get(hi, 2) - gif_q_get(lo, 2) + 1u;
+        const uint32_t vol = (gif_q_get(hi, 0) - gif_q_get(lo, 0) + 1u) * dg * db;
+        for (uint32_t i = (uint32_t)lane; i < vol && i < (uint32_t)GIF_Q_CELLS; i += 256u) {
+            const uint32_t r = i / (dg * db), g = i / db % dg, b = i % db;
+            map[(gif_q_cell_of(lo) + (r << 10 | g << 5 | b)) & (uint32_t)(GIF_Q_CELLS - 1)] = (uint8_t)box;
+        }
+    }
+}
+IMP_GIF_HD void gif_q_sums_lane(GifQuantCut* Q, const uint8_t* map, const uint32_t* hist, int lane) {
+    for (int cell = lane; cell < GIF_Q_CELLS; cell += 256) {
+        if (hist[cell] == 0u) continue;
+        const uint32_t box = map[cell];
+        gif_add(&Q->acc[0][box], hist[GIF_Q_CELLS + cell]);
+        gif_add(&Q->acc[1][box], hist[2 * GIF_Q_CELLS + cell]);
+        gif_add(&Q->acc[2][box], hist[3 * GIF_Q_CELLS + cell]);
+    }
+}
+// (2 * sum + n) / (2 * n) without the overflow: the quotient, and one more when twice the remainder reaches n
+IMP_GIF_HD uint32_t gif_q_mean(uint32_t sum, uint32_t n) {
+    if (n == 0u) return 0u;
+    const uint32_t q = sum / n, rem = sum - q * n;
+    return q + (rem >= n - rem ? 1u : 0u);
+}
+IMP_GIF_HD void gif_q_colour_lane(GifQuantCut* Q, int lane) {
+    if ((uint32_t)lane >= Q->nb) return;
+    const uint32_t n = Q->n[lane];
+    Q->key[lane] = GIF_KEY_COLOUR | (gif_q_mean(Q->acc[0][lane], n) & 255u) << 16 | (gif_q_mean(Q->acc[1][lane], n) & 255u) << 8 | (gif_q_mean(Q->acc[2][lane], n) & 255u);
+}
+// the table: the boxes' colours ascending, then the transparent key when T
+IMP_GIF_HD void gif_q_rank_lane(GifQuantCut* Q, uint32_t* tab, uint32_t T, int lane) {
+    if ((uint32_t)lane < Q->nb) {
+        const uint32_t rk = gif_rank(Q->key, Q->nb, (uint32_t)lane);
+        Q->rank[lane] = rk;
+        tab[rk] = Q->key[lane];
+    }
+    if (lane == 0 && T && Q->nb < GIF_SET_MAX) tab[Q->nb] = GIF_KEY_TRANSPARENT;
+}
+// the cell -> index table: 4 cells a lane at a time
+IMP_GIF_HD void gif_q_cellmap_lane(const GifQuantCut* Q, const uint8_t* map, uint8_t* out, int lane) {
+    for (int i = lane * 4; i < GIF_Q_CELLS; i += 1024) {
+        uint32_t v = 0;
+        for (int q = 0; q < 4; q++) {
+            const uint32_t box = map[i + q];                           // (a cell outside every box holds no pixel: any index will do)
+            v |= (box < Q->nb ? Q->rank[box] & 255u : 0u) << (8 * q);
+        }
+        *(uint32_t*)(out + i) = v;
+    }
+}
+IMP_GIF_HD void gif_q_rec(const GifQuantCut* Q, uint32_t T, GifEncRec* rec) {
+    rec->nkeys = Q->nb + T;
+    rec->has_trans = T;
+    rec->quant = 1u;
+}
+// a pixel's index in a quantised frame
+IMP_GIF_HD uint32_t gif_q_index(const uint8_t* cmap, uint32_t nkeys, uint32_t key) {
+    return (key & GIF_KEY_TRANSPARENT) ? nkeys - 1u : cmap[gif_q_cell(key)];
+}
+
 // ---------------------------------------------------------------- a segment's LZW
-constexpr int GIF_ENC_SLOTS = 8192;                        // at most 3838 entries between two clears: under half full
+constexpr int GIF_ENC_SLOTS = 8192;                       // at most 3838 entries between two clears: under half full
 constexpr uint32_t GIF_ENC_EMPTY = 0xFFFFFFFFu;            // (no entry looks like it: code 4095 never has prefix 4095)
 constexpr int GIF_ENC_CHUNK = 1024;                        // indices staged per load: 16 bytes a lane
 constexpr int GIF_ENC_BATCH = 64;                          // a batch is due at this many codes ...
@@ -326,7 +603,18 @@ struct GifEncDev {
     uint32_t* tabs;                                        // 256 keys per frame
     GifEncRec* recs;
     uint32_t* segbits;                                     // a segment's bit length
+    // the quantiser (flags & IMPGPU_GIF_ENC_QUANTIZE; null and 0 otherwise): a pool of `nslots` slots -- a histogram
+    // (GIF_Q_HIST_WORDS), a cell -> index table (GIF_Q_CELLS bytes) and the words "has a transparent pixel" and "frame + 1"
+    // each -- which k_gif_enc_claim hands to the frames that overflowed, a whole album or none of it
+    int flags, nslots;
+    int* slot_of;                                          // per frame: its slot, or -1
+    uint32_t* slot_frame;                                  // per slot: frame + 1, or 0
+    uint32_t* slot_trans;
+    uint32_t* hist;
+    uint8_t* cmaps;
+    uint32_t* album_need;                                  // per album: 0, or the slots it needed and did not get (it is deferred)
 };
+constexpr size_t GIF_Q_SLOT_BYTES = (size_t)GIF_Q_HIST_WORDS * 4 + GIF_Q_CELLS + 8;
 
 // ---------------------------------------------------------------- limits, bounds, the container (host)
 constexpr int GIF_ENC_MAX_SIDE = 4096, GIF_ENC_MAX_FRAMES = 4096;
@@ -411,10 +699,49 @@ inline void gif_enc_write_file(uint8_t* p, const GifEncPage* pages, int count, i
 }
 
 // ---------------------------------------------------------------- the host encoder: the launches, one lane after the other
-// SETS + TABLES for one album; false: refused
-inline bool host_tables(const unsigned char* const* frames, int count, int w, int h, int c, int step, std::vector<GifEncRec>* recs,
-                 std::vector<uint32_t>* tabs) {
+// HIST + CUT for one frame: its table (256 words), the record's nkeys / has_trans / quant, its cell -> index table
+inline void host_quantize(const GifEncFrame& fr, uint32_t total, GifEncRec* rec, uint32_t* tab, uint8_t* cmap) {
+    std::vector<uint32_t> hist((size_t)GIF_Q_HIST_WORDS, 0u), S((size_t)GIF_Q_CELLS);
+    std::vector<GifQuantWg> wg(1);
+    std::vector<GifQuantCut> cut(1);
+    GifQuantCut* Q = cut.data();
+    uint32_t T = 0;
+    for (uint32_t b0 = 0; b0 < total; b0 += GIF_ENC_PX_BLOCK) {                      // a workgroup of k_gif_enc_hist
+        for (int lane = 0; lane < 256; lane++) gif_q_wg_clear_lane(wg.data(), lane);
+        for (uint32_t tid = 0; tid < 256u; tid++)
+            if (gif_q_lane_pixels(fr, b0 + tid * 16u, total, wg.data(), hist.data())) T = 1u;
+        for (int i = 0; i < GIF_Q_WG_SLOTS; i++) gif_q_wg_flush_slot(wg.data(), hist.data(), i);
+    }
+    std::copy(hist.begin(), hist.begin() + GIF_Q_CELLS, S.begin());                  // k_gif_enc_cut
+    for (int axis = 2; axis >= 0; axis--)
+        for (int line = 0; line < 1024; line++) gif_q_svt_line(S.data(), axis, line);
+    gif_q_start(Q, S.data(), GIF_SET_MAX - T);
+    for (int lane = 0; lane < 256; lane++) gif_q_shrink_lane(Q, S.data(), lane);
+    gif_q_commit_first(Q);
+    for (int k = 0; k < 255 && Q->nb != 0u && Q->nb < Q->K; k++) {
+        for (int lane = 0; lane < 256; lane++) gif_q_score_lane(Q, lane);
+        for (int lane = 0; lane < 256; lane++) gif_q_pick_lane(Q, lane);
+        if (Q->best == 0u) break;
+        for (int lane = 0; lane < 256; lane++) gif_q_marginal_lane(Q, S.data(), lane);
+        for (int lane = 0; lane < 256; lane++) gif_q_shrink_lane(Q, S.data(), lane);
+        gif_q_commit(Q);
+    }
+    uint8_t* map = (uint8_t*)S.data();                                               // (the table has done its work)
+    for (int lane = 0; lane < 256; lane++) gif_q_map_lane(Q, map, lane);
+    for (int lane = 0; lane < 256; lane++) gif_q_sums_lane(Q, map, hist.data(), lane);
+    for (int lane = 0; lane < 256; lane++) gif_q_colour_lane(Q, lane);
+    for (int lane = 0; lane < 256; lane++) gif_q_rank_lane(Q, tab, T, lane);
+    for (int lane = 0; lane < 256; lane++) gif_q_cellmap_lane(Q, map, cmap, lane);
+    gif_q_rec(Q, T, rec);
+}
+
+inline int gif_frame_wide(const unsigned char* frame, int c, int step) { return (c == 4 && (((uintptr_t)frame | (uintptr_t)step) & 3) == 0) ? 1 : 0; }
+
+// SETS + TABLES (+ HIST + CUT under IMPGPU_GIF_ENC_QUANTIZE) for one album; false: refused.  cmaps: GIF_Q_CELLS bytes a frame
+inline bool host_tables(const unsigned char* const* frames, int count, int w, int h, int c, int step, int flags, std::vector<GifEncRec>* recs,
+                 std::vector<uint32_t>* tabs, std::vector<uint8_t>* cmaps) {
     const uint32_t total = (uint32_t)w * (uint32_t)h;
+    bool quant = false;
     std::vector<GifColourSet> sets((size_t)count);
     std::vector<uint32_t> lset(GIF_SET_SLOTS);
     for (int f = 0; f < count; f++) {
@@ -424,31 +751,39 @@ inline bool host_tables(const unsigned char* const* frames, int count, int w, in
             if (sets[(size_t)f].overflow) break;
             std::fill(lset.begin(), lset.end(), 0u);
             bool full = false;
+            uint32_t lcount = 0;
             for (uint32_t tid = 0; tid < 256u; tid++) {
                 uint32_t last = 0;
                 for (uint32_t j = 0; j < 16u; j++) {
                     const uint32_t pos = b0 + tid * 16u + j;
-                    if (pos >= total) break;
+                    if (pos >= total || full) break;
                     const uint32_t key = gif_enc_key_at(fr, pos);
                     if (key == last) continue;
                     last = key;
-                    if (gif_set_insert(lset.data(), key) < 0) full = true;
+                    if (gif_set_count(lset.data(), &lcount, key)) full = true;
                 }
             }
             if (full) { sets[(size_t)f].overflow = 1u; break; }
             for (int i = 0; i < GIF_SET_SLOTS; i++)
                 if (lset[(size_t)i]) gif_frame_set_add(&sets[(size_t)f], lset[(size_t)i]);
         }
-        if (sets[(size_t)f].overflow) return false;
+        if (sets[(size_t)f].overflow && !(flags & IMPGPU_GIF_ENC_QUANTIZE)) return false;
+        quant = quant || sets[(size_t)f].overflow != 0u;
     }
     recs->assign((size_t)count, GifEncRec{});
     tabs->assign((size_t)count * 256, 0u);
+    if (quant) cmaps->assign((size_t)count * GIF_Q_CELLS, 0);
     std::vector<uint32_t> list, uset(GIF_SET_SLOTS, 0u);
     uint32_t ucount = 0;
     auto sort_out = [&](uint32_t* tab) {
         for (uint32_t i = 0; i < (uint32_t)list.size(); i++) tab[gif_rank(list.data(), (uint32_t)list.size(), i)] = list[i];
     };
     for (int f = 0; f < count; f++) {                                                // k_gif_enc_tables
+        if (sets[(size_t)f].overflow) {
+            const GifEncFrame fr{frames[f], w, h, c, step, gif_frame_wide(frames[f], c, step)};
+            host_quantize(fr, total, &(*recs)[(size_t)f], tabs->data() + (size_t)f * 256, cmaps->data() + (size_t)f * GIF_Q_CELLS);
+            continue;
+        }
         list.clear();
         for (int i = 0; i < GIF_SET_SLOTS; i++)
             if (sets[(size_t)f].slot[i]) list.push_back(sets[(size_t)f].slot[i]);
@@ -462,7 +797,7 @@ inline bool host_tables(const unsigned char* const* frames, int count, int w, in
         }
         (*recs)[(size_t)f].nkeys = (uint32_t)list.size();
     }
-    if (ucount <= GIF_SET_MAX) {
+    if (!quant && ucount <= GIF_SET_MAX) {
         list.clear();
         bool gtrans = false;
         for (uint32_t k : uset)
@@ -490,13 +825,14 @@ inline void host_flush(GifEncMem* m, GifEncState* e, int mcs, uint32_t* words, u
 
 // INDEX + LZW + PACK for one frame: its framed stream; rec->stream_bytes
 inline void host_frame(const unsigned char* frame, int w, int h, int c, int step, uint32_t segment, GifEncRec* rec, const uint32_t* table,
-                GifEncMem* m, std::vector<uint8_t>* framed) {
+                const uint8_t* cmap, GifEncMem* m, std::vector<uint8_t>* framed) {
     const uint32_t total = (uint32_t)w * (uint32_t)h;
     const GifEncFrame fr{frame, w, h, c, step, (c == 4 && (((uintptr_t)frame | (uintptr_t)step) & 3) == 0) ? 1 : 0};
     uint32_t tab[256];
     for (uint32_t i = 0; i < 256u; i++) tab[i] = i < rec->nkeys ? table[i] : 0xFFFFFFFFu;
     std::vector<uint8_t> plane(total);
-    for (uint32_t pos = 0; pos < total; pos++) plane[pos] = (uint8_t)gif_table_find(tab, gif_enc_key_at(fr, pos));
+    for (uint32_t pos = 0; pos < total; pos++)
+        plane[pos] = (uint8_t)(rec->quant ? gif_q_index(cmap, rec->nkeys, gif_enc_key_at(fr, pos)) : gif_table_find(tab, gif_enc_key_at(fr, pos)));
     const int mcs = (int)rec->mcs;
     const uint32_t nseg = gif_enc_segments(total, segment), cap = gif_enc_slot_words(segment < total ? segment : total);
     std::vector<uint32_t> scratch((size_t)nseg * cap, 0u), segbits(nseg);
@@ -531,10 +867,11 @@ inline void host_frame(const unsigned char* frame, int w, int h, int c, int step
     }
 }
 
-// impgpu_gif_encode_host
-inline int gif_encode_host(const unsigned char* const* frames, int count, int width, int height, int channels, int step, const int* time_ms,
-                           const int* dispose, int loop_count, int segment, unsigned char* out, size_t capacity, size_t* length) {
+// impgpu_gif_encode_host_ex
+inline int gif_encode_host_ex(const unsigned char* const* frames, int count, int width, int height, int channels, int step, const int* time_ms,
+                              const int* dispose, int loop_count, int segment, int flags, unsigned char* out, size_t capacity, size_t* length) {
     if (length) *length = 0;
+    if (flags & ~IMPGPU_GIF_ENC_QUANTIZE) return IMP_ERROR_INVALID_ARGS;
     if (!frames || !length || count <= 0) return IMP_ERROR_INVALID_ARGS;
     if (int rc = gif_enc_check_args(count <= GIF_ENC_MAX_FRAMES ? count : 0, dispose, loop_count, segment)) return rc;
     if (int rc = gif_enc_check_geometry(width, height, channels, count)) return rc;
@@ -544,12 +881,13 @@ inline int gif_encode_host(const unsigned char* const* frames, int count, int wi
     const uint32_t seg = segment ? (uint32_t)segment : (uint32_t)IMPGPU_GIF_ENC_SEGMENT;
     std::vector<GifEncRec> recs;
     std::vector<uint32_t> tabs;
-    if (!host_tables(frames, count, width, height, channels, step, &recs, &tabs)) return IMP_ERROR_UNSUPPORTED;
+    std::vector<uint8_t> cmaps;
+    if (!host_tables(frames, count, width, height, channels, step, flags, &recs, &tabs, &cmaps)) return IMP_ERROR_UNSUPPORTED;
     std::vector<std::vector<uint8_t>> framed((size_t)count);
     std::vector<GifEncMem> mem(1);
     for (int f = 0; f < count; f++)
         host_frame(frames[f], width, height, channels, step, seg, &recs[(size_t)f], tabs.data() + (size_t)recs[(size_t)f].table_frame * 256,
-                   mem.data(), &framed[(size_t)f]);
+                   recs[(size_t)f].quant ? cmaps.data() + (size_t)f * GIF_Q_CELLS : nullptr, mem.data(), &framed[(size_t)f]);
     std::vector<GifEncPage> pages;
     for (int f = 0; f < count; f++)
         pages.push_back(GifEncPage{&recs[(size_t)f], tabs.data() + (size_t)recs[(size_t)f].table_frame * 256, framed[(size_t)f].data()});
@@ -557,6 +895,33 @@ inline int gif_encode_host(const unsigned char* const* frames, int count, int wi
     *length = need;
     if (!out || capacity < need) return IMP_ERROR_MALLOC_FAILED;
     gif_enc_write_file(out, pages.data(), count, width, height, time_ms, dispose, loop_count);
+    return IMP_OK;
+}
+// impgpu_gif_encode_host
+inline int gif_encode_host(const unsigned char* const* frames, int count, int width, int height, int channels, int step, const int* time_ms,
+                           const int* dispose, int loop_count, int segment, unsigned char* out, size_t capacity, size_t* length) {
+    return gif_encode_host_ex(frames, count, width, height, channels, step, time_ms, dispose, loop_count, segment, 0, out, capacity, length);
+}
+
+// impgpu_gif_quantize_host: steps 1-5 on one frame, whatever its colour count
+inline int gif_quantize_host(const unsigned char* frame, int width, int height, int channels, int step, unsigned char* table, int* entries,
+                             int* transparent_index, unsigned char* indices) {
+    if (!frame || !table || !entries || !transparent_index || !indices) return IMP_ERROR_INVALID_ARGS;
+    if (int rc = gif_enc_check_geometry(width, height, channels, 1)) return rc;
+    if ((long long)step < (long long)width * channels) return IMP_ERROR_INVALID_ARGS;
+    const GifEncFrame fr{frame, width, height, channels, step, gif_frame_wide(frame, channels, step)};
+    const uint32_t total = (uint32_t)width * (uint32_t)height;
+    GifEncRec rec{};
+    std::vector<uint32_t> tab(256, 0u);
+    std::vector<uint8_t> cmap((size_t)GIF_Q_CELLS);
+    host_quantize(fr, total, &rec, tab.data(), cmap.data());
+    for (uint32_t k = 0; k < rec.nkeys; k++) {
+        const uint32_t key = (tab[k] & GIF_KEY_TRANSPARENT) ? 0u : tab[k];
+        table[3 * k] = (uint8_t)(key >> 16); table[3 * k + 1] = (uint8_t)(key >> 8); table[3 * k + 2] = (uint8_t)key;
+    }
+    *entries = (int)rec.nkeys;
+    *transparent_index = rec.has_trans ? (int)rec.nkeys - 1 : -1;
+    for (uint32_t pos = 0; pos < total; pos++) indices[pos] = (uint8_t)gif_q_index(cmap.data(), rec.nkeys, gif_enc_key_at(fr, pos));
     return IMP_OK;
 }
 

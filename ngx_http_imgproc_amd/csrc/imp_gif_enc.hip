@@ -3,6 +3,8 @@
 // (impgpu_gif_encode_host) runs too.  Each launch reads what the one before wrote across the kernel boundary of one
 // stream; no wavefront waits for another workgroup.  Workgroup b of a launch finds its work in an item table
 // (GifEncItem: a frame of the call and the part of it), so the launches do not depend on how many albums there are.
+// Under IMPGPU_GIF_ENC_QUANTIZE three launches more run between the sets and the tables -- k_gif_enc_claim, _hist and _cut:
+// the frames past 256 colours get a median-cut table -- and k_gif_enc_index reads such a frame's cell -> index table.
 #include "imp_internal.h"
 #include "imp_gif_enc.h"
 
@@ -14,24 +16,24 @@ __device__ __forceinline__ GifEncFrame gif_enc_frame_of(const GifEncFrameDesc& f
 // holds 1024 keys: a workgroup that fills it has seen four times what any table takes, and says so in the frame's flag.
 __global__ __launch_bounds__(256) void k_gif_enc_sets(GifEncDev D) {
     __shared__ uint32_t lset[GIF_SET_SLOTS];
-    __shared__ uint32_t flag[2];
+    __shared__ uint32_t flag[3];
     const GifEncItem it = D.px_items[blockIdx.x];
     const GifEncFrameDesc& f = D.frames[it.frame];
     GifColourSet* fs = &D.sets[it.frame];
     const int tid = (int)threadIdx.x;
     for (int i = tid; i < GIF_SET_SLOTS; i += 256) lset[i] = 0;
-    if (tid == 0) { flag[0] = *(volatile uint32_t*)&fs->overflow; flag[1] = 0; }
+    if (tid == 0) { flag[0] = *(volatile uint32_t*)&fs->overflow; flag[1] = 0; flag[2] = 0; }
     __syncthreads();
     if (flag[0]) return;                                               // the frame is lost already
     const GifEncFrame fr = gif_enc_frame_of(f);
     const uint32_t p0 = (uint32_t)it.k * GIF_ENC_PX_BLOCK + (uint32_t)tid * 16u;
     uint32_t last = 0;
     for (uint32_t j = 0; j < 16u; j++) {
-        if (p0 + j >= f.total) break;
+        if (p0 + j >= f.total || *(volatile uint32_t*)&flag[1]) break;
         const uint32_t key = gif_enc_key_at(fr, p0 + j);
         if (key == last) continue;
         last = key;
-        if (gif_set_insert(lset, key) < 0) flag[1] = 1;
+        if (gif_set_count(lset, &flag[2], key)) flag[1] = 1;           // (a photo stops here, long before its keys crowd the set)
     }
     __syncthreads();
     if (flag[1]) {
@@ -58,11 +60,16 @@ __global__ __launch_bounds__(256) void k_gif_enc_tables(GifEncDev D) {
     for (int i = tid; i < GIF_SET_SLOTS; i += 256) uset[i] = 0;
     if (tid == 0) { n = 0; ucount = 0; gtrans = 0; }
     __syncthreads();
-    for (int q = 0; q < a.count; q++)                                  // (the sets are final: every lane reads the same)
-        if (D.sets[a.first + q].overflow) return;                      // a frame fits no table: every record stays REFUSED
+    bool quant = false;
+    for (int q = 0; q < a.count; q++) {                                // (the sets are final: every lane reads the same)
+        if (!D.sets[a.first + q].overflow) continue;
+        if (!D.slot_of || D.slot_of[a.first + q] < 0) return;          // a frame fits no table, or got no slot: every record stays REFUSED
+        quant = true;                                                  // k_gif_enc_cut has made its table: local tables
+    }
     for (int q = 0; q < a.count; q++) {
         const int f = a.first + q;
         const GifColourSet* fs = &D.sets[f];
+        if (fs->overflow) continue;
         const bool ufull = ucount > GIF_SET_MAX;
         for (int i = tid; i < GIF_SET_SLOTS; i += 256) {
             const uint32_t k = fs->slot[i];
@@ -85,7 +92,7 @@ __global__ __launch_bounds__(256) void k_gif_enc_tables(GifEncDev D) {
         if (tid == 0) n = 0;
         __syncthreads();
     }
-    if (ucount <= GIF_SET_MAX) {                                       // one global table: the union, sorted, in the first frame's slot
+    if (!quant && ucount <= GIF_SET_MAX) {                             // one global table: the union, sorted, in the first frame's slot
         for (int i = tid; i < GIF_SET_SLOTS; i += 256) {
             const uint32_t k = uset[i];
             if (!k) continue;
@@ -105,15 +112,127 @@ __global__ __launch_bounds__(256) void k_gif_enc_tables(GifEncDev D) {
     }
 }
 
-// INDEX: the frame's table in LDS, four pixels a lane at a time, a dword of indices out
+// CLAIM (under IMPGPU_GIF_ENC_QUANTIZE): one workgroup walks the albums in their order and hands the pool's slots to the
+// frames that overflowed -- to all of an album's or to none, so an album is either finished by this group or deferred
+// whole (album_need says how many slots it wants).  Every frame's slot_of is written.
+__global__ __launch_bounds__(256) void k_gif_enc_claim(GifEncDev D, int nalbums) {
+    __shared__ uint32_t need, taken;
+    const int tid = (int)threadIdx.x;
+    if (tid == 0) taken = 0;
+    uint32_t next = 0;                                                 // (= taken at every album's start; the same in all lanes)
+    for (int ai = 0; ai < nalbums; ai++) {
+        const GifEncAlbumDesc a = D.albums[ai];
+        if (tid == 0) need = 0;
+        __syncthreads();
+        for (int q = tid; q < a.count; q += 256)
+            if (D.sets[a.first + q].overflow) atomicAdd(&need, 1u);
+        __syncthreads();
+        const uint32_t nd = need;
+        const bool fits = nd <= (uint32_t)D.nslots - next;
+        if (tid == 0) D.album_need[ai] = fits ? 0u : nd;
+        for (int q = tid; q < a.count; q += 256) {
+            const int f = a.first + q;
+            int slot = -1;
+            if (fits && D.sets[f].overflow) {
+                const uint32_t s = atomicAdd(&taken, 1u);
+                if (s < (uint32_t)D.nslots) { slot = (int)s; D.slot_frame[s] = (uint32_t)f + 1u; }
+            }
+            D.slot_of[f] = slot;
+        }
+        if (fits) next += nd;
+        __syncthreads();
+    }
+}
+
+// HIST: SETS' items again, for the frames that hold a slot.  A lane sums a run of pixels of one cell in registers, the
+// workgroup combines equal cells in its LDS table, and a cell's four sums leave for device memory once a workgroup (a
+// cell that finds its place in the table taken goes there at once: that is the frame of many colours, whose adds spread).
+__global__ __launch_bounds__(256) void k_gif_enc_hist(GifEncDev D) {
+    __shared__ GifQuantWg wg;
+    const GifEncItem it = D.px_items[blockIdx.x];
+    const int slot = D.slot_of[it.frame];
+    if (slot < 0) return;
+    const GifEncFrameDesc& f = D.frames[it.frame];
+    const int tid = (int)threadIdx.x;
+    uint32_t* hist = D.hist + (size_t)slot * GIF_Q_HIST_WORDS;
+    gif_q_wg_clear_lane(&wg, tid);
+    __syncthreads();
+    const GifEncFrame fr = gif_enc_frame_of(f);
+    if (gif_q_lane_pixels(fr, (uint32_t)it.k * GIF_ENC_PX_BLOCK + (uint32_t)tid * 16u, f.total, &wg, hist)) *(volatile uint32_t*)&D.slot_trans[slot] = 1u;
+    __syncthreads();
+    for (int i = tid; i < GIF_Q_WG_SLOTS; i += 256) gif_q_wg_flush_slot(&wg, hist, i);
+}
+
+// CUT: a workgroup per slot.  The counts go into LDS and become the summed-volume table; up to 255 cuts of five steps
+// each; then the table, the record and the cell -> index table.  The box numbers of the cells overlay the summed-volume
+// table once the cuts are done.
+__global__ __launch_bounds__(256) void k_gif_enc_cut(GifEncDev D) {
+    __shared__ alignas(16) uint32_t S[GIF_Q_CELLS];                                // 128 KB of the CU's 160
+    __shared__ GifQuantCut Q;
+    const int slot = (int)blockIdx.x;
+    if (D.slot_frame[slot] == 0u) return;
+    const int frame = (int)(D.slot_frame[slot] - 1u);
+    const int tid = (int)threadIdx.x;
+    const uint32_t* hist = D.hist + (size_t)slot * GIF_Q_HIST_WORDS;
+    const uint32_t T = D.slot_trans[slot] ? 1u : 0u;
+    for (int i = tid * 4; i < GIF_Q_CELLS; i += 1024) *(uint4*)&S[i] = *(const uint4*)&hist[i];
+    __syncthreads();
+    for (int axis = 2; axis >= 0; axis--) {
+        for (int line = tid; line < 1024; line += 256) gif_q_svt_line(S, axis, line);
+        __syncthreads();
+    }
+    if (tid == 0) gif_q_start(&Q, S, GIF_SET_MAX - T);
+    __syncthreads();
+    gif_q_shrink_lane(&Q, S, tid);
+    __syncthreads();
+    if (tid == 0) gif_q_commit_first(&Q);
+    __syncthreads();
+#pragma unroll 1
+    for (int k = 0; k < 255; k++) {
+        if (Q.nb == 0u || Q.nb >= Q.K) break;                          // (LDS words behind a barrier: the same in every lane)
+        gif_q_score_lane(&Q, tid);
+        __syncthreads();
+        gif_q_pick_lane(&Q, tid);
+        __syncthreads();
+        if (Q.best == 0u) break;
+        gif_q_marginal_lane(&Q, S, tid);
+        __syncthreads();
+        gif_q_shrink_lane(&Q, S, tid);
+        __syncthreads();
+        if (tid == 0) gif_q_commit(&Q);
+        __syncthreads();
+    }
+    uint8_t* map = (uint8_t*)S;
+    gif_q_map_lane(&Q, map, tid);
+    __syncthreads();
+    gif_q_sums_lane(&Q, map, hist, tid);
+    __syncthreads();
+    gif_q_colour_lane(&Q, tid);
+    __syncthreads();
+    gif_q_rank_lane(&Q, D.tabs + (size_t)frame * 256, T, tid);
+    __syncthreads();
+    gif_q_cellmap_lane(&Q, map, D.cmaps + (size_t)slot * GIF_Q_CELLS, tid);
+    if (tid == 0) gif_q_rec(&Q, T, &D.recs[frame]);
+}
+
+// INDEX: the frame's table in LDS, four pixels a lane at a time, a dword of indices out.  QUANT: the launch under
+// IMPGPU_GIF_ENC_QUANTIZE, in which a quantised frame's workgroup stages the frame's cell -> index table instead.
+template <bool QUANT>
 __global__ __launch_bounds__(256) void k_gif_enc_index(GifEncDev D) {
     __shared__ uint32_t tab[256];
+    __shared__ alignas(16) uint32_t cmap[QUANT ? GIF_Q_CELLS / 4 : 4];
     const GifEncItem it = D.px_items[blockIdx.x];
     const GifEncFrameDesc& f = D.frames[it.frame];
     const GifEncRec& rec = D.recs[it.frame];
     if (rec.mode == GIF_ENC_REFUSED) return;
     const int tid = (int)threadIdx.x;
-    tab[tid] = (uint32_t)tid < rec.nkeys ? D.tabs[(size_t)rec.table_frame * 256 + tid] : 0xFFFFFFFFu;
+    const bool quant = QUANT && rec.quant != 0u;
+    if (QUANT && quant) {
+        const uint32_t* src = (const uint32_t*)(D.cmaps + (size_t)D.slot_of[it.frame] * GIF_Q_CELLS);
+        for (int i = tid * 4; i < GIF_Q_CELLS / 4; i += 1024) *(uint4*)&cmap[i] = *(const uint4*)&src[i];
+    } else {
+        tab[tid] = (uint32_t)tid < rec.nkeys ? D.tabs[(size_t)rec.table_frame * 256 + tid] : 0xFFFFFFFFu;
+    }
     __syncthreads();
     const GifEncFrame fr = gif_enc_frame_of(f);
     uint8_t* plane = D.mem + f.plane_off;
@@ -123,7 +242,10 @@ __global__ __launch_bounds__(256) void k_gif_enc_index(GifEncDev D) {
         if (pos >= f.total) break;
         const uint32_t cnt = f.total - pos < 4u ? f.total - pos : 4u;
         uint32_t v = 0;
-        for (uint32_t q = 0; q < cnt; q++) v |= gif_table_find(tab, gif_enc_key_at(fr, pos + q)) << (8u * q);
+        for (uint32_t q = 0; q < cnt; q++) {
+            const uint32_t key = gif_enc_key_at(fr, pos + q);
+            v |= (QUANT && quant ? gif_q_index((const uint8_t*)cmap, rec.nkeys, key) : gif_table_find(tab, key)) << (8u * q);
+        }
         if (cnt == 4u) *(uint32_t*)(plane + pos) = v;
         else for (uint32_t q = 0; q < cnt; q++) plane[pos + q] = (uint8_t)(v >> (8u * q));
     }
@@ -242,11 +364,22 @@ __global__ __launch_bounds__(256) void k_gif_enc_pack(GifEncDev D) {
 int launch_gif_encode(const GifEncDev& D, long long npx, long long nseg, long long npack, int nalbums, hipStream_t s) {
     if (!D.mem || npx <= 0 || nseg <= 0 || npack <= 0 || nalbums <= 0 || npx > 0x7fffffffLL || nseg > 0x7fffffffLL || npack > 0x7fffffffLL)
         return IMP_ERROR_INVALID_ARGS;
+    const bool quant = (D.flags & IMPGPU_GIF_ENC_QUANTIZE) != 0;
+    if (quant && (D.nslots <= 0 || !D.slot_of || !D.slot_frame || !D.slot_trans || !D.hist || !D.cmaps || !D.album_need)) return IMP_ERROR_INVALID_ARGS;
     hipLaunchKernelGGL(k_gif_enc_sets, dim3((unsigned)npx), dim3(256), 0, s, D);
     IMP_HIP(hipGetLastError());
+    if (quant) {                                                       // three launches more, whatever overflowed
+        hipLaunchKernelGGL(k_gif_enc_claim, dim3(1), dim3(256), 0, s, D, nalbums);
+        IMP_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_gif_enc_hist, dim3((unsigned)npx), dim3(256), 0, s, D);
+        IMP_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_gif_enc_cut, dim3((unsigned)D.nslots), dim3(256), 0, s, D);
+        IMP_HIP(hipGetLastError());
+    }
     hipLaunchKernelGGL(k_gif_enc_tables, dim3((unsigned)nalbums), dim3(256), 0, s, D);
     IMP_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_gif_enc_index, dim3((unsigned)npx), dim3(256), 0, s, D);
+    if (quant) hipLaunchKernelGGL(k_gif_enc_index<true>, dim3((unsigned)npx), dim3(256), 0, s, D);
+    else hipLaunchKernelGGL(k_gif_enc_index<false>, dim3((unsigned)npx), dim3(256), 0, s, D);
     IMP_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_gif_enc_lzw, dim3((unsigned)nseg), dim3(GIF_LANES), 0, s, D);
     IMP_HIP(hipGetLastError());

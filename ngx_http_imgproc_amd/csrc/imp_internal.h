@@ -513,7 +513,8 @@ int launch_gif_lzw_split(uint8_t* blob, size_t table_off, size_t split_off, size
 
 // imp_gif_enc.hip: the albums of a call into GIF streams (impgpu_batch_encode_gif): k_gif_enc_sets and k_gif_enc_index over
 // `npx` pixel items, k_gif_enc_tables over the albums, k_gif_enc_lzw over `nseg` segment items, k_gif_enc_pack over `npack`
-// items; the descriptors (imp_gif_enc.h) lie in the call's device block.
+// items; the descriptors (imp_gif_enc.h) lie in the call's device block.  With D.flags & IMPGPU_GIF_ENC_QUANTIZE three more run
+// behind the sets (k_gif_enc_claim, k_gif_enc_hist over `npx`, k_gif_enc_cut over D.nslots): eight launches instead of five.
 struct GifEncDev;
 int launch_gif_encode(const GifEncDev& D, long long npx, long long nseg, long long npack, int nalbums, hipStream_t s);
 
