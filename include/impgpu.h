@@ -836,6 +836,88 @@ int impgpu_gif_encode_host_ex(const unsigned char* const* frames, int count, int
 int impgpu_gif_quantize_host(const unsigned char* frame, int width, int height, int channels, int step,
                              unsigned char* table, int* entries, int* transparent_index, unsigned char* indices);
 
+/* ---- WEBP ANSWERS out, LOSSLESS, written ON THE DEVICE (opt-in: nothing calls these by default; the broker does not yet).
+ *      `format=webp&quality=256..511` asks FreeImage for a lossless file (bit 8 of its flags word is WEBP_LOSSLESS;
+ *      impgpu_request_webp_lossless says whether a parsed request does).  The file is deterministic, all-integer and NOT
+ *      libwebp's bytes; any VP8L decoder returns exactly the frame's pixels.  THE FILE, completely:
+ *      CONTAINER  "RIFF", u32 file size - 8, "WEBP", "VP8L", u32 payload size, the payload, one 0 byte when that size is odd.
+ *      BITS  are packed LSB-first, a value's low bit first.  PAYLOAD HEADER: the byte 0x2f, 14 bits width - 1, 14 bits
+ *        height - 1, 1 bit alpha_is_used (1 iff the frame has 4 channels and some alpha is not 255; alpha is written
+ *        faithfully either way), 3 bits version 0.
+ *      PIXELS  are A<<24 | R<<16 | G<<8 | B; a gray frame has R = G = B = v and A = 255, a B,G,R frame has A = 255.
+ *      TRANSFORMS, each announced by a 1 bit and 2 bits of type: subtract-green (type 2: R -= G, B -= G mod 256), then the
+ *        predictor (type 0), which adds 3 bits IMPGPU_WEBP_TILE_BITS - 2 and its MODE IMAGE; then a 0 bit.  The predictor
+ *        works on the green-subtracted image; the residual is pixel - prediction per channel mod 256.
+ *      PREDICTIONS  with L, T, TL, TR the left, top, top-left and top-right green-subtracted pixels (TR of the last column
+ *        is column 0 of the current row): pixel (0,0) is predicted 0xff000000, the rest of row 0 by L, the rest of column 0
+ *        by T; elsewhere the mode of the pixel's tile (tiles of 2^IMPGPU_WEBP_TILE_BITS pixels a side) applies: 0 0xff000000,
+ *        1 L, 2 T, 3 TR, 4 TL, 5 Avg2(Avg2(L,TR),T), 6 Avg2(L,TL), 7 Avg2(L,T), 8 Avg2(TL,T), 9 Avg2(T,TR),
+ *        10 Avg2(Avg2(L,TL),Avg2(T,TR)), 11 Select, 12 ClampAddSubtractFull(L,T,TL), 13 ClampAddSubtractHalf(Avg2(L,T),TL).
+ *        Avg2 is (a+b)>>1 per channel.  Select: with p = L+T-TL per channel, L when sum|p-L| < sum|p-T| over the four
+ *        channels, else T.  Full is clamp(L+T-TL) to 0..255; Half(a,b) is clamp(a + (a-b)/2), C division toward zero.
+ *      MODE CHOICE  per tile: every mode 0..13 is evaluated over the tile's pixels (the ones whose prediction the edge rules
+ *        fix included: they cost the same under every mode); a mode's cost is the sum of min(r, 256-r) over the four
+ *        residual channels; the smallest cost wins, a tie goes to the lowest mode.
+ *      MODE IMAGE  ceil(w / 2^bits) x ceil(h / 2^bits) pixels 0xff000000 | mode<<8, an entropy-coded image WITHOUT the
+ *        meta-prefix bit.
+ *      ENTROPY-CODED IMAGE  a 0 bit (no colour cache); for the main image alone a 0 bit (no meta prefix image); five prefix
+ *        codes in the order green (alphabet 280), red, blue, alpha (256 each), distance (40); then the pixels in raster order,
+ *        each as its green, red, blue, alpha symbol.  No backward references: green symbols 256..279 never occur, and the
+ *        distance code is the bits 1,0,0,0 (simple, one symbol, 0).
+ *      PREFIX CODES  a code with exactly ONE used symbol is the simple form 1,0,1 and the 8-bit symbol, and its symbols take
+ *        no bits.  Every other code (two used symbols included) is the normal form: 0; 4 bits count - 4; `count` 3-bit lengths
+ *        of the code-length code in the order 17,18,0,1,2,3,4,5,16,6,7,...,15, count being 19 less the trailing zeros of that
+ *        list, at least 4; a 0 bit (no max_symbol); then the lengths of ALL symbols of the alphabet.
+ *        LENGTHS are what zlib 1.2.11's build_tree + gen_bitlen (trees.c) give the frequencies: the heap ordered by
+ *        (frequency, depth), equal pairs broken by the heap's own layout, at most 15 bits (7 for the code-length code) by
+ *        gen_bitlen's repair.  Such a code is complete (Kraft sum 1), which libwebp demands.  Codes are canonical
+ *        (gen_codes) and written bit-reversed, as in deflate.
+ *        RUNS  the length list is tokenised by zlib's send_tree over the whole alphabet: a run of zeros of 3..10 is 17 and
+ *        3 extra bits, of 11..138 is 18 and 7 extra bits; a run of a non-zero length is the length once (unless the run
+ *        before it had the same length) and then 16 with 2 extra bits for 3..6 repeats; shorter runs are literal lengths;
+ *        a run is cut at 138 zeros, at 7 (6 right after a run of the same length) otherwise.  16 always follows its own length.
+ *        The code-length code's frequencies are the tokens' counts.
+ *      tests/webp_writer.py writes the same bytes from this paragraph alone.
+ *      TAKEN: 1-, 3- and 4-channel single images with sides 1..16384; a window of a parent (step > width x channels) is
+ *      read in place.  REFUSED: IMP_ERROR_UNSUPPORTED, *length = 0, nothing written: an album, 2 channels, a larger side.
+ *      IMP_ERROR_MALLOC_FAILED: `capacity` is too small; nothing is written, *length is the size needed
+ *      (impgpu_webp_encode_bound is always enough) -- and, with *length = 0, a frame whose device block does not fit under
+ *      $IMPGPU_STAGE_CAP_MB.  IMP_ERROR_INVALID_ARGS before a device is looked for: NULL arrays with count > 0, a count
+ *      outside 0..256, a forced mode above 13.  IMP_ERROR_DEVICE without an env.
+ *      SIX launches for a call (for a group under $IMPGPU_STAGE_CAP_MB), whatever it holds: k_webp_modes (a wavefront per
+ *      tile sums the 14 costs, exchanged across the wave), k_webp_resid (residual plane; four 256-bin histograms in LDS per
+ *      workgroup, added to the frame's: the sums do not depend on the order, so every run gives the same file),
+ *      k_webp_codes (a wavefront per frame; five lanes build a code each, one lane strings the header pieces together and
+ *      writes the record and the container's sizes), k_webp_measure (the bits of every item of 1024 symbols), k_webp_scan
+ *      (64-bit exclusive offsets) and k_webp_emit (an item's codes are ORed into LDS at their bit positions, 32 bits at most at a time; whole dwords
+ *      leave by plain stores, an item's first and last dword by an OR into the zeroed file, since a neighbour may share
+ *      them).  No kernel walks pixels sequentially.  TWO waits: the records (the lengths), then the files that fit.
+ *      MEASURED: (profiles/webp_encode_probe.json, one session, BGRA frames): a lone 640x480 photo-like frame
+ *      1.43 ms, a lone 1920x1080 one 2.75 ms, 64 frames of 320x240 4.99 ms -- against 0.11 / 0.53 / 1.72 ms for impgpu_batch_download
+ *      of the frames alone and 8.9 / 94.8 / 119 ms for that plus Pillow's lossless save (method 0) on one core.  Files 5 % smaller
+ *      than libwebp's method 0 on photo-like frames, 4.3x LARGER on dithered 256-colour frames and no match at all on flat
+ *      colour (a bit per pixel against 38 bytes): there are no backward references.  k_webp_codes (five sequential trees per
+ *      frame in device memory) is 1.0-1.5 ms of every call; the other five launches together 0.07-0.19 ms. ---- */
+#define IMPGPU_WEBP_TILE_BITS 4
+int impgpu_image_encode_webp(const impgpu_image* image, unsigned char* out, size_t capacity, size_t* length);
+/* diagnostic: forced_modes = one byte 0..13 per tile in raster order, and the chooser is skipped; NULL IS the call above */
+int impgpu_image_encode_webp_ex(const impgpu_image* image, const unsigned char* forced_modes, unsigned char* out, size_t capacity,
+                                size_t* length);
+/* MANY frames (count 0..256) of mixed sizes and channel counts: codes[i] / lengths[i] / the file are exactly the lone
+ * call's; a refused frame gets its code alone and changes no other entry.  *launches (may be NULL): the kernels enqueued
+ * -- 6 for a call under the stage cap whatever it holds, 0 when no frame was accepted. */
+int impgpu_batch_encode_webp(const impgpu_image* const* images, int count, unsigned char* const* outs, const size_t* capacities,
+                             size_t* lengths, int* codes, int* launches);
+/* a size no file of that geometry exceeds (0: a geometry the calls refuse) */
+size_t impgpu_webp_encode_bound(int width, int height, int channels);
+/* host, no device: the same file from a frame in host memory (rows `step` bytes apart), made by the launches' own lane code
+ * (csrc/imp_webp_enc.h) run one lane after the other.  forced_modes as above (normally NULL). */
+int impgpu_webp_encode_host(const unsigned char* frame, int width, int height, int channels, int step,
+                            const unsigned char* forced_modes, unsigned char* out, size_t capacity, size_t* length);
+/* 1 when the request's answer format resolves to webp (format=, else the extension) and its parsed quality has bit 8 set
+ * (256..511: FreeImage's WEBP_LOSSLESS); otherwise 0.  A pure accessor: the parse and its error codes are unchanged. */
+int impgpu_request_webp_lossless(const impgpu_request* request);
+
 /* ---- batch entry points (benchmark / multi-frame albums: bridge.c:578,591,608,632).
  *      `count` frames of identical geometry, frame i at base + i*frame_stride bytes,
  *      already resident in HBM.  stream = hipStream_t to launch on (NULL = env stream).

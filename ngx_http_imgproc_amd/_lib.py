@@ -181,6 +181,12 @@ SIGNATURES = {
     "impgpu_gif_encode_host_ex": (C.c_int, [PP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, IP, IP, C.c_int, C.c_int, C.c_int, P, C.c_size_t,
                                             C.POINTER(C.c_size_t)]),
     "impgpu_gif_quantize_host": (C.c_int, [P, C.c_int, C.c_int, C.c_int, C.c_int, P, IP, IP, P]),
+    "impgpu_image_encode_webp": (C.c_int, [P, P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "impgpu_image_encode_webp_ex": (C.c_int, [P, P, P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "impgpu_batch_encode_webp": (C.c_int, [PP, C.c_int, PP, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), IP, IP]),
+    "impgpu_webp_encode_bound": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "impgpu_webp_encode_host": (C.c_int, [P, C.c_int, C.c_int, C.c_int, C.c_int, P, P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "impgpu_request_webp_lossless": (C.c_int, [P]),
     "impgpu_album_download_fi": (C.c_int, [P, C.c_int, PP, IP]),
     "impgpu_batch_download_fi": (C.c_int, [PP, IP, C.c_int, PP, IP, IP, IP]),
     "impgpu_batch_album_download": (C.c_int, [PP, C.c_int, PP, IP, IP]),

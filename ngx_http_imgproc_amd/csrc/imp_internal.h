@@ -518,6 +518,12 @@ int launch_gif_lzw_split(uint8_t* blob, size_t table_off, size_t split_off, size
 struct GifEncDev;
 int launch_gif_encode(const GifEncDev& D, long long npx, long long nseg, long long npack, int nalbums, hipStream_t s);
 
+// imp_webp_enc.hip: the frames of a call into lossless WebP files (impgpu_batch_encode_webp): k_webp_modes over `ntile_items`
+// groups of four tiles, k_webp_codes and k_webp_scan over the frames, k_webp_resid, _measure and _emit over `nitems` stream
+// items; the descriptors (imp_webp_enc.h) lie in the call's device block.  Six launches.
+struct WebpDev;
+int launch_webp_encode(const WebpDev& D, long long ntile_items, long long nitems, int nframes, hipStream_t s);
+
 // imp_png_inflate.hip: the zlib streams of a call's PNG files, one workgroup of one wavefront per stream (impgpu_batch_decode_png_ex
 // with IMPGPU_PNG_DEVICE_INFLATE).  `descs` (imp_png.h) lie in device memory; descriptor k is workgroup k's.
 struct PngInflateDesc;

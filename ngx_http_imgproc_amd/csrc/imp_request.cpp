@@ -17,6 +17,7 @@ struct impgpu_request {
     int page = -1;
     int mime = 0;
     int destructive = 0;
+    int webp_lossless = 0;                   // the answer is webp and quality has FreeImage's WEBP_LOSSLESS bit (0x100)
 };
 
 namespace {
@@ -134,6 +135,7 @@ int impgpu_parse_request(const char* uri, const char* extension, const impgpu_co
         if (ieq(e, "j2k") || ieq(e, "j2c") || ieq(e, "jp2") || ieq(e, "webp")) {
             const long qv = std::strtol(r->quality, nullptr, 10);
             if (qv < 0 || qv > 512) return IMP_ERROR_INVALID_ARGS;
+            r->webp_lossless = ieq(e, "webp") && (qv & 0x100) != 0;
         }
     }
     r->job.simple = cls == F_GIF;                                        // bridge.c:594
@@ -147,6 +149,7 @@ const char* impgpu_request_format(const impgpu_request* r) { return r ? r->forma
 int impgpu_request_page(const impgpu_request* r) { return r ? r->page : -1; }
 int impgpu_request_mime(const impgpu_request* r) { return r ? r->mime : 0; }
 int impgpu_request_destructive(const impgpu_request* r) { return r ? r->destructive : 0; }
+int impgpu_request_webp_lossless(const impgpu_request* r) { return r ? r->webp_lossless : 0; }
 void impgpu_request_free(impgpu_request** r) {
     if (!r || !*r) return;
     delete *r;
