@@ -914,6 +914,73 @@ size_t impgpu_webp_encode_bound(int width, int height, int channels);
  * (csrc/imp_webp_enc.h) run one lane after the other.  forced_modes as above (normally NULL). */
 int impgpu_webp_encode_host(const unsigned char* frame, int width, int height, int channels, int step,
                             const unsigned char* forced_modes, unsigned char* out, size_t capacity, size_t* length);
+/* ---- WEBP ANSWERS, BACKWARD REFERENCES (opt-in flag IMPGPU_WEBP_ENC_BACKREFS on the _flags calls below; without it every
+ *      call, byte and launch count above stays what it is).  THE FILE WITH THE FLAG:
+ *      THE SAME  container, payload header, transforms, predictions, mode choice and mode image, exactly.  The mode image
+ *        gets no backward references; its distance code stays the bits 1,0,0,0.  The prefix-code rules (simple / normal
+ *        form, build_tree, send_tree runs) are unchanged and now also serve the green code over all its 280 symbols and the
+ *        main image's distance code (alphabet 40, lengths of ALL 40 symbols).
+ *      WHAT DIFFERS  is the main image's pixel stream.  The residual plane, in raster order p = 0 .. w*h - 1, is cut into
+ *        items of 1024 positions; each item is parsed on its own, greedily, from its first position s to its end
+ *        e = min(s + 1024, w*h).
+ *        CANDIDATES  k = 1 .. 24 are the first 24 entries of VP8L's distance map, as (xi, yi): (0,1) (1,0) (1,1) (-1,1) (0,2)
+ *          (2,0) (1,2) (-1,2) (2,1) (-2,1) (2,2) (-2,2) (0,3) (3,0) (1,3) (-1,3) (3,1) (-3,1) (2,3) (-2,3) (3,2) (-3,2) (0,4)
+ *          (4,0).  Candidate k's distance is d_k = xi + yi * w; it is usable at p iff 1 <= d_k <= p.  A match may start at an
+ *          item's first position and read residuals of earlier items; it may not run past e.
+ *        MATCH LENGTH  L_k(p) is the largest L with p + L <= e and resid[p+i] == resid[p+i-d_k] for all 0 <= i < L (0 when k
+ *          is not usable at p); all four channels are compared as one dword; the match may overlap itself, as in any LZ77.
+ *        CHOICE  the largest L_k wins, a tie goes to the lowest k.  If the winner is >= IMPGPU_WEBP_MIN_MATCH (3) the token
+ *          is a backward reference (length, k) and p advances by the length; otherwise the token is the literal pixel and p
+ *          advances by 1.
+ *        A LITERAL is coded as above: its green, red, blue and alpha symbols.  A BACKWARD REFERENCE is, in this order, the
+ *          green code's symbol 256 + s_len, the length's extra bits, the distance code's symbol s_dist, its extra bits.
+ *          The length (3..1024) and the plane code k (1..24) both use VP8L's prefix coding of a value v >= 1: v <= 4 gives
+ *          symbol v - 1 and no extra bits; otherwise, with u = v - 1, hb = floor(log2 u) and sb = (u >> (hb-1)) & 1, the
+ *          symbol is 2*hb + sb and there are hb - 1 extra bits of value u & ((1 << (hb-1)) - 1), written LSB-first.  (The
+ *          decoder: a symbol below 4 stands for sym + 1; otherwise eb = (sym-2) >> 1 and v = ((2 + (sym&1)) << eb) + bits(eb)
+ *          + 1.)  Lengths use symbols 2..19, distances 0..8; a plane code above 120, a colour cache and a meta prefix image
+ *          never occur.
+ *        HISTOGRAMS  count tokens: a literal its four symbols, a reference one green symbol 256.. and one distance symbol.
+ *        DISTANCE CODE  no used symbol: the bits 1,0,0,0 as above; one used symbol: the simple form 1,0,1 and the 8-bit
+ *          symbol; otherwise the normal form over 40 symbols.
+ *        CONSEQUENCES  a frame in which no position finds a match of 3 is byte for byte the flag-less file; position 0 is
+ *          always a literal (so no code of the main image is unused but the distance code); 60 bits still bound a
+ *          position: 15 + 8 + 15 + 3 for a reference.
+ *      tests/webp_lz_writer.py writes the same bytes from this paragraph alone (and webp_writer's rules).
+ *      SEVEN launches with the flag, two waits: k_webp_resid writes the residual plane and counts nothing; k_webp_parse, a
+ *      workgroup per item of 1024 positions, follows it: per candidate the item's equality bits go to LDS as 32 words from
+ *      wave ballots, a position's L_k is the distance to the next zero bit found by word operations, every position notes
+ *      where its token would end, and the token starts -- the positions reached from s -- are marked by pointer doubling (ten
+ *      jump tables in LDS, applied from the highest power down); the tokens go to a TOKEN PLANE (a dword a position: 0
+ *      covered, a literal marker, or length | k << 16) and into histograms staged in LDS (green over 280, red, blue, alpha,
+ *      distance over 40, the total of the extra bits in 64 bits), added once a workgroup; the sums do not depend on the
+ *      order, so every run gives the same file.  k_webp_codes gives a sixth lane the distance code; k_webp_measure / _scan /
+ *      _emit keep their shape, a covered position being 0 bits and a reference four parts of at most 15, 8, 15 and 3 bits.
+ *      The device block grows by the token plane (4 bytes a pixel) and a second work area a frame; the groups under
+ *      $IMPGPU_STAGE_CAP_MB count both.
+ *      WHAT IT WINS AND WHAT NOT (profiles/webp_lz_sizes.json, 320x240 B,G,R, against the flag-less file / libwebp method 0):
+ *      flat colour 152 B / 28 852 B / 38 B; a synthetic screenshot 708 / 29 124 / 342; a Bayer-dithered frame 22 610 / 41 710 /
+ *      12 474; a photo-like frame 119 720 / 119 720 / 125 710 -- no match of 3 in sensor noise, the flag-less file.  Matches are
+ *      confined to an item of 1024 positions and to 24 neighbours, and there is no colour cache: libwebp stays 2x ahead on
+ *      graphics and dither.  MEASURED (profiles/webp_lz_probe.json, one session, flag off / on alternating, BGRA): a lone
+ *      640x480 frame 1.44 / 1.48 ms photo-like, 0.78 / 0.84 dithered, 0.49 / 0.56 flat; 1920x1080 3.05 / 3.07, 2.26 / 2.27,
+ *      1.60 / 1.69; 64 frames of 320x240 5.16 / 5.40, 4.64 / 4.75, 3.91 / 3.66.  The flagged call is BEHIND the flag-less one by
+ *      0.01-0.24 ms everywhere but the last: k_webp_parse costs 42-48 / 111-125 / 228-250 us, k_webp_codes 20-50 us more, and
+ *      k_webp_codes' 0.3-1.4 ms is still most of every call.  What crosses the link shrinks with the file: 1.7 MB -> 0.8 MB
+ *      (1080p dithered), 778 KB -> 2.6 KB (1080p flat). ----
+ * the calls with `flags`: 0 IS the call above (same bytes, same codes, six launches); IMPGPU_WEBP_ENC_BACKREFS writes the file
+ * of the paragraph above in seven launches.  An unknown flag bit: IMP_ERROR_INVALID_ARGS before a device is looked for.
+ * Refusals and the IMP_ERROR_MALLOC_FAILED contract are the ones above.  forced_modes: normally NULL. */
+#define IMPGPU_WEBP_ENC_BACKREFS 1
+#define IMPGPU_WEBP_MIN_MATCH 3
+int impgpu_image_encode_webp_flags(const impgpu_image* image, int flags, const unsigned char* forced_modes, unsigned char* out, size_t capacity,
+                                   size_t* length);
+int impgpu_batch_encode_webp_flags(const impgpu_image* const* images, int count, int flags, unsigned char* const* outs, const size_t* capacities,
+                                   size_t* lengths, int* codes, int* launches);
+int impgpu_webp_encode_host_flags(const unsigned char* frame, int width, int height, int channels, int step, int flags,
+                                  const unsigned char* forced_modes, unsigned char* out, size_t capacity, size_t* length);
+/* impgpu_webp_encode_bound with the flags' longer distance-code header included */
+size_t impgpu_webp_encode_bound_flags(int width, int height, int channels, int flags);
 /* 1 when the request's answer format resolves to webp (format=, else the extension) and its parsed quality has bit 8 set
  * (256..511: FreeImage's WEBP_LOSSLESS); otherwise 0.  A pure accessor: the parse and its error codes are unchanged. */
 int impgpu_request_webp_lossless(const impgpu_request* request);

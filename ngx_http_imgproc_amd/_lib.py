@@ -186,6 +186,10 @@ SIGNATURES = {
     "impgpu_batch_encode_webp": (C.c_int, [PP, C.c_int, PP, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), IP, IP]),
     "impgpu_webp_encode_bound": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "impgpu_webp_encode_host": (C.c_int, [P, C.c_int, C.c_int, C.c_int, C.c_int, P, P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "impgpu_image_encode_webp_flags": (C.c_int, [P, C.c_int, P, P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "impgpu_batch_encode_webp_flags": (C.c_int, [PP, C.c_int, C.c_int, PP, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), IP, IP]),
+    "impgpu_webp_encode_bound_flags": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "impgpu_webp_encode_host_flags": (C.c_int, [P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "impgpu_request_webp_lossless": (C.c_int, [P]),
     "impgpu_album_download_fi": (C.c_int, [P, C.c_int, PP, IP]),
     "impgpu_batch_download_fi": (C.c_int, [PP, IP, C.c_int, PP, IP, IP, IP]),

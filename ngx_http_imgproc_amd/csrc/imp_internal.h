@@ -520,7 +520,7 @@ int launch_gif_encode(const GifEncDev& D, long long npx, long long nseg, long lo
 
 // imp_webp_enc.hip: the frames of a call into lossless WebP files (impgpu_batch_encode_webp): k_webp_modes over `ntile_items`
 // groups of four tiles, k_webp_codes and k_webp_scan over the frames, k_webp_resid, _measure and _emit over `nitems` stream
-// items; the descriptors (imp_webp_enc.h) lie in the call's device block.  Six launches.
+// items; the descriptors (imp_webp_enc.h) lie in the call's device block.  Six launches; seven with D.lz (k_webp_parse).
 struct WebpDev;
 int launch_webp_encode(const WebpDev& D, long long ntile_items, long long nitems, int nframes, hipStream_t s);
 

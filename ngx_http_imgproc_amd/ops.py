@@ -1039,25 +1039,34 @@ def batch_encode_gif(albums, time_ms=None, dispose=None, loop_counts=None, segme
 
 
 WEBP_TILE_BITS = 4                            # IMPGPU_WEBP_TILE_BITS
+WEBP_ENC_BACKREFS = 1                         # IMPGPU_WEBP_ENC_BACKREFS
+WEBP_MIN_MATCH = 3                            # IMPGPU_WEBP_MIN_MATCH
 
 
-def webp_encode_bound(width, height, channels):
-    """impgpu_webp_encode_bound: a size no lossless WebP file of that frame exceeds (0: a geometry the encoder refuses)"""
-    return lib.impgpu_webp_encode_bound(int(width), int(height), int(channels))
+def webp_encode_bound(width, height, channels, flags=None):
+    """impgpu_webp_encode_bound: a size no lossless WebP file of that frame exceeds (0: a geometry the encoder refuses).
+    flags: None = the call itself; a number = impgpu_webp_encode_bound_flags (WEBP_ENC_BACKREFS: backward references)"""
+    if flags is None:
+        return lib.impgpu_webp_encode_bound(int(width), int(height), int(channels))
+    return lib.impgpu_webp_encode_bound_flags(int(width), int(height), int(channels), int(flags))
 
 
 def _modes(forced_modes):
     return None if forced_modes is None else np.ascontiguousarray(forced_modes, dtype=np.uint8).reshape(-1)
 
 
-def encode_webp(image, forced_modes=None, capacity=None, guard=64):
+def encode_webp(image, forced_modes=None, capacity=None, guard=64, flags=None):
     """impgpu_image_encode_webp: the image as a lossless WebP file written on the device -> (code, bytes or None, length,
     intact), as encode_gif: `capacity` defaults to webp_encode_bound, `guard` bytes behind it are checked.  forced_modes:
-    None = the call itself; one mode 0..13 per tile = impgpu_image_encode_webp_ex (the chooser is skipped)."""
-    cap = webp_encode_bound(image.shape[1], image.shape[0], image.shape[2]) if capacity is None else int(capacity)
+    None = the call itself; one mode 0..13 per tile = impgpu_image_encode_webp_ex (the chooser is skipped).  flags: None =
+    those calls; a number = impgpu_image_encode_webp_flags (WEBP_ENC_BACKREFS: backward references, seven launches)."""
+    cap = webp_encode_bound(image.shape[1], image.shape[0], image.shape[2], flags) if capacity is None else int(capacity)
     buf = np.full(max(1, cap) + guard, 0xA5, np.uint8)
     n = C.c_size_t(0)
-    if forced_modes is None:
+    if flags is not None:
+        keep = _modes(forced_modes)
+        rc = lib.impgpu_image_encode_webp_flags(image.h, int(flags), None if keep is None else keep.ctypes.data, buf.ctypes.data, cap, C.byref(n))
+    elif forced_modes is None:
         rc = lib.impgpu_image_encode_webp(image.h, buf.ctypes.data, cap, C.byref(n))
     else:
         keep = _modes(forced_modes)
@@ -1065,28 +1074,32 @@ def encode_webp(image, forced_modes=None, capacity=None, guard=64):
     return _gif_out(rc, buf, n)
 
 
-def encode_webp_host(frame, forced_modes=None, capacity=None, guard=64, channels=None):
+def encode_webp_host(frame, forced_modes=None, capacity=None, guard=64, channels=None, flags=None):
     """impgpu_webp_encode_host (no device): one HxWxC uint8 array (a view with padded rows is fine) -> (code, bytes or None,
-    length, intact), as encode_webp."""
+    length, intact), as encode_webp.  flags: None, or impgpu_webp_encode_host_flags'."""
     hh, ww, cc = frame.shape
     assert frame.dtype == np.uint8 and frame.strides[1:] == (cc, 1)
     cc = cc if channels is None else int(channels)
-    cap = webp_encode_bound(ww, hh, cc) if capacity is None else int(capacity)
+    cap = webp_encode_bound(ww, hh, cc, flags) if capacity is None else int(capacity)
     buf = np.full(max(1, cap) + guard, 0xA5, np.uint8)
     n = C.c_size_t(0)
     keep = _modes(forced_modes)
-    rc = lib.impgpu_webp_encode_host(frame.ctypes.data, ww, hh, cc, frame.strides[0], None if keep is None else keep.ctypes.data,
-                                     buf.ctypes.data, cap, C.byref(n))
+    if flags is None:
+        rc = lib.impgpu_webp_encode_host(frame.ctypes.data, ww, hh, cc, frame.strides[0], None if keep is None else keep.ctypes.data,
+                                         buf.ctypes.data, cap, C.byref(n))
+    else:
+        rc = lib.impgpu_webp_encode_host_flags(frame.ctypes.data, ww, hh, cc, frame.strides[0], int(flags), None if keep is None else keep.ctypes.data,
+                                               buf.ctypes.data, cap, C.byref(n))
     return _gif_out(rc, buf, n)
 
 
-def batch_encode_webp(images, capacities=None, count=None, guard=64):
+def batch_encode_webp(images, capacities=None, count=None, guard=64, flags=None):
     """impgpu_batch_encode_webp: images (an entry may be None) -> (code, [(code, bytes or None, length, intact) ...],
-    launches).  capacities default to webp_encode_bound."""
+    launches).  capacities default to webp_encode_bound.  flags: None, or impgpu_batch_encode_webp_flags'."""
     n = len(images)
     m = max(1, n)
     handles = (C.c_void_p * m)(*[_handle(a) for a in images])
-    caps = [(webp_encode_bound(a.shape[1], a.shape[0], a.shape[2]) if a is not None else 0) if capacities is None or capacities[i] is None
+    caps = [(webp_encode_bound(a.shape[1], a.shape[0], a.shape[2], flags) if a is not None else 0) if capacities is None or capacities[i] is None
             else int(capacities[i]) for i, a in enumerate(images)]
     bufs = [np.full(max(1, c) + guard, 0xA5, np.uint8) for c in caps]
     outs = (C.c_void_p * m)(*[b.ctypes.data for b in bufs])
@@ -1094,7 +1107,10 @@ def batch_encode_webp(images, capacities=None, count=None, guard=64):
     lens = (C.c_size_t * m)()
     codes = (C.c_int * m)(*([-1] * m))
     launches = C.c_int(-1)
-    rc = lib.impgpu_batch_encode_webp(handles, n if count is None else count, outs, carr, lens, codes, C.byref(launches))
+    if flags is None:
+        rc = lib.impgpu_batch_encode_webp(handles, n if count is None else count, outs, carr, lens, codes, C.byref(launches))
+    else:
+        rc = lib.impgpu_batch_encode_webp_flags(handles, n if count is None else count, int(flags), outs, carr, lens, codes, C.byref(launches))
     return rc, [_gif_out(codes[i], bufs[i], C.c_size_t(lens[i])) for i in range(n)], launches.value
 
 
