@@ -836,6 +836,65 @@ int impgpu_gif_encode_host_ex(const unsigned char* const* frames, int count, int
 int impgpu_gif_quantize_host(const unsigned char* frame, int width, int height, int channels, int step,
                              unsigned char* table, int* entries, int* transparent_index, unsigned char* indices);
 
+/* ---- GIF FILES out, DELTA FRAMES (opt-in): the _ex calls again, as _ex2, whose `flags` may hold IMPGPU_GIF_ENC_QUANTIZE |
+ *      IMPGPU_GIF_ENC_DELTA.  Any other bit: IMP_ERROR_INVALID_ARGS before a device is looked for.  Without the DELTA bit an
+ *      _ex2 call IS the _ex call -- files, codes, refusals, launches and waits -- and the _ex calls keep refusing the bit.
+ *      Why: a request with a destructive filter (blur, vignette) or a page extraction restores every frame to a full canvas
+ *      (advancedio.c:195-240), and the answer loses GIF's inter-frame compression.  Under the bit a pixel equal to the pixel
+ *      under it in the previous frame is written as transparent, and the frame shrinks to the rectangle that changed.
+ *      THE FILE.  Everything in the definitions above stands.  Under IMPGPU_GIF_ENC_DELTA, with d(i) = dispose[i] (0 where
+ *      dispose is NULL):
+ *      1. DELTA FRAMES.  Frame i is a CANDIDATE iff i >= 1, d(i-1) is 0 or 1, and d(i) is 0 or 1.  Frame 0 is never a
+ *         candidate.  A frame behind a "restore to background / previous" is never a candidate.  A frame that itself asks
+ *         for one is never a candidate either, because its disposal area would shrink with its window.
+ *      2. HELD PIXELS.  In a candidate, pixel p is HELD iff its key is a colour and equals the key of pixel p of frame i-1.
+ *         Keys are as defined today: GIF_KEY_TRANSPARENT for alpha 0 of a 4-channel frame, else the R,G,B.  The keys are
+ *         those of the caller's frames.  They are never a quantised colour and never what was written for frame i-1.  A
+ *         transparent pixel is never held.
+ *      3. WINDOW.  The window is the smallest rectangle x0,y0,ww,wh that contains every pixel that is not held.  If every
+ *         pixel is held, the window is the 1 x 1 rectangle at 0,0.  Outside the window every pixel is held.
+ *      4. WRITTEN KEYS.  In window raster order, a held pixel is written as GIF_KEY_TRANSPARENT and any other pixel keeps
+ *         its own key.  Set A is the set of written keys.  Set B is the frame's own key set over the whole frame, which is
+ *         today's set.
+ *      5. CHOICE, per candidate.  |A| <= 256: the frame is a DELTA FRAME.  Its "frame" for every later rule (union and
+ *         global-table decision, table, has_trans, indices, LZW, segments, which count window pixels) is the written window
+ *         with set A.  Else |B| <= 256: the frame is written PLAIN, exactly as without the bit.  Else, with
+ *         IMPGPU_GIF_ENC_QUANTIZE: the frame is a delta frame and is quantised.  Steps 1-5 of the quantiser run over the
+ *         window's pixels that are neither held nor transparent.  T = 1 iff the window has a held or a transparent pixel.
+ *         A held pixel's index is nkeys - 1.  Else: the album is refused as today.  A non-candidate frame is written as
+ *         without the bit.  So the bit never refuses an album the call without it takes, and it never quantises a frame the
+ *         call without it writes exactly.
+ *      6. CONTAINER.  A delta frame's image descriptor is x0, y0, ww, wh.  Its graphic control extension carries the
+ *         caller's dispose[i] and delay unchanged.  The transparency flag and index follow the window's has_trans.
+ *         Everything else is as today.
+ *      GUARANTEED: for an album in which no frame is quantised, a GIF viewer composites the flagged file to the same
+ *      canvases, frame by frame, as the file without the bit: a held pixel is replaced only where the canvas already holds
+ *      that colour.  Where a frame IS quantised, a held pixel shows an EARLIER frame's rendering of the same source colour
+ *      (that frame's own table entry, not this frame's), so such a file does not composite to the flag-less file's canvases.
+ *      impgpu_gif_encode_bound holds unchanged: a window is never larger than its frame.
+ *      ONE launch more per group than the same call without the bit -- 6, or 9 under IMPGPU_GIF_ENC_QUANTIZE; *launches says
+ *      so -- and the same two waits: k_gif_enc_delta runs ahead of k_gif_enc_sets on the same 4096-pixel items (a lane
+ *      compares its 16 keys with the previous frame's and leaves 16 held bits; the bounds of the pixels not held are folded
+ *      across the wave, then the workgroup, and one lane publishes them with atomicMax: integer and order-free, the same
+ *      file on every run).  The later launches read the held bits, never the previous frame.  The host plans the segments
+ *      for the whole frame (it cannot know the window without a third wait): the segments behind the window's last pixel
+ *      stay empty.  WHERE IT LOSES: an album in which everything changes pays k_gif_enc_delta and a second colour set per
+ *      candidate and gains nothing.
+ *      MEASURED (profiles/gif_delta_probe.json, one session, flag off -> on; a still background and a 64 x 64
+ *      patch that moves): 8 frames at 640x480 2.47 -> 2.30 ms and 3.28 -> 0.46 MB (past 256 colours, with QUANTIZE: 3.07 -> 2.80
+ *      ms, 1.20 -> 0.18 MB); 64 albums of 8 frames at 320x240 19.6 -> 10.1 ms, 50.8 -> 9.4 MB (25.1 -> 13.0 ms, 25.3 -> 5.6 MB).
+ *      A lone album gains little time: its first frame is written whole and one segment's walk is the call.  Everything
+ *      changing: 2.48 -> 2.52 ms (+1.8 %), and the file grows by 0.04 %. ---- */
+#define IMPGPU_GIF_ENC_DELTA 2
+int impgpu_album_encode_gif_ex2(const impgpu_image* album, const int* time_ms, const int* dispose, int loop_count, int segment,
+                                int flags, unsigned char* out, size_t capacity, size_t* length);
+int impgpu_batch_encode_gif_ex2(const impgpu_image* const* albums, const int* const* time_ms, const int* const* dispose,
+                                const int* loop_counts, int count, int segment, int flags, unsigned char* const* outs,
+                                const size_t* capacities, size_t* lengths, int* codes, int* launches);
+int impgpu_gif_encode_host_ex2(const unsigned char* const* frames, int count, int width, int height, int channels, int step,
+                               const int* time_ms, const int* dispose, int loop_count, int segment, int flags,
+                               unsigned char* out, size_t capacity, size_t* length);
+
 /* ---- WEBP ANSWERS out, LOSSLESS, written ON THE DEVICE (opt-in: nothing calls these by default; the broker does not yet).
  *      `format=webp&quality=256..511` asks FreeImage for a lossless file (bit 8 of its flags word is WEBP_LOSSLESS;
  *      impgpu_request_webp_lossless says whether a parsed request does).  The file is deterministic, all-integer and NOT

@@ -19,6 +19,6 @@ from .ops import (  # noqa: F401
     batch_cv_resize, batch_resize_mixed, ResizeItem, batch_resize_rotate_watermark, batch_filters, run_ops, batch_run_ops, Request, gif_compose,
     batch_calc_perceived_brightness, batch_ascii, batch_gif_compose, gif_page_array, batch_download_fi, batch_album_download,
     decode_gif, batch_decode_gif, gif_info, gif_pages, gif_pages_split, GIF_SPLIT, GIF_SPLIT_MIN_BYTES,
-    encode_gif, batch_encode_gif, encode_gif_host, gif_encode_bound, GIF_ENC_SEGMENT, gif_quantize_host, GIF_ENC_QUANTIZE,
+    encode_gif, batch_encode_gif, encode_gif_host, gif_encode_bound, GIF_ENC_SEGMENT, gif_quantize_host, GIF_ENC_QUANTIZE, GIF_ENC_DELTA,
     encode_webp, batch_encode_webp, encode_webp_host, webp_encode_bound, WEBP_TILE_BITS, WEBP_ENC_BACKREFS, WEBP_MIN_MATCH,
 )

@@ -180,6 +180,11 @@ SIGNATURES = {
                                              C.POINTER(C.c_size_t), IP, IP]),
     "impgpu_gif_encode_host_ex": (C.c_int, [PP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, IP, IP, C.c_int, C.c_int, C.c_int, P, C.c_size_t,
                                             C.POINTER(C.c_size_t)]),
+    "impgpu_album_encode_gif_ex2": (C.c_int, [P, IP, IP, C.c_int, C.c_int, C.c_int, P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "impgpu_batch_encode_gif_ex2": (C.c_int, [PP, C.POINTER(IP), C.POINTER(IP), IP, C.c_int, C.c_int, C.c_int, PP, C.POINTER(C.c_size_t),
+                                              C.POINTER(C.c_size_t), IP, IP]),
+    "impgpu_gif_encode_host_ex2": (C.c_int, [PP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, IP, IP, C.c_int, C.c_int, C.c_int, P, C.c_size_t,
+                                             C.POINTER(C.c_size_t)]),
     "impgpu_gif_quantize_host": (C.c_int, [P, C.c_int, C.c_int, C.c_int, C.c_int, P, IP, IP, P]),
     "impgpu_image_encode_webp": (C.c_int, [P, P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "impgpu_image_encode_webp_ex": (C.c_int, [P, P, P, C.c_size_t, C.POINTER(C.c_size_t)]),

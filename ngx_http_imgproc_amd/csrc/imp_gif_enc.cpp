@@ -6,6 +6,9 @@
 // (gif_enc_write_file).  impgpu_gif_encode_host is the same pipeline with no device: imp_gif_enc.h's lane code on one thread.
 // The _ex calls take flags: under IMPGPU_GIF_ENC_QUANTIZE a group's block also holds a pool of histogram slots, eight launches
 // run, and the albums the pool had no room for are encoded in further groups (impgpu_batch_encode_gif_ex).
+// The _ex2 calls also take IMPGPU_GIF_ENC_DELTA: the block then holds a candidate word and a window record per frame, a
+// second colour set and the candidates' held planes, k_gif_enc_delta runs ahead of the other launches, and the windows come
+// back with the records in the first wait.
 #include "imp_internal.h"
 #include "imp_gif_enc.h"
 
@@ -35,15 +38,24 @@ int encode_group(const std::vector<EncPlan>& plans, const impgpu_image* const* a
     std::vector<GifEncFrameDesc> fd((size_t)nf);
     std::vector<GifEncAlbumDesc> ad((size_t)na);
     std::vector<GifEncItem> px_items, seg_items, pack_items;
-    size_t planes = 0, scratch = 0, outb = 0;
+    const bool delta = (flags & IMPGPU_GIF_ENC_DELTA) != 0;
+    std::vector<GifDeltaDesc> dd(delta ? (size_t)nf : 0);
+    size_t planes = 0, scratch = 0, outb = 0, heldw = 0;
     uint64_t nsegs = 0;
     for (int a = 0; a < na; a++) {
         const impgpu_image* im = albums[plans[(size_t)a].entry];
         ad[(size_t)a] = GifEncAlbumDesc{plans[(size_t)a].first, plans[(size_t)a].frames};
         const uint32_t total = (uint32_t)im->w * (uint32_t)im->h;
         const uint32_t out_cap = gif_enc_framed_size((uint32_t)gif_enc_stream_bound(total));
+        const int* dis = dispose ? dispose[plans[(size_t)a].entry] : nullptr;
+        auto keeps = [&](int q) { const int d = dis ? dis[q] : 0; return d == 0 || d == 1; };
         for (int q = 0; q < im->frames; q++) {
             const int f = plans[(size_t)a].first + q;
+            if (delta) {                                                    // a candidate: a held plane, 16 pixels a word
+                const bool cand = q >= 1 && keeps(q - 1) && keeps(q);
+                dd[(size_t)f] = GifDeltaDesc{cand ? f - 1 : -1, (uint32_t)heldw};
+                if (cand) heldw += up256(((size_t)total + 15) / 16 * 2) / 2;
+            }
             GifEncFrameDesc& d = fd[(size_t)f];
             d.src = im->d + (size_t)q * im->fstride;
             d.w = im->w; d.h = im->h; d.c = im->c; d.step = im->step; d.album = a;
@@ -68,11 +80,13 @@ int encode_group(const std::vector<EncPlan>& plans, const impgpu_image* const* a
     const size_t ns = quant ? (size_t)nslots : 0;
     const size_t o_fd = 0, o_ad = o_fd + up256(fd.size() * sizeof(GifEncFrameDesc)), o_px = o_ad + up256(ad.size() * sizeof(GifEncAlbumDesc)),
                  o_seg = o_px + up256(px_items.size() * sizeof(GifEncItem)), o_pack = o_seg + up256(seg_items.size() * sizeof(GifEncItem)),
-                 o_rec = o_pack + up256(pack_items.size() * sizeof(GifEncItem)), o_need = o_rec + up256((size_t)nf * sizeof(GifEncRec)),
-                 o_set = o_need + (quant ? up256((size_t)na * 4) : 0), o_sframe = o_set + up256((size_t)nf * sizeof(GifColourSet)),
+                 o_dd = o_pack + up256(pack_items.size() * sizeof(GifEncItem)), o_rec = o_dd + up256(dd.size() * sizeof(GifDeltaDesc)),
+                 o_win = o_rec + up256((size_t)nf * sizeof(GifEncRec)), o_need = o_win + (delta ? up256((size_t)nf * sizeof(GifDeltaRec)) : 0),
+                 o_set = o_need + (quant ? up256((size_t)na * 4) : 0), o_seta = o_set + up256((size_t)nf * sizeof(GifColourSet)),
+                 o_sframe = o_seta + (delta ? up256((size_t)nf * sizeof(GifColourSet)) : 0),
                  o_strans = o_sframe + up256(ns * 4), o_hist = o_strans + up256(ns * 4), o_slotof = o_hist + ns * GIF_Q_HIST_WORDS * 4,
                  o_cmap = o_slotof + (quant ? up256((size_t)nf * 4) : 0), o_tab = o_cmap + ns * GIF_Q_CELLS, o_bits = o_tab + up256((size_t)nf * 1024),
-                 o_plane = o_bits + up256((size_t)nsegs * 4), o_scr = o_plane + planes, o_out = o_scr + scratch, o_end = o_out + outb;
+                 o_held = o_bits + up256((size_t)nsegs * 4), o_plane = o_held + up256(heldw * 2), o_scr = o_plane + planes, o_out = o_scr + scratch, o_end = o_out + outb;
     for (GifEncFrameDesc& d : fd) { d.plane_off += (long long)o_plane; d.scratch_off += (long long)o_scr; d.out_off += (long long)o_out; }
     void* mem = nullptr;
     if (int rc = dev_alloc(o_end, &mem)) return rc;
@@ -83,6 +97,7 @@ int encode_group(const std::vector<EncPlan>& plans, const impgpu_image* const* a
     std::memcpy(head.data() + o_px, px_items.data(), px_items.size() * sizeof(GifEncItem));
     std::memcpy(head.data() + o_seg, seg_items.data(), seg_items.size() * sizeof(GifEncItem));
     std::memcpy(head.data() + o_pack, pack_items.data(), pack_items.size() * sizeof(GifEncItem));
+    if (delta) std::memcpy(head.data() + o_dd, dd.data(), dd.size() * sizeof(GifDeltaDesc));
     int rc = upload_to(m, head.data(), head.size(), s);
     if (!rc) {
         const hipError_t e = hipMemsetAsync(m + o_rec, 0, (quant ? o_slotof : o_tab) - o_rec, s);
@@ -96,12 +111,16 @@ int encode_group(const std::vector<EncPlan>& plans, const impgpu_image* const* a
     D.slot_of = quant ? (int*)(m + o_slotof) : nullptr; D.slot_frame = quant ? (uint32_t*)(m + o_sframe) : nullptr;
     D.slot_trans = quant ? (uint32_t*)(m + o_strans) : nullptr; D.hist = quant ? (uint32_t*)(m + o_hist) : nullptr;
     D.cmaps = quant ? m + o_cmap : nullptr; D.album_need = quant ? (uint32_t*)(m + o_need) : nullptr;
+    D.ddesc = delta ? (const GifDeltaDesc*)(m + o_dd) : nullptr; D.wins = delta ? (GifDeltaRec*)(m + o_win) : nullptr;
+    D.held = delta ? (uint16_t*)(m + o_held) : nullptr; D.sets_a = delta ? (GifColourSet*)(m + o_seta) : nullptr;
     D.sets = (GifColourSet*)(m + o_set); D.tabs = (uint32_t*)(m + o_tab); D.recs = (GifEncRec*)(m + o_rec); D.segbits = (uint32_t*)(m + o_bits);
     if (!rc) rc = launch_gif_encode(D, (long long)px_items.size(), (long long)seg_items.size(), (long long)pack_items.size(), na, s);
-    // the first wait: the records (and, behind them, the albums' words)
+    // the first wait: the records (and, behind them, the frames' windows and the albums' words)
     std::vector<GifEncRec> recs((size_t)nf);
+    std::vector<GifDeltaRec> wins(delta ? (size_t)nf : 0);
     std::vector<uint32_t> need((size_t)na, 0u);
-    const size_t rec_bytes = quant ? (o_need - o_rec) + need.size() * 4 : recs.size() * sizeof(GifEncRec);
+    const size_t rec_bytes = quant ? (o_need - o_rec) + need.size() * 4 : delta ? (o_win - o_rec) + wins.size() * sizeof(GifDeltaRec)
+                                                                                : recs.size() * sizeof(GifEncRec);
     void *pin = nullptr, *token = nullptr;
     if (!rc) rc = stage_begin(rec_bytes, &pin, &token);
     if (!rc) {
@@ -112,6 +131,7 @@ int encode_group(const std::vector<EncPlan>& plans, const impgpu_image* const* a
     stage_hold(token, true);
     rc = lane_wait();
     if (!rc) std::memcpy(recs.data(), pin, recs.size() * sizeof(GifEncRec));
+    if (!rc && delta) std::memcpy(wins.data(), (const uint8_t*)pin + (o_win - o_rec), wins.size() * sizeof(GifDeltaRec));
     if (!rc && quant) std::memcpy(need.data(), (const uint8_t*)pin + (o_need - o_rec), need.size() * 4);
     stage_hold(token, false);
     if (rc) { dev_free(mem); return rc; }
@@ -130,6 +150,10 @@ int encode_group(const std::vector<EncPlan>& plans, const impgpu_image* const* a
         for (int q = 0; q < p.frames; q++) {
             const GifEncRec& r = r0[q];
             sane = sane && r.nkeys >= 1 && r.nkeys <= GIF_SET_MAX && gif_enc_framed_size(r.stream_bytes) <= fd[(size_t)(p.first + q)].out_cap;
+            if (delta) {
+                const GifDeltaRec& wr = wins[(size_t)(p.first + q)];
+                sane = sane && wr.ww >= 1 && wr.wh >= 1 && wr.x0 + wr.ww <= (uint32_t)albums[i]->w && wr.y0 + wr.wh <= (uint32_t)albums[i]->h;
+            }
             need += 8 + 10 + 1 + gif_enc_framed_size(r.stream_bytes) + (r.mode == GIF_ENC_LOCAL ? gif_enc_table_bytes(r.nkeys) : 0);
         }
         if (!sane) { codes[i] = IMP_ERROR_DEVICE; lens[i] = 0; set_error_text("gif encode: a stream outgrew its bound"); continue; }
@@ -174,7 +198,7 @@ int encode_group(const std::vector<EncPlan>& plans, const impgpu_image* const* a
                     pages.push_back(GifEncPage{&recs[f], (const uint32_t*)((const uint8_t*)pin + tab_at[tf]), (const uint8_t*)pin + str_at[f]});
                 }
                 gif_enc_write_file(outs[i], pages.data(), p.frames, albums[i]->w, albums[i]->h, time_ms ? time_ms[i] : nullptr,
-                                   dispose ? dispose[i] : nullptr, loop_counts[i]);
+                                   dispose ? dispose[i] : nullptr, loop_counts[i], delta ? wins.data() + p.first : nullptr);
             }
         }
         stage_hold(token, false);
@@ -204,6 +228,12 @@ int impgpu_gif_encode_host_ex(const unsigned char* const* frames, int count, int
     return gif_encode_host_ex(frames, count, width, height, channels, step, time_ms, dispose, loop_count, segment, flags, out, capacity, length);
 }
 
+int impgpu_gif_encode_host_ex2(const unsigned char* const* frames, int count, int width, int height, int channels, int step,
+                               const int* time_ms, const int* dispose, int loop_count, int segment, int flags, unsigned char* out,
+                               size_t capacity, size_t* length) {
+    return gif_encode_host_ex2(frames, count, width, height, channels, step, time_ms, dispose, loop_count, segment, flags, out, capacity, length);
+}
+
 int impgpu_gif_quantize_host(const unsigned char* frame, int width, int height, int channels, int step, unsigned char* table,
                              int* entries, int* transparent_index, unsigned char* indices) {
     return gif_quantize_host(frame, width, height, channels, step, table, entries, transparent_index, indices);
@@ -220,6 +250,14 @@ int impgpu_batch_encode_gif_ex(const impgpu_image* const* albums, const int* con
                                const size_t* capacities, size_t* lengths, int* codes, int* launches) {
     if (launches) *launches = 0;
     if (flags & ~IMPGPU_GIF_ENC_QUANTIZE) return IMP_ERROR_INVALID_ARGS;
+    return impgpu_batch_encode_gif_ex2(albums, time_ms, dispose, loop_counts, count, segment, flags, outs, capacities, lengths, codes, launches);
+}
+
+int impgpu_batch_encode_gif_ex2(const impgpu_image* const* albums, const int* const* time_ms, const int* const* dispose,
+                                const int* loop_counts, int count, int segment, int flags, unsigned char* const* outs,
+                                const size_t* capacities, size_t* lengths, int* codes, int* launches) {
+    if (launches) *launches = 0;
+    if (flags & ~(IMPGPU_GIF_ENC_QUANTIZE | IMPGPU_GIF_ENC_DELTA)) return IMP_ERROR_INVALID_ARGS;
     if (count < 0 || count > 256 || (count > 0 && (!albums || !loop_counts || !outs || !capacities || !lengths || !codes))) return IMP_ERROR_INVALID_ARGS;
     if (int rc = gif_enc_check_args(0, nullptr, 0, segment)) return rc;
     for (int i = 0; i < count; i++) lengths[i] = 0;
@@ -300,6 +338,17 @@ int impgpu_album_encode_gif_ex(const impgpu_image* album, const int* time_ms, co
     if (int rc = gif_enc_check_args(album->frames <= GIF_ENC_MAX_FRAMES ? album->frames : 0, dispose, loop_count, segment)) return rc;
     int code = IMP_OK;
     if (int rc = impgpu_batch_encode_gif_ex(&album, &time_ms, &dispose, &loop_count, 1, segment, flags, &out, &capacity, length, &code, nullptr)) return rc;
+    return code;
+}
+
+int impgpu_album_encode_gif_ex2(const impgpu_image* album, const int* time_ms, const int* dispose, int loop_count, int segment, int flags,
+                                unsigned char* out, size_t capacity, size_t* length) {
+    if (length) *length = 0;
+    if (flags & ~(IMPGPU_GIF_ENC_QUANTIZE | IMPGPU_GIF_ENC_DELTA)) return IMP_ERROR_INVALID_ARGS;
+    if (!album || !out || !length) return IMP_ERROR_INVALID_ARGS;
+    if (int rc = gif_enc_check_args(album->frames <= GIF_ENC_MAX_FRAMES ? album->frames : 0, dispose, loop_count, segment)) return rc;
+    int code = IMP_OK;
+    if (int rc = impgpu_batch_encode_gif_ex2(&album, &time_ms, &dispose, &loop_count, 1, segment, flags, &out, &capacity, length, &code, nullptr)) return rc;
     return code;
 }
 

@@ -18,7 +18,12 @@
 //           segments' bit strings (gif_enc_stream_byte) and stores them at their framed place behind the min_code_size
 //           byte, length bytes and terminator included (gif_enc_put_byte).
 //
-// Safe by construction: a probe loop ends after one trip round its table; gif_enc_drain_lane drops words at or past the
+// Under IMPGPU_GIF_ENC_DELTA a launch runs ahead of these -- DELTA: held bits and the bounds of what changed, per candidate
+// frame (gif_delta_lane, gif_delta_publish) -- and the others read a frame through its window and its held plane; see
+// "delta frames" below.
+//
+// Safe by construction: a probe loop ends after one trip round its table; a window read off the bounds lies inside its frame
+// (gif_delta_window); gif_enc_drain_lane drops words at or past the
 // slot's capacity; gif_enc_put_byte drops bytes at or past the region's.
 #pragma once
 #include <string.h>
@@ -426,8 +431,115 @@ IMP_GIF_HD uint32_t gif_q_index(const uint8_t* cmap, uint32_t nkeys, uint32_t ke
     return (key & GIF_KEY_TRANSPARENT) ? nkeys - 1u : cmap[gif_q_cell(key)];
 }
 
+// ---------------------------------------------------------------- delta frames (IMPGPU_GIF_ENC_DELTA; include/impgpu.h has the definition)
+// A CANDIDATE frame (its own disposal and its predecessor's are 0 or 1) is compared with the frame before it:
+//   DELTA   SETS' items, ahead of them: a lane compares its 16 keys with the previous frame's (gif_delta_lane), leaves the
+//           16 held bits as one word of the frame's held plane and grows the bounds of its pixels that are NOT held; a
+//           workgroup folds the bounds and one lane publishes them with four atomicMax (gif_delta_publish).  The bounds are
+//           kept as w - x, h - y, x + 1, y + 1, so that a zeroed record says "no such pixel" and every fold is a maximum.
+// The later launches read the window off the bounds (gif_delta_window) and a pixel's WRITTEN key through the held plane
+// (gif_delta_key_at): they never read the previous frame again.  SETS fills a second set per candidate, that of the written
+// keys (set A); the frame's own keys (set B) stay where they were.  TABLES makes the choice (gif_delta_needs_quant,
+// gif_delta_is_delta) and leaves the window every later launch and the container use (gif_delta_rec_fill).
+struct GifWindow { uint32_t x0, y0, ww, wh; };
+struct GifDeltaDesc { int prev; uint32_t held_off; };     // uploaded, per frame: the frame before it when it is a candidate, else -1; its held plane, in words
+struct GifDeltaRec {
+    uint32_t raw[4];                                       // DELTA: the maxima of w - x, h - y, x + 1, y + 1 over the pixels not held; 0: there is none
+    uint32_t x0, y0, ww, wh;                               // TABLES: the window written (the whole frame unless `delta`)
+    uint32_t delta;                                        // 1: a delta frame
+    uint32_t total;                                        // ww * wh: the pixels of the frame's stream
+    uint32_t pad[2];
+};
+IMP_GIF_HD void gif_max(uint32_t* p, uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    atomicMax(p, v);
+#else
+    if (v > *p) *p = v;
+#endif
+}
+// the smallest rectangle round the pixels not held; 1 x 1 at 0,0 when every pixel is held
+IMP_GIF_HD GifWindow gif_delta_window(const uint32_t* raw, uint32_t w, uint32_t h) {
+    GifWindow W{0u, 0u, 1u, 1u};
+    if (raw[2] == 0u || raw[3] == 0u || raw[0] == 0u || raw[1] == 0u || raw[0] > w || raw[1] > h) return W;
+    const uint32_t x0 = w - raw[0], y0 = h - raw[1];
+    if (raw[2] <= x0 || raw[3] <= y0 || raw[2] > w || raw[3] > h) return W;
+    W.x0 = x0; W.y0 = y0; W.ww = raw[2] - x0; W.wh = raw[3] - y0;
+    return W;
+}
+IMP_GIF_HD bool gif_window_has(const GifWindow& W, uint32_t x, uint32_t y) { return x - W.x0 < W.ww && y - W.y0 < W.wh; }
+IMP_GIF_HD uint32_t gif_held_at(const uint16_t* held, uint32_t pos) { return ((uint32_t)held[pos >> 4] >> (pos & 15u)) & 1u; }
+// held: the key is a colour and the pixel under it in the previous frame has the same key
+IMP_GIF_HD bool gif_delta_held(uint32_t key, uint32_t prev) { return key == prev && !(key & GIF_KEY_TRANSPARENT); }
+// A lane's 16 pixels from frame position p0 (a multiple of 16) of `fr` over `pv`, a frame of the same geometry: the held
+// bits, bit j for pixel p0 + j; b[0 .. 3] grow by the pixels that are not held.
+IMP_GIF_HD uint32_t gif_delta_lane(const GifEncFrame& fr, const GifEncFrame& pv, uint32_t p0, uint32_t total, uint32_t* b) {
+    uint32_t mask = 0;
+    if (p0 >= total) return mask;
+    uint32_t y = p0 / (uint32_t)fr.w, x = p0 - y * (uint32_t)fr.w;
+    for (uint32_t j = 0; j < 16u && p0 + j < total; j++) {
+        const size_t at = (size_t)y * (size_t)fr.step + (size_t)x * (size_t)fr.c, pat = (size_t)y * (size_t)pv.step + (size_t)x * (size_t)pv.c;
+        if (gif_delta_held(gif_enc_key(fr.src + at, fr.c, fr.wide != 0), gif_enc_key(pv.src + pat, pv.c, pv.wide != 0))) {
+            mask |= 1u << j;
+        } else {
+            const uint32_t nx = (uint32_t)fr.w - x, ny = (uint32_t)fr.h - y;
+            b[0] = nx > b[0] ? nx : b[0]; b[1] = ny > b[1] ? ny : b[1];
+            b[2] = x + 1u > b[2] ? x + 1u : b[2]; b[3] = y + 1u > b[3] ? y + 1u : b[3];
+        }
+        if (++x == (uint32_t)fr.w) { x = 0; y++; }
+    }
+    return mask;
+}
+IMP_GIF_HD void gif_delta_publish(GifDeltaRec* r, const uint32_t* b) {
+    if (b[2] == 0u) return;
+    for (int i = 0; i < 4; i++) gif_max(&r->raw[i], b[i]);
+}
+// the key frame position `pos` (= y * w + x) adds to the set of WRITTEN keys: its own when it is not held, "transparent"
+// when it is held inside the window, nothing (0) outside it
+IMP_GIF_HD uint32_t gif_delta_set_key(const GifEncFrame& fr, const GifWindow& W, const uint16_t* held, uint32_t pos) {
+    const uint32_t y = pos / (uint32_t)fr.w, x = pos - y * (uint32_t)fr.w;
+    if (!gif_held_at(held, pos)) return gif_enc_key(fr.src + (size_t)y * (size_t)fr.step + (size_t)x * (size_t)fr.c, fr.c, fr.wide != 0);
+    return gif_window_has(W, x, y) ? GIF_KEY_TRANSPARENT : 0u;
+}
+// the written key of WINDOW position `wpos` (raster order inside W)
+IMP_GIF_HD uint32_t gif_delta_key_at(const GifEncFrame& fr, const GifWindow& W, const uint16_t* held, uint32_t wpos) {
+    const uint32_t wy = wpos / W.ww, y = W.y0 + wy, x = W.x0 + (wpos - wy * W.ww);
+    if (held && gif_held_at(held, y * (uint32_t)fr.w + x)) return GIF_KEY_TRANSPARENT;
+    return gif_enc_key(fr.src + (size_t)y * (size_t)fr.step + (size_t)x * (size_t)fr.c, fr.c, fr.wide != 0);
+}
+// the choice, from "the written keys outgrew a table" and "the frame's own keys did"
+IMP_GIF_HD bool gif_delta_needs_quant(bool cand, bool a_over, bool b_over) { return cand ? a_over && b_over : b_over; }
+IMP_GIF_HD bool gif_delta_is_delta(bool cand, bool a_over, bool b_over) { return cand && (!a_over || b_over); }
+IMP_GIF_HD void gif_delta_rec_fill(GifDeltaRec* r, bool delta, uint32_t w, uint32_t h) {
+    const GifWindow W = delta ? gif_delta_window(r->raw, w, h) : GifWindow{0u, 0u, w, h};
+    r->x0 = W.x0; r->y0 = W.y0; r->ww = W.ww; r->wh = W.wh;
+    r->delta = delta ? 1u : 0u;
+    r->total = W.ww * W.wh;
+}
+IMP_GIF_HD GifWindow gif_delta_rec_window(const GifDeltaRec& r) { return GifWindow{r.x0, r.y0, r.ww, r.wh}; }
+// gif_q_lane_pixels for a delta frame: the lane's 16 FRAME positions from p0; the pixels that are neither held nor
+// transparent are summed; true: one of them is transparent, or held inside the window
+IMP_GIF_HD bool gif_q_lane_pixels_delta(const GifEncFrame& fr, const GifWindow& W, const uint16_t* held, uint32_t p0, uint32_t total,
+                                        GifQuantWg* t, uint32_t* hist) {
+    uint32_t cur = GIF_Q_NONE, n = 0, r = 0, g = 0, b = 0;
+    bool trans = false;
+    for (uint32_t j = 0; j < 16u; j++) {
+        if (p0 + j >= total) break;
+        const uint32_t key = gif_delta_set_key(fr, W, held, p0 + j);
+        if (key == 0u) continue;
+        if (key & GIF_KEY_TRANSPARENT) { trans = true; continue; }
+        const uint32_t cell = gif_q_cell(key);
+        if (cell != cur) {
+            if (n) gif_q_wg_add(t, hist, cur, n, r, g, b);
+            cur = cell; n = 0; r = 0; g = 0; b = 0;
+        }
+        n++; r += (key >> 16) & 255u; g += (key >> 8) & 255u; b += key & 255u;
+    }
+    if (n) gif_q_wg_add(t, hist, cur, n, r, g, b);
+    return trans;
+}
+
 // ---------------------------------------------------------------- a segment's LZW
-constexpr int GIF_ENC_SLOTS = 8192;                       // at most 3838 entries between two clears: under half full
+constexpr int GIF_ENC_SLOTS = 8192;                      // at most 3838 entries between two clears: under half full
 constexpr uint32_t GIF_ENC_EMPTY = 0xFFFFFFFFu;            // (no entry looks like it: code 4095 never has prefix 4095)
 constexpr int GIF_ENC_CHUNK = 1024;                        // indices staged per load: 16 bytes a lane
 constexpr int GIF_ENC_BATCH = 64;                          // a batch is due at this many codes ...
@@ -613,6 +725,12 @@ struct GifEncDev {
     uint32_t* hist;
     uint8_t* cmaps;
     uint32_t* album_need;                                  // per album: 0, or the slots it needed and did not get (it is deferred)
+    // delta frames (flags & IMPGPU_GIF_ENC_DELTA; null otherwise): per frame its candidate word and held plane, its window
+    // record (behind the records, zeroed with them) and the set of its written keys
+    const GifDeltaDesc* ddesc;
+    GifDeltaRec* wins;
+    uint16_t* held;
+    GifColourSet* sets_a;
 };
 constexpr size_t GIF_Q_SLOT_BYTES = (size_t)GIF_Q_HIST_WORDS * 4 + GIF_Q_CELLS + 8;
 
@@ -665,8 +783,9 @@ inline uint8_t* gif_enc_put_table(uint8_t* p, const uint32_t* keys, uint32_t nke
 inline uint8_t* gif_enc_put16(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); return p + 2; }
 // the file of gif_enc_file_size bytes: GIF89a, the screen, NETSCAPE2.0, then per frame a graphic control extension, the
 // image descriptor (and local table), min_code_size and the framed stream; the trailer
+// (wins: the frames' windows under IMPGPU_GIF_ENC_DELTA; null: every frame is w x h at 0,0)
 inline void gif_enc_write_file(uint8_t* p, const GifEncPage* pages, int count, int w, int h, const int* time_ms, const int* dispose,
-                               int loop_count) {
+                               int loop_count, const GifDeltaRec* wins = nullptr) {
     const bool global = pages[0].rec->mode == GIF_ENC_GLOBAL;
     memcpy(p, "GIF89a", 6); p += 6;
     p = gif_enc_put16(p, (uint32_t)w); p = gif_enc_put16(p, (uint32_t)h);
@@ -688,7 +807,8 @@ inline void gif_enc_write_file(uint8_t* p, const GifEncPage* pages, int count, i
         *p++ = (uint8_t)(r.has_trans ? r.trans_index : 0u);
         *p++ = 0;
         *p++ = 0x2C;
-        p = gif_enc_put16(p, 0); p = gif_enc_put16(p, 0); p = gif_enc_put16(p, (uint32_t)w); p = gif_enc_put16(p, (uint32_t)h);
+        if (wins) { p = gif_enc_put16(p, wins[i].x0); p = gif_enc_put16(p, wins[i].y0); p = gif_enc_put16(p, wins[i].ww); p = gif_enc_put16(p, wins[i].wh); }
+        else { p = gif_enc_put16(p, 0); p = gif_enc_put16(p, 0); p = gif_enc_put16(p, (uint32_t)w); p = gif_enc_put16(p, (uint32_t)h); }
         *p++ = (uint8_t)(global ? 0u : 0x80u | size_bits(r.nkeys));
         if (!global) p = gif_enc_put_table(p, pages[i].table, r.nkeys);
         *p++ = (uint8_t)r.mcs;
@@ -700,7 +820,9 @@ inline void gif_enc_write_file(uint8_t* p, const GifEncPage* pages, int count, i
 
 // ---------------------------------------------------------------- the host encoder: the launches, one lane after the other
 // HIST + CUT for one frame: its table (256 words), the record's nkeys / has_trans / quant, its cell -> index table
-inline void host_quantize(const GifEncFrame& fr, uint32_t total, GifEncRec* rec, uint32_t* tab, uint8_t* cmap) {
+// (held and W: a delta frame -- the pixels that are neither held nor transparent, T from the window)
+inline void host_quantize(const GifEncFrame& fr, uint32_t total, GifEncRec* rec, uint32_t* tab, uint8_t* cmap, const uint16_t* held = nullptr,
+                          const GifWindow* W = nullptr) {
     std::vector<uint32_t> hist((size_t)GIF_Q_HIST_WORDS, 0u), S((size_t)GIF_Q_CELLS);
     std::vector<GifQuantWg> wg(1);
     std::vector<GifQuantCut> cut(1);
@@ -709,7 +831,8 @@ inline void host_quantize(const GifEncFrame& fr, uint32_t total, GifEncRec* rec,
     for (uint32_t b0 = 0; b0 < total; b0 += GIF_ENC_PX_BLOCK) {                      // a workgroup of k_gif_enc_hist
         for (int lane = 0; lane < 256; lane++) gif_q_wg_clear_lane(wg.data(), lane);
         for (uint32_t tid = 0; tid < 256u; tid++)
-            if (gif_q_lane_pixels(fr, b0 + tid * 16u, total, wg.data(), hist.data())) T = 1u;
+            if (held ? gif_q_lane_pixels_delta(fr, *W, held, b0 + tid * 16u, total, wg.data(), hist.data())
+                     : gif_q_lane_pixels(fr, b0 + tid * 16u, total, wg.data(), hist.data())) T = 1u;
         for (int i = 0; i < GIF_Q_WG_SLOTS; i++) gif_q_wg_flush_slot(wg.data(), hist.data(), i);
     }
     std::copy(hist.begin(), hist.begin() + GIF_Q_CELLS, S.begin());                  // k_gif_enc_cut
@@ -737,38 +860,73 @@ inline void host_quantize(const GifEncFrame& fr, uint32_t total, GifEncRec* rec,
 
 inline int gif_frame_wide(const unsigned char* frame, int c, int step) { return (c == 4 && (((uintptr_t)frame | (uintptr_t)step) & 3) == 0) ? 1 : 0; }
 
-// SETS + TABLES (+ HIST + CUT under IMPGPU_GIF_ENC_QUANTIZE) for one album; false: refused.  cmaps: GIF_Q_CELLS bytes a frame
-inline bool host_tables(const unsigned char* const* frames, int count, int w, int h, int c, int step, int flags, std::vector<GifEncRec>* recs,
-                 std::vector<uint32_t>* tabs, std::vector<uint8_t>* cmaps) {
-    const uint32_t total = (uint32_t)w * (uint32_t)h;
-    bool quant = false;
-    std::vector<GifColourSet> sets((size_t)count);
+// a frame's walk through k_gif_enc_sets: its own keys into `fs`, or (held) its written keys
+inline void host_set(const GifEncFrame& fr, uint32_t total, GifColourSet* fs, const uint16_t* held, const GifWindow* W) {
     std::vector<uint32_t> lset(GIF_SET_SLOTS);
-    for (int f = 0; f < count; f++) {
-        memset(&sets[(size_t)f], 0, sizeof(GifColourSet));
-        const GifEncFrame fr{frames[f], w, h, c, step, (c == 4 && (((uintptr_t)frames[f] | (uintptr_t)step) & 3) == 0) ? 1 : 0};
-        for (uint32_t b0 = 0; b0 < total; b0 += GIF_ENC_PX_BLOCK) {                  // a workgroup of k_gif_enc_sets
-            if (sets[(size_t)f].overflow) break;
-            std::fill(lset.begin(), lset.end(), 0u);
-            bool full = false;
-            uint32_t lcount = 0;
-            for (uint32_t tid = 0; tid < 256u; tid++) {
-                uint32_t last = 0;
-                for (uint32_t j = 0; j < 16u; j++) {
-                    const uint32_t pos = b0 + tid * 16u + j;
-                    if (pos >= total || full) break;
-                    const uint32_t key = gif_enc_key_at(fr, pos);
-                    if (key == last) continue;
-                    last = key;
-                    if (gif_set_count(lset.data(), &lcount, key)) full = true;
-                }
+    memset(fs, 0, sizeof(GifColourSet));
+    for (uint32_t b0 = 0; b0 < total; b0 += GIF_ENC_PX_BLOCK) {                      // a workgroup of k_gif_enc_sets
+        if (fs->overflow) break;
+        std::fill(lset.begin(), lset.end(), 0u);
+        bool full = false;
+        uint32_t lcount = 0;
+        for (uint32_t tid = 0; tid < 256u; tid++) {
+            uint32_t last = 0;
+            for (uint32_t j = 0; j < 16u; j++) {
+                const uint32_t pos = b0 + tid * 16u + j;
+                if (pos >= total || full) break;
+                const uint32_t key = held ? gif_delta_set_key(fr, *W, held, pos) : gif_enc_key_at(fr, pos);
+                if (key == last || key == 0u) continue;
+                last = key;
+                if (gif_set_count(lset.data(), &lcount, key)) full = true;
             }
-            if (full) { sets[(size_t)f].overflow = 1u; break; }
-            for (int i = 0; i < GIF_SET_SLOTS; i++)
-                if (lset[(size_t)i]) gif_frame_set_add(&sets[(size_t)f], lset[(size_t)i]);
         }
-        if (sets[(size_t)f].overflow && !(flags & IMPGPU_GIF_ENC_QUANTIZE)) return false;
-        quant = quant || sets[(size_t)f].overflow != 0u;
+        if (full) { fs->overflow = 1u; break; }
+        for (int i = 0; i < GIF_SET_SLOTS; i++)
+            if (lset[(size_t)i]) gif_frame_set_add(fs, lset[(size_t)i]);
+    }
+}
+
+// k_gif_enc_delta for one candidate frame: its held plane and the bounds in its record
+inline void host_delta(const GifEncFrame& fr, const GifEncFrame& pv, uint32_t total, std::vector<uint16_t>* held, GifDeltaRec* rec) {
+    held->assign(((size_t)total + 15) / 16, 0);
+    for (uint32_t b0 = 0; b0 < total; b0 += GIF_ENC_PX_BLOCK) {
+        uint32_t b[4] = {0u, 0u, 0u, 0u};
+        for (uint32_t tid = 0; tid < 256u; tid++) {
+            const uint32_t p0 = b0 + tid * 16u;
+            if (p0 < total) (*held)[p0 >> 4] = (uint16_t)gif_delta_lane(fr, pv, p0, total, b);
+        }
+        gif_delta_publish(rec, b);
+    }
+}
+
+// DELTA + SETS + TABLES (+ HIST + CUT under IMPGPU_GIF_ENC_QUANTIZE) for one album; false: refused.  cmaps: GIF_Q_CELLS bytes a
+// frame.  Under IMPGPU_GIF_ENC_DELTA (`dispose` counts then, null = all 0): wins and held, per frame
+inline bool host_tables(const unsigned char* const* frames, int count, int w, int h, int c, int step, int flags, const int* dispose,
+                        std::vector<GifEncRec>* recs, std::vector<uint32_t>* tabs, std::vector<uint8_t>* cmaps, std::vector<GifDeltaRec>* wins,
+                        std::vector<std::vector<uint16_t>>* held) {
+    const uint32_t total = (uint32_t)w * (uint32_t)h;
+    const bool delta = (flags & IMPGPU_GIF_ENC_DELTA) != 0;
+    bool quant = false;
+    std::vector<GifColourSet> sets((size_t)count), sets_a(delta ? (size_t)count : 0);
+    std::vector<char> needs((size_t)count, 0), isd((size_t)count, 0);
+    if (delta) { wins->assign((size_t)count, GifDeltaRec{}); held->assign((size_t)count, std::vector<uint16_t>()); }
+    auto frame_of = [&](int f) { return GifEncFrame{frames[f], w, h, c, step, gif_frame_wide(frames[f], c, step)}; };
+    auto keeps = [&](int f) { const int d = dispose ? dispose[f] : 0; return d == 0 || d == 1; };
+    for (int f = 0; f < count; f++) {
+        const GifEncFrame fr = frame_of(f);
+        const bool cand = delta && f >= 1 && keeps(f - 1) && keeps(f);
+        host_set(fr, total, &sets[(size_t)f], nullptr, nullptr);
+        bool a_over = false;
+        if (cand) {
+            host_delta(fr, frame_of(f - 1), total, &(*held)[(size_t)f], &(*wins)[(size_t)f]);
+            const GifWindow W = gif_delta_window((*wins)[(size_t)f].raw, (uint32_t)w, (uint32_t)h);
+            host_set(fr, total, &sets_a[(size_t)f], (*held)[(size_t)f].data(), &W);
+            a_over = sets_a[(size_t)f].overflow != 0u;
+        }
+        needs[(size_t)f] = gif_delta_needs_quant(cand, a_over, sets[(size_t)f].overflow != 0u) ? 1 : 0;
+        isd[(size_t)f] = gif_delta_is_delta(cand, a_over, sets[(size_t)f].overflow != 0u) ? 1 : 0;
+        if (needs[(size_t)f] && !(flags & IMPGPU_GIF_ENC_QUANTIZE)) return false;
+        quant = quant || needs[(size_t)f];
     }
     recs->assign((size_t)count, GifEncRec{});
     tabs->assign((size_t)count * 256, 0u);
@@ -779,14 +937,17 @@ inline bool host_tables(const unsigned char* const* frames, int count, int w, in
         for (uint32_t i = 0; i < (uint32_t)list.size(); i++) tab[gif_rank(list.data(), (uint32_t)list.size(), i)] = list[i];
     };
     for (int f = 0; f < count; f++) {                                                // k_gif_enc_tables
-        if (sets[(size_t)f].overflow) {
-            const GifEncFrame fr{frames[f], w, h, c, step, gif_frame_wide(frames[f], c, step)};
-            host_quantize(fr, total, &(*recs)[(size_t)f], tabs->data() + (size_t)f * 256, cmaps->data() + (size_t)f * GIF_Q_CELLS);
+        if (delta) gif_delta_rec_fill(&(*wins)[(size_t)f], isd[(size_t)f] != 0, (uint32_t)w, (uint32_t)h);
+        if (needs[(size_t)f]) {
+            const GifWindow W = delta ? gif_delta_rec_window((*wins)[(size_t)f]) : GifWindow{};
+            host_quantize(frame_of(f), total, &(*recs)[(size_t)f], tabs->data() + (size_t)f * 256, cmaps->data() + (size_t)f * GIF_Q_CELLS,
+                          isd[(size_t)f] ? (*held)[(size_t)f].data() : nullptr, &W);
             continue;
         }
+        const GifColourSet& fs = isd[(size_t)f] ? sets_a[(size_t)f] : sets[(size_t)f];
         list.clear();
         for (int i = 0; i < GIF_SET_SLOTS; i++)
-            if (sets[(size_t)f].slot[i]) list.push_back(sets[(size_t)f].slot[i]);
+            if (fs.slot[i]) list.push_back(fs.slot[i]);
         sort_out(tabs->data() + (size_t)f * 256);
         const bool ufull = ucount > GIF_SET_MAX;
         for (uint32_t k : list) {
@@ -824,21 +985,28 @@ inline void host_flush(GifEncMem* m, GifEncState* e, int mcs, uint32_t* words, u
 }
 
 // INDEX + LZW + PACK for one frame: its framed stream; rec->stream_bytes
+// (win: the frame's window under IMPGPU_GIF_ENC_DELTA, held: a delta frame's held plane; the segments are planned for the whole
+// frame, as the device's are, and those behind the window's last pixel stay empty)
 inline void host_frame(const unsigned char* frame, int w, int h, int c, int step, uint32_t segment, GifEncRec* rec, const uint32_t* table,
-                const uint8_t* cmap, GifEncMem* m, std::vector<uint8_t>* framed) {
-    const uint32_t total = (uint32_t)w * (uint32_t)h;
+                const uint8_t* cmap, GifEncMem* m, std::vector<uint8_t>* framed, const GifDeltaRec* win = nullptr, const uint16_t* held = nullptr) {
+    const uint32_t whole = (uint32_t)w * (uint32_t)h, total = win ? win->total : whole;
+    const GifWindow W = win ? gif_delta_rec_window(*win) : GifWindow{0u, 0u, (uint32_t)w, (uint32_t)h};
     const GifEncFrame fr{frame, w, h, c, step, (c == 4 && (((uintptr_t)frame | (uintptr_t)step) & 3) == 0) ? 1 : 0};
     uint32_t tab[256];
     for (uint32_t i = 0; i < 256u; i++) tab[i] = i < rec->nkeys ? table[i] : 0xFFFFFFFFu;
     std::vector<uint8_t> plane(total);
-    for (uint32_t pos = 0; pos < total; pos++)
-        plane[pos] = (uint8_t)(rec->quant ? gif_q_index(cmap, rec->nkeys, gif_enc_key_at(fr, pos)) : gif_table_find(tab, gif_enc_key_at(fr, pos)));
+    for (uint32_t pos = 0; pos < total; pos++) {
+        const uint32_t key = win ? gif_delta_key_at(fr, W, win->delta ? held : nullptr, pos) : gif_enc_key_at(fr, pos);
+        plane[pos] = (uint8_t)(rec->quant ? gif_q_index(cmap, rec->nkeys, key) : gif_table_find(tab, key));
+    }
     const int mcs = (int)rec->mcs;
-    const uint32_t nseg = gif_enc_segments(total, segment), cap = gif_enc_slot_words(segment < total ? segment : total);
+    const uint32_t nseg = gif_enc_segments(whole, segment), cap = gif_enc_slot_words(segment < whole ? segment : whole);
     std::vector<uint32_t> scratch((size_t)nseg * cap, 0u), segbits(nseg);
     for (uint32_t k = 0; k < nseg; k++) {                                            // k_gif_enc_lzw
         uint32_t* words = scratch.data() + (size_t)k * cap;
-        const uint32_t begin = k * segment, end = total - begin < segment ? total : begin + segment;
+        const uint32_t begin = k * segment;
+        if (begin >= total) { segbits[k] = 0u; continue; }
+        const uint32_t end = total - begin <= segment ? total : begin + segment;
         GifEncState e;
         gif_enc_start(&e, mcs);
         for (int lane = 0; lane < GIF_LANES; lane++) gif_enc_rewind_lane(m, 0u, lane);
@@ -850,7 +1018,7 @@ inline void host_frame(const unsigned char* frame, int w, int h, int c, int step
         }
         for (uint32_t i = begin; i < end; i++)
             if (gif_enc_step(m, &e, mcs, plane[i])) host_flush(m, &e, mcs, words, cap);
-        gif_enc_finish(m, &e, mcs, k + 1u == nseg);
+        gif_enc_finish(m, &e, mcs, end == total);
         host_flush(m, &e, mcs, words, cap);
         gif_enc_last_word(m, e, words, cap);
         segbits[k] = e.s.bitpos;
@@ -867,11 +1035,11 @@ inline void host_frame(const unsigned char* frame, int w, int h, int c, int step
     }
 }
 
-// impgpu_gif_encode_host_ex
-inline int gif_encode_host_ex(const unsigned char* const* frames, int count, int width, int height, int channels, int step, const int* time_ms,
-                              const int* dispose, int loop_count, int segment, int flags, unsigned char* out, size_t capacity, size_t* length) {
+// impgpu_gif_encode_host_ex2
+inline int gif_encode_host_ex2(const unsigned char* const* frames, int count, int width, int height, int channels, int step, const int* time_ms,
+                               const int* dispose, int loop_count, int segment, int flags, unsigned char* out, size_t capacity, size_t* length) {
     if (length) *length = 0;
-    if (flags & ~IMPGPU_GIF_ENC_QUANTIZE) return IMP_ERROR_INVALID_ARGS;
+    if (flags & ~(IMPGPU_GIF_ENC_QUANTIZE | IMPGPU_GIF_ENC_DELTA)) return IMP_ERROR_INVALID_ARGS;
     if (!frames || !length || count <= 0) return IMP_ERROR_INVALID_ARGS;
     if (int rc = gif_enc_check_args(count <= GIF_ENC_MAX_FRAMES ? count : 0, dispose, loop_count, segment)) return rc;
     if (int rc = gif_enc_check_geometry(width, height, channels, count)) return rc;
@@ -882,20 +1050,31 @@ inline int gif_encode_host_ex(const unsigned char* const* frames, int count, int
     std::vector<GifEncRec> recs;
     std::vector<uint32_t> tabs;
     std::vector<uint8_t> cmaps;
-    if (!host_tables(frames, count, width, height, channels, step, flags, &recs, &tabs, &cmaps)) return IMP_ERROR_UNSUPPORTED;
+    const bool delta = (flags & IMPGPU_GIF_ENC_DELTA) != 0;
+    std::vector<GifDeltaRec> wins;
+    std::vector<std::vector<uint16_t>> held;
+    if (!host_tables(frames, count, width, height, channels, step, flags, dispose, &recs, &tabs, &cmaps, &wins, &held)) return IMP_ERROR_UNSUPPORTED;
     std::vector<std::vector<uint8_t>> framed((size_t)count);
     std::vector<GifEncMem> mem(1);
     for (int f = 0; f < count; f++)
         host_frame(frames[f], width, height, channels, step, seg, &recs[(size_t)f], tabs.data() + (size_t)recs[(size_t)f].table_frame * 256,
-                   recs[(size_t)f].quant ? cmaps.data() + (size_t)f * GIF_Q_CELLS : nullptr, mem.data(), &framed[(size_t)f]);
+                   recs[(size_t)f].quant ? cmaps.data() + (size_t)f * GIF_Q_CELLS : nullptr, mem.data(), &framed[(size_t)f],
+                   delta ? &wins[(size_t)f] : nullptr, delta ? held[(size_t)f].data() : nullptr);
     std::vector<GifEncPage> pages;
     for (int f = 0; f < count; f++)
         pages.push_back(GifEncPage{&recs[(size_t)f], tabs.data() + (size_t)recs[(size_t)f].table_frame * 256, framed[(size_t)f].data()});
     const size_t need = gif_enc_file_size(pages.data(), count, loop_count);
     *length = need;
     if (!out || capacity < need) return IMP_ERROR_MALLOC_FAILED;
-    gif_enc_write_file(out, pages.data(), count, width, height, time_ms, dispose, loop_count);
+    gif_enc_write_file(out, pages.data(), count, width, height, time_ms, dispose, loop_count, delta ? wins.data() : nullptr);
     return IMP_OK;
+}
+// impgpu_gif_encode_host_ex: no bit but IMPGPU_GIF_ENC_QUANTIZE
+inline int gif_encode_host_ex(const unsigned char* const* frames, int count, int width, int height, int channels, int step, const int* time_ms,
+                              const int* dispose, int loop_count, int segment, int flags, unsigned char* out, size_t capacity, size_t* length) {
+    if (length) *length = 0;
+    if (flags & ~IMPGPU_GIF_ENC_QUANTIZE) return IMP_ERROR_INVALID_ARGS;
+    return gif_encode_host_ex2(frames, count, width, height, channels, step, time_ms, dispose, loop_count, segment, flags, out, capacity, length);
 }
 // impgpu_gif_encode_host
 inline int gif_encode_host(const unsigned char* const* frames, int count, int width, int height, int channels, int step, const int* time_ms,

@@ -1,10 +1,12 @@
-// imp_gif_enc.hip -- the five launches that turn the albums of a call into GIF streams (impgpu_batch_encode_gif):
+// imp_gif_enc.hip -- the launches that turn the albums of a call into GIF streams (impgpu_batch_encode_gif):
 // k_gif_enc_sets, _tables, _index, _lzw and _pack.  The lanes' logic is imp_gif_enc.h's, which the host encoder
 // (impgpu_gif_encode_host) runs too.  Each launch reads what the one before wrote across the kernel boundary of one
 // stream; no wavefront waits for another workgroup.  Workgroup b of a launch finds its work in an item table
 // (GifEncItem: a frame of the call and the part of it), so the launches do not depend on how many albums there are.
 // Under IMPGPU_GIF_ENC_QUANTIZE three launches more run between the sets and the tables -- k_gif_enc_claim, _hist and _cut:
 // the frames past 256 colours get a median-cut table -- and k_gif_enc_index reads such a frame's cell -> index table.
+// Under IMPGPU_GIF_ENC_DELTA one launch more runs ahead of the sets -- k_gif_enc_delta: the held planes and the bounds of what
+// changed -- and the later launches are their DELTA instantiations; without the bit they are the ones they were.
 #include "imp_internal.h"
 #include "imp_gif_enc.h"
 
@@ -12,26 +14,72 @@ namespace imp {
 
 __device__ __forceinline__ GifEncFrame gif_enc_frame_of(const GifEncFrameDesc& f) { return GifEncFrame{f.src, f.w, f.h, f.c, f.step, f.wide}; }
 
+// DELTA (under IMPGPU_GIF_ENC_DELTA, ahead of SETS, on its items): a candidate frame against the frame before it.  A lane
+// leaves the held bits of its 16 pixels as one word of the frame's held plane; the bounds of the pixels that are not held
+// are folded across the wave with six exchanges, across the workgroup's four waves in LDS, and lane 0 publishes them.
+__global__ __launch_bounds__(256) void k_gif_enc_delta(GifEncDev D) {
+    __shared__ uint32_t wb[4][4];
+    const GifEncItem it = D.px_items[blockIdx.x];
+    const GifDeltaDesc dd = D.ddesc[it.frame];
+    if (dd.prev < 0) return;
+    const GifEncFrameDesc& f = D.frames[it.frame];
+    const int tid = (int)threadIdx.x;
+    const GifEncFrame fr = gif_enc_frame_of(f), pv = gif_enc_frame_of(D.frames[dd.prev]);
+    const uint32_t p0 = (uint32_t)it.k * GIF_ENC_PX_BLOCK + (uint32_t)tid * 16u;
+    uint32_t b[4] = {0u, 0u, 0u, 0u};
+    const uint32_t mask = gif_delta_lane(fr, pv, p0, f.total, b);
+    if (p0 < f.total) D.held[(size_t)dd.held_off + (p0 >> 4)] = (uint16_t)mask;
+    for (int i = 0; i < 4; i++) {
+        uint32_t x = b[i];
+        for (int d = 32; d; d >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)x, d); x = o > x ? o : x; }
+        if ((tid & 63) == 0) wb[tid >> 6][i] = x;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (int i = 0; i < 4; i++) {
+            uint32_t x = wb[0][i];
+            for (int w = 1; w < 4; w++) x = wb[w][i] > x ? wb[w][i] : x;
+            b[i] = x;
+        }
+        gif_delta_publish(&D.wins[it.frame], b);
+    }
+}
+
+// what TABLES, CLAIM and HIST ask of a frame under IMPGPU_GIF_ENC_DELTA: a candidate?  did its written keys (set A), did
+// its own keys (set B) outgrow a table?
+struct GifDeltaState { bool cand, a_over, b_over; };
+__device__ __forceinline__ GifDeltaState gif_delta_state(const GifEncDev& D, int f) {
+    const bool cand = D.ddesc[f].prev >= 0;
+    return GifDeltaState{cand, cand && D.sets_a[f].overflow != 0u, D.sets[f].overflow != 0u};
+}
+template <bool DELTA>
+__device__ __forceinline__ bool gif_enc_needs_quant(const GifEncDev& D, int f) {
+    if (!DELTA) return D.sets[f].overflow != 0u;
+    const GifDeltaState st = gif_delta_state(D, f);
+    return gif_delta_needs_quant(st.cand, st.a_over, st.b_over);
+}
+
 // SETS: 4096 pixels a workgroup, 16 consecutive ones a lane (a lane skips a key equal to its last one).  The LDS set
 // holds 1024 keys: a workgroup that fills it has seen four times what any table takes, and says so in the frame's flag.
-__global__ __launch_bounds__(256) void k_gif_enc_sets(GifEncDev D) {
-    __shared__ uint32_t lset[GIF_SET_SLOTS];
-    __shared__ uint32_t flag[3];
-    const GifEncItem it = D.px_items[blockIdx.x];
+// WRITTEN: a candidate's written keys (through the held plane and the window) into its set A, not its own into set B.
+template <bool WRITTEN>
+__device__ __forceinline__ void gif_enc_sets_pass(const GifEncDev& D, const GifEncItem it, uint32_t* lset, uint32_t* flag) {
     const GifEncFrameDesc& f = D.frames[it.frame];
-    GifColourSet* fs = &D.sets[it.frame];
+    GifColourSet* fs = WRITTEN ? &D.sets_a[it.frame] : &D.sets[it.frame];
     const int tid = (int)threadIdx.x;
     for (int i = tid; i < GIF_SET_SLOTS; i += 256) lset[i] = 0;
     if (tid == 0) { flag[0] = *(volatile uint32_t*)&fs->overflow; flag[1] = 0; flag[2] = 0; }
     __syncthreads();
     if (flag[0]) return;                                               // the frame is lost already
     const GifEncFrame fr = gif_enc_frame_of(f);
+    const GifWindow W = WRITTEN ? gif_delta_window(D.wins[it.frame].raw, (uint32_t)f.w, (uint32_t)f.h) : GifWindow{};
+    const uint16_t* held = WRITTEN ? D.held + D.ddesc[it.frame].held_off : nullptr;
     const uint32_t p0 = (uint32_t)it.k * GIF_ENC_PX_BLOCK + (uint32_t)tid * 16u;
     uint32_t last = 0;
     for (uint32_t j = 0; j < 16u; j++) {
         if (p0 + j >= f.total || *(volatile uint32_t*)&flag[1]) break;
-        const uint32_t key = gif_enc_key_at(fr, p0 + j);
-        if (key == last) continue;
+        const uint32_t key = WRITTEN ? gif_delta_set_key(fr, W, held, p0 + j) : gif_enc_key_at(fr, p0 + j);
+        if (key == last || (WRITTEN && key == 0u)) continue;
         last = key;
         if (gif_set_count(lset, &flag[2], key)) flag[1] = 1;           // (a photo stops here, long before its keys crowd the set)
     }
@@ -43,6 +91,18 @@ __global__ __launch_bounds__(256) void k_gif_enc_sets(GifEncDev D) {
     for (int i = tid; i < GIF_SET_SLOTS; i += 256)
         if (lset[i]) gif_frame_set_add(fs, lset[i]);
 }
+// DELTA: the launch under IMPGPU_GIF_ENC_DELTA, in which a candidate's workgroup goes on to the frame's written keys
+template <bool DELTA>
+__global__ __launch_bounds__(256) void k_gif_enc_sets(GifEncDev D) {
+    __shared__ uint32_t lset[GIF_SET_SLOTS];
+    __shared__ uint32_t flag[3];
+    const GifEncItem it = D.px_items[blockIdx.x];
+    gif_enc_sets_pass<false>(D, it, lset, flag);
+    if (DELTA && D.ddesc[it.frame].prev >= 0) {
+        __syncthreads();
+        gif_enc_sets_pass<true>(D, it, lset, flag);
+    }
+}
 
 // `n` keys (<= 256) of `list` into tabs[0 .. n), ascending: every lane ranks its own
 __device__ __forceinline__ void gif_enc_sort_out(const uint32_t* list, uint32_t n, uint32_t* tab, int tid) {
@@ -51,6 +111,8 @@ __device__ __forceinline__ void gif_enc_sort_out(const uint32_t* list, uint32_t 
 
 // TABLES: a workgroup per album walks its frames: the frame's keys out of its set, sorted into the frame's table slot,
 // and into the album's union (an LDS set; past 256 keys it is of no more use and takes no more).  Then the verdict.
+// DELTA: the launch under IMPGPU_GIF_ENC_DELTA: the choice per candidate, its window, and set A where it is a delta frame.
+template <bool DELTA>
 __global__ __launch_bounds__(256) void k_gif_enc_tables(GifEncDev D) {
     __shared__ uint32_t list[GIF_SET_MAX];
     __shared__ uint32_t uset[GIF_SET_SLOTS];
@@ -62,14 +124,20 @@ __global__ __launch_bounds__(256) void k_gif_enc_tables(GifEncDev D) {
     __syncthreads();
     bool quant = false;
     for (int q = 0; q < a.count; q++) {                                // (the sets are final: every lane reads the same)
-        if (!D.sets[a.first + q].overflow) continue;
+        if (!gif_enc_needs_quant<DELTA>(D, a.first + q)) continue;
         if (!D.slot_of || D.slot_of[a.first + q] < 0) return;          // a frame fits no table, or got no slot: every record stays REFUSED
         quant = true;                                                  // k_gif_enc_cut has made its table: local tables
     }
     for (int q = 0; q < a.count; q++) {
         const int f = a.first + q;
-        const GifColourSet* fs = &D.sets[f];
-        if (fs->overflow) continue;
+        bool isd = false;
+        if (DELTA) {
+            const GifDeltaState st = gif_delta_state(D, f);
+            isd = gif_delta_is_delta(st.cand, st.a_over, st.b_over);
+            if (tid == 0) gif_delta_rec_fill(&D.wins[f], isd, (uint32_t)D.frames[f].w, (uint32_t)D.frames[f].h);
+        }
+        if (gif_enc_needs_quant<DELTA>(D, f)) continue;
+        const GifColourSet* fs = DELTA && isd ? &D.sets_a[f] : &D.sets[f];
         const bool ufull = ucount > GIF_SET_MAX;
         for (int i = tid; i < GIF_SET_SLOTS; i += 256) {
             const uint32_t k = fs->slot[i];
@@ -115,6 +183,7 @@ __global__ __launch_bounds__(256) void k_gif_enc_tables(GifEncDev D) {
 // CLAIM (under IMPGPU_GIF_ENC_QUANTIZE): one workgroup walks the albums in their order and hands the pool's slots to the
 // frames that overflowed -- to all of an album's or to none, so an album is either finished by this group or deferred
 // whole (album_need says how many slots it wants).  Every frame's slot_of is written.
+template <bool DELTA>
 __global__ __launch_bounds__(256) void k_gif_enc_claim(GifEncDev D, int nalbums) {
     __shared__ uint32_t need, taken;
     const int tid = (int)threadIdx.x;
@@ -125,7 +194,7 @@ __global__ __launch_bounds__(256) void k_gif_enc_claim(GifEncDev D, int nalbums)
         if (tid == 0) need = 0;
         __syncthreads();
         for (int q = tid; q < a.count; q += 256)
-            if (D.sets[a.first + q].overflow) atomicAdd(&need, 1u);
+            if (gif_enc_needs_quant<DELTA>(D, a.first + q)) atomicAdd(&need, 1u);
         __syncthreads();
         const uint32_t nd = need;
         const bool fits = nd <= (uint32_t)D.nslots - next;
@@ -133,7 +202,7 @@ __global__ __launch_bounds__(256) void k_gif_enc_claim(GifEncDev D, int nalbums)
         for (int q = tid; q < a.count; q += 256) {
             const int f = a.first + q;
             int slot = -1;
-            if (fits && D.sets[f].overflow) {
+            if (fits && gif_enc_needs_quant<DELTA>(D, f)) {
                 const uint32_t s = atomicAdd(&taken, 1u);
                 if (s < (uint32_t)D.nslots) { slot = (int)s; D.slot_frame[s] = (uint32_t)f + 1u; }
             }
@@ -147,6 +216,8 @@ __global__ __launch_bounds__(256) void k_gif_enc_claim(GifEncDev D, int nalbums)
 // HIST: SETS' items again, for the frames that hold a slot.  A lane sums a run of pixels of one cell in registers, the
 // workgroup combines equal cells in its LDS table, and a cell's four sums leave for device memory once a workgroup (a
 // cell that finds its place in the table taken goes there at once: that is the frame of many colours, whose adds spread).
+// DELTA: a delta frame's pixels that are neither held nor transparent
+template <bool DELTA>
 __global__ __launch_bounds__(256) void k_gif_enc_hist(GifEncDev D) {
     __shared__ GifQuantWg wg;
     const GifEncItem it = D.px_items[blockIdx.x];
@@ -158,7 +229,14 @@ __global__ __launch_bounds__(256) void k_gif_enc_hist(GifEncDev D) {
     gif_q_wg_clear_lane(&wg, tid);
     __syncthreads();
     const GifEncFrame fr = gif_enc_frame_of(f);
-    if (gif_q_lane_pixels(fr, (uint32_t)it.k * GIF_ENC_PX_BLOCK + (uint32_t)tid * 16u, f.total, &wg, hist)) *(volatile uint32_t*)&D.slot_trans[slot] = 1u;
+    const uint32_t p0 = (uint32_t)it.k * GIF_ENC_PX_BLOCK + (uint32_t)tid * 16u;
+    bool trans;
+    if (DELTA && D.ddesc[it.frame].prev >= 0)                          // (a candidate that is quantised is a delta frame)
+        trans = gif_q_lane_pixels_delta(fr, gif_delta_window(D.wins[it.frame].raw, (uint32_t)f.w, (uint32_t)f.h), D.held + D.ddesc[it.frame].held_off, p0,
+                                        f.total, &wg, hist);
+    else
+        trans = gif_q_lane_pixels(fr, p0, f.total, &wg, hist);
+    if (trans) *(volatile uint32_t*)&D.slot_trans[slot] = 1u;
     __syncthreads();
     for (int i = tid; i < GIF_Q_WG_SLOTS; i += 256) gif_q_wg_flush_slot(&wg, hist, i);
 }
@@ -217,7 +295,9 @@ __global__ __launch_bounds__(256) void k_gif_enc_cut(GifEncDev D) {
 
 // INDEX: the frame's table in LDS, four pixels a lane at a time, a dword of indices out.  QUANT: the launch under
 // IMPGPU_GIF_ENC_QUANTIZE, in which a quantised frame's workgroup stages the frame's cell -> index table instead.
-template <bool QUANT>
+// DELTA: the launch under IMPGPU_GIF_ENC_DELTA: the items count WINDOW positions, the plane is the window's, and a held
+// pixel gets the transparent index.
+template <bool QUANT, bool DELTA>
 __global__ __launch_bounds__(256) void k_gif_enc_index(GifEncDev D) {
     __shared__ uint32_t tab[256];
     __shared__ alignas(16) uint32_t cmap[QUANT ? GIF_Q_CELLS / 4 : 4];
@@ -236,14 +316,17 @@ __global__ __launch_bounds__(256) void k_gif_enc_index(GifEncDev D) {
     __syncthreads();
     const GifEncFrame fr = gif_enc_frame_of(f);
     uint8_t* plane = D.mem + f.plane_off;
+    const GifWindow W = DELTA ? gif_delta_rec_window(D.wins[it.frame]) : GifWindow{};
+    const uint16_t* held = DELTA && D.wins[it.frame].delta ? D.held + D.ddesc[it.frame].held_off : nullptr;
+    const uint32_t total = DELTA ? W.ww * W.wh : f.total;
 #pragma unroll 1
     for (int j = 0; j < GIF_ENC_PX_BLOCK / 1024; j++) {
         const uint32_t pos = (uint32_t)it.k * GIF_ENC_PX_BLOCK + 4u * (uint32_t)(tid + 256 * j);
-        if (pos >= f.total) break;
-        const uint32_t cnt = f.total - pos < 4u ? f.total - pos : 4u;
+        if (pos >= total) break;
+        const uint32_t cnt = total - pos < 4u ? total - pos : 4u;
         uint32_t v = 0;
         for (uint32_t q = 0; q < cnt; q++) {
-            const uint32_t key = gif_enc_key_at(fr, pos + q);
+            const uint32_t key = DELTA ? gif_delta_key_at(fr, W, held, pos + q) : gif_enc_key_at(fr, pos + q);
             v |= (QUANT && quant ? gif_q_index((const uint8_t*)cmap, rec.nkeys, key) : gif_table_find(tab, key)) << (8u * q);
         }
         if (cnt == 4u) *(uint32_t*)(plane + pos) = v;
@@ -265,7 +348,9 @@ __device__ __forceinline__ void gif_enc_flush_wave(GifEncMem& m, GifEncState& e,
     __syncthreads();
 }
 
-// LZW: a workgroup IS one wavefront and owns one segment; its barriers are that wave's own
+// LZW: a workgroup IS one wavefront and owns one segment; its barriers are that wave's own.  DELTA: the launch under
+// IMPGPU_GIF_ENC_DELTA: the stream is the window's; a segment planned behind its last pixel is empty.
+template <bool DELTA>
 __global__ __launch_bounds__(GIF_LANES) void k_gif_enc_lzw(GifEncDev D) {
     __shared__ GifEncMem m;
     const GifEncItem it = D.seg_items[blockIdx.x];
@@ -276,7 +361,13 @@ __global__ __launch_bounds__(GIF_LANES) void k_gif_enc_lzw(GifEncDev D) {
     const int mcs = (int)rec.mcs;
     const uint32_t k = (uint32_t)it.k;
     if (k >= f.nseg) return;
-    const uint32_t begin = k * f.segment, end = f.total - begin < f.segment ? f.total : begin + f.segment;
+    const uint32_t total = DELTA ? D.wins[it.frame].total : f.total;
+    const uint32_t begin = k * f.segment;
+    if (DELTA && (begin >= total || total > f.total)) {
+        if (lane == 0) D.segbits[f.seg0 + k] = 0u;
+        return;
+    }
+    const uint32_t end = total - begin < f.segment ? total : begin + f.segment;
     const uint8_t* px = D.mem + f.plane_off;
     const uint32_t cap = f.slot_words;
     uint32_t* words = (uint32_t*)(D.mem + f.scratch_off) + (size_t)k * cap;
@@ -304,7 +395,7 @@ __global__ __launch_bounds__(GIF_LANES) void k_gif_enc_lzw(GifEncDev D) {
         }
         __syncthreads();
     }
-    gif_enc_finish(&m, &e, mcs, k + 1u == f.nseg);
+    gif_enc_finish(&m, &e, mcs, DELTA ? end == total : k + 1u == f.nseg);
     gif_enc_flush_wave(m, e, mcs, words, cap, lane);
     if (lane == 0) {
         gif_enc_last_word(&m, e, words, cap);
@@ -366,22 +457,35 @@ int launch_gif_encode(const GifEncDev& D, long long npx, long long nseg, long lo
         return IMP_ERROR_INVALID_ARGS;
     const bool quant = (D.flags & IMPGPU_GIF_ENC_QUANTIZE) != 0;
     if (quant && (D.nslots <= 0 || !D.slot_of || !D.slot_frame || !D.slot_trans || !D.hist || !D.cmaps || !D.album_need)) return IMP_ERROR_INVALID_ARGS;
-    hipLaunchKernelGGL(k_gif_enc_sets, dim3((unsigned)npx), dim3(256), 0, s, D);
+    const bool delta = (D.flags & IMPGPU_GIF_ENC_DELTA) != 0;
+    if (delta && (!D.ddesc || !D.wins || !D.held || !D.sets_a)) return IMP_ERROR_INVALID_ARGS;
+    if (delta) {                                                       // one launch more: the held planes and the windows' bounds
+        hipLaunchKernelGGL(k_gif_enc_delta, dim3((unsigned)npx), dim3(256), 0, s, D);
+        IMP_HIP(hipGetLastError());
+    }
+    if (delta) hipLaunchKernelGGL(k_gif_enc_sets<true>, dim3((unsigned)npx), dim3(256), 0, s, D);
+    else hipLaunchKernelGGL(k_gif_enc_sets<false>, dim3((unsigned)npx), dim3(256), 0, s, D);
     IMP_HIP(hipGetLastError());
     if (quant) {                                                       // three launches more, whatever overflowed
-        hipLaunchKernelGGL(k_gif_enc_claim, dim3(1), dim3(256), 0, s, D, nalbums);
+        if (delta) hipLaunchKernelGGL(k_gif_enc_claim<true>, dim3(1), dim3(256), 0, s, D, nalbums);
+        else hipLaunchKernelGGL(k_gif_enc_claim<false>, dim3(1), dim3(256), 0, s, D, nalbums);
         IMP_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_gif_enc_hist, dim3((unsigned)npx), dim3(256), 0, s, D);
+        if (delta) hipLaunchKernelGGL(k_gif_enc_hist<true>, dim3((unsigned)npx), dim3(256), 0, s, D);
+        else hipLaunchKernelGGL(k_gif_enc_hist<false>, dim3((unsigned)npx), dim3(256), 0, s, D);
         IMP_HIP(hipGetLastError());
         hipLaunchKernelGGL(k_gif_enc_cut, dim3((unsigned)D.nslots), dim3(256), 0, s, D);
         IMP_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_gif_enc_tables, dim3((unsigned)nalbums), dim3(256), 0, s, D);
+    if (delta) hipLaunchKernelGGL(k_gif_enc_tables<true>, dim3((unsigned)nalbums), dim3(256), 0, s, D);
+    else hipLaunchKernelGGL(k_gif_enc_tables<false>, dim3((unsigned)nalbums), dim3(256), 0, s, D);
     IMP_HIP(hipGetLastError());
-    if (quant) hipLaunchKernelGGL(k_gif_enc_index<true>, dim3((unsigned)npx), dim3(256), 0, s, D);
-    else hipLaunchKernelGGL(k_gif_enc_index<false>, dim3((unsigned)npx), dim3(256), 0, s, D);
+    if (delta && quant) hipLaunchKernelGGL((k_gif_enc_index<true, true>), dim3((unsigned)npx), dim3(256), 0, s, D);
+    else if (delta) hipLaunchKernelGGL((k_gif_enc_index<false, true>), dim3((unsigned)npx), dim3(256), 0, s, D);
+    else if (quant) hipLaunchKernelGGL((k_gif_enc_index<true, false>), dim3((unsigned)npx), dim3(256), 0, s, D);
+    else hipLaunchKernelGGL((k_gif_enc_index<false, false>), dim3((unsigned)npx), dim3(256), 0, s, D);
     IMP_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_gif_enc_lzw, dim3((unsigned)nseg), dim3(GIF_LANES), 0, s, D);
+    if (delta) hipLaunchKernelGGL(k_gif_enc_lzw<true>, dim3((unsigned)nseg), dim3(GIF_LANES), 0, s, D);
+    else hipLaunchKernelGGL(k_gif_enc_lzw<false>, dim3((unsigned)nseg), dim3(GIF_LANES), 0, s, D);
     IMP_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_gif_enc_pack, dim3((unsigned)npack), dim3(256), 0, s, D);
     IMP_HIP(hipGetLastError());

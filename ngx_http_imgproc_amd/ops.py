@@ -36,6 +36,7 @@ PNG_DEVICE_INFLATE = 8          # not part of PNG_ALL: how files are decoded (k_
 GIF_SPLIT = 1                   # cut every page at its clear codes, a wavefront per segment (k_gif_lzw_scan / _len / _emit)
 GIF_SPLIT_MIN_BYTES = 2048      # IMPGPU_GIF_SPLIT_MIN_BYTES: a clear code nearer than this to its segment's start is no cut
 GIF_ENC_QUANTIZE = 1            # IMPGPU_GIF_ENC_QUANTIZE: a frame past 256 colours gets a median-cut table (the _ex encode calls)
+GIF_ENC_DELTA = 2               # IMPGPU_GIF_ENC_DELTA: pixels equal to the previous frame's are written transparent, frames shrink to what changed (the _ex2 calls)
 GIF_ENC_SEGMENT = 8192          # IMPGPU_GIF_ENC_SEGMENT: the pixels between two clear codes of an encoded page (segment = 0)
 
 
@@ -960,16 +961,20 @@ def gif_encode_bound(width, height, frames):
     return lib.impgpu_gif_encode_bound(int(width), int(height), int(frames))
 
 
-def encode_gif(album, time_ms=None, dispose=None, loop_count=-1, segment=0, capacity=None, guard=64, flags=None):
+def encode_gif(album, time_ms=None, dispose=None, loop_count=-1, segment=0, capacity=None, guard=64, flags=None, delta=False):
     """impgpu_album_encode_gif: the album (or single image) as a GIF file written on the device -- exact palette, LZW cut into
     segments of `segment` pixels, a wavefront each -> (code, bytes or None, length, intact).  `capacity` defaults to
     gif_encode_bound; `guard` bytes behind it are checked: intact = nothing at or behind out[length] (out[0] when the call
     failed) was written.  flags: None = the call itself; a number = impgpu_album_encode_gif_ex with those flags
-    (GIF_ENC_QUANTIZE: frames past 256 colours are quantised on the device)."""
+    (GIF_ENC_QUANTIZE: frames past 256 colours are quantised on the device).  delta=True: impgpu_album_encode_gif_ex2 with
+    those flags (0 for None) and GIF_ENC_DELTA."""
     cap = gif_encode_bound(album.shape[1], album.shape[0], album.count) if capacity is None else int(capacity)
     buf = np.full(cap + guard, 0xA5, np.uint8)
     n = C.c_size_t(0)
-    if flags is None:
+    if delta:
+        rc = lib.impgpu_album_encode_gif_ex2(album.h, _ints(time_ms), _ints(dispose), int(loop_count), int(segment), int(flags or 0) | GIF_ENC_DELTA,
+                                             buf.ctypes.data, cap, C.byref(n))
+    elif flags is None:
         rc = lib.impgpu_album_encode_gif(album.h, _ints(time_ms), _ints(dispose), int(loop_count), int(segment), buf.ctypes.data, cap, C.byref(n))
     else:
         rc = lib.impgpu_album_encode_gif_ex(album.h, _ints(time_ms), _ints(dispose), int(loop_count), int(segment), int(flags), buf.ctypes.data, cap,
@@ -977,9 +982,10 @@ def encode_gif(album, time_ms=None, dispose=None, loop_count=-1, segment=0, capa
     return _gif_out(rc, buf, n)
 
 
-def encode_gif_host(frames, time_ms=None, dispose=None, loop_count=-1, segment=0, capacity=None, guard=64, channels=None, flags=None):
+def encode_gif_host(frames, time_ms=None, dispose=None, loop_count=-1, segment=0, capacity=None, guard=64, channels=None, flags=None, delta=False):
     """impgpu_gif_encode_host (no device): frames = HxWxC uint8 arrays of one geometry and one row pitch (views with padded
-    rows are fine) -> (code, bytes or None, length, intact), as encode_gif.  flags: None, or impgpu_gif_encode_host_ex's."""
+    rows are fine) -> (code, bytes or None, length, intact), as encode_gif.  flags: None, or impgpu_gif_encode_host_ex's;
+    delta=True: impgpu_gif_encode_host_ex2 with those flags and GIF_ENC_DELTA."""
     first = frames[0]
     hh, ww, cc = first.shape
     step = first.strides[0]
@@ -988,7 +994,10 @@ def encode_gif_host(frames, time_ms=None, dispose=None, loop_count=-1, segment=0
     cap = gif_encode_bound(ww, hh, len(frames)) if capacity is None else int(capacity)
     buf = np.full(cap + guard, 0xA5, np.uint8)
     n = C.c_size_t(0)
-    if flags is None:
+    if delta:
+        rc = lib.impgpu_gif_encode_host_ex2(ptrs, len(frames), ww, hh, cc if channels is None else channels, step, _ints(time_ms), _ints(dispose),
+                                            int(loop_count), int(segment), int(flags or 0) | GIF_ENC_DELTA, buf.ctypes.data, cap, C.byref(n))
+    elif flags is None:
         rc = lib.impgpu_gif_encode_host(ptrs, len(frames), ww, hh, cc if channels is None else channels, step, _ints(time_ms), _ints(dispose),
                                         int(loop_count), int(segment), buf.ctypes.data, cap, C.byref(n))
     else:
@@ -1010,9 +1019,10 @@ def gif_quantize_host(frame):
     return rc, table[: entries.value].copy(), tkey.value, indices
 
 
-def batch_encode_gif(albums, time_ms=None, dispose=None, loop_counts=None, segment=0, capacities=None, count=None, guard=64, flags=None):
+def batch_encode_gif(albums, time_ms=None, dispose=None, loop_counts=None, segment=0, capacities=None, count=None, guard=64, flags=None, delta=False):
     """impgpu_batch_encode_gif: albums (Images; an entry may be None) -> (code, [(code, bytes or None, length, intact) ...],
-    launches).  time_ms / dispose: per album a list or None; loop_counts default to -1; capacities to gif_encode_bound."""
+    launches).  time_ms / dispose: per album a list or None; loop_counts default to -1; capacities to gif_encode_bound.
+    flags: None, or impgpu_batch_encode_gif_ex's; delta=True: impgpu_batch_encode_gif_ex2 with those flags and GIF_ENC_DELTA."""
     n = len(albums)
     m = max(1, n)
     handles = (C.c_void_p * m)(*[_handle(a) for a in albums])
@@ -1029,7 +1039,10 @@ def batch_encode_gif(albums, time_ms=None, dispose=None, loop_counts=None, segme
     lens = (C.c_size_t * m)()
     codes = (C.c_int * m)(*([-1] * m))
     launches = C.c_int(-1)
-    if flags is None:
+    if delta:
+        rc = lib.impgpu_batch_encode_gif_ex2(handles, tarr, darr, loops, n if count is None else count, int(segment), int(flags or 0) | GIF_ENC_DELTA, outs,
+                                             carr, lens, codes, C.byref(launches))
+    elif flags is None:
         rc = lib.impgpu_batch_encode_gif(handles, tarr, darr, loops, n if count is None else count, int(segment), outs, carr, lens, codes,
                                          C.byref(launches))
     else:                                                                # impgpu_batch_encode_gif_ex
