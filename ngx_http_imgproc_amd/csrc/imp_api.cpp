@@ -13,11 +13,6 @@ using namespace imp;
 
 namespace {
 
-int need_env() {
-    if (!env_ready()) { set_error("impgpu_env_start has not been called", hipErrorNotInitialized); return IMP_ERROR_DEVICE; }
-    return IMP_OK;
-}
-
 Frames one_frame(const View& v, impgpu_image* dst) {
     Frames f{};
     f.src = v.d; f.src_stride = 0; f.v = v;

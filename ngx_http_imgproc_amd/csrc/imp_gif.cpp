@@ -10,11 +10,6 @@
 #include "../../include/impgpu_gif.h"
 
 namespace imp {
-static int need_env() {
-    if (!env_ready()) { set_error("impgpu_env_start has not been called", hipErrorNotInitialized); return IMP_ERROR_DEVICE; }
-    return IMP_OK;
-}
-
 static size_t up16(size_t v) { return (v + 15) & ~size_t(15); }
 // a file whose index planes pass this goes back to the host decoder (4096 pages of 4096 x 4096 would be 64 GB)
 static constexpr size_t GIF_PLANES_MAX = size_t(1) << 30;

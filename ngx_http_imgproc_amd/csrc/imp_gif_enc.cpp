@@ -10,17 +10,11 @@
 // second colour set and the candidates' held planes, k_gif_enc_delta runs ahead of the other launches, and the windows come
 // back with the records in the first wait.
 #include "imp_internal.h"
+#include "imp_enc_host.h"
 #include "imp_gif_enc.h"
 
 namespace imp {
 namespace {
-
-size_t up256(size_t v) { return (v + 255) & ~size_t(255); }
-
-int need_env() {
-    if (!env_ready()) { set_error("impgpu_env_start has not been called", hipErrorNotInitialized); return IMP_ERROR_DEVICE; }
-    return IMP_OK;
-}
 
 // ---------------------------------------------------------------- the device route: one group of albums
 struct EncPlan { int entry, first, frames; };
@@ -78,26 +72,40 @@ int encode_group(const std::vector<EncPlan>& plans, const impgpu_image* const* a
     // the block: what is uploaded | records + album words + sets + pool (zeroed) | tables | segment lengths | planes | slots | streams
     const bool quant = (flags & IMPGPU_GIF_ENC_QUANTIZE) != 0;
     const size_t ns = quant ? (size_t)nslots : 0;
-    const size_t o_fd = 0, o_ad = o_fd + up256(fd.size() * sizeof(GifEncFrameDesc)), o_px = o_ad + up256(ad.size() * sizeof(GifEncAlbumDesc)),
-                 o_seg = o_px + up256(px_items.size() * sizeof(GifEncItem)), o_pack = o_seg + up256(seg_items.size() * sizeof(GifEncItem)),
-                 o_dd = o_pack + up256(pack_items.size() * sizeof(GifEncItem)), o_rec = o_dd + up256(dd.size() * sizeof(GifDeltaDesc)),
-                 o_win = o_rec + up256((size_t)nf * sizeof(GifEncRec)), o_need = o_win + (delta ? up256((size_t)nf * sizeof(GifDeltaRec)) : 0),
-                 o_set = o_need + (quant ? up256((size_t)na * 4) : 0), o_seta = o_set + up256((size_t)nf * sizeof(GifColourSet)),
-                 o_sframe = o_seta + (delta ? up256((size_t)nf * sizeof(GifColourSet)) : 0),
-                 o_strans = o_sframe + up256(ns * 4), o_hist = o_strans + up256(ns * 4), o_slotof = o_hist + ns * GIF_Q_HIST_WORDS * 4,
-                 o_cmap = o_slotof + (quant ? up256((size_t)nf * 4) : 0), o_tab = o_cmap + ns * GIF_Q_CELLS, o_bits = o_tab + up256((size_t)nf * 1024),
-                 o_held = o_bits + up256((size_t)nsegs * 4), o_plane = o_held + up256(heldw * 2), o_scr = o_plane + planes, o_out = o_scr + scratch, o_end = o_out + outb;
+    BlockLayout L;
+    const size_t o_fd = L.take(fd.size() * sizeof(GifEncFrameDesc));    // the frames
+    const size_t o_ad = L.take(ad.size() * sizeof(GifEncAlbumDesc));    // the albums
+    const size_t o_px = L.take(px_items.size() * sizeof(GifEncItem));   // the items of the pixel launches
+    const size_t o_seg = L.take(seg_items.size() * sizeof(GifEncItem)); // ... of k_gif_enc_lzw
+    const size_t o_pack = L.take(pack_items.size() * sizeof(GifEncItem));   // ... of k_gif_enc_pack
+    const size_t o_dd = L.take(dd.size() * sizeof(GifDeltaDesc));       // delta: the candidates (none without the bit)
+    const size_t o_rec = L.take((size_t)nf * sizeof(GifEncRec));        // the records: where the upload ends and the zeroed stretch begins
+    const size_t o_win = delta ? L.take((size_t)nf * sizeof(GifDeltaRec)) : L.size();     // delta: the frames' windows
+    const size_t o_need = quant ? L.take((size_t)na * 4) : L.size();    // quantise: a word an album, the slots it got none of
+    const size_t o_set = L.take((size_t)nf * sizeof(GifColourSet));     // the colour sets
+    const size_t o_seta = delta ? L.take((size_t)nf * sizeof(GifColourSet)) : L.size();   // delta: the second sets
+    const size_t o_sframe = L.take(ns * 4);                             // the pool: a slot's frame,
+    const size_t o_strans = L.take(ns * 4);                             // ... its transparency,
+    const size_t o_hist = L.take_exact(ns * GIF_Q_HIST_WORDS * 4);      // ... its histogram
+    const size_t o_slotof = quant ? L.take((size_t)nf * 4) : L.size();  // quantise: a frame's slot; where the zeroed stretch ends under the flag,
+    const size_t o_cmap = L.take_exact(ns * GIF_Q_CELLS);               // the slots' cell maps
+    const size_t o_tab = L.take((size_t)nf * 1024);                     // the tables: ... and where it ends without
+    const size_t o_bits = L.take((size_t)nsegs * 4);                    // the segments' lengths
+    const size_t o_held = L.take(heldw * 2);                            // delta: the candidates' held planes
+    const size_t o_plane = L.take_exact(planes);                        // the index planes
+    const size_t o_scr = L.take_exact(scratch);                         // the segment slots
+    const size_t o_out = L.take_exact(outb);                            // the framed streams
     for (GifEncFrameDesc& d : fd) { d.plane_off += (long long)o_plane; d.scratch_off += (long long)o_scr; d.out_off += (long long)o_out; }
-    void* mem = nullptr;
-    if (int rc = dev_alloc(o_end, &mem)) return rc;
-    uint8_t* m = (uint8_t*)mem;
+    DevBlock block;
+    if (int rc = dev_alloc(L.size(), &block.p)) return rc;
+    uint8_t* m = block.bytes();
     std::vector<uint8_t> head(o_rec, 0);
-    std::memcpy(head.data() + o_fd, fd.data(), fd.size() * sizeof(GifEncFrameDesc));
-    std::memcpy(head.data() + o_ad, ad.data(), ad.size() * sizeof(GifEncAlbumDesc));
-    std::memcpy(head.data() + o_px, px_items.data(), px_items.size() * sizeof(GifEncItem));
-    std::memcpy(head.data() + o_seg, seg_items.data(), seg_items.size() * sizeof(GifEncItem));
-    std::memcpy(head.data() + o_pack, pack_items.data(), pack_items.size() * sizeof(GifEncItem));
-    if (delta) std::memcpy(head.data() + o_dd, dd.data(), dd.size() * sizeof(GifDeltaDesc));
+    head_put(head, o_fd, fd);
+    head_put(head, o_ad, ad);
+    head_put(head, o_px, px_items);
+    head_put(head, o_seg, seg_items);
+    head_put(head, o_pack, pack_items);
+    head_put(head, o_dd, dd);
     int rc = upload_to(m, head.data(), head.size(), s);
     if (!rc) {
         const hipError_t e = hipMemsetAsync(m + o_rec, 0, (quant ? o_slotof : o_tab) - o_rec, s);
@@ -116,37 +124,25 @@ int encode_group(const std::vector<EncPlan>& plans, const impgpu_image* const* a
     D.sets = (GifColourSet*)(m + o_set); D.tabs = (uint32_t*)(m + o_tab); D.recs = (GifEncRec*)(m + o_rec); D.segbits = (uint32_t*)(m + o_bits);
     if (!rc) rc = launch_gif_encode(D, (long long)px_items.size(), (long long)seg_items.size(), (long long)pack_items.size(), na, s);
     // the first wait: the records (and, behind them, the frames' windows and the albums' words)
-    std::vector<GifEncRec> recs((size_t)nf);
-    std::vector<GifDeltaRec> wins(delta ? (size_t)nf : 0);
-    std::vector<uint32_t> need((size_t)na, 0u);
-    const size_t rec_bytes = quant ? (o_need - o_rec) + need.size() * 4 : delta ? (o_win - o_rec) + wins.size() * sizeof(GifDeltaRec)
-                                                                                : recs.size() * sizeof(GifEncRec);
-    void *pin = nullptr, *token = nullptr;
-    if (!rc) rc = stage_begin(rec_bytes, &pin, &token);
-    if (!rc) {
-        const hipError_t e = hipMemcpyAsync(pin, D.recs, rec_bytes, hipMemcpyDeviceToHost, s);
-        if (e != hipSuccess) { set_error("hipMemcpyAsync(gif encode records)", e); rc = IMP_ERROR_DEVICE; }
-    }
-    if (rc) { (void)hipStreamSynchronize(s); dev_free(mem); return rc; }
-    stage_hold(token, true);
-    rc = lane_wait();
-    if (!rc) std::memcpy(recs.data(), pin, recs.size() * sizeof(GifEncRec));
-    if (!rc && delta) std::memcpy(wins.data(), (const uint8_t*)pin + (o_win - o_rec), wins.size() * sizeof(GifDeltaRec));
-    if (!rc && quant) std::memcpy(need.data(), (const uint8_t*)pin + (o_need - o_rec), need.size() * 4);
-    stage_hold(token, false);
-    if (rc) { dev_free(mem); return rc; }
+    if (rc) return drained(rc);
+    const size_t rec_bytes = quant ? (o_need - o_rec) + (size_t)na * 4 : delta ? (o_win - o_rec) + (size_t)nf * sizeof(GifDeltaRec)
+                                                                               : (size_t)nf * sizeof(GifEncRec);
+    std::vector<uint8_t> back(rec_bytes);
+    if ((rc = fetch_records(D.recs, rec_bytes, back.data(), "hipMemcpyAsync(gif encode records)"))) return rc;
+    const GifEncRec* recs = (const GifEncRec*)back.data();
+    const GifDeltaRec* wins = delta ? (const GifDeltaRec*)(back.data() + (o_win - o_rec)) : nullptr;
+    const uint32_t* album_need = quant ? (const uint32_t*)(back.data() + (o_need - o_rec)) : nullptr;
     // the files' sizes; what fits is fetched: per frame its table (local tables; the first frame's for a global one) and its stream
-    std::vector<size_t> tab_at((size_t)nf, 0), str_at((size_t)nf, 0);
-    std::vector<char> fetch((size_t)na, 0);
-    size_t total = 0;
+    AnswerFetch pieces;
+    std::vector<int> tab_at((size_t)nf, -1), str_at((size_t)nf, -1);
     for (int a = 0; a < na; a++) {
         const EncPlan& p = plans[(size_t)a];
         const int i = p.entry;
         const GifEncRec* r0 = &recs[(size_t)p.first];
-        if (r0->mode == GIF_ENC_REFUSED && need[(size_t)a]) { deferred->push_back(EncDeferred{i, need[(size_t)a]}); continue; }
+        if (r0->mode == GIF_ENC_REFUSED && quant && album_need[a]) { deferred->push_back(EncDeferred{i, album_need[a]}); continue; }
         if (r0->mode == GIF_ENC_REFUSED) { codes[i] = IMP_ERROR_UNSUPPORTED; lens[i] = 0; continue; }
         bool sane = true;
-        size_t need = 13 + (loop_counts[i] >= 0 ? 19 : 0) + 1 + (r0->mode == GIF_ENC_GLOBAL ? gif_enc_table_bytes(r0->nkeys) : 0);
+        size_t file_bytes = 13 + (loop_counts[i] >= 0 ? 19 : 0) + 1 + (r0->mode == GIF_ENC_GLOBAL ? gif_enc_table_bytes(r0->nkeys) : 0);
         for (int q = 0; q < p.frames; q++) {
             const GifEncRec& r = r0[q];
             sane = sane && r.nkeys >= 1 && r.nkeys <= GIF_SET_MAX && gif_enc_framed_size(r.stream_bytes) <= fd[(size_t)(p.first + q)].out_cap;
@@ -154,56 +150,30 @@ int encode_group(const std::vector<EncPlan>& plans, const impgpu_image* const* a
                 const GifDeltaRec& wr = wins[(size_t)(p.first + q)];
                 sane = sane && wr.ww >= 1 && wr.wh >= 1 && wr.x0 + wr.ww <= (uint32_t)albums[i]->w && wr.y0 + wr.wh <= (uint32_t)albums[i]->h;
             }
-            need += 8 + 10 + 1 + gif_enc_framed_size(r.stream_bytes) + (r.mode == GIF_ENC_LOCAL ? gif_enc_table_bytes(r.nkeys) : 0);
+            file_bytes += 8 + 10 + 1 + gif_enc_framed_size(r.stream_bytes) + (r.mode == GIF_ENC_LOCAL ? gif_enc_table_bytes(r.nkeys) : 0);
         }
         if (!sane) { codes[i] = IMP_ERROR_DEVICE; lens[i] = 0; set_error_text("gif encode: a stream outgrew its bound"); continue; }
-        lens[i] = need;
-        if (need > caps[i]) { codes[i] = IMP_ERROR_MALLOC_FAILED; continue; }
-        codes[i] = IMP_OK;
-        fetch[(size_t)a] = 1;
+        if (!answer_fits(file_bytes, caps[i], &codes[i], &lens[i])) continue;
         for (int q = 0; q < p.frames; q++) {
             const size_t f = (size_t)(p.first + q);
-            if (r0->mode == GIF_ENC_LOCAL || q == 0) { tab_at[f] = total; total += 1024; }
-            str_at[f] = total;
-            total += (gif_enc_framed_size(r0[q].stream_bytes) + 63) & ~size_t(63);
+            if (r0->mode == GIF_ENC_LOCAL || q == 0) tab_at[f] = pieces.add(D.tabs + f * 256, (size_t)r0[q].nkeys * 4);
+            str_at[f] = pieces.add(m + fd[f].out_off, gif_enc_framed_size(r0[q].stream_bytes));
         }
     }
-    if (total) {
-        if ((rc = stage_begin(total, &pin, &token))) { dev_free(mem); return rc; }
-        hipError_t e = hipSuccess;
-        for (int a = 0; a < na && e == hipSuccess; a++) {
-            if (!fetch[(size_t)a]) continue;
-            const EncPlan& p = plans[(size_t)a];
-            for (int q = 0; q < p.frames && e == hipSuccess; q++) {
-                const size_t f = (size_t)(p.first + q);
-                const GifEncRec& r = recs[f];
-                if (r.mode == GIF_ENC_LOCAL || q == 0)
-                    e = hipMemcpyAsync((uint8_t*)pin + tab_at[f], D.tabs + f * 256, (size_t)r.nkeys * 4, hipMemcpyDeviceToHost, s);
-                if (e == hipSuccess)
-                    e = hipMemcpyAsync((uint8_t*)pin + str_at[f], m + fd[f].out_off, gif_enc_framed_size(r.stream_bytes), hipMemcpyDeviceToHost, s);
-            }
+    rc = pieces.run("hipMemcpyAsync(gif encode download)");             // the second wait: the files
+    std::vector<GifEncPage> pages;
+    for (int a = 0; a < na && !rc; a++) {
+        const EncPlan& p = plans[(size_t)a];
+        const int i = p.entry;
+        if (str_at[(size_t)p.first] < 0) continue;                      // refused, deferred or too long for its buffer
+        pages.clear();
+        for (int q = 0; q < p.frames; q++) {
+            const size_t f = (size_t)(p.first + q), tf = tab_at[f] >= 0 ? f : (size_t)p.first;     // its own table, or the album's
+            pages.push_back(GifEncPage{&recs[f], (const uint32_t*)pieces.at(tab_at[tf]), pieces.at(str_at[f])});
         }
-        if (e != hipSuccess) { set_error("hipMemcpyAsync(gif encode download)", e); (void)hipStreamSynchronize(s); dev_free(mem); return IMP_ERROR_DEVICE; }
-        stage_hold(token, true);
-        rc = lane_wait();                                               // the second wait: the files
-        if (!rc) {
-            std::vector<GifEncPage> pages;
-            for (int a = 0; a < na; a++) {
-                if (!fetch[(size_t)a]) continue;
-                const EncPlan& p = plans[(size_t)a];
-                const int i = p.entry;
-                pages.clear();
-                for (int q = 0; q < p.frames; q++) {
-                    const size_t f = (size_t)(p.first + q), tf = recs[f].mode == GIF_ENC_LOCAL ? f : (size_t)p.first;
-                    pages.push_back(GifEncPage{&recs[f], (const uint32_t*)((const uint8_t*)pin + tab_at[tf]), (const uint8_t*)pin + str_at[f]});
-                }
-                gif_enc_write_file(outs[i], pages.data(), p.frames, albums[i]->w, albums[i]->h, time_ms ? time_ms[i] : nullptr,
-                                   dispose ? dispose[i] : nullptr, loop_counts[i], delta ? wins.data() + p.first : nullptr);
-            }
-        }
-        stage_hold(token, false);
+        gif_enc_write_file(outs[i], pages.data(), p.frames, albums[i]->w, albums[i]->h, time_ms ? time_ms[i] : nullptr,
+                           dispose ? dispose[i] : nullptr, loop_counts[i], delta ? wins + p.first : nullptr);
     }
-    dev_free(mem);
     return rc;
 }
 
@@ -320,36 +290,31 @@ int impgpu_batch_encode_gif_ex2(const impgpu_image* const* albums, const int* co
     return IMP_OK;
 }
 
-int impgpu_album_encode_gif(const impgpu_image* album, const int* time_ms, const int* dispose, int loop_count, int segment,
-                            unsigned char* out, size_t capacity, size_t* length) {
+// one album: the _ex2 batch call with arrays of one, behind the checks of a lone call; `allowed` = the flags of the entry point
+static int album_encode(const impgpu_image* album, const int* time_ms, const int* dispose, int loop_count, int segment, int flags, int allowed,
+                        unsigned char* out, size_t capacity, size_t* length) {
     if (length) *length = 0;
-    if (!album || !out || !length) return IMP_ERROR_INVALID_ARGS;
-    if (int rc = gif_enc_check_args(album->frames <= GIF_ENC_MAX_FRAMES ? album->frames : 0, dispose, loop_count, segment)) return rc;
-    int code = IMP_OK;
-    if (int rc = impgpu_batch_encode_gif(&album, &time_ms, &dispose, &loop_count, 1, segment, &out, &capacity, length, &code, nullptr)) return rc;
-    return code;
-}
-
-int impgpu_album_encode_gif_ex(const impgpu_image* album, const int* time_ms, const int* dispose, int loop_count, int segment, int flags,
-                               unsigned char* out, size_t capacity, size_t* length) {
-    if (length) *length = 0;
-    if (flags & ~IMPGPU_GIF_ENC_QUANTIZE) return IMP_ERROR_INVALID_ARGS;
-    if (!album || !out || !length) return IMP_ERROR_INVALID_ARGS;
-    if (int rc = gif_enc_check_args(album->frames <= GIF_ENC_MAX_FRAMES ? album->frames : 0, dispose, loop_count, segment)) return rc;
-    int code = IMP_OK;
-    if (int rc = impgpu_batch_encode_gif_ex(&album, &time_ms, &dispose, &loop_count, 1, segment, flags, &out, &capacity, length, &code, nullptr)) return rc;
-    return code;
-}
-
-int impgpu_album_encode_gif_ex2(const impgpu_image* album, const int* time_ms, const int* dispose, int loop_count, int segment, int flags,
-                                unsigned char* out, size_t capacity, size_t* length) {
-    if (length) *length = 0;
-    if (flags & ~(IMPGPU_GIF_ENC_QUANTIZE | IMPGPU_GIF_ENC_DELTA)) return IMP_ERROR_INVALID_ARGS;
+    if (flags & ~allowed) return IMP_ERROR_INVALID_ARGS;
     if (!album || !out || !length) return IMP_ERROR_INVALID_ARGS;
     if (int rc = gif_enc_check_args(album->frames <= GIF_ENC_MAX_FRAMES ? album->frames : 0, dispose, loop_count, segment)) return rc;
     int code = IMP_OK;
     if (int rc = impgpu_batch_encode_gif_ex2(&album, &time_ms, &dispose, &loop_count, 1, segment, flags, &out, &capacity, length, &code, nullptr)) return rc;
     return code;
+}
+
+int impgpu_album_encode_gif(const impgpu_image* album, const int* time_ms, const int* dispose, int loop_count, int segment,
+                            unsigned char* out, size_t capacity, size_t* length) {
+    return album_encode(album, time_ms, dispose, loop_count, segment, 0, 0, out, capacity, length);
+}
+
+int impgpu_album_encode_gif_ex(const impgpu_image* album, const int* time_ms, const int* dispose, int loop_count, int segment, int flags,
+                               unsigned char* out, size_t capacity, size_t* length) {
+    return album_encode(album, time_ms, dispose, loop_count, segment, flags, IMPGPU_GIF_ENC_QUANTIZE, out, capacity, length);
+}
+
+int impgpu_album_encode_gif_ex2(const impgpu_image* album, const int* time_ms, const int* dispose, int loop_count, int segment, int flags,
+                                unsigned char* out, size_t capacity, size_t* length) {
+    return album_encode(album, time_ms, dispose, loop_count, segment, flags, IMPGPU_GIF_ENC_QUANTIZE | IMPGPU_GIF_ENC_DELTA, out, capacity, length);
 }
 
 }  // extern "C"

@@ -59,6 +59,7 @@ inline bool view_fits(long long w, long long h, int c, long long step) {
 void set_error(const char* what, hipError_t e);
 void set_error_text(const char* what);             // impgpu_last_error() text for failures that are not HIP errors
 bool env_ready();
+int  need_env();                                   // IMP_OK, or IMP_ERROR_DEVICE and the error text of a call made before impgpu_env_start
 hipStream_t env_stream();
 int  dev_alloc(size_t bytes, void** out);          // stream-ordered pool; IMP_* code
 void dev_free(void* p);

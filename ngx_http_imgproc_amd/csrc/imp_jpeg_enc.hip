@@ -1075,7 +1075,7 @@ size_t impgpu_jpeg_encode_bound(int width, int height, int channels) {
 int impgpu_batch_encode_jpeg(const impgpu_image* const* images, int count, int quality, unsigned char* const* outs,
                              const size_t* capacities, size_t* lengths, int* codes) {
     if (count < 0 || (count && (!images || !outs || !capacities || !lengths || !codes))) return IMP_ERROR_INVALID_ARGS;
-    if (!env_ready()) { set_error("impgpu_env_start has not been called", hipErrorNotInitialized); return IMP_ERROR_DEVICE; }
+    if (int rc = need_env()) return rc;
     TraceRange tr("IMP_STEP_ENCODE");                           // bridge.c:679-710
     IMP_FAULT_POINT(IMP_STEP_ENCODE);
     for (int at = 0; at < count; at += ENC_MAX_BATCH) {
@@ -1089,7 +1089,7 @@ int impgpu_batch_encode_jpeg_begin(const impgpu_image* const* images, int count,
     if (!encode) return IMP_ERROR_INVALID_ARGS;
     *encode = nullptr;
     if (count <= 0 || count > ENC_MAX_BATCH || !images) return IMP_ERROR_INVALID_ARGS;
-    if (!env_ready()) { set_error("impgpu_env_start has not been called", hipErrorNotInitialized); return IMP_ERROR_DEVICE; }
+    if (int rc = need_env()) return rc;
     TraceRange tr("IMP_STEP_ENCODE");
     IMP_FAULT_POINT(IMP_STEP_ENCODE);
     impgpu_jpeg_encode* h = new impgpu_jpeg_encode();

@@ -25,6 +25,7 @@
 #include <cstring>
 #include <vector>
 #include "imp_internal.h"
+#include "imp_enc_host.h"
 #include "imp_inflate.h"
 #include "imp_png_deflate.h"
 
@@ -492,7 +493,7 @@ int encode_group(const impgpu_image* const* images, int count, int level, unsign
         J.nseg = (uint32_t)((n + PNG_SEG - 1) / PNG_SEG); J.seg0 = segs; segs += J.nseg;
         J.maxblk = (uint32_t)(n / BLOCK_SYMS + 1); J.blk0 = blks; blks += J.maxblk;
         J.zwords = (uint32_t)((zlib_bound(n) + 3) / 4);
-        o_f.push_back(f_bytes); f_bytes += (n + 255) & ~uint64_t(255);
+        o_f.push_back(f_bytes); f_bytes += up256(n);
         o_s.push_back(sym_words); sym_words += (n + 63) & ~uint64_t(63);
         o_z.push_back(z_words); z_words += ((uint64_t)J.zwords + 63) & ~uint64_t(63);
         jobs.push_back(J);
@@ -501,24 +502,29 @@ int encode_group(const impgpu_image* const* images, int count, int level, unsign
     const int nj = (int)jobs.size();
     if (!nj) return IMP_OK;
     // one pool block: filtered streams | symbols | zlib words | row pieces | segment records | block records | results
-    auto up = [](uint64_t v) { return (v + 255) & ~uint64_t(255); };
-    const uint64_t a_f = 0, a_s = a_f + up(f_bytes), a_z = a_s + up(sym_words * 4), a_rows = a_z + up(z_words * 4),
-                   a_seg = a_rows + up((uint64_t)rows * 8), a_hist = a_seg + up((uint64_t)segs * 24),
-                   a_bs = a_hist + up((uint64_t)blks * L_CODES * 4), a_tab = a_bs + up((uint64_t)blks * 4 + 4),
-                   a_hdr = a_tab + up((uint64_t)blks * PNG_TAB * 4), a_blk = a_hdr + up((uint64_t)blks * PNG_HDR_WORDS * 4),
-                   a_res = a_blk + up((uint64_t)blks * sizeof(PngBlk)), a_end = a_res + up((uint64_t)nj * PNG_RES * 4);
-    void* mem = nullptr;
-    if (int rc = dev_alloc(a_end, &mem)) return rc;
-    uint8_t* m = (uint8_t*)mem;
+    BlockLayout L;
+    const size_t a_f = L.take(f_bytes);                                 // the filtered streams
+    const size_t a_s = L.take(sym_words * 4);                           // the symbols
+    const size_t a_z = L.take(z_words * 4);                             // the zlib words (zeroed)
+    const size_t a_rows = L.take((size_t)rows * 8);                     // row pieces: rowA, rowB
+    const size_t a_seg = L.take((size_t)segs * 24);                     // six words a segment
+    const size_t a_hist = L.take((size_t)blks * L_CODES * 4);           // the blocks' histograms (zeroed)
+    const size_t a_bs = L.take((size_t)blks * 4 + 4);                   // the blocks' starts
+    const size_t a_tab = L.take((size_t)blks * PNG_TAB * 4);            // ... code tables
+    const size_t a_hdr = L.take((size_t)blks * PNG_HDR_WORDS * 4);      // ... headers
+    const size_t a_blk = L.take((size_t)blks * sizeof(PngBlk));         // ... records
+    const size_t a_res = L.take((size_t)nj * PNG_RES * 4);              // the results (zeroed)
+    DevBlock block, table;                                              // the block, and the jobs table uploaded beside it
+    if (int rc = dev_alloc(L.size(), &block.p)) return rc;
+    uint8_t* m = block.bytes();
     for (int k = 0; k < nj; k++) {
         jobs[k].f = m + a_f + o_f[k];
         jobs[k].syms = (uint32_t*)(m + a_s) + o_s[k];
         jobs[k].z = (uint32_t*)(m + a_z) + o_z[k];
     }
-    void* djobs = nullptr;
-    if (int rc = upload_small(jobs.data(), jobs.size() * sizeof(PngJob), &djobs, s)) { dev_free(mem); return rc; }
+    if (int rc = upload_small(jobs.data(), jobs.size() * sizeof(PngJob), &table.p, s)) return rc;
     PngDev D;
-    D.jobs = (const PngJob*)djobs; D.njobs = nj;
+    D.jobs = (const PngJob*)table.p; D.njobs = nj;
     D.rowA = (uint32_t*)(m + a_rows); D.rowB = D.rowA + rows;
     D.segF = (uint32_t*)(m + a_seg); D.segL = D.segF + segs; D.segRS = D.segL + segs; D.segRE = D.segRS + segs;
     D.segCnt = D.segRE + segs; D.segBase = D.segCnt + segs;
@@ -526,7 +532,7 @@ int encode_group(const impgpu_image* const* images, int count, int level, unsign
     D.hdrs = (uint32_t*)(m + a_hdr); D.blk = (PngBlk*)(m + a_blk); D.res = (uint32_t*)(m + a_res);
     hipError_t e = hipMemsetAsync(m + a_z, 0, z_words * 4, s);
     if (e == hipSuccess) e = hipMemsetAsync(m + a_hist, 0, a_bs - a_hist, s);
-    if (e == hipSuccess) e = hipMemsetAsync(m + a_res, 0, a_end - a_res, s);
+    if (e == hipSuccess) e = hipMemsetAsync(m + a_res, 0, L.size() - a_res, s);
     const unsigned sg = (segs + 255) / 256;
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_png_filter, dim3(rows), dim3(256), 0, s, D);
@@ -540,51 +546,26 @@ int encode_group(const impgpu_image* const* images, int count, int level, unsign
         hipLaunchKernelGGL(k_png_emit, dim3(blks), dim3(256), 0, s, D);
         e = hipGetLastError();
     }
-    void *pin = nullptr, *token = nullptr;
-    if (e == hipSuccess) {
-        if (int rc = stage_begin((size_t)nj * PNG_RES * 4, &pin, &token)) { (void)hipStreamSynchronize(s); dev_free(djobs); dev_free(mem); return rc; }
-        e = hipMemcpyAsync(pin, D.res, (size_t)nj * PNG_RES * 4, hipMemcpyDeviceToHost, s);
-    }
-    if (e != hipSuccess) { set_error("png encode", e); (void)hipStreamSynchronize(s); dev_free(djobs); dev_free(mem); return IMP_ERROR_DEVICE; }
-    stage_hold(token, true);
-    int rc = lane_wait();
+    if (e != hipSuccess) { set_error("png encode", e); return drained(IMP_ERROR_DEVICE); }
     std::vector<uint32_t> res((size_t)nj * PNG_RES);
-    if (!rc) std::memcpy(res.data(), pin, res.size() * 4);
-    stage_hold(token, false);
-    if (rc) { dev_free(djobs); dev_free(mem); return rc; }
+    if (int rc = fetch_records(D.res, res.size() * 4, res.data(), "png encode")) return rc;      // the first wait
     // the streams that fit their callers' buffers, in one pinned area
-    std::vector<uint64_t> at((size_t)nj, 0);
-    uint64_t total = 0;
+    AnswerFetch answers;
+    std::vector<int> piece((size_t)nj, -1);
     for (int k = 0; k < nj; k++) {
         const int i = owner[k];
         const uint32_t* r = &res[(size_t)k * PNG_RES];
         if (r[4]) { codes[i] = IMP_ERROR_DEVICE; set_error_text("png encode: a stream outgrew its bound"); continue; }
-        lens[i] = (size_t)file_len(r[2]);
-        if (lens[i] > caps[i]) { codes[i] = IMP_ERROR_MALLOC_FAILED; continue; }
-        at[k] = total;
-        total += (r[2] + 63) & ~uint64_t(63);
+        if (answer_fits((size_t)file_len(r[2]), caps[i], &codes[i], &lens[i])) piece[k] = answers.add(jobs[k].z, r[2]);
     }
-    if (total) {
-        if ((rc = stage_begin(total, &pin, &token))) { dev_free(djobs); dev_free(mem); return rc; }
-        for (int k = 0; k < nj && e == hipSuccess; k++)
-            if (codes[owner[k]] == IMP_OK)
-                e = hipMemcpyAsync((uint8_t*)pin + at[k], (const uint8_t*)jobs[k].z, res[(size_t)k * PNG_RES + 2], hipMemcpyDeviceToHost, s);
-        if (e != hipSuccess) { set_error("png encode download", e); (void)hipStreamSynchronize(s); dev_free(djobs); dev_free(mem); return IMP_ERROR_DEVICE; }
-        stage_hold(token, true);
-        rc = lane_wait();
-        if (!rc)
-            for (int k = 0; k < nj; k++) {
-                const int i = owner[k];
-                if (codes[i] != IMP_OK) continue;
-                const PngJob& J = jobs[k];
-                uint8_t* zs = (uint8_t*)pin + at[k];
-                zlib_header(J.n, zs);                           // (the kernels leave the first two bytes to the host)
-                write_file(outs[i], J.w, J.h, J.c, zs, res[(size_t)k * PNG_RES + 2]);
-            }
-        stage_hold(token, false);
+    const int rc = answers.run("png encode download");                 // the second wait
+    for (int k = 0; k < nj && !rc; k++) {
+        if (piece[k] < 0) continue;
+        const PngJob& J = jobs[k];
+        uint8_t* zs = answers.at(piece[k]);
+        zlib_header(J.n, zs);                                   // (the kernels leave the first two bytes to the host)
+        write_file(outs[owner[k]], J.w, J.h, J.c, zs, res[(size_t)k * PNG_RES + 2]);
     }
-    dev_free(djobs);
-    dev_free(mem);
     return rc;
 }
 
@@ -605,7 +586,7 @@ size_t impgpu_png_encode_bound(int width, int height, int channels) {
 int impgpu_batch_encode_png(const impgpu_image* const* images, int count, int level, unsigned char* const* outs,
                             const size_t* capacities, size_t* lengths, int* codes) {
     if (count < 0 || count > PNG_MAX_BATCH || (count && (!images || !outs || !capacities || !lengths || !codes))) return IMP_ERROR_INVALID_ARGS;
-    if (!env_ready()) { set_error("impgpu_env_start has not been called", hipErrorNotInitialized); return IMP_ERROR_DEVICE; }
+    if (int rc = need_env()) return rc;
     TraceRange tr("IMP_STEP_ENCODE");                           // bridge.c:679-710
     IMP_FAULT_POINT(IMP_STEP_ENCODE);
     return encode_group(images, count, level, outs, capacities, lengths, codes);

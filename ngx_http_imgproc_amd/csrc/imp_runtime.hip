@@ -160,6 +160,10 @@ void set_error(const char* what, hipError_t e) {
 }
 void set_error_text(const char* what) { t_error = what; }
 bool env_ready() { return g_env != nullptr; }
+int need_env() {
+    if (!env_ready()) { set_error("impgpu_env_start has not been called", hipErrorNotInitialized); return IMP_ERROR_DEVICE; }
+    return IMP_OK;
+}
 
 static int no_env() {
     t_error = "impgpu_env_start has not been called";

@@ -8,17 +8,11 @@
 // with them) and the token planes behind the residuals, a file's region is sized by the flagged bound, and there are seven
 // launches; with flags 0 the block and the launches are the flag-less call's.
 #include "imp_internal.h"
+#include "imp_enc_host.h"
 #include "imp_webp_enc.h"
 
 namespace imp {
 namespace {
-
-size_t up256(size_t v) { return (v + 255) & ~size_t(255); }
-
-int need_env() {
-    if (!env_ready()) { set_error("impgpu_env_start has not been called", hipErrorNotInitialized); return IMP_ERROR_DEVICE; }
-    return IMP_OK;
-}
 
 // what a frame takes of a group's device block, for the stage cap: its file, its residuals, its work area
 size_t webp_frame_bytes(const impgpu_image* im, int flags) {
@@ -72,23 +66,32 @@ int encode_group(const std::vector<int>& entries, const impgpu_image* const* ima
     if (items.size() > 0x7fffffffull || tile_items.size() > 0x7fffffffull) return IMP_ERROR_UNSUPPORTED;
     // the block: what is uploaded | records | work areas [+ WebpLz's] + files (zeroed) | item bits | item offsets | modes | residuals
     // [| token planes]
-    const size_t o_fd = 0, o_items = o_fd + up256(fd.size() * sizeof(WebpFrameDesc)), o_tiles = o_items + up256(items.size() * sizeof(WebpItem)),
-                 o_forced = o_tiles + up256(tile_items.size() * sizeof(WebpTileItem)), o_rec = o_forced + up256(forced_bytes.size()),
-                 o_work = o_rec + up256((size_t)nf * sizeof(WebpRec)), o_lz = o_work + up256((size_t)nf * sizeof(WebpWork)), o_out = o_lz + (lz ? up256((size_t)nf * sizeof(WebpLz)) : 0), o_bits = o_out + outb,
-                 o_off = o_bits + up256(items.size() * 4u), o_modes = o_off + up256(items.size() * 8u), o_resid = o_modes + modesb,
-                 o_tok = o_resid + residb, o_end = o_tok + tokb;
+    BlockLayout L;
+    const size_t o_fd = L.take(fd.size() * sizeof(WebpFrameDesc));      // the frames
+    const size_t o_items = L.take(items.size() * sizeof(WebpItem));     // the items of k_webp_measure / _scan / _emit
+    const size_t o_tiles = L.take(tile_items.size() * sizeof(WebpTileItem));   // the items of k_webp_modes
+    const size_t o_forced = L.take(forced_bytes.size());                // the forced modes
+    const size_t o_rec = L.take((size_t)nf * sizeof(WebpRec));          // the records: where the upload ends and the zeroed stretch begins
+    const size_t o_work = L.take((size_t)nf * sizeof(WebpWork));        // the work areas
+    const size_t o_lz = lz ? L.take((size_t)nf * sizeof(WebpLz)) : L.size();      // back references: a WebpLz a frame
+    const size_t o_out = L.take_exact(outb);                            // the files
+    const size_t o_bits = L.take(items.size() * 4u);                    // the items' bit counts: where the zeroed stretch ends
+    const size_t o_off = L.take(items.size() * 8u);                     // the items' offsets
+    const size_t o_modes = L.take_exact(modesb);                        // the modes
+    const size_t o_resid = L.take_exact(residb);                        // the residuals
+    const size_t o_tok = L.take_exact(tokb);                            // the token planes
     for (WebpFrameDesc& d : fd) {
         d.out_off += (long long)o_out; d.modes_off += (long long)o_modes; d.resid_off += (long long)o_resid; d.forced_off += (long long)o_forced;
         d.tok_off += (long long)o_tok;
     }
-    void* mem = nullptr;
-    if (int rc = dev_alloc(o_end, &mem)) return rc;
-    uint8_t* m = (uint8_t*)mem;
+    DevBlock block;
+    if (int rc = dev_alloc(L.size(), &block.p)) return rc;
+    uint8_t* m = block.bytes();
     std::vector<uint8_t> head(o_rec, 0);
-    std::memcpy(head.data() + o_fd, fd.data(), fd.size() * sizeof(WebpFrameDesc));
-    std::memcpy(head.data() + o_items, items.data(), items.size() * sizeof(WebpItem));
-    std::memcpy(head.data() + o_tiles, tile_items.data(), tile_items.size() * sizeof(WebpTileItem));
-    if (!forced_bytes.empty()) std::memcpy(head.data() + o_forced, forced_bytes.data(), forced_bytes.size());
+    head_put(head, o_fd, fd);
+    head_put(head, o_items, items);
+    head_put(head, o_tiles, tile_items);
+    head_put(head, o_forced, forced_bytes);
     int rc = upload_to(m, head.data(), head.size(), s);
     if (!rc) {
         const hipError_t e = hipMemsetAsync(m + o_rec, 0, o_bits - o_rec, s);
@@ -101,24 +104,12 @@ int encode_group(const std::vector<int>& entries, const impgpu_image* const* ima
     D.tile_bits = tb;
     D.lz = lz ? (WebpLz*)(m + o_lz) : nullptr;
     if (!rc) rc = launch_webp_encode(D, (long long)tile_items.size(), (long long)items.size(), nf, s);
-    // the first wait: the records
+    if (rc) return drained(rc);
     std::vector<WebpRec> recs((size_t)nf);
-    void *pin = nullptr, *token = nullptr;
-    if (!rc) rc = stage_begin(recs.size() * sizeof(WebpRec), &pin, &token);
-    if (!rc) {
-        const hipError_t e = hipMemcpyAsync(pin, D.recs, recs.size() * sizeof(WebpRec), hipMemcpyDeviceToHost, s);
-        if (e != hipSuccess) { set_error("hipMemcpyAsync(webp encode records)", e); rc = IMP_ERROR_DEVICE; }
-    }
-    if (rc) { (void)hipStreamSynchronize(s); dev_free(mem); return rc; }
-    stage_hold(token, true);
-    rc = lane_wait();
-    if (!rc) std::memcpy(recs.data(), pin, recs.size() * sizeof(WebpRec));
-    stage_hold(token, false);
-    if (rc) { dev_free(mem); return rc; }
+    if ((rc = fetch_records(D.recs, recs.size() * sizeof(WebpRec), recs.data(), "hipMemcpyAsync(webp encode records)"))) return rc;   // the first wait
     // the files' sizes; what fits is fetched
-    std::vector<size_t> at((size_t)nf, 0);
-    std::vector<char> fetch((size_t)nf, 0);
-    size_t total = 0;
+    AnswerFetch files;
+    std::vector<int> piece((size_t)nf, -1);
     for (int f = 0; f < nf; f++) {
         const int i = entries[(size_t)f];
         const size_t len = (size_t)recs[(size_t)f].file_len;
@@ -126,28 +117,11 @@ int encode_group(const std::vector<int>& entries, const impgpu_image* const* ima
             codes[i] = IMP_ERROR_DEVICE; lens[i] = 0; set_error_text("webp encode: a file outgrew its bound");
             continue;
         }
-        lens[i] = len;
-        if (len > caps[i]) { codes[i] = IMP_ERROR_MALLOC_FAILED; continue; }
-        codes[i] = IMP_OK;
-        fetch[(size_t)f] = 1;
-        at[(size_t)f] = total;
-        total += (len + 63) & ~size_t(63);
+        if (answer_fits(len, caps[i], &codes[i], &lens[i])) piece[(size_t)f] = files.add(m + fd[(size_t)f].out_off, len);
     }
-    if (total) {
-        if ((rc = stage_begin(total, &pin, &token))) { dev_free(mem); return rc; }
-        hipError_t e = hipSuccess;
-        for (int f = 0; f < nf && e == hipSuccess; f++)
-            if (fetch[(size_t)f])
-                e = hipMemcpyAsync((uint8_t*)pin + at[(size_t)f], m + fd[(size_t)f].out_off, (size_t)recs[(size_t)f].file_len, hipMemcpyDeviceToHost, s);
-        if (e != hipSuccess) { set_error("hipMemcpyAsync(webp encode download)", e); (void)hipStreamSynchronize(s); dev_free(mem); return IMP_ERROR_DEVICE; }
-        stage_hold(token, true);
-        rc = lane_wait();                                               // the second wait: the files
-        if (!rc)
-            for (int f = 0; f < nf; f++)
-                if (fetch[(size_t)f]) std::memcpy(outs[entries[(size_t)f]], (const uint8_t*)pin + at[(size_t)f], (size_t)recs[(size_t)f].file_len);
-        stage_hold(token, false);
-    }
-    dev_free(mem);
+    rc = files.run("hipMemcpyAsync(webp encode download)");            // the second wait
+    for (int f = 0; f < nf && !rc; f++)
+        if (piece[(size_t)f] >= 0) std::memcpy(outs[entries[(size_t)f]], files.at(piece[(size_t)f]), (size_t)recs[(size_t)f].file_len);
     return rc;
 }
 
@@ -222,11 +196,7 @@ int impgpu_batch_encode_webp(const impgpu_image* const* images, int count, unsig
 }
 
 int impgpu_image_encode_webp_ex(const impgpu_image* image, const unsigned char* forced_modes, unsigned char* out, size_t capacity, size_t* length) {
-    if (length) *length = 0;
-    if (!image || !out || !length) return IMP_ERROR_INVALID_ARGS;
-    int code = IMP_OK;
-    if (int rc = batch_encode(&image, forced_modes ? &forced_modes : nullptr, 1, &out, &capacity, length, &code, nullptr)) return rc;
-    return code;
+    return impgpu_image_encode_webp_flags(image, 0, forced_modes, out, capacity, length);
 }
 
 size_t impgpu_webp_encode_bound_flags(int width, int height, int channels, int flags) {

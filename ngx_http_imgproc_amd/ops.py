@@ -673,16 +673,21 @@ def jpeg_request_one_wait(blob, config, quality=86, **ops):
     return (0, out) if out is not None else (rc_enc or ecode[0] or IMP_ERROR_DEVICE, None)
 
 
+def _answer_arrays(images, bound, capacities=None, guard=0):
+    """What a batch encode call takes for `images` (an entry may be None) -> (handles, capacities, buffers, their addresses,
+    lengths, codes).  A capacity that `capacities` leaves open is bound(image); a buffer is `guard` bytes longer than its
+    capacity and filled with 0xA5, so that _answer can tell what the call wrote; the codes start at -1."""
+    m = max(1, len(images))
+    caps = [(bound(a) if a is not None else 0) if capacities is None or capacities[i] is None else int(capacities[i]) for i, a in enumerate(images)]
+    bufs = [np.full(max(1, c) + guard, 0xA5, np.uint8) for c in caps]
+    return ((C.c_void_p * m)(*[_handle(a) for a in images]), (C.c_size_t * m)(*caps), bufs, (C.c_void_p * m)(*[b.ctypes.data for b in bufs]),
+            (C.c_size_t * m)(), (C.c_int * m)(*([-1] * m)))
+
+
 def batch_encode_jpeg(images, quality=95):
     """impgpu_batch_encode_jpeg -> [(code, file bytes or None)] in the order of `images`."""
     n = len(images)
-    hs = (C.c_void_p * n)(*[im.h.value for im in images])
-    caps = [lib.impgpu_jpeg_encode_bound(im.shape[1], im.shape[0], im.shape[2]) for im in images]
-    bufs = [np.empty(max(1, c), dtype=np.uint8) for c in caps]
-    outs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-    ccaps = (C.c_size_t * n)(*caps)
-    lens = (C.c_size_t * n)()
-    codes = (C.c_int * n)()
+    hs, ccaps, bufs, outs, lens, codes = _answer_arrays(images, lambda im: lib.impgpu_jpeg_encode_bound(im.shape[1], im.shape[0], im.shape[2]))
     rc = lib.impgpu_batch_encode_jpeg(hs, n, int(quality), outs, ccaps, lens, codes)
     if rc:
         raise ImpError(rc, "impgpu_batch_encode_jpeg")
@@ -692,13 +697,7 @@ def batch_encode_jpeg(images, quality=95):
 def batch_encode_png(images, level=9):
     """impgpu_batch_encode_png -> [(code, file bytes or None)] in the order of `images`."""
     n = len(images)
-    hs = (C.c_void_p * n)(*[im.h.value for im in images])
-    caps = [lib.impgpu_png_encode_bound(im.shape[1], im.shape[0], im.shape[2]) for im in images]
-    bufs = [np.empty(max(1, c), dtype=np.uint8) for c in caps]
-    outs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-    ccaps = (C.c_size_t * n)(*caps)
-    lens = (C.c_size_t * n)()
-    codes = (C.c_int * n)()
+    hs, ccaps, bufs, outs, lens, codes = _answer_arrays(images, lambda im: lib.impgpu_png_encode_bound(im.shape[1], im.shape[0], im.shape[2]))
     rc = lib.impgpu_batch_encode_png(hs, n, int(level), outs, ccaps, lens, codes)
     if rc:
         raise ImpError(rc, "impgpu_batch_encode_png")
@@ -949,7 +948,7 @@ def _ints(values):
     return None if values is None else (C.c_int * max(1, len(values)))(*[int(v) for v in values])
 
 
-def _gif_out(rc, buf, length):
+def _answer(rc, buf, length):
     """(code, the file or None, *length, whether every byte the call had no business writing still holds the fill)"""
     n = length.value
     written = n if rc == 0 else 0
@@ -979,7 +978,7 @@ def encode_gif(album, time_ms=None, dispose=None, loop_count=-1, segment=0, capa
     else:
         rc = lib.impgpu_album_encode_gif_ex(album.h, _ints(time_ms), _ints(dispose), int(loop_count), int(segment), int(flags), buf.ctypes.data, cap,
                                             C.byref(n))
-    return _gif_out(rc, buf, n)
+    return _answer(rc, buf, n)
 
 
 def encode_gif_host(frames, time_ms=None, dispose=None, loop_count=-1, segment=0, capacity=None, guard=64, channels=None, flags=None, delta=False):
@@ -1003,7 +1002,7 @@ def encode_gif_host(frames, time_ms=None, dispose=None, loop_count=-1, segment=0
     else:
         rc = lib.impgpu_gif_encode_host_ex(ptrs, len(frames), ww, hh, cc if channels is None else channels, step, _ints(time_ms), _ints(dispose),
                                            int(loop_count), int(segment), int(flags), buf.ctypes.data, cap, C.byref(n))
-    return _gif_out(rc, buf, n)
+    return _answer(rc, buf, n)
 
 
 def gif_quantize_host(frame):
@@ -1025,19 +1024,12 @@ def batch_encode_gif(albums, time_ms=None, dispose=None, loop_counts=None, segme
     flags: None, or impgpu_batch_encode_gif_ex's; delta=True: impgpu_batch_encode_gif_ex2 with those flags and GIF_ENC_DELTA."""
     n = len(albums)
     m = max(1, n)
-    handles = (C.c_void_p * m)(*[_handle(a) for a in albums])
     keep_t = [_ints(None if time_ms is None else time_ms[i]) for i in range(n)]
     keep_d = [_ints(None if dispose is None else dispose[i]) for i in range(n)]
     tarr = (IP_ * m)(*[C.cast(t, IP_) if t is not None else IP_() for t in keep_t])
     darr = (IP_ * m)(*[C.cast(d, IP_) if d is not None else IP_() for d in keep_d])
     loops = (C.c_int * m)(*[-1 if loop_counts is None else int(loop_counts[i]) for i in range(n)])
-    caps = [(gif_encode_bound(a.shape[1], a.shape[0], a.count) if a is not None else 0) if capacities is None or capacities[i] is None else int(capacities[i])
-            for i, a in enumerate(albums)]
-    bufs = [np.full(max(1, c) + guard, 0xA5, np.uint8) for c in caps]
-    outs = (C.c_void_p * m)(*[b.ctypes.data for b in bufs])
-    carr = (C.c_size_t * m)(*caps)
-    lens = (C.c_size_t * m)()
-    codes = (C.c_int * m)(*([-1] * m))
+    handles, carr, bufs, outs, lens, codes = _answer_arrays(albums, lambda a: gif_encode_bound(a.shape[1], a.shape[0], a.count), capacities, guard)
     launches = C.c_int(-1)
     if delta:
         rc = lib.impgpu_batch_encode_gif_ex2(handles, tarr, darr, loops, n if count is None else count, int(segment), int(flags or 0) | GIF_ENC_DELTA, outs,
@@ -1048,7 +1040,7 @@ def batch_encode_gif(albums, time_ms=None, dispose=None, loop_counts=None, segme
     else:                                                                # impgpu_batch_encode_gif_ex
         rc = lib.impgpu_batch_encode_gif_ex(handles, tarr, darr, loops, n if count is None else count, int(segment), int(flags), outs, carr, lens,
                                             codes, C.byref(launches))
-    return rc, [_gif_out(codes[i], bufs[i], C.c_size_t(lens[i])) for i in range(n)], launches.value
+    return rc, [_answer(codes[i], bufs[i], C.c_size_t(lens[i])) for i in range(n)], launches.value
 
 
 WEBP_TILE_BITS = 4                            # IMPGPU_WEBP_TILE_BITS
@@ -1084,7 +1076,7 @@ def encode_webp(image, forced_modes=None, capacity=None, guard=64, flags=None):
     else:
         keep = _modes(forced_modes)
         rc = lib.impgpu_image_encode_webp_ex(image.h, keep.ctypes.data, buf.ctypes.data, cap, C.byref(n))
-    return _gif_out(rc, buf, n)
+    return _answer(rc, buf, n)
 
 
 def encode_webp_host(frame, forced_modes=None, capacity=None, guard=64, channels=None, flags=None):
@@ -1103,28 +1095,20 @@ def encode_webp_host(frame, forced_modes=None, capacity=None, guard=64, channels
     else:
         rc = lib.impgpu_webp_encode_host_flags(frame.ctypes.data, ww, hh, cc, frame.strides[0], int(flags), None if keep is None else keep.ctypes.data,
                                                buf.ctypes.data, cap, C.byref(n))
-    return _gif_out(rc, buf, n)
+    return _answer(rc, buf, n)
 
 
 def batch_encode_webp(images, capacities=None, count=None, guard=64, flags=None):
     """impgpu_batch_encode_webp: images (an entry may be None) -> (code, [(code, bytes or None, length, intact) ...],
     launches).  capacities default to webp_encode_bound.  flags: None, or impgpu_batch_encode_webp_flags'."""
     n = len(images)
-    m = max(1, n)
-    handles = (C.c_void_p * m)(*[_handle(a) for a in images])
-    caps = [(webp_encode_bound(a.shape[1], a.shape[0], a.shape[2], flags) if a is not None else 0) if capacities is None or capacities[i] is None
-            else int(capacities[i]) for i, a in enumerate(images)]
-    bufs = [np.full(max(1, c) + guard, 0xA5, np.uint8) for c in caps]
-    outs = (C.c_void_p * m)(*[b.ctypes.data for b in bufs])
-    carr = (C.c_size_t * m)(*caps)
-    lens = (C.c_size_t * m)()
-    codes = (C.c_int * m)(*([-1] * m))
+    handles, carr, bufs, outs, lens, codes = _answer_arrays(images, lambda a: webp_encode_bound(a.shape[1], a.shape[0], a.shape[2], flags), capacities, guard)
     launches = C.c_int(-1)
     if flags is None:
         rc = lib.impgpu_batch_encode_webp(handles, n if count is None else count, outs, carr, lens, codes, C.byref(launches))
     else:
         rc = lib.impgpu_batch_encode_webp_flags(handles, n if count is None else count, int(flags), outs, carr, lens, codes, C.byref(launches))
-    return rc, [_gif_out(codes[i], bufs[i], C.c_size_t(lens[i])) for i in range(n)], launches.value
+    return rc, [_answer(codes[i], bufs[i], C.c_size_t(lens[i])) for i in range(n)], launches.value
 
 
 def batch_filters(ptr, stride, w, h, c, step, count, filters, allow_experiments=1, stream=None):
