@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from resize_guard import GUARD_BYTES, GUARD_ROWS
+from test_gpu_exit_guard import layouts_used as exit_layouts_used
 from test_gpu_operator_guard import layouts_used
 from window_guard import KINDS, WindowLayout, describe, guard_compare, layout_for, locate, make_parent
 
@@ -16,15 +17,23 @@ def _frames(lay, n):
 
 
 def test_every_layout_of_the_operator_tests_is_in_its_class():
-    n = 0
-    for lay in layouts_used():
-        where = (lay.cls, lay.row_bytes, lay.rows, lay.count, lay.offset, lay.step, lay.stride)
-        assert lay.in_class(), where
-        guard = max(GUARD_ROWS * lay.step, GUARD_BYTES)
-        assert lay.step >= lay.row_bytes and lay.offset >= guard and lay.total - lay.last >= guard, where
-        assert lay.stride >= (lay.rows + GUARD_ROWS) * lay.step, where            # guard rows between frames
-        n += 1
+    n = exits = 0
+    for used in (layouts_used, exit_layouts_used):
+        for lay in used():
+            where = (lay.cls, lay.row_bytes, lay.rows, lay.count, lay.offset, lay.step, lay.stride)
+            assert lay.in_class(), where
+            guard = max(GUARD_ROWS * lay.step, GUARD_BYTES)
+            assert lay.step >= lay.row_bytes and lay.offset >= guard and lay.total - lay.last >= guard, where
+            assert lay.stride >= (lay.rows + GUARD_ROWS) * lay.step, where            # guard rows between frames
+            if used is exit_layouts_used:
+                # the exits' windows: a padded pitch, and a JPEG block's 15 columns past a row's end (60 bytes of BGRA) or a
+                # download's step * rows bytes from the last window's start are still the parent's
+                assert lay.step > lay.row_bytes and lay.total - lay.last >= 60 + lay.step, where
+                exits += 1
+            else:
+                n += 1
     assert n > 100
+    assert exits > 100
 
 
 def test_the_kinds_differ_where_the_kernels_look():
