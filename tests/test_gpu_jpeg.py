@@ -676,3 +676,49 @@ def test_files_nobody_chose_every_way_of_decoding_them(gpu, monkeypatch):
             got = im.numpy()
             im.release()
             assert np.array_equal(got, want), (tag, k, want.shape)
+
+
+def test_trace_3_reads_every_files_entry_states_where_the_kernels_left_them():
+    """IMPGPU_JPEG_TRACE=3 prints each chunk's entry state and slot count, `ce <chunk> <state> <slots>`: the host model
+    (impgpu_jpeg_coefficients, how = 1) as it computes them, a device decode as it reads them back from the file's work
+    area.  Three files decoded by ONE call -- the second and third lie at a work_off that is not zero -- must give, file by
+    file, the model's lines, and Pillow's pixels.  (Files this small are cut into the same 32-byte chunks by both.)  In a
+    child process: the lines go to the process's stderr."""
+    import subprocess
+    import sys
+
+    names = ["c420_q90_67x45", "gray_q90_57x43", "c444_q90_48x40"]
+    code = r'''
+import hashlib, os, sys
+import numpy as np
+import ngx_http_imgproc_amd as imp
+blobs = [open(os.path.join(%r, n + ".jpg"), "rb").read() for n in %r]
+out = np.zeros(1 << 16, np.int16)
+for b in blobs:
+    assert imp.lib.impgpu_jpeg_coefficients(b, len(b), 1, out.ctypes.data, out.size, None) == 0
+    sys.stderr.write("== file\n"); sys.stderr.flush()
+sys.stderr.write("== device\n"); sys.stderr.flush()
+imp.env_start(0)
+for code, im in imp.batch_decode_jpeg(blobs):
+    assert code == 0
+    print(hashlib.sha256(im.numpy().tobytes()).hexdigest())
+    im.release()
+imp.env_destroy()
+''' % (GOLD, names)
+    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120, cwd=ROOT,
+                       env=dict(os.environ, IMPGPU_JPEG_HUFF="device", IMPGPU_JPEG_TRACE="3", PYTHONPATH=ROOT))
+    assert p.returncode == 0, p.stderr[-2000:]
+    sha = {c["name"]: c["sha256_bgr"] for c in MANIFEST["cases"]}
+    assert p.stdout.split() == [sha[n] for n in names]
+    model, _, device = p.stderr.partition("== device\n")
+    model = [[ln for ln in part.split("\n") if ln.startswith("ce ")] for part in model.split("== file\n")[:-1]]
+    assert len(model) == len(names) and all(len(m) >= 2 for m in model)
+    # the device's lines come file after file, each file's chunks counted from 0: cut them where the model's lists end
+    device = [ln for ln in device.split("\n") if ln.startswith("ce ")]
+    chunks = [int(ln.split(":")[1].split()[0]) for ln in p.stderr.split("\n") if ln.startswith("jpeg ") and " chunks of " in ln]
+    assert chunks == [len(m) for m in model]
+    at = 0
+    for name, m in zip(names, model):
+        assert device[at:at + len(m)] == m, name
+        at += len(m)
+    assert at == len(device)
