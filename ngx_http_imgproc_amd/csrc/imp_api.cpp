@@ -668,175 +668,6 @@ int impgpu_blend_with_paper(impgpu_image* image) {
     return launch_blend_paper(image->d, (long long)image->fstride, image->w, image->h, image->step, image->frames, env_stream());
 }
 
-static int gif_compose(const impgpu_gif_page* pages, int count, int destructive, int page, bool as_album, impgpu_image** frames) {
-    if (!pages || !frames || count <= 0 || page < -1) return IMP_ERROR_INVALID_ARGS;   // page < -1: the reference reads Frames[page] below the array
-    if (page != -1) {                                              // advancedio.c:111-116: a page request is always a
-        destructive = 1;                                           // destructive walk, and a page past the end is page 0
-        if (page > count - 1) page = 0;
-    }
-    if (int rc = need_env()) return rc;
-    const int cw = pages[0].width, ch = pages[0].height;           // advancedio.c:133-136: canvas = first page
-    if (cw <= 0 || ch <= 0) return IMP_ERROR_INVALID_ARGS;
-    const int npages = page >= 0 ? page + 1 : count;               // the walk stops at the requested page (:249-251)
-    const int nout = page >= 0 ? 1 : count;
-    // one blob: page table | output pointers | palettes | index planes
-    std::vector<GifPageDev> meta((size_t)npages);
-    size_t off = (size_t)npages * sizeof(GifPageDev) + (size_t)nout * sizeof(uint8_t*);
-    off = (off + 15) & ~size_t(15);
-    for (int f = 0; f < npages; f++) {
-        const impgpu_gif_page& p = pages[f];
-        if (!p.indices || !p.palette || p.width <= 0 || p.height <= 0 || p.pitch < p.width) return IMP_ERROR_INVALID_ARGS;
-        meta[f].pal_off = (long long)off; off += 1024;
-        meta[f].idx_off = (long long)off; off += ((size_t)p.pitch * p.height + 15) & ~size_t(15);
-        meta[f].w = p.width; meta[f].h = p.height; meta[f].pitch = p.pitch; meta[f].left = p.left; meta[f].top = p.top;
-        meta[f].dispose = p.dispose; meta[f].key = p.transparency_key; meta[f].pad = 0;
-    }
-    std::vector<impgpu_image*> imgs((size_t)nout, nullptr);
-    auto drop = [&]() { for (impgpu_image* im : imgs) if (im) image_delete(im); };
-    if (as_album) {                                                // every output frame in one block behind one handle
-        imgs.resize(1);
-        if (int rc = image_new_album(cw, ch, 4, nout, &imgs[0])) return rc;
-    } else {
-        for (int i = 0; i < nout; i++)
-            if (int rc = image_new(cw, ch, 4, &imgs[i])) { drop(); return rc; }
-    }
-    std::vector<uint8_t> blob(off, 0);
-    std::memcpy(blob.data(), meta.data(), (size_t)npages * sizeof(GifPageDev));
-    uint8_t** optr = (uint8_t**)(blob.data() + (size_t)npages * sizeof(GifPageDev));
-    for (int i = 0; i < nout; i++) optr[i] = as_album ? imgs[0]->d + (size_t)i * imgs[0]->fstride : imgs[i]->d;
-    for (int f = 0; f < npages; f++) {
-        std::memcpy(blob.data() + meta[f].pal_off, pages[f].palette, 1024);
-        std::memcpy(blob.data() + meta[f].idx_off, pages[f].indices, (size_t)pages[f].pitch * pages[f].height);
-    }
-    void* dev = nullptr;
-    hipStream_t s = env_stream();
-    if (int rc = upload_small(blob.data(), blob.size(), &dev, s)) { drop(); return rc; }
-    const uint8_t* d = (const uint8_t*)dev;
-    int rc = launch_gif_compose(d, (const GifPageDev*)d, (uint8_t* const*)(d + (size_t)npages * sizeof(GifPageDev)), npages,
-                                cw, ch, imgs[0]->step, destructive ? 1 : 0, page, s);
-    dev_free(dev);                                                 // stream-ordered: after the kernel
-    if (rc) { drop(); return rc; }
-    for (size_t i = 0; i < imgs.size(); i++) frames[i] = imgs[i];
-    return IMP_OK;
-}
-
-int impgpu_gif_compose(const impgpu_gif_page* pages, int count, int destructive, int page, impgpu_image** frames) {
-    return gif_compose(pages, count, destructive, page, false, frames);
-}
-
-int impgpu_gif_compose_album(const impgpu_gif_page* pages, int count, int destructive, int page, impgpu_image** album) {
-    return gif_compose(pages, count, destructive, page, true, album);
-}
-
-// Many files, one compose launch.  Every entry is judged as gif_compose judges it alone; the accepted ones' page tables,
-// output pointers, palettes and index planes are laid out in ONE blob behind the descriptor table (launch_gif_compose_mixed),
-// which is one upload and one launch.  The blob is built in the pinned staging buffer itself and leaves in pieces of
-// GIF_PIECE bytes while the next entries are still being copied in (one pass over the pages, the copy to the device beside
-// it: built in a vector and uploaded whole, 16 files of 40 MB took four times the lone calls' loop).  A blob that would
-// pass the staging cap is cut at an entry boundary: one upload and one launch per group, in entry order (an entry that is
-// past the cap by itself goes alone, as its lone call would).
-static constexpr size_t GIF_PIECE = size_t(2) << 20;
-int impgpu_batch_gif_compose(const impgpu_gif_set* sets, int count, impgpu_image** albums, int* codes, int* launches) {
-    if (launches) *launches = 0;
-    if (count < 0 || count > 256 || (count > 0 && (!sets || !albums || !codes))) return IMP_ERROR_INVALID_ARGS;
-    for (int i = 0; i < count; i++) albums[i] = nullptr;
-    if (int rc = need_env()) {
-        for (int i = 0; i < count; i++) codes[i] = rc;
-        return rc;
-    }
-    struct Plan { int entry, npages, nout, destructive, only; size_t bytes; };
-    auto page_bytes = [](const impgpu_gif_page& p) { return ((size_t)p.pitch * p.height + 15) & ~size_t(15); };
-    auto head_bytes = [](int npages, int nout) { return ((size_t)npages * sizeof(GifPageDev) + (size_t)nout * sizeof(uint8_t*) + 15) & ~size_t(15); };
-    std::vector<Plan> plans;
-    for (int i = 0; i < count; i++) {
-        const impgpu_gif_set& st = sets[i];
-        int destructive = st.destructive, page = st.page;
-        codes[i] = IMP_ERROR_INVALID_ARGS;
-        if (!st.pages || st.count <= 0 || page < -1) continue;
-        if (page != -1) {                                          // (gif_compose: a page request walks destructively, past the end = page 0)
-            destructive = 1;
-            if (page > st.count - 1) page = 0;
-        }
-        if (st.pages[0].width <= 0 || st.pages[0].height <= 0) continue;
-        Plan pl{i, page >= 0 ? page + 1 : st.count, page >= 0 ? 1 : st.count, destructive ? 1 : 0, page, 0};
-        bool ok = true;
-        pl.bytes = head_bytes(pl.npages, pl.nout);
-        for (int f = 0; f < pl.npages && ok; f++) {
-            const impgpu_gif_page& p = st.pages[f];
-            ok = p.indices && p.palette && p.width > 0 && p.height > 0 && p.pitch >= p.width;
-            if (ok) pl.bytes += 1024 + page_bytes(p);
-        }
-        if (!ok) continue;
-        codes[i] = image_new_album(st.pages[0].width, st.pages[0].height, 4, pl.nout, &albums[i]);
-        if (codes[i] == IMP_OK) plans.push_back(pl);
-    }
-    const size_t cap = stage_cap();
-    hipStream_t s = env_stream();
-    int issued = 0;
-    for (size_t g0 = 0; g0 < plans.size();) {
-        // the group [g0, g1): as many entries as the cap and the grid take
-        size_t g1 = g0, bytes = 0;
-        long long blocks = 0;
-        while (g1 < plans.size()) {
-            const impgpu_image* im = albums[plans[g1].entry];
-            const long long nb = ((long long)im->w * im->h + 255) / 256;
-            const size_t table = gif_mix_table_bytes((int)(g1 - g0 + 1));
-            if (g1 > g0 && ((cap && table + bytes + plans[g1].bytes > cap) || (blocks + nb) * 8 > 0x7fffffffLL)) break;
-            bytes += plans[g1].bytes;
-            blocks += nb;
-            g1++;
-        }
-        const int n = (int)(g1 - g0);
-        const size_t total = gif_mix_table_bytes(n) + bytes;
-        std::vector<GifMixItem> items((size_t)n);
-        MixStaged up{};
-        int rc = stage_begin(total, &up.host, &up.token);
-        if (!rc && (rc = dev_alloc(total, &up.dev)) != IMP_OK) (void)stage_upload_part(up.token, 0, nullptr, 0, true);
-        uint8_t* const whole = (uint8_t*)up.host;
-        size_t off = gif_mix_table_bytes(n), sent = off;
-        for (int k = 0; k < n && !rc; k++) {
-            const Plan& pl = plans[g0 + (size_t)k];
-            const impgpu_gif_set& st = sets[pl.entry];
-            const impgpu_image* im = albums[pl.entry];
-            GifMixItem& it = items[(size_t)k];
-            it.pages_off = off;
-            it.outs_off = off + (size_t)pl.npages * sizeof(GifPageDev);
-            it.npages = pl.npages; it.cw = im->w; it.ch = im->h; it.ostep = im->step; it.destructive = pl.destructive; it.only = pl.only;
-            GifPageDev* meta = (GifPageDev*)(whole + it.pages_off);
-            uint8_t** optr = (uint8_t**)(whole + it.outs_off);
-            for (int o = 0; o < pl.nout; o++) optr[o] = im->d + (size_t)o * im->fstride;
-            off += head_bytes(pl.npages, pl.nout);
-            for (int f = 0; f < pl.npages; f++) {
-                const impgpu_gif_page& p = st.pages[f];
-                meta[f].pal_off = (long long)off;
-                std::memcpy(whole + off, p.palette, 1024);
-                off += 1024;
-                meta[f].idx_off = (long long)off;
-                std::memcpy(whole + off, p.indices, (size_t)p.pitch * p.height);
-                off += page_bytes(p);
-                meta[f].w = p.width; meta[f].h = p.height; meta[f].pitch = p.pitch; meta[f].left = p.left; meta[f].top = p.top;
-                meta[f].dispose = p.dispose; meta[f].key = p.transparency_key; meta[f].pad = 0;
-            }
-            if (off - sent >= GIF_PIECE || k == n - 1) {
-                rc = stage_upload_part(up.token, sent, (uint8_t*)up.dev + sent, off - sent, false);
-                if (rc) { (void)stage_upload_part(up.token, 0, up.dev, 0, true); dev_free(up.dev); }
-                sent = off;
-            }
-        }
-        if (!rc) rc = launch_gif_compose_mixed(items.data(), n, up, total, s);     // (sends the table, fences the buffer, frees up.dev)
-        if (rc == IMP_OK) issued++;
-        else
-            for (size_t k = g0; k < g1; k++) {                      // this group's entries fail together; the others stand
-                image_delete(albums[plans[k].entry]);
-                albums[plans[k].entry] = nullptr;
-                codes[plans[k].entry] = rc;
-            }
-        g0 = g1;
-    }
-    if (launches) *launches = issued;
-    return IMP_OK;
-}
-
 // impgpu_image_download_fi for every frame of an album: each frame's flip and repack into one device block, ONE copy
 // into pinned staging, one wait, then the rows into the caller's bitmaps.
 int impgpu_album_download_fi(const impgpu_image* album, int bpp, unsigned char* const* bits, const int* pitches) {

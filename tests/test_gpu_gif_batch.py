@@ -103,6 +103,29 @@ def test_all_bad_launches_nothing_and_the_count_is_checked(gpu, eight):
     assert gpu.lib.impgpu_batch_gif_compose(None, 2, None, None, None) == gpu.IMP_ERROR_INVALID_ARGS
 
 
+def test_a_call_that_leaves_in_several_pieces(gpu):
+    """Five albums of nine full-canvas 300 x 200 noise pages.  An entry is 512 + 9 * (1024 + 60 000) = 549 728 bytes of the
+    blob, so the fourth ends 2 198 912 bytes behind the table -- past the 2 MiB at which a piece of the staging buffer leaves
+    -- and the fifth is the last piece: one launch, every album the oracle's and the lone call's."""
+    rng = np.random.default_rng(90)
+    sets = [([page(rng.integers(0, 256, (200, 300), dtype=np.uint8), dispose=(f + i) % 4, key=(-1, 3, 255)[f % 3], pal=palette(900 + 10 * i + f % 2))
+              for f in range(9)], bool(i & 1), -1) for i in range(5)]
+    up16 = lambda v: (v + 15) & ~15
+    entry = [up16(9 * 48 + 9 * 8) + sum(1024 + up16(p["indices"].size) for p in pages) for pages, _, _ in sets]
+    assert entry == [549728] * 5 and sum(entry[:3]) < (2 << 20) < sum(entry[:4])
+    rc, albums, codes, launches = gpu.batch_gif_compose(sets)
+    assert rc == 0 and codes == [0] * 5 and launches == 1
+    for i, (pages, destructive, pg) in enumerate(sets):
+        rc_o, want = orc.gif_compose(pages, destructive, pg)
+        rc1, alone = gpu.gif_compose(pages, destructive, pg, album=True)
+        got = albums[i].frames()
+        assert rc_o == 0 and rc1 == 0 and len(got) == len(want) == 9, i
+        for f, (g, o, a) in enumerate(zip(got, want, alone.frames())):
+            assert g.shape == o.shape and np.array_equal(g, o) and np.array_equal(g, a), (i, f)
+        alone.release()
+        albums[i].release()
+
+
 def test_a_blob_past_the_staging_cap_is_cut_at_an_entry():
     """IMPGPU_STAGE_CAP_MB is read once per process: a child with a 1 MB cap composes four albums of 0.7 MB of pages each
     (no two fit one blob: a launch per entry) and an album that is past the cap by itself (alone, like its lone call)."""

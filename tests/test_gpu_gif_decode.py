@@ -3,6 +3,7 @@ page of every file of the call on the device (one wavefront per page) into the i
 two launches per call, one wait.  Every album must be what the oracle's LoadGIF loop (advancedio.c:204-247) gives for the
 model's pages (tests/gif_writer.py, pinned against Pillow in test_gif_decode_host.py), what the lone call gives, and what
 impgpu_gif_compose gives for those pages.  Exact comparisons throughout."""
+import functools
 import os
 import subprocess
 import sys
@@ -102,6 +103,49 @@ def test_eight_files_two_launches_equal_the_oracle_the_lone_call_and_the_compose
             assert g.shape == o.shape and np.array_equal(g, o), (i, f)
             assert np.array_equal(g, a) and np.array_equal(g, c), (i, f)
         alone.release(); composed.release(); albums[i].release()
+
+
+@functools.lru_cache(maxsize=None)
+def several_pieces():
+    """Five files of nine full-canvas 300 x 200 noise pages, and the oracle's albums: [(file, model pages, destructive, page)],
+    [frames].  Noise does not compress, so a page's stream is longer than its 60 000 indices and the first four files put more
+    than 2 MiB into the staging blob (asserted from the writer's streams): a piece of the buffer leaves before the last file
+    has been copied in.  Nine streams are encoded; the files take them in turn, each page with a table, disposal and key of its own."""
+    rng = np.random.default_rng(91)
+    noise = [rng.integers(0, 256, (200, 300), dtype=np.uint8) for _ in range(9)]
+    streams = [G.page_stream(G.make_page(idx, mcs=8)) for idx in noise]
+    up16 = lambda v: (v + 15) & ~15
+    files = []
+    for i in range(5):
+        pages = [G.make_page(noise[(f + i) % 9], palette=rgb_table(256, 40 + 9 * i + f), gce=dict(dispose=(f + i) % 4, key=(-1, 3, 255)[f % 3], delay=f),
+                             mcs=8, lzw=streams[(f + i) % 9]) for f in range(9)]
+        files.append((G.write(pages), G.model(pages), bool(i & 1), -1))
+    entry = up16(9 * 48 + 9 * 8) + sum(1024 + up16(len(s)) for s in streams)
+    assert min(len(s) for s in streams) > 60000 and 4 * entry > (2 << 20)
+    want = []
+    for blob, pages, destructive, pg in files:
+        rc, frames = orc.gif_compose(pages, destructive, pg)
+        assert rc == 0 and len(frames) == 9
+        want.append(frames)
+    return files, want
+
+
+def check_several_pieces(gpu, flags, expect_launches):
+    files, want = several_pieces()
+    rc, albums, codes, launches = gpu.batch_decode_gif([(b, d, p) for b, _, d, p in files], flags=flags)
+    assert rc == 0 and codes == [0] * 5 and launches == expect_launches
+    for i, (blob, pages, destructive, pg) in enumerate(files):
+        rc1, alone = gpu.decode_gif(blob, destructive, pg, flags=flags)
+        got = albums[i].frames()
+        assert rc1 == 0 and len(got) == 9, i
+        for f, (g, o, a) in enumerate(zip(got, want[i], alone.frames())):
+            assert g.shape == o.shape and np.array_equal(g, o) and np.array_equal(g, a), (i, f)
+        alone.release()
+        albums[i].release()
+
+
+def test_a_call_that_leaves_in_several_pieces(gpu):
+    check_several_pieces(gpu, 0, 2)
 
 
 def bad_files():

@@ -16,7 +16,7 @@ import oracle_lib as orc
 from conftest import ROOT
 from test_gif_decode_host import rgb_table
 from test_gif_split_host import cut_cases, damage_behind_a_cut, model_counts, noise, page_file
-from test_gpu_gif_decode import bad_files, the_eight
+from test_gpu_gif_decode import bad_files, check_several_pieces, the_eight
 
 pytestmark = pytest.mark.gpu
 
@@ -107,6 +107,10 @@ def test_twenty_segments_and_an_album_of_small_pages_in_one_call(gpu):
     same(albums, want, ["320x240", "album"])
     same(plain, want, ["320x240", "album"])
     release(albums + plain)
+
+
+def test_a_call_that_leaves_in_several_pieces_with_the_flag(gpu):
+    check_several_pieces(gpu, gpu.GIF_SPLIT, 4)
 
 
 def test_damage_behind_a_cut_between_good_neighbours(gpu, eight, cuts):
