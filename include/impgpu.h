@@ -1044,6 +1044,79 @@ size_t impgpu_webp_encode_bound_flags(int width, int height, int channels, int f
  * (256..511: FreeImage's WEBP_LOSSLESS); otherwise 0.  A pure accessor: the parse and its error codes are unchanged. */
 int impgpu_request_webp_lossless(const impgpu_request* request);
 
+/* ---- WEBP UPLOADS in, LOSSLESS, decoded ON THE DEVICE (opt-in: nothing calls these by default; the broker only with
+ *      --webp-accept lossless).  THE FRAME is what the reference's route gives for the same file -- FreeImage's WebP plugin,
+ *      ConvertTo32Bits, LoadSingle (advancedio.c:276-318), then impgpu_image_upload_fi32: 4 channels, top-down, B,G,R,A; A is
+ *      the decoded alpha when the VP8L header's alpha_is_used bit is set and 255 otherwise (Pillow: mode RGBA with the bit,
+ *      RGB without).  `channels` is always 4.
+ *      TAKEN: a RIFF / WEBP file whose image is ONE VP8L chunk, alone or inside a VP8X container (ICCP, EXIF, XMP and unknown
+ *      chunks are skipped, as libwebp's plain decode skips them); version 0; any width and height the format can say (16384
+ *      a side) up to IMPGPU_WEBP_DEC_MAX_PIXELS pixels (8192 x 8192); all of VP8L: the four transforms, each at most once, in
+ *      any order; colour indexing with 1, 2, 4 and 8 pixels a value (an index past the palette is 0x00000000); the colour
+ *      cache at 1..11 bits; the entropy image with any number of prefix-code groups; normal and simple prefix codes with the
+ *      repeat codes 16, 17, 18 and max_symbol; backward references with all 120 mapped distance codes and the plain ones
+ *      beyond, a mapped distance below 1 being 1.
+ *      IMP_ERROR_UNSUPPORTED (decode on the host as before): a VP8 (lossy) image, ANIM / ANMF, ALPH, a version other than 0,
+ *      more pixels than the limit, or not a WebP at all.
+ *      IMP_ERROR_DECODE_FAILED: a chunk size that runs past the file; a transform that appears twice; a colour-cache size
+ *      outside 1..11; a prefix code libwebp refuses (no symbol at all, over-subscribed, incomplete -- but exactly one symbol
+ *      of length 1..14 is the code of zero bits); a repeat past the alphabet, max_symbol past it; a colour-cache index when
+ *      no cache exists; a distance before the first pixel; a match that runs past the image; a stream that runs past its
+ *      chunk (anywhere: in the headers, the sub-images or the pixels).  Judged per file: a bad file changes no other file's
+ *      result.
+ *      HOW: the host reads what lies in front of the main image's pixel stream (the container, the header, the transforms
+ *      with their small sub-images, the cache size, the entropy image, every group's code lengths) with the lanes' own
+ *      decoder; the compressed bytes, the code lengths, the sub-images and a descriptor per file go up in ONE upload a group
+ *      (one pinned block, one device block).  IMPGPU_WEBP_DEC_LAUNCHES (3) kernels a group, whatever it holds:
+ *      k_webp_dec_tables (a wavefront per prefix code builds and judges every group's lookup tables, in global memory),
+ *      k_webp_dec_pixels (a wavefront per file, in rounds: stage words, decode symbols wave-uniformly into a token list,
+ *      emit in token order -- colour-cache tokens are resolved in token order by one lane, not side by side), and
+ *      k_webp_dec_inverse (a workgroup per file undoes the transforms last to first, the predictor with rows skewed two
+ *      pixels apart, and writes B,G,R,A).  A call is cut into groups under $IMPGPU_STAGE_CAP_MB like the other batch calls.
+ *      ONE wait per call: for the files' status words.
+ *      MEASURED (profiles/webp_decode_probe.json, tools/webp_decode_probe.py; one session, Pillow-encoded files; the call against
+ *      Pillow's decode of the same file on one core + impgpu_image_upload): a lone 640x480 file 201.5 / 4.5 ms photo-like,
+ *      60.8 / 2.3 dithered 256-colour, 0.58 / 1.24 flat; a lone 1920x1080 file 1490 / 30.8, 471 / 15.1, 5.7 / 8.1; 64 files of
+ *      320x240 54.8 / 75.0, 20.1 / 35.6, 0.92 / 21.1.  A wave on a sequential bit stream LOSES to the host for a lone file, by
+ *      27-48x on everything but flat colour: k_webp_dec_pixels is 97-99 % of those calls (199.3 of 201.5 ms: 0.65 us a
+ *      literal pixel, four dependent table reads), k_webp_dec_tables 46-73 us, k_webp_dec_inverse 0.4-2.1 ms at 640x480 and
+ *      4.9-15.4 ms at 1920x1080, the host front 0.02-0.22 ms a file.  The files of a call decode side by side, a wave each, so
+ *      a call takes what its slowest file takes: 64 files are AHEAD of the host route (1.4x photo-like, 1.8x dithered, 23x
+ *      flat), and the crossover lies near 45 photo-like or 35 dithered files of 320x240 a call. ---- */
+#define IMPGPU_WEBP_DEC_MAX_PIXELS (1 << 26)
+#define IMPGPU_WEBP_DEC_LAUNCHES 3
+#define IMPGPU_WEBP_DEC_INFO_WORDS 8
+/* the feature word, info[0] of impgpu_webp_decode_host: what the file uses (the tests prove their coverage with it) */
+#define IMPGPU_WEBP_DEC_F_PREDICTOR      0x0001
+#define IMPGPU_WEBP_DEC_F_COLOR          0x0002
+#define IMPGPU_WEBP_DEC_F_SUB_GREEN      0x0004
+#define IMPGPU_WEBP_DEC_F_INDEXING       0x0008
+#define IMPGPU_WEBP_DEC_F_CACHE          0x0010   /* a colour cache, in the main image or a sub-image */
+#define IMPGPU_WEBP_DEC_F_GROUPS         0x0020   /* more than one prefix-code group */
+#define IMPGPU_WEBP_DEC_F_BACKREF        0x0040
+#define IMPGPU_WEBP_DEC_F_SIMPLE         0x0080   /* a simple prefix code */
+#define IMPGPU_WEBP_DEC_F_DIST_ABOVE_24  0x0100   /* a distance code above 24 */
+#define IMPGPU_WEBP_DEC_F_DIST_CLAMPED   0x0200   /* a mapped distance below 1 that became 1 */
+#define IMPGPU_WEBP_DEC_F_BUNDLE_1       0x0400   /* colour indexing, one pixel a value (more than 16 colours) */
+#define IMPGPU_WEBP_DEC_F_BUNDLE_2       0x0800   /* two pixels a value (5..16 colours) */
+#define IMPGPU_WEBP_DEC_F_BUNDLE_4       0x1000   /* four (3..4 colours) */
+#define IMPGPU_WEBP_DEC_F_BUNDLE_8       0x2000   /* eight (1..2 colours) */
+#define IMPGPU_WEBP_DEC_F_ALL            0x3fff
+/* The geometry alone: IMP_OK, or the refusal / failure the container and the five header bytes already show.  Host only. */
+int impgpu_webp_info(const unsigned char* blob, size_t size, int* width, int* height, int* channels);
+int impgpu_image_decode_webp(const unsigned char* blob, size_t size, impgpu_image** out);
+/* codes[i] / images[i] are what the single-file call returns alone (images[i] = NULL unless codes[i] == IMP_OK).
+ * IMP_ERROR_INVALID_ARGS = a NULL array or count outside 0..256, before any device is looked for; IMP_ERROR_DEVICE without
+ * an env (every codes[i] says so too); otherwise IMP_OK with the verdicts in codes[].  *launches (may be NULL): the
+ * kernels launched, IMPGPU_WEBP_DEC_LAUNCHES a group that holds a file the host front took. */
+int impgpu_batch_decode_webp(const unsigned char* const* blobs, const size_t* sizes, int count, impgpu_image** images, int* codes, int* launches);
+/* The same decoder with no device: the lanes' code, one lane after the other.  Writes the B,G,R,A frame (width * 4 bytes a
+ * row) into out[0, capacity); *width / *height are set once the header is read; IMP_ERROR_MALLOC_FAILED = capacity is
+ * smaller than width * height * 4 (nothing written).  info (may be NULL) receives IMPGPU_WEBP_DEC_INFO_WORDS ints: [0] the
+ * feature word, [1] prefix-code groups, [2] the main image's cache bits, [3] transforms, [4] the coded width, [5] the
+ * main image's status word (0 complete, 1 damaged, 2 ran past the chunk). */
+int impgpu_webp_decode_host(const unsigned char* blob, size_t size, unsigned char* out, size_t capacity, int* width, int* height, int* info);
+
 /* ---- batch entry points (benchmark / multi-frame albums: bridge.c:578,591,608,632).
  *      `count` frames of identical geometry, frame i at base + i*frame_stride bytes,
  *      already resident in HBM.  stream = hipStream_t to launch on (NULL = env stream).

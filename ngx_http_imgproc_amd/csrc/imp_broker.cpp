@@ -28,7 +28,8 @@
 // the answer's placement is the broker's own: it is written to the slot for the worker and never read back from there.
 //
 //   impgpu_broker [--name /impgpu-broker-0] [--device 0] [--slots 64] [--slot-mb 32] [--register-mb 8] [--threads 2] [--batch 64]
-//                 [--gather-us 0] [--png-accept none|all] [--png-inflate host|device] [--jpeg-accept none|progressive] [--supervise]
+//                 [--gather-us 0] [--png-accept none|all] [--png-inflate host|device] [--jpeg-accept none|progressive]
+//                 [--webp-accept none|lossless] [--supervise]
 //                 [--ready-file PATH]
 // --supervise: this process only forks and watches; the child is the broker.  A child that dies (a lost device, a bug) is
 // replaced by a FRESH child -- fork() from a parent that never touched the GPU, no exec of a process that did.
@@ -88,6 +89,10 @@ struct Options {
     // IMPGPU_JPEG_PROGRESSIVE, so a progressive upload (which the workers pass on whole) is answered instead of NOT_TAKEN;
     // none (the default) keeps impgpu_batch_decode_jpeg_prepared.
     int jpeg_accept = 0;
+    // --webp-accept lossless: an IMPB_IN_FILE request whose bytes start RIFF....WEBP joins the batch's one
+    // impgpu_batch_decode_webp call (lossless VP8L, decoded on the device); what that call refuses -- a lossy or animated
+    // file, damage -- is NOT_TAKEN like the other decode refusals.  none (the default): such a file is NOT_TAKEN as before.
+    int webp_accept = 0;
     bool supervise = false;
     std::string ready_file;
 };
@@ -281,6 +286,7 @@ void prepare(Req& r, const Segment& S) {
 }
 
 bool is_jpeg(const uint8_t* p, uint64_t n) { return n >= 3 && p[0] == 0xFF && p[1] == 0xD8 && p[2] == 0xFF; }
+bool is_webp(const uint8_t* p, uint64_t n) { return n >= 12 && !std::memcmp(p, "RIFF", 4) && !std::memcmp(p + 8, "WEBP", 4); }
 bool is_png(const uint8_t* p, uint64_t n) {
     static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
     return n >= 8 && !std::memcmp(p, sig, 8);
@@ -517,6 +523,26 @@ struct Worker {
                 png_sizes[j] = (size_t)reqs[pngs[j]].q.in_bytes;
             }
             decoded(pngs, impgpu_batch_decode_png_ex(png_blobs.data(), png_sizes.data(), (int)m, O.png_accept | O.png_inflate, imgs.data(), codes.data(), nullptr));
+        }
+        // --webp-accept lossless: every WebP upload of the batch in ONE impgpu_batch_decode_webp call, behind the PNG call
+        if (O.webp_accept) {
+            std::vector<size_t> webps;
+            for (size_t k = 0; k < n; k++) {
+                const Req& r = reqs[k];
+                if (!r.done && !r.img && r.q.in_kind == IMPB_IN_FILE && is_webp(r.in, r.q.in_bytes)) webps.push_back(k);
+            }
+            if (!webps.empty()) {
+                const size_t m = webps.size();
+                std::vector<const unsigned char*> blobs(m);
+                std::vector<size_t> sizes(m);
+                imgs.assign(m, nullptr);
+                codes.assign(m, IMP_OK);
+                for (size_t j = 0; j < m; j++) {
+                    blobs[j] = reqs[webps[j]].in;
+                    sizes[j] = (size_t)reqs[webps[j]].q.in_bytes;
+                }
+                decoded(webps, impgpu_batch_decode_webp(blobs.data(), sizes.data(), (int)m, imgs.data(), codes.data(), nullptr));
+            }
         }
         // every GIF of the batch: one upload of all their pages and ONE compose launch (advancedio.c:204-247), behind the file
         // decodes on the lane's stream.  The answer's image is the album; a page request (in_page >= 0) makes an album of one.
@@ -834,7 +860,7 @@ int supervise(const Options& o) {
 
 static const char USAGE[] =
     "usage: impgpu_broker [--name /impgpu-broker-0] [--device 0] [--slots 64] [--slot-mb 32] [--register-mb 8] [--threads 2] [--batch 64] "
-    "[--gather-us 0] [--png-accept none|all] [--png-inflate host|device] [--jpeg-accept none|progressive] [--supervise] [--ready-file PATH]\n";
+    "[--gather-us 0] [--png-accept none|all] [--png-inflate host|device] [--jpeg-accept none|progressive] [--webp-accept none|lossless] [--supervise] [--ready-file PATH]\n";
 
 int main(int argc, char** argv) {
     Options o;
@@ -870,6 +896,12 @@ int main(int argc, char** argv) {
             if (v == "progressive") o.jpeg_accept = IMPGPU_JPEG_PROGRESSIVE;
             else if (v == "none") o.jpeg_accept = 0;
             else { std::fprintf(stderr, "impgpu_broker: --jpeg-accept takes progressive or none\n"); return 2; }
+        }
+        else if (a == "--webp-accept") {
+            const std::string v = val("--webp-accept");
+            if (v == "lossless") o.webp_accept = 1;
+            else if (v == "none") o.webp_accept = 0;
+            else { std::fprintf(stderr, "impgpu_broker: --webp-accept takes lossless or none\n"); std::fputs(USAGE, stderr); return 2; }
         }
         else if (a == "--supervise") o.supervise = true;
         else { std::fputs(USAGE, stderr); return 2; }

@@ -1,0 +1,210 @@
+// imp_webp_dec.cpp -- lossless WebP uploads in: impgpu_batch_decode_webp reads every file's front on the host
+// (imp_webp_dec_host.h: the container, the header, the transforms with their sub-images, the cache size, the entropy
+// image, the code lengths), lays the files it took out in one device block a group -- descriptors, the table launch's
+// items, then per file the compressed words, the code lengths, the entropy image and the transforms' data, uploaded once
+// from one pinned block; behind them the status words (zeroed) and per file the codes, their sorted symbols and the
+// residual plane, which never cross the link -- runs the three launches of imp_webp_dec.hip on it and waits ONCE per
+// call, for the status words of all its groups.  impgpu_webp_decode_host is the same decoder with no device.
+#include "imp_internal.h"
+#include "imp_enc_host.h"
+#include "imp_webp_dec_host.h"
+
+namespace imp {
+
+int launch_webp_decode(uint8_t* mem, const WdFileDesc* files, const WdCodeItem* items, long long nitems, uint32_t* status, int nfiles, hipStream_t s);
+
+namespace {
+
+struct WdEntry {
+    int entry;                            // its index in the call's arrays
+    WdPlan plan;
+    size_t upload, device;                // what it puts into the group's upload, and behind it
+};
+
+size_t wd_upload_bytes(const WdPlan& P) {
+    size_t n = up256(P.words.size() * 4u) + up256(P.lens.size()) + up256(P.meta.size() * 4u);
+    for (int i = 0; i < P.ntrans; i++) n += up256(P.trdata[i].size() * 4u);
+    return n + up256(sizeof(WdFileDesc)) + up256((size_t)P.ngroups * WD_CODES * sizeof(WdCodeItem));
+}
+size_t wd_device_bytes(const WdPlan& P) {
+    return up256((size_t)P.ngroups * WD_CODES * sizeof(WdCode)) + up256((size_t)P.ngroups * wd_sorted_stride(P.cache_bits) * 2u) +
+           up256((size_t)P.w * (size_t)P.h * 4u) + 256u;
+}
+
+struct WdGroupRun {                       // a group in flight: its block lives until the call's one wait is over
+    DevBlock block;
+    std::vector<int> entries;
+    uint32_t* status = nullptr;
+    int piece = -1;
+};
+
+// one group: upload and launches, nothing waited for
+int decode_group(const std::vector<WdEntry*>& group, impgpu_image** images, WdGroupRun* run) {
+    hipStream_t s = env_stream();
+    const int nf = (int)group.size();
+    std::vector<WdFileDesc> fd((size_t)nf);
+    std::vector<WdCodeItem> items;
+    BlockLayout L;
+    const size_t o_fd = L.take((size_t)nf * sizeof(WdFileDesc));
+    size_t nitems = 0;
+    for (const WdEntry* e : group) nitems += (size_t)e->plan.ngroups * WD_CODES;
+    if (nitems > 0x7fffffffull) return IMP_ERROR_UNSUPPORTED;
+    const size_t o_items = L.take(nitems * sizeof(WdCodeItem));
+    std::vector<size_t> o_tr((size_t)nf * 4u, 0);
+    for (int f = 0; f < nf; f++) {
+        const WdPlan& P = group[(size_t)f]->plan;
+        WdFileDesc& d = fd[(size_t)f];
+        std::memset(&d, 0, sizeof d);
+        d.in_off = (long long)L.take(P.words.size() * 4u);
+        d.lens_off = (long long)L.take(P.lens.size());
+        d.meta_off = (long long)L.take(P.meta.size() * 4u);
+        d.ntrans = P.ntrans;
+        for (int i = 0; i < P.ntrans; i++) {
+            d.tr[i] = P.tr[i];
+            d.tr[i].data_off = (long long)(o_tr[(size_t)f * 4u + (size_t)i] = L.take(P.trdata[i].size() * 4u));
+        }
+        d.bitpos = P.bitpos;
+        d.in_size = P.in_size; d.in_cap = (uint32_t)(P.words.size() * 4u); d.ngroups = P.ngroups;
+        d.w = P.w; d.h = P.h; d.cw = P.cw; d.alpha_used = P.alpha_used;
+        d.cache_bits = P.cache_bits; d.meta_bits = P.meta_bits; d.meta_w = P.meta_w;
+        d.img = images[group[(size_t)f]->entry]->d;
+        for (uint32_t g = 0; g < P.ngroups; g++)
+            for (int k = 0; k < WD_CODES; k++) items.push_back(WdCodeItem{f, g, k, 0});
+    }
+    const size_t upload = L.size();                                     // where the upload ends
+    const size_t o_status = L.take((size_t)nf * 4u);
+    for (int f = 0; f < nf; f++) {
+        const WdPlan& P = group[(size_t)f]->plan;
+        fd[(size_t)f].codes_off = (long long)L.take((size_t)P.ngroups * WD_CODES * sizeof(WdCode));
+        fd[(size_t)f].sorted_off = (long long)L.take((size_t)P.ngroups * wd_sorted_stride(P.cache_bits) * 2u);
+        fd[(size_t)f].plane_off = (long long)L.take((size_t)P.w * (size_t)P.h * 4u);
+    }
+    if (int rc = dev_alloc(L.size(), &run->block.p)) return rc;
+    uint8_t* m = run->block.bytes();
+    void *host = nullptr, *token = nullptr;
+    if (int rc = stage_begin(upload, &host, &token)) return rc;
+    uint8_t* hp = (uint8_t*)host;
+    std::memcpy(hp + o_fd, fd.data(), fd.size() * sizeof(WdFileDesc));
+    std::memcpy(hp + o_items, items.data(), items.size() * sizeof(WdCodeItem));
+    for (int f = 0; f < nf; f++) {
+        const WdPlan& P = group[(size_t)f]->plan;
+        const WdFileDesc& d = fd[(size_t)f];
+        std::memcpy(hp + d.in_off, P.words.data(), P.words.size() * 4u);
+        std::memcpy(hp + d.lens_off, P.lens.data(), P.lens.size());
+        if (!P.meta.empty()) std::memcpy(hp + d.meta_off, P.meta.data(), P.meta.size() * 4u);
+        for (int i = 0; i < P.ntrans; i++)
+            if (!P.trdata[i].empty()) std::memcpy(hp + o_tr[(size_t)f * 4u + (size_t)i], P.trdata[i].data(), P.trdata[i].size() * 4u);
+    }
+    int rc = stage_upload(token, m, upload);
+    if (!rc) {
+        const hipError_t e = hipMemsetAsync(m + o_status, 0, up256((size_t)nf * 4u), s);
+        if (e != hipSuccess) { set_error("hipMemsetAsync(webp decode)", e); rc = IMP_ERROR_DEVICE; }
+    }
+    run->status = (uint32_t*)(m + o_status);
+    if (!rc) rc = launch_webp_decode(m, (const WdFileDesc*)(m + o_fd), (const WdCodeItem*)(m + o_items), (long long)nitems, run->status, nf, s);
+    return rc;
+}
+
+int batch_decode(const unsigned char* const* blobs, const size_t* sizes, int count, impgpu_image** images, int* codes, int* launches) {
+    if (launches) *launches = 0;
+    if (count < 0 || count > 256 || (count > 0 && (!blobs || !sizes || !images || !codes))) return IMP_ERROR_INVALID_ARGS;
+    for (int i = 0; i < count; i++) images[i] = nullptr;
+    if (count == 0) return IMP_OK;
+    if (int rc = need_env()) {
+        for (int i = 0; i < count; i++) codes[i] = rc;
+        return rc;
+    }
+    const unsigned long long launched = t_launches;
+    const size_t cap = stage_cap();
+    std::vector<std::unique_ptr<WdEntry>> taken;
+    std::unique_ptr<WdMem> mem(new WdMem());
+    for (int i = 0; i < count; i++) {
+        if (!blobs[i]) { codes[i] = IMP_ERROR_INVALID_ARGS; continue; }
+        std::unique_ptr<WdEntry> e(new WdEntry());
+        e->entry = i;
+        if ((codes[i] = wd_parse(blobs[i], sizes[i], &e->plan, mem.get())) != IMP_OK) continue;
+        e->upload = wd_upload_bytes(e->plan);
+        e->device = wd_device_bytes(e->plan);
+        if (cap && e->upload + e->device > cap) { codes[i] = IMP_ERROR_MALLOC_FAILED; continue; }   // a file that does not fit under the stage cap
+        if ((codes[i] = image_new(e->plan.w, e->plan.h, 4, &images[i])) != IMP_OK) { images[i] = nullptr; continue; }
+        taken.push_back(std::move(e));
+    }
+    // the groups: as many files as the stage cap takes; all are enqueued before the one wait
+    std::vector<std::unique_ptr<WdGroupRun>> runs;
+    AnswerFetch words;
+    std::vector<WdEntry*> group;
+    size_t bytes = 0;
+    auto fail = [&](const std::vector<WdEntry*>& g, int rc) {
+        for (const WdEntry* e : g) { codes[e->entry] = rc; image_delete(images[e->entry]); images[e->entry] = nullptr; }
+    };
+    int hard = IMP_OK;                                                   // a failure behind enqueued work: drain before the blocks go
+    auto flush = [&]() {
+        if (group.empty()) return;
+        std::unique_ptr<WdGroupRun> run(new WdGroupRun());
+        const int rc = decode_group(group, images, run.get());
+        if (rc) {
+            fail(group, rc);
+            hard = rc;
+        } else {
+            for (const WdEntry* e : group) run->entries.push_back(e->entry);
+            run->piece = words.add(run->status, group.size() * 4u);
+        }
+        runs.push_back(std::move(run));
+        group.clear();
+        bytes = 0;
+    };
+    for (auto& e : taken) {
+        if (!group.empty() && cap && bytes + e->upload + e->device > cap) flush();
+        group.push_back(e.get());
+        bytes += e->upload + e->device;
+    }
+    flush();
+    int rc = words.run("hipMemcpyAsync(webp decode status)");            // the call's one wait
+    if (hard && !rc) (void)drained(hard);
+    for (auto& run : runs) {
+        if (run->piece < 0) continue;
+        const uint32_t* st = (const uint32_t*)words.at(run->piece);
+        for (size_t k = 0; k < run->entries.size(); k++) {
+            const int i = run->entries[k];
+            const int code = rc ? rc : st[k] ? IMP_ERROR_DECODE_FAILED : IMP_OK;
+            codes[i] = code;
+            if (code) { image_delete(images[i]); images[i] = nullptr; }
+        }
+    }
+    if (launches) *launches = (int)(t_launches - launched);
+    return IMP_OK;
+}
+
+}  // namespace
+}  // namespace imp
+
+using namespace imp;
+
+extern "C" {
+
+int impgpu_webp_info(const unsigned char* blob, size_t size, int* width, int* height, int* channels) {
+    int w = 0, h = 0, alpha = 0;
+    if (int rc = wd_info(blob, size, &w, &h, &alpha)) return rc;
+    if (width) *width = w;
+    if (height) *height = h;
+    if (channels) *channels = 4;
+    return IMP_OK;
+}
+
+int impgpu_webp_decode_host(const unsigned char* blob, size_t size, unsigned char* out, size_t capacity, int* width, int* height, int* info) {
+    return wd_decode_host(blob, size, out, capacity, width, height, info);
+}
+
+int impgpu_batch_decode_webp(const unsigned char* const* blobs, const size_t* sizes, int count, impgpu_image** images, int* codes, int* launches) {
+    return batch_decode(blobs, sizes, count, images, codes, launches);
+}
+
+int impgpu_image_decode_webp(const unsigned char* blob, size_t size, impgpu_image** out) {
+    if (out) *out = nullptr;
+    if (!blob || !out) return IMP_ERROR_INVALID_ARGS;
+    int code = IMP_OK;
+    if (int rc = batch_decode(&blob, &size, 1, out, &code, nullptr)) return rc;
+    return code;
+}
+
+}  // extern "C"

@@ -1111,6 +1111,52 @@ def batch_encode_webp(images, capacities=None, count=None, guard=64, flags=None)
     return rc, [_answer(codes[i], bufs[i], C.c_size_t(lens[i])) for i in range(n)], launches.value
 
 
+def webp_info(blob):
+    """impgpu_webp_info -> (code, width, height, channels); host only."""
+    b = bytes(blob)
+    w, h, c = C.c_int(0), C.c_int(0), C.c_int(0)
+    rc = lib.impgpu_webp_info(b, len(b), C.byref(w), C.byref(h), C.byref(c))
+    return rc, w.value, h.value, c.value
+
+
+def webp_decode_host(blob, capacity=None, guard=64):
+    """impgpu_webp_decode_host (no device): a lossless WebP file -> (code, HxWx4 B,G,R,A array or None, info, intact).
+    capacity defaults to what impgpu_webp_info says the frame takes; `intact`: the guard band behind it was not written."""
+    b = bytes(blob)
+    rc, w, h, _ = webp_info(b)
+    cap = (w * h * 4 if rc == 0 else 0) if capacity is None else int(capacity)
+    buf = np.full(max(1, cap) + guard, 0xA5, np.uint8)
+    ww, hh = C.c_int(0), C.c_int(0)
+    info = (C.c_int * 8)()
+    rc = lib.impgpu_webp_decode_host(b, len(b), buf.ctypes.data, cap, C.byref(ww), C.byref(hh), info)
+    intact = bool((buf[cap:] == 0xA5).all())
+    frame = buf[:ww.value * hh.value * 4].reshape(hh.value, ww.value, 4).copy() if rc == 0 else None
+    return rc, frame, list(info), intact
+
+
+def batch_decode_webp(blobs, count=None):
+    """impgpu_batch_decode_webp -> ([(code, Image or None)] in the order of `blobs`, kernel launches of the call)."""
+    n = len(blobs)
+    keep = [bytes(b) for b in blobs]
+    arr = (C.c_char_p * max(1, n))(*keep)
+    sizes = (C.c_size_t * max(1, n))(*[len(b) for b in keep])
+    imgs = (C.c_void_p * max(1, n))()
+    codes = (C.c_int * max(1, n))()
+    launches = C.c_int()
+    rc = lib.impgpu_batch_decode_webp(arr, sizes, n if count is None else count, imgs, codes, C.byref(launches))
+    if rc:
+        raise ImpError(rc, "impgpu_batch_decode_webp")
+    return [(codes[i], Image(handle=imgs[i]) if codes[i] == 0 else None) for i in range(n)], launches.value
+
+
+def decode_webp(blob):
+    """impgpu_image_decode_webp -> (code, Image or None)."""
+    b = bytes(blob)
+    h = C.c_void_p()
+    rc = lib.impgpu_image_decode_webp(b, len(b), C.byref(h))
+    return rc, Image(handle=h.value) if rc == 0 else None
+
+
 def batch_filters(ptr, stride, w, h, c, step, count, filters, allow_experiments=1, stream=None):
     """Pointwise filter-* requests on every frame of a resident batch, one fused launch. Returns the IMP_* code."""
     arr = (C.c_char_p * max(1, len(filters)))(*[_b(f) for f in filters])
