@@ -23,6 +23,15 @@
  * 4:2:0, 4:4:0 and gray files, odd sizes, with and without restart intervals, and tests/golden/jpeg/ holds
  * the committed files with Pillow's pixels.
  *
+ * THE DOMAIN of that pin: blocks whose max |coef * q| and max |pass-1 output| (the column pass below, descaled by
+ * CONST_BITS - PASS1_BITS = 11) are both <= 16383.  Outside it there are three answers: libjpeg-turbo's SIMD IDCT (what
+ * Pillow runs; 16-bit lanes that wrap), plain-C libjpeg (which masks the range-limit index), and this file, which
+ * dequantises and transforms in 32 bits and saturates -- as the product's kernel does.  A DC-only block of 100 x q 255
+ * already differs from Pillow in all 64 samples.  tests/jpeg_writer.py (idct_domain) states the rule in int64,
+ * tests/make_jpeg_hand.py measures it against Pillow on every run: 1696 random in-domain blocks, none differs (final
+ * outputs up to +-2150; the files of tests/golden/jpeg_hand/ reach +-3542); of 3704 blocks outside 2819 differ, the
+ * smallest pass-1 peak among those is 18049.  The rule is empirical (libjpeg-turbo's source was not consulted).
+ *
  * Scope (everything else returns ORC_ERROR_UNSUPPORTED, and the product hands such files to the
  * host decoder unchanged): 8-bit baseline / extended-sequential Huffman (SOF0, SOF1), one
  * interleaved scan, 1 component, or 3 components with luma sampling 1x1, 2x1, 1x2 or 2x2 and
