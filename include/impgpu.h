@@ -1044,6 +1044,113 @@ size_t impgpu_webp_encode_bound_flags(int width, int height, int channels, int f
  * (256..511: FreeImage's WEBP_LOSSLESS); otherwise 0.  A pure accessor: the parse and its error codes are unchanged. */
 int impgpu_request_webp_lossless(const impgpu_request* request);
 
+/* ---- LOSSY WEBP ANSWERS out, written ON THE DEVICE (opt-in: nothing calls these by default; the broker does not yet).
+ *      `format=webp` with a quality of 0..100 asks for a lossy file (impgpu_request_webp_quality says which).  The file is
+ *      a VP8 key frame restricted to tools that run in parallel and can be tested exactly; it is deterministic, all-integer
+ *      and NOT libwebp's bytes.  libwebp decodes it to exactly the encoder's own reconstruction.  Names of syntax elements
+ *      and "the standard ..." refer to RFC 6386; the standard tables are include/impgpu_vp8_tables.h.  THE FILE, completely:
+ *      CONTAINER  "RIFF", u32 file size - 8, "WEBP", then chunks: a tag, u32 size, the body, one 0 byte when the size is
+ *        odd.  A 1- or 3-channel frame, or a 4-channel frame whose alpha is 255 everywhere, has the one chunk "VP8 ".  A
+ *        4-channel frame with any other alpha has "VP8X" (10 bytes: 0x10, 0, 0, 0, u24 width - 1, u24 height - 1), then
+ *        "ALPH" (the byte 0 -- no pre-processing, no filter, no compression -- and width x height raw alpha bytes), then
+ *        "VP8 ".  Sides run 1..16383.
+ *      COLOUR  with R, G, B of a pixel (gray: R = G = B): Y = (16839 R + 33059 G + 6420 B + (16<<16) + (1<<15)) >> 16.
+ *        U and V come from the SUMS R, G, B of a 2x2 cell: U = (-9719 R - 19081 G + 28800 B + (128<<18) + (1<<17)) >> 18,
+ *        V = (28800 R - 24116 G - 4684 B + (128<<18) + (1<<17)) >> 18, arithmetic shifts, clipped to 0..255.  A cell at an odd
+ *        right or bottom edge repeats its last column or row.  The planes are padded to whole macroblocks (16x16 Y, 8x8 U
+ *        and V) by repeating the last sample of a row and then the last row.
+ *      VP8 CHUNK  the 3-byte frame tag (u24: bit 0 = 0 key frame, bits 1..3 version 0, bit 4 show_frame 1, bits 5..23 the
+ *        first partition's size), 0x9d 0x01 0x2a, u16 width, u16 height (scale bits 0), the first partition, then u24 sizes
+ *        of all token partitions but the last, then the token partitions.
+ *      BOOLEAN CODER  the standard one (section 7.3: range 255, bottom 0, bit_count 24; split = 1 + (((range - 1) * prob)
+ *        >> 8); a carry is added into the bytes already written) with that section's flush, which always writes 4 more
+ *        bytes.  A literal of n bits is its bits from the highest down at probability 128.  Each partition is one coder.
+ *      FIRST PARTITION  literals: colour space 0 (1 bit), clamping type 0 (1), segmentation_enabled 0 (1), filter type 0
+ *        (1), loop filter level 0 (6), sharpness 0 (3), loop_filter_adj_enable 0 (1), log2 of the partition count (2), the
+ *        quantiser index qi (7), five absent quantiser deltas (0, 1 bit each), refresh_entropy_probs 0 (1); then 1056 flags
+ *        0, one per coefficient probability, each coded with its update probability; mb_no_coeff_skip 1 (1) and
+ *        prob_skip_false (8) = clamp(1..255, (256 * (MBs - skipped) + MBs/2) / MBs).  Then per macroblock in raster order:
+ *        the skip flag at prob_skip_false; a 1 at 145 (not B_PRED); the luma mode: at 156 a 0 then at 163 DC 0 / V 1, or
+ *        a 1 then at 128 H 0 / TM 1; the chroma mode: DC is 0 at 142; V is 1 at 142, 0 at 114; H is 1, 1, 0 at 183; TM is
+ *        1, 1, 1.
+ *      PARTITIONS  P = the largest of 1, 2, 4, 8 that does not exceed the number of macroblock rows; row r's tokens go to
+ *        partition r mod P, rows and macroblocks in raster order.
+ *      QUANTISER  qi = 127 - (127 * quality + 50) / 100.  With dc[] and ac[] the standard lookups at qi the steps are:
+ *        Y1 AC ac; Y2 DC 2 dc; Y2 AC max(8, ac * 155 / 100); chroma DC min(132, dc); chroma AC ac (Y1 DC is not coded:
+ *        every macroblock has a Y2 block).  level = sign(c) * min(2047, (|c| + q/2) / q); a de-quantised value is level * q.
+ *      PREDICTION  modes DC, V, H, TM (numbered 0..3 in this library) for the 16x16 luma block and, one mode for both, the
+ *        8x8 U and V blocks; never B_PRED.  A prediction reads the RECONSTRUCTED samples above (A), to the left (L) and at
+ *        the corner (C): the row above the frame is 127, its corner too; the column left of the frame is 129, and so is the
+ *        corner of the first macroblock of every row below the first.  V is A[x]; H is L[y]; TM is clip(A[x] + L[y] - C);
+ *        DC is (sum A + sum L + n) >> log2(2n) inside (n = 16 or 8), (sum + n/2) >> log2(n) over the one side that exists in
+ *        the first row or column, and 128 for the first macroblock.
+ *      MODE CHOICE  luma: the mode with the smallest sum of squared differences between prediction and source over the
+ *        macroblock wins, a tie goes to the first of DC, V, H, TM.  Chroma likewise over the sum of both planes.
+ *      FORWARD TRANSFORMS  of the differences d (source - prediction) of a 4x4 block, rows first: a0 = d0 + d3, a1 = d1 + d2,
+ *        a2 = d1 - d2, a3 = d0 - d3; t0 = (a0 + a1) * 8, t1 = (a2 * 2217 + a3 * 5352 + 1812) >> 9, t2 = (a0 - a1) * 8,
+ *        t3 = (a3 * 2217 - a2 * 5352 + 937) >> 9.  Then columns of t, with the same a0..a3: c0 = (a0 + a1 + 7) >> 4,
+ *        c1 = ((a2 * 2217 + a3 * 5352 + 12000) >> 16) + (a3 != 0), c2 = (a0 - a1 + 7) >> 4, c3 = (a3 * 2217 - a2 * 5352 +
+ *        51000) >> 16, c_k being row k of the block's coefficients.  The 16 luma blocks' first coefficients (their DCs), in
+ *        the blocks' raster order, form the 4x4 Y2 input; its Walsh-Hadamard transform, rows first: a0 = i0 + i2, a1 = i1 + i3, a2 = i1 - i3, a3 = i0 - i2;
+ *        t = a0 + a1, a3 + a2, a3 - a2, a0 - a1; then columns: a0 = t0 + t2, a1 = t1 + t3, a2 = t1 - t3, a3 = t0 - t2 (t_k
+ *        row k) and the outputs (a0 + a1) >> 1, (a3 + a2) >> 1, (a3 - a2) >> 1, (a0 - a1) >> 1 as rows 0..3.
+ *      RECONSTRUCTION  is the decoder's: the standard inverse WHT of the de-quantised Y2 block gives the luma blocks' DCs
+ *        (used as they are); the standard inverse DCT (20091 / 35468, section 14.3) of each de-quantised block is added to the
+ *        prediction and clamped to 0..255.
+ *      SKIP  a macroblock whose 25 blocks have only zero levels is skipped: no tokens, all its context flags 0.
+ *      TOKENS  of a coded macroblock: the Y2 block (type 1), the 16 luma blocks in raster order (type 0, from position 1),
+ *        the 4 U and the 4 V blocks (type 2): the standard token tree with the DEFAULT coefficient probabilities, the
+ *        standard bands, zigzag and category extra bits, the sign at 128; a block's context is the number of its left and
+ *        upper neighbours of the same kind (in this macroblock or the next one over, 0 outside the frame) that coded a
+ *        non-zero level; the context after a token is 0, 1 or 2 for a zero, a one, anything larger.
+ *      tests/webp_vp8_writer.py writes the same bytes from this paragraph alone.
+ *      TAKEN: 1-, 3- and 4-channel single images with sides 1..16383, quality 0..100; a window of a parent (step > width x
+ *      channels) is read in place.  REFUSED: IMP_ERROR_UNSUPPORTED, *length = 0, nothing written: an album, 2 channels, a
+ *      larger side -- and a frame whose first partition outgrows the format's 19-bit size or a token partition its 24 bits
+ *      (about 300 000 macroblocks).  IMP_ERROR_MALLOC_FAILED: `capacity` is too small; nothing is written, *length is the
+ *      size needed (impgpu_webp_lossy_encode_bound is always enough: it is the worst case of the token tree, about 8 KB a
+ *      macroblock) -- and, with *length = 0, a frame whose device block does not fit under $IMPGPU_STAGE_CAP_MB.
+ *      IMP_ERROR_INVALID_ARGS before a device is looked for: a quality outside 0..100, NULL arrays with count > 0, a
+ *      count outside 0..256.  IMP_ERROR_DEVICE without an env.
+ *      FIVE launches for a call (for a group under $IMPGPU_STAGE_CAP_MB), whatever it holds: k_vp8_planes (padded Y, U, V
+ *      and the alpha plane, a gather per sample), k_vp8_recon (a workgroup per frame, a wavefront per macroblock row in
+ *      flight -- 8, fewer past 7168 pixels a row -- each one macroblock behind the row above; progress counters and the border rows in LDS; the 64 lanes share
+ *      a macroblock's mode costs, 25 transforms, quantiser and reconstruction; it leaves the levels and a word of modes
+ *      and non-zero flags per macroblock), k_vp8_tokens (a lane per macroblock writes its (probability, bit) records),
+ *      k_vp8_bool (a lane per frame and partition walks its records through the boolean coder, carries resolved in its
+ *      own output; a ninth lane codes the first partition) and k_vp8_pack (sizes, frame tag, partition table, chunks and
+ *      the pieces into the answer).  TWO waits: the records (the lengths), then the files that fit.
+ *      MEASURED (profiles/webp_lossy_probe.json, one session, photo-like BGRA frames, quality 75): 64
+ *      frames of 320x240 2.93 ms (two groups), a lone 640x480 frame 4.08 ms, a lone 1920x1080 one 24.3 ms -- against 1.33 /
+ *      0.09 / 0.41 ms for impgpu_batch_download of the frames alone and 63.6 / 3.92 / 24.4 ms for that plus Pillow's lossy
+ *      save at method 0 on one core (233 / 14.1 / 93.5 ms at method 4).  A lone frame only ties libwebp's fastest setting:
+ *      k_vp8_recon and k_vp8_bool are sequential and take half the call each (1.9 + 2.1 ms at 640x480, 11.9 + 12.7 ms at
+ *      1080p); the other three launches together are under 0.35 ms.  Files are about libwebp's size at equal quality and
+ *      1.4x / 2.2x / 3.2x larger at equal PSNR (quality 50 / 75 / 90, profiles/webp_lossy_sizes.json): no B_PRED, default
+ *      probabilities, no loop filter, plain rounding. ---- */
+int impgpu_image_encode_webp_lossy(const impgpu_image* image, int quality, unsigned char* out, size_t capacity, size_t* length);
+/* MANY frames (count 0..256) of mixed sizes, channel counts and qualities: codes[i] / lengths[i] / the file are exactly the
+ * lone call's; a refused frame gets its code alone and changes no other entry.  *launches (may be NULL): the kernels
+ * enqueued -- 5 for a call under the stage cap whatever it holds, 0 when no frame was accepted. */
+int impgpu_batch_encode_webp_lossy(const impgpu_image* const* images, int count, const int* qualities, unsigned char* const* outs,
+                                   const size_t* capacities, size_t* lengths, int* codes, int* launches);
+/* a size no file of that geometry exceeds (0: a geometry the calls refuse) */
+size_t impgpu_webp_lossy_encode_bound(int width, int height, int channels);
+/* host, no device: the same file from a frame in host memory (rows `step` bytes apart), made by the launches' own lane code
+ * (csrc/imp_webp_lossy.h) run one lane after the other. */
+int impgpu_webp_lossy_encode_host(const unsigned char* frame, int width, int height, int channels, int step, int quality,
+                                  unsigned char* out, size_t capacity, size_t* length);
+/* the same, and what the encoder decided, for the tests (each may be NULL): per macroblock in raster order `modes` 2 bytes
+ * (luma, chroma), `levels` 400 shorts (25 blocks -- 16 Y, 4 U, 4 V, Y2 -- of 16 levels in raster order); the reconstructed
+ * planes padded to whole macroblocks (16 mbw x 16 mbh, and half that a side for U and V). */
+int impgpu_webp_lossy_encode_host_ex(const unsigned char* frame, int width, int height, int channels, int step, int quality,
+                                     unsigned char* out, size_t capacity, size_t* length, unsigned char* modes, short* levels,
+                                     unsigned char* recon_y, unsigned char* recon_u, unsigned char* recon_v);
+/* -1 unless the request's answer format resolves to webp (format=, else the extension) with bit 8 of its parsed quality
+ * clear; otherwise the lossy quality: an absent quality or 0 is 75, one above 100 is 100.  (The mapping is this
+ * library's.)  A pure accessor: the parse and its error codes are unchanged. */
+int impgpu_request_webp_quality(const impgpu_request* request);
+
 /* ---- WEBP UPLOADS in, LOSSLESS, decoded ON THE DEVICE (opt-in: nothing calls these by default; the broker only with
  *      --webp-accept lossless).  THE FRAME is what the reference's route gives for the same file -- FreeImage's WebP plugin,
  *      ConvertTo32Bits, LoadSingle (advancedio.c:276-318), then impgpu_image_upload_fi32: 4 channels, top-down, B,G,R,A; A is

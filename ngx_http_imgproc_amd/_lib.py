@@ -196,6 +196,12 @@ SIGNATURES = {
     "impgpu_webp_encode_bound_flags": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "impgpu_webp_encode_host_flags": (C.c_int, [P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "impgpu_request_webp_lossless": (C.c_int, [P]),
+    "impgpu_request_webp_quality": (C.c_int, [P]),
+    "impgpu_image_encode_webp_lossy": (C.c_int, [P, C.c_int, P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "impgpu_batch_encode_webp_lossy": (C.c_int, [PP, C.c_int, IP, PP, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), IP, IP]),
+    "impgpu_webp_lossy_encode_bound": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "impgpu_webp_lossy_encode_host": (C.c_int, [P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "impgpu_webp_lossy_encode_host_ex": (C.c_int, [P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, C.c_size_t, C.POINTER(C.c_size_t), P, P, P, P, P]),
     "impgpu_webp_info": (C.c_int, [C.c_char_p, C.c_size_t, IP, IP, IP]),
     "impgpu_image_decode_webp": (C.c_int, [C.c_char_p, C.c_size_t, PP]),
     "impgpu_batch_decode_webp": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, PP, IP, IP]),

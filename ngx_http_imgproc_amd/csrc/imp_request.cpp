@@ -18,6 +18,7 @@ struct impgpu_request {
     int mime = 0;
     int destructive = 0;
     int webp_lossless = 0;                   // the answer is webp and quality has FreeImage's WEBP_LOSSLESS bit (0x100)
+    int webp_quality = -1;                   // the answer is webp without that bit: 0..100 (impgpu_request_webp_quality)
 };
 
 namespace {
@@ -138,6 +139,12 @@ int impgpu_parse_request(const char* uri, const char* extension, const impgpu_co
             r->webp_lossless = ieq(e, "webp") && (qv & 0x100) != 0;
         }
     }
+    if (r->mime == -4) {                                                // impgpu_request_webp_quality: absent or 0 -> 75, above 100 -> 100
+        const char* e = format;
+        if (const char* dot = std::strrchr(e, '.')) e = dot + 1;
+        const long qv = r->quality ? std::strtol(r->quality, nullptr, 10) : 0;
+        if (ieq(e, "webp") && !(qv & 0x100)) r->webp_quality = qv == 0 ? 75 : (qv > 100 ? 100 : (int)qv);
+    }
     r->job.simple = cls == F_GIF;                                        // bridge.c:594
     r->job.need_flatten = r->mime == -1 || (r->mime == -4 && cls == F_NO_ALPHA);   // bridge.c:643-647
     return IMP_OK;
@@ -150,6 +157,7 @@ int impgpu_request_page(const impgpu_request* r) { return r ? r->page : -1; }
 int impgpu_request_mime(const impgpu_request* r) { return r ? r->mime : 0; }
 int impgpu_request_destructive(const impgpu_request* r) { return r ? r->destructive : 0; }
 int impgpu_request_webp_lossless(const impgpu_request* r) { return r ? r->webp_lossless : 0; }
+int impgpu_request_webp_quality(const impgpu_request* r) { return r ? r->webp_quality : -1; }
 void impgpu_request_free(impgpu_request** r) {
     if (!r || !*r) return;
     delete *r;

@@ -1111,6 +1111,59 @@ def batch_encode_webp(images, capacities=None, count=None, guard=64, flags=None)
     return rc, [_answer(codes[i], bufs[i], C.c_size_t(lens[i])) for i in range(n)], launches.value
 
 
+def webp_lossy_encode_bound(width, height, channels):
+    """impgpu_webp_lossy_encode_bound: a size no lossy WebP file of that frame exceeds (0: a geometry the encoder refuses)"""
+    return lib.impgpu_webp_lossy_encode_bound(int(width), int(height), int(channels))
+
+
+def encode_webp_lossy(image, quality=75, capacity=None, guard=64):
+    """impgpu_image_encode_webp_lossy: the image as a lossy WebP file (VP8 key frame) written on the device -> (code, bytes
+    or None, length, intact), as encode_webp: `capacity` defaults to webp_lossy_encode_bound."""
+    cap = webp_lossy_encode_bound(image.shape[1], image.shape[0], image.shape[2]) if capacity is None else int(capacity)
+    buf = np.full(max(1, cap) + guard, 0xA5, np.uint8)
+    n = C.c_size_t(0)
+    rc = lib.impgpu_image_encode_webp_lossy(image.h, int(quality), buf.ctypes.data, cap, C.byref(n))
+    return _answer(rc, buf, n)
+
+
+def encode_webp_lossy_host(frame, quality=75, capacity=None, guard=64, channels=None, details=False):
+    """impgpu_webp_lossy_encode_host (no device): one HxWxC uint8 array (a view with padded rows is fine) -> (code, bytes or
+    None, length, intact).  details=True: impgpu_webp_lossy_encode_host_ex, and a fifth entry: a dict of the macroblocks'
+    modes (n, 2: luma, chroma), levels (n, 25, 16) and the padded reconstructed planes y, u, v."""
+    hh, ww, cc = frame.shape
+    assert frame.dtype == np.uint8 and frame.strides[1:] == (cc, 1)
+    cc = cc if channels is None else int(channels)
+    cap = webp_lossy_encode_bound(ww, hh, cc) if capacity is None else int(capacity)
+    buf = np.full(max(1, cap) + guard, 0xA5, np.uint8)
+    n = C.c_size_t(0)
+    if not details:
+        rc = lib.impgpu_webp_lossy_encode_host(frame.ctypes.data, ww, hh, cc, frame.strides[0], int(quality), buf.ctypes.data, cap, C.byref(n))
+        return _answer(rc, buf, n)
+    mw, mh = (max(ww, 1) + 15) // 16, (max(hh, 1) + 15) // 16
+    d = {"modes": np.zeros((mw * mh, 2), np.uint8), "levels": np.zeros((mw * mh, 25, 16), np.int16), "y": np.zeros((mh * 16, mw * 16), np.uint8),
+         "u": np.zeros((mh * 8, mw * 8), np.uint8), "v": np.zeros((mh * 8, mw * 8), np.uint8)}
+    rc = lib.impgpu_webp_lossy_encode_host_ex(frame.ctypes.data, ww, hh, cc, frame.strides[0], int(quality), buf.ctypes.data, cap, C.byref(n),
+                                              d["modes"].ctypes.data, d["levels"].ctypes.data, d["y"].ctypes.data, d["u"].ctypes.data, d["v"].ctypes.data)
+    return _answer(rc, buf, n) + (d,)
+
+
+def batch_encode_webp_lossy(images, qualities=None, capacities=None, count=None, guard=64):
+    """impgpu_batch_encode_webp_lossy: images (an entry may be None) -> (code, [(code, bytes or None, length, intact) ...],
+    launches).  qualities: one per image (default 75); None passes a NULL array.  capacities default to
+    webp_lossy_encode_bound."""
+    n = len(images)
+    handles, carr, bufs, outs, lens, codes = _answer_arrays(images, lambda a: webp_lossy_encode_bound(a.shape[1], a.shape[0], a.shape[2]), capacities, guard)
+    launches = C.c_int(-1)
+    q = None if qualities is None else (C.c_int * max(1, n))(*[int(v) for v in qualities])
+    rc = lib.impgpu_batch_encode_webp_lossy(handles, n if count is None else count, q, outs, carr, lens, codes, C.byref(launches))
+    return rc, [_answer(codes[i], bufs[i], C.c_size_t(lens[i])) for i in range(n)], launches.value
+
+
+def request_webp_quality(uri, extension="", config=None):
+    """impgpu_request_webp_quality of the parsed request line: -1, or the lossy WebP quality 0..100 the answer asks for"""
+    return Request(uri, extension, config).webp_quality
+
+
 def webp_info(blob):
     """impgpu_webp_info -> (code, width, height, channels); host only."""
     b = bytes(blob)
@@ -1182,6 +1235,7 @@ class Request:
         self.mime = lib.impgpu_request_mime(self.h)
         self.destructive = lib.impgpu_request_destructive(self.h)
         self.webp_lossless = lib.impgpu_request_webp_lossless(self.h)
+        self.webp_quality = lib.impgpu_request_webp_quality(self.h)
 
     def run(self, image, config):
         """impgpu_run_ops with the parsed job. Returns (code, step)."""
