@@ -1221,7 +1221,8 @@ int impgpu_batch_decode_webp(const unsigned char* const* blobs, const size_t* si
  * row) into out[0, capacity); *width / *height are set once the header is read; IMP_ERROR_MALLOC_FAILED = capacity is
  * smaller than width * height * 4 (nothing written).  info (may be NULL) receives IMPGPU_WEBP_DEC_INFO_WORDS ints: [0] the
  * feature word, [1] prefix-code groups, [2] the main image's cache bits, [3] transforms, [4] the coded width, [5] the
- * main image's status word (0 complete, 1 damaged, 2 ran past the chunk). */
+ * main image's status word (0 complete, 1 damaged, 2 ran past the chunk), [6] the rounds the main image took (a round ends
+ * at 512 tokens or where the 512 staged words run low), [7] the longest code length among the main image's codes. */
 int impgpu_webp_decode_host(const unsigned char* blob, size_t size, unsigned char* out, size_t capacity, int* width, int* height, int* info);
 
 /* ---- batch entry points (benchmark / multi-frame albums: bridge.c:578,591,608,632).

@@ -524,6 +524,7 @@ IMP_WD_HD uint32_t wd_predict(int mode, uint32_t L, uint32_t T, uint32_t TL, uin
 // step s on pixel x = s - 2 j, two pixels behind the lane above -- whose pixels through x + 1 (TR) an earlier step
 // stored.  A band takes w + 2 (nlanes - 1) steps; in place: the residual at (x, y) becomes the pixel.
 IMP_WD_HD int wd_pred_steps(int w, int nlanes) { return w + 2 * (nlanes - 1); }
+constexpr int WD_INV_LANES = 256;                           // k_webp_dec_inverse's workgroup: a band is min(h, this) rows, on the host too
 IMP_WD_HD void wd_inv_pred_step(uint32_t* p, int w, int h, int bits, const uint32_t* modes, int row0, int step, int lane) {
     const int y = row0 + lane, x = step - 2 * lane;
     if (y >= h || x < 0 || x >= w) return;
@@ -573,11 +574,13 @@ inline bool wd_build_host(WdCode* c, const uint8_t* lens, int n, uint16_t* sorte
     return true;
 }
 
-inline int wd_rounds_host(const WdImage& im, uint64_t bitpos, WdMem* m, uint32_t* feat, uint64_t* endbit) {
+inline int wd_rounds_host(const WdImage& im, uint64_t bitpos, WdMem* m, uint32_t* feat, uint64_t* endbit, int* rounds = nullptr) {
     WdState s;
     wd_start(&s, im, bitpos);
+    int nrounds = 0;
     for (int j = 0; j < WD_LANES; j++) wd_cache_clear(m, j);
     while (!s.done) {
+        nrounds++;
         for (int j = 0; j < WD_LANES; j++) wd_stage(m, im, s.bitpos, j);
         WdBits b;
         wd_bits_begin(&b, m->in, WD_IN_WORDS, (s.bitpos >> 5) << 5, s.bitpos);
@@ -608,6 +611,7 @@ inline int wd_rounds_host(const WdImage& im, uint64_t bitpos, WdMem* m, uint32_t
     }
     *feat |= s.feat;
     *endbit = s.bitpos;
+    if (rounds) *rounds = nrounds;
     return s.status;
 }
 

@@ -110,7 +110,7 @@ __global__ __launch_bounds__(WD_LANES) void k_webp_dec_pixels(uint8_t* __restric
     if (lane == 0 && s.status != WD_OK) atomicMax(&status[f], (uint32_t)s.status);
 }
 
-constexpr int WD_INV_THREADS = 256;
+constexpr int WD_INV_THREADS = WD_INV_LANES;
 
 __global__ __launch_bounds__(WD_INV_THREADS) void k_webp_dec_inverse(uint8_t* __restrict__ mem, const WdFileDesc* __restrict__ files,
                                                                       const uint32_t* __restrict__ status) {

@@ -261,9 +261,10 @@ inline uint32_t* wd_inverse_host(const WdPlan& P, uint32_t* a, uint32_t* b) {
             for (int j = 0; j < L; j++) wd_inv_index(cur, other, w, P.h, t.bits, data, t.ncolors, (uint32_t)j, (uint32_t)L);
             std::swap(cur, other);
         } else {
-            for (int row0 = 0; row0 < P.h; row0 += L)
-                for (int s = 0; s < wd_pred_steps(w, L); s++)
-                    for (int j = 0; j < L; j++) wd_inv_pred_step(cur, w, P.h, t.bits, data, row0, s, j);
+            const int band = P.h < WD_INV_LANES ? P.h : WD_INV_LANES;       // the device's bands: the same rows are a band's first
+            for (int row0 = 0; row0 < P.h; row0 += band)
+                for (int s = 0; s < wd_pred_steps(w, band); s++)
+                    for (int j = 0; j < band; j++) wd_inv_pred_step(cur, w, P.h, t.bits, data, row0, s, j);
         }
     }
     return cur;
@@ -289,8 +290,10 @@ inline int wd_decode_host(const uint8_t* blob, size_t size, uint8_t* out, size_t
     const WdImage im = wd_main_image(P, codes.data(), sorted.data(), a.data());
     uint64_t endbit = 0;
     uint32_t feat = P.feat;
-    const int status = wd_rounds_host(im, P.bitpos, m.get(), &feat, &endbit);
-    if (info) { info[0] = (int)feat; info[5] = status; }
+    int rounds = 0, longest = 0;
+    const int status = wd_rounds_host(im, P.bitpos, m.get(), &feat, &endbit, &rounds);
+    for (uint8_t l : P.lens) longest = std::max(longest, (int)l);
+    if (info) { info[0] = (int)feat; info[5] = status; info[6] = rounds; info[7] = longest; }
     if (status) return IMP_ERROR_DECODE_FAILED;
     uint32_t* cur = wd_inverse_host(P, a.data(), b.data());
     uint32_t* dst = cur == a.data() ? b.data() : a.data();

@@ -2,7 +2,8 @@
 B,G,R,A frame Pillow's libwebp DECODER gives for each (alpha 255 where the file's alpha_is_used bit is clear: Pillow opens
 such a file as RGB).  Two kinds of file:
   * Pillow's libwebp ENCODER (lossless=True, methods 0 / 3 / 6) on seeded numpy frames: p_<name>_m<method>.webp;
-  * the hand-written streams of tests/webp_dec_cases.py: h_<name>.webp;
+  * the hand-written streams of tests/webp_dec_cases.py: h_<name>.webp from cases() (the format) and h_b_<family><what>.webp
+    from boundary_cases() (the implementation's seams);
 and three files the decoder must refuse (lossy.webp, anim.webp, not_webp.png), which have no expectation.
 expected.npz holds a Pillow-encoded frame once for its three methods (key p_<name>) and every hand-written file (h_<name>).
 Made with Pillow 12.2.0 / libwebp 1.6.0:   python tests/golden/webp_dec/make_webp_dec_golden.py
@@ -58,7 +59,7 @@ def main():
             bio = io.BytesIO()
             Image.fromarray(frame).save(bio, "WEBP", lossless=True, method=method, **kw)
             files.append(("p_%s_m%d" % (name, method), bio.getvalue()))
-    files += [("h_" + name, blob) for name, blob in webp_dec_cases.cases()]
+    files += [("h_" + name, blob) for name, blob in webp_dec_cases.cases() + webp_dec_cases.boundary_cases()]
     for f in os.listdir(HERE):
         if f.endswith(".webp") or f.endswith(".png") or f.endswith(".npz"):
             os.remove(os.path.join(HERE, f))

@@ -1,6 +1,6 @@
 """impgpu_image_decode_webp / impgpu_batch_decode_webp on the device against Pillow's frames for the fixtures of
 tests/golden/webp_dec (Pillow-encoded at methods 0 / 3 / 6 and the hand-written streams of webp_dec_cases.py): alone, the
-whole set in one call with a lossy and two damaged files in its middle, a call of one, a call cut into two groups by
+whole set in calls of at most 256 files with a lossy and two damaged files in the middle of each, a call of one, a call cut into two groups by
 $IMPGPU_STAGE_CAP_MB, and a decoded frame going on through resize like an uploaded one."""
 import ctypes as C
 import json
@@ -40,22 +40,28 @@ def test_every_fixture_alone(gpu):
 
 
 def test_the_whole_set_in_one_call_with_refused_and_damaged_files_in_the_middle(gpu):
+    """every fixture, in calls of at most 256 files (what a call takes): 253 fixtures a call and the three others in its middle"""
     imp = gpu
-    fixtures = F.load()[:250]
+    every = F.load()
     damaged = F.damaged()
     host = [imp.ops.webp_decode_host(blob)[0] for _, blob in damaged]
     assert host == [F.IMP_ERROR_DECODE_FAILED] * 2
-    half = len(fixtures) // 2
-    blobs = [b for _, b, _ in fixtures[:half]] + [damaged[0][1], F.read("lossy.webp"), damaged[1][1]] + [b for _, b, _ in fixtures[half:]]
-    want = [e for _, _, e in fixtures[:half]] + [None] * 3 + [e for _, _, e in fixtures[half:]]
-    codes = [0] * half + [host[0], F.IMP_ERROR_UNSUPPORTED, host[1]] + [0] * (len(fixtures) - half)
-    assert len(blobs) <= 256
-    results, launches = imp.ops.batch_decode_webp(blobs)
-    assert launches == LAUNCHES
-    got = _frames(results)
-    assert [rc for rc, _ in got] == codes
-    for k, ((rc, frame), e) in enumerate(zip(got, want)):
-        assert (frame is None) == (e is None) and (e is None or np.array_equal(frame, e)), k
+    covered = []
+    for at in range(0, len(every), 253):
+        fixtures = every[at:at + 253]
+        half = len(fixtures) // 2
+        blobs = [b for _, b, _ in fixtures[:half]] + [damaged[0][1], F.read("lossy.webp"), damaged[1][1]] + [b for _, b, _ in fixtures[half:]]
+        want = [e for _, _, e in fixtures[:half]] + [None] * 3 + [e for _, _, e in fixtures[half:]]
+        codes = [0] * half + [host[0], F.IMP_ERROR_UNSUPPORTED, host[1]] + [0] * (len(fixtures) - half)
+        assert len(blobs) <= 256
+        results, launches = imp.ops.batch_decode_webp(blobs)
+        assert launches == LAUNCHES
+        got = _frames(results)
+        assert [rc for rc, _ in got] == codes
+        for k, ((rc, frame), e) in enumerate(zip(got, want)):
+            assert (frame is None) == (e is None) and (e is None or np.array_equal(frame, e)), (at, k)
+        covered += [name for name, _, _ in fixtures]
+    assert covered == [name for name, _, _ in every] and len(set(covered)) == len(every) >= 301
 
 
 def test_a_call_of_one_and_calls_nothing_is_launched_for(gpu):
