@@ -1225,6 +1225,92 @@ int impgpu_batch_decode_webp(const unsigned char* const* blobs, const size_t* si
  * at 512 tokens or where the 512 staged words run low), [7] the longest code length among the main image's codes. */
 int impgpu_webp_decode_host(const unsigned char* blob, size_t size, unsigned char* out, size_t capacity, int* width, int* height, int* info);
 
+/* ---- WEBP UPLOADS in, LOSSY (a VP8 key frame), decoded ON THE DEVICE (opt-in twice: the _ex calls below, and in them the
+ *      IMPGPU_WEBP_ACCEPT_LOSSY bit of `accept`; the broker only with --webp-accept all).  accept == 0 IS the call without
+ *      _ex: the same frames, codes and launch counts, a lossy file still IMP_ERROR_UNSUPPORTED.  With the bit set a call may
+ *      mix lossless, lossy, refused and damaged files in any order; each is judged on its own.
+ *      THE FRAME is what the reference's route gives for the file -- FreeImage's WebP plugin, ConvertTo32Bits, LoadSingle,
+ *      impgpu_image_upload_fi32: 4 channels, top-down, B,G,R,A with A = 255 -- libwebp's default decode (fancy chroma
+ *      upsampling, no dithering), byte for byte what Pillow's libwebp returns as mode RGB.  Where libwebp and RFC 6386
+ *      differ libwebp is followed: the edge values 127 / 129, the above-right samples of the rightmost macroblock, the 16-bit
+ *      storage of de-quantised coefficients (and the 16-bit lanes of its inverse DCT for blocks past three coefficients:
+ *      "libwebp" here is its x86 SSE2 build, the one Pillow ships; a NEON or plain-C build may differ from it, and so from
+ *      this decoder, on streams whose coefficients leave 16 bits -- no encoder writes such values),
+ *      frame level 0 switching the filter off whatever the segments say, the clamp and scale bits ignored.
+ *      TAKEN: a RIFF / WEBP file whose image is ONE `VP8 ` chunk, alone or inside VP8X without ALPH and animation (ICCP,
+ *      EXIF, XMP and unknown chunks are skipped); all of a key frame: versions 0..3; any size up to 16383 a side under
+ *      IMPGPU_WEBP_DEC_MAX_PIXELS, multiples of 16 or not; 1, 2, 4 and 8 token partitions, empty ones included (a size in
+ *      the table that runs past the chunk is cut to it, as libwebp does); segmentation with and without a map update,
+ *      absolute or delta values; the five quantiser deltas, indices clamped to 0..127; coefficient probability updates;
+ *      mb_no_coeff_skip 0 and 1; the four 16x16 and chroma modes, B_PRED with the ten sub-block modes; every token category
+ *      up to DCT_CAT6; both loop filters at levels 0..63 and sharpness 0..7 with the key frame's high-edge-variance
+ *      thresholds; mode_ref_lf_delta; the inner-edge rule.
+ *      IMP_ERROR_UNSUPPORTED (decode on the host as before): ALPH, ANIM / ANMF, an inter frame (libwebp: "Not a key frame",
+ *      VP8_STATUS_UNSUPPORTED_FEATURE), show_frame 0 ("Frame not displayable", the same status), more pixels than the limit,
+ *      not a WebP.
+ *      IMP_ERROR_DECODE_FAILED: a `VP8 ` chunk (or any chunk in front of the image) whose size runs past the file -- with the
+ *      bit set the four calls agree on that; without it such a file is IMP_ERROR_UNSUPPORTED as in the calls without _ex,
+ *      which refuse the chunk by its name before they look at its size; a bad start code (VP8_STATUS_BITSTREAM_ERROR); a version past 3 (libwebp answers "Incorrect
+ *      keyframe parameters" before any pixel: a stream no decoder of this format reads, so a failure here, not a route to
+ *      the host); a width or height of 0; a first partition or a partition table that runs past the chunk, a last
+ *      partition of no bytes (VP8_STATUS_NOT_ENOUGH_DATA / SUSPENDED); a frame header that runs off the first partition; a
+ *      partition the decoder runs off the end of (NOT_ENOUGH_DATA).  The last follows libwebp's rule exactly: the end is
+ *      looked at per macroblock (per macroblock row for the first partition), and failure comes only once a byte past the
+ *      end HAD to be loaded -- so a file whose last partition lost its 1..3 bytes of flush still decodes to the same frame.
+ *      HOW: the host reads the container, the frame tag, the frame header and the partition table (imp_vp8_dec_host.h, with
+ *      the lanes' boolean decoder); a descriptor and the chunk's bytes per file go up in the group's ONE upload, beside the
+ *      lossless files' blocks.  IMPGPU_WEBP_DEC_LOSSY_LAUNCHES (3) kernels a group that holds a lossy file, whatever else it
+ *      holds (a group with a lossless file adds IMPGPU_WEBP_DEC_LAUNCHES; a group of one kind launches that kind's only):
+ *      k_vp8_dec_recon (a workgroup per file; ONE lane walks the macroblocks in raster order: modes from the first
+ *      partition, tokens from the row's partition, prediction and inverse transforms into padded planes -- everything a
+ *      macroblock depends on is that lane's own earlier work, so nothing is waited for), k_vp8_dec_filter (a workgroup per
+ *      file: macroblocks in raster order, as the result depends on it; the 16 + 8 + 8 lines of an edge side by side, eight
+ *      barrier-separated steps a macroblock) and k_vp8_dec_frame (fully parallel: upsample, convert, crop).  Every loop
+ *      over stream data is bounded by the partition's size, 16 coefficients a block and the macroblock count: a damaged file
+ *      sets its status word, writes only its own planes and cannot hang.  ONE wait per call.
+ *      MEASURED (profiles/webp_lossy_decode_probe.json, tools/webp_lossy_decode_probe.py; one session, Pillow-encoded files at
+ *      quality 75; the call against Pillow's decode of the same file on one core + impgpu_image_upload, medians after a
+ *      warm-up): a lone 640x480 file 113.4 / 1.9 ms photo-like, 283.3 / 4.2 dithered, 69.8 / 1.4 flat; a lone 1920x1080 file
+ *      777 / 12.6, 1931 / 29.1, 468 / 10.1; 64 files of 320x240 30.0 / 32.8, 76.4 / 70.8, 18.4 / 24.3; the host front 0.01-0.02
+ *      ms a file.  One lane on sequential boolean streams LOSES to the host for a lone file by 46-67x.  The files of a call
+ *      decode side by side, so a call takes what its slowest file takes, and the crossover lies near 64 files of 320x240 a
+ *      call (ahead 1.1x photo-like and 1.3x flat there, behind 1.08x dithered).  Per kernel (a separate rocprofv3 --kernel-trace
+ *      run of the same cases): k_vp8_dec_recon is 91-98 % of every call (640x480: 102.9 / 276.6 / 66.2 ms; 1920x1080: 717 /
+ *      1937 / 438), k_vp8_dec_filter 2.3-7.0 ms at 640x480 and 16-51 ms at 1920x1080, k_vp8_dec_frame 0.02-0.09 ms.  It takes decode work off the workers' cores; it does not answer a lone request sooner. ---- */
+#define IMPGPU_WEBP_ACCEPT_LOSSY 1
+#define IMPGPU_WEBP_DEC_LOSSY_LAUNCHES 3
+/* the feature word of a lossy file, info[0] of impgpu_webp_decode_host_ex */
+#define IMPGPU_VP8_DEC_F_SEGMENTS     0x000001
+#define IMPGPU_VP8_DEC_F_MAP_UPDATE   0x000002
+#define IMPGPU_VP8_DEC_F_DELTA_VALUES 0x000004   /* segment values added to the frame's */
+#define IMPGPU_VP8_DEC_F_SIMPLE       0x000008   /* the simple loop filter, at a level above 0 */
+#define IMPGPU_VP8_DEC_F_NORMAL       0x000010
+#define IMPGPU_VP8_DEC_F_SHARPNESS    0x000020
+#define IMPGPU_VP8_DEC_F_LF_DELTA     0x000040
+#define IMPGPU_VP8_DEC_F_PARTS2       0x000080
+#define IMPGPU_VP8_DEC_F_PARTS4       0x000100
+#define IMPGPU_VP8_DEC_F_PARTS8       0x000200
+#define IMPGPU_VP8_DEC_F_BPRED        0x000400
+#define IMPGPU_VP8_DEC_F_PROB_UPDATE  0x000800
+#define IMPGPU_VP8_DEC_F_SKIP_OFF     0x001000   /* mb_no_coeff_skip 0 */
+#define IMPGPU_VP8_DEC_F_DQ_Y1DC      0x002000   /* a quantiser delta other than 0: y dc, y2 dc, y2 ac, uv dc, uv ac */
+#define IMPGPU_VP8_DEC_F_DQ_Y2DC      0x004000
+#define IMPGPU_VP8_DEC_F_DQ_Y2AC      0x008000
+#define IMPGPU_VP8_DEC_F_DQ_UVDC      0x010000
+#define IMPGPU_VP8_DEC_F_DQ_UVAC      0x020000
+#define IMPGPU_VP8_DEC_F_CAT6         0x040000
+#define IMPGPU_VP8_DEC_F_CROP_W       0x080000   /* a width that is no multiple of 16 */
+#define IMPGPU_VP8_DEC_F_CROP_H       0x100000
+#define IMPGPU_VP8_DEC_F_ALL          0x1fffff
+#define IMPGPU_VP8_DEC_MODES_ALL      0x3ffff    /* info[1]: 16x16 modes in bits 0..3, chroma 4..7, sub-block 8..17 (libwebp's order) */
+/* The calls above with an accept mask.  For a lossy file impgpu_webp_decode_host_ex fills info[] with: [0] the feature
+ * word above, [1] the masks of the modes met, [2] token partitions, [3] macroblock columns, [4] macroblock rows, [5] the
+ * status word (0 complete, 1 ran off a partition), [6] 0, [7] 1 (a lossless file leaves 0 there). */
+int impgpu_webp_info_ex(const unsigned char* blob, size_t size, int accept, int* width, int* height, int* channels);
+int impgpu_image_decode_webp_ex(const unsigned char* blob, size_t size, int accept, impgpu_image** out);
+int impgpu_batch_decode_webp_ex(const unsigned char* const* blobs, const size_t* sizes, int count, int accept, impgpu_image** images, int* codes, int* launches);
+int impgpu_webp_decode_host_ex(const unsigned char* blob, size_t size, int accept, unsigned char* out, size_t capacity, int* width, int* height, int* info);
+
 /* ---- batch entry points (benchmark / multi-frame albums: bridge.c:578,591,608,632).
  *      `count` frames of identical geometry, frame i at base + i*frame_stride bytes,
  *      already resident in HBM.  stream = hipStream_t to launch on (NULL = env stream).

@@ -206,6 +206,10 @@ SIGNATURES = {
     "impgpu_image_decode_webp": (C.c_int, [C.c_char_p, C.c_size_t, PP]),
     "impgpu_batch_decode_webp": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, PP, IP, IP]),
     "impgpu_webp_decode_host": (C.c_int, [C.c_char_p, C.c_size_t, P, C.c_size_t, IP, IP, IP]),
+    "impgpu_webp_info_ex": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, IP, IP, IP]),
+    "impgpu_image_decode_webp_ex": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, PP]),
+    "impgpu_batch_decode_webp_ex": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, PP, IP, IP]),
+    "impgpu_webp_decode_host_ex": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, P, C.c_size_t, IP, IP, IP]),
     "impgpu_album_download_fi": (C.c_int, [P, C.c_int, PP, IP]),
     "impgpu_batch_download_fi": (C.c_int, [PP, IP, C.c_int, PP, IP, IP, IP]),
     "impgpu_batch_album_download": (C.c_int, [PP, C.c_int, PP, IP, IP]),

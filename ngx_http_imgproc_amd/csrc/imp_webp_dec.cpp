@@ -5,12 +5,17 @@
 // from one pinned block; behind them the status words (zeroed) and per file the codes, their sorted symbols and the
 // residual plane, which never cross the link -- runs the three launches of imp_webp_dec.hip on it and waits ONCE per
 // call, for the status words of all its groups.  impgpu_webp_decode_host is the same decoder with no device.
+// The _ex calls with IMPGPU_WEBP_ACCEPT_LOSSY take VP8 key frames too (imp_vp8_dec_host.h, imp_vp8_dec.hip): a lossy file
+// puts a descriptor and its chunk's bytes into the same upload, its planes and contexts behind it, and its status word
+// behind the lossless files' -- a group launches each kind's kernels only if it holds that kind.
 #include "imp_internal.h"
 #include "imp_enc_host.h"
 #include "imp_webp_dec_host.h"
+#include "imp_vp8_dec_host.h"
 
 namespace imp {
 
+int launch_vp8_decode(uint8_t* mem, const VdFileDesc* files, uint32_t* status, int nfiles, hipStream_t s);
 int launch_webp_decode(uint8_t* mem, const WdFileDesc* files, const WdCodeItem* items, long long nitems, uint32_t* status, int nfiles, hipStream_t s);
 
 namespace {
@@ -18,6 +23,8 @@ namespace {
 struct WdEntry {
     int entry;                            // its index in the call's arrays
     WdPlan plan;
+    bool lossy = false;
+    VdPlan vplan;
     size_t upload, device;                // what it puts into the group's upload, and behind it
 };
 
@@ -31,6 +38,12 @@ size_t wd_device_bytes(const WdPlan& P) {
            up256((size_t)P.w * (size_t)P.h * 4u) + 256u;
 }
 
+size_t vd_upload_bytes(const VdPlan& P) { return up256(sizeof(VdFileDesc)) + up256(P.chunk.size()); }
+size_t vd_device_bytes(const VdPlan& P) {
+    const size_t mbw = (size_t)P.hdr.mbw, mbh = (size_t)P.hdr.mbh;
+    return up256(mbw * mbh * 256u) + 2u * up256(mbw * mbh * 64u) + up256(mbw * mbh * 4u) + up256(mbw * 6u) + 256u;
+}
+
 struct WdGroupRun {                       // a group in flight: its block lives until the call's one wait is over
     DevBlock block;
     std::vector<int> entries;
@@ -39,9 +52,15 @@ struct WdGroupRun {                       // a group in flight: its block lives 
 };
 
 // one group: upload and launches, nothing waited for
-int decode_group(const std::vector<WdEntry*>& group, impgpu_image** images, WdGroupRun* run) {
+int decode_group(const std::vector<WdEntry*>& all, impgpu_image** images, WdGroupRun* run) {
     hipStream_t s = env_stream();
-    const int nf = (int)group.size();
+    std::vector<WdEntry*> group, lossy;                                 // the lossless files, then the lossy ones: the order of the status words
+    for (WdEntry* e : all) (e->lossy ? lossy : group).push_back(e);
+    const int nf = (int)group.size(), ny = (int)lossy.size();
+    run->entries.clear();
+    for (const WdEntry* e : group) run->entries.push_back(e->entry);
+    for (const WdEntry* e : lossy) run->entries.push_back(e->entry);
+    std::vector<VdFileDesc> vfd((size_t)ny);
     std::vector<WdFileDesc> fd((size_t)nf);
     std::vector<WdCodeItem> items;
     BlockLayout L;
@@ -71,8 +90,25 @@ int decode_group(const std::vector<WdEntry*>& group, impgpu_image** images, WdGr
         for (uint32_t g = 0; g < P.ngroups; g++)
             for (int k = 0; k < WD_CODES; k++) items.push_back(WdCodeItem{f, g, k, 0});
     }
+    const size_t o_vfd = L.take((size_t)ny * sizeof(VdFileDesc));
+    for (int f = 0; f < ny; f++) {
+        VdFileDesc& d = vfd[(size_t)f];
+        std::memset(&d, 0, sizeof d);
+        d.hdr = lossy[(size_t)f]->vplan.hdr;
+        d.chunk_off = (long long)L.take(lossy[(size_t)f]->vplan.chunk.size());
+        d.img = images[lossy[(size_t)f]->entry]->d;
+    }
     const size_t upload = L.size();                                     // where the upload ends
-    const size_t o_status = L.take((size_t)nf * 4u);
+    const size_t o_status = L.take((size_t)(nf + ny) * 4u);
+    for (int f = 0; f < ny; f++) {
+        VdFileDesc& d = vfd[(size_t)f];
+        const size_t nmb = (size_t)d.hdr.mbw * (size_t)d.hdr.mbh;
+        d.y_off = (long long)L.take(nmb * 256u);
+        d.u_off = (long long)L.take(nmb * 64u);
+        d.v_off = (long long)L.take(nmb * 64u);
+        d.finfo_off = (long long)L.take(nmb * 4u);
+        d.ctx_off = (long long)L.take((size_t)d.hdr.mbw * 6u);
+    }
     for (int f = 0; f < nf; f++) {
         const WdPlan& P = group[(size_t)f]->plan;
         fd[(size_t)f].codes_off = (long long)L.take((size_t)P.ngroups * WD_CODES * sizeof(WdCode));
@@ -84,8 +120,10 @@ int decode_group(const std::vector<WdEntry*>& group, impgpu_image** images, WdGr
     void *host = nullptr, *token = nullptr;
     if (int rc = stage_begin(upload, &host, &token)) return rc;
     uint8_t* hp = (uint8_t*)host;
-    std::memcpy(hp + o_fd, fd.data(), fd.size() * sizeof(WdFileDesc));
-    std::memcpy(hp + o_items, items.data(), items.size() * sizeof(WdCodeItem));
+    if (nf) std::memcpy(hp + o_fd, fd.data(), fd.size() * sizeof(WdFileDesc));
+    if (!items.empty()) std::memcpy(hp + o_items, items.data(), items.size() * sizeof(WdCodeItem));
+    if (ny) std::memcpy(hp + o_vfd, vfd.data(), vfd.size() * sizeof(VdFileDesc));
+    for (int f = 0; f < ny; f++) std::memcpy(hp + vfd[(size_t)f].chunk_off, lossy[(size_t)f]->vplan.chunk.data(), lossy[(size_t)f]->vplan.chunk.size());
     for (int f = 0; f < nf; f++) {
         const WdPlan& P = group[(size_t)f]->plan;
         const WdFileDesc& d = fd[(size_t)f];
@@ -97,15 +135,16 @@ int decode_group(const std::vector<WdEntry*>& group, impgpu_image** images, WdGr
     }
     int rc = stage_upload(token, m, upload);
     if (!rc) {
-        const hipError_t e = hipMemsetAsync(m + o_status, 0, up256((size_t)nf * 4u), s);
+        const hipError_t e = hipMemsetAsync(m + o_status, 0, up256((size_t)(nf + ny) * 4u), s);
         if (e != hipSuccess) { set_error("hipMemsetAsync(webp decode)", e); rc = IMP_ERROR_DEVICE; }
     }
     run->status = (uint32_t*)(m + o_status);
-    if (!rc) rc = launch_webp_decode(m, (const WdFileDesc*)(m + o_fd), (const WdCodeItem*)(m + o_items), (long long)nitems, run->status, nf, s);
+    if (!rc && nf) rc = launch_webp_decode(m, (const WdFileDesc*)(m + o_fd), (const WdCodeItem*)(m + o_items), (long long)nitems, run->status, nf, s);
+    if (!rc && ny) rc = launch_vp8_decode(m, (const VdFileDesc*)(m + o_vfd), run->status + nf, ny, s);
     return rc;
 }
 
-int batch_decode(const unsigned char* const* blobs, const size_t* sizes, int count, impgpu_image** images, int* codes, int* launches) {
+int batch_decode(const unsigned char* const* blobs, const size_t* sizes, int count, int accept, impgpu_image** images, int* codes, int* launches) {
     if (launches) *launches = 0;
     if (count < 0 || count > 256 || (count > 0 && (!blobs || !sizes || !images || !codes))) return IMP_ERROR_INVALID_ARGS;
     for (int i = 0; i < count; i++) images[i] = nullptr;
@@ -122,9 +161,21 @@ int batch_decode(const unsigned char* const* blobs, const size_t* sizes, int cou
         if (!blobs[i]) { codes[i] = IMP_ERROR_INVALID_ARGS; continue; }
         std::unique_ptr<WdEntry> e(new WdEntry());
         e->entry = i;
-        if ((codes[i] = wd_parse(blobs[i], sizes[i], &e->plan, mem.get())) != IMP_OK) continue;
-        e->upload = wd_upload_bytes(e->plan);
-        e->device = wd_device_bytes(e->plan);
+        const uint8_t* payload = nullptr;
+        uint32_t psize = 0;
+        int lossy = 0;
+        if ((codes[i] = vd_route(blobs[i], sizes[i], accept, &payload, &psize, &lossy)) != IMP_OK) continue;
+        if (lossy) {
+            e->lossy = true;
+            if ((codes[i] = vd_plan(payload, psize, &e->vplan)) != IMP_OK) continue;
+            e->plan.w = e->vplan.hdr.w; e->plan.h = e->vplan.hdr.h;
+            e->upload = vd_upload_bytes(e->vplan);
+            e->device = vd_device_bytes(e->vplan);
+        } else {
+            if ((codes[i] = wd_parse(blobs[i], sizes[i], &e->plan, mem.get())) != IMP_OK) continue;
+            e->upload = wd_upload_bytes(e->plan);
+            e->device = wd_device_bytes(e->plan);
+        }
         if (cap && e->upload + e->device > cap) { codes[i] = IMP_ERROR_MALLOC_FAILED; continue; }   // a file that does not fit under the stage cap
         if ((codes[i] = image_new(e->plan.w, e->plan.h, 4, &images[i])) != IMP_OK) { images[i] = nullptr; continue; }
         taken.push_back(std::move(e));
@@ -146,7 +197,6 @@ int batch_decode(const unsigned char* const* blobs, const size_t* sizes, int cou
             fail(group, rc);
             hard = rc;
         } else {
-            for (const WdEntry* e : group) run->entries.push_back(e->entry);
             run->piece = words.add(run->status, group.size() * 4u);
         }
         runs.push_back(std::move(run));
@@ -196,14 +246,39 @@ int impgpu_webp_decode_host(const unsigned char* blob, size_t size, unsigned cha
 }
 
 int impgpu_batch_decode_webp(const unsigned char* const* blobs, const size_t* sizes, int count, impgpu_image** images, int* codes, int* launches) {
-    return batch_decode(blobs, sizes, count, images, codes, launches);
+    return batch_decode(blobs, sizes, count, 0, images, codes, launches);
 }
 
 int impgpu_image_decode_webp(const unsigned char* blob, size_t size, impgpu_image** out) {
     if (out) *out = nullptr;
     if (!blob || !out) return IMP_ERROR_INVALID_ARGS;
     int code = IMP_OK;
-    if (int rc = batch_decode(&blob, &size, 1, out, &code, nullptr)) return rc;
+    if (int rc = batch_decode(&blob, &size, 1, 0, out, &code, nullptr)) return rc;
+    return code;
+}
+
+int impgpu_webp_info_ex(const unsigned char* blob, size_t size, int accept, int* width, int* height, int* channels) {
+    int w = 0, h = 0;
+    if (int rc = vd_info(blob, size, accept, &w, &h)) return rc;
+    if (width) *width = w;
+    if (height) *height = h;
+    if (channels) *channels = 4;
+    return IMP_OK;
+}
+
+int impgpu_webp_decode_host_ex(const unsigned char* blob, size_t size, int accept, unsigned char* out, size_t capacity, int* width, int* height, int* info) {
+    return vd_decode_host_any(blob, size, accept, out, capacity, width, height, info);
+}
+
+int impgpu_batch_decode_webp_ex(const unsigned char* const* blobs, const size_t* sizes, int count, int accept, impgpu_image** images, int* codes, int* launches) {
+    return batch_decode(blobs, sizes, count, accept, images, codes, launches);
+}
+
+int impgpu_image_decode_webp_ex(const unsigned char* blob, size_t size, int accept, impgpu_image** out) {
+    if (out) *out = nullptr;
+    if (!blob || !out) return IMP_ERROR_INVALID_ARGS;
+    int code = IMP_OK;
+    if (int rc = batch_decode(&blob, &size, 1, accept, out, &code, nullptr)) return rc;
     return code;
 }
 

@@ -1164,31 +1164,44 @@ def request_webp_quality(uri, extension="", config=None):
     return Request(uri, extension, config).webp_quality
 
 
-def webp_info(blob):
-    """impgpu_webp_info -> (code, width, height, channels); host only."""
+WEBP_ACCEPT_LOSSY = 1                         # IMPGPU_WEBP_ACCEPT_LOSSY
+WEBP_DEC_LOSSY_LAUNCHES = 3                   # IMPGPU_WEBP_DEC_LOSSY_LAUNCHES
+
+
+def webp_info(blob, accept=None):
+    """impgpu_webp_info -> (code, width, height, channels); host only.  accept: None = the call itself; a mask =
+    impgpu_webp_info_ex (WEBP_ACCEPT_LOSSY: a VP8 key frame's size too)."""
     b = bytes(blob)
     w, h, c = C.c_int(0), C.c_int(0), C.c_int(0)
+    if accept is not None:
+        rc = lib.impgpu_webp_info_ex(b, len(b), int(accept), C.byref(w), C.byref(h), C.byref(c))
+        return rc, w.value, h.value, c.value
     rc = lib.impgpu_webp_info(b, len(b), C.byref(w), C.byref(h), C.byref(c))
     return rc, w.value, h.value, c.value
 
 
-def webp_decode_host(blob, capacity=None, guard=64):
+def webp_decode_host(blob, capacity=None, guard=64, accept=None):
     """impgpu_webp_decode_host (no device): a lossless WebP file -> (code, HxWx4 B,G,R,A array or None, info, intact).
-    capacity defaults to what impgpu_webp_info says the frame takes; `intact`: the guard band behind it was not written."""
+    capacity defaults to what impgpu_webp_info says the frame takes; `intact`: the guard band behind it was not written.
+    accept: None = the call itself; a mask = impgpu_webp_decode_host_ex (WEBP_ACCEPT_LOSSY: lossy files too)."""
     b = bytes(blob)
-    rc, w, h, _ = webp_info(b)
+    rc, w, h, _ = webp_info(b, accept)
     cap = (w * h * 4 if rc == 0 else 0) if capacity is None else int(capacity)
     buf = np.full(max(1, cap) + guard, 0xA5, np.uint8)
     ww, hh = C.c_int(0), C.c_int(0)
     info = (C.c_int * 8)()
-    rc = lib.impgpu_webp_decode_host(b, len(b), buf.ctypes.data, cap, C.byref(ww), C.byref(hh), info)
+    if accept is None:
+        rc = lib.impgpu_webp_decode_host(b, len(b), buf.ctypes.data, cap, C.byref(ww), C.byref(hh), info)
+    else:
+        rc = lib.impgpu_webp_decode_host_ex(b, len(b), int(accept), buf.ctypes.data, cap, C.byref(ww), C.byref(hh), info)
     intact = bool((buf[cap:] == 0xA5).all())
     frame = buf[:ww.value * hh.value * 4].reshape(hh.value, ww.value, 4).copy() if rc == 0 else None
     return rc, frame, list(info), intact
 
 
-def batch_decode_webp(blobs, count=None):
-    """impgpu_batch_decode_webp -> ([(code, Image or None)] in the order of `blobs`, kernel launches of the call)."""
+def batch_decode_webp(blobs, count=None, accept=None):
+    """impgpu_batch_decode_webp -> ([(code, Image or None)] in the order of `blobs`, kernel launches of the call).
+    accept: None = the call itself; a mask = impgpu_batch_decode_webp_ex."""
     n = len(blobs)
     keep = [bytes(b) for b in blobs]
     arr = (C.c_char_p * max(1, n))(*keep)
@@ -1196,17 +1209,23 @@ def batch_decode_webp(blobs, count=None):
     imgs = (C.c_void_p * max(1, n))()
     codes = (C.c_int * max(1, n))()
     launches = C.c_int()
-    rc = lib.impgpu_batch_decode_webp(arr, sizes, n if count is None else count, imgs, codes, C.byref(launches))
+    if accept is None:
+        rc = lib.impgpu_batch_decode_webp(arr, sizes, n if count is None else count, imgs, codes, C.byref(launches))
+    else:
+        rc = lib.impgpu_batch_decode_webp_ex(arr, sizes, n if count is None else count, int(accept), imgs, codes, C.byref(launches))
     if rc:
         raise ImpError(rc, "impgpu_batch_decode_webp")
     return [(codes[i], Image(handle=imgs[i]) if codes[i] == 0 else None) for i in range(n)], launches.value
 
 
-def decode_webp(blob):
-    """impgpu_image_decode_webp -> (code, Image or None)."""
+def decode_webp(blob, accept=None):
+    """impgpu_image_decode_webp -> (code, Image or None).  accept: None = the call itself; a mask = impgpu_image_decode_webp_ex."""
     b = bytes(blob)
     h = C.c_void_p()
-    rc = lib.impgpu_image_decode_webp(b, len(b), C.byref(h))
+    if accept is None:
+        rc = lib.impgpu_image_decode_webp(b, len(b), C.byref(h))
+    else:
+        rc = lib.impgpu_image_decode_webp_ex(b, len(b), int(accept), C.byref(h))
     return rc, Image(handle=h.value) if rc == 0 else None
 
 
