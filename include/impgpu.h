@@ -1311,6 +1311,68 @@ int impgpu_image_decode_webp_ex(const unsigned char* blob, size_t size, int acce
 int impgpu_batch_decode_webp_ex(const unsigned char* const* blobs, const size_t* sizes, int count, int accept, impgpu_image** images, int* codes, int* launches);
 int impgpu_webp_decode_host_ex(const unsigned char* blob, size_t size, int accept, unsigned char* out, size_t capacity, int* width, int* height, int* info);
 
+/* ---- WEBP UPLOADS in, LOSSY WITH ALPHA (VP8X + ALPH + `VP8 `), decoded ON THE DEVICE (opt-in three times: the _ex calls,
+ *      IMPGPU_WEBP_ACCEPT_LOSSY and with it the IMPGPU_WEBP_ACCEPT_ALPHA bit of `accept`; the broker only with
+ *      --webp-accept alpha).  The bit means something only together with IMPGPU_WEBP_ACCEPT_LOSSY: accept 2 is accept 0, and
+ *      accept 0 / 1 and the calls without _ex give every frame, code and launch count they gave without it (such a file is
+ *      IMP_ERROR_UNSUPPORTED there).  These are the files libwebp, Pillow and impgpu_image_encode_webp_lossy (on a 4-channel
+ *      frame) write for cut-outs, stickers and logos.
+ *      THE FRAME: B,G,R are byte for byte those of the file's `VP8 ` chunk decoded alone; byte 3 is the alpha plane --
+ *      what Pillow's libwebp returns as mode RGBA.
+ *      THE ALPH CHUNK: a header byte -- bits 0-1 the method (0: w * h raw bytes follow, bytes behind them are ignored; 1: a
+ *      VP8L image stream WITHOUT its five header bytes, w x h the frame's, whose green channel is the plane), bits 2-3 the
+ *      filter (0 none, 1 horizontal, 2 vertical, 3 gradient), bits 4-5 pre-processing (0 or 1; 1 is level quantisation,
+ *      nothing to undo), bits 6-7 reserved -- then the residuals r.  The inverse filter, sums mod 256, a the alpha:
+ *      row 0 of every filter but none a[0][x] = r[0][x] + a[0][x-1] with a[0][0] = r[0][0]; column 0 of the rows below
+ *      a[y][0] = r[y][0] + a[y-1][0]; elsewhere horizontal adds a[y][x-1], vertical a[y-1][x], gradient
+ *      clip(a[y][x-1] + a[y-1][x] - a[y-1][x-1], 0, 255).
+ *      TAKEN: the canonical layout only -- a VP8X chunk of at least 10 bytes with the alpha flag (0x10) set and the
+ *      animation flag clear, whose canvas is the `VP8 ` frame's width x height, exactly ONE ALPH chunk in front of the one
+ *      `VP8 ` chunk, other chunks skipped (a repeated VP8X among them: the first one's flag and canvas hold).  A VP8X flag with no ALPH chunk gives A = 255, as the lossy route always did.
+ *      IMP_ERROR_UNSUPPORTED (the host decoder judges it as before; libwebp's plain decode and its demuxer disagree about
+ *      these, and this decoder does not pick a side): an ALPH in front of VP8L, an ALPH behind the image chunk, a second
+ *      ALPH, an ALPH without VP8X or with the alpha flag clear, a canvas that differs from the frame, ANIM / ANMF.
+ *      IMP_ERROR_DECODE_FAILED: an ALPH chunk of fewer than 2 bytes; a method above 1, pre-processing above 1 or a reserved
+ *      bit; a raw plane shorter than w * h; a VP8L stream the lossless decoder fails or that runs past its chunk; and
+ *      everything the lossy route fails.  The checks come in one order in all four calls: the container, the frame tag,
+ *      the canvas, the header byte, then the frame header and the streams.
+ *      HOW: a file with alpha is one lossy item as before.  A raw plane's w * h bytes join the group's ONE upload.  A VP8L
+ *      plane is parsed by the lossless front entered without container and header (wd_parse_stream, bit 0 of the byte
+ *      behind the header byte) and becomes one more item of the group's three lossless launches: its frame is a scratch
+ *      plane of w * h * 4 bytes in the group's device block that never crosses the link, and it has a status word of its
+ *      own -- the file fails if either of its two words is set.  Behind k_vp8_dec_frame and k_webp_dec_inverse on the same
+ *      stream ONE launch, IMPGPU_WEBP_DEC_ALPHA_LAUNCHES (1) a group that holds an alpha file: k_webp_alpha, a workgroup
+ *      a file, reads the raw bytes or byte 1 of each scratch word, undoes the filter and writes byte 3 of every pixel and
+ *      nothing else; a file with a status word set is skipped.  None is a copy; horizontal a prefix sum down column 0 and
+ *      then one along every row (a wave a row, 64 columns a step); vertical a prefix sum along row 0 and a lane a column
+ *      downwards; the gradient, which its clip makes sequential, runs a band of 64 rows in a wave, the rows a column
+ *      apart, left / top / top-left moving between lanes in registers and the band's last row to the next band through LDS,
+ *      one band after the other (MEASURED below says why not pipelined).  Every loop is bounded by w, h and the band count.
+ *      A group launches 3 (lossy) + 1 (alpha), and 3 more when it holds a lossless file or a VP8L plane.  ONE wait per call.
+ *      impgpu_webp_alpha_info (host only): info[0] method, [1] filter, [2] pre-processing, [3] the VP8L stream's feature
+ *      word as IMPGPU_WEBP_DEC_F_* (0 for a raw plane); IMP_ERROR_UNSUPPORTED for a file with no alpha plane this route
+ *      takes, the route's own code for a damaged one.  For a VP8L plane it walks the stream's entropy-coded image (back
+ *      references and distance codes show only there) into one buffer of w * h * 4 bytes -- no inverse transform, no
+ *      frame; a caller that only routes files needs no more than impgpu_webp_info_ex.
+ *      MEASURED (profiles/webp_alpha_decode_probe.json, tools/webp_alpha_decode_probe.py; one session, interleaved, medians after
+ *      a warm-up; photo-like colour at quality 75 with (a) a soft mask and (b) a noise alpha, both Pillow-written -- (a) comes
+ *      out as a VP8L plane, (b) as a raw one -- and (c) the mask hand-assembled under the gradient filter; the call with accept 3
+ *      / the same files' bare `VP8 ` chunks with accept 1 / Pillow's decode on one core + impgpu_image_upload, ms): a lone
+ *      640x480 file (a) 117.9 / 105.8 / 2.9, (b) 113.0 / 112.3 / 2.7, (c) 117.2 / 105.6 / 3.5; a lone 1920x1080 file (a) 794 /
+ *      717 / 20.0, (b) 772 / 775 / 17.4, (c) 747 / 703 / 24.2; 64 files of 320x240 (a) 35.2 / 28.5 / 52.5, (b) 30.4 / 30.0 / 44.0,
+ *      (c) 33.4 / 28.9 / 61.7.  A raw plane costs nothing that shows; a VP8L plane costs 4-12 ms at these sizes and 44-77 ms at
+ *      1920x1080, nearly all of it the lossless launches (k_webp_dec_pixels 31-73 ms at 1920x1080 for the mask under the four filters, 84 for Pillow's own file of it), which run in front of the
+ *      lossy ones on the one stream.  A lone file still LOSES to the host by 30-40x, as the lossy route does (the one-lane
+ *      k_vp8_dec_recon); 64 files of 320x240 a call are ahead 1.4-1.8x.  Per kernel (a separate rocprofv3 --kernel-trace
+ *      --stats run, the mask under each filter, k_webp_alpha none / horizontal / vertical / gradient next to
+ *      k_vp8_dec_recon, ms): 640x480 0.07 / 0.42 / 0.19 / 1.43 next to 97; 1920x1080 0.67 / 4.13 / 2.16 / 13.6 next to 658;
+ *      64 x 320x240 0.03 / 0.16 / 0.12 / 0.63 next to 26.4.  The gradient at 1920x1080 is 2.1 % of that call's k_vp8_dec_recon,
+ *      under the tenth that would have called for pipelining its bands across the workgroup's waves: they run one after
+ *      the other. ---- */
+#define IMPGPU_WEBP_ACCEPT_ALPHA 2
+#define IMPGPU_WEBP_DEC_ALPHA_LAUNCHES 1
+int impgpu_webp_alpha_info(const unsigned char* blob, size_t size, int info[4]);
+
 /* ---- batch entry points (benchmark / multi-frame albums: bridge.c:578,591,608,632).
  *      `count` frames of identical geometry, frame i at base + i*frame_stride bytes,
  *      already resident in HBM.  stream = hipStream_t to launch on (NULL = env stream).

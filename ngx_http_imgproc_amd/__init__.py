@@ -22,5 +22,6 @@ from .ops import (  # noqa: F401
     encode_gif, batch_encode_gif, encode_gif_host, gif_encode_bound, GIF_ENC_SEGMENT, gif_quantize_host, GIF_ENC_QUANTIZE, GIF_ENC_DELTA,
     encode_webp, batch_encode_webp, encode_webp_host, webp_encode_bound, WEBP_TILE_BITS, WEBP_ENC_BACKREFS, WEBP_MIN_MATCH,
     decode_webp, batch_decode_webp, webp_decode_host, webp_info, WEBP_ACCEPT_LOSSY, WEBP_DEC_LOSSY_LAUNCHES,
+    webp_alpha_info, WEBP_ACCEPT_ALPHA, WEBP_DEC_ALPHA_LAUNCHES,
     encode_webp_lossy, batch_encode_webp_lossy, encode_webp_lossy_host, webp_lossy_encode_bound, request_webp_quality,
 )

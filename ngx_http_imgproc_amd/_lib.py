@@ -210,6 +210,7 @@ SIGNATURES = {
     "impgpu_image_decode_webp_ex": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, PP]),
     "impgpu_batch_decode_webp_ex": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, PP, IP, IP]),
     "impgpu_webp_decode_host_ex": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, P, C.c_size_t, IP, IP, IP]),
+    "impgpu_webp_alpha_info": (C.c_int, [C.c_char_p, C.c_size_t, IP]),
     "impgpu_album_download_fi": (C.c_int, [P, C.c_int, PP, IP]),
     "impgpu_batch_download_fi": (C.c_int, [PP, IP, C.c_int, PP, IP, IP, IP]),
     "impgpu_batch_album_download": (C.c_int, [PP, C.c_int, PP, IP, IP]),

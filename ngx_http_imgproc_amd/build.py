@@ -31,6 +31,7 @@ SOURCES = [
     "imp_webp_enc.hip",
     "imp_webp_dec.hip",
     "imp_vp8_dec.hip",
+    "imp_webp_alpha.hip",
     "imp_webp_lossy.hip",
     "imp_api.cpp",
     "imp_args.cpp",
@@ -47,7 +48,7 @@ SOURCES = [
     "imp_webp_dec.cpp",
     "imp_webp_lossy.cpp",
 ]
-HEADERS = ["imp_internal.h", "imp_enc_host.h", "imp_host_pool.h", "imp_jpeg.h", "imp_jpeg_core.h", "imp_jpeg_plan.h", "imp_jpeg_prog.h", "imp_jpeg_std.h", "imp_png.h", "imp_png_deflate.h", "imp_inflate.h", "imp_inflate_lanes.h", "imp_gif.h", "imp_gif_plan.h", "imp_gif_enc.h", "imp_webp_enc.h", "imp_webp_dec.h", "imp_webp_dec_host.h", "imp_vp8_dec.h", "imp_vp8_dec_host.h", "imp_webp_lossy.h", os.path.join("..", "..", "include", "impgpu.h"), os.path.join("..", "..", "include", "impgpu_vp8_tables.h"), os.path.join("..", "..", "include", "impgpu_gif.h"),
+HEADERS = ["imp_internal.h", "imp_enc_host.h", "imp_host_pool.h", "imp_jpeg.h", "imp_jpeg_core.h", "imp_jpeg_plan.h", "imp_jpeg_prog.h", "imp_jpeg_std.h", "imp_png.h", "imp_png_deflate.h", "imp_inflate.h", "imp_inflate_lanes.h", "imp_gif.h", "imp_gif_plan.h", "imp_gif_enc.h", "imp_webp_enc.h", "imp_webp_dec.h", "imp_webp_dec_host.h", "imp_vp8_dec.h", "imp_vp8_dec_host.h", "imp_webp_alpha.h", "imp_webp_lossy.h", os.path.join("..", "..", "include", "impgpu.h"), os.path.join("..", "..", "include", "impgpu_vp8_tables.h"), os.path.join("..", "..", "include", "impgpu_gif.h"),
            os.path.join("..", "..", "include", "impgpu_broker.h")]
 FLAGS = [
     "--offload-arch=gfx950",

@@ -29,7 +29,7 @@
 //
 //   impgpu_broker [--name /impgpu-broker-0] [--device 0] [--slots 64] [--slot-mb 32] [--register-mb 8] [--threads 2] [--batch 64]
 //                 [--gather-us 0] [--png-accept none|all] [--png-inflate host|device] [--jpeg-accept none|progressive]
-//                 [--webp-accept none|lossless|all] [--supervise]
+//                 [--webp-accept none|lossless|all|alpha] [--supervise]
 //                 [--ready-file PATH]
 // --supervise: this process only forks and watches; the child is the broker.  A child that dies (a lost device, a bug) is
 // replaced by a FRESH child -- fork() from a parent that never touched the GPU, no exec of a process that did.
@@ -92,7 +92,8 @@ struct Options {
     // --webp-accept lossless: an IMPB_IN_FILE request whose bytes start RIFF....WEBP joins the batch's one
     // impgpu_batch_decode_webp call (lossless VP8L, decoded on the device); what that call refuses -- a lossy or animated
     // file, damage -- is NOT_TAKEN like the other decode refusals.  none (the default): such a file is NOT_TAKEN as before.
-    int webp_accept = 0;                  // 1 lossless, 2 all: the lossy bit goes to that one call too (VP8 key frames)
+    // alpha: all, and IMPGPU_WEBP_ACCEPT_ALPHA too (VP8X + ALPH + `VP8 `); under all such a file stays NOT_TAKEN.
+    int webp_accept = 0;                  // 1 lossless, 2 all: the lossy bit goes to that one call too (VP8 key frames), 3 alpha
     bool supervise = false;
     std::string ready_file;
 };
@@ -541,7 +542,7 @@ struct Worker {
                     blobs[j] = reqs[webps[j]].in;
                     sizes[j] = (size_t)reqs[webps[j]].q.in_bytes;
                 }
-                decoded(webps, impgpu_batch_decode_webp_ex(blobs.data(), sizes.data(), (int)m, O.webp_accept == 2 ? IMPGPU_WEBP_ACCEPT_LOSSY : 0, imgs.data(), codes.data(), nullptr));
+                decoded(webps, impgpu_batch_decode_webp_ex(blobs.data(), sizes.data(), (int)m, O.webp_accept == 3 ? IMPGPU_WEBP_ACCEPT_LOSSY | IMPGPU_WEBP_ACCEPT_ALPHA : O.webp_accept == 2 ? IMPGPU_WEBP_ACCEPT_LOSSY : 0, imgs.data(), codes.data(), nullptr));
             }
         }
         // every GIF of the batch: one upload of all their pages and ONE compose launch (advancedio.c:204-247), behind the file
@@ -860,7 +861,7 @@ int supervise(const Options& o) {
 
 static const char USAGE[] =
     "usage: impgpu_broker [--name /impgpu-broker-0] [--device 0] [--slots 64] [--slot-mb 32] [--register-mb 8] [--threads 2] [--batch 64] "
-    "[--gather-us 0] [--png-accept none|all] [--png-inflate host|device] [--jpeg-accept none|progressive] [--webp-accept none|lossless|all] [--supervise] [--ready-file PATH]\n";
+    "[--gather-us 0] [--png-accept none|all] [--png-inflate host|device] [--jpeg-accept none|progressive] [--webp-accept none|lossless|all|alpha] [--supervise] [--ready-file PATH]\n";
 
 int main(int argc, char** argv) {
     Options o;
@@ -901,8 +902,9 @@ int main(int argc, char** argv) {
             const std::string v = val("--webp-accept");
             if (v == "lossless") o.webp_accept = 1;
             else if (v == "all") o.webp_accept = 2;
+            else if (v == "alpha") o.webp_accept = 3;
             else if (v == "none") o.webp_accept = 0;
-            else { std::fprintf(stderr, "impgpu_broker: --webp-accept takes all, lossless or none\n"); std::fputs(USAGE, stderr); return 2; }
+            else { std::fprintf(stderr, "impgpu_broker: --webp-accept takes alpha, all, lossless or none\n"); std::fputs(USAGE, stderr); return 2; }
         }
         else if (a == "--supervise") o.supervise = true;
         else { std::fputs(USAGE, stderr); return 2; }

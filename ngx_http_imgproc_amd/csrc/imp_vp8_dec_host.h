@@ -3,11 +3,14 @@
 // partition -- segments, filter, partition count, quantisers, probability updates, the skip probability -- and the
 // partition table.  What comes out is a VdPlan: a VdHdr and the chunk's bytes, which go into the group's one upload.
 // vd_decode_host goes on from there with no device, the lanes one after the other -- impgpu_webp_decode_host_ex.
-// Host only, no HIP: tests/c/vp8_dec_test.cpp builds it with g++ under AddressSanitizer / UBSan.
+// With IMPGPU_WEBP_ACCEPT_ALPHA the front also finds a file's ALPH chunk (va_container, va_plane) and the host model
+// puts the plane into byte 3 (va_decode_host: imp_webp_alpha.h's lanes, a VP8L plane by the lossless front's wd_parse_stream).
+// Host only, no HIP: tests/c/vp8_dec_test.cpp and tests/c/webp_alpha_test.cpp build it with g++ under AddressSanitizer / UBSan.
 #pragma once
 #include <cstring>
 #include <vector>
 #include "imp_vp8_dec.h"
+#include "imp_webp_alpha.h"
 #include "imp_webp_dec_host.h"
 
 namespace imp {
@@ -187,13 +190,100 @@ inline int vd_plan(const uint8_t* payload, uint32_t n, VdPlan* P) {
     return IMP_OK;
 }
 
+// ---------------------------------------------------------------- the alpha plane (IMPGPU_WEBP_ACCEPT_ALPHA)
+struct VaChunk {                                  // what the container walk found
+    const uint8_t* p = nullptr;                   // the ALPH chunk's payload, its header byte first
+    uint32_t n = 0;
+    int canvas_w = 0, canvas_h = 0;               // VP8X's
+};
+struct VaPlane {                                  // the plane a file's frame gets; present 0: none, A stays 255
+    int present = 0, method = 0, filter = 0, pre = 0;
+    const uint8_t* data = nullptr;                // behind the header byte: w * h raw bytes (what follows is ignored), or the VP8L stream
+    uint32_t size = 0;
+};
+
+// The container with both bits set.  The canonical layout is taken: VP8X with the alpha flag (and no animation flag), ONE
+// ALPH chunk in front of the one `VP8 ` chunk, other chunks skipped (a second VP8X among them: the first one speaks).  An ALPH chunk anywhere else -- without VP8X or its
+// flag, a second one, in front of VP8L, behind the image chunk -- is IMP_ERROR_UNSUPPORTED: libwebp's plain decode and its
+// demuxer disagree about those, and the host decoder judges them as before.  A file without ALPH gets vd_container's verdict.
+inline int va_container(const uint8_t* blob, size_t size, const uint8_t** payload, uint32_t* psize, int* lossy, VaChunk* A) {
+    *lossy = 0;
+    *A = VaChunk{};
+    if (!blob || size < 12 || std::memcmp(blob, "RIFF", 4) != 0 || std::memcmp(blob + 8, "WEBP", 4) != 0) return IMP_ERROR_UNSUPPORTED;
+    const uint64_t riff_end = (uint64_t)wd_le32(blob + 4) + 8u;
+    const size_t end = riff_end < (uint64_t)size ? (size_t)riff_end : size;
+    size_t at = 12;
+    bool image = false, flagged = false, vp8x = false;
+    for (;;) {
+        if (at + 8 > end) return image ? IMP_OK : IMP_ERROR_DECODE_FAILED;
+        const uint8_t* c = blob + at;
+        const uint64_t n = wd_le32(c + 4);
+        const bool alph = !std::memcmp(c, "ALPH", 4);
+        if (image) {                                                          // behind the image only an ALPH is looked at
+            if (alph) return IMP_ERROR_UNSUPPORTED;
+            if ((uint64_t)at + 8u + n > (uint64_t)end) return IMP_OK;
+            at += 8 + (size_t)n + (size_t)(n & 1u);
+            continue;
+        }
+        if (!std::memcmp(c, "ANIM", 4) || !std::memcmp(c, "ANMF", 4)) return IMP_ERROR_UNSUPPORTED;
+        if (alph && (!flagged || A->p)) return IMP_ERROR_UNSUPPORTED;
+        if ((uint64_t)at + 8u + n > (uint64_t)end) return IMP_ERROR_DECODE_FAILED;
+        if (!std::memcmp(c, "VP8X", 4)) {
+            if (n >= 1 && (c[8] & 0x02)) return IMP_ERROR_UNSUPPORTED;
+            if (!vp8x) flagged = n >= 10 && (c[8] & 0x10);
+            if (!vp8x && n >= 10) {
+                A->canvas_w = 1 + (int)((uint32_t)c[12] | (uint32_t)c[13] << 8 | (uint32_t)c[14] << 16);
+                A->canvas_h = 1 + (int)((uint32_t)c[15] | (uint32_t)c[16] << 8 | (uint32_t)c[17] << 16);
+            }
+            vp8x = true;                                                      // a repeated VP8X is skipped like any other chunk: the first one's flag and canvas hold
+        }
+        if (alph) { A->p = c + 8; A->n = (uint32_t)n; }
+        if (!std::memcmp(c, "VP8L", 4) || !std::memcmp(c, "VP8 ", 4)) {
+            *lossy = c[3] == ' ';
+            if (A->p && !*lossy) return IMP_ERROR_UNSUPPORTED;
+            *payload = c + 8;
+            *psize = (uint32_t)n;
+            if (*lossy && (n & 1u) && (uint64_t)at + 8u + n + 1u <= (uint64_t)end) *psize += 1u;   // the pad byte: see vd_container
+            image = true;
+        }
+        at += 8 + (size_t)n + (size_t)(n & 1u);
+    }
+}
+
+// The ALPH chunk of a w x h frame -> IMP_OK and the plane, IMP_ERROR_UNSUPPORTED (a canvas that is not the frame) or
+// IMP_ERROR_DECODE_FAILED: fewer than 2 bytes, a method above 1, pre-processing above 1, a reserved bit, a raw plane
+// shorter than w * h.
+inline int va_plane(const VaChunk& A, int w, int h, VaPlane* P) {
+    *P = VaPlane{};
+    if (!A.p) return IMP_OK;
+    if (A.canvas_w != w || A.canvas_h != h) return IMP_ERROR_UNSUPPORTED;
+    if (A.n < 2u) return IMP_ERROR_DECODE_FAILED;
+    const uint32_t b = A.p[0];
+    P->method = (int)(b & 3u); P->filter = (int)((b >> 2) & 3u); P->pre = (int)((b >> 4) & 3u);
+    if (P->method > 1 || P->pre > 1 || (b >> 6)) return IMP_ERROR_DECODE_FAILED;
+    P->data = A.p + 1; P->size = A.n - 1u;
+    if (P->method == 0 && (uint64_t)P->size < (uint64_t)w * (uint64_t)h) return IMP_ERROR_DECODE_FAILED;
+    P->present = 1;
+    return IMP_OK;
+}
+
 // Which decoder a file goes to, for every _ex call alike.  Without the lossy bit: the lossless one, whose own container
 // walk gives the codes of the calls without _ex (*lossy = 0, nothing else looked at).  With it: vd_container's verdict is
-// the file's -- a `VP8 ` chunk that runs past the file is IMP_ERROR_DECODE_FAILED like any other chunk that does.
-inline int vd_route(const uint8_t* blob, size_t size, int accept, const uint8_t** payload, uint32_t* psize, int* lossy) {
+// the file's -- a `VP8 ` chunk that runs past the file is IMP_ERROR_DECODE_FAILED like any other chunk that does.  With
+// the alpha bit too: va_container's, and for a file with an ALPH chunk the frame tag's and va_plane's -- the one order of
+// the checks for the info call, the host model and the device path.
+inline int vd_route(const uint8_t* blob, size_t size, int accept, const uint8_t** payload, uint32_t* psize, int* lossy, VaPlane* alpha) {
     *lossy = 0;
+    *alpha = VaPlane{};
     if (!(accept & IMPGPU_WEBP_ACCEPT_LOSSY)) return IMP_OK;
-    return vd_container(blob, size, payload, psize, lossy);
+    if (!(accept & IMPGPU_WEBP_ACCEPT_ALPHA)) return vd_container(blob, size, payload, psize, lossy);
+    VaChunk A;
+    if (int rc = va_container(blob, size, payload, psize, lossy, &A)) return rc;
+    if (!A.p) return IMP_OK;
+    int w = 0, h = 0;
+    uint32_t first = 0;
+    if (int rc = vd_tag(*payload, *psize, &w, &h, &first)) return rc;
+    return va_plane(A, w, h, alpha);
 }
 
 // the geometry alone
@@ -201,9 +291,39 @@ inline int vd_info(const uint8_t* blob, size_t size, int accept, int* w, int* h)
     const uint8_t* p = nullptr;
     uint32_t n = 0, first = 0;
     int lossy = 0, alpha = 0;
-    if (int rc = vd_route(blob, size, accept, &p, &n, &lossy)) return rc;
+    VaPlane plane;
+    if (int rc = vd_route(blob, size, accept, &p, &n, &lossy, &plane)) return rc;
     if (!lossy) return wd_info(blob, size, w, h, &alpha);
     return vd_tag(p, n, w, h, &first);
+}
+
+// A VP8L alpha stream's front: the lossless parse entered without container and header -> IMP_OK or IMP_ERROR_DECODE_FAILED
+inline int va_parse_stream(const VaPlane& A, int w, int h, WdPlan* P, WdMem* m) {
+    P->w = w; P->h = h; P->alpha_used = 1;
+    return wd_parse_stream(A.data, A.size, 0, P, m) ? IMP_ERROR_DECODE_FAILED : IMP_OK;
+}
+
+// The plane into byte 3 of the w x h frame `out`, with no device; *feat (may be null): a VP8L stream's feature word.
+// out == nullptr: the feature word alone -- the stream's entropy-coded image is still walked (back references and
+// distance codes show only there), into one buffer of w * h words; no inverse transform, no frame.
+inline int va_decode_host(const VaPlane& A, int w, int h, uint8_t* out, uint32_t* feat) {
+    if (feat) *feat = 0;
+    if (A.method == 0) {
+        if (out) wa_unfilter_host(WaSrc{A.data, 1, 0}, out, w, h, A.filter);
+        return IMP_OK;
+    }
+    std::unique_ptr<WdMem> m(new WdMem());
+    WdPlan P;
+    if (int rc = va_parse_stream(A, w, h, &P, m.get())) return rc;
+    std::vector<uint32_t> a, b;
+    const uint32_t* argb = nullptr;
+    int info[IMPGPU_WEBP_DEC_INFO_WORDS] = {0};
+    info[0] = (int)P.feat;
+    const int rc = out ? wd_pixels_host(P, m.get(), info, &a, &b, &argb) : wd_coded_host(P, m.get(), info, &a);
+    if (feat) *feat = (uint32_t)info[0];
+    if (rc) return rc;
+    if (out) wa_unfilter_host(WaSrc{(const uint8_t*)argb, 4, 1}, out, w, h, A.filter);
+    return IMP_OK;
 }
 
 struct VdHostMem {
@@ -258,12 +378,34 @@ inline int vd_decode_host_any(const uint8_t* blob, size_t size, int accept, uint
     const uint8_t* p = nullptr;
     uint32_t n = 0;
     int lossy = 0;
-    const int rc = vd_route(blob, size, accept, &p, &n, &lossy);
+    VaPlane alpha;
+    int rc = vd_route(blob, size, accept, &p, &n, &lossy, &alpha);
     if (rc || lossy) {
         if (info) std::memset(info, 0, sizeof(int) * IMPGPU_WEBP_DEC_INFO_WORDS);
-        return rc ? rc : vd_decode_host(p, n, out, capacity, width, height, info);
+        if (rc) return rc;
+        int w = 0, h = 0;
+        rc = vd_decode_host(p, n, out, capacity, &w, &h, info);
+        if (width) *width = w;
+        if (height) *height = h;
+        if (rc == IMP_OK && alpha.present) rc = va_decode_host(alpha, w, h, out, nullptr);
+        return rc;
     }
     return wd_decode_host(blob, size, out, capacity, width, height, info);
+}
+
+// impgpu_webp_alpha_info
+inline int va_info(const uint8_t* blob, size_t size, int* info) {
+    const uint8_t* p = nullptr;
+    uint32_t n = 0, first = 0, feat = 0;
+    int lossy = 0, w = 0, h = 0;
+    VaPlane alpha;
+    if (int rc = vd_route(blob, size, IMPGPU_WEBP_ACCEPT_LOSSY | IMPGPU_WEBP_ACCEPT_ALPHA, &p, &n, &lossy, &alpha)) return rc;
+    if (!lossy || !alpha.present) return IMP_ERROR_UNSUPPORTED;
+    if (int rc = vd_tag(p, n, &w, &h, &first)) return rc;
+    if (alpha.method == 1)
+        if (int rc = va_decode_host(alpha, w, h, nullptr, &feat)) return rc;
+    if (info) { info[0] = alpha.method; info[1] = alpha.filter; info[2] = alpha.pre; info[3] = (int)feat; }
+    return IMP_OK;
 }
 
 }  // namespace imp

@@ -8,6 +8,10 @@
 // The _ex calls with IMPGPU_WEBP_ACCEPT_LOSSY take VP8 key frames too (imp_vp8_dec_host.h, imp_vp8_dec.hip): a lossy file
 // puts a descriptor and its chunk's bytes into the same upload, its planes and contexts behind it, and its status word
 // behind the lossless files' -- a group launches each kind's kernels only if it holds that kind.
+// With IMPGPU_WEBP_ACCEPT_ALPHA too a lossy file may bring an alpha plane (imp_webp_alpha.h): raw bytes that join the
+// upload, or a VP8L stream that is one more item of the lossless launches, decoded into a scratch plane behind the upload
+// with a status word of its own; k_webp_alpha (imp_webp_alpha.hip) then writes byte 3 of the frame.
+#include <algorithm>
 #include "imp_internal.h"
 #include "imp_enc_host.h"
 #include "imp_webp_dec_host.h"
@@ -17,6 +21,7 @@ namespace imp {
 
 int launch_vp8_decode(uint8_t* mem, const VdFileDesc* files, uint32_t* status, int nfiles, hipStream_t s);
 int launch_webp_decode(uint8_t* mem, const WdFileDesc* files, const WdCodeItem* items, long long nitems, uint32_t* status, int nfiles, hipStream_t s);
+int launch_webp_alpha(uint8_t* mem, const WaFileDesc* files, const uint32_t* status, int nfiles, hipStream_t s);
 
 namespace {
 
@@ -25,6 +30,7 @@ struct WdEntry {
     WdPlan plan;
     bool lossy = false;
     VdPlan vplan;
+    VaPlane alpha;                        // of a lossy file; method 1: `plan` is its VP8L stream's
     size_t upload, device;                // what it puts into the group's upload, and behind it
 };
 
@@ -44,9 +50,17 @@ size_t vd_device_bytes(const VdPlan& P) {
     return up256(mbw * mbh * 256u) + 2u * up256(mbw * mbh * 64u) + up256(mbw * mbh * 4u) + up256(mbw * 6u) + 256u;
 }
 
+size_t va_upload_bytes(const WdEntry& e) {
+    if (!e.alpha.present) return 0;
+    return up256(sizeof(WaFileDesc)) + (e.alpha.method ? wd_upload_bytes(e.plan) : up256((size_t)e.plan.w * (size_t)e.plan.h));
+}
+size_t va_device_bytes(const WdEntry& e) {                               // a VP8L plane: the stream's own blocks and the scratch plane it decodes into
+    return e.alpha.present && e.alpha.method ? wd_device_bytes(e.plan) + up256((size_t)e.plan.w * (size_t)e.plan.h * 4u) : 0;
+}
+
 struct WdGroupRun {                       // a group in flight: its block lives until the call's one wait is over
     DevBlock block;
-    std::vector<int> entries;
+    std::vector<int> entries;             // the entry of every status word: a lossy file with a VP8L plane has two
     uint32_t* status = nullptr;
     int piece = -1;
 };
@@ -54,12 +68,20 @@ struct WdGroupRun {                       // a group in flight: its block lives 
 // one group: upload and launches, nothing waited for
 int decode_group(const std::vector<WdEntry*>& all, impgpu_image** images, WdGroupRun* run) {
     hipStream_t s = env_stream();
-    std::vector<WdEntry*> group, lossy;                                 // the lossless files, then the lossy ones: the order of the status words
+    // the lossless files, the VP8L alpha planes (lossless items too), then the lossy files: the order of the status words
+    std::vector<WdEntry*> group, lossy, planes;
     for (WdEntry* e : all) (e->lossy ? lossy : group).push_back(e);
-    const int nf = (int)group.size(), ny = (int)lossy.size();
+    const int nreal = (int)group.size();                                // those that decode into an image
+    for (WdEntry* e : lossy)
+        if (e->alpha.present) {
+            planes.push_back(e);
+            if (e->alpha.method) group.push_back(e);
+        }
+    const int nf = (int)group.size(), ny = (int)lossy.size(), na = (int)planes.size();
     run->entries.clear();
     for (const WdEntry* e : group) run->entries.push_back(e->entry);
     for (const WdEntry* e : lossy) run->entries.push_back(e->entry);
+    std::vector<WaFileDesc> afd((size_t)na);
     std::vector<VdFileDesc> vfd((size_t)ny);
     std::vector<WdFileDesc> fd((size_t)nf);
     std::vector<WdCodeItem> items;
@@ -86,7 +108,7 @@ int decode_group(const std::vector<WdEntry*>& all, impgpu_image** images, WdGrou
         d.in_size = P.in_size; d.in_cap = (uint32_t)(P.words.size() * 4u); d.ngroups = P.ngroups;
         d.w = P.w; d.h = P.h; d.cw = P.cw; d.alpha_used = P.alpha_used;
         d.cache_bits = P.cache_bits; d.meta_bits = P.meta_bits; d.meta_w = P.meta_w;
-        d.img = images[group[(size_t)f]->entry]->d;
+        d.img = f < nreal ? images[group[(size_t)f]->entry]->d : nullptr;   // a plane's scratch: placed below
         for (uint32_t g = 0; g < P.ngroups; g++)
             for (int k = 0; k < WD_CODES; k++) items.push_back(WdCodeItem{f, g, k, 0});
     }
@@ -97,6 +119,17 @@ int decode_group(const std::vector<WdEntry*>& all, impgpu_image** images, WdGrou
         d.hdr = lossy[(size_t)f]->vplan.hdr;
         d.chunk_off = (long long)L.take(lossy[(size_t)f]->vplan.chunk.size());
         d.img = images[lossy[(size_t)f]->entry]->d;
+    }
+    const size_t o_afd = L.take((size_t)na * sizeof(WaFileDesc));
+    for (int f = 0, k = nreal; f < na; f++) {
+        const WdEntry* e = planes[(size_t)f];
+        WaFileDesc& d = afd[(size_t)f];
+        std::memset(&d, 0, sizeof d);
+        d.img = images[e->entry]->d;
+        d.w = e->plan.w; d.h = e->plan.h; d.filter = e->alpha.filter; d.method = e->alpha.method;
+        d.status_frame = nf + (int)(std::find(lossy.begin(), lossy.end(), e) - lossy.begin());
+        d.status_stream = e->alpha.method ? k++ : d.status_frame;
+        if (!e->alpha.method) d.src_off = (long long)L.take((size_t)d.w * (size_t)d.h);
     }
     const size_t upload = L.size();                                     // where the upload ends
     const size_t o_status = L.take((size_t)(nf + ny) * 4u);
@@ -115,14 +148,22 @@ int decode_group(const std::vector<WdEntry*>& all, impgpu_image** images, WdGrou
         fd[(size_t)f].sorted_off = (long long)L.take((size_t)P.ngroups * wd_sorted_stride(P.cache_bits) * 2u);
         fd[(size_t)f].plane_off = (long long)L.take((size_t)P.w * (size_t)P.h * 4u);
     }
+    std::vector<size_t> o_scratch((size_t)na, 0);
+    for (int f = 0; f < na; f++)
+        if (afd[(size_t)f].method) afd[(size_t)f].src_off = (long long)(o_scratch[(size_t)f] = L.take((size_t)afd[(size_t)f].w * (size_t)afd[(size_t)f].h * 4u));
     if (int rc = dev_alloc(L.size(), &run->block.p)) return rc;
     uint8_t* m = run->block.bytes();
+    for (int f = 0; f < na; f++)
+        if (afd[(size_t)f].method) fd[(size_t)afd[(size_t)f].status_stream].img = m + o_scratch[(size_t)f];
     void *host = nullptr, *token = nullptr;
     if (int rc = stage_begin(upload, &host, &token)) return rc;
     uint8_t* hp = (uint8_t*)host;
     if (nf) std::memcpy(hp + o_fd, fd.data(), fd.size() * sizeof(WdFileDesc));
     if (!items.empty()) std::memcpy(hp + o_items, items.data(), items.size() * sizeof(WdCodeItem));
     if (ny) std::memcpy(hp + o_vfd, vfd.data(), vfd.size() * sizeof(VdFileDesc));
+    if (na) std::memcpy(hp + o_afd, afd.data(), afd.size() * sizeof(WaFileDesc));
+    for (int f = 0; f < na; f++)
+        if (!afd[(size_t)f].method) std::memcpy(hp + afd[(size_t)f].src_off, planes[(size_t)f]->alpha.data, (size_t)afd[(size_t)f].w * (size_t)afd[(size_t)f].h);
     for (int f = 0; f < ny; f++) std::memcpy(hp + vfd[(size_t)f].chunk_off, lossy[(size_t)f]->vplan.chunk.data(), lossy[(size_t)f]->vplan.chunk.size());
     for (int f = 0; f < nf; f++) {
         const WdPlan& P = group[(size_t)f]->plan;
@@ -141,6 +182,7 @@ int decode_group(const std::vector<WdEntry*>& all, impgpu_image** images, WdGrou
     run->status = (uint32_t*)(m + o_status);
     if (!rc && nf) rc = launch_webp_decode(m, (const WdFileDesc*)(m + o_fd), (const WdCodeItem*)(m + o_items), (long long)nitems, run->status, nf, s);
     if (!rc && ny) rc = launch_vp8_decode(m, (const VdFileDesc*)(m + o_vfd), run->status + nf, ny, s);
+    if (!rc && na) rc = launch_webp_alpha(m, (const WaFileDesc*)(m + o_afd), run->status, na, s);
     return rc;
 }
 
@@ -164,13 +206,14 @@ int batch_decode(const unsigned char* const* blobs, const size_t* sizes, int cou
         const uint8_t* payload = nullptr;
         uint32_t psize = 0;
         int lossy = 0;
-        if ((codes[i] = vd_route(blobs[i], sizes[i], accept, &payload, &psize, &lossy)) != IMP_OK) continue;
+        if ((codes[i] = vd_route(blobs[i], sizes[i], accept, &payload, &psize, &lossy, &e->alpha)) != IMP_OK) continue;
         if (lossy) {
             e->lossy = true;
             if ((codes[i] = vd_plan(payload, psize, &e->vplan)) != IMP_OK) continue;
             e->plan.w = e->vplan.hdr.w; e->plan.h = e->vplan.hdr.h;
-            e->upload = vd_upload_bytes(e->vplan);
-            e->device = vd_device_bytes(e->vplan);
+            if (e->alpha.present && e->alpha.method && (codes[i] = va_parse_stream(e->alpha, e->plan.w, e->plan.h, &e->plan, mem.get())) != IMP_OK) continue;
+            e->upload = vd_upload_bytes(e->vplan) + va_upload_bytes(*e);
+            e->device = vd_device_bytes(e->vplan) + va_device_bytes(*e);
         } else {
             if ((codes[i] = wd_parse(blobs[i], sizes[i], &e->plan, mem.get())) != IMP_OK) continue;
             e->upload = wd_upload_bytes(e->plan);
@@ -197,7 +240,7 @@ int batch_decode(const unsigned char* const* blobs, const size_t* sizes, int cou
             fail(group, rc);
             hard = rc;
         } else {
-            run->piece = words.add(run->status, group.size() * 4u);
+            run->piece = words.add(run->status, run->entries.size() * 4u);
         }
         runs.push_back(std::move(run));
         group.clear();
@@ -214,12 +257,14 @@ int batch_decode(const unsigned char* const* blobs, const size_t* sizes, int cou
     for (auto& run : runs) {
         if (run->piece < 0) continue;
         const uint32_t* st = (const uint32_t*)words.at(run->piece);
-        for (size_t k = 0; k < run->entries.size(); k++) {
+        for (size_t k = 0; k < run->entries.size(); k++) codes[run->entries[k]] = IMP_OK;
+        for (size_t k = 0; k < run->entries.size(); k++) {                // a file fails if any of its status words is set
             const int i = run->entries[k];
             const int code = rc ? rc : st[k] ? IMP_ERROR_DECODE_FAILED : IMP_OK;
-            codes[i] = code;
-            if (code) { image_delete(images[i]); images[i] = nullptr; }
+            if (code) codes[i] = code;
         }
+        for (int i : run->entries)
+            if (codes[i] && images[i]) { image_delete(images[i]); images[i] = nullptr; }
     }
     if (launches) *launches = (int)(t_launches - launched);
     return IMP_OK;
@@ -265,6 +310,8 @@ int impgpu_webp_info_ex(const unsigned char* blob, size_t size, int accept, int*
     if (channels) *channels = 4;
     return IMP_OK;
 }
+
+int impgpu_webp_alpha_info(const unsigned char* blob, size_t size, int info[4]) { return va_info(blob, size, info); }
 
 int impgpu_webp_decode_host_ex(const unsigned char* blob, size_t size, int accept, unsigned char* out, size_t capacity, int* width, int* height, int* info) {
     return vd_decode_host_any(blob, size, accept, out, capacity, width, height, info);

@@ -170,18 +170,16 @@ inline int wd_sub_image(const WdPlan& P, WdBits* b, int w, int h, std::vector<ui
     return WD_OK;
 }
 
-// Everything in front of the main image's pixel stream -> IMP_*
-inline int wd_parse(const uint8_t* blob, size_t size, WdPlan* P, WdMem* m) {
-    const uint8_t* payload = nullptr;
-    uint32_t n = 0;
-    if (int rc = wd_container(blob, size, &payload, &n)) return rc;
-    if (int rc = wd_header(payload, n, &P->w, &P->h, &P->alpha_used)) return rc;
+// Everything in front of the main image's pixel stream, of a stream whose first bit is bit `bitpos` of `payload` and whose
+// size P->w x P->h the caller has set: 40 behind the five header bytes of a VP8L chunk, 0 for the headerless stream of an
+// ALPH chunk (imp_vp8_dec_host.h) -> IMP_*
+inline int wd_parse_stream(const uint8_t* payload, uint32_t n, uint64_t bitpos, WdPlan* P, WdMem* m) {
     P->in_size = n;
     P->words.assign(((size_t)n + 3) / 4, 0);
-    std::memcpy(P->words.data(), payload, n);
+    if (n) std::memcpy(P->words.data(), payload, n);
     const uint64_t in_bits = (uint64_t)n * 8u;
     WdBits b;
-    wd_bits_begin(&b, P->words.data(), (int)P->words.size(), 0, 40);
+    wd_bits_begin(&b, P->words.data(), (int)P->words.size(), 0, bitpos);
     int xsize = P->w;
     unsigned seen = 0;
     while (wd_read(&b, 1)) {
@@ -230,6 +228,15 @@ inline int wd_parse(const uint8_t* blob, size_t size, WdPlan* P, WdMem* m) {
     return IMP_OK;
 }
 
+// the same of a file: the container and the five header bytes first
+inline int wd_parse(const uint8_t* blob, size_t size, WdPlan* P, WdMem* m) {
+    const uint8_t* payload = nullptr;
+    uint32_t n = 0;
+    if (int rc = wd_container(blob, size, &payload, &n)) return rc;
+    if (int rc = wd_header(payload, n, &P->w, &P->h, &P->alpha_used)) return rc;
+    return wd_parse_stream(payload, n, 40, P, m);
+}
+
 // the main image as the lanes see it; `out` holds cw * h pixels
 inline WdImage wd_main_image(const WdPlan& P, const WdCode* codes, const uint16_t* sorted, uint32_t* out) {
     WdImage im{};
@@ -270,6 +277,37 @@ inline uint32_t* wd_inverse_host(const WdPlan& P, uint32_t* a, uint32_t* b) {
     return cur;
 }
 
+// A parsed stream's coded plane: tables and the main image's rounds, the lanes one after the other, into a (w * h words;
+// cw * h are written).  info (may be null): words 0, 5, 6, 7 -- the feature word is complete behind this.
+inline int wd_coded_host(const WdPlan& P, WdMem* m, int* info, std::vector<uint32_t>* a) {
+    const size_t npix = (size_t)P.w * (size_t)P.h;
+    std::vector<WdCode> codes;
+    std::vector<uint16_t> sorted;
+    if (!wd_tables_host(P.lens.data(), P.ngroups, P.cache_bits, &codes, &sorted)) return IMP_ERROR_DECODE_FAILED;
+    a->assign(npix, 0);
+    const WdImage im = wd_main_image(P, codes.data(), sorted.data(), a->data());
+    uint64_t endbit = 0;
+    uint32_t feat = P.feat;
+    int rounds = 0, longest = 0;
+    const int status = wd_rounds_host(im, P.bitpos, m, &feat, &endbit, &rounds);
+    for (uint8_t l : P.lens) longest = std::max(longest, (int)l);
+    if (info) { info[0] = (int)feat; info[5] = status; info[6] = rounds; info[7] = longest; }
+    return status ? IMP_ERROR_DECODE_FAILED : IMP_OK;
+}
+
+// A parsed stream's pixels: the coded plane, then the inverse transforms.  a / b: w * h words each; *dst is the one that
+// holds the frame's ARGB words.
+inline int wd_pixels_host(const WdPlan& P, WdMem* m, int* info, std::vector<uint32_t>* a, std::vector<uint32_t>* b, const uint32_t** dst) {
+    const size_t npix = (size_t)P.w * (size_t)P.h;
+    if (int rc = wd_coded_host(P, m, info, a)) return rc;
+    b->assign(npix, 0);
+    uint32_t* cur = wd_inverse_host(P, a->data(), b->data());
+    uint32_t* out = cur == a->data() ? b->data() : a->data();
+    for (int j = 0; j < WD_LANES; j++) wd_finish(cur, out, (uint32_t)npix, P.alpha_used, (uint32_t)j, (uint32_t)WD_LANES);
+    *dst = out;
+    return IMP_OK;
+}
+
 // impgpu_webp_decode_host
 inline int wd_decode_host(const uint8_t* blob, size_t size, uint8_t* out, size_t capacity, int* width, int* height, int* info) {
     if (info) std::memset(info, 0, sizeof(int) * IMPGPU_WEBP_DEC_INFO_WORDS);
@@ -283,21 +321,9 @@ inline int wd_decode_host(const uint8_t* blob, size_t size, uint8_t* out, size_t
     if (info) { info[0] = (int)P.feat; info[1] = (int)P.ngroups; info[2] = P.cache_bits; info[3] = P.ntrans; info[4] = P.cw; }
     const size_t npix = (size_t)P.w * (size_t)P.h;
     if (!out || capacity < npix * 4u) return IMP_ERROR_MALLOC_FAILED;
-    std::vector<WdCode> codes;
-    std::vector<uint16_t> sorted;
-    if (!wd_tables_host(P.lens.data(), P.ngroups, P.cache_bits, &codes, &sorted)) return IMP_ERROR_DECODE_FAILED;
-    std::vector<uint32_t> a(npix), b(npix);
-    const WdImage im = wd_main_image(P, codes.data(), sorted.data(), a.data());
-    uint64_t endbit = 0;
-    uint32_t feat = P.feat;
-    int rounds = 0, longest = 0;
-    const int status = wd_rounds_host(im, P.bitpos, m.get(), &feat, &endbit, &rounds);
-    for (uint8_t l : P.lens) longest = std::max(longest, (int)l);
-    if (info) { info[0] = (int)feat; info[5] = status; info[6] = rounds; info[7] = longest; }
-    if (status) return IMP_ERROR_DECODE_FAILED;
-    uint32_t* cur = wd_inverse_host(P, a.data(), b.data());
-    uint32_t* dst = cur == a.data() ? b.data() : a.data();
-    for (int j = 0; j < WD_LANES; j++) wd_finish(cur, dst, (uint32_t)npix, P.alpha_used, (uint32_t)j, (uint32_t)WD_LANES);
+    std::vector<uint32_t> a, b;
+    const uint32_t* dst = nullptr;
+    if (int rc2 = wd_pixels_host(P, m.get(), info, &a, &b, &dst)) return rc2;
     std::memcpy(out, dst, npix * 4u);
     return IMP_OK;
 }

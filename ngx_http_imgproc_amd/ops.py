@@ -1166,11 +1166,22 @@ def request_webp_quality(uri, extension="", config=None):
 
 WEBP_ACCEPT_LOSSY = 1                         # IMPGPU_WEBP_ACCEPT_LOSSY
 WEBP_DEC_LOSSY_LAUNCHES = 3                   # IMPGPU_WEBP_DEC_LOSSY_LAUNCHES
+WEBP_ACCEPT_ALPHA = 2                         # IMPGPU_WEBP_ACCEPT_ALPHA: with WEBP_ACCEPT_LOSSY, VP8X + ALPH + `VP8 ` files too
+WEBP_DEC_ALPHA_LAUNCHES = 1                   # IMPGPU_WEBP_DEC_ALPHA_LAUNCHES
+
+
+def webp_alpha_info(blob):
+    """impgpu_webp_alpha_info -> (code, [method, filter, pre-processing, the VP8L stream's feature word]); host only.
+    IMP_ERROR_UNSUPPORTED: no alpha plane that WEBP_ACCEPT_LOSSY | WEBP_ACCEPT_ALPHA would take."""
+    b = bytes(blob)
+    info = (C.c_int * 4)()
+    rc = lib.impgpu_webp_alpha_info(b, len(b), info)
+    return rc, list(info)
 
 
 def webp_info(blob, accept=None):
     """impgpu_webp_info -> (code, width, height, channels); host only.  accept: None = the call itself; a mask =
-    impgpu_webp_info_ex (WEBP_ACCEPT_LOSSY: a VP8 key frame's size too)."""
+    impgpu_webp_info_ex (WEBP_ACCEPT_LOSSY: a VP8 key frame's size too; | WEBP_ACCEPT_ALPHA: one with an ALPH chunk)."""
     b = bytes(blob)
     w, h, c = C.c_int(0), C.c_int(0), C.c_int(0)
     if accept is not None:
@@ -1183,7 +1194,8 @@ def webp_info(blob, accept=None):
 def webp_decode_host(blob, capacity=None, guard=64, accept=None):
     """impgpu_webp_decode_host (no device): a lossless WebP file -> (code, HxWx4 B,G,R,A array or None, info, intact).
     capacity defaults to what impgpu_webp_info says the frame takes; `intact`: the guard band behind it was not written.
-    accept: None = the call itself; a mask = impgpu_webp_decode_host_ex (WEBP_ACCEPT_LOSSY: lossy files too)."""
+    accept: None = the call itself; a mask = impgpu_webp_decode_host_ex (WEBP_ACCEPT_LOSSY: lossy files too; | WEBP_ACCEPT_ALPHA: their
+    alpha planes)."""
     b = bytes(blob)
     rc, w, h, _ = webp_info(b, accept)
     cap = (w * h * 4 if rc == 0 else 0) if capacity is None else int(capacity)
